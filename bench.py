@@ -20,6 +20,13 @@ Prints ONE JSON line on rank 0.  `value` counts every ray handed to traversal
 (primary + secondary radiance + shadow); the reference's own figure,
 width*height*fps/1e6 primary rays only (src/utils/DXSample.cpp:114), is reported
 beside it as `primary_mrays_per_s`.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything
+else -- the live counter passes and the rooflines, the per-stage table, the same
+frames frame by frame and once more, the fixed-total pass, the 10 M-triangle
+workload, the CPU baseline, the warm BVH rebuild -- runs only with --full.
+--dump-outputs DIR writes the accumulated image of the timed steps (what a caller of
+rt_pipeline_render reads back after the last step) to DIR/output.npy, float32.
 """
 import argparse
 import json
@@ -68,6 +75,20 @@ STAGE_IO_BYTES = {"primary": 0 + 20, "secondary": 32 + 20, "shadow": 32 + 4}
 TRACE_STAGES = {"primary": (("ms_primary",), "k_primary", ("primary",)),
                 "secondary": (("ms_trace_secondary",), "k_trace_secondary", ("secondary",)),
                 "shadow": (("ms_trace_shadow0", "ms_trace_shadow1"), "k_trace_shadow", ("shadow0", "shadow1"))}
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: the accumulated image the timed steps left (H, W, 4) as DIR/output.npy, float32.  An image above
+    DUMP_MAX_BYTES is written as a fixed sample of its pixels (seed 0, in pixel order): (n, 4), the same pixels every run."""
+    import numpy as np
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes + 4096 > DUMP_MAX_BYTES:                 # (room for the .npy header)
+        px = image.reshape(-1, image.shape[-1])
+        n = (DUMP_MAX_BYTES - 4096) // px[0].nbytes
+        image = px[np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "output.npy"), image)
 
 
 def parse(argv=None):
@@ -106,6 +127,13 @@ def parse(argv=None):
     ap.add_argument("--partition", choices=("samples", "tiles"), default="samples",
                     help="samples (default, the headline): frames sharded over the GPUs, one all-reduce.  tiles: BASELINE configs[4], the "
                          "10 M-triangle 4K 4-bounce frame split into interleaved 16-row bands over the GPUs, one all-gather of the bands")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: live rocprofv3 counter passes and the rooflines, the per-stage table, "
+                         "frame_by_frame, repeat_of_timed_steps, the fixed-total pass (strong_scaling), the 10 M-triangle workload (roofline_hbm), "
+                         "the CPU baseline and the warm BVH rebuild.  The --no-* and --cpu-seconds / --hbm-frames options tune these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed -- the accumulated output image, float32 (H, W, 4) -- to DIR/output.npy "
+                         "(above %d MB: a fixed, seeded sample of its pixels, (n, 4))" % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args(argv)
     args.batch_given = any(a == "--batch" or a.startswith("--batch=") for a in (sys.argv[1:] if argv is None else argv))
     return args
@@ -243,7 +271,7 @@ def live_traffic(workload, width, height, budget_s=110.0, passes=("ea", "write",
     if not os.path.exists(exe):
         return {}
     here = os.path.dirname(os.path.abspath(__file__))
-    child = [os.path.join(here, "bench.py"), "--cpu-seconds", "0", "--no-roofline", "--no-live-pmc", "--no-frame-by-frame"]
+    child = [os.path.join(here, "bench.py"), "--full", "--cpu-seconds", "0", "--no-roofline", "--no-live-pmc", "--no-frame-by-frame"]
     child += (["--steps", str(8 if per_set == 1 else 4 * per_set), "--warmup", str(2 if per_set == 1 else per_set), "--batch", str(per_set),
                "--hbm-frames", "0", "--width", str(width), "--height", str(height)] if workload == "c2"
               else ["--workload", "c5", "--hbm-frames", "2"] if per_set == 1 else ["--workload", "c5", "--hbm-frames", str(per_set), "--batch", str(per_set)])
@@ -634,6 +662,8 @@ def tiles_main(args, rank, world, local_rank, dev, capi, D, T, scenes, torch, di
         dist.barrier()
     elapsed = time.perf_counter() - t0
     report = rank_report(torch, dist, ctx, rank, world, local_rank, dev, os.environ.get("DXR_BENCH_BACKEND", "nccl"), mine_elapsed, ev[0].elapsed_time(ev[1]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, acc.cpu().numpy())
     tot = pipe.totals()
     red = torch.tensor([elapsed, float(tot["rays_primary"] + tot["rays_secondary"] + tot["rays_shadow"] - tot["rays_shadow_skipped"]),
                         float(tot["rays_primary"])], dtype=torch.float64, device=dev)
@@ -677,7 +707,7 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     # memory-side traffic for the two rooflines, measured by child runs under rocprofv3 BEFORE this process touches the GPU
     live = {}
-    if world == 1 and not args.no_roofline and not args.no_live_pmc and args.partition == "samples" and args.workload == "c2":
+    if args.full and world == 1 and not args.no_roofline and not args.no_live_pmc and args.partition == "samples" and args.workload == "c2":
         t_live = time.perf_counter()
         n_sets_ = (args.steps + max(1, min(args.batch, 32)) - 1) // max(1, min(args.batch, 32))
         live["c2"] = live_traffic("c2", args.width, args.height, budget_s=100.0, per_set=(args.steps + n_sets_ - 1) // n_sets_)
@@ -705,6 +735,7 @@ def main():
 
     if args.workload == "c5":            # profiling passes: only the HBM-bound workload, one JSON line of its own
         assert world == 1, "--workload c5 is a single-GPU profiling mode"
+        assert not args.dump_outputs, "--dump-outputs writes the headline path's image, not --workload c5's"
         ctx = capi.Context(local_rank, stream=torch.cuda.current_stream().cuda_stream)
         h = hbm_workload(ctx, capi, T, scenes, max(args.hbm_frames, 1), 2, batch=args.batch if args.batch_given else 1, one_frame_walk=not args.no_roofline)
         print(json.dumps({"metric": "Mrays/s, 10 M triangles 4K 4-bounce (roofline workload)", "value": h["Mrays_per_s"], "unit": "Mrays/s",
@@ -728,11 +759,13 @@ def main():
     pipe.bind_output(acc.data_ptr(), W, H)
     pipe.build_acceleration_structures()
     build_ms = scene.build_ms()              # first build of the process: includes loading the build kernels
-    scene2 = capi.Scene(ctx)                 # the same build again, warm: the steady-state figure
-    scene2.add_model(capi.Model(ctx, verts, tris))
-    scene2.build()
-    rebuild_ms = scene2.build_ms()
-    del scene2
+    rebuild_ms = None
+    if args.full:
+        scene2 = capi.Scene(ctx)             # the same build again, warm: the steady-state figure
+        scene2.add_model(capi.Model(ctx, verts, tris))
+        scene2.build()
+        rebuild_ms = scene2.build_ms()
+        del scene2
 
     # every rank generates the SAME global frame sequence and renders its share of it
     host = capi.ProgressiveHost(1234)
@@ -856,8 +889,8 @@ def main():
     ev[0].record(); ev[1].record(); span[0].record(); span[1].record()
     torch.cuda.synchronize()
     ev[0].elapsed_time(ev[1]); span[0].elapsed_time(span[1])
-    if not args.no_roofline:
-        pipe.enable_timing(K)
+    if args.full and not args.no_roofline:
+        pipe.enable_timing(K)               # (HIP events around every stage kernel: the stage table of the roofline)
     pipe.reset_totals()
 
     if world > 1:
@@ -881,6 +914,8 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     report = rank_report(torch, dist, ctx, rank, world, local_rank, dev, backend, mine_elapsed, ev[0].elapsed_time(ev[1]))
+    if args.dump_outputs and rank == 0:      # (before anything below renders into the same buffer again)
+        dump_outputs(args.dump_outputs, (mean if world > 1 else acc).cpu().numpy())
 
     tot = pipe.totals()
     # `value` counts rays that were actually TRAVERSED: every ray the reference's shaders trace.  (rt_pipeline_set_skip_unlit_shadow_rays,
@@ -926,13 +961,15 @@ def main():
             # every ray the reference's shaders trace for these frames (the unlit shadow rays included) per second of this run
             "reference_ray_budget_mrays_per_s": (rays_all + skipped_all) / elapsed / 1e6,
             "shadow_rays_not_traversed_per_frame": skipped_all / (K * world),
-            "bvh_build_ms": build_ms, "bvh_rebuild_ms": rebuild_ms,
+            "bvh_build_ms": build_ms,
             # the host's side of the timed region: time inside the K update() + render() calls (deferred mode: the last one enqueues the
             # set), the slowest single call, the explicit flush, then the wait for the device.  Kernel time is in `stages`.
             "timed_region_host_ms": timed_host_ms,
             "ranks": report,
         }
-        if not args.no_roofline:
+        if args.full:
+            out["bvh_rebuild_ms"] = rebuild_ms
+        if args.full and not args.no_roofline:
             if S > 1:
                 pipe.set_deferred(0)
                 step(Wu + K - 1)        # (the walk counters below are those of ONE frame: the last one again, by itself, after the timed region)
@@ -941,7 +978,7 @@ def main():
             n_nodes, n_recs = scene.wide_counts(0)        # the one instance's BLAS: the traversal arrays of the headline scene
             out["roofline"] = headline_roofline(args, stages, dom, n_t, n_sets, S, live, W, H, out["ms_per_step"], n_nodes * NODE_LINE_BYTES + n_recs * TRIREC_BYTES)
             out["stages"] = stages
-        if world == 1 and not args.no_sample_batches and S > 1:
+        if args.full and world == 1 and not args.no_sample_batches and S > 1:
             # the same K frames again, one update() + render() per frame as the reference's app loop issues them
             # (DXRExperimentsApp::OnUpdate / OnRender): the same image bit for bit, every persistent traversal launch and its tail
             # paid per frame instead of per set
@@ -965,7 +1002,7 @@ def main():
                                      "note": "the same update() + render() calls with deferred mode off (rt_pipeline_set_deferred(0)): every frame is rendered "
                                              "by its own set of launches before render() returns -- what an application that presents every frame gets; "
                                              "same frames, same bits; `value` above renders them %d per set of launches" % S}
-        if world == 1 and not args.no_sample_batches:
+        if args.full and world == 1 and not args.no_sample_batches:
             # the timed steps ONCE MORE, now that the process has rendered for a while: how much of `value` is the state the chip and
             # the shadow cache are in when the K steps start right after W = 5 warm-up frames (say the spread in the line)
             pipe.clear_output()
@@ -983,9 +1020,10 @@ def main():
                                                     "`value` is the FIRST pass; measured over rounds 3 - 4 it reads 3 - 7 % below this one (chip power state "
                                                     "after the idle set-up phase, a shadow cache still filling: profiles/r04/warmup_sensitivity.txt, preroll.txt) "
                                                     "and varies +-1.5 % from box to box"}
-    # the fixed-total form of configs[2] (every rank: it ends in a collective); at N = 1 after the extras above, which replay the timed frames
+    # the fixed-total form of configs[2] (every rank: it ends in a collective); at N = 1 after the extras above, which replay the timed frames.
+    # --full, or --total-frames, which makes it the line itself
     strong = None
-    if not args.no_strong:
+    if not args.no_strong and (args.full or args.total_frames):
         strong = fixed_total(args.total_frames if args.total_frames else 256)
     if rank == 0:
         if strong is not None:
@@ -1000,7 +1038,7 @@ def main():
                 out["strong_scaling"] = {k: v for k, v in strong.items() if k not in ("metric", "value", "unit", "steps", "ms_per_step", "scaling", "frames_per_s")}
             else:
                 out["strong_scaling"] = strong
-        if world == 1 and args.hbm_frames > 0 and not args.no_roofline:
+        if args.full and world == 1 and args.hbm_frames > 0 and not args.no_roofline:
             del pipe, scene, model
             hb = HBM_SET if S > 1 else 1                       # like the headline: sets of frames
             h = hbm_workload(ctx, capi, T, scenes, args.hbm_frames, 2, batch=hb)
@@ -1034,7 +1072,7 @@ def main():
                                                             "SQ_INSTS_VALU") if k in k5},
                              "pmc_source": prof5.get("source"), "pmc_commit": prof5.get("commit")}
             out["roofline_hbm"] = h
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(verts, tris, mat, env, pfcs[mine[Wu]], W, H, args.cpu_seconds)
     if world > 1:
         dist.barrier()

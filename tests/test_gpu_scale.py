@@ -190,7 +190,7 @@ def test_bench_two_ranks_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DXR_BENCH_BACKEND="gloo", DXR_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29871", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+           "--master-port", "29871", os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--width", "480", "--height", "270", "--cpu-seconds", "0"]
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -210,7 +210,7 @@ def test_bench_two_ranks_on_one_gpu():
     assert sg["scaling"] == "strong" and sg["n_gpus"] == 2 and sg["total_frames"] == 256 and sg["frames_per_rank_max"] == 128
     assert sg["frames_per_launch_set"] == 32 and sg["launch_sets_per_rank"] == 4 and sg["value"] > 0 and sg["collective_ms_max"] > 0
     assert sg["collective_bytes"] == 480 * 270 * 16
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--width", "480", "--height", "270",
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--width", "480", "--height", "270",
                           "--cpu-seconds", "0", "--no-live-pmc", "--hbm-frames", "0"], cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-3000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
@@ -242,7 +242,7 @@ def test_bench_two_ranks_on_one_gpu():
     s1 = d1["strong_scaling"]
     assert s1["scaling"] == "strong" and s1["n_gpus"] == 1 and s1["total_frames"] == 256 and s1["collective_bytes"] == 0
     # the fixed-total form as the line itself: --total-frames T
-    st = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--width", "480", "--height", "270", "--total-frames", "48",
+    st = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--width", "480", "--height", "270", "--total-frames", "48",
                          "--cpu-seconds", "0", "--no-live-pmc", "--hbm-frames", "0", "--no-roofline", "--no-frame-by-frame"], cwd=root, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, text=True, timeout=600)
     assert st.returncode == 0, st.stderr[-3000:]
@@ -263,3 +263,32 @@ def test_tile_partition_two_ranks_on_one_gpu():
            "--master-port", "29873", os.path.join(root, "tests", "scripts", "tile_ranks.py")]
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert r.returncode == 0 and "tiles ok: 2 ranks" in r.stdout, r.stdout[-3000:]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run prints the headline line and nothing of what --full adds; --dump-outputs DIR writes the image the
+    timed steps accumulated, float32 (H, W, 4), and two runs with the same arguments write the same bits."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, images = [], []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--width", "480",
+                            "--height", "270", "--dump-outputs", str(tmp_path / run)], cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        assert sorted(os.listdir(tmp_path / run)) == ["output.npy"]
+        images.append(np.load(tmp_path / run / "output.npy"))
+    d = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mrays/s" and d["higher_is_better"] is True
+    assert d["config"]["frames_per_launch_set"] == 5 and d["config"]["launch_sets"] == 1
+    for key in ("roofline", "stages", "frame_by_frame", "repeat_of_timed_steps", "strong_scaling", "roofline_hbm", "cpu_baseline", "bvh_rebuild_ms"):
+        assert key not in d, key
+    img = images[0]
+    assert img.dtype == np.float32 and img.shape == (270, 480, 4) and np.isfinite(img).all() and img[..., :3].max() > 0
+    assert np.array_equal(img.view(np.uint32), images[1].view(np.uint32))

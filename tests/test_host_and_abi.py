@@ -412,3 +412,27 @@ def test_bench_frame_sets():
     assert split(20, 32) == (1, 20) and split(60, 32) == (2, 30) and split(20, 16) == (2, 10) and split(5, 32) == (1, 5) and split(20, 1) == (20, 1) and split(128, 99) == (4, 32)
     # ... and that is the expression bench.py uses
     assert "n_sets = (K + max(1, min(args.batch, 32)) - 1) // max(1, min(args.batch, 32))" in src and "S = (K + n_sets - 1) // n_sets" in src
+
+
+def test_bench_options_and_output_dump(tmp_path):
+    """bench.py --full is off by default; --dump-outputs DIR writes the accumulated image as DIR/output.npy, float32 -- whole up to
+    64 MB, above that a fixed sample of its pixels that stays within 64 MB and is the same for every run"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    img = np.random.default_rng(5).random((1080, 1920, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "small"), img)
+    got = np.load(tmp_path / "small" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    big = np.random.default_rng(6).random((2160, 3840, 4)).astype(np.float32)      # 133 MB
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    s1, s2 = np.load(tmp_path / "big1" / "output.npy"), np.load(tmp_path / "big2" / "output.npy")
+    assert os.path.getsize(tmp_path / "big1" / "output.npy") <= 64 << 20
+    assert s1.dtype == np.float32 and s1.shape[1] == 4 and s1.shape[0] > 3_000_000 and np.array_equal(s1, s2)
+    assert np.isin(s1[:1000, 0], big[..., 0]).all()

@@ -8,8 +8,9 @@ The reference ships no tests, but it does hold the files its default scene is ma
                                           (DenoiseCompositor::loadResources, src/DenoiseCompositor.cpp:52-68)
 tests/golden/reference_assets.json holds what an INDEPENDENT reading of those files gives (readers written in
 tests/golden/make_fixtures.py, sharing no code with the product or the oracle).  Here the product's device-free
-readers (rt_dds_read_cube, rt_obj_read) and the oracle's are run on the real files when the checkout is present
-(the build container) and, always, on the committed re-emitted meshes."""
+readers (rt_dds_read_cube, rt_obj_read) and the oracle's are run on the reference's own files, as
+tests/golden/make_reference_copies.py stored them under tests/golden/reference_assets (util.reference_asset), and on
+the committed re-emitted meshes."""
 import hashlib
 import json
 import os
@@ -17,10 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from util import GOLDEN
-
-REF = "/root/reference/assets"
-have_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is not on this machine")
+from util import GOLDEN, reference_asset
 
 
 def sha(a):
@@ -37,27 +35,27 @@ def flat(v):
     return np.concatenate([v["position"], v["normal"]], 1)
 
 
-@have_ref
-def test_product_dds_reader_on_the_reference_environment_map(capi, pins):
+def test_product_dds_reader_on_the_reference_environment_map(capi, pins, tmp_path):
     p = pins["CathedralRadiance.dds"]
-    faces = capi.dds_read_cube(REF + "/textures/CathedralRadiance.dds")
+    path = reference_asset("CathedralRadiance.dds", tmp_path)
+    assert os.path.getsize(path) == p["bytes"]
+    faces = capi.dds_read_cube(path)
     assert faces.shape == (6, p["width"], p["width"], 4) and p["mips"] == 7 and p["dxgi_format"] == 10
     assert sha(faces) == p["mip0_fp32_sha256"]
     for f, y, x, *rgba in p["probes"]:
         assert np.array_equal(faces[f, y, x], np.array(rgba, np.float32))
     # a second reference-held cube map (128^2, one mip) goes through the same reader
-    irr = capi.dds_read_cube(REF + "/textures/CathedralIrradiance.dds")
+    irr = capi.dds_read_cube(reference_asset("CathedralIrradiance.dds", tmp_path))
     assert irr.shape == (6, 128, 128, 4) and np.isfinite(irr).all() and irr[..., 3].min() == 1.0
 
 
-@have_ref
-def test_cube_adjacency_against_the_reference_map(capi, oracle, pins):
+def test_cube_adjacency_against_the_reference_map(capi, oracle, pins, tmp_path):
     """CathedralRadiance.dds was exported with edge fix-up: every edge row equals the neighbouring face's (checked
     geometrically by make_fixtures.py: edge_fixup_max_abs_diff = 0).  On such a map seamless filtering -- taps taken
     from the face across the edge through the oracle's adjacency table -- must equal face-clamped filtering for every
     direction whose footprint hangs over ONE edge; a wrong table entry would show up as a difference."""
     assert pins["CathedralRadiance.dds"]["edge_fixup_max_abs_diff"] == 0.0
-    faces = capi.dds_read_cube(REF + "/textures/CathedralRadiance.dds")
+    faces = capi.dds_read_cube(reference_asset("CathedralRadiance.dds", tmp_path))
     n = faces.shape[1]
     r = np.random.default_rng(3)
     dirs = []
@@ -90,12 +88,11 @@ def test_cube_adjacency_against_the_reference_map(capi, oracle, pins):
     assert np.abs(a - b).max() > 1e-4
 
 
-@have_ref
 @pytest.mark.parametrize("name", ["susanne.obj", "cornell.obj"])
-def test_obj_readers_on_the_reference_meshes(capi, oracle, pins, name):
+def test_obj_readers_on_the_reference_meshes(capi, oracle, pins, name, tmp_path):
     p = pins[name]
     for reader in (capi.obj_read, oracle.obj_load):
-        v, t = reader(REF + "/models/" + name)
+        v, t = reader(reference_asset(name, tmp_path))
         assert (v.shape[0], t.shape[0]) == (p["n_verts"], p["n_tris"])
         assert sha(flat(v)) == p["verts_sha256"] and sha(t) == p["indices_sha256"]
 
@@ -177,10 +174,9 @@ def test_oracle_environment_on_the_cathedral_fixture(oracle):
         assert np.array_equal(img, g[key])
 
 
-@have_ref
-def test_oracle_environment_on_the_full_size_map(capi, oracle):
+def test_oracle_environment_on_the_full_size_map(capi, oracle, tmp_path):
     g = np.load(os.path.join(GOLDEN, "cathedral32.npz"))
-    faces = capi.dds_read_cube(REF + "/textures/CathedralRadiance.dds")
+    faces = capi.dds_read_cube(reference_asset("CathedralRadiance.dds", tmp_path))
     for mode, key in ((True, "env_seamless"), (False, "env_clamp")):
         oracle.set_cube_seamless(mode)
         got = oracle.sample_cube(faces, g["dirs"])
@@ -260,15 +256,14 @@ def test_fbx_reader_refuses_what_it_does_not_understand(capi, tmp_path):
         capi.fbx_read(str(cut))
 
 
-@have_ref
-def test_product_fbx_reader_on_the_reference_model(capi, pins):
+def test_product_fbx_reader_on_the_reference_model(capi, pins, tmp_path):
     p = pins["ground.fbx"]
-    v, i = capi.fbx_read(REF + "/models/ground.fbx")
+    v, i = capi.fbx_read(reference_asset("ground.fbx", tmp_path))
     assert v.shape[0] == p["vertices"] and i.shape[0] == p["triangles"]
     assert sha(flat(v)) == p["verts_sha256"] and sha(i) == p["indices_sha256"]
     assert np.array_equal(np.concatenate([v["position"].min(axis=0), v["position"].max(axis=0)]), np.array(p["bounds"], np.float32))
     import fbx_tools as F
-    iv, ii = F.ingest(REF + "/models/ground.fbx")           # the independent parser again, live
+    iv, ii = F.ingest(reference_asset("ground.fbx", tmp_path))          # the independent parser again, live
     assert sha(iv) == p["verts_sha256"] and sha(ii) == p["indices_sha256"]
 
 

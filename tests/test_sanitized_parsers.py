@@ -3,11 +3,11 @@
 rt_obj.cpp, rt_fbx.cpp (zlib, 32- / 64-bit records), rt_dds.cpp, rt_image.cpp and rt_host.cpp parse untrusted files and hostile arguments
 inside the product library; they need no device, so THE SAME SOURCES are compiled here with `g++ -fsanitize=address,undefined
 -fno-sanitize-recover=undefined` into tests/cpp/fuzz_parsers.cpp and driven with a 10^5-case mutation fuzz seeded from the reference's
-own assets -- susanne.obj / cornell.obj (committed re-emissions), ground.fbx (committed re-emission + the reference's file when it is
-there), CathedralRadiance.dds (a 32^2 down-sample written here as DDS in both header forms + the reference's 4 MB file when it is
-there) -- and from FBX files the tests' writer synthesises in every container variant.  Zero sanitizer reports, every accepted
+own assets -- susanne.obj / cornell.obj (committed re-emissions + the reference's own susanne.obj), ground.fbx (committed re-emission +
+the reference's file), CathedralRadiance.dds (a 32^2 down-sample written here as DDS in both header forms + the reference's 4 MB map
+rebuilt from tests/golden/reference_assets) -- and from FBX files the tests' writer synthesises in every container variant.  Zero sanitizer reports, every accepted
 mesh self-consistent, every short buffer refused.  (GPU AddressSanitizer is not available on this pool; this is the CPU build.)
-Import behaviour kept: /root/reference/libs/DXRFramework/RtModel.cpp:24-82; DDS call site src/ProgressiveRaytracingPipeline.cpp:114-118."""
+Import behaviour kept: libs/DXRFramework/RtModel.cpp:24-82; DDS call site src/ProgressiveRaytracingPipeline.cpp:114-118."""
 import os
 import struct
 import subprocess
@@ -24,7 +24,6 @@ OUT = os.path.join(ROOT, "build_san")
 SOURCES = ["rt_obj.cpp", "rt_fbx.cpp", "rt_dds.cpp", "rt_image.cpp", "rt_host.cpp"]
 FLAGS = ["-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
          "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include")]
-REF = "/root/reference/assets"
 
 
 def _newer(target, deps):
@@ -93,8 +92,10 @@ def _seeds(tmp):
         p = os.path.join(tmp, "cube%d.dds" % k)
         write_dds(p, faces[:, ::2, ::2] if not half else faces, half, dx10, mips)
         seeds.append(("dds", p, 8000))
-    if os.path.exists(REF):          # this container: the reference's own files as well (the big DDS: few cases, it is 4 MB per write)
-        seeds += [("fbx", REF + "/models/ground.fbx", 4000), ("obj", REF + "/models/susanne.obj", 300), ("dds", REF + "/textures/CathedralRadiance.dds", 150)]
+    # the reference's own files as well (the big DDS: few cases, it is 4 MB per write)
+    from util import reference_asset
+    seeds += [("fbx", reference_asset("ground.fbx", tmp), 4000), ("obj", reference_asset("susanne.obj", tmp), 300),
+              ("dds", reference_asset("CathedralRadiance.dds", tmp), 150)]
     seeds.append(("host", "-", 12000))
     return seeds
 

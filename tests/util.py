@@ -159,3 +159,39 @@ def nodes_equal(a, b):
 
 def cam_array(cam, aspect):
     return np.array([*cam["eye"], *cam["at"], *cam["up"], cam["fov"], aspect], np.float32)
+
+
+REFERENCE_ASSETS = os.path.join(GOLDEN, "reference_assets")
+
+
+def reference_asset(name, directory):
+    """The reference checkout's asset file `name` as tests/golden/make_reference_copies.py stored it: the committed copy of a mesh
+    (cornell.obj, susanne.obj, ground.fbx), or a cube map written out into `directory` -- CathedralIrradiance.dds byte for byte;
+    CathedralRadiance.dds with its own header and level 0 (what the readers return) and levels 1 - 6, which the readers skip,
+    made again by a 2x2 box filter (the file's layout and size are the original's)."""
+    import lzma
+    if not name.endswith(".dds"):
+        return os.path.join(REFERENCE_ASSETS, name)
+    path = os.path.join(str(directory), name)
+    if name == "CathedralIrradiance.dds":
+        with open(os.path.join(REFERENCE_ASSETS, name + ".xz"), "rb") as f:
+            data = lzma.decompress(f.read())
+    else:
+        with open(os.path.join(REFERENCE_ASSETS, "CathedralRadiance.mip0.xz"), "rb") as f:
+            raw = lzma.decompress(f.read())
+        header, body = raw[:148], np.frombuffer(raw, np.uint8, offset=148)
+        size, mips = int(np.frombuffer(header, np.uint32, 1, 12)[0]), int(np.frombuffer(header, np.uint32, 1, 28)[0])
+        delta = np.stack([body[:body.size // 2], body[body.size // 2:]], 1).copy().view(np.uint16).reshape(3, 6, size, size)
+        planes = np.cumsum(delta, axis=-1, dtype=np.uint16)                       # (wraps mod 2^16 as the deltas did)
+        level = np.full((6, size, size, 4), 0x3C00, np.uint16)
+        level[..., :3] = np.moveaxis(planes, 0, 3)
+        faces = [[level[f]] for f in range(6)]
+        lv = level.view(np.float16).astype(np.float32)
+        for m in range(1, mips):
+            lv = 0.25 * (lv[:, 0::2, 0::2] + lv[:, 1::2, 0::2] + lv[:, 0::2, 1::2] + lv[:, 1::2, 1::2])
+            for f in range(6):
+                faces[f].append(lv[f].astype(np.float16).view(np.uint16))
+        data = header + b"".join(m.tobytes() for face in faces for m in face)
+    with open(path, "wb") as f:
+        f.write(data)
+    return path

@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 4: the run-time and compile-time knobs of the traversal kernels re-measured on the new kernels (bench scene in sets, 10 M triangles in sets of 16)
-run() { python bench.py --steps 60 --warmup 30 --cpu-seconds 0 --no-live-pmc --hbm-frames ${HBM:-0} --no-frame-by-frame 2>/dev/null | python -c "
+run() { python bench.py --full --steps 60 --warmup 30 --cpu-seconds 0 --no-live-pmc --hbm-frames ${HBM:-0} --no-frame-by-frame 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); h=d.get('roofline_hbm')
 print('$1', round(d['ms_per_step'],4), {k:round(v['avg_ms'],4) for k,v in d['stages'].items() if isinstance(v,dict)}, ('| c5 %.3f' % h['ms_per_frame']) if h else '')"; }

@@ -6,7 +6,7 @@ R=$PWD
 n=0
 mkdir -p gpurun_out
 : > gpurun_out/pmc_${TAG}.md
-ARGS=${BENCH_ARGS:---steps 40 --warmup 20}
+ARGS="--full ${BENCH_ARGS:---steps 40 --warmup 20}"
 for C in "$@"; do
   n=$((n+1))
   ( cd /tmp && export TMPDIR=/tmp && timeout 240 rocprofv3 --kernel-trace --pmc $C -d $R/gpurun_out/pmc_${TAG}_$n -o pmc --output-format csv -- python3 $R/bench.py $ARGS --cpu-seconds 0 --no-roofline --no-frame-by-frame --hbm-frames 0 --no-live-pmc > $R/gpurun_out/pmc_${TAG}_$n.log 2>&1 )

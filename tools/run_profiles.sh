@@ -15,11 +15,11 @@ for w in $WL; do
   PROG=$R/bench.py
   if [ $w = c2h ]; then ARGS="--cpu-seconds 0 --no-live-pmc";
   elif [ $w = c2d ]; then ARGS="--gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-live-pmc";       # the driver's form of the command
-  elif [ $w = c2 ]; then ARGS="--steps 8 --warmup 2 --batch 1 --cpu-seconds 0 --hbm-frames 0 --no-live-pmc";
-  elif [ $w = c2b ]; then ARGS="--steps 60 --warmup 30 --cpu-seconds 0 --hbm-frames 0 --no-live-pmc --no-frame-by-frame --no-roofline";       # the headline launches only: sets of 30 frames
+  elif [ $w = c2 ]; then ARGS="--full --steps 8 --warmup 2 --batch 1 --cpu-seconds 0 --hbm-frames 0 --no-live-pmc";
+  elif [ $w = c2b ]; then ARGS="--full --steps 60 --warmup 30 --cpu-seconds 0 --hbm-frames 0 --no-live-pmc --no-frame-by-frame --no-roofline";       # the headline launches only: sets of 30 frames
   elif [ $w = c5 ]; then ARGS="--workload c5 --hbm-frames 4 --no-live-pmc";
   elif [ $w = c5b ]; then ARGS="--workload c5 --hbm-frames 16 --batch 16 --no-live-pmc --no-roofline";
-  elif [ $w = c2s ]; then ARGS="--steps 20 --warmup 20 --batch 20 --cpu-seconds 0 --hbm-frames 0 --no-live-pmc --no-frame-by-frame --no-roofline";      # sets of 20: what the driver's --steps 20 renders
+  elif [ $w = c2s ]; then ARGS="--full --steps 20 --warmup 20 --batch 20 --cpu-seconds 0 --hbm-frames 0 --no-live-pmc --no-frame-by-frame --no-roofline";      # sets of 20: what the driver's --steps 20 renders
   else PROG=$R/tools/profile_c4.py; ARGS="4"; fi
   run() {   # name, rocprof options...
     n=$1; shift

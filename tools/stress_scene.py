@@ -16,7 +16,7 @@ def run(scene, cache):
     env = dict(os.environ)
     if not cache:
         env["RT_DEBUG_OPTIONS"] = "shadow_cache_res=0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scene", scene, "--steps", str(steps), "--warmup", "20", "--no-live-pmc", "--hbm-frames", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scene", scene, "--steps", str(steps), "--warmup", "20", "--no-live-pmc", "--hbm-frames", "0",
            "--cpu-seconds", "0", "--no-strong"] + ([] if cache else ["--no-frame-by-frame"])
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
