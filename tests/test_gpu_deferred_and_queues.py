@@ -444,3 +444,55 @@ def test_primary_launch_without_stack_rows_hands_rays_to_the_retry_launch(gpu, c
             assert np.array_equal(got, want), (opts, deferred, int((got != want).any(axis=2).sum()))
             for k in ("rays_primary", "rays_secondary", "rays_shadow", "primary_hits", "secondary_hits"):
                 assert gt[k] == wt[k], (opts, deferred, k)
+
+
+def glossy_frames(capi, ctx, model, W, H, cam, n, deferred, env=None):
+    """n progressive frames of one model under a glossy material (type 1, roughness 0.4), deferred in sets of `deferred` (0: one by one):
+    the image, the ray totals, the material and the frames' constants"""
+    sc = capi.Scene(ctx)
+    sc.add_model(capi.Model(ctx, *model))
+    p = capi.Pipeline(ctx)
+    p.set_scene(sc)
+    mat = T.default_material()
+    mat["type"] = 1
+    mat["roughness"] = 0.4
+    p.add_material(mat)
+    if env is not None:
+        p.set_environment_cube(env)
+    p.create_output(W, H)
+    p.build_acceleration_structures()
+    p.set_deferred(deferred)
+    host = capi.ProgressiveHost(11)
+    pfcs = [host.update(cam, 0.0, f + 1, W, H) for f in range(n)]
+    for pfc in pfcs:
+        p.update(pfc)
+        p.render()
+    return p.read_output(), p.totals(), mat, pfcs
+
+
+@pytest.mark.parametrize("deferred", (0, 3))
+def test_glossy_cornell_against_the_oracle(gpu, capi, oracle, deferred):
+    """Cornell under a glossy material, three frames one by one and as one set: the oracle's image bit for bit"""
+    W, H = 96, 80
+    model = oracle.obj_load(CORNELL_OBJ)
+    got, _, mat, pfcs = glossy_frames(capi, gpu, model, W, H, cam_array(scenes.cornell_camera(), W / H), 3, deferred)
+    osc = oracle.Scene()
+    osc.add_instance(osc.add_model(*model))
+    osc.build()
+    acc = np.zeros((H, W, 4), np.float32)
+    for pfc in pfcs:
+        acc, _ = osc.render(mat, pfc, W, H, accum=acc, nthreads=4)
+    assert np.array_equal(got, acc), "%d pixels differ" % int((got != acc).any(axis=2).sum())
+
+
+def test_glossy_atrium_deferred_equals_immediate(gpu, capi):
+    """the atrium under a glossy material, three frames as one set: the image and the ray totals of the frames one by one"""
+    W, H = 480, 270
+    model = scenes.sponza_class(seed=42, detail=0.5)
+    cam = cam_array(scenes.sponza_camera(), W / H)
+    env = scenes.sky_cubemap(16)
+    want, t0, _, _ = glossy_frames(capi, gpu, model, W, H, cam, 3, 0, env)
+    got, t1, _, _ = glossy_frames(capi, gpu, model, W, H, cam, 3, 3, env)
+    assert np.array_equal(got, want), "%d pixels differ" % int((got != want).any(axis=2).sum())
+    for k in ("rays_primary", "rays_secondary", "rays_shadow", "primary_hits", "secondary_hits"):
+        assert t0[k] == t1[k], (k, t0[k], t1[k])
