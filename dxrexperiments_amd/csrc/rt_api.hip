@@ -1,5 +1,7 @@
 // rt_api.hip -- C-ABI entry points for context, model, scene and batch TraceRay
 // (include/dxr_amd.h).  Stand-ins for libs/DXRFramework/Rt{Context,Model,Scene}.
+#include <cmath>
+#include <cstring>
 #include <new>
 
 #include "rt_trace_device.h"
@@ -113,35 +115,41 @@ extern "C" int rt_debug_set_option(rt_context *c, const char *name, const char *
 {
     RT_REQUIRE(c && name && value, "null argument");
     const std::string n(name);
-    // every option but fast_bvh takes a number: the whole of `value` must be one ('true', 'on', '4x' used to read as 0 and quietly switch things off)
+    // every option but fast_bvh takes a number: the whole of `value` must be one, decimal and finite ('true', 'on', '4x' used to read as 0 and
+    // quietly switch things off; strtod also reads 'inf', 'nan' and '0x10').  The name is matched first, so that a misspelt option is reported as
+    // unknown whatever its value: is() notes that the name exists and lets its branch run only with a well-formed value.
     char *end_i = nullptr, *end_f = nullptr;
     const long iv = strtol(value, &end_i, 10);
     const double fv = strtod(value, &end_f);
     auto bad = [&]() { rt_set_error("rt_debug_set_option: value '%s' out of range for '%s'", value, name); return RT_ERR_INVALID_ARG; };
-    const bool is_int = *value != '\0' && end_i && *end_i == '\0', is_num = *value != '\0' && end_f && *end_f == '\0';
+    const bool is_int = *value != '\0' && end_i && *end_i == '\0';
+    const bool is_num = *value != '\0' && end_f && *end_f == '\0' && std::isfinite(fv) && !strpbrk(value, "xX");
     const bool wants_float = n == "sah_node" || n == "sah_prim" || n == "dist_check_seconds";
-    if (n != "fast_bvh" && !(wants_float ? is_num : is_int)) { rt_set_error("rt_debug_set_option: '%s' is not a number (option '%s')", value, name); return RT_ERR_INVALID_ARG; }
-    if (n == "lds_top") c->lds_top = iv != 0;
-    else if (n == "lds_stack_rows") { if (iv != 0 && iv != RT_LDS_STACK_ROWS && iv != RT_LDS_STACK_ROWS_TEST) return bad(); c->lds_stack_rows = (uint32_t)iv; }
-    else if (n == "persistent_blocks_per_cu") { if (iv < 0 || iv > 16) return bad(); c->blocks_per_cu_override = (uint32_t)iv; }
-    else if (n == "fast_bvh") { if (strcmp(value, "lbvh") != 0 && strcmp(value, "ploc") != 0) return bad(); c->use_ploc = strcmp(value, "ploc") == 0; }
-    else if (n == "build_batch") { if (iv < 0 || iv > 64) return bad(); c->build_batch = (uint32_t)iv; }
-    else if (n == "leaf_max") { if (iv < 1 || iv > 8) return bad(); c->leaf_max = (uint32_t)iv; }
-    else if (n == "wide_sah") c->wide_sah = iv != 0;
-    else if (n == "sah_node") { if (!(fv > 0.0)) return bad(); c->sah_node = (float)fv; }
-    else if (n == "sah_prim") { if (!(fv > 0.0)) return bad(); c->sah_prim = (float)fv; }
-    else if (n == "verbose") c->verbose = iv != 0;
-    else if (n == "shadow_cache_res") { if (iv < -1 || iv > 8192) return bad(); c->opt_shadow_cache_res = (int)iv; }
-    else if (n == "shadow_cache_pixels") { if (iv < -1 || iv > 1) return bad(); c->opt_shadow_cache_pixels = (int)iv; }
-    else if (n == "primary_persistent") { if (iv < -1 || iv > 1) return bad(); c->opt_primary_persistent = (int)iv; }
-    else if (n == "seven_waves_always") c->opt_seven_waves_always = iv != 0;
-    else if (n == "free_radius") c->opt_free_radius = iv != 0;
-    else if (n == "split_refs") c->opt_split_refs = iv != 0;
-    else if (n == "fail_ploc_rounds") c->opt_fail_ploc_rounds = iv != 0;
-    else if (n == "primary_retry_cap") { if (iv < 0 || iv > (1 << 24)) return bad(); c->opt_primary_retry_cap = (uint32_t)iv; }
-    else if (n == "batch_max") { if (iv < 0 || iv > 32) return bad(); c->opt_batch_max = (uint32_t)iv; }
-    else if (n == "queue_budget_mb") { if (iv < 0) return bad(); c->opt_queue_budget_mb = (size_t)iv; }
-    else if (n == "dist_check_seconds") { if (!(fv >= 0.0)) return bad(); c->opt_dist_check_seconds = fv; }
+    const bool value_ok = n == "fast_bvh" || (wants_float ? is_num : is_int);
+    bool known = false;
+    auto is = [&](bool match) { known = known || match; return match && value_ok; };
+    if (is(n == "lds_top")) c->lds_top = iv != 0;
+    else if (is(n == "lds_stack_rows")) { if (iv != 0 && iv != RT_LDS_STACK_ROWS && iv != RT_LDS_STACK_ROWS_TEST) return bad(); c->lds_stack_rows = (uint32_t)iv; }
+    else if (is(n == "persistent_blocks_per_cu")) { if (iv < 0 || iv > 16) return bad(); c->blocks_per_cu_override = (uint32_t)iv; }
+    else if (is(n == "fast_bvh")) { if (strcmp(value, "lbvh") != 0 && strcmp(value, "ploc") != 0) return bad(); c->use_ploc = strcmp(value, "ploc") == 0; }
+    else if (is(n == "build_batch")) { if (iv < 0 || iv > 64) return bad(); c->build_batch = (uint32_t)iv; }
+    else if (is(n == "leaf_max")) { if (iv < 1 || iv > 8) return bad(); c->leaf_max = (uint32_t)iv; }
+    else if (is(n == "wide_sah")) c->wide_sah = iv != 0;
+    else if (is(n == "sah_node")) { if (!(fv > 0.0)) return bad(); c->sah_node = (float)fv; }
+    else if (is(n == "sah_prim")) { if (!(fv > 0.0)) return bad(); c->sah_prim = (float)fv; }
+    else if (is(n == "verbose")) c->verbose = iv != 0;
+    else if (is(n == "shadow_cache_res")) { if (iv < -1 || iv > 8192) return bad(); c->opt_shadow_cache_res = (int)iv; }
+    else if (is(n == "shadow_cache_pixels")) { if (iv < -1 || iv > 1) return bad(); c->opt_shadow_cache_pixels = (int)iv; }
+    else if (is(n == "primary_persistent")) { if (iv < -1 || iv > 1) return bad(); c->opt_primary_persistent = (int)iv; }
+    else if (is(n == "seven_waves_always")) c->opt_seven_waves_always = iv != 0;
+    else if (is(n == "free_radius")) c->opt_free_radius = iv != 0;
+    else if (is(n == "split_refs")) c->opt_split_refs = iv != 0;
+    else if (is(n == "fail_ploc_rounds")) c->opt_fail_ploc_rounds = iv != 0;
+    else if (is(n == "primary_retry_cap")) { if (iv < 0 || iv > (1 << 24)) return bad(); c->opt_primary_retry_cap = (uint32_t)iv; }
+    else if (is(n == "batch_max")) { if (iv < 0 || iv > 32) return bad(); c->opt_batch_max = (uint32_t)iv; }
+    else if (is(n == "queue_budget_mb")) { if (iv < 0) return bad(); c->opt_queue_budget_mb = (size_t)iv; }
+    else if (is(n == "dist_check_seconds")) { if (!(fv >= 0.0)) return bad(); c->opt_dist_check_seconds = fv; }
+    else if (known) { rt_set_error("rt_debug_set_option: '%s' is not a number (option '%s')", value, name); return RT_ERR_INVALID_ARG; }
     else { rt_set_error("rt_debug_set_option: unknown option '%s'", name); return RT_ERR_INVALID_ARG; }
     return RT_OK;
 }
@@ -183,7 +191,11 @@ static int context_create(int device, void *stream, bool own, rt_context **out)
         while (at < all.size()) {
             size_t end = all.find(',', at);
             if (end == std::string::npos) end = all.size();
-            const std::string item = all.substr(at, end - at);
+            auto trim = [](const std::string &t) {          // blanks around an item, a name or a value are not part of it
+                const size_t a = t.find_first_not_of(" \t"), b = t.find_last_not_of(" \t");
+                return a == std::string::npos ? std::string() : t.substr(a, b - a + 1);
+            };
+            const std::string item = trim(all.substr(at, end - at));
             const size_t eq = item.find('=');
             if (item.empty()) { at = end + 1; continue; }
             if (eq == std::string::npos) {
@@ -191,7 +203,7 @@ static int context_create(int device, void *stream, bool own, rt_context **out)
                 rt_context_release(c);
                 return RT_ERR_INVALID_ARG;
             }
-            if (rt_debug_set_option(c, item.substr(0, eq).c_str(), item.substr(eq + 1).c_str()) != RT_OK) {
+            if (rt_debug_set_option(c, trim(item.substr(0, eq)).c_str(), trim(item.substr(eq + 1)).c_str()) != RT_OK) {
                 const std::string why = rt_last_error();
                 rt_set_error("RT_DEBUG_OPTIONS: %s", why.c_str());
                 rt_context_release(c);

@@ -611,19 +611,21 @@ int rt_build_blas(rt_context *ctx, rt_model *m)
             rc = split_layout ? rt_build_ploc_layout(ctx, m, &ploc_done, n_refs, r_leaf_box.as<float>(), r_leaf_prim.as<uint32_t>())
                               : rt_build_ploc_layout(ctx, m, &ploc_done);
             // PLOC's nearest-neighbour rounds make no progress on boxes whose surface is not finite (NaN / inf vertices,
-            // extents that overflow): such a mesh keeps the LBVH as its traversal layout (m->tris is still in LBVH order)
+            // extents that overflow): such a mesh keeps the LBVH as its traversal layout.  rt_build_ploc_layout may give up AFTER k_ploc_tris
+            // had rewritten m->tris in PLOC order (the collapse that follows it can refuse a tree too), so the records are gathered again
+            // in LBVH order whatever the mesh: that is the order the collapse below and k_ref_mark_records index
             if (rc == RT_ERR_STATE || (rc == RT_OK && ctx->opt_fail_ploc_rounds)) {      // (the option: tests force this path)
                 rc = RT_OK;
                 ploc_done = false;
                 if (split_layout) {
-                    // the split-reference path had already grown m->tris for one record per REFERENCE (DevBuf::reserve keeps no contents):
-                    // back to one LBVH-ordered record per triangle, which is what the collapse below and k_ref_mark_records index
+                    // the split-reference path had grown m->tris for one record per REFERENCE (DevBuf::reserve keeps no contents):
+                    // back to one record per triangle
                     m->rec_boxes.release();
                     m->n_recs = n;
                     if ((rc = m->tris.reserve(sizeof(TriRec) * (size_t)n)) != RT_OK) break;
-                    k_gather_tris<<<grid_for(n, B), B, 0, st>>>(m->blas.keys.as<uint64_t>(), m->d_verts.as<rt_vertex>(),
-                                                                m->d_idx.as<uint32_t>(), n, m->tris.as<TriRec>());
                 }
+                k_gather_tris<<<grid_for(n, B), B, 0, st>>>(m->blas.keys.as<uint64_t>(), m->d_verts.as<rt_vertex>(),
+                                                            m->d_idx.as<uint32_t>(), n, m->tris.as<TriRec>());
             }
             if (rc != RT_OK) break;
         }

@@ -173,12 +173,34 @@ def test_a_nan_vertex_among_slivers(gpu, oracle, capi):
 
 
 def test_debug_options_are_parsed_strictly(gpu, capi):
-    """rt_debug_set_option: a value that is not a number is an error, not a silent 0 ('lds_top=true' used to switch the LDS top off)"""
+    """rt_debug_set_option: a value that is not a number is an error, not a silent 0 (ADVICE r5: 'lds_top=true' used to switch the LDS top off);
+    nor is one that strtod reads but that is no finite decimal number ('inf', 'nan', '0x10'); the name is judged before the value, so a
+    misspelt option is reported as unknown whatever it is set to; blanks around the items of RT_DEBUG_OPTIONS are not part of them."""
+    import subprocess
+    import sys
     ctx = capi.Context(0)
-    for name, value in (("lds_top", "true"), ("split_refs", "yes"), ("leaf_max", "4x"), ("sah_node", "one"), ("verbose", "")):
+    for name, value in (("lds_top", "true"), ("split_refs", "yes"), ("leaf_max", "4x"), ("sah_node", "one"), ("verbose", ""),
+                        ("sah_node", "inf"), ("sah_node", "nan"), ("sah_node", "-inf"), ("sah_prim", "0x10"), ("sah_prim", "infinity"), ("leaf_max", "0x4")):
         with pytest.raises(capi.RtError):
             ctx.set_option(name, value)
+    for name, value in (("lds_topp", "true"), ("no_such_option", "yes"), ("no_such_option", "1"), ("", "")):
+        with pytest.raises(capi.RtError) as e:
+            ctx.set_option(name, value)
+        assert "unknown option" in str(e.value) and "not a number" not in str(e.value), str(e.value)
+    with pytest.raises(capi.RtError) as e:
+        ctx.set_option("leaf_max", "four")
+    assert "not a number" in str(e.value), str(e.value)
     ctx.set_option("lds_top", 1)
     ctx.set_option("sah_node", "1.5")
+    ctx.set_option("sah_prim", "2.5e-1")
     ctx.set_option("fast_bvh", "ploc")
     ctx.close()
+    # the environment variable, read when a context is created: in a child process, with blanks around the items
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "from dxrexperiments_amd import capi; c = capi.Context(0); c.close(); print('context ok')"
+    for text, ok in (("lds_top=1 , leaf_max=3 ", True), (" lds_top = 1 ,, leaf_max=3", True), ("lds_top=1 , leaf_max=3 x", False), ("lds_topp=1", False)):
+        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RT_DEBUG_OPTIONS=text), cwd=root, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True, timeout=300)
+        assert (r.returncode == 0 and "context ok" in r.stdout) == ok, (text, r.returncode, r.stdout[-2000:])
+        if not ok:
+            assert "RT_DEBUG_OPTIONS" in r.stdout, (text, r.stdout[-2000:])

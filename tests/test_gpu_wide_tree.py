@@ -21,29 +21,7 @@ def build(capi, gpu, models, instances):
     return sc
 
 
-def check_blas(sc, which, v, i):
-    nodes, root, recs = sc.wide_read(which)
-    lo, hi, prim = W.record_bounds(recs)
-    n = i.shape[0]
-    off, boxes, rec_boxes = sc.refs(which)
-    mark = recs.view(np.uint32)[:, 10]
-    if off is None:
-        assert recs.shape[0] == n and np.array_equal(np.sort(prim), np.arange(n, dtype=np.uint32)), "records are not a permutation of the triangles"
-        assert not mark.any()
-    else:
-        # split references (round 5, rt_refs.h): a record per reference -- every triangle at least once, a split one once per box -- and a
-        # record that is one of several is held by ITS box, which is what the child boxes above it must contain
-        cnt = np.diff(off)
-        single = recs.shape[0] == n                         # a layout that holds every triangle once (LBVH layout, option split_refs=0)
-        assert np.array_equal(np.bincount(prim, minlength=n), np.ones(n, np.int64) if single else cnt), "records do not cover the references"
-        assert np.array_equal(mark, np.where(cnt[prim] > 1, 2 if single else 1, 0))
-        if not single:
-            lo = np.where((mark == 1)[:, None], rec_boxes[:, :3], lo)
-            hi = np.where((mark == 1)[:, None], rec_boxes[:, 3:], hi)
-    tri = v["position"][i[prim]]                           # the record of primitive p holds p's vertices, bit for bit
-    assert np.array_equal(recs[:, :9].reshape(-1, 3, 3), tri)
-    st = W.check(nodes, root, lo, hi, recs.shape[0], blas=True)
-    return st, nodes, root
+check_blas = W.check_blas
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 6, 7, 64, 1000, 30000])
@@ -216,11 +194,10 @@ def test_surface_area_collapse_option(gpu, capi):
     _same_hits(sc3, O, D)
 
 
-def test_three_blases_two_of_them_lds_resident(gpu, capi):
-    """RT_LDS_BLAS=1 (round 3; off by default: measured no faster): two-level kernels keep the tops of the TLAS and of the TWO
-    most-instanced BLASes in LDS; a third model's instances walk their BLAS from global memory.  Same hits as the canonical
-    kernel for all three, in both usage orders, and the same hits as with the option off."""
-    import os
+def test_three_blases_in_two_usage_orders(gpu, capi):
+    """Three models under one TLAS, one of them rare (10 of 90 instances), in two usage orders -- which model is the rare one decides
+    the order the kernels meet the BLASes in.  For both: the production walk returns the canonical kernel's hits (closest bit for
+    bit, any-hit verdicts), and two builds of the same scene agree with each other bit for bit."""
     from util import assert_hits_equal, random_rays
     models = [scenes.blob_mesh(level=2), triangle_soup(600, seed=21, extent=2.0, size=0.5), triangle_soup(3000, seed=22, extent=2.5, size=0.3)]
     xf = random_xforms(90, seed=23, spread=9.0)
@@ -228,10 +205,6 @@ def test_three_blases_two_of_them_lds_resident(gpu, capi):
     for order in ((0, 1, 2), (2, 0, 1)):                 # which model is the rare one (10 of 90 instances)
         inst = [(order[0] if k % 9 else order[2], xf[k]) if k % 2 else (order[1] if k % 9 else order[2], xf[k]) for k in range(90)]
         plain = build(capi, gpu, models, inst).trace(O, D)
-        os.environ["RT_LDS_BLAS"] = "1"                  # (read when the TLAS is built)
-        try:
-            sc = build(capi, gpu, models, inst)
-        finally:
-            del os.environ["RT_LDS_BLAS"]
+        sc = build(capi, gpu, models, inst)
         _same_hits(sc, O, D)
-        assert_hits_equal(sc.trace(O, D), plain, "BLAS tops in LDS vs not")
+        assert_hits_equal(sc.trace(O, D), plain, "second build vs first")

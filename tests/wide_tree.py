@@ -94,7 +94,7 @@ def levels_of(code):
 
 def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True):
     """Invariants of a wide tree.  leaf_lo / leaf_hi: true bounds per record (BLAS) or per instance (TLAS).
-    Returns a dict of statistics; raises AssertionError with a description on the first violation."""
+    Returns a dict of statistics (largest_leaf: the most records any one leaf holds); raises AssertionError with a description on the first violation."""
     n = nodes.shape[0]
     if root_code < 0:
         assert n == 0, "a one-leaf structure has no nodes"
@@ -104,7 +104,7 @@ def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True):
             assert first == 0 and cnt == n_leaf_items, "root leaf does not cover the structure"
         else:
             assert code == 0 and n_leaf_items == 1
-        return {"nodes": 0, "levels": 0}
+        return {"nodes": 0, "levels": 0, "largest_leaf": int(n_leaf_items)}
     d = decode(nodes)
     code = d["code"]
     WIDE = d["width"]
@@ -177,7 +177,35 @@ def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True):
     mant, _ = np.frexp(sc[np.isfinite(sc)])
     assert np.all(mant == 0.5), "a scale that is not a power of two"
     return {"nodes": n, "levels": int(level.max()) + 1, "children_per_node": float(used.sum()) / n,
-            "leaf_children": int(leaf.sum()), "decoded": d, "true_lo": tlo, "true_hi": thi, "level": level}
+            "leaf_children": int(leaf.sum()), "largest_leaf": int((((~code[leaf]) & 7) + 1).max()) if blas else 1, "decoded": d, "true_lo": tlo, "true_hi": thi, "level": level}
+
+
+def check_blas(sc, which, v, i):
+    """The BLAS of instance `which`'s model (capi.Scene.wide_read) against the mesh (v, i) it was built from: the records are the
+    triangles bit for bit, every triangle -- or every reference of a split one (rt_refs.h) -- once, then check().
+    Returns (statistics, nodes, root_code)."""
+    nodes, root, recs = sc.wide_read(which)
+    lo, hi, prim = record_bounds(recs)
+    n = i.shape[0]
+    off, boxes, rec_boxes = sc.refs(which)
+    mark = recs.view(np.uint32)[:, 10]
+    if off is None:
+        assert recs.shape[0] == n and np.array_equal(np.sort(prim), np.arange(n, dtype=np.uint32)), "records are not a permutation of the triangles"
+        assert not mark.any()
+    else:
+        # split references (round 5, rt_refs.h): a record per reference -- every triangle at least once, a split one once per box -- and a
+        # record that is one of several is held by ITS box, which is what the child boxes above it must contain
+        cnt = np.diff(off)
+        single = recs.shape[0] == n                         # a layout that holds every triangle once (LBVH layout, option split_refs=0)
+        assert np.array_equal(np.bincount(prim, minlength=n), np.ones(n, np.int64) if single else cnt), "records do not cover the references"
+        assert np.array_equal(mark, np.where(cnt[prim] > 1, 2 if single else 1, 0))
+        if not single:
+            lo = np.where((mark == 1)[:, None], rec_boxes[:, :3], lo)
+            hi = np.where((mark == 1)[:, None], rec_boxes[:, 3:], hi)
+    tri = v["position"][i[prim]]                           # the record of primitive p holds p's vertices, bit for bit
+    assert np.array_equal(recs[:, :9].reshape(-1, 3, 3), tri)
+    st = check(nodes, root, lo, hi, recs.shape[0], blas=True)
+    return st, nodes, root
 
 
 def half_area(lo, hi):
