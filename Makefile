@@ -55,7 +55,7 @@ $(LIB): $(OBJS)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $(OBJS) -ldl -lz
 
 oracle:
-	$(MAKE) -C oracle liboracle.so
+	$(MAKE) -C oracle liboracle.so refshade
 
 clean:
 	rm -rf build $(LIB) $(BIN)

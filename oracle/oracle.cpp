@@ -10,8 +10,9 @@
  * cannot be built or run here (Windows/D3D12/DXC + un-vendored Fallback
  * Layer).  The shading/RNG/raygen half follows the reference's HLSL text line
  * by line and is pinned by the integer RNG known-answer values derived from
- * that text; the acceleration-structure and intersection
- * half is "parity unpinned" -- see oracle_bvh.h.
+ * that text and, bit for bit, by that text itself compiled as
+ * C++ (refshade/README.md, tests/test_refshade.py); the acceleration-structure
+ * and intersection half is "parity unpinned" -- see oracle_bvh.h.
  *
  * Host-side restatements in this file:
  *   RtModel::RtModel mesh ingestion      libs/DXRFramework/RtModel.cpp:24-82
@@ -351,6 +352,19 @@ int orc_scene_instance_info(const orc_scene *sc, uint32_t inst, float world_box[
     world_box[0] = in.world.lo.x; world_box[1] = in.world.lo.y; world_box[2] = in.world.lo.z;
     world_box[3] = in.world.hi.x; world_box[4] = in.world.hi.y; world_box[5] = in.world.hi.z;
     memcpy(inv, in.inv, sizeof in.inv);
+    return 0;
+}
+
+int orc_scene_instance_geometry(const orc_scene *sc, uint32_t inst, const rt_vertex **verts, uint32_t *nv,
+                                const uint32_t **idx, uint32_t *nt, uint32_t *n_instances)
+{
+    if (n_instances) *n_instances = (uint32_t)sc->s.inst.size();
+    if (inst >= sc->s.inst.size()) return -1;
+    const Model &m = sc->s.models[sc->s.inst[inst].model];
+    if (verts) *verts = m.verts.data();
+    if (nv) *nv = (uint32_t)m.verts.size();
+    if (idx) *idx = m.idx.data();
+    if (nt) *nt = m.ntris;
     return 0;
 }
 

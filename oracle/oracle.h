@@ -50,6 +50,9 @@ void orc_set_split_refs(int on);     /* scenes built from now on: 0 = no triangl
 int  orc_scene_refs_info(const orc_scene *s, uint32_t model, uint32_t *n_refs);
 int  orc_scene_refs_read(const orc_scene *s, uint32_t model, uint32_t *off, float *boxes);
 int  orc_scene_instance_info(const orc_scene *s, uint32_t inst, float world_box[6], float inv[12]);
+/* oracle/refshade: the vertex and index arrays of an instance's model (owned by the scene); *n_instances = the scene's instance count */
+int  orc_scene_instance_geometry(const orc_scene *s, uint32_t inst, const rt_vertex **verts, uint32_t *nv,
+                                 const uint32_t **idx, uint32_t *nt, uint32_t *n_instances);
 
 int  orc_trace(const orc_scene *s, const float *origin_tmin, const float *dir_tmax, size_t n, uint32_t flags, int mode,
                float *t, float *u, float *v, uint32_t *prim, uint32_t *inst, uint32_t *cnt_nodes, uint32_t *cnt_tris,
