@@ -11,9 +11,16 @@
 //   - normals come from LayerElementNormal (ByPolygonVertex or ByVertice / ByVertex, Direct or IndexToDirect); a geometry
 //     without them gets generated smooth normals: the normalised sum of cross(b-a, c-a) over the triangles at a position;
 //   - vertices are joined per distinct (position index, normal value) pair and numbered in first-use order;
-//   - "PreTransformVertices": the Lcl Translation / Lcl Rotation (Euler XYZ, degrees) / Lcl Scaling of the Model a geometry is
-//     connected to are applied (normals by the inverse transpose, renormalised).  Parent chains, pivots and pre / post
-//     rotations are not: a file that needs them is outside this reader's scope and says so in the error text.
+//   - "PreTransformVertices": the node hierarchy is flattened.  Each Model's local matrix is FBX's
+//       L = T * Roff * Rp * Rpre * R * Rpost^-1 * Rp^-1 * Soff * Sp * S * Sp^-1
+//     (Lcl Translation, RotationOffset, RotationPivot, PreRotation, Lcl Rotation under RotationOrder 0 ... 5, PostRotation, ScalingOffset,
+//     ScalingPivot, Lcl Scaling; degrees; pre / post rotations in XYZ order; the static values, animation curves are ignored), a mesh's
+//     World is the product of L down the "OO" Model -> Model chain (non-mesh Models included), and its vertices are World * G * v with
+//     G = GeometricTranslation * Rotation * Scaling of its own Model only; normals by the inverse transpose, renormalised.  A Geometry
+//     connected to k Models is emitted k times, in Connections order.  Refused, by name: RotationOrder 6 (spheric), InheritType 0 / 2
+//     under an ancestor with non-unit Lcl Scaling (where the three types differ), a singular total transform; and as malformed: a
+//     parent cycle, a chain deeper than 256, a Model under two Models.  Not applied: GlobalSettings axis / unit conversion, winding
+//     flips under mirroring transforms, skins and blend shapes.
 // Doubles are converted to float with a plain cast.  Arrays may be zlib-compressed (encoding 1).
 #include <math.h>
 #include <stdlib.h>
@@ -157,36 +164,141 @@ struct M34 { double m[12]; };       // 3x4 row-major affine
 
 M34 identity34() { M34 r = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}}; return r; }
 
-// T * Rz * Ry * Rx * S (FBX's default eEulerXYZ order: X applied first), angles in degrees
-M34 model_transform(const Node &model, bool *unsupported)
+// a * b
+M34 mul34(const M34 &a, const M34 &b)
 {
-    double t[3] = {0, 0, 0}, rdeg[3] = {0, 0, 0}, s[3] = {1, 1, 1};
-    if (const Node *p70 = model.kid("Properties70")) {
-        for (const Node &p : p70->kids) {
-            if (p.name != "P" || p.props.empty()) continue;
-            const std::string &key = p.props[0].str;
-            double *dst = key == "Lcl Translation" ? t : key == "Lcl Rotation" ? rdeg : key == "Lcl Scaling" ? s : nullptr;
-            if (dst) {
-                int k = 0;
-                for (size_t i = 4; i < p.props.size() && k < 3; i++)
-                    if (!p.props[i].nums.empty()) dst[k++] = p.props[i].nums[0];
-            } else if (key == "PreRotation" || key == "PostRotation" || key == "RotationPivot" || key == "ScalingPivot" || key == "RotationOffset" ||
-                       key == "ScalingOffset" || key == "GeometricTranslation" || key == "GeometricRotation" || key == "GeometricScaling") {
-                for (size_t i = 4; i < p.props.size(); i++)
-                    if (!p.props[i].nums.empty() && p.props[i].nums[0] != 0.0 && !(key == "GeometricScaling" && p.props[i].nums[0] == 1.0)) *unsupported = true;
-            }
-        }
-    }
-    const double k = 3.14159265358979323846 / 180.0;
-    const double cx = cos(rdeg[0] * k), sx = sin(rdeg[0] * k), cy = cos(rdeg[1] * k), sy = sin(rdeg[1] * k), cz = cos(rdeg[2] * k), sz = sin(rdeg[2] * k);
-    // R = Rz * Ry * Rx
-    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx,
-                         sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx,
-                         -sy, cy * sx, cy * cx};
     M34 o;
     for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) o.m[4 * r + c] = R[3 * r + c] * s[c];
-        o.m[4 * r + 3] = t[r];
+        for (int c = 0; c < 3; c++) o.m[4 * r + c] = a.m[4 * r] * b.m[c] + a.m[4 * r + 1] * b.m[4 + c] + a.m[4 * r + 2] * b.m[8 + c];
+        o.m[4 * r + 3] = a.m[4 * r] * b.m[3] + a.m[4 * r + 1] * b.m[7] + a.m[4 * r + 2] * b.m[11] + a.m[4 * r + 3];
+    }
+    return o;
+}
+
+// the static transform properties of one Model (Properties70; animation curves connected to them are ignored)
+struct Xform {
+    double t[3] = {0, 0, 0}, roff[3] = {0, 0, 0}, rp[3] = {0, 0, 0}, pre[3] = {0, 0, 0}, r[3] = {0, 0, 0}, post[3] = {0, 0, 0}, soff[3] = {0, 0, 0},
+           sp[3] = {0, 0, 0}, s[3] = {1, 1, 1}, gt[3] = {0, 0, 0}, gr[3] = {0, 0, 0}, gs[3] = {1, 1, 1};
+    long long order = 0, inherit = -1;          // RotationOrder; InheritType, -1 = not in the file (plain composition)
+};
+
+Xform read_xform(const Node &model)
+{
+    Xform x;
+    const Node *p70 = model.kid("Properties70");
+    if (!p70) return x;
+    for (const Node &p : p70->kids) {
+        if (p.name != "P" || p.props.empty()) continue;
+        const std::string &key = p.props[0].str;
+        double *dst = key == "Lcl Translation" ? x.t : key == "Lcl Rotation" ? x.r : key == "Lcl Scaling" ? x.s : key == "PreRotation" ? x.pre :
+                      key == "PostRotation" ? x.post : key == "RotationPivot" ? x.rp : key == "ScalingPivot" ? x.sp : key == "RotationOffset" ? x.roff :
+                      key == "ScalingOffset" ? x.soff : key == "GeometricTranslation" ? x.gt : key == "GeometricRotation" ? x.gr :
+                      key == "GeometricScaling" ? x.gs : nullptr;
+        if (dst) {
+            int k = 0;
+            for (size_t i = 4; i < p.props.size() && k < 3; i++)
+                if (!p.props[i].nums.empty()) dst[k++] = p.props[i].nums[0];
+        } else if (key == "RotationOrder" || key == "InheritType") {
+            for (size_t i = 4; i < p.props.size(); i++)
+                if (!p.props[i].nums.empty()) {
+                    const double d = p.props[i].nums[0];          // (an enum; a value no enum can hold is refused below, by name)
+                    (key == "RotationOrder" ? x.order : x.inherit) = !p.props[i].ints.empty() ? p.props[i].ints[0] : (d >= 0.0 && d <= 100.0) ? (long long)d : 101;
+                    break;
+                }
+        }
+    }
+    return x;
+}
+
+bool all3(const double *v, double what) { return v[0] == what && v[1] == what && v[2] == what; }
+
+// Rz * Ry * Rx (FBX's default eEulerXYZ order: X applied first), angles in degrees
+void euler_xyz(const double *deg, double *R)
+{
+    const double k = 3.14159265358979323846 / 180.0;
+    const double cx = cos(deg[0] * k), sx = sin(deg[0] * k), cy = cos(deg[1] * k), sy = sin(deg[1] * k), cz = cos(deg[2] * k), sz = sin(deg[2] * k);
+    const double r[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx,
+                         sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx,
+                         -sy, cy * sx, cy * cx};
+    memcpy(R, r, sizeof r);
+}
+
+void mul33(const double *a, const double *b, double *o)
+{
+    double t[9];
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) t[3 * r + c] = a[3 * r] * b[c] + a[3 * r + 1] * b[3 + c] + a[3 * r + 2] * b[6 + c];
+    memcpy(o, t, sizeof t);
+}
+
+void axis_rotation(int axis, double deg, double *R)
+{
+    const double a = deg * (3.14159265358979323846 / 180.0), c = cos(a), s = sin(a);
+    const double x[9] = {1, 0, 0, 0, c, -s, 0, s, c}, y[9] = {c, 0, s, 0, 1, 0, -s, 0, c}, z[9] = {c, -s, 0, s, c, 0, 0, 0, 1};
+    memcpy(R, axis == 0 ? x : axis == 1 ? y : z, sizeof x);
+}
+
+// Lcl Rotation under RotationOrder 0 ... 5 (the first axis of the order's name is applied first, so it stands rightmost)
+void euler_ordered(const double *deg, long long order, double *R)
+{
+    if (order == 0) { euler_xyz(deg, R); return; }
+    static const int axes[6][3] = {{2, 1, 0}, {1, 2, 0}, {0, 2, 1}, {2, 0, 1}, {1, 0, 2}, {0, 1, 2}};      // left, middle, right factor
+    double a[9], b[9], c[9];
+    axis_rotation(axes[order][0], deg[axes[order][0]], a);
+    axis_rotation(axes[order][1], deg[axes[order][1]], b);
+    axis_rotation(axes[order][2], deg[axes[order][2]], c);
+    mul33(b, c, b);
+    mul33(a, b, R);
+}
+
+// p += v, where identity terms (v = 0, and p while nothing has been put into it) are skipped, not added: 0 + x can turn -0 into +0
+void add3(double *p, bool &have, const double *v, double sign)
+{
+    if (all3(v, 0.0)) return;
+    for (int k = 0; k < 3; k++) p[k] = have ? p[k] + sign * v[k] : sign * v[k];
+    have = true;
+}
+
+// L = T * Roff * Rp * Rpre * R * Rpost^-1 * Rp^-1 * Soff * Sp * S * Sp^-1: the linear part is Rpre * R * Rpost^-1 * S, the translation is
+// the image of the origin.  With every factor but T, R (order XYZ), S at its identity this is exactly T * Rz * Ry * Rx * S as before.
+M34 local_matrix(const Xform &x)
+{
+    double Q[9], F[9];
+    euler_ordered(x.r, x.order, Q);
+    if (!all3(x.pre, 0.0)) { euler_xyz(x.pre, F); mul33(F, Q, Q); }
+    if (!all3(x.post, 0.0)) {
+        euler_xyz(x.post, F);
+        const double Ft[9] = {F[0], F[3], F[6], F[1], F[4], F[7], F[2], F[5], F[8]};       // (the inverse of a rotation)
+        mul33(Q, Ft, Q);
+    }
+    double p[3] = {0, 0, 0};
+    bool have = false;
+    add3(p, have, x.sp, -1.0);
+    if (have) for (int k = 0; k < 3; k++) p[k] = p[k] * x.s[k] + x.sp[k];
+    add3(p, have, x.soff, 1.0);
+    add3(p, have, x.rp, -1.0);
+    if (have) {
+        const double a = Q[0] * p[0] + Q[1] * p[1] + Q[2] * p[2], b = Q[3] * p[0] + Q[4] * p[1] + Q[5] * p[2], c = Q[6] * p[0] + Q[7] * p[1] + Q[8] * p[2];
+        p[0] = a; p[1] = b; p[2] = c;
+    }
+    add3(p, have, x.rp, 1.0);
+    add3(p, have, x.roff, 1.0);
+    M34 o;
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) o.m[4 * r + c] = Q[3 * r + c] * x.s[c];
+        o.m[4 * r + 3] = have ? p[r] + x.t[r] : x.t[r];
+    }
+    return o;
+}
+
+// G = GT * GR * GS: applies to the node's own mesh, not to its children
+M34 geometric_matrix(const Xform &x)
+{
+    double R[9];
+    euler_xyz(x.gr, R);
+    M34 o;
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) o.m[4 * r + c] = R[3 * r + c] * x.gs[c];
+        o.m[4 * r + 3] = x.gt[r];
     }
     return o;
 }
@@ -324,6 +436,58 @@ int add_geometry(const Node &geo, const M34 &xf, std::vector<rt_vertex> &verts, 
     return RT_OK;
 }
 
+struct ModelInfo {
+    Xform x;
+    const ModelInfo *parent = nullptr;      // the Model this one is "OO"-connected to, if any
+    bool two_parents = false;
+};
+
+const int MAX_CHAIN = 256;
+
+// World * G of the mesh under Model m: World = L(root-most ancestor) * ... * L(parent) * L(m), plain matrix composition.  Identity
+// factors are skipped, not multiplied in, so a Model directly under the scene root keeps exactly the matrix local_matrix() gives.
+int world_matrix(const char *path, const ModelInfo &m, size_t n_models, M34 &out)
+{
+    const ModelInfo *chain[MAX_CHAIN];
+    int n = 0;
+    for (const ModelInfo *k = &m; k; k = k->parent) {
+        if (k->two_parents) { rt_set_error("%s: a Model is connected to more than one parent Model", path); return RT_ERR_IO; }
+        if (n == MAX_CHAIN) {
+            size_t steps = 0;                                     // a chain that does not end within the number of Models there are is a cycle
+            while (k && steps <= n_models) { k = k->parent; steps++; }
+            if (k) rt_set_error("%s: the Model parent connections form a cycle", path);
+            else rt_set_error("%s: a Model parent chain is deeper than %d", path, MAX_CHAIN);
+            return RT_ERR_IO;
+        }
+        chain[n++] = k;
+    }
+    bool have = false, scaled_above = false;
+    for (int i = n - 1; i >= 0; i--) {                             // from the root down
+        const Xform &x = chain[i]->x;
+        if (x.order < 0 || x.order > 5) {
+            rt_set_error("%s: RotationOrder %lld (%s) is not supported: only the six Euler orders 0 ... 5 are", path, x.order, x.order == 6 ? "spheric XYZ" : "unknown");
+            return RT_ERR_UNSUPPORTED;
+        }
+        if ((x.inherit == 0 || x.inherit == 2) && scaled_above) {
+            rt_set_error("%s: InheritType %lld under a scaled ancestor is not supported (only InheritType 1, or unit Lcl Scaling on every ancestor)", path, x.inherit);
+            return RT_ERR_UNSUPPORTED;
+        }
+        if (x.inherit < -1 || x.inherit > 2) { rt_set_error("%s: InheritType %lld is not one of 0, 1, 2", path, x.inherit); return RT_ERR_UNSUPPORTED; }
+        if (!all3(x.s, 1.0)) scaled_above = true;
+        const M34 L = local_matrix(x);
+        if (is_identity(L)) continue;
+        out = have ? mul34(out, L) : L;
+        have = true;
+    }
+    if (!all3(m.x.gt, 0.0) || !all3(m.x.gr, 0.0) || !all3(m.x.gs, 1.0)) {
+        const M34 G = geometric_matrix(m.x);
+        out = have ? mul34(out, G) : G;
+        have = true;
+    }
+    if (!have) out = identity34();
+    return RT_OK;
+}
+
 }  // namespace
 
 static int fbx_parse_unguarded(const char *path, std::vector<rt_vertex> &verts, std::vector<uint32_t> &idx);
@@ -368,38 +532,36 @@ static int fbx_parse_unguarded(const char *path, std::vector<rt_vertex> &verts, 
     const Node *objects = nullptr, *conns = nullptr;
     for (const Node &n : top) { if (n.name == "Objects") objects = &n; else if (n.name == "Connections") conns = &n; }
     if (!objects) { rt_set_error("%s: no Objects section", path); return RT_ERR_IO; }
-    // geometry id -> the Model it is connected to ("OO" child, parent)
-    std::map<long long, const Node *> models;
+    std::map<long long, ModelInfo> models;
     for (const Node &o : objects->kids)
-        if (o.name == "Model" && !o.props.empty() && !o.props[0].ints.empty()) models[o.props[0].ints[0]] = &o;
-    std::map<long long, long long> parent_of;
+        if (o.name == "Model" && !o.props.empty() && !o.props[0].ints.empty()) models[o.props[0].ints[0]].x = read_xform(o);
+    // "OO" connections (child, parent): Model -> Model gives the node hierarchy, Geometry -> Model the meshes' owners, in this order
+    std::map<long long, std::vector<ModelInfo *> > owners;
     if (conns)
-        for (const Node &c : conns->kids)
-            if (c.name == "C" && c.props.size() >= 3 && c.props[0].str == "OO" && !c.props[1].ints.empty() && !c.props[2].ints.empty())
-                parent_of[c.props[1].ints[0]] = c.props[2].ints[0];
+        for (const Node &c : conns->kids) {
+            if (c.name != "C" || c.props.size() < 3 || c.props[0].str != "OO" || c.props[1].ints.empty() || c.props[2].ints.empty()) continue;
+            const std::map<long long, ModelInfo>::iterator parent = models.find(c.props[2].ints[0]);
+            if (parent == models.end()) continue;                 // (the scene root, id 0, and objects that are no Models: no transform)
+            const std::map<long long, ModelInfo>::iterator child = models.find(c.props[1].ints[0]);
+            if (child == models.end()) owners[c.props[1].ints[0]].push_back(&parent->second);
+            else if (child->second.parent && child->second.parent != &parent->second) child->second.two_parents = true;
+            else child->second.parent = &parent->second;
+        }
     verts.clear();
     idx.clear();
-    bool unsupported = false;
     for (const Node &o : objects->kids) {
         if (o.name != "Geometry" || o.props.size() < 3 || o.props[2].str != "Mesh") continue;
-        M34 xf = identity34();
+        const std::vector<ModelInfo *> *own = nullptr;
         if (!o.props[0].ints.empty()) {
-            std::map<long long, long long>::const_iterator p = parent_of.find(o.props[0].ints[0]);
-            if (p != parent_of.end()) {
-                std::map<long long, const Node *>::const_iterator m = models.find(p->second);
-                if (m != models.end()) {
-                    xf = model_transform(*m->second, &unsupported);
-                    // a Model whose own parent is another Model (not the scene root, id 0) has an inherited transform
-                    std::map<long long, long long>::const_iterator gp = parent_of.find(p->second);
-                    if (gp != parent_of.end() && gp->second != 0 && models.count(gp->second)) unsupported = true;
-                }
-            }
+            const std::map<long long, std::vector<ModelInfo *> >::const_iterator f = owners.find(o.props[0].ints[0]);
+            if (f != owners.end()) own = &f->second;
         }
-        if (unsupported) {
-            rt_set_error("%s: a mesh needs pivots, pre / post rotations, geometric or inherited transforms, which this reader does not apply", path);
-            return RT_ERR_UNSUPPORTED;
+        if (!own) { RT_TRY(add_geometry(o, identity34(), verts, idx)); continue; }      // connected to no Model: as it stands
+        for (const ModelInfo *m : *own) {                         // an instanced geometry: once per Model
+            M34 xf;
+            RT_TRY(world_matrix(path, *m, models.size(), xf));
+            RT_TRY(add_geometry(o, xf, verts, idx));
         }
-        RT_TRY(add_geometry(o, xf, verts, idx));
     }
     if (idx.empty()) { rt_set_error("%s: no mesh geometry with polygons", path); return RT_ERR_IO; }
     return RT_OK;

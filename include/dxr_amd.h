@@ -76,7 +76,8 @@ int rt_device_download(rt_context *ctx, void *host_dst, const void *device_src, 
 
 /* RtModel::create(ctx, filePath) (RtModel.h:13; the reference imports through Assimp, RtModel.cpp:26-27).  By extension:
  * ".fbx" -> the binary-FBX mesh reader (rt_fbx.cpp: Geometry nodes' Vertices / PolygonVertexIndex / LayerElementNormal,
- * zlib arrays, Lcl transforms of the owning Model; enough for the reference's assets/models/ground.fbx), anything else ->
+ * zlib arrays; the node hierarchy is flattened as the reference's aiProcess_PreTransformVertices does: Lcl transforms, pivots,
+ * offsets, pre / post rotations and RotationOrder down the Model parent chain, geometric transforms, instanced geometry), anything else ->
  * Wavefront OBJ.  See DESIGN.md for the vertex / primitive ordering these readers define. */
 int rt_model_create_from_file(rt_context *ctx, const char *path, rt_model **out);
 int rt_model_create_from_obj(rt_context *ctx, const char *path, rt_model **out);
@@ -448,7 +449,10 @@ int rt_dds_read_cube(const char *path, float *faces_rgba32f, size_t capacity_flo
 /* The OBJ reader behind rt_model_create_from_obj, without a device: counts first (verts / indices NULL), then data. */
 int rt_obj_read(const char *path, rt_vertex *verts, uint32_t capacity_verts, uint32_t *indices, uint32_t capacity_tris,
                 uint32_t *n_verts, uint32_t *n_tris);
-/* The binary-FBX reader behind rt_model_create_from_file, likewise */
+/* The binary-FBX reader behind rt_model_create_from_file, likewise.  The arrays are the file's meshes with the node hierarchy
+ * flattened ("FBX ingestion"): Geometry objects in file order, each once per Model it is connected to.
+ * RT_ERR_UNSUPPORTED names what is not applied (RotationOrder 6, InheritType 0 / 2 under a scaled ancestor, a singular transform,
+ * ASCII FBX); RT_ERR_IO a malformed file (parent cycle, chain deeper than 256, a Model under two Models). */
 int rt_fbx_read(const char *path, rt_vertex *verts, uint32_t capacity_verts, uint32_t *indices, uint32_t capacity_tris,
                 uint32_t *n_verts, uint32_t *n_tris);
 
