@@ -418,14 +418,19 @@ static inline void scene_build(Scene &s)
             /* the instance's world box: the exact box of its triangles' transformed vertices (not the box of the BLAS
              * box's eight transformed corners, which is up to 1.6x wider in footprint for a rotated mesh and makes a
              * third of all instance entries false ones, profiles/r04/tight_boxes.txt); min / max: order free */
+            /* ... by fmin_ / fmax_, which pass over a NaN (a transform with a NaN entry, products that overflow to inf - inf): min2 /
+             * max2 would keep whatever followed the last NaN, which is NOT order free.  An axis on which every coordinate is NaN
+             * keeps the empty box's +inf / -inf, and no slab test culls on it (tests/test_gpu_instance_transforms.py) */
             const Model &md = s.models[in.model];
             in.world = box_empty();
             for (uint32_t p = 0; p < md.ntris; p++) {
-                V3 a, bb, c;
-                tri_verts(md, p, a, bb, c);
-                box_grow(in.world, xform_point(in.m, a));
-                box_grow(in.world, xform_point(in.m, bb));
-                box_grow(in.world, xform_point(in.m, c));
+                V3 q[3];
+                tri_verts(md, p, q[0], q[1], q[2]);
+                for (int k = 0; k < 3; k++) {
+                    const V3 w = xform_point(in.m, q[k]);
+                    in.world.lo = v3(fmin_(in.world.lo.x, w.x), fmin_(in.world.lo.y, w.y), fmin_(in.world.lo.z, w.z));
+                    in.world.hi = v3(fmax_(in.world.hi.x, w.x), fmax_(in.world.hi.y, w.y), fmax_(in.world.hi.z, w.z));
+                }
             }
         }
         ib[i] = in.world;

@@ -10,7 +10,7 @@ with a candidate rule; where the two name different primit
 import numpy as np
 
 from dxrexperiments_amd import scenes
-from util import CORNELL_OBJ, random_xforms, sliver_soup
+from util import CORNELL_OBJ, HARD_FAMILIES, hard_xforms, random_xforms, sliver_soup
 
 TIE = 1e-4
 BOUND_RAYS, BOUND_SEED = 20000, 7            # the ray sets the committed bounds (tests/golden/s2_bounds.json) were measured on
@@ -34,10 +34,13 @@ def scene_models(name):
     if name == "sliver_soup":
         v, t = sliver_soup(600, seed=77)
         return [(v, t)], [(0, None)], np.arange(600)
+    if name.startswith("instances_"):            # the same mesh under the instance transforms random_xforms never makes (util.hard_xforms)
+        return [scenes.blob_mesh(seed=3, level=2)], [(0, x) for x in hard_xforms(name[len("instances_"):], 12, seed=11)], None
     raise KeyError(name)
 
 
 SCENES = ("cornell", "atrium", "instances", "terrain", "stadium_slivers", "sliver_soup")
+INSTANCE_SCENES = tuple("instances_" + f for f in HARD_FAMILIES)        # bounds of their own: tests/golden/s2_instance_bounds.json
 
 
 def load_arrays(orc, models):

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from dxrexperiments_amd import rtypes as T, scenes
-from util import ANY, CORNELL_OBJ, CULL, GOLDEN, assert_hits_equal, primary_rays, random_rays, random_xforms, triangle_soup
+from util import ANY, CORNELL_OBJ, CULL, GOLDEN, HARD_FAMILIES, assert_hits_equal, hard_xforms, primary_rays, random_rays, random_xforms, triangle_soup, world_box_of_vertices
 
 
 def test_rng_known_answers(oracle):
@@ -197,6 +197,29 @@ def test_instance_world_box_is_the_box_of_the_transformed_vertices(oracle):
         w = np.stack([((a[r, 0] * p[:, 0] + a[r, 1] * p[:, 1]) + a[r, 2] * p[:, 2]) + a[r, 3] for r in range(3)], axis=1)
         box, _ = sc.instance_info(k)
         assert np.array_equal(box, np.concatenate([w.min(axis=0), w.max(axis=0)]))
+
+
+@pytest.mark.parametrize("family", HARD_FAMILIES + ("extreme", "degenerate"))
+def test_instance_world_box_under_hard_transforms(oracle, family):
+    """... under the transforms of util.hard_xforms as well: min / max pass over a NaN coordinate (order free, as DESIGN.md section 2 says of
+    them), an axis with nothing but NaN keeps the empty box's +inf / -inf; and brute force and BVH still agree on rays through the scene"""
+    models = [scenes.blob_mesh(level=2), triangle_soup(300, seed=2, extent=1.5, size=0.4)]
+    xf = hard_xforms(family, 12, seed=5)
+    sc = oracle.Scene()
+    for v, i in models:
+        sc.add_model(v, i)
+    for k, x in enumerate(xf):
+        sc.add_instance(k % 2, x)
+    sc.add_instance(0, None)
+    sc.build()
+    for k, x in enumerate(xf):
+        box, _ = sc.instance_info(k)
+        assert np.array_equal(box, world_box_of_vertices(*models[k % 2], x), equal_nan=True), (k, box)
+        assert not np.isnan(box).any()
+    O, D = random_rays(4000, 3, [-8, -8, -8], [8, 8, 8])
+    a, b = sc.trace(O, D, flags=0, mode=0, nthreads=8), sc.trace(O, D, flags=0, mode=1, nthreads=8)
+    assert_hits_equal(a, b, "brute force vs BVH, %s" % family)
+    assert int((a["inst"] == 12).sum()) > 0
 
 
 def test_bvh_equals_brute_force(oracle):

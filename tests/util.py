@@ -68,6 +68,66 @@ def random_xforms(n, seed, spread=8.0):
     return out
 
 
+HARD_FAMILIES = ("mirror", "stretch", "squash", "shear", "small", "large", "far")       # ... whose distance from geometry is bounded (s2_truth.py)
+FAR_SHIFT = (40000.0, -25000.0, 30000.0)
+
+
+def hard_xforms(family, n, seed):
+    """Instance transforms random_xforms never makes: random_xforms(n, seed, spread=6) changed in float64, returned as fp32 [n, 12].
+    mirror (negative determinant), stretch / squash (1000:1 anisotropy either way), shear, small / large (uniform scale 1e-4 / 1e4, the
+    latter with its translation), far (translation 4 - 5 orders above the mesh's size), extreme (linear part x 1e12, 1e-12, 1e20, 1e-20 in
+    turn: the adjugate or the determinant leaves fp32's range) and degenerate (index k takes case k % 5: a zero column, a zero linear
+    part, one NaN entry, one +inf translation entry, two equal rows)."""
+    m = random_xforms(n, seed, spread=6.0).astype(np.float64).reshape(n, 3, 4)
+    L, t = m[:, :, :3], m[:, :, 3]
+    with np.errstate(over="ignore"):
+        if family == "mirror":
+            L[:, :, 0] = -L[:, :, 0]
+        elif family == "stretch":
+            L[:] = L @ np.diag([1000.0, 1.0, 1.0])
+        elif family == "squash":
+            L[:] = L @ np.diag([1.0, 1e-3, 1.0])
+        elif family == "shear":
+            L[:] = L @ np.array([[1.0, 30.0, 0.0], [0.0, 1.0, -20.0], [0.0, 0.0, 1.0]])
+        elif family == "small":
+            L *= 1e-4
+        elif family == "large":
+            L *= 1e4
+            t *= 1e4
+        elif family == "far":
+            t += np.array(FAR_SHIFT)
+        elif family == "extreme":
+            for k in range(n):
+                L[k] *= (1e12, 1e-12, 1e20, 1e-20)[k % 4]
+        elif family == "degenerate":
+            for k in range(n):
+                case = k % 5
+                if case == 0:
+                    L[k, :, 1] = 0.0
+                elif case == 1:
+                    L[k] = 0.0
+                elif case == 2:
+                    L[k, 1, 2] = np.nan
+                elif case == 3:
+                    t[k, 2] = np.inf
+                else:
+                    L[k, 2] = L[k, 0]
+        else:
+            raise KeyError(family)
+        return m.reshape(n, 12).astype(np.float32)
+
+
+def world_box_of_vertices(v, idx, m):
+    """the definition (oracle_bvh.h scene_build): the box of the triangles' transformed vertices, x' = ((m0 x + m1 y) + m2 z) + m3 in fp32,
+    by min / max that start from the empty box and pass over a NaN"""
+    p = v["position"][np.asarray(idx).reshape(-1)].astype(np.float32)
+    m = np.asarray(m, np.float32).reshape(3, 4)
+    with np.errstate(all="ignore"):
+        w = np.stack([((m[r, 0] * p[:, 0] + m[r, 1] * p[:, 1]) + m[r, 2] * p[:, 2]) + m[r, 3] for r in range(3)], axis=1)
+    inf = np.float32(np.inf)
+    return np.concatenate([np.fmin.reduce(w, axis=0, initial=inf), np.fmax.reduce(w, axis=0, initial=-inf)])
+
+
 class Pair:
     """The same scene on the oracle and on the GPU."""
 
