@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from dxrexperiments_amd import rtypes as T, scenes
+from denoise_cases import PARAM_CASES, synthetic_aovs
 from util import CORNELL_OBJ, cam_array, random_xforms, triangle_soup
 
 pytestmark = pytest.mark.gpu
@@ -84,23 +85,6 @@ def test_realtime_pipeline_instanced_with_misses(gpu, capi, oracle):
     gst = p.stats()
     for key in ("rays_secondary", "rays_shadow", "secondary_hits"):
         assert gst[key] == ost[key], key
-
-
-def synthetic_aovs(W, H, seed):
-    r = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    direct = np.zeros((H, W, 4), np.float32)
-    direct[..., 0] = 0.5 + 0.5 * np.sin(xx / 9.0)
-    direct[..., 1] = (yy // 16 % 2) * 0.8               # hard edges the bilateral weight must respect
-    direct[..., 2] = 0.3
-    direct[..., 3] = 1.0
-    ind = (r.uniform(0, 1, (H, W, 4)) ** 3).astype(np.float32)
-    ind[..., 3] = 1.0
-    return direct, ind
-
-
-PARAM_CASES = [dict(), dict(maxKernelSize=1), dict(maxKernelSize=20), dict(maxKernelSize=0), dict(debugVisualize=1), dict(debugVisualize=2),
-               dict(debugVisualize=3), dict(tonemap=0), dict(gammaCorrect=1), dict(exposure=2.5, gamma=1.8, gammaCorrect=1)]
 
 
 @pytest.mark.parametrize("over", PARAM_CASES, ids=lambda o: "-".join("%s=%s" % kv for kv in o.items()) or "defaults")
