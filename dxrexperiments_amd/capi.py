@@ -46,6 +46,9 @@ class StageWalk(C.Structure):
 STAGES = ("primary", "secondary", "shadow0", "shadow1")
 
 PIPELINE_PROGRESSIVE, PIPELINE_REALTIME = 0, 1
+WIDE_STEP_ANYHIT, WIDE_STEP_DEEP, WIDE_STEP_LDS_TOP = 1, 2, 4
+WIDE_STEP_TOP_NODES = 128          # nodes of the LDS-resident top (csrc/rt_internal.h RT_TOP_NODES)
+NODE_EMPTY, NODE_NONE = 0x7FFFFFFE, -2 ** 31
 CUBE_SEAMLESS, CUBE_FACE_CLAMP = 0, 1
 DENOISER_PARAMS = np.dtype([("exposure", "<f4"), ("gamma", "<f4"), ("tonemap", "<u4"), ("gammaCorrect", "<u4"),
                             ("maxKernelSize", "<i4"), ("debugVisualize", "<u4")])
@@ -167,6 +170,7 @@ SIGNATURES = {
     "rt_debug_math": (_i, [_p, _i, _p, _p, _p, _sz]),
     "rt_debug_sample": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _sz]),
     "rt_debug_sample_cube": (_i, [_p, _p, _u32, _u32, _p, _p, _sz]),
+    "rt_debug_wide_step": (_i, [_p, _p, _u32, _p, _p, _p, _sz, _u32, _p]),
     "rt_pipeline_set_environment_filter": (_i, [_p, _u32]),
     "rt_shard_frame_count": (_i, [_u32, _u32, _u32, C.POINTER(C.c_uint32)]),
     "rt_tile_bands": (_i, [_u32, _u32, _u32, _u32, _p, _p, _u32, C.POINTER(C.c_uint32)]),
@@ -305,6 +309,32 @@ class Context:
         out = np.empty_like(dirs)
         _check(lib().rt_debug_sample_cube(self.h, _ptr(faces), faces.shape[1], CUBE_SEAMLESS if seamless else CUBE_FACE_CLAMP,
                                           _ptr(dirs), _ptr(out), dirs.shape[0]))
+        return out
+
+    def wide_step(self, nodes, node_index, origin_tmin, dir_tbest, anyhit=False, deep=False, lds_top=False):
+        """rt_debug_wide_step: one step of the traversal engine per item, from an empty stack, on the four-wide nodes uint32[n_nodes, 16]
+        -> int32[n, 5]: node entered (NODE_EMPTY: all culled), stack pointer, the rows pushed in stack order (NODE_NONE above it).
+        lds_top: the nodes are read from the LDS-resident top, WIDE_STEP_TOP_NODES of them per launch (more are run in slices)."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 16)
+        index = np.ascontiguousarray(node_index, dtype=np.int32)
+        o = _f32(origin_tmin, (-1, 4))
+        d = _f32(dir_tbest, (-1, 4))
+        assert o.shape[0] == d.shape[0] == index.size
+        variant = (WIDE_STEP_ANYHIT if anyhit else 0) | (WIDE_STEP_DEEP if deep else 0) | (WIDE_STEP_LDS_TOP if lds_top else 0)
+        out = np.empty((index.size, 5), np.int32)
+        if not lds_top or nodes.shape[0] <= WIDE_STEP_TOP_NODES:
+            _check(lib().rt_debug_wide_step(self.h, _ptr(nodes), nodes.shape[0], _ptr(index), _ptr(o), _ptr(d), index.size, variant, _ptr(out)))
+            return out
+        if index.size and (index.min() < 0 or index.max() >= nodes.shape[0]):
+            raise RtError(-1, "rt_debug_wide_step: node index out of range")
+        for first in range(0, nodes.shape[0], WIDE_STEP_TOP_NODES):
+            sel = np.nonzero((index >= first) & (index < first + WIDE_STEP_TOP_NODES))[0]
+            if sel.size:
+                part = np.ascontiguousarray(nodes[first:first + WIDE_STEP_TOP_NODES])
+                ix, po, pd = index[sel] - np.int32(first), np.ascontiguousarray(o[sel]), np.ascontiguousarray(d[sel])
+                res = np.empty((sel.size, 5), np.int32)
+                _check(lib().rt_debug_wide_step(self.h, _ptr(part), part.shape[0], _ptr(ix), _ptr(po), _ptr(pd), sel.size, variant, _ptr(res)))
+                out[sel] = res
         return out
 
 

@@ -68,7 +68,89 @@ void launch_fast(const rt_context *ctx, bool two_level, hipStream_t st, const Sc
         k_trace_fast<STACK, false><<<rt_persistent_grid(ctx, k_trace_fast<STACK, false>, TRACE_BLOCK, src.n), TRACE_BLOCK, 0, st>>>(sc, src, sink, pool);
 }
 
+#if RT_WIDE == 4
+// rt_debug_wide_step: ONE call of the engine's wide_step per lane, on caller-supplied nodes, from an empty stack (sp = 0, where the pure-LDS
+// instantiation is legal too) -- the production STACK / BLOCK, the engine's make_inv and its prologue's copy of the nodes to LDS.
+// out: five ints per item -- the node entered (RT_NODE_EMPTY: every child culled), the new sp, the rows pushed in stack order
+// (RT_NODE_NONE in the rows above sp).
+template <bool DEEP, bool ANYHIT>
+__global__ void __launch_bounds__(TRACE_BLOCK)
+k_debug_wide_step(const WNode *nodes, uint32_t top_n, const int *__restrict__ index, const float4 *__restrict__ o, const float4 *__restrict__ d,
+                  uint32_t n, int *deep, int *__restrict__ out)
+{
+    constexpr int STACK = RT_LDS_STACK_ROWS;
+    __shared__ int smem[(STACK + RT_TOP_ROWS(TRACE_BLOCK)) * TRACE_BLOCK];
+    LaneStack<STACK, TRACE_BLOCK> st;
+    st.lds = smem + threadIdx.x;
+    st.threads = gridDim.x * TRACE_BLOCK;
+    st.deep = deep + (size_t)blockIdx.x * TRACE_BLOCK + threadIdx.x;
+    int *topl = smem + STACK * TRACE_BLOCK;
+    if (top_n != 0) {
+        const int *src_top = (const int *)nodes;
+        for (uint32_t i = threadIdx.x; i < top_n * RT_TOP_WORDS; i += TRACE_BLOCK) topl[i] = src_top[(i / RT_TOP_WORDS) * (uint32_t)(sizeof(WNode) / 4) + i % RT_TOP_WORDS];
+        __syncthreads();
+    }
+    const uint32_t i = blockIdx.x * TRACE_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const RayD r = load_ray(o, d, i);
+    const RayInv ri = make_inv(r.o, r.d);
+    for (int row = 0; row < 3; row++) st.lds[row * TRACE_BLOCK] = RT_NODE_NONE;
+    int node = index[i], sp = 0;
+    wide_step<DEEP, ANYHIT>(nodes, topl, top_n, ri, r.tmin, r.tmax, st, node, sp);
+    out[5 * (size_t)i] = node;
+    out[5 * (size_t)i + 1] = sp;
+    for (int row = 0; row < 3; row++) out[5 * (size_t)i + 2 + row] = row < sp ? st.read(row) : RT_NODE_NONE;
+}
+#endif
+
 }  // namespace
+
+extern "C" int rt_debug_wide_step(rt_context *ctx, const void *nodes, uint32_t n_nodes, const int32_t *node_index, const float *origin_tmin,
+                                  const float *dir_tbest, size_t n, uint32_t variant, int32_t *out)
+{
+#if RT_WIDE == 4
+    RT_REQUIRE(ctx && nodes && node_index && origin_tmin && dir_tbest && out, "null argument");
+    RT_REQUIRE(variant < 8u, "unknown variant bits");
+    RT_REQUIRE(n_nodes > 0 && n_nodes < (1u << 24) && n < (1u << 24), "too many nodes or items");
+    const bool lds_top = (variant & RT_WIDE_STEP_LDS_TOP) != 0;
+    if (lds_top) RT_REQUIRE(n_nodes <= RT_TOP_NODES, "the LDS-resident top holds RT_TOP_NODES nodes at most");
+    for (size_t i = 0; i < n; i++) RT_REQUIRE(node_index[i] >= 0 && (uint32_t)node_index[i] < n_nodes, "node index out of range");
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf *sb = ctx->scratch;
+    const unsigned grid = (unsigned)((n + TRACE_BLOCK - 1) / TRACE_BLOCK);
+    RT_TRY(sb[0].reserve(sizeof(WNode) * (size_t)n_nodes));
+    RT_TRY(sb[1].reserve(n * 4));
+    RT_TRY(sb[2].reserve(n * 16));
+    RT_TRY(sb[3].reserve(n * 16));
+    RT_TRY(sb[4].reserve(n * 20));
+    RT_TRY(sb[5].reserve((size_t)grid * TRACE_BLOCK * 4));          // one global stack row: a step from sp = 0 reaches none
+    HIP_TRY(hipMemcpyAsync(sb[0].p, nodes, sizeof(WNode) * (size_t)n_nodes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(sb[1].p, node_index, n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(sb[2].p, origin_tmin, n * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(sb[3].p, dir_tbest, n * 16, hipMemcpyHostToDevice, st));
+    const WNode *nd = sb[0].as<WNode>();
+    const uint32_t top_n = lds_top ? n_nodes : 0u;
+    const int *ix = sb[1].as<int>();
+    const float4 *o = sb[2].as<float4>(), *d = sb[3].as<float4>();
+    int *deep = sb[5].as<int>(), *res = sb[4].as<int>();
+    switch (variant & (RT_WIDE_STEP_ANYHIT | RT_WIDE_STEP_DEEP)) {
+    case 0: k_debug_wide_step<false, false><<<grid, TRACE_BLOCK, 0, st>>>(nd, top_n, ix, o, d, (uint32_t)n, deep, res); break;
+    case RT_WIDE_STEP_ANYHIT: k_debug_wide_step<false, true><<<grid, TRACE_BLOCK, 0, st>>>(nd, top_n, ix, o, d, (uint32_t)n, deep, res); break;
+    case RT_WIDE_STEP_DEEP: k_debug_wide_step<true, false><<<grid, TRACE_BLOCK, 0, st>>>(nd, top_n, ix, o, d, (uint32_t)n, deep, res); break;
+    default: k_debug_wide_step<true, true><<<grid, TRACE_BLOCK, 0, st>>>(nd, top_n, ix, o, d, (uint32_t)n, deep, res); break;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, sb[4].p, n * 20, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+#else
+    (void)ctx; (void)nodes; (void)n_nodes; (void)node_index; (void)origin_tmin; (void)dir_tbest; (void)n; (void)variant; (void)out;
+    rt_set_error("rt_debug_wide_step: the eight-wide build has no such entry");
+    return RT_ERR_UNSUPPORTED;
+#endif
+}
 
 int rt_launch_trace(rt_context *ctx, const rt_scene *s, const float4 *o, const float4 *d, size_t n, uint32_t ray_flags,
                     uint32_t kernel, const TraceOut &out)

@@ -41,7 +41,10 @@ struct LaneStack {
 // planes B + D; which byte is the near plane follows the sign of inv, so no min / max per axis is needed.  Hence
 //     canonical test passes on the true child box  =>  it passes on the decoded box (monotone, rt_bvh_wide.hip)
 //                                                  =>  this test passes,
-// which is all the exactness rule asks of a traversal.  (All reciprocals are finite and at most 2^16 here: steeper rays
+// which is all the exactness rule asks of a traversal -- and is held, one step at a time on inputs placed at the threshold, by
+// tests/test_wide_step_edges.py (the test infrastructure's restatement of this step against the canonical test: zero exceptions, and broken by a margin
+// of 0 or without the 1e-37) and tests/test_gpu_wide_step.py (this template, through rt_debug_wide_step, against that restatement value for
+// value).  A change to the margin, the steep threshold, the byte selection or the sort goes through both.  (All reciprocals are finite and at most 2^16 here: steeper rays
 // take the exact path inside the step.  An axis the builder could not quantise has an infinite scale and q = 0 planes:
 // A is +-inf, t(0) = fma(0, inf, B) is NaN, and max / min ignore a NaN operand -- that axis does not cull.)
 template <bool DEEP, bool ANYHIT, int STACK, int BLOCK>

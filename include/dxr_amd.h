@@ -442,6 +442,18 @@ int rt_debug_set_option(rt_context *ctx, const char *name, const char *value);
 /* test hook: device allocations of more than `bytes` bytes fail with RT_ERR_OOM as if the device were full (0: no limit) */
 int rt_debug_set_alloc_limit(size_t bytes);
 int rt_debug_sample_cube(rt_context *ctx, const float *faces_rgba32f, uint32_t size, uint32_t filter, const float *dirs, float *out, size_t n);
+/* ONE step of the traversal engine (csrc/rt_wide_step.h, the function the trace kernels call) per item, from an empty stack, on caller-supplied
+ * four-wide nodes in the 64-B layout of rt_scene_wide_read: item i steps on node node_index[i] with the ray origin_tmin[4 i ..] (origin, tmin),
+ * dir_tbest[4 i ..] (direction, the far limit of the window).  variant: RT_WIDE_STEP_ANYHIT (the unordered step; else the closest-hit one),
+ * RT_WIDE_STEP_DEEP (the instantiation whose stack continues in global rows; else the pure-LDS one), RT_WIDE_STEP_LDS_TOP (the nodes are
+ * read from the LDS-resident top: at most 128 nodes; else from global memory).  out: five int32 per item -- the node code entered (0x7FFFFFFE:
+ * every child was culled), the stack pointer after the step, and the rows pushed in stack order (INT32_MIN above the stack pointer).
+ * tests/test_gpu_wide_step.py holds it to oracle/wide_step_model.h.  RT_ERR_UNSUPPORTED in a -DRT_WIDE=8 build. */
+#define RT_WIDE_STEP_ANYHIT  1u
+#define RT_WIDE_STEP_DEEP    2u
+#define RT_WIDE_STEP_LDS_TOP 4u
+int rt_debug_wide_step(rt_context *ctx, const void *nodes, uint32_t n_nodes, const int32_t *node_index, const float *origin_tmin,
+                       const float *dir_tbest, size_t n, uint32_t variant, int32_t *out);
 /* The DDS cube-map reader behind rt_pipeline_load_environment_dds, without a device (tests run it on the reference's
  * own assets/textures/CathedralRadiance.dds): *size = edge length of mip 0; faces_rgba32f (may be NULL to query the
  * size) receives 6 x size x size x 4 floats when capacity_floats is large enough, else RT_ERR_INVALID_ARG. */

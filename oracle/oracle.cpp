@@ -29,6 +29,7 @@
 #include "oracle_shade.h"
 #include "oracle.h"
 #include "truth64.h"
+#include "wide_step_model.h"
 
 using namespace orc;
 
@@ -59,6 +60,35 @@ float orc_next_rand(uint32_t *s) { return nextRand(s); }
 void orc_round_to_half(const float *x, float *out, size_t n, int nearest)
 {
     for (size_t i = 0; i < n; i++) out[i] = round_to_half(x[i], nearest != 0);
+}
+
+/* the canonical box test, slab() of oracle_bvh.h, on n boxes (lo, hi: 3 floats each) with n rays (origin tmin, direction tmax) */
+void orc_slab_batch(const float *origin_tmin, const float *dir_tmax, const float *lo, const float *hi, size_t n, uint8_t *hit, float *entry)
+{
+    for (size_t i = 0; i < n; i++) {
+        const float *o = origin_tmin + 4 * i, *d = dir_tmax + 4 * i;
+        const RayInv ri = ray_inv(v3(o[0], o[1], o[2]), v3(d[0], d[1], d[2]));
+        float e;
+        hit[i] = slab(ri, lo + 3 * i, hi + 3 * i, o[3], d[3], &e) ? 1 : 0;
+        if (entry) entry[i] = e;
+    }
+}
+
+/* wide_step_model.h on n items: item i steps on node index[i] of nodes (16 words each).  mask / steep: one byte per item, dist: 4 floats,
+ * closest / anyhit: 5 ints (node entered, sp, rows pushed in stack order).  margin_scale / tiny: 2^-20 and 1e-37 are the product's. */
+int orc_wide_step_model(const uint32_t *nodes, uint32_t n_nodes, const int32_t *index, const float *origin_tmin, const float *dir_tbest, size_t n,
+                        float margin_scale, float tiny, uint8_t *mask, uint8_t *steep, float *dist, int32_t *closest, int32_t *anyhit)
+{
+    for (size_t i = 0; i < n; i++) if (index[i] < 0 || (uint32_t)index[i] >= n_nodes) return -1;
+    for (size_t i = 0; i < n; i++) {
+        const WideStepOut r = wide_step_model(nodes + 16 * (size_t)index[i], origin_tmin + 4 * i, dir_tbest + 4 * i, margin_scale, tiny);
+        mask[i] = (uint8_t)r.mask;
+        steep[i] = (uint8_t)r.steep;
+        memcpy(dist + 4 * i, r.dist, 16);
+        memcpy(closest + 5 * i, r.closest, 20);
+        memcpy(anyhit + 5 * i, r.anyhit, 20);
+    }
+    return 0;
 }
 
 void orc_math_batch(int fn, const float *x, const float *y, float *out, size_t n)

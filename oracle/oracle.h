@@ -29,6 +29,9 @@ typedef struct orc_render_stats {
 uint32_t orc_init_rand(uint32_t v0, uint32_t v1);
 float    orc_next_rand(uint32_t *s);
 void     orc_round_to_half(const float *x, float *out, size_t n, int nearest);      /* binary32 -> binary16 -> binary32 */
+void     orc_slab_batch(const float *origin_tmin, const float *dir_tmax, const float *lo, const float *hi, size_t n, uint8_t *hit, float *entry);
+int      orc_wide_step_model(const uint32_t *nodes, uint32_t n_nodes, const int32_t *index, const float *origin_tmin, const float *dir_tbest, size_t n,
+                             float margin_scale, float tiny, uint8_t *mask, uint8_t *steep, float *dist, int32_t *closest, int32_t *anyhit);
 void     orc_math_batch(int fn, const float *x, const float *y, float *out, size_t n);
 void     orc_sample_batch(int kind, const uint32_t *seeds, const float *vec3_in, float exponent,
                           float *vec3_out, float *pdf_brdf, uint32_t *seeds_out, size_t n);

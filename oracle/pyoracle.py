@@ -54,6 +54,9 @@ def lib():
         L.orc_next_rand.argtypes = [C.POINTER(C.c_uint32)]
         L.orc_math_batch.argtypes = [C.c_int, p, p, p, C.c_size_t]
         L.orc_sample_batch.argtypes = [C.c_int, p, p, C.c_float, p, p, p, C.c_size_t]
+        L.orc_slab_batch.argtypes = [p, p, p, p, C.c_size_t, p, p]
+        L.orc_slab_batch.restype = None
+        L.orc_wide_step_model.argtypes = [p, C.c_uint32, p, p, p, C.c_size_t, C.c_float, C.c_float, p, p, p, p, p]
         L.orc_fresnel.argtypes = [p, p, p, p]
         L.orc_sample_cube.argtypes = [p, C.c_int, p, p, C.c_size_t]
         L.orc_set_cube_seamless.argtypes = [C.c_int]
@@ -125,6 +128,45 @@ def sample(kind, seeds, vecs, exponent=0.0):
     so = np.empty(n, np.uint32)
     lib().orc_sample_batch(SAMPLE[kind], _ptr(seeds), _ptr(vecs), exponent, _ptr(out), _ptr(pb), _ptr(so), n)
     return out, pb, so
+
+
+def slab_batch(origin_tmin, dir_tmax, lo, hi):
+    """the canonical box test (slab() of oracle_bvh.h) of ray i on box i -> (hit bool[n], entry float32[n])"""
+    o = _f32(origin_tmin).reshape(-1, 4)
+    d = _f32(dir_tmax).reshape(-1, 4)
+    lo = _f32(lo).reshape(-1, 3)
+    hi = _f32(hi).reshape(-1, 3)
+    n = o.shape[0]
+    assert d.shape[0] == lo.shape[0] == hi.shape[0] == n
+    hit = np.empty(n, np.uint8)
+    entry = np.empty(n, np.float32)
+    lib().orc_slab_batch(_ptr(o), _ptr(d), _ptr(lo), _ptr(hi), n, _ptr(hit), _ptr(entry))
+    return hit != 0, entry
+
+
+WIDE_NODE_NONE, WIDE_NODE_EMPTY = -2 ** 31, 0x7FFFFFFE
+WIDE_MARGIN_SCALE, WIDE_MARGIN_TINY = 2.0 ** -20, 1e-37
+
+
+def wide_step_model(nodes, node_index, origin_tmin, dir_tbest, margin_scale=WIDE_MARGIN_SCALE, tiny=WIDE_MARGIN_TINY):
+    """wide_step_model.h: one step of the product's traversal engine on four-wide nodes uint32[n_nodes, 16], from an empty stack.
+    -> dict(mask uint8[n] (bit k: slot k kept), steep bool[n] (the exact path), dist float32[n, 4] (entry distances, +inf where culled),
+    closest / anyhit int32[n, 5]: node entered (WIDE_NODE_EMPTY: none), stack pointer, rows pushed in stack order (WIDE_NODE_NONE above it)).
+    margin_scale / tiny exist so that the tests can show what a smaller margin would lose; the product has no such knob."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 16)
+    index = np.ascontiguousarray(node_index, dtype=np.int32)
+    o = _f32(origin_tmin).reshape(-1, 4)
+    d = _f32(dir_tbest).reshape(-1, 4)
+    n = index.size
+    assert o.shape[0] == d.shape[0] == n
+    mask = np.empty(n, np.uint8); steep = np.empty(n, np.uint8)
+    dist = np.empty((n, 4), np.float32)
+    closest = np.empty((n, 5), np.int32); anyhit = np.empty((n, 5), np.int32)
+    rc = lib().orc_wide_step_model(_ptr(nodes), nodes.shape[0], _ptr(index), _ptr(o), _ptr(d), n, margin_scale, tiny,
+                                   _ptr(mask), _ptr(steep), _ptr(dist), _ptr(closest), _ptr(anyhit))
+    if rc != 0:
+        raise ValueError("orc_wide_step_model: node index out of range")
+    return dict(mask=mask, steep=steep != 0, dist=dist, closest=closest, anyhit=anyhit)
 
 
 def fresnel(I, N, f0):
