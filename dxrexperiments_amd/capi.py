@@ -228,7 +228,7 @@ def device_count():
 
 
 def wide_layout():
-    """(children per traversal node, bytes per node) of the loaded library: (4, 64), or (8, 128) for a -DRT_WIDE=8 build"""
+    """(children per traversal node, bytes per node) of the loaded library: (4, 64)"""
     w, b = C.c_uint32(), C.c_uint32()
     _check(lib().rt_wide_layout_info(C.byref(w), C.byref(b)))
     return w.value, b.value
@@ -447,8 +447,7 @@ class Scene:
         return off, boxes, rec
 
     def wide_read(self, which=0):
-        """The production traversal layout: (nodes uint32[n, 16] (64-B four-wide nodes, raw words; [n, 32] from a library built
-        with -DRT_WIDE=8), root_code, records float32[m, 12] (BLAS triangle records; empty for the TLAS))."""
+        """The production traversal layout: (nodes uint32[n, 16] (64-B four-wide nodes, raw words), root_code, records float32[m, 12] (BLAS triangle records; empty for the TLAS))."""
         n, root, m = C.c_uint32(), C.c_int32(), C.c_uint32()
         _check(lib().rt_scene_wide_info(self.h, which, C.byref(n), C.byref(root), C.byref(m)))
         nodes = np.empty((n.value, wide_layout()[1] // 4), np.uint32)

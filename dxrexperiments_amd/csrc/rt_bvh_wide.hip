@@ -1,33 +1,29 @@
-// rt_bvh_wide.hip -- the eight-wide, quantised traversal layout (WNode, rt_internal.h).
+// rt_bvh_wide.hip -- the four-wide, quantised traversal layout (WNode, rt_internal.h).
 //
 // Input: a binary tree over the sorted leaves (the PLOC tree of rt_bvh_ploc.hip, or the canonical LBVH for a TLAS,
-// tiny meshes and option fast_bvh=lbvh).  Output: nodes with up to EIGHT children in one 128-B-aligned record of which the
-// traversal reads the first 96 B.  Why eight (round 3, profiles/r03/slab_fetch.txt): the L2 line and every fabric / HBM
-// request are 128 B, so a 64-B node already moved 128 B per miss (TCC_EA0_RDREQ_128B = 99.7 % of the reads on the 10 M
-// triangle scene); from HBM a lane's 128-B block costs exactly what its 64-B half costs (291 vs 292 ns per wave step per
-// CU), from the Infinity Cache 96 B of one block cost 1.19x a 64-B line (128 B: 1.57x) -- and a tree of eight-wide nodes
-// is a third shallower, so a ray makes a third fewer dependent fetches.  Child boxes are quantised to one byte per plane
-// on a power-of-two grid anchored at the node's own box: origin, three scale exponents, 48 plane bytes and eight child
-// codes are 96 B.
+// tiny meshes and option fast_bvh=lbvh).  Output: nodes with up to RT_WIDE = FOUR children in one 64-B line.  Child boxes
+// are quantised to one byte per plane on a power-of-two grid anchored at the node's own box: origin, three scales,
+// 24 plane bytes and four child codes are 64 B.  (Eight children in a 128-B record of which the traversal reads 96 B --
+// the L2 line and every fabric / HBM request are 128 B, profiles/r03/slab_fetch.txt, and the tree is a third shallower --
+// was round 3's experiment: a third fewer steps, each nearly twice the arithmetic, 29 - 40 % slower;
+// profiles/r03/wide8_experiment.md, experiments/r03_wide8.patch.  The code below is written in terms of RT_WIDE, and the
+// bounds it takes for the growth of a level -- eight times the level before -- hold for either width.)
 //
 // Collapse: breadth first, two launches per level and no host round trip inside a batch of levels (rt_level_scan.h).  A
-// frontier element is a binary node that becomes a wide node: its two children are taken, and while fewer than eight, the
+// frontier element is a binary node that becomes a wide node: its two children are taken, and while fewer than RT_WIDE, the
 // child with the largest surface that is not a leaf is replaced by its own two children (surface-area greedy, as in Wald
 // et al. 2008 / Ylitie et al. 2017).  Node numbers come from prefix sums (deterministic), level after level, so the array
 // is in breadth-first order and its first RT_TOP_NODES entries are the LDS-resident top of the traversal kernels; the
 // internal children of a node have consecutive numbers in slot order.
 //
-// Slots: the traversal visits the hit children of a node in the order of (slot XOR direction octant) and never sorts by
-// distance, so the builder places the children (Ylitie et al. 2017, section 3.3): slot s stands for the box diagonal with
-// sign +1 on the axes whose bit is set in s, the cost of putting child c there is dot(centre(c) - centre(node), diagonal(s)),
-// and the (child, slot) pairs are fixed greedily, dearest first.  A ray whose direction is negative on the axes in `oct`
-// then meets slot `oct` first and slot `7 - oct` last.
+// Slots: the children are packed at the front, larger surface first.  Any-hit rays visit the hit children in slot order
+// (the likelier occluder first), closest-hit rays sort them by entry distance (rt_wide_step.h).
 //
 // Exactness: plane = fma(q, scale, origin) is evaluated here with the same expression the traversal uses; every lo
 // plane is stepped down and every hi plane up until the decoded box CONTAINS the child's true box.  The slab test is
 // monotone under box inclusion (DESIGN.md "Exactness rule"), so culling against the decoded boxes never loses a
 // candidate the canonical definition accepts.  An axis that cannot be quantised at all (non-finite or overflowing
-// extents: huge instance boxes, NaN / inf vertices) gets the scale exponent 255 and q = 0 planes: the decoded planes are
+// extents: huge instance boxes, NaN / inf vertices) gets an infinite scale and q = 0 planes: the decoded planes are
 // NaN, which every slab test here ignores, i.e. that axis never culls -- slower, never wrong.
 #include "rt_internal.h"
 
@@ -140,33 +136,6 @@ __device__ __forceinline__ uint32_t expand_node(const TreeView &t, uint32_t b, u
     // (Filling the slots that are still free with the halves of multi-triangle leaves was measured on the four-wide layout:
     // 3 % fewer triangle tests, but more leaf visits, frame 2.67 -> 2.83 ms.)
     for (int k = 0; k < RT_WIDE; k++) kid[k] = NO_KID;
-#if RT_WIDE == 8
-    // slot assignment: greedy over (child, slot) pairs, dearest first; ties and NaN centres fall to the first free pair
-    const Box6 nb = t.box[b];
-    float cx[RT_WIDE], cy[RT_WIDE], cz[RT_WIDE];
-    for (int k = 0; k < nk; k++) {
-        const Box6 cb = t.box[open[k]];
-        cx[k] = (cb.lo[0] + cb.hi[0]) - (nb.lo[0] + nb.hi[0]);
-        cy[k] = (cb.lo[1] + cb.hi[1]) - (nb.lo[1] + nb.hi[1]);
-        cz[k] = (cb.lo[2] + cb.hi[2]) - (nb.lo[2] + nb.hi[2]);
-    }
-    uint32_t free_kids = (1u << nk) - 1u, free_slots = (1u << RT_WIDE) - 1u;
-    for (int round = 0; round < nk; round++) {
-        int bc = -1, bs = -1;
-        float best = 0.0f;
-        for (int c = 0; c < nk; c++) {
-            if (!((free_kids >> c) & 1u)) continue;
-            for (int sl = 0; sl < RT_WIDE; sl++) {
-                if (!((free_slots >> sl) & 1u)) continue;
-                const float cost = ((sl & 1) ? cx[c] : -cx[c]) + ((sl & 2) ? cy[c] : -cy[c]) + ((sl & 4) ? cz[c] : -cz[c]);
-                if (bc < 0 || cost > best) { best = cost; bc = c; bs = sl; }       // (a NaN cost never beats anything)
-            }
-        }
-        kid[bs] = open[bc];
-        free_kids &= ~(1u << bc);
-        free_slots &= ~(1u << bs);
-    }
-#else
     // packed at the front, larger surface first (insertion sort, stable): any-hit rays walk in slot order
     float ar[RT_WIDE];
     for (int k = 0; k < nk; k++) { ar[k] = box_area(t.box[open[k]]); kid[k] = open[k]; }
@@ -175,7 +144,6 @@ __device__ __forceinline__ uint32_t expand_node(const TreeView &t, uint32_t b, u
             const float ta = ar[j]; ar[j] = ar[j - 1]; ar[j - 1] = ta;
             const uint32_t tk = kid[j]; kid[j] = kid[j - 1]; kid[j - 1] = tk;
         }
-#endif
     uint32_t cnt = 0;
     for (int k = 0; k < RT_WIDE; k++)
         if (kid[k] != NO_KID && !t.is_leaf(kid[k])) cnt++;
@@ -331,7 +299,6 @@ __device__ __forceinline__ void emit_node(const TreeView &t, uint32_t b, const u
     Box6 cb[RT_WIDE];
     int code[RT_WIDE];
     uint32_t valid = 0;
-    const uint32_t child_base = next_level_base + next;
     for (int k = 0; k < RT_WIDE; k++) {
         const uint32_t id = kid[k];
         code[k] = RT_NODE_NONE;
@@ -345,7 +312,6 @@ __device__ __forceinline__ void emit_node(const TreeView &t, uint32_t b, const u
             next++;
         }
     }
-    uint32_t expo[3];
     float scale[3];
     unsigned long long lo8[3], hi8[3];
     for (int a = 0; a < 3; a++) {
@@ -360,33 +326,18 @@ __device__ __forceinline__ void emit_node(const TreeView &t, uint32_t b, const u
             ok = s < 1.0e38f && quantise_axis(cb, valid, a, nb.lo[a], s, lo8[a], hi8[a]);
             if (!ok) s = s * 2.0f;                      // rounding in fma left the last step short: coarser grid
         }
-        expo[a] = (__float_as_uint(s) >> 23) & 0xffu;
         scale[a] = s;
         if (!ok) {
-            // not quantisable (non-finite or overflowing extents): an infinite scale (exponent 255) with q = 0 planes --
+            // not quantisable (non-finite or overflowing extents): an infinite scale with q = 0 planes --
             // fma(0, inf, origin) is NaN, which the slab tests ignore: this axis never culls
-            expo[a] = 255u; scale[a] = __builtin_inff(); lo8[a] = 0; hi8[a] = 0;
+            scale[a] = __builtin_inff(); lo8[a] = 0; hi8[a] = 0;
         }
     }
     WNode w;
-#if RT_WIDE == 8
-    w.q0 = make_float4(nb.lo[0], nb.lo[1], nb.lo[2], __uint_as_float(expo[0] | (expo[1] << 8) | (expo[2] << 16) | (valid << 24)));
-    w.q1 = make_float4(__uint_as_float((uint32_t)lo8[0]), __uint_as_float((uint32_t)(lo8[0] >> 32)), __uint_as_float((uint32_t)hi8[0]), __uint_as_float((uint32_t)(hi8[0] >> 32)));
-    w.q2 = make_float4(__uint_as_float((uint32_t)lo8[1]), __uint_as_float((uint32_t)(lo8[1] >> 32)), __uint_as_float((uint32_t)hi8[1]), __uint_as_float((uint32_t)(hi8[1] >> 32)));
-    w.q3 = make_float4(__uint_as_float((uint32_t)lo8[2]), __uint_as_float((uint32_t)(lo8[2] >> 32)), __uint_as_float((uint32_t)hi8[2]), __uint_as_float((uint32_t)(hi8[2] >> 32)));
-    w.q4 = make_float4(__int_as_float(code[0]), __int_as_float(code[1]), __int_as_float(code[2]), __int_as_float(code[3]));
-    w.q5 = make_float4(__int_as_float(code[4]), __int_as_float(code[5]), __int_as_float(code[6]), __int_as_float(code[7]));
-    // not read by the traversal: the first internal child (they are consecutive in slot order), the internal-slot mask, the binary node this came from
-    w.q6 = make_float4(__uint_as_float(internal ? child_base : 0u), __uint_as_float(internal), __uint_as_float(b), 0.0f);
-    w.q7 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    (void)scale;
-#else
-    (void)expo; (void)child_base;
     w.q0 = make_float4(nb.lo[0], nb.lo[1], nb.lo[2], scale[0]);
     w.q1 = make_float4(__uint_as_float((uint32_t)lo8[0]), __uint_as_float((uint32_t)hi8[0]), __uint_as_float((uint32_t)lo8[1]), __uint_as_float((uint32_t)hi8[1]));
     w.q2 = make_float4(__uint_as_float((uint32_t)lo8[2]), __uint_as_float((uint32_t)hi8[2]), scale[1], scale[2]);
     w.q3 = make_float4(__int_as_float(code[0]), __int_as_float(code[1]), __int_as_float(code[2]), __int_as_float(code[3]));
-#endif
     out[node_index] = w;
 }
 
@@ -580,7 +531,7 @@ int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, uint32_t n, uint32_t root,
         if (rc != RT_OK) break;
         bv.wide_n = wide_n;
         bv.root_code = 0;
-        bv.fast_depth = (RT_WIDE - 1) * levels;        // a step leaves at most seven siblings behind
+        bv.fast_depth = (RT_WIDE - 1) * levels;        // a step leaves at most three siblings behind
     } while (0);
     own.release();
     return rc;

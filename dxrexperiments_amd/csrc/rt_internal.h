@@ -100,28 +100,10 @@ struct DevBuf {
 // traversal kernels).  Children are packed at the front, larger surface first (any-hit rays walk unordered and try the
 // likelier occluder first); closest-hit rays sort the hit children by entry distance.  A scale of +inf (with q = 0 planes)
 // marks an axis the builder could not quantise: its planes decode to NaN and never cull.
-//
-// RT_WIDE = 8 (build option -DRT_WIDE=8; round 3's experiment, measured SLOWER and kept reproducible: DESIGN.md section 4,
-// profiles/r03/wide8_experiment.md): EIGHT children in one 128-B-aligned record of which the traversal reads 96 B,
-//   q0 = origin.xyz meta      meta = ex | ey << 8 | ez << 16 | valid << 24: biased exponents of the three scales (255: not
-//                             quantised) and the mask of the slots in use
-//   q1 = lo.x[0..3] lo.x[4..7] hi.x[0..3] hi.x[4..7]    q2, q3 = the same for y, z    q4 = code[0..3]    q5 = code[4..7]
-//   q6 = first internal child, internal-slot mask, source binary node, 0 (inspection only)    q7 = 0
-// The internal children of a node are consecutive in slot order.  Slots: the builder puts the child that lies towards
-// the (+,+,+) corner of the node in slot 7, towards (-,-,-) in slot 0, ... so that (slot XOR direction octant) ascending is
-// a front-to-back order and the traversal never sorts by distance (Ylitie, Karras, Laine 2017).
-#ifndef RT_WIDE
-#define RT_WIDE 4
-#endif
-#if RT_WIDE == 8
-struct __attribute__((aligned(128))) WNode { float4 q0, q1, q2, q3, q4, q5, q6, q7; };
-#define RT_NODE_SHIFT 7               // log2(sizeof(WNode))
-#define RT_TOP_WORDS 24               // ints of a node kept in LDS (the part the traversal reads)
-#else
+#define RT_WIDE 4                     // children of a node (the eight-wide layout of round 3, measured slower: experiments/r03_wide8.patch)
 struct WNode { float4 q0, q1, q2, q3; };
-#define RT_NODE_SHIFT 6
-#define RT_TOP_WORDS 16
-#endif
+#define RT_NODE_SHIFT 6               // log2(sizeof(WNode))
+#define RT_TOP_WORDS 16               // ints of a node kept in LDS: all of it
 #define RT_NODE_NONE ((int)0x80000000)
 
 // One triangle in leaf order: the three ORIGINAL vertex positions (so that the
@@ -168,12 +150,7 @@ struct SceneDev {
 };
 
 #ifndef RT_TOP_NODES
-#if RT_WIDE == 8
-#define RT_TOP_NODES  80              // nodes of the LDS-resident top, 96 B each (the part of a node the traversal reads): 7.5 KiB of
-                                      //   LDS per 256-thread block; levels 0 .. 2 of an eight-wide tree have at most 73 nodes
-#else
-#define RT_TOP_NODES  128             // 8 KiB (with four-wide nodes the size hardly matters: 32 .. 192 nodes all within 1 %)
-#endif
+#define RT_TOP_NODES  128             // nodes of the LDS-resident top: 8 KiB per 256-thread block (the size hardly matters: 32 .. 192 nodes all within 1 %)
 #endif
 #define RT_TOP_ROWS(BLOCK) ((RT_TOP_NODES * RT_TOP_WORDS + (BLOCK) - 1) / (BLOCK))      // LDS rows (of BLOCK ints) the top table takes
 

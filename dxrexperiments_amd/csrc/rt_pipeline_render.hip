@@ -101,7 +101,7 @@ float free_radius(rt_pipeline *p, const PipeDev &pd, const float lp[3])
 // The shadow cache of the coming launches (ShadowCacheDev): single-level scenes only (an entry is an index into the one sorted
 // triangle array); the table is cleared when the scene has changed (an index must stay inside the array), its directional cells
 // span the bounding sphere of the model, its basis follows the frame's light (entries of another direction are merely stale).
-int prepare_shadow_cache(rt_pipeline *p, const rt_per_frame_constants &pfc, const LightRays &lr)
+int prepare_shadow_cache(rt_pipeline *p, const LightRays &lr)
 {
     p->shadow_cache_dev = ShadowCacheDev{};
     const rt_scene *s = p->scene;
@@ -176,16 +176,15 @@ int prepare_shadow_cache(rt_pipeline *p, const rt_per_frame_constants &pfc, cons
         c.va[3] -= p->shadow_cache_centre[i] * c.va[i];
         c.lp[i] = lr.point_pos[i];
     }
-    (void)pfc;
     p->shadow_cache_dev = c;
     return RT_OK;
 }
 
-// The scene as a set of n_frames frames over `cap` pixel slots walks it: which kernels (LDS stack rows) and the global stack rows
+// The scene as a set of n_frames frames walks it: which kernels (LDS stack rows) and the global stack rows
 // behind them -- (tree bound - LDS rows) x 4 B per thread of the largest launch, and the primary stage of a single-level scene runs
 // one thread per pixel slot: 4.3 GB for 20 frames of 1080p.  Insurance that is never touched on the bench scene, but an allocation:
 // rt_pipeline_reserve_batch makes it too (round 4: on some boxes that hipMalloc took 126 ms of the first set's render() call).
-int scene_for_set(rt_pipeline *p, uint32_t n_frames, size_t cap, SceneDev *out, bool *sets_kernels = nullptr)
+int scene_for_set(rt_pipeline *p, uint32_t n_frames, SceneDev *out, bool *sets_kernels = nullptr)
 {
     rt_context *ctx = p->ctx;
     const bool seven_waves_always = ctx->opt_seven_waves_always;      // (experiment: single frames on the sets' kernels)
@@ -194,7 +193,6 @@ int scene_for_set(rt_pipeline *p, uint32_t n_frames, size_t cap, SceneDev *out, 
     // (round 5: rows for the threads of the PERSISTENT launches only -- at most eight 256-thread workgroups per CU fit their LDS, sixteen
     // is the option's limit; the one-tile-per-wave primary launch, one thread per pixel slot, keeps none: PipeDev::retry)
     const size_t resident = (size_t)ctx->cu_count * (ctx->blocks_per_cu_override > (uint32_t)RT_RESIDENT_BLOCKS_PER_CU ? ctx->blocks_per_cu_override : (uint32_t)RT_RESIDENT_BLOCKS_PER_CU) * PBLOCK;      // (rt_persistent_grid clamps its launches to the same count)
-    (void)cap;
     if (sets_kernels) *sets_kernels = set_rows;
     return rt_scene_dev_for_launch(ctx, p->scene, set_rows ? RT_LDS_STACK_ROWS_SETS : rt_lds_stack_rows(ctx), resident, out);
 }
@@ -257,7 +255,7 @@ static int render_region(rt_pipeline *p, uint32_t width, uint32_t height, uint32
     PipeDev pd;
     // (threads of the largest launch: the primary stage runs one thread per pixel slot, the persistent stages fewer)
     bool set_rows = false;
-    RT_TRY(scene_for_set(p, n_frames, cap, &pd.sc, &set_rows));
+    RT_TRY(scene_for_set(p, n_frames, &pd.sc, &set_rows));
     pd.pfc = frames[0];
     pd.n_frames = n_frames; pd.fcap = fcap;
     pd.pfcs = nullptr; pd.frame_lights = nullptr;
@@ -269,7 +267,7 @@ static int render_region(rt_pipeline *p, uint32_t width, uint32_t height, uint32
         pd.point_free = free_on ? free_radius(p, pd, lp0) : 0.0f;
     }
     if (ao_view) p->shadow_cache_dev = ShadowCacheDev{};
-    else RT_TRY(prepare_shadow_cache(p, frames[0], light_rays(1u, frames[0])));
+    else RT_TRY(prepare_shadow_cache(p, light_rays(1u, frames[0])));
     if (n_frames > 1) {
         // the batch's constants and light rays go to device memory: kernels index them by the frame of a slot
         const size_t cb = sizeof(rt_per_frame_constants) * RT_MAX_BATCH, lb = sizeof(LightRays) * RT_MAX_BATCH;
@@ -577,10 +575,10 @@ int rt_pipeline_reserve_batch(rt_pipeline *p, uint32_t width, uint32_t height, u
     if (frames > 1) RT_TRY(p->batch_consts.reserve((sizeof(rt_per_frame_constants) + sizeof(LightRays)) * RT_MAX_BATCH));
     if (p->scene && p->scene->built) {                 // the traversal kernels' global stack rows and the shadow cache's table as well
         SceneDev sc;
-        RT_TRY(scene_for_set(p, frames, cap, &sc));
+        RT_TRY(scene_for_set(p, frames, &sc));
         LightRays only_allocate = no_light_rays();
         only_allocate.on = 0xffffffffu;
-        RT_TRY(prepare_shadow_cache(p, p->pfc, only_allocate));
+        RT_TRY(prepare_shadow_cache(p, only_allocate));
         p->shadow_cache_dev = ShadowCacheDev{};
     }
     return RT_OK;

@@ -68,7 +68,6 @@ void launch_fast(const rt_context *ctx, bool two_level, hipStream_t st, const Sc
         k_trace_fast<STACK, false><<<rt_persistent_grid(ctx, k_trace_fast<STACK, false>, TRACE_BLOCK, src.n), TRACE_BLOCK, 0, st>>>(sc, src, sink, pool);
 }
 
-#if RT_WIDE == 4
 // rt_debug_wide_step: ONE call of the engine's wide_step per lane, on caller-supplied nodes, from an empty stack (sp = 0, where the pure-LDS
 // instantiation is legal too) -- the production STACK / BLOCK, the engine's make_inv and its prologue's copy of the nodes to LDS.
 // out: five ints per item -- the node entered (RT_NODE_EMPTY: every child culled), the new sp, the rows pushed in stack order
@@ -101,14 +100,12 @@ k_debug_wide_step(const WNode *nodes, uint32_t top_n, const int *__restrict__ in
     out[5 * (size_t)i + 1] = sp;
     for (int row = 0; row < 3; row++) out[5 * (size_t)i + 2 + row] = row < sp ? st.read(row) : RT_NODE_NONE;
 }
-#endif
 
 }  // namespace
 
 extern "C" int rt_debug_wide_step(rt_context *ctx, const void *nodes, uint32_t n_nodes, const int32_t *node_index, const float *origin_tmin,
                                   const float *dir_tbest, size_t n, uint32_t variant, int32_t *out)
 {
-#if RT_WIDE == 4
     RT_REQUIRE(ctx && nodes && node_index && origin_tmin && dir_tbest && out, "null argument");
     RT_REQUIRE(variant < 8u, "unknown variant bits");
     RT_REQUIRE(n_nodes > 0 && n_nodes < (1u << 24) && n < (1u << 24), "too many nodes or items");
@@ -145,11 +142,6 @@ extern "C" int rt_debug_wide_step(rt_context *ctx, const void *nodes, uint32_t n
     HIP_TRY(hipMemcpyAsync(out, sb[4].p, n * 20, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RT_OK;
-#else
-    (void)ctx; (void)nodes; (void)n_nodes; (void)node_index; (void)origin_tmin; (void)dir_tbest; (void)n; (void)variant; (void)out;
-    rt_set_error("rt_debug_wide_step: the eight-wide build has no such entry");
-    return RT_ERR_UNSUPPORTED;
-#endif
 }
 
 int rt_launch_trace(rt_context *ctx, const rt_scene *s, const float4 *o, const float4 *d, size_t n, uint32_t ray_flags,

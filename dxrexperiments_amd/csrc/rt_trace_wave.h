@@ -11,7 +11,7 @@
 //     most of a wave's 64 lanes parked while the longest ray finishes.  (Round 6: an any-hit
 //     walk over a source with cached first candidates tests a new ray's candidate at the
 //     refill, goes round until the wave is full, and -- while its rays are short-lived --
-//     waits for 32 / 40 free lanes before it starts: RT_REFILL_TESTS, RT_REFILL_ENTER_TESTS*);
+//     waits for 32 / 48 free lanes before it starts: REFILL_TESTS below, RT_REFILL_ENTER_TESTS*);
 //   * "while-while" order with a straggler exit: lanes walk internal nodes until they
 //     stand on a leaf; once those still walking are fewer than half of those waiting,
 //     the wave turns to the leaves, so the (short) triangle code is not serialised
@@ -34,10 +34,9 @@
 // so the visiting order, leaf collapsing and ray-to-lane assignment used here cannot
 // change any result bit.
 //
-// What was measured and is NOT here (each bit-exact, each slower or flat; the code of every one is the patch
-// dxrexperiments_amd/csrc/experiments/r03_traversal_experiments.patch, the numbers are under profiles/r03/): eight-wide 128-B nodes
-// (experiments/rt_wide8_step.h, -DRT_WIDE=8), splitting the last rays of a launch over idle lanes, touching the node
-// that will be popped next, the tops of the two most-instanced BLASes in LDS, packed-fp32 plane arithmetic, a
+// What was measured and is NOT here (each bit-exact, each slower or flat; the code is under experiments/ -- eight-wide 128-B nodes:
+// r03_wide8.patch, the rest: r03_traversal_experiments.patch -- the numbers under profiles/r03/): splitting the last rays of a launch
+// over idle lanes, touching the node that will be popped next, the tops of the two most-instanced BLASes in LDS, packed-fp32 plane arithmetic, a
 // three-exchange sort, and the instrumentation builds that counted lanes and timed waves from the inside.
 #pragma once
 
@@ -88,12 +87,6 @@ RT_DEV v4f ldg16(const void *base, size_t byte_off)
 #define RT_POOL_GROUPS 32u              // chunk counters per traversal launch (8: 3.08, 32: 3.07, 128: 3.09, 512: 3.12 ms; static: 3.21)
 #endif
 #define RT_POOL_STRIDE 32u              // words between two counters: one 128-B L2 line each
-#ifndef RT_SENTINEL_INLINE
-#define RT_SENTINEL_INLINE 1            // two-level walks leave a BLAS inside the node loop (round 4: the 4096-instance frame 4.70 -> 4.60 ms, profiles/r04/c4_variants.txt)
-#endif
-#ifndef RT_POOL_XCD
-#define RT_POOL_XCD 1                   // any-hit launches: every XCD works through one contiguous eighth of the queue (then helps its neighbours)
-#endif
 #ifndef RT_REFILL_RAYS_PER_PASS
 #define RT_REFILL_RAYS_PER_PASS 28u     // "loading rays is the work": the wave has loaded more rays than this per pass of its outer loop (refill, node loop, leaf phase)
 #endif
@@ -108,12 +101,6 @@ RT_DEV v4f ldg16(const void *base, size_t byte_off)
 #endif
 #ifndef RT_REFILL_STOP_TESTS_SETS
 #define RT_REFILL_STOP_TESTS_SETS 24
-#endif
-#ifndef RT_REFILL_TESTS_TWO_LEVEL
-#define RT_REFILL_TESTS_TWO_LEVEL 1     // ... in two-level walks too (the candidate is tested in its instance's space)
-#endif
-#ifndef RT_REFILL_TESTS
-#define RT_REFILL_TESTS 1               // (round 6) a new shadow ray's cached candidate is tested at the refill, and the refill repeats until the wave is full
 #endif
 #ifndef RT_EXIT_K
 #define RT_EXIT_K 1                     // leave the node loop once (lanes still on internal nodes) * K < lanes waiting on a leaf
@@ -225,9 +212,7 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
     uint32_t next_chunk = blockIdx.x * (BLOCK / 64) + threadIdx.x / 64;   // wave-uniform
     const uint32_t n_groups = gridDim.x < RT_POOL_GROUPS ? gridDim.x : RT_POOL_GROUPS;
     const uint32_t pool_group = blockIdx.x % n_groups;
-#if RT_POOL_XCD
-    uint32_t xcd_steal = 0;          // wave-uniform: how many XCDs' eighths of the queue this wave has seen run dry
-#endif
+    uint32_t xcd_steal = 0;          // wave-uniform (any-hit launches): how many XCDs' eighths of the queue this wave has seen run dry
     uint32_t idx = 0;                 // the ticket of the lane's ray: what the sink gets with its result
     RayD r;
     RayInv wri;
@@ -249,13 +234,14 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
     for (;;) {
         // ---- refill idle lanes: the wave owns a chunk [chunk_next, chunk_end) of the ray pool and
         //      only goes to the global counter (one atomic, lane 0) when the chunk is used up ----
-        // (round 6) REFILL_TESTS: any-hit walks of single-level scenes whose source keeps first candidates (the pipeline's shadow cache) test a new
-        // ray's candidate RIGHT HERE -- every lane of the refill has one, so the triangle test runs with the whole refill live -- and a ray it occludes
+        // (round 6) REFILL_TESTS: any-hit walks whose source keeps first candidates (the pipeline's shadow cache; two-level walks test the
+        // candidate in its instance's space) test a new ray's candidate RIGHT HERE -- every lane of the refill has one, so the triangle test runs with the whole refill live -- and a ray it occludes
         // never takes the lane: the refill goes round again until the wave is full (or the pool dry).  Until round 5 the candidate went in front of
         // the root as a one-triangle leaf: its lane sat through the wave's next node loop doing nothing, was tested in the leaf phase, and most of
         // the time (a cached occluder usually still occludes) ended there -- node steps of the shadow stage ran with 0.4 - 0.5 of their lanes by
-        // the hardware's count (profiles/r05/c2s_lanes.md) against 0.66 in the walk without the cache.
-        constexpr bool REFILL_TESTS = src_has_cache<Src>::value && ANYHIT && !COUNT && (!TWO_LEVEL || RT_REFILL_TESTS_TWO_LEVEL) && RT_REFILL_TESTS;
+        // the hardware's count (profiles/r05/c2s_lanes.md) against 0.66 in the walk without the cache (that path:
+        // experiments/r06_refill_tests_off.patch).
+        constexpr bool REFILL_TESTS = src_has_cache<Src>::value && ANYHIT && !COUNT;
         unsigned long long idle = __ballot(!alive);
         int n_idle = __popcll(idle);
         // (round 6) A refill pass of a walk that tests candidates is ~500 instructions (ray, light ray, 1 / d, cache cell, candidate: half of the any-hit stage's
@@ -284,7 +270,6 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
                 // the frame).  Workgroups are dealt to the XCDs round-robin and G is a multiple of 8, so a
                 // group and its counter stay on one XCD.
                 uint32_t cidx;
-#if RT_POOL_XCD
                 // Any-hit launches (round 4): every XCD owns one contiguous EIGHTH of the queue -- its four groups deal that eighth among
                 // themselves -- and moves on to the next XCD's eighth when its own is used up: the shadow rays of one part of the image
                 // (their origins: the compaction keeps tile order) share an L2.  Any-hit stage -2.4 % on both workloads; the closest-hit
@@ -303,9 +288,7 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
                         if (c < (x + 1u) * per && c < chunks) { cidx = c; break; }
                         xcd_steal++;
                     }
-                } else
-#endif
-                if (pool) {
+                } else if (pool) {
                     uint32_t k = 0;
                     if ((threadIdx.x & 63u) == 0u) k = atomicAdd(&pool[pool_group * RT_POOL_STRIDE], 1u);
                     k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
@@ -352,30 +335,6 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
                                 occluded_at_once = true;
                             }
                         }
-                    } else
-                    if constexpr (src_has_cache<Src>::value && ANYHIT && !COUNT) {
-                        // the triangle that answered this question last time goes first: a one-triangle leaf in front of the root
-                        uint32_t slot, ci;
-                        const uint32_t ct = src.template cached_leaf<TWO_LEVEL>(idx, r, slot, ci);       // (idx: the ray's ticket)
-                        st.lds[(STACK - 1) * BLOCK] = (int)slot;
-                        // (an entry is only ever tested if it names a triangle that exists: the table is emptied with the scene, but a pair
-                        // torn between two writers, or a table handed over by mistake, must not read past an array)
-                        if (ct != RT_NO_HIT && (!TWO_LEVEL || (ci < sc.n_inst && ct < sc.inst[ci].n_recs))) {      // (single level: the source checks against its own count)
-                            st.lds[0] = root0;
-                            sp = 1;
-                            if (TWO_LEVEL) {          // ... inside its instance: the leaf, then the sentinel that leads back out, then the TLAS root
-                                ii = ci;
-                                in = sc.inst + ii;
-                                cur = to_object(*in, r);
-                                nodes = in->wide;
-                                tris = in->tris;
-                                in_blas = true;
-                                top_lim = 0;
-                                st.lds[BLOCK] = RT_NODE_SENTINEL;
-                                sp = 2;
-                            }
-                            node = ~(int)(ct << 3);
-                        }
                     }
                     alive = !occluded_at_once;
                     started = true;
@@ -408,12 +367,13 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
             if (COUNT) {
                 if ((uint32_t)node < top_lim) wk_top++; else wk_glob++;
                 const uint32_t dl = distinct_node_lines(node, !((uint32_t)node < top_lim));
-                if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec())) { wk_lines += (RT_WIDE == 8 ? 2u : 1u) * dl; wk_node_lines += (RT_WIDE == 8 ? 2u : 1u) * dl; wv_steps++; }       // 64-B lines (96 B of a 128-B record: two)
+                if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec())) { wk_lines += dl; wk_node_lines += dl; wv_steps++; }       // 64-B lines: one per node
             }
             wide_step<false, ANYHIT>(nodes, top_cur, top_lim, cur.ri, r.tmin, ANYHIT ? r.tmax : best.t, st, node, sp);
-#if RT_SENTINEL_INLINE
             // (two-level walks) a pop that brings up the sentinel ends the walk of a BLAS: the lane returns to the TLAS here, inside the
-            // node loop, and pops what lies beneath -- instead of waiting for the wave's next leaf phase to do only that
+            // node loop, and pops what lies beneath -- instead of waiting for the wave's next leaf phase to do only that (round 4: the
+            // 4096-instance frame 4.70 -> 4.60 ms, profiles/r04/c4_variants.txt; the DEEP loop and the leaf phase's own pops still reach
+            // the sentinel branch of the leaf phase below)
             if (TWO_LEVEL && node == RT_NODE_SENTINEL) {
                 in_blas = false;
                 nodes = sc.tlas_wide;
@@ -422,7 +382,6 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
                 if (sp > 0) { sp--; node = st.lds[sp * BLOCK]; }
                 else node = RT_NODE_EMPTY;
             }
-#endif
 #if RT_EXIT_K > 0
             // stragglers: most of the wave already waits on a leaf -> run the leaf phase now, come back after
             const int walking = __popcll(__ballot(alive && node_is_internal(node)));
@@ -437,7 +396,7 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
                 if (COUNT) {
                     if ((uint32_t)node < top_lim) wk_top++; else wk_glob++;
                     const uint32_t dl = distinct_node_lines(node, !((uint32_t)node < top_lim));
-                    if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec())) { wk_lines += (RT_WIDE == 8 ? 2u : 1u) * dl; wk_node_lines += (RT_WIDE == 8 ? 2u : 1u) * dl; wv_steps++; }       // 64-B lines (96 B of a 128-B record: two)
+                    if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec())) { wk_lines += dl; wk_node_lines += dl; wv_steps++; }       // 64-B lines: one per node
                 }
                 wide_step<true, ANYHIT>(nodes, top_cur, top_lim, cur.ri, r.tmin, ANYHIT ? r.tmax : best.t, st, node, sp);
             }

@@ -23,9 +23,6 @@ struct LaneStack {
     }
 };
 
-#if RT_WIDE == 8      // round 3's experiment, not part of the default build
-#include "experiments/rt_wide8_step.h"
-#else
 // One step on a wide node: slab-test the four children, enter the nearest hit one (any-hit: the first in slot order),
 // push the other hit ones (farthest first), pop if none is hit.  The lane's stack pointer may rise by three, so the
 // pure-LDS instantiation (DEEP = false) is only called with sp <= STACK - 3.
@@ -137,6 +134,5 @@ RT_DEV void wide_step(const WNode *nodes, const int *top, uint32_t top_lim, cons
     if (any) node = c[0];
     else { node = sp > 0 ? under : RT_NODE_EMPTY; sp = below; }
 }
-#endif
 
 }  // namespace rtd

@@ -108,24 +108,12 @@ int rt_scene_bvh_info(const rt_scene *s, int which, uint32_t *n_prims, uint32_t 
 int rt_scene_bvh_read(const rt_scene *s, int which, rt_bvh_node *nodes, uint64_t *sorted_keys, uint32_t *parents);
 /* world_box: the TLAS leaf box of the instance = the exact box of its triangles' transformed vertices (an identity instance: of its BLAS) */
 int rt_scene_instance_info(const rt_scene *s, uint32_t instance, float world_box[6], float world_to_object[12]);
-/* Inspection of the PRODUCTION traversal layout of the same structures (tests, tools).  rt_wide_layout_info tells which
- * of the two layouts the library was built with.
- * width 4 (the default), 64-B nodes of 16 words:
+/* Inspection of the PRODUCTION traversal layout of the same structures (tests, tools).  rt_wide_layout_info reports
+ * its width and node size: (4, 64) -- 64-B nodes of 16 words:
  *   w0..w2 float origin.xyz of the node's box, w3 float scale.x | w4 lo.x bytes of children 0..3 (child k in bits 8k..),
  *   w5 hi.x, w6 lo.y, w7 hi.y | w8 lo.z, w9 hi.z, w10 float scale.y, w11 float scale.z | w12..w15 int32 child codes;
  *   children packed at the front, larger surface first; plane = fma(byte, scale, origin); a scale of +inf (bytes 0) marks
  *   an axis that is not quantised (non-finite extents): its planes bound nothing.
- * width 8 (build option -DRT_WIDE=8), 128-B records of 32 words:
- *   w0..w2  float origin.xyz
- *   w3      ex | ey << 8 | ez << 16 | valid << 24: biased exponents of the three power-of-two scales (scale = 2^(e - 127);
- *           e = 255: axis not quantised) and the mask of the slots that hold a child
- *   w4,w5   lo.x bytes of slots 0..3, 4..7 (slot k in bits 8 (k mod 4) ...)    w6,w7   hi.x bytes
- *   w8..w11 lo.y, hi.y likewise        w12..w15 lo.z, hi.z likewise
- *   w16..w23 int32 child codes of slots 0..7
- *   w24     index of the first internal child (the internal children of a node are consecutive, in slot order)
- *   w25     mask of the slots that hold an internal child      w26 builder's binary node      w27..w31 zero
- *   Slots: the child nearest the (-,-,-) corner of the node sits in slot 0, nearest (+,+,+) in slot 7 (bit a of the slot =
- *   axis a positive); the traversal visits hit children in the order of slot XOR (sign bits of the ray direction).
  * Child codes: >= 0 node index, INT32_MIN unused, otherwise ~code with code = instance (TLAS) or
  * first_record << 3 | (count - 1) (BLAS).  BLAS records are 48 B: nine floats p0 p1 p2, the uint32 primitive index, 8 B
  * padding.  root_code: 0 = node 0, negative = the whole structure is one leaf. */
@@ -448,7 +436,7 @@ int rt_debug_sample_cube(rt_context *ctx, const float *faces_rgba32f, uint32_t s
  * RT_WIDE_STEP_DEEP (the instantiation whose stack continues in global rows; else the pure-LDS one), RT_WIDE_STEP_LDS_TOP (the nodes are
  * read from the LDS-resident top: at most 128 nodes; else from global memory).  out: five int32 per item -- the node code entered (0x7FFFFFFE:
  * every child was culled), the stack pointer after the step, and the rows pushed in stack order (INT32_MIN above the stack pointer).
- * tests/test_gpu_wide_step.py holds it to oracle/wide_step_model.h.  RT_ERR_UNSUPPORTED in a -DRT_WIDE=8 build. */
+ * tests/test_gpu_wide_step.py holds it to oracle/wide_step_model.h. */
 #define RT_WIDE_STEP_ANYHIT  1u
 #define RT_WIDE_STEP_DEEP    2u
 #define RT_WIDE_STEP_LDS_TOP 4u

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from dxrexperiments_amd import rtypes as T, scenes
-from util import CORNELL_OBJ, GOLDEN, cam_array, random_xforms, triangle_soup
+from util import CORNELL_OBJ, CULL, GOLDEN, cam_array, primary_rays, random_xforms, triangle_soup
 
 pytestmark = pytest.mark.gpu
 
@@ -459,6 +459,33 @@ def test_count_walk_is_the_production_walk(gpu, capi):
         p2.count_walk()
     with pytest.raises(capi.RtError):
         p2.count_work()
+
+
+@pytest.mark.parametrize("two_level", [False, True], ids=["single_level", "two_level"])
+def test_count_work_primary_stage_is_the_canonical_walk_of_the_walked_rays(gpu, oracle, capi, two_level):
+    """rt_pipeline_count_work's primary stage on a 64 x 64 Cornell frame (every stage's rays go through ONE counting kernel and the
+    queue views of the frame's own launches).  Its rays are the rays rt_pipeline_count_walk walked and the frame traced; its nodes and
+    triangles are the sums, exactly, of the oracle's canonical walk over the frame's primary rays: both walk the canonical tree, where the
+    counts depend on the ray alone.  (The re-walk's node and triangle tallies are those of another tree, the four-wide layout, and equal
+    neither; what must hold in either tree: a ray that hit something tested at least one triangle.)"""
+    W = H = 64
+    v, i = oracle.obj_load(CORNELL_OBJ)
+    inst = [(0, None), (0, random_xforms(1, 11, spread=0.5)[0])] if two_level else [(0, None)]
+    mats = [T.default_material()] * len(inst)
+    p = make_gpu_pipeline(capi, gpu, [(v, i)], inst, mats, W, H)
+    pfc = capi.ProgressiveHost(3).update(cam_array(scenes.cornell_camera(), W / H), 0.0, 1, W, H)
+    p.update(pfc)
+    p.render()
+    work, walk = p.count_work()["primary"], p.count_walk()["primary"]
+    O, D = primary_rays(pfc, W, H)
+    ob = make_oracle_scene(oracle, [(v, i)], inst).trace(O, D, flags=CULL, mode=1, nthreads=8)
+    hits = int((ob["inst"] != T.RT_NO_HIT).sum())
+    print("count_work %s, oracle rays %d nodes %d tris %d hits %d, count_walk rays %d tris %d instance entries %d" % (
+        work, W * H, int(ob["nodes"].sum()), int(ob["tris"].sum()), hits, walk["rays"], walk["tris"], walk["instance_entries"]))
+    assert work["rays"] == walk["rays"] == p.stats()["rays_primary"] == W * H
+    assert work["nodes"] == int(ob["nodes"].sum(dtype=np.uint64)) and work["tris"] == int(ob["tris"].sum(dtype=np.uint64))
+    assert hits > W * H // 2 and work["tris"] >= hits and walk["tris"] >= hits
+    assert (walk["instance_entries"] > 0) == two_level
 
 
 def test_cornell_lit_by_the_reference_environment_map(gpu, capi, tmp_path):

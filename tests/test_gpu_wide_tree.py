@@ -1,4 +1,4 @@
-"""The PRODUCTION traversal layout (four-wide quantised nodes; eight-wide from a -DRT_WIDE=8 build, rt_bvh_wide.hip) read back through the C ABI and checked by
+"""The PRODUCTION traversal layout (four-wide quantised nodes, rt_bvh_wide.hip) read back through the C ABI and checked by
 an independent numpy reader (tests/wide_tree.py): every primitive is in exactly one leaf, every decoded child box contains
 its subtree (the premise of the exactness rule), breadth-first numbering, power-of-two grids.  The
 parity tests show that images do not depend on this tree; these show that the tree is what the design says it is."""

@@ -9,10 +9,11 @@ NONE = -2 ** 31
 
 
 def decode(nodes):
-    """nodes: uint32[n, 16] (four-wide, 64 B) or uint32[n, 32] (eight-wide, 128 B; a -DRT_WIDE=8 build) ->
-    dict(lo float32[n, W, 3], hi float32[n, W, 3] (NaN: the axis bounds nothing), code int32[n, W], scale float32[n, 3],
-    width W; eight-wide only: valid bool[n, 8], first_child, internal_mask)."""
-    return decode8(nodes) if nodes.shape[1] == 32 else decode4(nodes)
+    """nodes: uint32[n, 16] (four-wide, 64 B) ->
+    dict(lo float32[n, W, 3], hi float32[n, W, 3] (NaN: the axis bounds nothing), code int32[n, W], scale float32[n, 3], width W = 4).
+    (The reader of round 3's eight-wide records left with that layout: dxrexperiments_amd/csrc/experiments/r03_wide8.patch.)"""
+    assert nodes.shape[1] == 16, "not the four-wide layout"
+    return decode4(nodes)
 
 
 def decode4(nodes):
@@ -36,36 +37,9 @@ def decode4(nodes):
     return out
 
 
-def decode8(nodes):
-    W = 8
-    f = nodes.view(np.float32)
-    origin = f[:, 0:3]
-    meta = nodes[:, 3]
-    expo = np.stack([meta & 0xFF, (meta >> 8) & 0xFF, (meta >> 16) & 0xFF], axis=1).astype(np.int64)
-    with np.errstate(over="ignore"):
-        scale = np.where(expo == 255, np.float32(np.inf), np.ldexp(np.float32(1.0), (expo - 127).astype(np.int32))).astype(np.float32)
-    valid = ((meta >> 24)[:, None] >> np.arange(W, dtype=np.uint32)[None, :]) & 1 == 1
-    out = {"width": 8}
-    for name, first in (("lo", 4), ("hi", 6)):
-        planes = np.empty((nodes.shape[0], W, 3), np.float32)
-        for a in range(3):
-            for k in range(W):
-                w = nodes[:, first + 4 * a + k // 4]
-                q = ((w >> np.uint32(8 * (k % 4))) & np.uint32(0xFF)).astype(np.float32)
-                with np.errstate(invalid="ignore"):
-                    planes[:, k, a] = q * scale[:, a] + origin[:, a]
-        out[name] = planes
-    out["code"] = nodes[:, 16:24].view(np.int32).copy()
-    out["valid"] = valid
-    out["scale"] = scale
-    out["first_child"] = nodes[:, 24].astype(np.int64)
-    out["internal_mask"] = nodes[:, 25]
-    return out
-
-
 def code_columns(nodes):
     """the slice of node words that holds the child codes"""
-    return slice(16, 24) if nodes.shape[1] == 32 else slice(12, 16)
+    return slice(12, 16)
 
 
 def record_bounds(recs):
@@ -110,10 +84,7 @@ def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True):
     WIDE = d["width"]
     used = code != NONE
     assert np.all(used.sum(axis=1) >= 2), "a node with fewer than two children"
-    if WIDE == 4:
-        assert np.all(used[:, :-1] | ~used[:, 1:]), "children not packed at the front"
-    else:
-        assert np.array_equal(used, d["valid"]), "valid mask and child codes disagree"
+    assert np.all(used[:, :-1] | ~used[:, 1:]), "children not packed at the front"
     internal = used & (code >= 0)
     leaf = used & (code < 0)
     assert np.all(code[internal] < n) and np.all(code[internal] > 0), "child index out of range"
@@ -122,14 +93,6 @@ def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True):
     assert refs[0] == 0 and np.all(refs[1:] == 1), "a node with more than one parent"
     # breadth-first numbering: levels are contiguous and ascending (the first nodes are the LDS-resident top)
     assert np.all(np.diff(level) >= 0), "nodes are not in breadth-first order"
-    if WIDE == 8:
-        # the internal children of a node are consecutive, in slot order (the inspection words say where they start)
-        imask = (internal.astype(np.uint32) << np.arange(WIDE, dtype=np.uint32)[None, :]).sum(axis=1).astype(np.uint32)
-        assert np.array_equal(imask, d["internal_mask"]), "internal-slot mask"
-        rank = np.cumsum(internal, axis=1) - 1
-        has = internal.any(axis=1)
-        assert np.all((code == (d["first_child"][:, None] + rank))[internal]), "internal children are not consecutive in slot order"
-        assert np.all(d["first_child"][~has] == 0)
     # leaves cover every item exactly once
     covered = np.zeros(n_leaf_items, np.int64)
     lc = ~code[leaf]
