@@ -177,7 +177,7 @@ static int context_create(int device, void *stream, bool own, rt_context **out)
     } else c->stream = (hipStream_t)stream;
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
         rt_set_error("hipEventCreate failed");
-        delete c;
+        delete c;          // (the stream and the first event go with it)
         return RT_ERR_HIP;
     }
     hipDeviceProp_t prop;
@@ -251,17 +251,28 @@ void rt_scene_retain(rt_scene *s) { if (s) s->refs++; }
 void rt_context_release(rt_context *ctx)
 {
     if (!ctx || --ctx->refs > 0) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    for (DevBuf &b : ctx->scratch) b.release();
-    ctx->pool.release();
-    ctx->deep_stack.release();
-    ctx->build_arena.release();
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
+}
+
+rt_context::~rt_context()
+{
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    if (pinned) (void)hipHostFree(pinned);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+}
+
+rt_model::~rt_model()
+{
+    if (ctx) (void)hipSetDevice(ctx->device);
+}
+
+rt_scene::~rt_scene()
+{
+    (void)hipSetDevice(ctx->device);
+    for (SceneInstance &in : inst) rt_model_destroy(in.model);
 }
 
 extern "C" {
@@ -350,8 +361,8 @@ static int model_finish(rt_context *ctx, rt_model *m, rt_model **out)
     for (uint32_t i : m->h_idx)
         if (i >= m->n_verts) {
             rt_set_error("index %u out of range (%u vertices)", i, m->n_verts);
-            rt_context_release(ctx);
             delete m;
+            rt_context_release(ctx);
             return RT_ERR_INVALID_ARG;
         }
     int rc = use_device(ctx);
@@ -359,9 +370,8 @@ static int model_finish(rt_context *ctx, rt_model *m, rt_model **out)
     if (rc == RT_OK) rc = upload(ctx, m->d_idx, m->h_idx.data(), sizeof(uint32_t) * m->h_idx.size());
     if (rc == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { rt_set_error("geometry upload failed"); rc = RT_ERR_HIP; }
     if (rc != RT_OK) {
-        m->d_verts.release(); m->d_idx.release();
-        rt_context_release(ctx);
         delete m;
+        rt_context_release(ctx);
         return rc;
     }
     *out = m;
@@ -430,8 +440,6 @@ int rt_model_destroy(rt_model *m)
 {
     if (!m) return RT_OK;
     if (--m->refs > 0) return RT_OK;
-    (void)hipSetDevice(m->ctx->device);
-    m->d_verts.release(); m->d_idx.release(); m->tris.release(); m->normals.release(); m->blas.release(); m->rec_boxes.release(); m->ref_off.release(); m->ref_boxes.release();
     rt_context *ctx = m->ctx;
     delete m;
     rt_context_release(ctx);
@@ -481,35 +489,24 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     rt_context *ctx = s->ctx;
     RT_TRY(use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); rt_set_error("rt_scene_build: hipEventCreate failed"); return RT_ERR_HIP; }
-    if (hipEventRecord(e0, ctx->stream) != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); rt_set_error("rt_scene_build: hipEventRecord failed"); return RT_ERR_HIP; }
+    ScopedEvent e0, e1;
+    HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventCreate(&e1.e));
+    HIP_TRY(hipEventRecord(e0.e, ctx->stream));
     s->generation++;          // device arrays are about to be reallocated: pipelines drop what they cached
-    int rc = RT_OK;
-    for (SceneInstance &in : s->inst)
-        if ((rc = rt_build_blas(ctx, in.model)) != RT_OK) break;
-    if (rc == RT_OK) rc = rt_build_tlas(ctx, s);
-    if (rc == RT_OK) {
-        if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-            hipEventElapsedTime(&s->build_ms, e0, e1) != hipSuccess) {
-            rt_set_error("rt_scene_build: timing events failed: %s", hipGetErrorString(hipGetLastError()));
-            rc = RT_ERR_HIP;
-        } else s->built = true;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    for (SceneInstance &in : s->inst) RT_TRY(rt_build_blas(ctx, in.model));
+    RT_TRY(rt_build_tlas(ctx, s));
+    HIP_TRY(hipEventRecord(e1.e, ctx->stream));
+    HIP_TRY(hipEventSynchronize(e1.e));
+    HIP_TRY(hipEventElapsedTime(&s->build_ms, e0.e, e1.e));
+    s->built = true;
+    return RT_OK;
 }
 
 int rt_scene_destroy(rt_scene *s)
 {
     if (!s) return RT_OK;
     if (--s->refs > 0) return RT_OK;
-    (void)hipSetDevice(s->ctx->device);
-    for (SceneInstance &in : s->inst) rt_model_destroy(in.model);
-    s->d_inst.release();
-    s->tlas.release();
     rt_context *ctx = s->ctx;
     delete s;
     rt_context_release(ctx);

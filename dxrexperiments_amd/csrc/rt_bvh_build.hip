@@ -408,24 +408,64 @@ __global__ void k_ref_mark_records(TriRec *__restrict__ tris, uint32_t n, const 
     if (off[prim + 1] - off[prim] > 1u) tris[k].c.z = __uint_as_float(2u);
 }
 
-// Temporaries of a build over n primitives as slices of the context's build arena (sized for the larger of
-// the LBVH and the PLOC phase, which run one after the other).  A slice that turns out too small makes
-// its DevBuf allocate on its own (DevBuf::reserve), so the sizes here are a fast path, not a contract.
-struct BuildTemps { DevBuf boxes, enc, bounds, tkeys, tsort, tenc, tdepth, extra; };
-int take_build_temps(rt_context *ctx, uint32_t n, BuildTemps &t, size_t extra_bytes = 0)
+// Temporaries of an LBVH build over n primitives: slices of the context's build arena.  Every builder describes its slices once, to a
+// Carver; the arena is sized by running the same description without a base (and for the larger of the LBVH and the PLOC / collapse
+// phases, which run one after the other).
+struct LbvhTemps {
+    Box6 *boxes;
+    uint32_t *enc;               // encoded bounds (k_init_bounds .. k_decode_bounds)
+    float *bounds;
+    uint64_t *keys;              // unsorted Morton keys
+    void *sort; size_t sort_bytes;      // room for the radix sort's scratch: what rocPRIM asks for is only known from its query
+    uint32_t *refit_enc, *depth;
+};
+void carve_lbvh(Carver &c, uint32_t n, LbvhTemps &t)
 {
-    const size_t A = 256;
-    auto up = [&](size_t b) { return (b + A - 1) & ~(A - 1); };
-    const size_t want[8] = {up(sizeof(Box6) * (size_t)n), A, A, up(8 * (size_t)n), up(16 * (size_t)n + (4u << 20)), up(64 * (size_t)n), A, up(extra_bytes)};
-    size_t lbvh = 0;
-    for (size_t w : want) lbvh += w;
+    t.boxes = c.take<Box6>(n);
+    t.enc = c.take<uint32_t>(6);
+    t.bounds = c.take<float>(6);
+    t.keys = c.take<uint64_t>(n);
+    t.sort_bytes = 16 * (size_t)n + (4u << 20);
+    t.sort = c.take<char>(t.sort_bytes);
+    t.refit_enc = c.take<uint32_t>(8 * (2 * (size_t)n - 1));
+    t.depth = c.take<uint32_t>(1);
+}
+// (+ the reference count of every triangle, its scan and the scan's scratch)
+struct BlasTemps : LbvhTemps {
+    uint32_t *ref_count, *ref_off;      // n + 1 each
+    void *scan; size_t scan_bytes;
+};
+void carve_blas(Carver &c, uint32_t n, BlasTemps &t)
+{
+    carve_lbvh(c, n, t);
+    t.ref_count = c.take<uint32_t>((size_t)n + 1);
+    t.ref_off = c.take<uint32_t>((size_t)n + 1);
+    t.scan_bytes = (size_t)1 << 20;
+    t.scan = c.take<char>(t.scan_bytes);
+}
+// (+ k_instance_boxes' work memory: per-instance encoded bounds, the forward transforms, the work list)
+struct TlasTemps : LbvhTemps {
+    uint32_t *inst_enc;
+    float *inst_xf;
+    uint2 *inst_items;
+};
+void carve_tlas(Carver &c, uint32_t n, size_t n_items, TlasTemps &t)
+{
+    carve_lbvh(c, n, t);
+    t.inst_enc = c.take<uint32_t>(6 * (size_t)n);
+    t.inst_xf = c.take<float>(12 * (size_t)n);
+    t.inst_items = c.take<uint2>(n_items);
+}
+template <class Temps, class Carve> int take_build_temps(rt_context *ctx, uint32_t n, Temps &t, Carve carve)
+{
+    Carver sizing(nullptr);
+    carve(sizing, t);
     const size_t ploc = rt_ploc_temp_bytes(n), wide = rt_wide_lbvh_temp_bytes(n);
-    size_t most = lbvh > ploc ? lbvh : ploc;
+    size_t most = sizing.offset > ploc ? sizing.offset : ploc;
     most = most > wide ? most : wide;
     RT_TRY(ctx->build_arena.reserve(most));
-    DevBuf *bufs[8] = {&t.boxes, &t.enc, &t.bounds, &t.tkeys, &t.tsort, &t.tenc, &t.tdepth, &t.extra};
-    size_t at = 0;
-    for (int k = 0; k < 8; k++) { bufs[k]->adopt((char *)ctx->build_arena.p + at, want[k]); at += want[k]; }
+    Carver c(ctx->build_arena.p);
+    carve(c, t);
     return RT_OK;
 }
 void drop_build_arena_if_large(rt_context *ctx)
@@ -434,8 +474,7 @@ void drop_build_arena_if_large(rt_context *ctx)
 }
 
 // Steps 2..6 for a structure whose primitive boxes and bounds are already on the device.
-int lbvh_from_boxes(rt_context *ctx, BvhDev &bv, const Box6 *boxes, uint32_t n, const float *d_bounds, bool tlas,
-                    DevBuf &tmp_keys, DevBuf &tmp_sort, DevBuf &tmp_enc, DevBuf &tmp_depth)
+int lbvh_from_boxes(rt_context *ctx, BvhDev &bv, uint32_t n, const LbvhTemps &t)
 {
     hipStream_t st = ctx->stream;
     const unsigned B = 256;
@@ -448,36 +487,34 @@ int lbvh_from_boxes(rt_context *ctx, BvhDev &bv, const Box6 *boxes, uint32_t n, 
     RT_TRY(bv.keys.reserve(sizeof(uint64_t) * n));
     RT_TRY(bv.parents.reserve(sizeof(uint32_t) * (2 * (size_t)n - 1)));
     RT_TRY(bv.ranges.reserve(sizeof(uint2) * (n > 1 ? n - 1 : 1)));
-    RT_TRY(tmp_keys.reserve(sizeof(uint64_t) * n));
-    RT_TRY(tmp_depth.reserve(sizeof(uint32_t)));
 
-    k_morton<<<grid_for(n, B), B, 0, st>>>(boxes, n, d_bounds, tmp_keys.as<uint64_t>());
+    k_morton<<<grid_for(n, B), B, 0, st>>>(t.boxes, n, t.bounds, t.keys);
     // keys are (30-bit Morton code << 32) | index with the indices ascending on input: a STABLE sort of the code bits alone
     // gives the order of the full 64-bit keys (the oracle's) with half the radix passes
     size_t sort_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, tmp_keys.as<uint64_t>(), bv.keys.as<uint64_t>(), n, 32, 62, st));
-    RT_TRY(tmp_sort.reserve(sort_bytes));
-    HIP_TRY(rocprim::radix_sort_keys(tmp_sort.p, sort_bytes, tmp_keys.as<uint64_t>(), bv.keys.as<uint64_t>(), n, 32, 62, st));
+    HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, t.keys, bv.keys.as<uint64_t>(), n, 32, 62, st));
+    DevBuf sort_tmp;             // the arena's slice, or an allocation of its own when the library asks for more
+    sort_tmp.adopt(t.sort, t.sort_bytes);
+    RT_TRY(sort_tmp.reserve(sort_bytes));
+    HIP_TRY(rocprim::radix_sort_keys(sort_tmp.p, sort_bytes, t.keys, bv.keys.as<uint64_t>(), n, 32, 62, st));
 
     rt_bvh_node *nodes = bv.nodes.as<rt_bvh_node>();
     uint32_t *parents = bv.parents.as<uint32_t>();
-    k_leaves<<<grid_for(n, B), B, 0, st>>>(bv.keys.as<uint64_t>(), boxes, n, nodes, parents);
-    HIP_TRY(hipMemsetAsync(tmp_depth.p, 0, sizeof(uint32_t), st));
+    k_leaves<<<grid_for(n, B), B, 0, st>>>(bv.keys.as<uint64_t>(), t.boxes, n, nodes, parents);
+    HIP_TRY(hipMemsetAsync(t.depth, 0, sizeof(uint32_t), st));
     if (n > 1) {
         k_karras<<<grid_for(n - 1, B), B, 0, st>>>(bv.keys.as<uint64_t>(), (int)n, nodes, parents, bv.ranges.as<uint2>());
-        RT_TRY(tmp_enc.reserve(sizeof(uint32_t) * 8 * (2 * (size_t)n - 1)));
-        HIP_TRY(hipMemsetAsync(tmp_enc.p, 0, sizeof(uint32_t) * 8 * (2 * (size_t)n - 1), st));
-        k_refit<<<grid_for(n, B), B, 0, st>>>(nodes, parents, n, tmp_enc.as<uint32_t>(), tmp_depth.as<uint32_t>());
-        k_refit_decode<<<grid_for(n - 1, B), B, 0, st>>>(tmp_enc.as<uint32_t>(), nodes, n - 1);
+        HIP_TRY(hipMemsetAsync(t.refit_enc, 0, sizeof(uint32_t) * 8 * (2 * (size_t)n - 1), st));
+        k_refit<<<grid_for(n, B), B, 0, st>>>(nodes, parents, n, t.refit_enc, t.depth);
+        k_refit_decode<<<grid_for(n - 1, B), B, 0, st>>>(t.refit_enc, nodes, n - 1);
     }
     HIP_TRY(hipGetLastError());
     // depth and bounds come back through page-locked memory and are picked up by lbvh_collect() once the caller has queued
     // the rest of the build: no host round trip in the middle of it
     uint32_t *back = ctx->pinned ? ctx->pinned + RT_PINNED_LBVH : nullptr;
-    HIP_TRY(hipMemcpyAsync(back ? (void *)back : (void *)&bv.max_depth, tmp_depth.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(back ? (void *)(back + 1) : (void *)bv.bounds, d_bounds, 6 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(back ? (void *)back : (void *)&bv.max_depth, t.depth, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(back ? (void *)(back + 1) : (void *)bv.bounds, t.bounds, 6 * sizeof(float), hipMemcpyDeviceToHost, st));
     if (!back) HIP_TRY(hipStreamSynchronize(st));
-    (void)tlas;
     return RT_OK;
 }
 
@@ -492,158 +529,187 @@ int lbvh_collect(rt_context *ctx, BvhDev &bv)
     return RT_OK;
 }
 
+// ---- the steps of a BLAS build (rt_build_blas) ----
+
+constexpr unsigned BB = 256;
+
+// option verbose=1: wall time of each build phase on stderr (synchronises: diagnostics only)
+struct PhaseClock {
+    rt_context *ctx;
+    std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    void mark(const char *what)
+    {
+        if (!ctx->verbose) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[dxr_amd]   BLAS %-18s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(now - prev).count());
+        prev = now;
+    }
+};
+
+// The references of a model with split triangles (rt_refs.h), from their count to the leaves the production tree is built from.  The
+// buffers live until the build's last step has been queued and joined: freeing one earlier would wait for the device in mid-build.
+struct RefLeaves {
+    uint32_t n_refs = 0;         // boxes all triangles together are validated against: n_tris when none is split
+    bool split_layout = false;   // the production tree gets one leaf per reference
+    DevBuf prim, keys, sorted, sort_tmp, leaf_box, leaf_prim;
+};
+
+int blas_boxes_and_bounds(rt_context *ctx, rt_model *m, const BlasTemps &t, PhaseClock &clock)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = m->n_tris;
+    RT_TRY(m->tris.reserve(sizeof(TriRec) * (size_t)n));
+    RT_TRY(m->normals.reserve(sizeof(TriRec) * (size_t)n));
+    clock.mark("tris alloc");
+    k_init_bounds<<<1, 64, 0, st>>>(t.enc);
+    k_tri_boxes<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, t.boxes, t.enc);
+    k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
+    clock.mark("alloc + boxes");
+    return RT_OK;
+}
+
+int blas_records(rt_context *ctx, rt_model *m)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = m->n_tris;
+    k_gather_tris<<<grid_for(n, BB), BB, 0, st>>>(m->blas.keys.as<uint64_t>(), m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, m->tris.as<TriRec>());
+    k_normal_records<<<grid_for(n, BB), BB, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, m->normals.as<TriRec>());
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// Split references (rt_refs.h): how many boxes every triangle is validated against.  One each leaves the model as it was; otherwise the
+// boxes by primitive (the canonical walk validates against them) and the primitive of every reference.
+int blas_split_refs(rt_context *ctx, rt_model *m, const BlasTemps &t, RefLeaves &r)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = m->n_tris;
+    m->n_recs = n;
+    m->rec_boxes.release(); m->ref_off.release(); m->ref_boxes.release();      // (a rebuild starts from a model without references)
+    k_ref_count<<<grid_for(n + 1, BB), BB, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, t.bounds, t.ref_count);
+    size_t scan_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, t.ref_count, t.ref_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+    DevBuf scan_tmp;             // as lbvh_from_boxes' sort_tmp
+    scan_tmp.adopt(t.scan, t.scan_bytes);
+    RT_TRY(scan_tmp.reserve(scan_bytes));
+    HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, t.ref_count, t.ref_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+    r.n_refs = n;
+    uint32_t *back = ctx->pinned ? ctx->pinned : &r.n_refs;
+    HIP_TRY(hipMemcpyAsync(back, t.ref_off + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    r.n_refs = *back;
+    // up to RT_REF_MAX_PIECES references per triangle: beyond 2^32 / 128 triangles the 32-bit scan can wrap past a plausible
+    // total, so such a mesh has its counts summed again in 64 bits
+    if ((uint64_t)n * RT_REF_MAX_PIECES > 0xFFFFFFFFull) {
+        DevBuf sum64;
+        unsigned long long total64 = 0;
+        RT_TRY(sum64.reserve(8));
+        HIP_TRY(hipMemsetAsync(sum64.p, 0, 8, st));
+        k_sum64<<<1024, BB, 0, st>>>(t.ref_count, n, sum64.as<unsigned long long>());
+        HIP_TRY(hipMemcpyAsync(&total64, sum64.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (total64 != (unsigned long long)r.n_refs) { rt_set_error("split references: %llu for %u triangles", total64, n); return RT_ERR_UNSUPPORTED; }
+    }
+    if (r.n_refs == n) return RT_OK;
+    if (r.n_refs < n || r.n_refs > (1u << (32 - RT_NODE_SHIFT))) { rt_set_error("split references: %u for %u triangles", r.n_refs, n); return RT_ERR_UNSUPPORTED; }
+    RT_TRY(m->ref_off.reserve(4 * ((size_t)n + 1)));
+    HIP_TRY(hipMemcpyAsync(m->ref_off.p, t.ref_off, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, st));
+    RT_TRY(m->ref_boxes.reserve(24 * (size_t)r.n_refs));
+    RT_TRY(r.prim.reserve(4 * (size_t)r.n_refs));
+    k_ref_emit<<<grid_for(n, BB), BB, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, t.bounds, m->ref_off.as<uint32_t>(),
+                                             m->ref_boxes.as<float>(), r.prim.as<uint32_t>());
+    if (ctx->verbose) fprintf(stderr, "[dxr_amd]   BLAS %u triangles -> %u references\n", n, r.n_refs);
+    return RT_OK;
+}
+
+// the references in Morton order: the leaves of the production tree
+int blas_ref_leaves(rt_context *ctx, rt_model *m, const BlasTemps &t, RefLeaves &r)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n_refs = r.n_refs;
+    RT_TRY(r.keys.reserve(8 * (size_t)n_refs));
+    RT_TRY(r.sorted.reserve(8 * (size_t)n_refs));
+    RT_TRY(r.leaf_box.reserve(24 * (size_t)n_refs));
+    RT_TRY(r.leaf_prim.reserve(4 * (size_t)n_refs));
+    k_ref_keys<<<grid_for(n_refs, BB), BB, 0, st>>>(m->ref_boxes.as<float>(), n_refs, t.bounds, r.keys.as<uint64_t>());
+    size_t sort_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, r.keys.as<uint64_t>(), r.sorted.as<uint64_t>(), n_refs, 32, 62, st));
+    RT_TRY(r.sort_tmp.reserve(sort_bytes));
+    HIP_TRY(rocprim::radix_sort_keys(r.sort_tmp.p, sort_bytes, r.keys.as<uint64_t>(), r.sorted.as<uint64_t>(), n_refs, 32, 62, st));
+    k_ref_leaves<<<grid_for(n_refs, BB), BB, 0, st>>>(r.sorted.as<uint64_t>(), n_refs, m->ref_boxes.as<float>(), r.prim.as<uint32_t>(),
+                                                    r.leaf_box.as<float>(), r.leaf_prim.as<uint32_t>());
+    return RT_OK;
+}
+
+// production traversal layout: re-cluster the same leaves with PLOC (rt_bvh_ploc.hip), then collapse the binary
+// tree into wide quantised nodes (rt_bvh_wide.hip); tiny meshes and option fast_bvh=lbvh collapse the LBVH itself
+int blas_layout(rt_context *ctx, rt_model *m, const RefLeaves &r, PhaseClock &clock)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = m->n_tris;
+    bool ploc_done = false;
+    if (ctx->use_ploc) {
+        const int rc = r.split_layout ? rt_build_ploc_layout(ctx, m, &ploc_done, r.n_refs, r.leaf_box.as<float>(), r.leaf_prim.as<uint32_t>())
+                                      : rt_build_ploc_layout(ctx, m, &ploc_done);
+        // PLOC's nearest-neighbour rounds make no progress on boxes whose surface is not finite (NaN / inf vertices,
+        // extents that overflow): such a mesh keeps the LBVH as its traversal layout.  rt_build_ploc_layout may give up AFTER k_ploc_tris
+        // had rewritten m->tris in PLOC order (the collapse that follows it can refuse a tree too), so the records are gathered again
+        // in LBVH order whatever the mesh: that is the order the collapse below and k_ref_mark_records index
+        if (rc == RT_ERR_STATE || (rc == RT_OK && ctx->opt_fail_ploc_rounds)) {      // (the option: tests force this path)
+            ploc_done = false;
+            if (r.split_layout) {
+                // the split-reference path had grown m->tris for one record per REFERENCE (DevBuf::reserve keeps no contents):
+                // back to one record per triangle
+                m->rec_boxes.release();
+                m->n_recs = n;
+                RT_TRY(m->tris.reserve(sizeof(TriRec) * (size_t)n));
+            }
+            k_gather_tris<<<grid_for(n, BB), BB, 0, st>>>(m->blas.keys.as<uint64_t>(), m->d_verts.as<rt_vertex>(),
+                                                        m->d_idx.as<uint32_t>(), n, m->tris.as<TriRec>());
+        } else RT_TRY(rc);
+    }
+    clock.mark("PLOC + wide layout");
+    if (!ploc_done) RT_TRY(rt_build_wide_from_lbvh(ctx, m->blas, false, ctx->leaf_max));
+    if (r.n_refs > n && !(ploc_done && r.split_layout)) {
+        // a layout with one record per triangle (LBVH; PLOC with the option split_refs=0): split triangles are validated by primitive
+        m->n_recs = n;
+        k_ref_mark_records<<<grid_for(n, BB), BB, 0, st>>>(m->tris.as<TriRec>(), n, m->ref_off.as<uint32_t>());
+    }
+    clock.mark("wide layout (LBVH)");
+    return RT_OK;
+}
+
+int blas_steps(rt_context *ctx, rt_model *m, PhaseClock &clock)
+{
+    const uint32_t n = m->n_tris;
+    BlasTemps t;
+    RefLeaves refs;
+    RT_TRY(take_build_temps(ctx, n, t, [n](Carver &c, BlasTemps &bt) { carve_blas(c, n, bt); }));
+    clock.mark("arena");
+    RT_TRY(blas_boxes_and_bounds(ctx, m, t, clock));
+    RT_TRY(lbvh_from_boxes(ctx, m->blas, n, t));
+    clock.mark("LBVH");
+    RT_TRY(blas_records(ctx, m));
+    RT_TRY(blas_split_refs(ctx, m, t, refs));
+    refs.split_layout = refs.n_refs > n && ctx->opt_split_refs && ctx->use_ploc;
+    if (refs.split_layout) RT_TRY(blas_ref_leaves(ctx, m, t, refs));
+    clock.mark("gather");
+    RT_TRY(blas_layout(ctx, m, refs, clock));
+    RT_TRY(lbvh_collect(ctx, m->blas));
+    m->built = true;
+    return RT_OK;
+}
+
 }  // namespace
 
 int rt_build_blas(rt_context *ctx, rt_model *m)
 {
     if (m->built) return RT_OK;
-    hipStream_t st = ctx->stream;
-    const unsigned B = 256;
-    const uint32_t n = m->n_tris;
-    BuildTemps bt;
-    DevBuf &boxes = bt.boxes, &enc = bt.enc, &bounds = bt.bounds, &tkeys = bt.tkeys, &tsort = bt.tsort, &tenc = bt.tenc, &tdepth = bt.tdepth;
-    int rc = RT_OK;
-    const bool verbose = ctx->verbose;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what) {          // RT_VERBOSE: wall time of each build phase (synchronises: diagnostics only)
-        if (!verbose) return;
-        (void)hipStreamSynchronize(st);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[dxr_amd]   BLAS %-18s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
-    do {
-        // (+ the reference count of every triangle, its scan and the scan's scratch: slices of the arena, no allocation of their own)
-        const size_t ref_words = ((size_t)n + 1 + 63) & ~(size_t)63;
-        if ((rc = take_build_temps(ctx, n, bt, 8 * ref_words + ((size_t)1 << 20))) != RT_OK) break;
-        mark("arena");
-        if ((rc = boxes.reserve(sizeof(Box6) * (size_t)n)) != RT_OK) break;
-        if ((rc = enc.reserve(6 * sizeof(uint32_t))) != RT_OK) break;
-        if ((rc = bounds.reserve(6 * sizeof(float))) != RT_OK) break;
-        if ((rc = m->tris.reserve(sizeof(TriRec) * (size_t)n)) != RT_OK) break;
-        if ((rc = m->normals.reserve(sizeof(TriRec) * (size_t)n)) != RT_OK) break;
-        mark("tris alloc");
-        k_init_bounds<<<1, 64, 0, st>>>(enc.as<uint32_t>());
-        k_tri_boxes<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, boxes.as<Box6>(),
-                                                                        enc.as<uint32_t>());
-        k_decode_bounds<<<1, 64, 0, st>>>(enc.as<uint32_t>(), bounds.as<float>());
-        mark("alloc + boxes");
-        if ((rc = lbvh_from_boxes(ctx, m->blas, boxes.as<Box6>(), n, bounds.as<float>(), false, tkeys, tsort, tenc, tdepth)) != RT_OK) break;
-        mark("LBVH");
-        k_gather_tris<<<grid_for(n, B), B, 0, st>>>(m->blas.keys.as<uint64_t>(), m->d_verts.as<rt_vertex>(),
-                                                    m->d_idx.as<uint32_t>(), n, m->tris.as<TriRec>());
-        k_normal_records<<<grid_for(n, B), B, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, m->normals.as<TriRec>());
-        if (hipGetLastError() != hipSuccess) {
-            rt_set_error("BLAS build kernels failed");
-            rc = RT_ERR_HIP;
-            break;
-        }
-        // Split references (rt_refs.h): how many boxes every triangle is validated against.  One each -- every scene of rounds 1 - 4 --
-        // leaves the model as it was; otherwise the boxes by primitive (the canonical walk validates against them) and, below, the
-        // references as the leaves the production tree is built from.
-        m->n_recs = n;
-        m->rec_boxes.release(); m->ref_off.release(); m->ref_boxes.release();
-        DevBuf r_scan, r_prim, r_keys, r_sorted, r_sort_tmp, r_leaf_box, r_leaf_prim;
-        uint32_t n_refs = n;
-        uint32_t *d_count = bt.extra.as<uint32_t>(), *d_off = d_count + ref_words;
-        {
-            void *scan_tmp = (void *)(d_off + ref_words);
-            const size_t scan_room = (size_t)1 << 20;
-            k_ref_count<<<grid_for(n + 1, B), B, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, bounds.as<float>(), d_count);
-            size_t scan_bytes = 0;
-            if (rocprim::exclusive_scan(nullptr, scan_bytes, d_count, d_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st) != hipSuccess) { rt_set_error("reference scan failed"); rc = RT_ERR_HIP; break; }
-            if (scan_bytes > scan_room) { if ((rc = r_scan.reserve(scan_bytes)) != RT_OK) break; scan_tmp = r_scan.p; }
-            if (rocprim::exclusive_scan(scan_tmp, scan_bytes, d_count, d_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st) != hipSuccess) { rt_set_error("reference scan failed"); rc = RT_ERR_HIP; break; }
-            uint32_t *back = ctx->pinned ? ctx->pinned : &n_refs;
-            if (hipMemcpyAsync(back, d_off + n, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                rt_set_error("reference count read-back failed");
-                rc = RT_ERR_HIP;
-                break;
-            }
-            n_refs = *back;
-            r_scan.release();
-            // up to RT_REF_MAX_PIECES references per triangle: beyond 2^32 / 128 triangles the 32-bit scan can wrap past a plausible
-            // total, so such a mesh has its counts summed again in 64 bits
-            if ((uint64_t)n * RT_REF_MAX_PIECES > 0xFFFFFFFFull) {
-                DevBuf sum64;
-                unsigned long long total64 = 0;
-                if ((rc = sum64.reserve(8)) != RT_OK) break;
-                if (hipMemsetAsync(sum64.p, 0, 8, st) != hipSuccess) { rt_set_error("reference count (64-bit) failed"); rc = RT_ERR_HIP; break; }
-                k_sum64<<<1024, B, 0, st>>>(d_count, n, sum64.as<unsigned long long>());
-                if (hipMemcpyAsync(&total64, sum64.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                    rt_set_error("reference count (64-bit) failed");
-                    rc = RT_ERR_HIP;
-                    break;
-                }
-                if (total64 != (unsigned long long)n_refs) { rt_set_error("split references: %llu for %u triangles", total64, n); rc = RT_ERR_UNSUPPORTED; break; }
-            }
-        }
-        if (n_refs != n) {
-            if (n_refs < n || n_refs > (1u << (32 - RT_NODE_SHIFT))) { rt_set_error("split references: %u for %u triangles", n_refs, n); rc = RT_ERR_UNSUPPORTED; break; }
-            if ((rc = m->ref_off.reserve(4 * ((size_t)n + 1))) != RT_OK) break;
-            if (hipMemcpyAsync(m->ref_off.p, d_off, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, st) != hipSuccess) { rt_set_error("reference offsets copy failed"); rc = RT_ERR_HIP; break; }
-            if ((rc = m->ref_boxes.reserve(24 * (size_t)n_refs)) != RT_OK || (rc = r_prim.reserve(4 * (size_t)n_refs)) != RT_OK) break;
-            k_ref_emit<<<grid_for(n, B), B, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, bounds.as<float>(), m->ref_off.as<uint32_t>(),
-                                                    m->ref_boxes.as<float>(), r_prim.as<uint32_t>());
-            if (ctx->verbose) fprintf(stderr, "[dxr_amd]   BLAS %u triangles -> %u references\n", n, n_refs);
-        }
-        const bool split_layout = n_refs > n && ctx->opt_split_refs && ctx->use_ploc;
-        if (split_layout) {
-            // the references in Morton order: the leaves of the production tree
-            if ((rc = r_keys.reserve(8 * (size_t)n_refs)) != RT_OK || (rc = r_sorted.reserve(8 * (size_t)n_refs)) != RT_OK ||
-                (rc = r_leaf_box.reserve(24 * (size_t)n_refs)) != RT_OK || (rc = r_leaf_prim.reserve(4 * (size_t)n_refs)) != RT_OK) break;
-            k_ref_keys<<<grid_for(n_refs, B), B, 0, st>>>(m->ref_boxes.as<float>(), n_refs, bounds.as<float>(), r_keys.as<uint64_t>());
-            size_t sort_bytes = 0;
-            if (rocprim::radix_sort_keys(nullptr, sort_bytes, r_keys.as<uint64_t>(), r_sorted.as<uint64_t>(), n_refs, 32, 62, st) != hipSuccess ||
-                (rc = r_sort_tmp.reserve(sort_bytes)) != RT_OK ||
-                rocprim::radix_sort_keys(r_sort_tmp.p, sort_bytes, r_keys.as<uint64_t>(), r_sorted.as<uint64_t>(), n_refs, 32, 62, st) != hipSuccess) {
-                if (rc == RT_OK) { rt_set_error("reference sort failed"); rc = RT_ERR_HIP; }
-                break;
-            }
-            k_ref_leaves<<<grid_for(n_refs, B), B, 0, st>>>(r_sorted.as<uint64_t>(), n_refs, m->ref_boxes.as<float>(), r_prim.as<uint32_t>(),
-                                                           r_leaf_box.as<float>(), r_leaf_prim.as<uint32_t>());
-        }
-        // production traversal layout: re-cluster the same leaves with PLOC (rt_bvh_ploc.hip), then collapse the binary
-        // tree into wide quantised nodes (rt_bvh_wide.hip); tiny meshes and option fast_bvh=lbvh collapse the LBVH itself
-        mark("gather");
-        bool ploc_done = false;
-        if (ctx->use_ploc) {
-            rc = split_layout ? rt_build_ploc_layout(ctx, m, &ploc_done, n_refs, r_leaf_box.as<float>(), r_leaf_prim.as<uint32_t>())
-                              : rt_build_ploc_layout(ctx, m, &ploc_done);
-            // PLOC's nearest-neighbour rounds make no progress on boxes whose surface is not finite (NaN / inf vertices,
-            // extents that overflow): such a mesh keeps the LBVH as its traversal layout.  rt_build_ploc_layout may give up AFTER k_ploc_tris
-            // had rewritten m->tris in PLOC order (the collapse that follows it can refuse a tree too), so the records are gathered again
-            // in LBVH order whatever the mesh: that is the order the collapse below and k_ref_mark_records index
-            if (rc == RT_ERR_STATE || (rc == RT_OK && ctx->opt_fail_ploc_rounds)) {      // (the option: tests force this path)
-                rc = RT_OK;
-                ploc_done = false;
-                if (split_layout) {
-                    // the split-reference path had grown m->tris for one record per REFERENCE (DevBuf::reserve keeps no contents):
-                    // back to one record per triangle
-                    m->rec_boxes.release();
-                    m->n_recs = n;
-                    if ((rc = m->tris.reserve(sizeof(TriRec) * (size_t)n)) != RT_OK) break;
-                }
-                k_gather_tris<<<grid_for(n, B), B, 0, st>>>(m->blas.keys.as<uint64_t>(), m->d_verts.as<rt_vertex>(),
-                                                            m->d_idx.as<uint32_t>(), n, m->tris.as<TriRec>());
-            }
-            if (rc != RT_OK) break;
-        }
-        mark("PLOC + wide layout");
-        if (!ploc_done && (rc = rt_build_wide_from_lbvh(ctx, m->blas, false, ctx->leaf_max)) != RT_OK) break;
-        if (n_refs > n && !(ploc_done && split_layout)) {
-            // a layout with one record per triangle (LBVH; PLOC with the option split_refs=0): split triangles are validated by primitive
-            m->n_recs = n;
-            k_ref_mark_records<<<grid_for(n, B), B, 0, st>>>(m->tris.as<TriRec>(), n, m->ref_off.as<uint32_t>());
-        }
-        r_prim.release(); r_keys.release(); r_sorted.release(); r_sort_tmp.release(); r_leaf_box.release(); r_leaf_prim.release();
-        mark("wide layout (LBVH)");
-        if ((rc = lbvh_collect(ctx, m->blas)) != RT_OK) break;
-        m->built = true;
-    } while (0);
-    boxes.release(); enc.release(); bounds.release(); tkeys.release(); tsort.release(); tenc.release(); tdepth.release();
+    PhaseClock clock{ctx};
+    const int rc = blas_steps(ctx, m, clock);          // (its buffers are gone when it returns, whichever way)
     drop_build_arena_if_large(ctx);
-    mark("free");
+    clock.mark("free");
     return rc;
 }
 
@@ -764,67 +830,43 @@ int rt_build_tlas(rt_context *ctx, rt_scene *s)
         if (!identity)
             for (uint32_t c = 0; c * INST_BOX_REFS < 3u * m->n_tris; c++) items.push_back(make_uint2(i, c));
     }
-    BuildTemps bt;
-    DevBuf &boxes = bt.boxes, &enc = bt.enc, &bounds = bt.bounds, &tkeys = bt.tkeys, &tsort = bt.tsort, &tenc = bt.tenc, &tdepth = bt.tdepth;
-    // (k_instance_boxes' work memory, a slice of the build arena: per-instance encoded bounds, the forward transforms, the work list)
-    const size_t ienc_bytes = (6 * sizeof(uint32_t) * (size_t)n + 255) & ~(size_t)255, ixf_bytes = (12 * sizeof(float) * (size_t)n + 255) & ~(size_t)255;
-    int rc = RT_OK;
-    do {
-        if ((rc = take_build_temps(ctx, n, bt, ienc_bytes + ixf_bytes + items.size() * sizeof(uint2))) != RT_OK) break;
-        uint32_t *const ienc = bt.extra.as<uint32_t>();
-        float *const ixf = (float *)((char *)bt.extra.p + ienc_bytes);
-        uint2 *const iitems = (uint2 *)((char *)bt.extra.p + ienc_bytes + ixf_bytes);
-        if ((rc = s->d_inst.reserve(sizeof(InstanceRec) * (size_t)n)) != RT_OK) break;
-        if ((rc = boxes.reserve(sizeof(Box6) * (size_t)n)) != RT_OK) break;
-        if ((rc = enc.reserve(6 * sizeof(uint32_t))) != RT_OK) break;
-        if ((rc = bounds.reserve(6 * sizeof(float))) != RT_OK) break;
-        if (hipMemcpyAsync(s->d_inst.p, s->h_inst.data(), sizeof(InstanceRec) * n, hipMemcpyHostToDevice, st) != hipSuccess) {
-            rt_set_error("instance upload failed");
-            rc = RT_ERR_HIP;
-            break;
-        }
-        // world boxes: of the transformed instances from their vertices, then all of them into the records and the leaf boxes
-        k_instance_boxes_init<<<grid_for(6 * n, 256), 256, 0, st>>>(ienc, n);        // (a transformed instance without triangles keeps the empty box)
-        if (!items.empty()) {
-            xf.resize(12 * (size_t)n);
-            for (uint32_t i = 0; i < n; i++) memcpy(&xf[12 * (size_t)i], s->inst[i].xform, 12 * sizeof(float));
-            if (hipMemcpyAsync(ixf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipMemcpyAsync(iitems, items.data(), items.size() * sizeof(uint2), hipMemcpyHostToDevice, st) != hipSuccess) {
-                rt_set_error("instance upload failed");
-                rc = RT_ERR_HIP;
-                break;
-            }
-            k_instance_boxes<<<(uint32_t)items.size(), BOUNDS_BLOCK, 0, st>>>(s->d_inst.as<InstanceRec>(), ixf, iitems, ienc);
-        }
-        k_instance_boxes_finish<<<grid_for(n, 256), 256, 0, st>>>(s->d_inst.as<InstanceRec>(), ienc, boxes.as<Box6>(), n);
-        if (hipMemcpyAsync(hb.data(), boxes.p, sizeof(Box6) * n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            rt_set_error("instance box read-back failed");
-            rc = RT_ERR_HIP;
-            break;
-        }
-        for (uint32_t i = 0; i < n; i++)
-            for (int c = 0; c < 3; c++) { s->h_inst[i].wlo[c] = hb[i].lo[c]; s->h_inst[i].whi[c] = hb[i].hi[c]; }
-        k_init_bounds<<<1, 64, 0, st>>>(enc.as<uint32_t>());
-        k_box_bounds<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(boxes.as<Box6>(), n, enc.as<uint32_t>());
-        k_decode_bounds<<<1, 64, 0, st>>>(enc.as<uint32_t>(), bounds.as<float>());
-        if ((rc = lbvh_from_boxes(ctx, s->tlas, boxes.as<Box6>(), n, bounds.as<float>(), true, tkeys, tsort, tenc, tdepth)) != RT_OK) break;
-        // the TLAS is walked in the same four-wide layout (a single instance: the root is the leaf of instance 0)
-        if ((rc = rt_build_wide_from_lbvh(ctx, s->tlas, true, 1)) != RT_OK) break;
-        if ((rc = lbvh_collect(ctx, s->tlas)) != RT_OK) break;
-        // a step leaves at most three siblings behind; two-level walks add the TLAS path and the sentinel that marks the
-        // bottom of a BLAS walk
-        s->two_level = !(n == 1 && (s->h_inst[0].flags & RT_INST_IDENTITY));
-        s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;
-        // the canonical traversal (parity / counting kernels and the deep-stack path of the fast one) keeps
-        // 128-entry private stacks per structure
-        uint32_t canon = s->tlas.max_depth;
-        for (uint32_t i = 0; i < n; i++) canon = s->inst[i].model->blas.max_depth > canon ? s->inst[i].model->blas.max_depth : canon;
-        if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); rc = RT_ERR_UNSUPPORTED; break; }
-        if (ctx->verbose)
-            fprintf(stderr, "[dxr_amd] TLAS %u instances depth %u; deepest BLAS layout depth %u (%s); stack need %u; %s walk\n", n,
-                    s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
-    } while (0);
-    boxes.release(); enc.release(); bounds.release(); tkeys.release(); tsort.release(); tenc.release(); tdepth.release();
-    bt.extra.release();
-    return rc;
+    TlasTemps t;
+    const size_t n_items = items.size();
+    RT_TRY(take_build_temps(ctx, n, t, [n, n_items](Carver &c, TlasTemps &tt) { carve_tlas(c, n, n_items, tt); }));
+    RT_TRY(s->d_inst.reserve(sizeof(InstanceRec) * (size_t)n));
+    HIP_TRY(hipMemcpyAsync(s->d_inst.p, s->h_inst.data(), sizeof(InstanceRec) * n, hipMemcpyHostToDevice, st));
+    // world boxes: of the transformed instances from their vertices, then all of them into the records and the leaf boxes
+    k_instance_boxes_init<<<grid_for(6 * n, 256), 256, 0, st>>>(t.inst_enc, n);        // (a transformed instance without triangles keeps the empty box)
+    if (!items.empty()) {
+        xf.resize(12 * (size_t)n);
+        for (uint32_t i = 0; i < n; i++) memcpy(&xf[12 * (size_t)i], s->inst[i].xform, 12 * sizeof(float));
+        HIP_TRY(hipMemcpyAsync(t.inst_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.inst_items, items.data(), items.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        k_instance_boxes<<<(uint32_t)items.size(), BOUNDS_BLOCK, 0, st>>>(s->d_inst.as<InstanceRec>(), t.inst_xf, t.inst_items, t.inst_enc);
+    }
+    k_instance_boxes_finish<<<grid_for(n, 256), 256, 0, st>>>(s->d_inst.as<InstanceRec>(), t.inst_enc, t.boxes, n);
+    HIP_TRY(hipMemcpyAsync(hb.data(), t.boxes, sizeof(Box6) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n; i++)
+        for (int c = 0; c < 3; c++) { s->h_inst[i].wlo[c] = hb[i].lo[c]; s->h_inst[i].whi[c] = hb[i].hi[c]; }
+    k_init_bounds<<<1, 64, 0, st>>>(t.enc);
+    k_box_bounds<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, n, t.enc);
+    k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
+    RT_TRY(lbvh_from_boxes(ctx, s->tlas, n, t));
+    // the TLAS is walked in the same four-wide layout (a single instance: the root is the leaf of instance 0)
+    RT_TRY(rt_build_wide_from_lbvh(ctx, s->tlas, true, 1));
+    RT_TRY(lbvh_collect(ctx, s->tlas));
+    // a step leaves at most three siblings behind; two-level walks add the TLAS path and the sentinel that marks the
+    // bottom of a BLAS walk
+    s->two_level = !(n == 1 && (s->h_inst[0].flags & RT_INST_IDENTITY));
+    s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;
+    // the canonical traversal (parity / counting kernels and the deep-stack path of the fast one) keeps
+    // 128-entry private stacks per structure
+    uint32_t canon = s->tlas.max_depth;
+    for (uint32_t i = 0; i < n; i++) canon = s->inst[i].model->blas.max_depth > canon ? s->inst[i].model->blas.max_depth : canon;
+    if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); return RT_ERR_UNSUPPORTED; }
+    if (ctx->verbose)
+        fprintf(stderr, "[dxr_amd] TLAS %u instances depth %u; deepest BLAS layout depth %u (%s); stack need %u; %s walk\n", n,
+                s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
+    return RT_OK;
 }

@@ -47,12 +47,6 @@ __device__ __forceinline__ float merged_area(const Box6 &a, const Box6 &b)
     return dx * dy + dy * dz + dz * dx;
 }
 
-// a piece of the build's one temporary allocation
-struct View {
-    void *p = nullptr;
-    template <class T> T *as() const { return (T *)p; }
-};
-
 // where the clustering stands before round r (device memory, one entry per round of a batch)
 struct PlocRound { uint32_t c, next_node, cur, error; };
 constexpr uint32_t PLOC_TAIL = 2048, TAIL_BLOCK = 1024, PLOC_MAX_BATCH = 64;   // (tail at 4096: 0.20 ms in the one workgroup; a multi-kernel round costs ~12 us)
@@ -347,15 +341,46 @@ __global__ void k_ploc_tris(const uint64_t *__restrict__ keys, const uint32_t *_
 
 inline unsigned gr(size_t n) { return (unsigned)((n + PB - 1) / PB); }
 
+// Every temporary of the build is carved out of ONE allocation, the context's build arena (hipMalloc / hipFree synchronise the
+// device and cost more than the kernels of a small build).  The cluster arrays of the rounds, up to `left`, are free once the tree
+// stands and serve the collapse into wide nodes as its scratch.
+struct PlocTemps {
+    PlocArrays pa;
+    PlocRound *result;           // where a batch of rounds stopped: the entry behind pa.round's PLOC_MAX_BATCH + 1
+    uint32_t *offset;
+    size_t scratch_bytes;        // from pa.cl_node[0]
+};
+void carve_ploc(Carver &c, uint32_t n, PlocTemps &t)
+{
+    const size_t nn2 = 2 * (size_t)n - 1, scratch_from = c.offset;
+    PlocArrays &pa = t.pa;
+    for (int k = 0; k < 2; k++) pa.cl_node[k] = c.take<uint32_t>(n);
+    for (int k = 0; k < 2; k++) pa.cl_box[k] = c.take<Box6>(n);
+    pa.nn = c.take<uint32_t>(n);
+    pa.flags = c.take<uint32_t>(n);
+    pa.tally = c.take<uint64_t>(gr(n));
+    (void)c.take<char>(64 * (size_t)n);          // (only widens what the collapse uses as its scratch: rt_wide_temp_bytes)
+    t.scratch_bytes = c.offset - scratch_from;
+    pa.left = c.take<uint32_t>(n - 1);
+    pa.right = c.take<uint32_t>(n - 1);
+    pa.node_box = c.take<Box6>(nn2);
+    pa.size = c.take<uint32_t>(nn2);
+    pa.parent = c.take<uint32_t>(nn2);
+    t.offset = c.take<uint32_t>(nn2);
+    pa.round = c.take<PlocRound>(PLOC_MAX_BATCH + 2);
+    t.result = pa.round ? pa.round + PLOC_MAX_BATCH + 1 : nullptr;
+    pa.arrivals = c.take<uint32_t>(1);
+}
+
 }  // namespace
 
-// bytes of temporaries rt_build_ploc_layout slices out of the context's build arena (an upper estimate: the
-// scan scratch is small next to the rest)
+// bytes of temporaries rt_build_ploc_layout slices out of the context's build arena
 size_t rt_ploc_temp_bytes(uint32_t n)
 {
-    const size_t nn2 = 2 * (size_t)n;
-    return 8 * (size_t)n + 2 * sizeof(Box6) * (size_t)n + 8 * (size_t)n + 8 * ((size_t)n / PB + 1) + 64 * (size_t)n + 8 * (size_t)n + sizeof(Box6) * nn2 + 12 * nn2 +
-           sizeof(PlocRound) * (PLOC_MAX_BATCH + 2) + 16 + 16 * 256;
+    Carver sizing(nullptr);
+    PlocTemps t;
+    carve_ploc(sizing, n, t);
+    return sizing.offset;
 }
 
 // Rebuilds m->tris and m->blas.wide / root_code / fast_depth from a PLOC tree.  The canonical arrays
@@ -366,99 +391,64 @@ int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, uint32_t n_le
     *done = false;
     if (n < 2 * ctx->leaf_max + 2) return RT_OK;          // tiny meshes: the LBVH layout is as good as any
     hipStream_t st = ctx->stream;
-    // every temporary of the build is carved out of ONE allocation (hipMalloc / hipFree synchronise the
-    // device and cost more than the kernels of a small build)
-    View cl_node[2], cl_box[2], nn, flags, tally, wide_extra, left, right, node_box, size, parent, offset, state;
-    int rc = RT_OK;
-    do {
-        const size_t nn2 = 2 * (size_t)n - 1;
-        struct Want { View *v; size_t bytes; };
-        const Want wants[] = {{&cl_node[0], 4 * (size_t)n}, {&cl_node[1], 4 * (size_t)n}, {&cl_box[0], sizeof(Box6) * (size_t)n}, {&cl_box[1], sizeof(Box6) * (size_t)n},
-                              {&nn, 4 * (size_t)n}, {&flags, 4 * (size_t)n}, {&tally, 8 * (size_t)gr(n)},
-                              {&wide_extra, 64 * (size_t)n},           // (only widens the slice the collapse uses as its scratch: rt_wide_temp_bytes)
-                              {&left, 4 * (size_t)(n - 1)}, {&right, 4 * (size_t)(n - 1)},
-                              {&node_box, sizeof(Box6) * nn2}, {&size, 4 * nn2}, {&parent, 4 * nn2}, {&offset, 4 * nn2},
-                              {&state, sizeof(PlocRound) * (PLOC_MAX_BATCH + 2) + 16}};
-        size_t total = 0;
-        for (const Want &w : wants) total += (w.bytes + 255) & ~(size_t)255;
-        if ((rc = ctx->build_arena.reserve(total)) != RT_OK) break;      // normally already there (rt_ploc_temp_bytes)
-        size_t at = 0;
-        for (const Want &w : wants) { w.v->p = (char *)ctx->build_arena.p + at; at += (w.bytes + 255) & ~(size_t)255; }
+    const size_t nn2 = 2 * (size_t)n - 1;
+    RT_TRY(ctx->build_arena.reserve(rt_ploc_temp_bytes(n)));      // normally already there (take_build_temps)
+    Carver arena(ctx->build_arena.p);
+    PlocTemps t;
+    carve_ploc(arena, n, t);
+    const PlocArrays &pa = t.pa;
+    // 68 KiB of dynamic LDS: above the default 64 KiB limit of a launch (the attribute is per device, set every build)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ploc_tail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(TailLds)));
 
-        PlocArrays pa;
-        pa.nn = nn.as<uint32_t>(); pa.flags = flags.as<uint32_t>(); pa.tally = tally.as<uint64_t>();
-        pa.round = state.as<PlocRound>();
-        PlocRound *d_result = pa.round + PLOC_MAX_BATCH + 1;
-        pa.arrivals = (uint32_t *)(d_result + 1);
-        for (int k = 0; k < 2; k++) { pa.cl_node[k] = cl_node[k].as<uint32_t>(); pa.cl_box[k] = cl_box[k].as<Box6>(); }
-        pa.left = left.as<uint32_t>(); pa.right = right.as<uint32_t>(); pa.size = size.as<uint32_t>(); pa.parent = parent.as<uint32_t>();
-        pa.node_box = node_box.as<Box6>();
-        // 68 KiB of dynamic LDS: above the default 64 KiB limit of a launch (the attribute is per device, set every build)
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_ploc_tail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(TailLds)) != hipSuccess) {
-            rt_set_error("PLOC tail: cannot reserve %zu bytes of LDS", sizeof(TailLds));
-            rc = RT_ERR_HIP;
-            break;
+    if (leaf_box6) {          // records and their boxes for every reference
+        RT_TRY(m->tris.reserve(sizeof(TriRec) * (size_t)n));
+        RT_TRY(m->rec_boxes.reserve(24 * (size_t)n));
+    }
+    k_ploc_init<<<gr(n), PB, 0, st>>>(m->blas.nodes.as<rt_bvh_node>(), leaf_box6, n, pa.cl_node[0], pa.cl_box[0], pa.size, pa.parent, pa.round, pa.arrivals);
+    k_ploc_leaf_boxes<<<gr(n), PB, 0, st>>>(pa.cl_box[0], n, pa.node_box);
+    // Rounds are launched in batches without looking at the cluster count: every launch covers the count the batch
+    // started with (workgroups past the live count leave at once), a round past the tail threshold costs two empty
+    // launches, and the tail kernel closes the batch.  A round keeps ~0.76 of its clusters on the scenes measured;
+    // the estimate below assumes 0.78 and a batch that falls short is simply followed by another.
+    PlocRound res = {n, n, 0u, 0u};
+    for (int batchno = 0; batchno < 4096; batchno++) {
+        uint32_t rounds = 0;
+        for (double x = (double)res.c; x > (double)PLOC_TAIL && rounds < PLOC_MAX_BATCH; x *= 0.78) rounds++;
+        if (rounds > 0 && rounds < PLOC_MAX_BATCH) rounds++;
+        if (ctx->build_batch && rounds > ctx->build_batch) rounds = ctx->build_batch;      // (tests: force short batches)
+        for (uint32_t r = 0; r < rounds; r++) {
+            k_ploc_pair<<<gr(res.c), PB, 0, st>>>(pa, r);
+            k_ploc_apply<<<gr(res.c), PB, 0, st>>>(pa, r, n);
         }
-
-        if (leaf_box6) {          // records and their boxes for every reference
-            if ((rc = m->tris.reserve(sizeof(TriRec) * (size_t)n)) != RT_OK || (rc = m->rec_boxes.reserve(24 * (size_t)n)) != RT_OK) break;
+        k_ploc_tail<<<1, TAIL_BLOCK, sizeof(TailLds), st>>>(pa, rounds, n, t.result);
+        PlocRound *host = ctx->pinned ? (PlocRound *)ctx->pinned : &res;      // page-locked: no staging copy
+        HIP_TRY(hipMemcpyAsync(host, t.result, sizeof(PlocRound), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipGetLastError());
+        const uint32_t before = res.c;
+        res = *host;
+        if (res.error || (res.c > PLOC_TAIL && res.c >= before)) {
+            rt_set_error("PLOC made no progress (%u clusters)", res.c);
+            return RT_ERR_STATE;
         }
-        k_ploc_init<<<gr(n), PB, 0, st>>>(m->blas.nodes.as<rt_bvh_node>(), leaf_box6, n, cl_node[0].as<uint32_t>(), cl_box[0].as<Box6>(),
-                                         size.as<uint32_t>(), parent.as<uint32_t>(), pa.round, pa.arrivals);
-        k_ploc_leaf_boxes<<<gr(n), PB, 0, st>>>(cl_box[0].as<Box6>(), n, node_box.as<Box6>());
-        // Rounds are launched in batches without looking at the cluster count: every launch covers the count the batch
-        // started with (workgroups past the live count leave at once), a round past the tail threshold costs two empty
-        // launches, and the tail kernel closes the batch.  A round keeps ~0.76 of its clusters on the scenes measured;
-        // the estimate below assumes 0.78 and a batch that falls short is simply followed by another.
-        PlocRound res = {n, n, 0u, 0u};
-        for (int batchno = 0; batchno < 4096; batchno++) {
-            uint32_t rounds = 0;
-            for (double x = (double)res.c; x > (double)PLOC_TAIL && rounds < PLOC_MAX_BATCH; x *= 0.78) rounds++;
-            if (rounds > 0 && rounds < PLOC_MAX_BATCH) rounds++;
-            if (ctx->build_batch && rounds > ctx->build_batch) rounds = ctx->build_batch;      // (tests: force short batches)
-            for (uint32_t r = 0; r < rounds; r++) {
-                k_ploc_pair<<<gr(res.c), PB, 0, st>>>(pa, r);
-                k_ploc_apply<<<gr(res.c), PB, 0, st>>>(pa, r, n);
-            }
-            k_ploc_tail<<<1, TAIL_BLOCK, sizeof(TailLds), st>>>(pa, rounds, n, d_result);
-            PlocRound *host = ctx->pinned ? (PlocRound *)ctx->pinned : &res;      // page-locked: no staging copy
-            if (hipMemcpyAsync(host, d_result, sizeof(PlocRound), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
-                hipGetLastError() != hipSuccess) {
-                rt_set_error("PLOC rounds failed: %s", hipGetErrorString(hipGetLastError()));
-                rc = RT_ERR_HIP;
-                break;
-            }
-            const uint32_t before = res.c;
-            res = *host;
-            if (res.error || (res.c > PLOC_TAIL && res.c >= before)) {
-                rt_set_error("PLOC made no progress (%u clusters)", res.c);
-                rc = RT_ERR_STATE;
-                break;
-            }
-            if (res.c <= PLOC_TAIL) break;
-            // short of the tail: the next batch starts from where this one stopped
-            if (hipMemcpyAsync(pa.round, d_result, sizeof(PlocRound), hipMemcpyDeviceToDevice, st) != hipSuccess) { rt_set_error("PLOC: state copy failed"); rc = RT_ERR_HIP; break; }
-        }
-        if (rc != RT_OK) break;
-        const uint32_t c = res.c, next_node = res.next_node;
-        if (c != 1 || next_node != 2 * n - 1) {
-            rt_set_error("PLOC did not converge (%u clusters, %u nodes)", c, next_node);
-            rc = RT_ERR_STATE;
-            break;
-        }
-        k_ploc_offsets<<<gr(nn2), PB, 0, st>>>(left.as<uint32_t>(), right.as<uint32_t>(), size.as<uint32_t>(), parent.as<uint32_t>(), n,
-                                              offset.as<uint32_t>());
-        k_ploc_tris<<<gr(n), PB, 0, st>>>(m->blas.keys.as<uint64_t>(), leaf_prim, leaf_box6, leaf_box6 ? m->ref_off.as<uint32_t>() : nullptr,
-                                         m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), offset.as<uint32_t>(), n, m->tris.as<TriRec>(),
-                                         leaf_box6 ? m->rec_boxes.as<float>() : nullptr);
-        if (hipGetLastError() != hipSuccess) { rt_set_error("PLOC layout kernels failed"); rc = RT_ERR_HIP; break; }
-        // four-wide nodes from the binary tree (root = the last node created); the cluster arrays of the rounds are free now
-        // and serve as its scratch
-        if ((rc = rt_build_wide_layout(ctx, m->blas, n, 2 * n - 2, left.as<uint32_t>(), right.as<uint32_t>(), parent.as<uint32_t>(), (const float *)node_box.p,
-                                       size.as<uint32_t>(), offset.as<uint32_t>(), nullptr, ctx->leaf_max, cl_node[0].p,
-                                       (size_t)((char *)left.p - (char *)cl_node[0].p))) != RT_OK) break;
-        if (leaf_box6) m->n_recs = n;
-        *done = true;
-    } while (0);
-    return rc;
+        if (res.c <= PLOC_TAIL) break;
+        // short of the tail: the next batch starts from where this one stopped
+        HIP_TRY(hipMemcpyAsync(pa.round, t.result, sizeof(PlocRound), hipMemcpyDeviceToDevice, st));
+    }
+    if (res.c != 1 || res.next_node != 2 * n - 1) {
+        rt_set_error("PLOC did not converge (%u clusters, %u nodes)", res.c, res.next_node);
+        return RT_ERR_STATE;
+    }
+    k_ploc_offsets<<<gr(nn2), PB, 0, st>>>(pa.left, pa.right, pa.size, pa.parent, n, t.offset);
+    k_ploc_tris<<<gr(n), PB, 0, st>>>(m->blas.keys.as<uint64_t>(), leaf_prim, leaf_box6, leaf_box6 ? m->ref_off.as<uint32_t>() : nullptr,
+                                     m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), t.offset, n, m->tris.as<TriRec>(),
+                                     leaf_box6 ? m->rec_boxes.as<float>() : nullptr);
+    HIP_TRY(hipGetLastError());
+    // four-wide nodes from the binary tree (root = the last node created); the cluster arrays of the rounds are free now
+    // and serve as its scratch
+    RT_TRY(rt_build_wide_layout(ctx, m->blas, n, 2 * n - 2, pa.left, pa.right, pa.parent, (const float *)pa.node_box, pa.size, t.offset, nullptr,
+                                ctx->leaf_max, pa.cl_node[0], t.scratch_bytes));
+    if (leaf_box6) m->n_recs = n;
+    *done = true;
+    return RT_OK;
 }

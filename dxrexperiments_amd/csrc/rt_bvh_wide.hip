@@ -440,16 +440,55 @@ __global__ void __launch_bounds__(WB) k_lbvh_to_tree(const rt_bvh_node *__restri
 }
 
 inline unsigned gr(size_t n) { return (unsigned)((n + WB - 1) / WB); }
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// scratch of the collapse: two frontiers, the children of a frontier, one tally per workgroup of a level, the level table, and (option
+// wide_sah) the cost records with their arrival counters
+struct WideTemps {
+    size_t fcap;                 // entries of a frontier
+    uint32_t *frontier[2], *kids, *tally;
+    WideState *ws;
+    SahRecord *sah;
+    uint32_t *arrive;
+};
+void carve_wide(Carver &c, uint32_t n, WideTemps &t)
+{
+    t.fcap = (size_t)n / 2 + 2;
+    for (int k = 0; k < 2; k++) t.frontier[k] = c.take<uint32_t>(t.fcap);
+    t.kids = c.take<uint32_t>(RT_WIDE * t.fcap);
+    t.tally = c.take<uint32_t>(gr(t.fcap));
+    t.ws = c.take<WideState>(1);
+    t.sah = c.take<SahRecord>(n);
+    t.arrive = c.take<uint32_t>(n);
+}
+
+// the canonical LBVH as a tree in cluster numbering (rt_build_wide_from_lbvh), and behind it the scratch of its collapse
+struct LbvhTreeTemps {
+    uint32_t *left, *right;
+    Box6 *box;
+    uint32_t *size, *offset, *leaf_prim, *parent;
+    void *scratch; size_t scratch_bytes;
+};
+void carve_lbvh_tree(Carver &c, uint32_t n, LbvhTreeTemps &t)
+{
+    const size_t nn2 = 2 * (size_t)n - 1;
+    t.left = c.take<uint32_t>(n - 1);
+    t.right = c.take<uint32_t>(n - 1);
+    t.box = c.take<Box6>(nn2);
+    t.size = c.take<uint32_t>(nn2);
+    t.offset = c.take<uint32_t>(nn2);
+    t.leaf_prim = c.take<uint32_t>(nn2);
+    t.parent = c.take<uint32_t>(nn2);
+    t.scratch_bytes = rt_wide_temp_bytes(n);
+    t.scratch = c.take<char>(t.scratch_bytes);
+}
 
 }  // namespace
 
-// two frontiers, the children of a frontier, one tally per workgroup of a level, the level table
 size_t rt_wide_temp_bytes(uint32_t n)
 {
-    const size_t f = (size_t)n / 2 + 2;
-    return 2 * up256(4 * f) + up256(4 * RT_WIDE * f) + up256(4 * (size_t)gr(f)) + up256(sizeof(WideState)) +
-           up256(sizeof(SahRecord) * (size_t)n) + up256(4 * (size_t)n);
+    Carver sizing(nullptr);
+    WideTemps t;
+    carve_wide(sizing, n, t);
+    return sizing.offset;
 }
 
 int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, uint32_t n, uint32_t root, const uint32_t *left, const uint32_t *right, const uint32_t *parent,
@@ -469,79 +508,67 @@ int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, uint32_t n, uint32_t root,
         RT_TRY(bv.wide.reserve(sizeof(WNode)));
         return RT_OK;
     }
-    const size_t fcap = (size_t)n / 2 + 2;
-    const size_t need = rt_wide_temp_bytes(n);
     DevBuf own;                        // only if the caller's slice is too small
-    char *p = (char *)tmp;
-    if (need > tmp_bytes) { RT_TRY(own.reserve(need)); p = (char *)own.p; }
-    uint32_t *frontier[2] = {(uint32_t *)p, (uint32_t *)(p + up256(4 * fcap))};
-    p += 2 * up256(4 * fcap);
-    uint32_t *kids = (uint32_t *)p; p += up256(4 * RT_WIDE * fcap);
-    uint32_t *tally = (uint32_t *)p; p += up256(4 * (size_t)gr(fcap));
-    WideState *ws = (WideState *)p; p += up256(sizeof(WideState));
-    SahRecord *sah = (SahRecord *)p; p += up256(sizeof(SahRecord) * (size_t)n);
-    uint32_t *arrive = (uint32_t *)p;
-    int rc = RT_OK;
-    do {
-        if ((rc = bv.wide.reserve(sizeof(WNode) * (size_t)(n - 1))) != RT_OK) break;
-        if (ctx->wide_sah && parent) {
-            // which binary nodes become wide nodes, which leaves, and how a wide node spends its slots: one bottom-up pass
-            if (hipMemsetAsync(arrive, 0, 4 * (size_t)(n - 1), st) != hipSuccess) { rt_set_error("wide layout: memset failed"); rc = RT_ERR_HIP; break; }
-            k_wide_sah<<<gr(n), WB, 0, st>>>(t, parent, sah, arrive, ctx->sah_node, ctx->sah_prim);
-            t.sah = sah;
+    if (rt_wide_temp_bytes(n) > tmp_bytes) { RT_TRY(own.reserve(rt_wide_temp_bytes(n))); tmp = own.p; }
+    Carver scratch(tmp);
+    WideTemps w;
+    carve_wide(scratch, n, w);
+    const size_t fcap = w.fcap;
+    uint32_t *const *frontier = w.frontier;
+    RT_TRY(bv.wide.reserve(sizeof(WNode) * (size_t)(n - 1)));
+    if (ctx->wide_sah && parent) {
+        // which binary nodes become wide nodes, which leaves, and how a wide node spends its slots: one bottom-up pass
+        HIP_TRY(hipMemsetAsync(w.arrive, 0, 4 * (size_t)(n - 1), st));
+        k_wide_sah<<<gr(n), WB, 0, st>>>(t, parent, w.sah, w.arrive, ctx->sah_node, ctx->sah_prim);
+        t.sah = w.sah;
+    }
+    k_wide_top<<<1, TOPW, 0, st>>>(t, frontier[0], frontier[1], w.ws, root, (uint32_t)fcap, bv.wide.as<WNode>());
+    // Levels are launched in batches without looking at their sizes: a level has at most eight times the nodes of the
+    // one before (and never more than fcap), a level past the end of the tree costs two empty launches.  The first
+    // batch is sized for a tree half again as deep as a balanced one; the host reads the level table after each batch.
+    // k_wide_top has certainly built levels 0 .. TOP_SURE-1 (a level has at most 8^l nodes, it takes every level of <= TOPW)
+    uint32_t lvl = TOP_SURE, levels = 0, wide_n = 0;
+    uint64_t bound = 2 * TOPW;                            // upper bound of the frontier at level lvl: 8^TOP_SURE
+    uint32_t log8 = 0;
+    for (uint32_t m = n; m > 1; m >>= 3) log8++;
+    uint32_t batch = 4 + log8 + log8 / 2;
+    batch = batch > TOP_SURE + 2 ? batch - TOP_SURE : 2; // (the first levels are k_wide_top's)
+    if (ctx->build_batch) batch = ctx->build_batch;      // (tests: force short batches)
+    WideState host_state;
+    for (bool done = false; !done;) {
+        const uint32_t end = lvl + batch < RT_WIDE_MAX_LEVELS + 1 ? lvl + batch : RT_WIDE_MAX_LEVELS + 1;
+        for (; lvl < end; lvl++) {
+            const unsigned blocks = gr((size_t)(bound < fcap ? bound : fcap));
+            k_wide_expand<<<blocks, WB, 0, st>>>(t, frontier[lvl & 1], w.ws, lvl, w.kids, w.tally, (uint32_t)fcap);
+            k_wide_emit<<<blocks, WB, 0, st>>>(t, frontier[lvl & 1], w.ws, lvl, w.kids, w.tally, frontier[(lvl & 1) ^ 1], bv.wide.as<WNode>());
+            bound = bound < fcap ? bound * RT_WIDE : fcap;
         }
-        k_wide_top<<<1, TOPW, 0, st>>>(t, frontier[0], frontier[1], ws, root, (uint32_t)fcap, bv.wide.as<WNode>());
-        // Levels are launched in batches without looking at their sizes: a level has at most eight times the nodes of the
-        // one before (and never more than fcap), a level past the end of the tree costs two empty launches.  The first
-        // batch is sized for a tree half again as deep as a balanced one; the host reads the level table after each batch.
-        // k_wide_top has certainly built levels 0 .. TOP_SURE-1 (a level has at most 8^l nodes, it takes every level of <= TOPW)
-        uint32_t lvl = TOP_SURE, levels = 0, wide_n = 0;
-        uint64_t bound = 2 * TOPW;                            // upper bound of the frontier at level lvl: 8^TOP_SURE
-        uint32_t log8 = 0;
-        for (uint32_t m = n; m > 1; m >>= 3) log8++;
-        uint32_t batch = 4 + log8 + log8 / 2;
-        batch = batch > TOP_SURE + 2 ? batch - TOP_SURE : 2; // (the first levels are k_wide_top's)
-        if (ctx->build_batch) batch = ctx->build_batch;      // (tests: force short batches)
-        WideState host_state;
-        bool done = false;
-        while (!done) {
-            const uint32_t end = lvl + batch < RT_WIDE_MAX_LEVELS + 1 ? lvl + batch : RT_WIDE_MAX_LEVELS + 1;
-            for (; lvl < end; lvl++) {
-                const unsigned blocks = gr((size_t)(bound < fcap ? bound : fcap));
-                k_wide_expand<<<blocks, WB, 0, st>>>(t, frontier[lvl & 1], ws, lvl, kids, tally, (uint32_t)fcap);
-                k_wide_emit<<<blocks, WB, 0, st>>>(t, frontier[lvl & 1], ws, lvl, kids, tally, frontier[(lvl & 1) ^ 1], bv.wide.as<WNode>());
-                bound = bound < fcap ? bound * RT_WIDE : fcap;
-            }
-            const size_t bytes = offsetof(WideState, level) + sizeof(WideLevel) * (lvl + 1);
-            WideState *back = (ctx->pinned && bytes <= 64 * sizeof(uint32_t)) ? (WideState *)ctx->pinned : &host_state;      // page-locked: no staging copy
-            if (hipMemcpyAsync(back, ws, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
-                hipGetLastError() != hipSuccess) {
-                rt_set_error("wide layout failed: %s", hipGetErrorString(hipGetLastError()));
-                rc = RT_ERR_HIP;
-                break;
-            }
-            const WideLevel *table = back->level;
-            if (back->error) { rt_set_error("wide layout: the frontier of level %u does not fit (%u primitives)", back->error, n); rc = RT_ERR_STATE; break; }
-            for (uint32_t l = 0; l <= lvl; l++)
-                if (table[l].count == 0) { levels = l; wide_n = table[l].base; done = true; break; }
-            if (!done && lvl >= RT_WIDE_MAX_LEVELS + 1) { rt_set_error("wide layout: deeper than %u levels", RT_WIDE_MAX_LEVELS); rc = RT_ERR_STATE; break; }
-            bound = table[lvl].count;
-            batch = ctx->build_batch ? ctx->build_batch : 8;
-        }
-        if (rc != RT_OK) break;
-        bv.wide_n = wide_n;
-        bv.root_code = 0;
-        bv.fast_depth = (RT_WIDE - 1) * levels;        // a step leaves at most three siblings behind
-    } while (0);
-    own.release();
-    return rc;
+        const size_t bytes = offsetof(WideState, level) + sizeof(WideLevel) * (lvl + 1);
+        WideState *back = (ctx->pinned && bytes <= 64 * sizeof(uint32_t)) ? (WideState *)ctx->pinned : &host_state;      // page-locked: no staging copy
+        HIP_TRY(hipMemcpyAsync(back, w.ws, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipGetLastError());
+        const WideLevel *table = back->level;
+        if (back->error) { rt_set_error("wide layout: the frontier of level %u does not fit (%u primitives)", back->error, n); return RT_ERR_STATE; }
+        for (uint32_t l = 0; l <= lvl && !done; l++)
+            if (table[l].count == 0) { levels = l; wide_n = table[l].base; done = true; }
+        if (!done && lvl >= RT_WIDE_MAX_LEVELS + 1) { rt_set_error("wide layout: deeper than %u levels", RT_WIDE_MAX_LEVELS); return RT_ERR_STATE; }
+        bound = table[lvl].count;
+        batch = ctx->build_batch ? ctx->build_batch : 8;
+    }
+    bv.wide_n = wide_n;
+    bv.root_code = 0;
+    bv.fast_depth = (RT_WIDE - 1) * levels;        // a step leaves at most three siblings behind
+    return RT_OK;
 }
 
 // arena bytes rt_build_wide_from_lbvh takes: the tree in cluster numbering + the scratch of the collapse
 size_t rt_wide_lbvh_temp_bytes(uint32_t n)
 {
-    const size_t nn2 = 2 * (size_t)n;
-    return 2 * up256(4 * (size_t)n) + up256(sizeof(Box6) * nn2) + 4 * up256(4 * nn2) + rt_wide_temp_bytes(n);
+    Carver sizing(nullptr);
+    LbvhTreeTemps t;
+    carve_lbvh_tree(sizing, n, t);
+    return sizing.offset;
 }
 
 int rt_build_wide_from_lbvh(rt_context *ctx, BvhDev &bv, bool tlas, uint32_t leaf_max)
@@ -555,20 +582,12 @@ int rt_build_wide_from_lbvh(rt_context *ctx, BvhDev &bv, bool tlas, uint32_t lea
         RT_TRY(bv.wide.reserve(sizeof(WNode)));
         return RT_OK;
     }
-    const size_t nn2 = 2 * (size_t)n - 1;
-    const size_t tree = 2 * up256(4 * (size_t)(n - 1)) + up256(sizeof(Box6) * nn2) + 4 * up256(4 * nn2);
-    const size_t wide = rt_wide_temp_bytes(n);
-    RT_TRY(ctx->build_arena.reserve(tree + wide));
-    char *p = (char *)ctx->build_arena.p;
-    uint32_t *left = (uint32_t *)p; p += up256(4 * (size_t)(n - 1));
-    uint32_t *right = (uint32_t *)p; p += up256(4 * (size_t)(n - 1));
-    Box6 *box = (Box6 *)p; p += up256(sizeof(Box6) * nn2);
-    uint32_t *size = (uint32_t *)p; p += up256(4 * nn2);
-    uint32_t *offset = (uint32_t *)p; p += up256(4 * nn2);
-    uint32_t *leaf_prim = (uint32_t *)p; p += up256(4 * nn2);
-    uint32_t *parent = (uint32_t *)p; p += up256(4 * nn2);
-    k_lbvh_to_tree<<<gr(nn2), WB, 0, st>>>(bv.nodes.as<rt_bvh_node>(), bv.ranges.as<uint2>(), n, left, right, box, size, offset, leaf_prim, parent);
+    RT_TRY(ctx->build_arena.reserve(rt_wide_lbvh_temp_bytes(n)));
+    Carver arena(ctx->build_arena.p);
+    LbvhTreeTemps t;
+    carve_lbvh_tree(arena, n, t);
+    k_lbvh_to_tree<<<gr(2 * (size_t)n - 1), WB, 0, st>>>(bv.nodes.as<rt_bvh_node>(), bv.ranges.as<uint2>(), n, t.left, t.right, t.box, t.size, t.offset, t.leaf_prim, t.parent);
     HIP_TRY(hipGetLastError());
-    return rt_build_wide_layout(ctx, bv, n, n /* canonical root 0 */, left, right, parent, (const float *)box, size, offset, tlas ? leaf_prim : nullptr,
-                                tlas ? 1u : leaf_max, p, wide);
+    return rt_build_wide_layout(ctx, bv, n, n /* canonical root 0 */, t.left, t.right, t.parent, (const float *)t.box, t.size, t.offset, tlas ? t.leaf_prim : nullptr,
+                                tlas ? 1u : leaf_max, t.scratch, t.scratch_bytes);
 }

@@ -205,6 +205,13 @@ struct rt_denoiser {
     DevBuf out[2], half_out;        // out[0] = pass H, out[1] = pass V (the result, DenoiseCompositor.h:23)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool dispatched = false;
+    ~rt_denoiser()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
 };
 
 extern "C" {
@@ -229,11 +236,6 @@ int rt_denoiser_create(rt_context *ctx, rt_denoiser **out)
 int rt_denoiser_destroy(rt_denoiser *d)
 {
     if (!d) return RT_OK;
-    (void)hipSetDevice(d->ctx->device);
-    (void)hipStreamSynchronize(d->ctx->stream);
-    d->out[0].release(); d->out[1].release(); d->half_out.release();
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
     rt_context *ctx = d->ctx;
     delete d;
     rt_context_release(ctx);

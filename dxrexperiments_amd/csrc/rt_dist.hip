@@ -189,6 +189,15 @@ struct rt_dist {
     std::string rendezvous_file;       // this rank's entry of the one-device-per-rank check (removed on destroy)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;                // an event pair brackets the last collective
+    ~rt_dist()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        if (comm) (void)lib->comm_destroy(comm);
+        if (!rendezvous_file.empty()) unlink(rendezvous_file.c_str());
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
 };
 
 extern "C" {
@@ -257,6 +266,7 @@ int rt_dist_create(rt_context *ctx, int rank, int world, const void *id128, rt_d
         if (chk != RT_OK) {
             // (this rank's entry stays: the other rank on the same device has to find it to fail the same way instead of
             // waiting for RCCL; the next rendezvous on this node sweeps it)
+            d->rendezvous_file.clear();
             delete d;
             return chk;
         }
@@ -266,7 +276,7 @@ int rt_dist_create(rt_context *ctx, int rank, int world, const void *id128, rt_d
     const int rc = lib->comm_init_rank(&d->comm, world, id, rank);
     if (rc != 0) {
         rt_set_error("ncclCommInitRank(rank %d of %d): %s", rank, world, lib->error_string ? lib->error_string(rc) : "RCCL error");
-        if (!d->rendezvous_file.empty()) unlink(d->rendezvous_file.c_str());
+        d->comm = nullptr;
         delete d;
         return RT_ERR_HIP;
     }
@@ -279,13 +289,6 @@ int rt_dist_create(rt_context *ctx, int rank, int world, const void *id128, rt_d
 int rt_dist_destroy(rt_dist *d)
 {
     if (!d) return RT_OK;
-    (void)hipSetDevice(d->ctx->device);
-    (void)hipStreamSynchronize(d->ctx->stream);
-    if (d->comm) (void)d->lib->comm_destroy(d->comm);
-    if (!d->rendezvous_file.empty()) unlink(d->rendezvous_file.c_str());
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    d->gathered.release();
     rt_context *ctx = d->ctx;
     delete d;
     rt_context_release(ctx);

@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/dxr_amd.h"
@@ -41,11 +43,27 @@ void rt_set_error(const char *fmt, ...);
 size_t &rt_alloc_limit_ref();
 static inline size_t rt_alloc_limit() { return rt_alloc_limit_ref(); }
 
-// Owning device allocation; grows on demand, never shrinks.
+// Owning device allocation; grows on demand, never shrinks.  Frees itself when it goes out of scope and moves, never copies: an owner
+// lists no buffers to release, it only selects the device (and joins its stream) before its members die.  None has static or thread storage
+// duration: a hipFree after the runtime has shut down is not acceptable.
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
     bool borrowed = false;       // p points into somebody else's allocation (adopt): never freed here
+    DevBuf() = default;
+    ~DevBuf() { release(); }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes), borrowed(o.borrowed) { o.p = nullptr; o.bytes = 0; o.borrowed = false; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; bytes = o.bytes; borrowed = o.borrowed;
+            o.p = nullptr; o.bytes = 0; o.borrowed = false;
+        }
+        return *this;
+    }
     // use a slice of another allocation; a later reserve() beyond it falls back to an allocation of its own
     void adopt(void *ptr, size_t n) { release(); p = ptr; bytes = n; borrowed = ptr != nullptr; }
     // Grows to at least n bytes (contents are NOT kept).  The new block is allocated BEFORE the old one is freed, so a
@@ -82,6 +100,30 @@ struct DevBuf {
         borrowed = false;
     }
     template <class T> T *as() const { return (T *)p; }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "a DevBuf has one owner");
+
+// An event a function creates and also destroys (an owner's own events are its destructor's business).
+struct ScopedEvent {
+    hipEvent_t e = nullptr;
+    ScopedEvent() = default;
+    ScopedEvent(const ScopedEvent &) = delete;
+    ScopedEvent &operator=(const ScopedEvent &) = delete;
+    ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
+};
+
+// Slices of one allocation, each 256-byte aligned.  A builder describes its temporaries ONCE, as a function that takes a carver and
+// fills a struct of typed pointers; with a null base the same calls only add up the bytes the allocation must hold.
+struct Carver {
+    char *base = nullptr;
+    size_t offset = 0;
+    explicit Carver(void *b) : base((char *)b) {}
+    template <class T> T *take(size_t count)
+    {
+        const size_t at = offset;
+        offset += (sizeof(T) * count + 255) & ~(size_t)255;
+        return base ? (T *)(base + at) : nullptr;
+    }
 };
 
 // ---- device-visible records -------------------------------------------------
@@ -202,6 +244,7 @@ struct rt_context {
     double opt_dist_check_seconds = 5.0;    // dist_check_seconds: how long rt_dist_create waits for the other ranks' device ids
     std::vector<struct rt_pipeline *> deferred;      // pipelines holding frames that render() has accepted and not rendered yet
                                  //   (rt_pipeline_set_deferred): whatever changes what those frames would see flushes them first
+    ~rt_context();               // (rt_api.hip) selects the device and joins the stream; pinned memory, events, an owned stream; then the buffers
 };
 
 struct BvhDev {
@@ -216,7 +259,6 @@ struct BvhDev {
     uint32_t wide_n = 0;
     int root_code = -1;
     uint32_t fast_depth = 0;     // stack entries the traversal layout can need
-    void release() { nodes.release(); keys.release(); parents.release(); ranges.release(); wide.release(); }
 };
 
 struct rt_model {
@@ -233,6 +275,7 @@ struct rt_model {
     DevBuf ref_off, ref_boxes;   // uint32[n_tris + 1], float[6 refs]: the same boxes by primitive (canonical walk, LBVH layout)
     BvhDev blas;
     bool built = false;
+    ~rt_model();                 // (rt_api.hip) selects the device before the buffers go
 };
 
 struct SceneInstance {
@@ -265,6 +308,7 @@ struct rt_scene {
         s.top_n = 0;
         return s;
     }
+    ~rt_scene();                 // (rt_api.hip) selects the device, lets go of the models it retains; then the buffers
 };
 
 // ---- internal entry points shared between translation units ---------------------

@@ -249,6 +249,7 @@ struct rt_pipeline {
     uint32_t last_pixels = 0;
     bool rendered = false;
     uint32_t last_scene_gen = 0;       // generation of the scene last_pd was filled from
+    ~rt_pipeline();                    // (rt_pipeline_host.hip) selects the device and joins the stream; events, pinned memory, the scene it retains; then the buffers
 };
 
 // renders the frames a deferred pipeline holds (rt_pipeline.hip); every entry point that reads or changes what they see calls it first

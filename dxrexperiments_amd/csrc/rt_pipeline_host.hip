@@ -55,27 +55,27 @@ int rt_pipeline_destroy(rt_pipeline *p)
         for (size_t k = 0; k < reg.size(); k++) if (reg[k] == p) { reg.erase(reg.begin() + (long)k); break; }
         p->pending.clear();
     }
-    (void)hipStreamSynchronize(p->ctx->stream);
-    DevBuf *all[] = {&p->d_mats, &p->d_env, &p->accum_own, &p->aov_own, &p->counters, &p->half_out, &p->totals, &p->work, &p->batch_consts, &p->shadow_cache,
-                     &p->sh_hits, &p->sh_O, &p->sh_D, &p->sh_vis};
-    for (DevBuf *b : all) b->release();
-    for (rt_pipeline::LevelBuf &l : p->lv) {
-        DevBuf *lb[] = {&l.O, &l.D, &l.hit, &l.inst, &l.slot_j, &l.jlist, &l.pix, &l.color};
-        for (DevBuf *b : lb) b->release();
-    }
-    for (hipEvent_t e : p->ring) if (e) (void)hipEventDestroy(e);
-    if (p->free_sphere.landed) (void)hipEventDestroy(p->free_sphere.landed);
-    if (p->primary_mode.landed) (void)hipEventDestroy(p->primary_mode.landed);
-    if (p->primary_mode.h_count) (void)hipHostFree(p->primary_mode.h_count);
-    p->retry.release();
-    if (p->free_sphere.h_min) (void)hipHostFree(p->free_sphere.h_min);
-    p->free_sphere.d_min.release();
-    if (p->scene) rt_scene_destroy(p->scene);
     rt_context *ctx = p->ctx;
     delete p;
     rt_context_release(ctx);
     return RT_OK;
 }
+
+}  // extern "C"
+
+rt_pipeline::~rt_pipeline()
+{
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (hipEvent_t e : ring) if (e) (void)hipEventDestroy(e);
+    if (free_sphere.landed) (void)hipEventDestroy(free_sphere.landed);
+    if (primary_mode.landed) (void)hipEventDestroy(primary_mode.landed);
+    if (primary_mode.h_count) (void)hipHostFree(primary_mode.h_count);
+    if (free_sphere.h_min) (void)hipHostFree(free_sphere.h_min);
+    if (scene) rt_scene_destroy(scene);
+}
+
+extern "C" {
 
 const char *rt_pipeline_get_name(const rt_pipeline *p)
 {

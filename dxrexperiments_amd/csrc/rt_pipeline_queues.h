@@ -71,12 +71,10 @@ inline int grow_keep(DevBuf &b, size_t bytes, size_t keep_bytes, hipStream_t st)
     if (keep_bytes && b.p) {
         if (hipMemcpyAsync(bigger.p, b.p, keep_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
             rt_set_error("shadow queue: copy into the grown buffer failed: %s", hipGetErrorString(hipGetLastError()));
-            bigger.release();
             return RT_ERR_HIP;
         }
     }
-    b.release();
-    b = bigger;
+    b = std::move(bigger);
     return RT_OK;
 }
 inline int reserve_shadows(rt_pipeline *p, size_t hits, uint32_t log2, bool compact, size_t keep_hits)

@@ -62,3 +62,90 @@ def test_no_device_memory_leak_and_any_destroy_order(gpu, capi):
     gpu.synchronize()
     leaked = base - free_bytes()
     assert leaked < (8 << 20), "device memory shrank by %d bytes over 30 create/destroy cycles" % leaked
+
+
+RT_ERR_OOM = -5                                                  # include/dxr_amd_types.h
+
+
+def _cable_rays(v, t):
+    """a fixed set of rays from inside the hall: 3000 at the centroids of triangles drawn from the whole mesh (most of them the slivers of
+    cables and slats), 1000 in random directions"""
+    r = np.random.default_rng(11)
+    pos = v["position"].astype(np.float64)
+    eye = np.array([2.0, 3.0, 1.0])
+    aim = pos[t[r.integers(0, t.shape[0], 3000)]].mean(axis=1) - eye
+    d = np.concatenate([aim, r.normal(size=(1000, 3))])
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    o = np.empty((d.shape[0], 4), np.float32)
+    o[:, :3], o[:, 3] = eye, 1e-3
+    dd = np.empty_like(o)
+    dd[:, :3], dd[:, 3] = d, 1e30
+    return o, dd
+
+
+def _build_and_trace(capi, ctx, v, t, rays):
+    model = capi.Model(ctx, v, t)
+    sc = capi.Scene(ctx)
+    try:
+        sc.add_model(model)
+        sc.build()
+        return sc.trace(*rays)
+    finally:
+        sc.close()
+        model.close()
+
+
+def _ladder_of_failed_builds(capi, ctx, v, t, rays):
+    want = _build_and_trace(capi, ctx, v, t, rays)
+    assert np.unique(want["prim"]).size > 500, "the rays hit next to nothing"
+    gc.collect()
+    ctx.synchronize()
+    base = free_bytes()
+    raised, built = [], []
+    try:
+        for k in range(11):
+            capi.lib().rt_debug_set_alloc_limit(1024 * 4 ** k)
+            model = sc = None
+            try:
+                model = capi.Model(ctx, v, t)
+                sc = capi.Scene(ctx)
+                sc.add_model(model)
+                sc.build()
+                built.append(k)
+            except capi.RtError as e:
+                assert e.code == RT_ERR_OOM, "rung %d (limit %d bytes): %r" % (k, 1024 * 4 ** k, e)
+                raised.append(k)
+            finally:
+                if sc is not None:
+                    sc.close()
+                if model is not None:
+                    model.close()
+    finally:
+        capi.lib().rt_debug_set_alloc_limit(0)
+    # 1 KiB does not hold the vertex upload (271 KB), 1 GiB holds every buffer of a 6771-triangle build
+    assert raised and built and raised[0] == 0 and built[-1] == 10, (raised, built)
+    gc.collect()
+    ctx.synchronize()
+    leaked = base - free_bytes()
+    assert leaked < (8 << 20), "device memory shrank by %d bytes over the failed builds of rungs %s" % (leaked, raised)
+    got = _build_and_trace(capi, ctx, v, t, rays)
+    for k in ("t", "u", "v", "prim", "inst"):
+        assert np.array_equal(want[k].view(np.uint32), got[k].view(np.uint32)), k
+    return raised
+
+
+def test_failed_builds_leak_nothing(gpu, capi):
+    """A build that runs out of device memory anywhere -- the vertex upload, the arena, the records, the split references, the reference
+    sort, either layout -- gives back what it had reserved and leaves the context usable.  Every failure is an allocation the host
+    refuses (rt_debug_set_alloc_limit walked up from 1 KiB to 1 GiB in steps of 4x); the mesh is the hall of cables whose triangles
+    are held as split references.  Then the same with the LBVH layout and with one record per triangle, on a second context."""
+    v, t = scenes.stadium_class(5, 0.25, ("hall", "cables", "slats"))
+    rays = _cable_rays(v, t)
+    _ladder_of_failed_builds(capi, gpu, v, t, rays)
+    for name, value in (("fast_bvh", "lbvh"), ("split_refs", 0)):
+        ctx = capi.Context(0)
+        try:
+            ctx.set_option(name, value)
+            _ladder_of_failed_builds(capi, ctx, v, t, rays)
+        finally:
+            ctx.close()
