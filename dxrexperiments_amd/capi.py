@@ -91,6 +91,10 @@ SIGNATURES = {
     "rt_scene_wide_read": (_i, [_p, _i, _p, _p]),
     "rt_debug_wide_write": (_i, [_p, _i, _p, _u32]),
     "rt_scene_build_ms": (_i, [_p, C.POINTER(_f)]),
+    "rt_scene_set_instance_transform": (_i, [_p, _u32, _p]),
+    "rt_scene_set_instance_transforms": (_i, [_p, _u32, _u32, _p]),
+    "rt_scene_update": (_i, [_p]),
+    "rt_scene_update_ms": (_i, [_p, C.POINTER(_f)]),
     "rt_trace_batch": (_i, [_p, _p, _p, _p, _sz, _u32, _u32, _u32, _p, _p, _p, _p, _p, _p, _p]),
     "rt_trace_last_ms": (_i, [_p, C.POINTER(_f)]),
     "rt_pipeline_create": (_i, [_p, _u32, _pp]),
@@ -421,6 +425,27 @@ class Scene:
     def build_ms(self):
         ms = C.c_float()
         _check(lib().rt_scene_build_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def set_transform(self, i, transform=None):
+        """Extension (the reference's RtScene has no such call): a new object-to-world transform for instance i; None = identity.  A built
+        scene is stale until update() or build()."""
+        x = _f32(T.IDENTITY_3X4 if transform is None else transform, 12)
+        _check(lib().rt_scene_set_instance_transform(self.h, i, _ptr(x)))
+
+    def set_transforms(self, first, transforms):
+        """... for instances first .. first + len(transforms) - 1; an entry None = identity"""
+        rows = [T.IDENTITY_3X4 if x is None else x for x in transforms]
+        x = _f32(rows, (-1, 12)) if len(rows) else np.zeros((0, 12), np.float32)
+        _check(lib().rt_scene_set_instance_transforms(self.h, first, x.shape[0], _ptr(x)))
+
+    def update(self):
+        """Extension: applies the pending transforms on the device (instance records, world boxes, TLAS); the scene is then what build() gives"""
+        _check(lib().rt_scene_update(self.h))
+
+    def update_ms(self):
+        ms = C.c_float()
+        _check(lib().rt_scene_update_ms(self.h, C.byref(ms)))
         return ms.value
 
     def bvh(self, which):

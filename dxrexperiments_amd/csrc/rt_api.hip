@@ -470,7 +470,63 @@ int rt_scene_add_model(rt_scene *s, rt_model *m, const float transform3x4[12])
     m->refs++;
     s->inst.push_back(in);
     s->built = false;
+    s->updatable = false;     // the TLAS no longer stands for this instance list: only rt_scene_build brings the scene back
     s->generation++;
+    return RT_OK;
+}
+
+int rt_scene_set_instance_transforms(rt_scene *s, uint32_t first, uint32_t count, const float *transforms3x4)
+{
+    RT_REQUIRE(s && (transforms3x4 || count == 0), "null argument");
+    const size_t n = s->inst.size();
+    if (first > n || count > n - first) {
+        rt_set_error("rt_scene_set_instance_transforms: instances %u .. %llu out of range: the scene has %zu", first, (unsigned long long)first + count, n);
+        return RT_ERR_STATE;
+    }
+    if (count == 0) return RT_OK;
+    RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
+    for (uint32_t k = 0; k < count; k++) memcpy(s->inst[first + k].xform, transforms3x4 + 12 * (size_t)k, sizeof s->inst[0].xform);
+    if (!s->updatable) return RT_OK;                  // never built (or instances added since): the next build reads the stored transforms
+    s->is_pending.resize(n, 0);
+    for (uint32_t i = first; i < first + count; i++)
+        if (!s->is_pending[i]) { s->is_pending[i] = 1; s->pending.push_back(i); }
+    s->built = false;         // stale until rt_scene_update or rt_scene_build: nothing traces a half-applied state
+    return RT_OK;
+}
+
+int rt_scene_set_instance_transform(rt_scene *s, uint32_t instance, const float transform3x4[12])
+{
+    RT_REQUIRE(s && transform3x4, "null argument");
+    if (instance >= s->inst.size()) {
+        rt_set_error("rt_scene_set_instance_transform: instance %u out of range: the scene has %zu", instance, s->inst.size());
+        return RT_ERR_STATE;
+    }
+    return rt_scene_set_instance_transforms(s, instance, 1, transform3x4);
+}
+
+int rt_scene_update(rt_scene *s)
+{
+    RT_REQUIRE(s, "null scene");
+    if (!s->updatable) {
+        rt_set_error("rt_scene_update: the scene has not been built since its last rt_scene_add_model (an update builds no BLAS: rt_scene_build)");
+        return RT_ERR_STATE;
+    }
+    if (s->pending.empty()) return RT_OK;             // nothing to apply: nothing launched, the generation stays
+    rt_context *ctx = s->ctx;
+    RT_TRY(use_device(ctx));
+    RT_TRY(rt_context_flush_deferred(ctx));
+    s->generation++;          // pipelines drop what they cached from the old geometry: shadow-cache occluders, per-pixel entries, the free sphere, the primary-mode samples
+    RT_TRY(rt_update_tlas(ctx, s));                   // (a failure leaves the scene stale and the transforms pending)
+    for (uint32_t i : s->pending) s->is_pending[i] = 0;
+    s->pending.clear();
+    s->built = true;
+    return RT_OK;
+}
+
+int rt_scene_update_ms(const rt_scene *s, float *ms)
+{
+    RT_REQUIRE(s && ms, "null argument");
+    *ms = s->update_ms;
     return RT_OK;
 }
 
@@ -495,11 +551,16 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     HIP_TRY(hipEventRecord(e0.e, ctx->stream));
     s->generation++;          // device arrays are about to be reallocated: pipelines drop what they cached
     for (SceneInstance &in : s->inst) RT_TRY(rt_build_blas(ctx, in.model));
+    s->updatable = false;
     RT_TRY(rt_build_tlas(ctx, s));
+    RT_TRY(rt_upload_blas_bounds(ctx, s));
     HIP_TRY(hipEventRecord(e1.e, ctx->stream));
     HIP_TRY(hipEventSynchronize(e1.e));
     HIP_TRY(hipEventElapsedTime(&s->build_ms, e0.e, e1.e));
     s->built = true;
+    s->updatable = true;
+    s->pending.clear();       // the build has read every stored transform
+    s->is_pending.assign(s->inst.size(), 0);
     return RT_OK;
 }
 
@@ -524,7 +585,7 @@ static const BvhDev *pick_bvh(const rt_scene *s, int which)
 int rt_scene_bvh_info(const rt_scene *s, int which, uint32_t *n_prims, uint32_t *n_nodes, uint32_t *max_depth)
 {
     const BvhDev *b = pick_bvh(s, which);
-    if (!b) { rt_set_error("rt_scene_bvh_info: scene not built or index out of range"); return RT_ERR_STATE; }
+    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_bvh_info")) rt_set_error("rt_scene_bvh_info: scene not built or index out of range"); return RT_ERR_STATE; }
     if (n_prims) *n_prims = b->n;
     if (n_nodes) *n_nodes = 2 * b->n - 1;
     if (max_depth) *max_depth = b->max_depth;
@@ -534,7 +595,7 @@ int rt_scene_bvh_info(const rt_scene *s, int which, uint32_t *n_prims, uint32_t 
 int rt_scene_bvh_read(const rt_scene *s, int which, rt_bvh_node *nodes, uint64_t *sorted_keys, uint32_t *parents)
 {
     const BvhDev *b = pick_bvh(s, which);
-    if (!b) { rt_set_error("rt_scene_bvh_read: scene not built or index out of range"); return RT_ERR_STATE; }
+    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_bvh_read")) rt_set_error("rt_scene_bvh_read: scene not built or index out of range"); return RT_ERR_STATE; }
     RT_TRY(use_device(s->ctx));
     const size_t nn = 2 * (size_t)b->n - 1;
     if (nodes) HIP_TRY(hipMemcpy(nodes, b->nodes.p, sizeof(rt_bvh_node) * nn, hipMemcpyDeviceToHost));
@@ -546,7 +607,7 @@ int rt_scene_bvh_read(const rt_scene *s, int which, rt_bvh_node *nodes, uint64_t
 int rt_scene_wide_info(const rt_scene *s, int which, uint32_t *n_nodes, int32_t *root_code, uint32_t *n_records)
 {
     const BvhDev *b = pick_bvh(s, which);
-    if (!b) { rt_set_error("rt_scene_wide_info: scene not built or index out of range"); return RT_ERR_STATE; }
+    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_wide_info")) rt_set_error("rt_scene_wide_info: scene not built or index out of range"); return RT_ERR_STATE; }
     if (n_nodes) *n_nodes = b->wide_n;
     if (root_code) *root_code = b->root_code;
     if (n_records) *n_records = which < 0 ? 0u : s->inst[which].model->n_recs;
@@ -563,7 +624,7 @@ int rt_wide_layout_info(uint32_t *width, uint32_t *node_bytes)
 int rt_scene_wide_read(const rt_scene *s, int which, void *nodes, void *records)
 {
     const BvhDev *b = pick_bvh(s, which);
-    if (!b) { rt_set_error("rt_scene_wide_read: scene not built or index out of range"); return RT_ERR_STATE; }
+    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_wide_read")) rt_set_error("rt_scene_wide_read: scene not built or index out of range"); return RT_ERR_STATE; }
     RT_TRY(use_device(s->ctx));
     if (nodes && b->wide_n) HIP_TRY(hipMemcpy(nodes, b->wide.p, sizeof(WNode) * (size_t)b->wide_n, hipMemcpyDeviceToHost));
     if (records && which >= 0) HIP_TRY(hipMemcpy(records, s->inst[which].model->tris.p, sizeof(TriRec) * (size_t)s->inst[which].model->n_recs, hipMemcpyDeviceToHost));
@@ -574,7 +635,7 @@ int rt_scene_wide_read(const rt_scene *s, int which, void *nodes, void *records)
 int rt_scene_refs_info(const rt_scene *s, int which, uint32_t *n_tris, uint32_t *n_refs)
 {
     const BvhDev *b = pick_bvh(s, which);
-    if (!b || which < 0) { rt_set_error("rt_scene_refs_info: scene not built or index out of range"); return RT_ERR_STATE; }
+    if (!b || which < 0) { if (!rt_scene_stale_error(s, "rt_scene_refs_info")) rt_set_error("rt_scene_refs_info: scene not built or index out of range"); return RT_ERR_STATE; }
     const rt_model *m = s->inst[which].model;
     if (n_tris) *n_tris = m->n_tris;
     if (n_refs) *n_refs = m->ref_off.p ? (uint32_t)(m->ref_boxes.bytes / 24) : 0u;
@@ -584,7 +645,7 @@ int rt_scene_refs_info(const rt_scene *s, int which, uint32_t *n_tris, uint32_t 
 int rt_scene_refs_read(const rt_scene *s, int which, uint32_t *ref_off, float *ref_boxes, float *record_boxes)
 {
     const BvhDev *b = pick_bvh(s, which);
-    if (!b || which < 0) { rt_set_error("rt_scene_refs_read: scene not built or index out of range"); return RT_ERR_STATE; }
+    if (!b || which < 0) { if (!rt_scene_stale_error(s, "rt_scene_refs_read")) rt_set_error("rt_scene_refs_read: scene not built or index out of range"); return RT_ERR_STATE; }
     const rt_model *m = s->inst[which].model;
     if (!m->ref_off.p) { rt_set_error("rt_scene_refs_read: no triangle of this model is split"); return RT_ERR_STATE; }
     RT_TRY(use_device(s->ctx));
@@ -609,7 +670,10 @@ int rt_debug_wide_write(rt_scene *s, int which, const void *nodes, uint32_t n_no
 int rt_scene_instance_info(const rt_scene *s, uint32_t instance, float world_box[6], float world_to_object[12])
 {
     RT_REQUIRE(s, "null scene");
-    if (!s->built || instance >= s->h_inst.size()) { rt_set_error("scene not built or instance out of range"); return RT_ERR_STATE; }
+    if (!s->built || instance >= s->h_inst.size()) {
+        if (!rt_scene_stale_error(s, "rt_scene_instance_info")) rt_set_error("scene not built or instance out of range");
+        return RT_ERR_STATE;
+    }
     const InstanceRec &r = s->h_inst[instance];
     if (world_box) for (int c = 0; c < 3; c++) { world_box[c] = r.wlo[c]; world_box[3 + c] = r.whi[c]; }
     if (world_to_object) memcpy(world_to_object, r.inv, sizeof r.inv);
@@ -630,7 +694,7 @@ int rt_trace_batch(rt_context *ctx, const rt_scene *s, const float *origin_tmin,
                    uint32_t *inst, uint32_t *cnt_nodes, uint32_t *cnt_tris)
 {
     RT_REQUIRE(ctx && s, "null argument");
-    if (!s->built) { rt_set_error("rt_trace_batch: scene not built"); return RT_ERR_STATE; }
+    if (!s->built) { if (!rt_scene_stale_error(s, "rt_trace_batch")) rt_set_error("rt_trace_batch: scene not built"); return RT_ERR_STATE; }
     RT_REQUIRE(kernel == RT_TRACE_FAST || kernel == RT_TRACE_CANONICAL, "unknown kernel selector");
     if (n == 0) return RT_OK;
     RT_REQUIRE(origin_tmin && dir_tmax, "null ray arrays");

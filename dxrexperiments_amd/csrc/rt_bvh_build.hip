@@ -23,6 +23,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rt_refs.h"
+#include "rt_xform.h"
 
 namespace {
 
@@ -106,7 +107,16 @@ __global__ void k_box_bounds(const Box6 *__restrict__ boxes, uint32_t n, uint32_
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     Box6 b;
     bool valid = i < n;
-    if (valid) b = boxes[i];
+    if (valid) {
+        // the structure's box holds BOTH corners of every primitive box (oracle_bvh.h box_merge): the same thing unless a box is the
+        // empty, inverted one -- an instance none of whose vertices has a number in some axis -- whose corners then reach to both infinities
+        b = boxes[i];
+        for (int c = 0; c < 3; c++) {
+            const float lo = b.lo[c], hi = b.hi[c];
+            b.lo[c] = fminf(lo, hi);
+            b.hi[c] = fmaxf(lo, hi);
+        }
+    }
     reduce_bounds(b, valid, enc);
 }
 
@@ -713,30 +723,7 @@ int rt_build_blas(rt_context *ctx, rt_model *m)
     return rc;
 }
 
-// world-to-object = inverse of the affine 3x4 (adjugate / determinant in fp32,
-// operation order fixed: see DESIGN.md "Instances")
-static void invert3x4(const float m[12], float o[12])
-{
-    float a = m[0], b = m[1], c = m[2];
-    float d = m[4], e = m[5], f = m[6];
-    float g = m[8], h = m[9], i = m[10];
-    float A = e * i - f * h;
-    float B = f * g - d * i;
-    float C = d * h - e * g;
-    float det = a * A;
-    det = det + b * B;
-    det = det + c * C;
-    float id = 1.0f / det;
-    o[0] = A * id; o[1] = (c * h - b * i) * id; o[2] = (b * f - c * e) * id;
-    o[4] = B * id; o[5] = (a * i - c * g) * id; o[6] = (c * d - a * f) * id;
-    o[8] = C * id; o[9] = (b * g - a * h) * id; o[10] = (a * e - b * d) * id;
-    for (int r = 0; r < 3; r++) {
-        float s = o[4 * r + 0] * m[3];
-        s = s + o[4 * r + 1] * m[7];
-        s = s + o[4 * r + 2] * m[11];
-        o[4 * r + 3] = -s;
-    }
-}
+// (invert3x4, the world-to-object matrix of an instance: rt_xform.h -- one text for this file's host and device code)
 
 // The world box of a transformed instance: the exact box of its triangles' transformed vertices (oracle_bvh.h
 // scene_build; the box of the BLAS box's eight transformed corners is up to 1.6x wider in footprint for a rotated mesh, and a third
@@ -868,5 +855,206 @@ int rt_build_tlas(rt_context *ctx, rt_scene *s)
     if (ctx->verbose)
         fprintf(stderr, "[dxr_amd] TLAS %u instances depth %u; deepest BLAS layout depth %u (%s); stack need %u; %s walk\n", n,
                 s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
+    return RT_OK;
+}
+
+// ---- rt_scene_update: the transforms set since the last build, applied on the device ----
+//
+// Stands in for the generators' update path (libs/DXRFramework/Helpers/TopLevelASGenerator.h:144-163 `updateOnly`), which the reference's
+// RtScene never calls.  The definition is "update == build": the canonical TLAS is a pure function of the instance boxes and every traversal
+// returns the same bits on any tree, so the TLAS is rebuilt -- by the build's own steps, into the scene's own buffers --
+// from boxes of which only the pending instances' are computed anew.  Only the pending transforms and their indices go up; the records are
+// rewritten, and the work list of the world boxes is made, on the device.
+
+// The BLAS box of every instance's model: what an instance set (back) to the identity takes as its world box.
+int rt_upload_blas_bounds(rt_context *ctx, rt_scene *s)
+{
+    const size_t n = s->inst.size();
+    s->h_blas_bounds.resize(6 * n);                    // (a member: alive whenever the copy runs)
+    for (size_t i = 0; i < n; i++) memcpy(&s->h_blas_bounds[6 * i], s->inst[i].model->blas.bounds, 6 * sizeof(float));
+    RT_TRY(s->blas_bounds.reserve(6 * n * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(s->blas_bounds.p, s->h_blas_bounds.data(), 6 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return RT_OK;
+}
+
+namespace {
+
+constexpr unsigned UPD_BLOCK = 256;
+constexpr unsigned UPD_BACK_WORDS = 20;      // inv[12], wlo[3], root_code, whi[3], flags: the head of an InstanceRec
+static_assert(offsetof(InstanceRec, flags) == 4 * (UPD_BACK_WORDS - 1), "the read-back of an update is the head of the record");
+
+// One lane per pending instance: the record's inverse, flags and (empty or BLAS) box, as rt_build_tlas writes them on the host; and the
+// (slot, chunk of INST_BOX_REFS vertex references) work items of the transformed ones, compacted into `items`: a wave-wide prefix sum of
+// the lanes' chunk counts, ONE atomic per wave that has any (a ballot says so), every lane then writes its own run.  The order of the
+// list depends on the order of the atomics; the boxes made from it do not (min / max).  max_items = the chunks of all pending
+// instances, transformed or not: the host's bound of the list and the next launch's grid.
+__global__ void __launch_bounds__(UPD_BLOCK) k_update_records(InstanceRec *__restrict__ inst, const float *__restrict__ blas_bounds,
+                                                              const uint32_t *__restrict__ pend_idx, const float *__restrict__ pend_xf, uint32_t n_pending,
+                                                              uint32_t *__restrict__ enc, uint2 *__restrict__ items, uint32_t *__restrict__ n_items,
+                                                              uint32_t max_items)
+{
+    const uint32_t slot = blockIdx.x * UPD_BLOCK + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63u;
+    uint32_t chunks = 0;
+    if (slot < n_pending) {
+        const uint32_t i = pend_idx[slot];
+        float m[12], inv[12];
+        for (int k = 0; k < 12; k++) m[k] = pend_xf[12u * (size_t)slot + k];
+        const bool identity = is_identity3x4(m);
+        InstanceRec &r = inst[i];
+        if (identity)
+            for (int k = 0; k < 12; k++) inv[k] = m[k];              // (the floats as given: a -0 stays one)
+        else
+            invert3x4(m, inv);
+        const float inf = __uint_as_float(0x7f800000u);
+        for (int k = 0; k < 12; k++) r.inv[k] = inv[k];
+        for (int c = 0; c < 3; c++) {
+            r.wlo[c] = identity ? blas_bounds[6u * (size_t)i + c] : inf;     // (a transformed instance: empty until k_update_apply)
+            r.whi[c] = identity ? blas_bounds[6u * (size_t)i + 3 + c] : -inf;
+            enc[6u * (size_t)slot + c] = ENC_POS_INF;
+            enc[6u * (size_t)slot + 3 + c] = ENC_NEG_INF;
+        }
+        r.flags = identity ? RT_INST_IDENTITY : 0u;
+        if (!identity) chunks = (3u * r.n_prims + INST_BOX_REFS - 1u) / INST_BOX_REFS;
+    }
+    // (every lane of the block is here: the block is whole waves and nothing has returned)
+    if (__ballot(chunks != 0u) == 0ull) return;        // wave-uniform
+    uint32_t incl = chunks;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t below = __shfl_up(incl, o, 64);
+        if (lane >= (unsigned)o) incl += below;
+    }
+    const uint32_t total = __shfl(incl, 63, 64);
+    uint32_t base = 0;
+    if (lane == 63u) base = atomicAdd(n_items, total);
+    base = __shfl(base, 63, 64);
+    const uint32_t first = base + (incl - chunks);
+    for (uint32_t c = 0; c < chunks; c++)
+        if (first + c < max_items) items[first + c] = make_uint2(slot, c);
+}
+
+// k_instance_boxes for the items of that list: the same arithmetic on the same vertex references, the transform and the encoded box by
+// pending slot.  The grid is the host's bound; blocks beyond the list's count have nothing to do.
+__global__ void __launch_bounds__(BOUNDS_BLOCK) k_update_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx,
+                                                              const float *__restrict__ pend_xf, const uint2 *__restrict__ items,
+                                                              const uint32_t *__restrict__ n_items, uint32_t *__restrict__ enc)
+{
+    if (blockIdx.x >= *n_items) return;                // (block-uniform)
+    const uint2 it = items[blockIdx.x];
+    const InstanceRec &in = inst[pend_idx[it.x]];
+    const float *m = pend_xf + 12u * (size_t)it.x;
+    const uint32_t refs = 3u * in.n_prims;
+    const float inf = __uint_as_float(0x7f800000u);
+    Box6 b;
+    for (int c = 0; c < 3; c++) { b.lo[c] = inf; b.hi[c] = -inf; }
+    for (uint32_t k = it.y * INST_BOX_REFS + threadIdx.x; k < refs && k < (it.y + 1u) * INST_BOX_REFS; k += BOUNDS_BLOCK) {
+        const rt_float3 p = in.verts[in.indices[k]].position;
+        for (int r = 0; r < 3; r++) {
+            float w = m[4 * r + 0] * p.x;
+            w = w + m[4 * r + 1] * p.y;
+            w = w + m[4 * r + 2] * p.z;
+            w = w + m[4 * r + 3];
+            b.lo[r] = fminf(b.lo[r], w);
+            b.hi[r] = fmaxf(b.hi[r], w);
+        }
+    }
+    reduce_bounds(b, true, enc + 6u * (size_t)it.x);
+}
+
+// the boxes into the records of the pending transformed instances; the head of every pending record into the read-back for h_inst
+__global__ void k_update_apply(InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx, uint32_t n_pending,
+                               const uint32_t *__restrict__ enc, uint32_t *__restrict__ back)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_pending) return;
+    InstanceRec &r = inst[pend_idx[slot]];
+    if (!(r.flags & RT_INST_IDENTITY))
+        for (int c = 0; c < 3; c++) { r.wlo[c] = f_dec(enc[6u * (size_t)slot + c]); r.whi[c] = f_dec(enc[6u * (size_t)slot + 3 + c]); }
+    const uint32_t *head = reinterpret_cast<const uint32_t *>(&r);
+    for (unsigned k = 0; k < UPD_BACK_WORDS; k++) back[UPD_BACK_WORDS * (size_t)slot + k] = head[k];
+}
+
+// every instance's box (an untouched one's as it stands in its record) -> the TLAS builder's leaf boxes
+__global__ void k_update_leaf_boxes(const InstanceRec *__restrict__ inst, Box6 *__restrict__ boxes, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int c = 0; c < 3; c++) { boxes[i].lo[c] = inst[i].wlo[c]; boxes[i].hi[c] = inst[i].whi[c]; }
+}
+
+// (+ the pending indices and transforms, their encoded boxes, the work list and its count)
+struct UpdateTemps : LbvhTemps {
+    uint32_t *pend_idx;
+    float *pend_xf;
+    uint32_t *pend_enc;
+    uint2 *items;
+    uint32_t *n_items;
+};
+void carve_update(Carver &c, uint32_t n, size_t n_pending, size_t max_items, UpdateTemps &t)
+{
+    carve_lbvh(c, n, t);
+    t.pend_idx = c.take<uint32_t>(n_pending);
+    t.pend_xf = c.take<float>(12 * n_pending);
+    t.pend_enc = c.take<uint32_t>(6 * n_pending);
+    t.items = c.take<uint2>(max_items);
+    t.n_items = c.take<uint32_t>(1);
+}
+
+}  // namespace
+
+int rt_update_tlas(rt_context *ctx, rt_scene *s)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)s->inst.size();
+    const size_t np = s->pending.size();
+    std::vector<float> xf(12 * np);                    // (alive, as the index list is, until the last synchronisation below)
+    size_t max_items = 0;
+    for (size_t k = 0; k < np; k++) {
+        const SceneInstance &in = s->inst[s->pending[k]];
+        memcpy(&xf[12 * k], in.xform, 12 * sizeof(float));
+        max_items += (3 * (size_t)in.model->n_tris + INST_BOX_REFS - 1) / INST_BOX_REFS;
+    }
+    if (max_items > 0x7fffffffu) { rt_set_error("rt_scene_update: %zu work items for the world boxes: the limit is 2^31 - 1", max_items); return RT_ERR_UNSUPPORTED; }
+    UpdateTemps t;
+    RT_TRY(take_build_temps(ctx, n, t, [n, np, max_items](Carver &c, UpdateTemps &ut) { carve_update(c, n, np, max_items, ut); }));
+    RT_TRY(s->update_back.reserve(sizeof(uint32_t) * UPD_BACK_WORDS * (size_t)n));     // (for all of them at once: never grows again)
+    std::vector<uint32_t> back(UPD_BACK_WORDS * np);
+    ScopedEvent e0, e1;
+    HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventCreate(&e1.e));
+    HIP_TRY(hipEventRecord(e0.e, st));
+    HIP_TRY(hipMemcpyAsync(t.pend_idx, s->pending.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
+    InstanceRec *inst = s->d_inst.as<InstanceRec>();
+    k_update_records<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->blas_bounds.as<float>(), t.pend_idx, t.pend_xf, (uint32_t)np, t.pend_enc,
+                                                                   t.items, t.n_items, (uint32_t)max_items);
+    if (max_items) k_update_boxes<<<(uint32_t)max_items, BOUNDS_BLOCK, 0, st>>>(inst, t.pend_idx, t.pend_xf, t.items, t.n_items, t.pend_enc);
+    k_update_apply<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.pend_idx, (uint32_t)np, t.pend_enc, s->update_back.as<uint32_t>());
+    k_update_leaf_boxes<<<grid_for(n, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.boxes, n);
+    // from here on: rt_build_tlas' own steps, into the buffers the scene has (the same sizes: nothing is allocated)
+    k_init_bounds<<<1, 64, 0, st>>>(t.enc);
+    k_box_bounds<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, n, t.enc);
+    k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
+    RT_TRY(lbvh_from_boxes(ctx, s->tlas, n, t));
+    RT_TRY(rt_build_wide_from_lbvh(ctx, s->tlas, true, 1));
+    HIP_TRY(hipEventRecord(e1.e, st));
+    // the final join: it brings back the rewritten records' heads with the TLAS' depth and bounds
+    HIP_TRY(hipMemcpyAsync(back.data(), s->update_back.p, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    RT_TRY(lbvh_collect(ctx, s->tlas));
+    HIP_TRY(hipEventElapsedTime(&s->update_ms, e0.e, e1.e));
+    for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[s->pending[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
+    uint32_t deepest = 0, canon = s->tlas.max_depth;
+    for (uint32_t i = 0; i < n; i++) {
+        const BvhDev &b = s->inst[i].model->blas;
+        deepest = b.fast_depth > deepest ? b.fast_depth : deepest;
+        canon = b.max_depth > canon ? b.max_depth : canon;
+    }
+    s->two_level = !(n == 1 && (s->h_inst[0].flags & RT_INST_IDENTITY));
+    s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;
+    if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); return RT_ERR_UNSUPPORTED; }
+    if (ctx->verbose)
+        fprintf(stderr, "[dxr_amd] TLAS update: %zu of %u instances, depth %u; stack need %u; %s walk\n", np, n, s->tlas.max_depth, s->stack_need,
+                s->two_level ? "two-level" : "single-level");
     return RT_OK;
 }

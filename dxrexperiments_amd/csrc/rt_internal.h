@@ -291,11 +291,19 @@ struct rt_scene {
     DevBuf d_inst;
     BvhDev tlas;
     bool built = false;
-    uint32_t generation = 0;     // bumped by every add_model / build: device pointers cached from an older one are stale
+    uint32_t generation = 0;     // bumped by every add_model / build / update: device pointers cached from an older one are stale
     float build_ms = 0.0f;
     uint32_t stack_need = 0;     // traversal stack entries a ray can hold at once
     bool two_level = true;       // false: one identity instance, rays walk its BLAS directly
     bool has_refs = false;       // some model of the scene holds triangles as several references (rt_refs.h)
+    // rt_scene_set_instance_transform(s) / rt_scene_update: rigid animation without a rebuild of the instance list
+    bool updatable = false;      // the TLAS stands for THIS instance list (built, and no rt_scene_add_model since): an update can apply transforms
+    std::vector<uint32_t> pending;       // instances whose transform a setter has changed since the last build / update (each once); while
+    std::vector<uint8_t> is_pending;     //   there are any the scene is STALE: built == false, nothing traces or reads it
+    std::vector<float> h_blas_bounds;    // float[6 n]: the BLAS box of every instance's model, as uploaded to ...
+    DevBuf blas_bounds;          // ... the box an instance set (back) to the identity takes (written by every build)
+    DevBuf update_back;          // the first 20 words (inv, world box, flags) of the records an update rewrote, on their way to h_inst
+    float update_ms = 0.0f;
     SceneDev dev() const
     {
         SceneDev s;
@@ -316,6 +324,19 @@ struct rt_scene {
 // rt_bvh_build.hip
 int rt_build_blas(rt_context *ctx, rt_model *m);
 int rt_build_tlas(rt_context *ctx, rt_scene *s);
+// after rt_build_tlas: the per-instance BLAS boxes rt_update_tlas reads on the device
+int rt_upload_blas_bounds(rt_context *ctx, rt_scene *s);
+// applies s->pending to the instance records, their world boxes and the TLAS, on the device
+int rt_update_tlas(rt_context *ctx, rt_scene *s);
+
+// A scene whose transforms were set and not applied yet: says so (the message names them) and returns true.
+static inline bool rt_scene_stale_error(const rt_scene *s, const char *who)
+{
+    if (!s || s->built || s->pending.empty()) return false;
+    rt_set_error("%s: %zu instance transform%s pending (rt_scene_set_instance_transform): rt_scene_update or rt_scene_build applies them", who,
+                 s->pending.size(), s->pending.size() == 1 ? "" : "s");
+    return true;
+}
 
 // rt_bvh_ploc.hip
 // n_leaves / leaf_box6 / leaf_prim: the leaves to cluster in Morton order -- nullptr: the canonical leaves (one per triangle); else the

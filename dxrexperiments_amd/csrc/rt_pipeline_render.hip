@@ -208,7 +208,7 @@ static int render_region(rt_pipeline *p, uint32_t width, uint32_t height, uint32
                          uint32_t band_rows, uint32_t band_rank, uint32_t band_world, const rt_per_frame_constants *frames = nullptr, uint32_t n_frames = 1)
 {
     RT_REQUIRE(p, "null pipeline");
-    if (!p->scene || !p->scene->built) { rt_set_error("render: acceleration structures not built"); return RT_ERR_STATE; }
+    if (!p->scene || !p->scene->built) { if (!rt_scene_stale_error(p->scene, "render")) rt_set_error("render: acceleration structures not built"); return RT_ERR_STATE; }
     if (!p->accum) { rt_set_error("render: no output resource"); return RT_ERR_STATE; }
     if (!frames && !p->have_pfc) { rt_set_error("render: update() has not been called"); return RT_ERR_STATE; }
     if (!frames) { frames = &p->pfc; n_frames = 1; }
@@ -494,7 +494,7 @@ int rt_pipeline_render(rt_pipeline *p, uint32_t width, uint32_t height)
     RT_REQUIRE(p, "null pipeline");
     if (p->deferred_max > 1 && p->kind == RT_PIPELINE_PROGRESSIVE) {
         // the checks render_region would make now, so that a bad call fails where it is made and not at some later flush
-        if (!p->scene || !p->scene->built) { rt_set_error("render: acceleration structures not built"); return RT_ERR_STATE; }
+        if (!p->scene || !p->scene->built) { if (!rt_scene_stale_error(p->scene, "render")) rt_set_error("render: acceleration structures not built"); return RT_ERR_STATE; }
         if (!p->accum) { rt_set_error("render: no output resource"); return RT_ERR_STATE; }
         if (!p->have_pfc) { rt_set_error("render: update() has not been called"); return RT_ERR_STATE; }
         if (p->mats.empty()) { rt_set_error("render: no material"); return RT_ERR_STATE; }

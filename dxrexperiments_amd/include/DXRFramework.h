@@ -167,6 +167,25 @@ namespace DXRFramework
             ThrowIfFailed(rt_scene_build(mHandle, hitGroupCount));
         }
         rt_scene *getHandle(RtContext::SharedPtr context) { realize(context); return mHandle; }
+        // EXTENSIONS (the reference's RtScene has neither; its generators' update path -- `updateOnly`, Helpers/TopLevelASGenerator.h:144-163 --
+        // is never called).  setTransform: a new object-to-world matrix for an instance already added; on a built scene nothing renders
+        // until update() or build().  update(context): applies the transforms set since on the device (rt_scene_update); no BLAS is built.
+        void setTransform(uint32_t index, const Matrix &transform)
+        {
+            if (index >= mInstances.size()) throw std::runtime_error("RtScene::setTransform: instance out of range");
+            mInstances[index].transform = transform;
+            if (index < mRealized) {
+                float x[12];
+                transform.toInstanceTransform(x);
+                ThrowIfFailed(rt_scene_set_instance_transform(mHandle, index, x));
+            }
+        }
+        void update(RtContext::SharedPtr context)
+        {
+            realize(context);
+            ThrowIfFailed(rt_scene_update(mHandle));
+        }
+        float getUpdateMilliseconds() const { float ms = 0; if (mHandle) rt_scene_update_ms(mHandle, &ms); return ms; }
         float getBuildMilliseconds() const { float ms = 0; if (mHandle) rt_scene_build_ms(mHandle, &ms); return ms; }
 
     private:

@@ -135,6 +135,28 @@ int rt_scene_refs_read(const rt_scene *s, int which, uint32_t *ref_off, float *r
 /* milliseconds the last rt_scene_build spent on the GPU (BLAS + TLAS) */
 int rt_scene_build_ms(const rt_scene *s, float *ms);
 
+/* Rigid animation -- EXTENSIONS: the reference's RtScene exposes none of this (its only statement of a transform is addModel, RtScene.h:30).
+ * rt_scene_set_instance_transform(s): overwrite the object-to-world rows of instances that rt_scene_add_model has added -- the Transform
+ * member of the instance descriptor (libs/DXRFramework/Helpers/TopLevelASGenerator.cpp:344-362).  Any twelve floats are taken, as by
+ * rt_scene_add_model; frames a deferred pipeline still holds are rendered first (they see the scene as it was); an index out of range is
+ * RT_ERR_STATE.  On a scene that was never built the call only overwrites the stored transform.  On a built scene it leaves the scene STALE:
+ * until rt_scene_update or rt_scene_build, rt_trace_batch, the render calls and the rt_scene_*_info / _read calls fail as on an unbuilt
+ * scene (the message names the pending transforms) -- nothing ever traces a half-applied state.
+ * `transforms3x4` of the plural form: count x 12 floats, for instances first .. first + count - 1. */
+int rt_scene_set_instance_transform(rt_scene *s, uint32_t instance, const float transform3x4[12]);
+int rt_scene_set_instance_transforms(rt_scene *s, uint32_t first, uint32_t count, const float *transforms3x4);
+/* EXTENSION: applies the pending transforms on the device -- instance records (fp32 inverse, flags), the world boxes of the pending
+ * instances, the TLAS -- and leaves the scene built.  Stands in for the generators' update path (`updateOnly` of
+ * TopLevelASGenerator::Generate, libs/DXRFramework/Helpers/TopLevelASGenerator.h:144-163, and `allowUpdate` / `updateOnly` of
+ * Helpers/BottomLevelASGenerator.h:136-176), which the reference's RtScene never calls.  The scene afterwards is, array for array, the
+ * scene rt_scene_build gives for the same instance list (DESIGN.md "update == build").  It builds no BLAS: on a scene that has not been
+ * built since its last rt_scene_add_model it fails (RT_ERR_STATE).  With nothing pending it returns RT_OK and changes nothing; otherwise
+ * pipelines drop what they cached from the old geometry (shadow cache, free sphere, primary-mode samples) -- their accumulation buffers are
+ * the caller's to clear (rt_pipeline_clear_output), as after a camera change. */
+int rt_scene_update(rt_scene *s);
+/* EXTENSION: milliseconds the last rt_scene_update spent on the GPU, as rt_scene_build_ms */
+int rt_scene_update_ms(const rt_scene *s, float *ms);
+
 /* ---- raw TraceRay over a batch (HLSL TraceRay semantics, used by tests and
  *      the traversal benchmark; ProgressiveRaytracing.hlsl:34,53,
  *      RaytracingCommon.hlsli:94) ------------------------------------------- */
