@@ -1,7 +1,8 @@
 """The registry of rt_debug_set_option's options (csrc/rt_api.hip) as plain data: for every option the values the suite runs it
 with, or the reason why it is exempt.  tests/test_option_registry.py (CPU) fails when the library has an option this table does
-not name, or the other way round; tests/test_gpu_option_matrix.py and tests/fuzz_parity.py take their option lists from here,
-so that an option entered here is run against the oracle and an option not entered here fails the CPU suite.
+not name, or the other way round; tests/test_gpu_option_matrix.py, tests/test_gpu_update_options.py (scenes that are updated:
+rt_scene_update) and tests/fuzz_parity.py take their option lists from here, so that an option entered here is run against the
+oracle and an option not entered here fails the CPU suite.
 
 kind "build": read when a model / scene is built (another traversal tree, same hits); "launch": read when a pipeline or a batch
 of rays is launched (another shape of launch, same image).  DESIGN.md section 2.1 S2.7: neither may change a bit."""

@@ -379,6 +379,22 @@ LAUNCH_SCENES = ("atrium", "instances", "cables")
 LAUNCH_W, LAUNCH_H, LAUNCH_FRAMES = 192, 108, 5
 
 
+def instances_scene():
+    """the two-level scene of the launch cases (tests/test_gpu_update_options.py animates it): a blob and a soup, 40 instances, a glossy material
+    each; (models, instances, materials, camera)"""
+    models = [scenes.blob_mesh(level=2), triangle_soup(500, seed=2, extent=2.0, size=0.4)]
+    xf = random_xforms(40, seed=3, spread=6.0)
+    inst = [(k % 2, xf[k]) for k in range(40)]
+    r = np.random.default_rng(5)
+    mats = []
+    for k in range(40):
+        m = material(1, float(r.uniform(0.1, 0.9)))
+        m["albedo"][:3] = r.uniform(0.05, 0.95, 3)
+        m["reflectivity"] = r.uniform(0.2, 1.0)
+        mats.append(m)
+    return models, inst, mats, dict(eye=(1.0, 3.0, 20.0), at=(0.0, 0.0, 0.0), up=(0, 1, 0), fov=0.8)
+
+
 def launch_truth(oracle, capi, name):
     """single-level: a reduced atrium; two-level: blobs and soups, 40 instances, a material each; split references: a hall full of cables.
     Glossy materials, both lights on, the point light INSIDE the geometry's bounds (its shadow rays end at the free sphere, the shadow
@@ -389,17 +405,8 @@ def launch_truth(oracle, capi, name):
             models, inst, mats = [scenes.sponza_class(detail=0.3)], [(0, None)], [material()]
             cam, lamp, ext = scenes.sponza_camera(), (2.0, 0.5, 1.0), 16.0
         elif name == "instances":
-            models = [scenes.blob_mesh(level=2), triangle_soup(500, seed=2, extent=2.0, size=0.4)]
-            xf = random_xforms(40, seed=3, spread=6.0)
-            inst = [(k % 2, xf[k]) for k in range(40)]
-            r = np.random.default_rng(5)
-            mats = []
-            for k in range(40):
-                m = material(1, float(r.uniform(0.1, 0.9)))
-                m["albedo"][:3] = r.uniform(0.05, 0.95, 3)
-                m["reflectivity"] = r.uniform(0.2, 1.0)
-                mats.append(m)
-            cam, lamp, ext = dict(eye=(1.0, 3.0, 20.0), at=(0.0, 0.0, 0.0), up=(0, 1, 0), fov=0.8), (0.5, 1.0, 0.5), 9.0
+            models, inst, mats, cam = instances_scene()
+            lamp, ext = (0.5, 1.0, 0.5), 9.0
         else:
             models, inst, mats = [scenes.stadium_class(5, 0.25, ("hall", "cables", "slats"))], [(0, None)], [material()]
             cam, lamp, ext = scenes.stadium_camera(), (3.0, 4.0, -2.0), 30.0
