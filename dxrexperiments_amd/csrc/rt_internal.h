@@ -112,6 +112,45 @@ struct ScopedEvent {
     ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
 };
 
+// A scalar on its way back from the device that nobody waits for: a page-locked block of 64 bytes and the event that says when a copy into
+// it has landed.  Made on first use, both or neither (a creation that failed is tried again by the next call); moves, never copies.  The
+// destructor frees both and reads neither: the owner has selected the device and joined the stream before its members die.
+struct PinnedReadback {
+    void *block = nullptr;
+    hipEvent_t event = nullptr;
+    bool in_flight = false;      // a copy has been sent and landed() has not said so yet
+    PinnedReadback() = default;
+    ~PinnedReadback() { release(); }
+    PinnedReadback(PinnedReadback &&o) noexcept { *this = std::move(o); }      // (and so no copies)
+    PinnedReadback &operator=(PinnedReadback &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            block = o.block; event = o.event; in_flight = o.in_flight;
+            o.block = nullptr; o.event = nullptr; o.in_flight = false;
+        }
+        return *this;
+    }
+    void release() { if (event) (void)hipEventDestroy(event); if (block) (void)hipHostFree(block); block = nullptr; event = nullptr; in_flight = false; }
+    bool ready()
+    {
+        if (block) return true;
+        void *b = nullptr;
+        if (hipHostMalloc(&b, 64, hipHostMallocDefault) != hipSuccess) return false;
+        if (hipEventCreateWithFlags(&event, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(b); event = nullptr; return false; }
+        block = b;
+        return true;
+    }
+    // `bytes` of device memory into the block, behind what the stream holds; true: a copy is in flight
+    bool send(const void *src, size_t bytes, hipStream_t st)
+    {
+        return in_flight = ready() && bytes <= 64 && hipMemcpyAsync(block, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess && hipEventRecord(event, st) == hipSuccess;
+    }
+    // true once per flight: the first time the event says that the copy is there (never waits)
+    bool landed() { const bool now = in_flight && hipEventQuery(event) == hipSuccess; in_flight = in_flight && !now; return now; }
+    template <class T> T read() const { T v; static_assert(sizeof v <= 64, "the block holds 64 bytes"); memcpy(&v, block, sizeof v); return v; }
+};
+
 // Slices of one allocation, each 256-byte aligned.  A builder describes its temporaries ONCE, as a function that takes a carver and
 // fills a struct of typed pointers; with a null base the same calls only add up the bytes the allocation must hold.
 struct Carver {

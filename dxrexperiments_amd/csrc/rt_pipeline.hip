@@ -673,11 +673,11 @@ ShadowQueue shadow_queue(const PipeDev &pd, uint32_t lv_first, uint32_t lv_count
     return sq;
 }
 
-// The launches of one frame, or of one set of frames.  `counted`: the levels beyond the pixel slots are sized by what the
-// compaction before them has counted (see "queue memory" above); otherwise the caller has reserved the worst case and set the
-// strides.  pd is updated as the levels are bound and is what the counting re-walks replay (rt_pipeline::last_pd).
-template <int STACK, bool TWO_LEVEL>
-int launch_frame(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counted)
+// The launches of one frame (BATCH = false), or of one set of frames: the shading kernels then pick the constants of every hit's frame.
+// plan.counted: the levels beyond the pixel slots are sized by what the compaction before them has counted (see "queue memory"
+// above); otherwise the caller has reserved the worst case and set the strides.  pd is updated as the levels are bound and is what the counting re-walks replay (rt_pipeline::last_pd).
+template <int STACK, bool TWO_LEVEL, bool BATCH>
+int launch_frame(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
 {
     hipError_t first_error = hipSuccess;
     auto record = [&](hipEvent_t e, hipStream_t s) { const hipError_t rc = hipEventRecord(e, s); if (first_error == hipSuccess) first_error = rc; };
@@ -687,8 +687,8 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counte
     hipEvent_t *ev = T ? &p->ring[ring_slot * EV_COUNT] : nullptr;
     const uint32_t cap = pd.cap;
     rt_context *ctx = p->ctx;
-    const uint32_t levels = frame_levels(p);
-    const bool deep = levels > 1, compact = pd.shadow_compact != 0;
+    const uint32_t levels = plan.levels;
+    const bool deep = levels > 1, counted = plan.counted;
     // counted queues: the hits the compaction of level l has just produced -> the shadow queue of level l and the ray queue of
     // level l + 1 get their sizes; `slots` = ray slots of the level whose launches come next (level 1: two batches)
     size_t hits_l = cap, slots = cap;
@@ -703,8 +703,8 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counte
         if (hits_l > 0xffffffc0ull / 2) { rt_set_error("render: more than 2^31 hits at radiance level %u", l); return RT_ERR_UNSUPPORTED; }
         pd.lv[l].hstride = (uint32_t)hits_l;
         if (casts_shadows) {
-            if (((sh_total + hits_l) << pd.sh_log2) >= 0xffffffc0ull) { rt_set_error("render: more than 2^32 shadow rays in one set of launches"); return RT_ERR_UNSUPPORTED; }
-            if (counted) RT_TRY(reserve_shadows(p, sh_total + hits_l, pd.sh_log2, compact, sh_total));
+            if (((sh_total + hits_l) << plan.sh_log2) >= 0xffffffc0ull) { rt_set_error("render: more than 2^32 shadow rays in one set of launches"); return RT_ERR_UNSUPPORTED; }
+            if (counted) RT_TRY(reserve_shadows(p, sh_total + hits_l, plan.sh_log2, plan.compact, sh_total));
             pd.sh_cbase[l] = (uint32_t)sh_total;
             sh_total += hits_l;
         }
@@ -718,23 +718,19 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counte
         return RT_OK;
     };
     if (T) record(ev[0], st);
-    // primary rays are coherent: one 8x8 tile per wave, scheduled by the hardware dispatcher
-    if (pd.primary_persistent) HIP_TRY(hipMemsetAsync(pd.pools + POOL_BYTES / 4, 0, PRIMARY_POOL_WORDS * 4, st));      // (its own first block cannot clear it: the others already draw from it)
     if (pd.primary_persistent) {
-        if (pd.n_frames > 1u) k_primary<STACK, TWO_LEVEL, true, true><<<rt_persistent_grid(ctx, k_primary<STACK, TWO_LEVEL, true, true>, PBLOCK, cap), PBLOCK, 0, st>>>(pd);
-        else k_primary<STACK, TWO_LEVEL, false, true><<<rt_persistent_grid(ctx, k_primary<STACK, TWO_LEVEL, false, true>, PBLOCK, cap), PBLOCK, 0, st>>>(pd);
+        HIP_TRY(hipMemsetAsync(pd.pools + POOL_BYTES / 4, 0, PRIMARY_POOL_WORDS * 4, st));      // (its own first block cannot clear it: the others already draw from it)
+        k_primary<STACK, TWO_LEVEL, BATCH, true><<<rt_persistent_grid(ctx, k_primary<STACK, TWO_LEVEL, BATCH, true>, PBLOCK, cap), PBLOCK, 0, st>>>(pd);
     } else {
-        if (pd.n_frames > 1u) k_primary<STACK, TWO_LEVEL, true, false><<<blocks(cap), PBLOCK, 0, st>>>(pd);
-        else k_primary<STACK, TWO_LEVEL, false, false><<<blocks(cap), PBLOCK, 0, st>>>(pd);
+        // primary rays are coherent: one 8x8 tile per wave, scheduled by the hardware dispatcher
+        k_primary<STACK, TWO_LEVEL, BATCH, false><<<blocks(cap), PBLOCK, 0, st>>>(pd);
         // the rays that would have needed a stack row beyond LDS (none on the bench scenes: the launch returns at once)
         if (pd.retry) k_primary_retry<STACK, TWO_LEVEL><<<rt_persistent_grid(ctx, k_primary_retry<STACK, TWO_LEVEL>, PBLOCK, cap), PBLOCK, 0, st>>>(pd);
     }
     k_compact_level<<<(cap + CTILES * CBLOCK - 1) / (CTILES * CBLOCK), CBLOCK, 0, st>>>(pd, 0);
     if (T) record(ev[1], st);
     RT_TRY(size_next(0, true, levels >= 1));
-    const bool B = pd.n_frames > 1u;            // a batch of frames: the shading kernels pick the constants of every hit's frame
-    if (B) k_shade_emit<true, true><<<blocks(hits_l), PBLOCK, 0, st>>>(pd, 0, shadow_slots, levels >= 1 ? 1u : 0u);
-    else k_shade_emit<true, false><<<blocks(hits_l), PBLOCK, 0, st>>>(pd, 0, shadow_slots, levels >= 1 ? 1u : 0u);
+    k_shade_emit<true, BATCH><<<blocks(hits_l), PBLOCK, 0, st>>>(pd, 0, plan.shadow_slots, levels >= 1 ? 1u : 0u);
     if (T) record(ev[2], st);
     for (uint32_t l = 1; l <= levels; l++) {
         const QueueSrc rays = level_rays(pd, l);
@@ -744,15 +740,12 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counte
         if (T) record(ev[3 + 2 * (l - 1)], st);
         const bool casts_shadows = l < pd.sh_levels, spawns = l < levels;
         RT_TRY(size_next(l, casts_shadows, spawns));
-        if (casts_shadows || spawns) {
-            if (B) k_shade_emit<false, true><<<blocks(hits_l), PBLOCK, 0, st>>>(pd, (int)l, 2u, spawns ? 1u : 0u);
-            else k_shade_emit<false, false><<<blocks(hits_l), PBLOCK, 0, st>>>(pd, (int)l, 2u, spawns ? 1u : 0u);
-        }
+        if (casts_shadows || spawns) k_shade_emit<false, BATCH><<<blocks(hits_l), PBLOCK, 0, st>>>(pd, (int)l, 2u, spawns ? 1u : 0u);
         if (T) record(ev[4 + 2 * (l - 1)], st);
     }
     {   // every shadow ray of the frame (or set) in ONE persistent any-hit launch over the shared queue
         ShadowQueue sq = shadow_queue(pd, 0, pd.sh_levels);
-        sq.cache = p->shadow_cache_dev;
+        sq.cache = p->shadow_cache.dev;
         sq.cache.jlist0 = pd.lv[0].jlist;
         sq.cache.hstride0 = pd.lv[0].hstride;
         sq.cache.n_frames = pd.n_frames;
@@ -760,37 +753,32 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counte
         if (sq.cache.px_slots > pd.fcap) sq.cache.px_slots = pd.fcap;
         const size_t rays_max = sh_total << pd.sh_log2;
         HIP_TRY(hipMemsetAsync(pd.sh_vis, 0, ((rays_max + 31) / 32) * 4, st));      // the visibility bits: set by the rays that reach their light
-        if (B) k_trace_shadow<STACK, TWO_LEVEL, true><<<rt_persistent_grid(ctx, k_trace_shadow<STACK, TWO_LEVEL, true>, PBLOCK, rays_max), PBLOCK, 0, st>>>(
-            pd.sc, sq, pd.pools, &pd.counters[C_SHADOW]);
-        else k_trace_shadow<STACK, TWO_LEVEL, false><<<rt_persistent_grid(ctx, k_trace_shadow<STACK, TWO_LEVEL, false>, PBLOCK, rays_max), PBLOCK, 0, st>>>(
+        k_trace_shadow<STACK, TWO_LEVEL, BATCH><<<rt_persistent_grid(ctx, k_trace_shadow<STACK, TWO_LEVEL, BATCH>, PBLOCK, rays_max), PBLOCK, 0, st>>>(
             pd.sc, sq, pd.pools, &pd.counters[C_SHADOW]);
     }
     if (T) record(ev[EV_SHADOW], st);
     // (resolve: one thread per pixel slot of ONE frame; a batch's frames are accumulated in order inside the thread)
-    if (levels <= 1) {                          // (level by level is slower here: 0.143 vs 0.118 ms at 1080p)
-        if (B) k_resolve<false, true><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);
-        else k_resolve<false, false><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);
-    } else {
-        for (uint32_t l = levels; l >= 1; l--) {
-            const size_t n_l = pd.lv[l].hstride;       // (one thread per hit of the level)
-            if (B) k_shade_level<true><<<blocks(n_l), PBLOCK, 0, st>>>(pd, (int)l);
-            else k_shade_level<false><<<blocks(n_l), PBLOCK, 0, st>>>(pd, (int)l);
-        }
-        if (B) k_resolve<true, true><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);
-        else k_resolve<true, false><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);
+    if (levels <= 1) k_resolve<false, BATCH><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);      // (level by level is slower here: 0.143 vs 0.118 ms at 1080p)
+    else {
+        for (uint32_t l = levels; l >= 1; l--) k_shade_level<BATCH><<<blocks(pd.lv[l].hstride), PBLOCK, 0, st>>>(pd, (int)l);      // (one thread per hit of the level)
+        k_resolve<true, BATCH><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);
     }
     if (T) { record(ev[EV_RESOLVE], st); p->ring_levels[ring_slot] = (uint8_t)levels; p->ring_nframes[ring_slot] = (uint8_t)pd.n_frames; p->ring_pos++; }
     HIP_TRY(first_error);
     return RT_OK;
 }
 
+template <int STACK, bool TWO_LEVEL>
+int launch_frame_sized(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
+{
+    return pd.n_frames > 1u ? launch_frame<STACK, TWO_LEVEL, true>(p, pd, plan) : launch_frame<STACK, TWO_LEVEL, false>(p, pd, plan);
+}
 // (+ RT_STACK_REFS: the instantiations that look references up, for scenes that hold split triangles)
 template <int STACK>
-int launch_frame_any(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counted)
+int launch_frame_any(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
 {
-    if (p->scene->has_refs)
-        return p->scene->two_level ? launch_frame<STACK + RT_STACK_REFS, true>(p, pd, shadow_slots, counted) : launch_frame<STACK + RT_STACK_REFS, false>(p, pd, shadow_slots, counted);
-    return p->scene->two_level ? launch_frame<STACK, true>(p, pd, shadow_slots, counted) : launch_frame<STACK, false>(p, pd, shadow_slots, counted);
+    if (p->scene->has_refs) return p->scene->two_level ? launch_frame_sized<STACK + RT_STACK_REFS, true>(p, pd, plan) : launch_frame_sized<STACK + RT_STACK_REFS, false>(p, pd, plan);
+    return p->scene->two_level ? launch_frame_sized<STACK, true>(p, pd, plan) : launch_frame_sized<STACK, false>(p, pd, plan);
 }
 
 template <bool TWO_LEVEL>
@@ -816,16 +804,16 @@ static int count_walk_launch(rt_pipeline *p, unsigned long long *w)
 
 }  // namespace
 
-int rt_frame_launch(rt_pipeline *p, PipeDev &pd, uint32_t shadow_slots, bool counted, bool set_rows)
+int rt_frame_launch(rt_pipeline *p, PipeDev &pd, const SetPlan &plan, bool set_rows)
 {
     // 18 LDS stack rows + the 8-row top table = 26 KiB per 256-thread block = 6 resident blocks per CU, whatever
     // the depth of the tree; the rare deeper walk continues in global rows (rt_trace_wave.h)
-    if (p->ctx->lds_stack_rows == RT_LDS_STACK_ROWS_TEST) return launch_frame_any<RT_LDS_STACK_ROWS_TEST>(p, pd, shadow_slots, counted);
+    if (p->ctx->lds_stack_rows == RT_LDS_STACK_ROWS_TEST) return launch_frame_any<RT_LDS_STACK_ROWS_TEST>(p, pd, plan);
     // (scene_for_set never asks for the sets' rows on a scene with split triangles: there the 18-row six-wave kernels are the faster ones --
     // 2.2 M-triangle stress scene 5.63 -> 4.89 ms per frame, 272 k 4.88 -> 4.86: profiles/r05/ref_rule.txt -- and the reference-aware
     // seven-wave instantiations, which spilled 36 - 72 B, are not compiled)
-    if (set_rows) return launch_frame<RT_LDS_STACK_ROWS_SETS, false>(p, pd, shadow_slots, counted);
-    return launch_frame_any<RT_LDS_STACK_ROWS>(p, pd, shadow_slots, counted);
+    if (set_rows) return launch_frame_sized<RT_LDS_STACK_ROWS_SETS, false>(p, pd, plan);
+    return launch_frame_any<RT_LDS_STACK_ROWS>(p, pd, plan);
 }
 
 int rt_frame_count_walk(rt_pipeline *p, unsigned long long *w)

@@ -210,22 +210,24 @@ struct rt_pipeline {
     DevBuf batch_consts;               // per-frame constants and light rays of a batch (rt_pipeline_render_batch)
     int ring_frames = 0;               // 0 = timing off
     // the shadow cache (ShadowCacheDev): table, the scene it was filled from, the bounds its directional cells span
-    DevBuf shadow_cache;
-    int shadow_cache_res = -1;         // rt_pipeline_set_shadow_cache: -1 automatic (the option shadow_cache_res, else by triangle count), 0 off, n cells per side
-    uint32_t shadow_cache_gen = 0xffffffffu;
-    float shadow_cache_centre[3] = {0, 0, 0}, shadow_cache_radius = 1.0f;
-    ShadowCacheDev shadow_cache_dev = {};      // what the next shadow launches get (table == nullptr: off)
+    struct ShadowCache {
+        DevBuf table;
+        int res = -1;                      // rt_pipeline_set_shadow_cache: -1 automatic (the option shadow_cache_res, else by triangle count), 0 off, n cells per side
+        uint32_t gen = 0xffffffffu;        // scene generation the table was filled from
+        float centre[3] = {0, 0, 0}, radius = 1.0f;
+        ShadowCacheDev dev = {};           // what the next shadow launches get (table == nullptr: off)
+        void invalidate() { gen = 0xffffffffu; }       // the table is cleared before its next use
+    } shadow_cache;
     // the free sphere around the point light (LightRays::point_free): the least distance from the light to the box of any triangle
     // (instances: to any instance's world box), found by a device pass over them when the scene or the light has changed and read
     // back without a host round trip: page-locked word + event, used from the first render call that finds the event complete
     struct FreeSphere {
         DevBuf d_min;                      // one float (bits): running minimum of the pass in flight
-        float *h_min = nullptr;            // page-locked landing place
-        hipEvent_t landed = nullptr;
+        PinnedReadback back;               // ... and its landing place
         uint32_t asked_gen = 0xffffffffu, known_gen = 0xffffffffu;
         float asked_lp[3] = {0, 0, 0}, known_lp[3] = {0, 0, 0}, known_radius = 0.0f;
         float asked_size = 0.0f;           // the largest coordinate of the scene's bounds when the pass was queued
-        bool in_flight = false;
+        void invalidate() { known_gen = asked_gen = 0xffffffffu; }      // (a pass in flight lands unused)
     } free_sphere;
     // How the primary stage runs on a single-level scene (round 5): one tile per wave without stack rows beyond LDS + the retry launch, unless
     // the retry list says that this scene's primary rays outgrow the LDS rows in numbers (the 10 M-triangle mesh: every retried ray is
@@ -233,13 +235,14 @@ struct rt_pipeline {
     // scene's.  The list's count of a set of launches comes back through a page-locked word behind the set (never waited for); the first
     // sets of a scene are sampled, the decision holds until the scene changes.  Same image either way.
     struct PrimaryMode {
-        uint32_t *h_count = nullptr;       // page-locked landing place of PipeDev::retry[0]
-        hipEvent_t landed = nullptr;
-        bool in_flight = false;
+        PinnedReadback back;               // landing place of PipeDev::retry[1], the count of the set before
         uint32_t asked_slots = 0;          // pixel slots of the launch whose count is in flight
         uint32_t gen = 0xffffffffu;        // scene generation the samples belong to
         int samples = 0;                   // sets sampled so far for this scene
         bool persistent = false;           // the decision
+        void invalidate() { gen = 0xffffffffu; }       // the next set starts the samples over
+        bool choose(const rt_context *ctx, const rt_scene *scene);      // the coming set's primary stage: true = persistent; a count that has landed is weighed first
+        void sample(const rt_context *ctx, const uint32_t *d_count, uint32_t slots, hipStream_t st);      // behind the set: its retry count, of `slots` pixel slots, starts its way back
     } primary_mode;
     uint64_t ring_pos = 0;             // frames recorded since enable / reset
     DevBuf totals, work;
@@ -249,7 +252,7 @@ struct rt_pipeline {
     uint32_t last_pixels = 0;
     bool rendered = false;
     uint32_t last_scene_gen = 0;       // generation of the scene last_pd was filled from
-    ~rt_pipeline();                    // (rt_pipeline_host.hip) selects the device and joins the stream; events, pinned memory, the scene it retains; then the buffers
+    ~rt_pipeline();                    // (rt_pipeline_host.hip) selects the device and joins the stream; the ring's events, the scene it retains; then the members
 };
 
 // renders the frames a deferred pipeline holds (rt_pipeline.hip); every entry point that reads or changes what they see calls it first

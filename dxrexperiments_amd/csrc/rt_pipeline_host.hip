@@ -68,10 +68,6 @@ rt_pipeline::~rt_pipeline()
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (hipEvent_t e : ring) if (e) (void)hipEventDestroy(e);
-    if (free_sphere.landed) (void)hipEventDestroy(free_sphere.landed);
-    if (primary_mode.landed) (void)hipEventDestroy(primary_mode.landed);
-    if (primary_mode.h_count) (void)hipHostFree(primary_mode.h_count);
-    if (free_sphere.h_min) (void)hipHostFree(free_sphere.h_min);
     if (scene) rt_scene_destroy(scene);
 }
 
@@ -92,8 +88,9 @@ int rt_pipeline_set_scene(rt_pipeline *p, rt_scene *s)
     if (p->scene) rt_scene_destroy(p->scene);
     p->scene = s;
     p->rendered = false;        // last_pd holds device pointers of the previous scene
-    p->shadow_cache_gen = 0xffffffffu;      // ... and the shadow cache triangle indices of its arrays (another scene may carry the same generation number)
-    p->free_sphere.known_gen = p->free_sphere.asked_gen = 0xffffffffu;      // ... and the free sphere its geometry (a pass in flight lands unused)
+    p->shadow_cache.invalidate();           // ... and the shadow cache triangle indices of its arrays (another scene may carry the same generation number)
+    p->free_sphere.invalidate();            // ... and the free sphere its geometry (a pass in flight lands unused)
+    p->primary_mode.invalidate();           // ... and the primary stage's choice its retry counts
     return RT_OK;
 }
 
@@ -215,15 +212,15 @@ int rt_pipeline_set_shadow_cache(rt_pipeline *p, int cells_per_side)
 {
     RT_REQUIRE(p, "null pipeline");
     RT_REQUIRE(cells_per_side >= -1 && cells_per_side <= 8192, "shadow cache: cells per side in [16, 8192], 0 = off, -1 = automatic");
-    p->shadow_cache_res = cells_per_side;
-    p->shadow_cache_gen = 0xffffffffu;          // (a table of another size starts empty)
+    p->shadow_cache.res = cells_per_side;
+    p->shadow_cache.invalidate();               // (a table of another size starts empty)
     return RT_OK;
 }
 
 int rt_pipeline_get_shadow_cache(const rt_pipeline *p, int *cells_per_side)
 {
     RT_REQUIRE(p && cells_per_side, "null argument");
-    *cells_per_side = p->shadow_cache_dev.table ? (int)p->shadow_cache_dev.res : 0;       // what the last frame ran with
+    *cells_per_side = p->shadow_cache.dev.table ? (int)p->shadow_cache.dev.res : 0;       // what the last frame ran with
     return RT_OK;
 }
 

@@ -1,6 +1,7 @@
 // rt_pipeline_queues.h -- host-side helpers the two translation units of the pipeline share (rt_pipeline.hip: the frame's kernels and
 // launches; rt_pipeline_render.hip: the render calls): the frame's light rays as the host computes them, and the queue memory -- what a
-// level's buffers hold, the worst case and the budget, reservation by count, binding a level's buffers into the kernels' argument.
+// level's buffers hold, the worst case and the budget, reservation by count, binding a level's buffers into the kernels' argument, and
+// the plan of one set of launches (SetPlan: what sizes it, and the one reservation that follows from it).
 #pragma once
 
 #include "rt_pipeline_dev.h"
@@ -23,13 +24,6 @@ inline LightRays light_rays(uint32_t shadow_compact, const rt_per_frame_constant
     return l;
 }
 inline LightRays light_rays(const PipeDev &pd) { LightRays l = light_rays(pd.shadow_compact, pd.pfc); l.point_free = pd.point_free; return l; }
-inline LightRays no_light_rays()
-{
-    LightRays l;
-    memset(&l, 0, sizeof l);
-    return l;
-}
-
 
 // ---- queue memory ------------------------------------------------------------------------------------------------------
 // Level l keeps, per RAY slot (l = 0: per pixel slot; no ray is stored there), the ray (32 B + 4 B pixel slot), its hit record
@@ -127,12 +121,54 @@ inline void bind_level(const rt_pipeline *p, PipeDev &pd, int l)
 // radiance levels a frame traces: level l exists when hits of depth l-1 may spawn rays
 inline uint32_t frame_levels(const rt_pipeline *p) { return p->max_rad < (uint32_t)MAXD ? p->max_rad : (uint32_t)MAXD; }
 
+// ---- one set of launches: what sizes it, decided once (render_region and rt_pipeline_reserve_batch ask the same two functions) ----
+struct SetPlan {
+    uint32_t fcap, n_frames, cap;      // pixel slots of one frame (the 8x8 tiles of its rectangle), frames, pixel slots of the set
+    uint32_t levels;                   // frame_levels
+    bool ao_view, compact;             // the ambient-occlusion view: four shadow rays of random directions per hit, in explicit form (else PipeDev::shadow_compact)
+    uint32_t shadow_slots, sh_log2;    // shadow rays per primary hit and their log2: 2 / 1 (the two lights), 4 / 2 (the view)
+    bool counted;                      // the worst case is over the budget: levels beyond the pixel slots are sized as their counts come in
+};
+// the batch's constants and light rays in device memory (rt_pipeline::batch_consts): kernels index them by the frame of a slot
+constexpr size_t BATCH_PFC_BYTES = sizeof(rt_per_frame_constants) * RT_MAX_BATCH, BATCH_LIGHT_BYTES = sizeof(LightRays) * RT_MAX_BATCH;
+
+// `who`: the calling entry point, as its messages name it
+inline int plan_set(rt_pipeline *p, uint32_t tw, uint32_t th, uint32_t n_frames, bool ao_view, const char *who, SetPlan *out)
+{
+    SetPlan &s = *out;
+    s.fcap = ((tw + 7u) / 8u) * ((th + 7u) / 8u) * 64u;
+    if ((uint64_t)s.fcap * n_frames >= 0x40000000ull) { rt_set_error("%s: batch: more than 2^30 pixel slots in one set of launches", who); return RT_ERR_INVALID_ARG; }
+    s.n_frames = n_frames; s.cap = s.fcap * n_frames; s.levels = frame_levels(p);
+    s.ao_view = ao_view; s.compact = !ao_view;      // the AO view's four rays have random directions
+    s.shadow_slots = ao_view ? 4u : 2u; s.sh_log2 = ao_view ? 2u : 1u;
+    // queue memory: the worst case up front when it fits the budget, else level by level as the counts come in (launch_frame)
+    s.counted = worst_case_queue_bytes(s.cap, s.levels, p->max_shadow, s.shadow_slots, s.compact) > queue_budget(p);
+    return RT_OK;
+}
+// every buffer the plan sizes: the counters, the queues (a counted set: the pixel slots' only), a set's constants, the totals
+inline int reserve_set(rt_pipeline *p, const SetPlan &s)
+{
+    hipStream_t st = p->ctx->stream;
+    if (p->counters.bytes < POOL_OFFSET_WORDS * 4 + POOL_BYTES + PRIMARY_POOL_WORDS * 4) {
+        RT_TRY(p->counters.reserve(POOL_OFFSET_WORDS * 4 + POOL_BYTES + PRIMARY_POOL_WORDS * 4));
+        HIP_TRY(hipMemsetAsync(p->counters.p, 0, p->counters.bytes, st));
+    }
+    if (s.counted) RT_TRY(reserve_level_rays(p, 0, s.cap, s.levels > 1));
+    else RT_TRY(reserve_worst_case(p, s.cap, s.levels, p->max_shadow, s.shadow_slots, s.compact));
+    if (s.n_frames > 1) RT_TRY(p->batch_consts.reserve(BATCH_PFC_BYTES + BATCH_LIGHT_BYTES));
+    if (!p->totals.p) {
+        RT_TRY(p->totals.reserve(8 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(p->totals.p, 0, 8 * sizeof(unsigned long long), st));
+    }
+    return RT_OK;
+}
+
 
 }  // namespace rtp
 
 // ---- what rt_pipeline.hip (kernels, launches) offers rt_pipeline_render.hip (the render calls) ----
 // the launches of one frame or one set of frames (set_rows: the sets' seven-wave single-level kernels); pd is updated as levels are bound
-int rt_frame_launch(rt_pipeline *p, rtp::PipeDev &pd, uint32_t shadow_slots, bool counted, bool set_rows);
+int rt_frame_launch(rt_pipeline *p, rtp::PipeDev &pd, const rtp::SetPlan &plan, bool set_rows);
 // the counting re-walks over the last frame's queues (p->last_pd): launches only, results in w[RT_STAGE_COUNT][RT_WALK_WORDS] / [3]
 int rt_frame_count_walk(rt_pipeline *p, unsigned long long *w);
 int rt_frame_count_work(rt_pipeline *p, unsigned long long *w);

@@ -4,8 +4,6 @@
 // replay the last frame's queues (work counting, primary hits).  The kernels and their launch sequence: rt_pipeline.hip.
 #include <hip/hip_fp16.h>
 
-#include <array>
-#include <new>
 #include <utility>
 
 #include "rt_pipeline_queues.h"
@@ -56,15 +54,14 @@ __global__ void __launch_bounds__(PBLOCK) k_free_sphere(SceneDev sc, uint32_t tw
 // a pass that has landed becomes what is known
 void free_sphere_poll(rt_pipeline::FreeSphere &f)
 {
-    if (f.in_flight && hipEventQuery(f.landed) == hipSuccess) {
-        f.in_flight = false;
+    if (f.back.landed()) {
         f.known_gen = f.asked_gen;
         memcpy(f.known_lp, f.asked_lp, sizeof f.known_lp);
         // (0.99 and the term in the coordinates' size -- 32 units in the last place of the largest one -- cover the rounding of
         // the rays' own arithmetic: a ray's parameter at a triangle is exact to a few ulps of the coordinates, not of the radius)
         double size = 0.0;
         for (int c = 0; c < 3; c++) size = fmax(size, fmax(fabs((double)f.asked_lp[c]), (double)f.asked_size));
-        const double r = sqrt((double)*f.h_min) * 0.99 - (double)RAY_EPSILON - size * 4e-6;
+        const double r = sqrt((double)f.back.read<float>()) * 0.99 - (double)RAY_EPSILON - size * 4e-6;
         f.known_radius = r > 0.0 && r < 1e30 ? (float)r : 0.0f;
     }
 }
@@ -75,20 +72,15 @@ float free_radius(rt_pipeline *p, const PipeDev &pd, const float lp[3])
     const rt_scene *s = p->scene;
     hipStream_t st = p->ctx->stream;
     if (!(lp[0] == lp[0] && lp[1] == lp[1] && lp[2] == lp[2])) return 0.0f;
-    if (!f.h_min) {
-        if (hipHostMalloc((void **)&f.h_min, 64, hipHostMallocDefault) != hipSuccess) { f.h_min = nullptr; return 0.0f; }
-        if (hipEventCreateWithFlags(&f.landed, hipEventDisableTiming) != hipSuccess || f.d_min.reserve(64) != RT_OK) return 0.0f;
-    }
+    if (!f.back.ready() || f.d_min.reserve(64) != RT_OK) return 0.0f;
     free_sphere_poll(f);
     const bool known = f.known_gen == s->generation && memcmp(f.known_lp, lp, sizeof f.known_lp) == 0;
-    const bool asked = f.in_flight && f.asked_gen == s->generation && memcmp(f.asked_lp, lp, sizeof f.asked_lp) == 0;
-    if (!known && !asked && !f.in_flight) {
+    if (!known && !f.back.in_flight) {
         const uint32_t n = s->two_level ? (uint32_t)s->inst.size() : (s->inst.empty() || !s->inst[0].model ? 0u : s->inst[0].model->n_recs);
-        if (n == 0u || !f.landed) return 0.0f;
+        if (n == 0u) return 0.0f;
         if (hipMemsetD32Async((hipDeviceptr_t)f.d_min.p, 0x7f800000, 1, st) != hipSuccess) return 0.0f;      // +inf
         k_free_sphere<<<(n + PBLOCK - 1) / PBLOCK, PBLOCK, 0, st>>>(pd.sc, s->two_level ? 1u : 0u, n, lp[0], lp[1], lp[2], f.d_min.as<uint32_t>());
-        if (hipMemcpyAsync(f.h_min, f.d_min.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(f.landed, st) != hipSuccess) return 0.0f;
-        f.in_flight = true;
+        if (!f.back.send(f.d_min.p, 4, st)) return 0.0f;
         f.asked_gen = s->generation;
         const float *bb = s->two_level ? s->tlas.bounds : s->inst[0].model->blas.bounds;
         f.asked_size = 0.0f;
@@ -101,17 +93,18 @@ float free_radius(rt_pipeline *p, const PipeDev &pd, const float lp[3])
 // The shadow cache of the coming launches (ShadowCacheDev): single-level scenes only (an entry is an index into the one sorted
 // triangle array); the table is cleared when the scene has changed (an index must stay inside the array), its directional cells
 // span the bounding sphere of the model, its basis follows the frame's light (entries of another direction are merely stale).
-int prepare_shadow_cache(rt_pipeline *p, const LightRays &lr)
+int prepare_shadow_cache(rt_pipeline *p, const LightRays *lr)
 {
-    p->shadow_cache_dev = ShadowCacheDev{};
+    rt_pipeline::ShadowCache &sc = p->shadow_cache;
+    sc.dev = ShadowCacheDev{};
     const rt_scene *s = p->scene;
-    if (p->shadow_cache_res == 0 || s->inst.empty()) return RT_OK;
+    if (sc.res == 0 || s->inst.empty()) return RT_OK;
     size_t n_tris_all = 0;
     for (const SceneInstance &si : s->inst) {
         if (!si.model || si.model->n_tris >= (1u << 28)) return RT_OK;
         n_tris_all += si.model->n_tris;
     }
-    int want = p->shadow_cache_res;
+    int want = sc.res;
     if (want < 0) {                         // not set through the API: the context's option, else by the size of the triangles
         want = p->ctx->opt_shadow_cache_res;
         if (want == 0) return RT_OK;
@@ -137,10 +130,10 @@ int prepare_shadow_cache(rt_pipeline *p, const LightRays &lr)
     const size_t px_slots = per_pixel ? (size_t)((p->width + 7u) / 8u) * ((p->height + 7u) / 8u) * 64u : 0;
     const size_t entries = cells + 2 * px_slots, entry_bytes = s->two_level ? 8 : 4;
     if (entries >= 0xffffffffull) return RT_OK;
-    if (p->shadow_cache.bytes < entries * entry_bytes) { RT_TRY(p->shadow_cache.reserve(entries * entry_bytes)); p->shadow_cache_gen = 0xffffffffu; }
-    if (lr.on == 0xffffffffu) return RT_OK;            // (rt_pipeline_reserve_batch: the allocation only)
-    if (p->shadow_cache_gen != s->generation) {
-        HIP_TRY(hipMemsetAsync(p->shadow_cache.p, 0xff, entries * entry_bytes, p->ctx->stream));
+    if (sc.table.bytes < entries * entry_bytes) { RT_TRY(sc.table.reserve(entries * entry_bytes)); sc.invalidate(); }
+    if (!lr) return RT_OK;                             // (rt_pipeline_reserve_batch: the allocation only)
+    if (sc.gen != s->generation) {
+        HIP_TRY(hipMemsetAsync(sc.table.p, 0xff, entries * entry_bytes, p->ctx->stream));
         // the world bounds: what the builds brought back (the model's own box for one identity instance, the TLAS's otherwise)
         const float *bb = s->two_level ? s->tlas.bounds : s->inst[0].model->blas.bounds;
         float lo[3], hi[3];
@@ -149,12 +142,12 @@ int prepare_shadow_cache(rt_pipeline *p, const LightRays &lr)
             if (!(lo[c] > -1e30f && hi[c] < 1e30f && lo[c] <= hi[c])) { lo[c] = -1.0f; hi[c] = 1.0f; }      // (any cell size is legal)
         }
         float r2 = 0.0f;
-        for (int c = 0; c < 3; c++) { p->shadow_cache_centre[c] = 0.5f * (lo[c] + hi[c]); const float h = 0.5f * (hi[c] - lo[c]); r2 += h * h; }
-        p->shadow_cache_radius = r2 > 0.0f && r2 < 1e30f ? sqrtf(r2) : 1.0f;
-        p->shadow_cache_gen = s->generation;
+        for (int c = 0; c < 3; c++) { sc.centre[c] = 0.5f * (lo[c] + hi[c]); const float h = 0.5f * (hi[c] - lo[c]); r2 += h * h; }
+        sc.radius = r2 > 0.0f && r2 < 1e30f ? sqrtf(r2) : 1.0f;
+        sc.gen = s->generation;
     }
     ShadowCacheDev c = {};
-    c.table = p->shadow_cache.as<uint32_t>();
+    c.table = sc.table.as<uint32_t>();
     c.res = res; c.res_f = (float)res;
     c.two_level = s->two_level ? 1u : 0u;
     c.n_tris = s->two_level ? 0u : s->inst[0].model->n_recs;
@@ -162,21 +155,21 @@ int prepare_shadow_cache(rt_pipeline *p, const LightRays &lr)
     c.px_base = px_slots ? (uint32_t)cells : 0u;
     c.px_slots = (uint32_t)px_slots;                 // (launch_frame fills in what belongs to the launch: jlist0, hstride0, the set's frames)
     // two unit vectors across the direction to the light
-    const float d[3] = {lr.dir_to_light[0], lr.dir_to_light[1], lr.dir_to_light[2]};
+    const float d[3] = {lr->dir_to_light[0], lr->dir_to_light[1], lr->dir_to_light[2]};
     const float ref[3] = {fabsf(d[1]) < 0.9f ? 0.0f : 1.0f, fabsf(d[1]) < 0.9f ? 1.0f : 0.0f, 0.0f};
     float a[3] = {d[1] * ref[2] - d[2] * ref[1], d[2] * ref[0] - d[0] * ref[2], d[0] * ref[1] - d[1] * ref[0]};
     const float al = sqrtf(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
     if (!(al > 1e-6f)) { a[0] = 1.0f; a[1] = 0.0f; a[2] = 0.0f; } else { a[0] /= al; a[1] /= al; a[2] /= al; }
     const float b[3] = {d[1] * a[2] - d[2] * a[1], d[2] * a[0] - d[0] * a[2], d[0] * a[1] - d[1] * a[0]};
-    const float k = 0.5f * (float)res / p->shadow_cache_radius;
+    const float k = 0.5f * (float)res / sc.radius;
     c.ua[3] = 0.5f * (float)res; c.va[3] = 0.5f * (float)res;
     for (int i = 0; i < 3; i++) {
         c.ua[i] = a[i] * k; c.va[i] = b[i] * k;
-        c.ua[3] -= p->shadow_cache_centre[i] * c.ua[i];
-        c.va[3] -= p->shadow_cache_centre[i] * c.va[i];
-        c.lp[i] = lr.point_pos[i];
+        c.ua[3] -= sc.centre[i] * c.ua[i];
+        c.va[3] -= sc.centre[i] * c.va[i];
+        c.lp[i] = lr->point_pos[i];
     }
-    p->shadow_cache_dev = c;
+    sc.dev = c;
     return RT_OK;
 }
 
@@ -197,145 +190,84 @@ int scene_for_set(rt_pipeline *p, uint32_t n_frames, SceneDev *out, bool *sets_k
     return rt_scene_dev_for_launch(ctx, p->scene, set_rows ? RT_LDS_STACK_ROWS_SETS : rt_lds_stack_rows(ctx), resident, out);
 }
 
-}  // namespace
-
-extern "C" {
-
-// one frame over the rectangle [x0,x1) x [y0,y1); band_rows != 0: over the interleaved bands {b : b mod band_world == band_rank}
-// of band_rows rows each (the rectangle then spans the full width and the rank's rows, packed)
-// frames / n_frames: the constants of the frames this set of launches renders (one: the last rt_pipeline_update)
-static int render_region(rt_pipeline *p, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
-                         uint32_t band_rows, uint32_t band_rank, uint32_t band_world, const rt_per_frame_constants *frames = nullptr, uint32_t n_frames = 1)
+// what every render call needs before it may record or render a frame (`own_frame`: the last update()'s); `who`: the entry point, as its messages name it
+int check_renderable(const rt_pipeline *p, uint32_t width, uint32_t height, bool own_frame, const char *who)
 {
-    RT_REQUIRE(p, "null pipeline");
     if (!p->scene || !p->scene->built) { if (!rt_scene_stale_error(p->scene, "render")) rt_set_error("render: acceleration structures not built"); return RT_ERR_STATE; }
     if (!p->accum) { rt_set_error("render: no output resource"); return RT_ERR_STATE; }
-    if (!frames && !p->have_pfc) { rt_set_error("render: update() has not been called"); return RT_ERR_STATE; }
-    if (!frames) { frames = &p->pfc; n_frames = 1; }
-    RT_REQUIRE(n_frames >= 1 && n_frames <= RT_MAX_BATCH, "batch size");
+    if (own_frame && !p->have_pfc) { rt_set_error("render: update() has not been called"); return RT_ERR_STATE; }
     if (p->mats.empty()) { rt_set_error("render: no material"); return RT_ERR_STATE; }
-    RT_REQUIRE(width == p->width && height == p->height, "width/height differ from the output resource");
-    if (x1 > width) x1 = width;
-    if (!band_rows && y1 > height) y1 = height;      // (band mode: y counts the rank's packed rows, checked per pixel)
-    RT_REQUIRE(x0 < x1 && y0 < y1, "empty tile");
-    rt_context *ctx = p->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    p->rendered = false;
-    // RayGen early-out (ProgressiveRaytracing.hlsl:14-16): nothing is traced or written (batches: the caller has dropped such frames)
-    if (p->kind == RT_PIPELINE_PROGRESSIVE && frames[0].cameraParams.accumCount >= frames[0].options.maxIterations) {
-        memset(&p->stats, 0, sizeof p->stats);
-        return RT_OK;
+    if (width != p->width || height != p->height) { rt_set_error("%s: width/height differ from the output resource", who); return RT_ERR_INVALID_ARG; }
+    return RT_OK;
+}
+
+int upload_materials(rt_pipeline *p)
+{
+    if (!p->mats_dirty) return RT_OK;
+    RT_TRY(p->d_mats.reserve(sizeof(rt_material_params) * p->mats.size()));
+    HIP_TRY(hipMemcpyAsync(p->d_mats.p, p->mats.data(), sizeof(rt_material_params) * p->mats.size(), hipMemcpyHostToDevice, p->ctx->stream));
+    p->mats_dirty = false;
+    return RT_OK;
+}
+
+// the set's lights: the free sphere around the first frame's point light, and the shadow cache of the coming launches
+int prepare_lights(rt_pipeline *p, PipeDev &pd, const SetPlan &plan, const rt_per_frame_constants &first)
+{
+    pd.point_free = p->ctx->opt_free_radius ? free_radius(p, pd, &first.pointLight.worldPos.x) : 0.0f;
+    const LightRays lr = light_rays(1u, first);
+    if (plan.ao_view) p->shadow_cache.dev = ShadowCacheDev{};      // (the light buffer is keyed by the two lights: the AO view's random rays do not use it)
+    else RT_TRY(prepare_shadow_cache(p, &lr));
+    return RT_OK;
+}
+
+// the constants and light rays of a set's frames go to device memory: kernels index them by the frame of a slot
+int stage_set_constants(rt_pipeline *p, PipeDev &pd, const rt_per_frame_constants *frames)
+{
+    pd.pfc = frames[0]; pd.pfcs = nullptr; pd.frame_lights = nullptr;
+    if (pd.n_frames <= 1) return RT_OK;
+    std::vector<unsigned char> stage(BATCH_PFC_BYTES + BATCH_LIGHT_BYTES, 0);
+    for (uint32_t f = 0; f < pd.n_frames; f++) {
+        memcpy(&stage[sizeof(rt_per_frame_constants) * f], &frames[f], sizeof(rt_per_frame_constants));
+        LightRays lr = light_rays(pd.shadow_compact, frames[f]);
+        // (frames whose point light is where the first frame's is share its sphere; a frame with another light gets none)
+        lr.point_free = memcmp(lr.point_pos, &frames[0].pointLight.worldPos, 3 * sizeof(float)) == 0 ? pd.point_free : 0.0f;
+        memcpy(&stage[BATCH_PFC_BYTES + sizeof(LightRays) * f], &lr, sizeof lr);
     }
-    if (p->mats_dirty) {
-        RT_TRY(p->d_mats.reserve(sizeof(rt_material_params) * p->mats.size()));
-        HIP_TRY(hipMemcpyAsync(p->d_mats.p, p->mats.data(), sizeof(rt_material_params) * p->mats.size(), hipMemcpyHostToDevice, st));
-        p->mats_dirty = false;
-    }
-    const uint32_t tw = x1 - x0, th = y1 - y0;
-    const uint32_t tiles_x = (tw + 7u) / 8u, fcap = tiles_x * ((th + 7u) / 8u) * 64u;
-    RT_REQUIRE((uint64_t)fcap * n_frames < 0x40000000ull, "batch: more than 2^30 pixel slots in one set of launches");
-    const uint32_t cap = fcap * n_frames;
-    const bool ao_view = p->kind == RT_PIPELINE_PROGRESSIVE && frames[0].options.showAmbientOcclusionOnly;
-    const uint32_t shadow_slots = ao_view ? 4u : 2u;
-    // queue memory: the worst case up front when it fits the budget, else level by level as the counts come in (launch_frame)
-    const uint32_t levels_now = frame_levels(p);
-    const bool counted = worst_case_queue_bytes(cap, levels_now, p->max_shadow, shadow_slots, !ao_view) > queue_budget(p);
-    if (p->counters.bytes < POOL_OFFSET_WORDS * 4 + POOL_BYTES + PRIMARY_POOL_WORDS * 4) {
-        RT_TRY(p->counters.reserve(POOL_OFFSET_WORDS * 4 + POOL_BYTES + PRIMARY_POOL_WORDS * 4));
-        HIP_TRY(hipMemsetAsync(p->counters.p, 0, p->counters.bytes, st));
-    }
-    if (counted) RT_TRY(reserve_level_rays(p, 0, cap, levels_now > 1));
-    else RT_TRY(reserve_worst_case(p, cap, levels_now, p->max_shadow, shadow_slots, !ao_view));
-    p->counted_queues = counted;
-    if (!p->totals.p) {
-        RT_TRY(p->totals.reserve(8 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(p->totals.p, 0, 8 * sizeof(unsigned long long), st));
-    }
-    PipeDev pd;
-    // (threads of the largest launch: the primary stage runs one thread per pixel slot, the persistent stages fewer)
-    bool set_rows = false;
-    RT_TRY(scene_for_set(p, n_frames, &pd.sc, &set_rows));
-    pd.pfc = frames[0];
-    pd.n_frames = n_frames; pd.fcap = fcap;
-    pd.pfcs = nullptr; pd.frame_lights = nullptr;
-    pd.shadow_compact = ao_view ? 0u : 1u;          // the AO view's four rays have random directions
-    // (the light buffer is keyed by the two lights: the AO view's random rays do not use it)
-    const bool free_on = ctx->opt_free_radius;
-    {
-        const float lp0[3] = {frames[0].pointLight.worldPos.x, frames[0].pointLight.worldPos.y, frames[0].pointLight.worldPos.z};
-        pd.point_free = free_on ? free_radius(p, pd, lp0) : 0.0f;
-    }
-    if (ao_view) p->shadow_cache_dev = ShadowCacheDev{};
-    else RT_TRY(prepare_shadow_cache(p, light_rays(1u, frames[0])));
-    if (n_frames > 1) {
-        // the batch's constants and light rays go to device memory: kernels index them by the frame of a slot
-        const size_t cb = sizeof(rt_per_frame_constants) * RT_MAX_BATCH, lb = sizeof(LightRays) * RT_MAX_BATCH;
-        RT_TRY(p->batch_consts.reserve(cb + lb));
-        std::vector<unsigned char> stage(cb + lb, 0);
-        for (uint32_t f = 0; f < n_frames; f++) {
-            memcpy(&stage[sizeof(rt_per_frame_constants) * f], &frames[f], sizeof(rt_per_frame_constants));
-            LightRays lr = light_rays(pd.shadow_compact, frames[f]);
-            // (frames whose point light is where the first frame's is share its sphere; a frame with another light gets none)
-            lr.point_free = free_on && memcmp(lr.point_pos, &frames[0].pointLight.worldPos, 3 * sizeof(float)) == 0 ? pd.point_free : 0.0f;
-            memcpy(&stage[cb + sizeof(LightRays) * f], &lr, sizeof lr);
-        }
-        HIP_TRY(hipMemcpyAsync(p->batch_consts.p, stage.data(), cb + lb, hipMemcpyHostToDevice, st));     // (pageable source: staged before the call returns)
-        pd.pfcs = p->batch_consts.as<rt_per_frame_constants>();
-        pd.frame_lights = (const LightRays *)((const char *)p->batch_consts.p + cb);
-    }
-    pd.mats = p->d_mats.as<rt_material_params>();
-    pd.nmats = (uint32_t)p->mats.size();
-    pd.env = p->d_env.as<float4>();
-    pd.env_size = p->env_size;
-    pd.env_filter = p->env_filter;
+    HIP_TRY(hipMemcpyAsync(p->batch_consts.p, stage.data(), stage.size(), hipMemcpyHostToDevice, p->ctx->stream));     // (pageable source: staged before the call returns)
+    pd.pfcs = p->batch_consts.as<rt_per_frame_constants>();
+    pd.frame_lights = (const LightRays *)((const char *)p->batch_consts.p + BATCH_PFC_BYTES);
+    return RT_OK;
+}
+
+// the rectangle [x0,x1) x [y0,y1) of the image a set of launches covers; band_rows != 0: the interleaved bands {b : b mod band_world == band_rank}
+// of band_rows rows each (the rectangle then spans the full width and the rank's rows, packed)
+struct Region { uint32_t x0, y0, x1, y1, band_rows, band_rank, band_world; };
+
+// everything of PipeDev that the pipeline's state, the plan and the region decide (the scene, the lights and the constants are in already;
+// the primary stage's choice follows)
+void fill_pipe_dev(const rt_pipeline *p, PipeDev &pd, const SetPlan &plan, const Region &r)
+{
+    const uint32_t tw = r.x1 - r.x0, th = r.y1 - r.y0, cap = plan.cap;
+    pd.mats = p->d_mats.as<rt_material_params>(); pd.nmats = (uint32_t)p->mats.size();
+    pd.env = p->d_env.as<float4>(); pd.env_size = p->env_size; pd.env_filter = p->env_filter;
     for (int k = 0; k < 3; k++) pd.env_const[k] = p->env_const[k];
-    pd.width = width; pd.height = height;
-    pd.x0 = x0; pd.y0 = y0; pd.tw = tw; pd.th = th; pd.cap = cap; pd.tiles_x = tiles_x;
-    pd.band_rows = band_rows; pd.band_rank = band_rank; pd.band_world = band_world;
+    pd.width = p->width; pd.height = p->height;
+    pd.x0 = r.x0; pd.y0 = r.y0; pd.tw = tw; pd.th = th; pd.cap = cap; pd.tiles_x = (tw + 7u) / 8u;
+    pd.band_rows = r.band_rows; pd.band_rank = r.band_rank; pd.band_world = r.band_world;
     uint32_t owned_rows = th;
-    if (band_rows) {            // rows of the rank's bands that lie inside the image (the last band may be short)
+    if (r.band_rows) {          // rows of the rank's bands that lie inside the image (the last band may be short)
         owned_rows = 0;
-        for (uint32_t b = band_rank; (uint64_t)b * band_rows < height; b += band_world)
-            owned_rows += (uint64_t)(b + 1) * band_rows <= height ? band_rows : height - b * band_rows;
+        for (uint32_t b = r.band_rank; (uint64_t)b * r.band_rows < p->height; b += r.band_world)
+            owned_rows += (uint64_t)(b + 1) * r.band_rows <= p->height ? r.band_rows : p->height - b * r.band_rows;
     }
     pd.n_pixels = tw * owned_rows;                  // (per frame)
     pd.max_rad = p->max_rad; pd.max_shadow = p->max_shadow;
-    pd.sh_log2 = ao_view ? 2u : 1u;
-    pd.sh_levels = shadow_levels(levels_now, p->max_shadow);
+    pd.sh_log2 = plan.sh_log2;
+    pd.sh_levels = shadow_levels(plan.levels, p->max_shadow);
     for (int k = 0; k <= MAXD; k++) pd.sh_cbase[k] = 0;
-    pd.accum_mode = p->accum_mode;
-    pd.accum_f16 = p->accum_f16;
-    pd.skip_unlit = p->skip_unlit;
-    pd.kind = p->kind;
-    // The primary stage as a persistent launch that refills its lanes from a pool of tiles (instead of one tile per wave, dealt by the
-    // hardware): pays where the rays of a tile part ways early -- two-level scenes, whose primary waves run at 0.48 of their lanes
-    // (4096 instances at 4K: 1.39 -> 1.31 ms) -- and costs 13 % where they stay together (the single-level bench scene: 0.69 of the lanes
-    // as it is).  The option primary_persistent = 0 / 1 overrides.  profiles/r04/c4_variants.txt, primary_persistent.txt
-    {   // (single-level scenes: one tile per wave, unless this scene's retry lists said otherwise -- rt_pipeline::PrimaryMode)
-        rt_pipeline::PrimaryMode &pm = p->primary_mode;
-        if (pm.gen != p->scene->generation) { pm.gen = p->scene->generation; pm.samples = 0; pm.persistent = false; pm.in_flight = false; }
-        if (pm.in_flight && hipEventQuery(pm.landed) == hipSuccess) {
-            pm.in_flight = false;
-            pm.samples++;
-            if ((double)*pm.h_count > 0.002 * (double)pm.asked_slots) pm.persistent = true;       // more than 0.2 % of the primary rays
-        }
-        pd.primary_persistent = (ctx->opt_primary_persistent < 0 ? (p->scene->two_level || pm.persistent) : ctx->opt_primary_persistent != 0) ? 1u : 0u;
-    }
-    pd.retry = nullptr;
-    pd.retry_cap = 0;
-    if (pd.sc.deep_stack && !pd.primary_persistent) {      // the primary launch keeps no rows beyond LDS: the list of the rays that would need one
-        const uint32_t want = ctx->opt_primary_retry_cap ? ctx->opt_primary_retry_cap : (1u << 20);
-        if (p->retry.bytes < (2 + (size_t)want) * 4) {
-            RT_TRY(p->retry.reserve((2 + (size_t)want) * 4));
-            HIP_TRY(hipMemsetAsync(p->retry.p, 0, 8, st));
-        }
-        pd.retry = p->retry.as<uint32_t>();
-        pd.retry_cap = want;
-    }
+    pd.accum_mode = p->accum_mode; pd.accum_f16 = p->accum_f16; pd.skip_unlit = p->skip_unlit; pd.kind = p->kind;
     pd.accum = p->accum;
-    pd.aov_direct = p->accum;                       // realtime: output 0 = direct lighting, output 1 = indirect specular
-    pd.aov_indirect = p->aov_own.as<float4>();
+    pd.aov_direct = p->accum; pd.aov_indirect = p->aov_own.as<float4>();      // realtime: output 0 = direct lighting, output 1 = indirect specular
     pd.counters = p->counters.as<uint32_t>();
     for (int l = 0; l <= MAXD; l++) {          // (counted queues: launch_frame binds a level again once it has sized it)
         bind_level(p, pd, l);
@@ -345,37 +277,78 @@ static int render_region(rt_pipeline *p, uint32_t width, uint32_t height, uint32
     static_assert(C_COUNT <= POOL_OFFSET_WORDS, "scalar counters overlap the chunk pools");
     pd.pools = pd.counters + POOL_OFFSET_WORDS;
     pd.totals = p->totals.as<unsigned long long>();
-    RT_TRY(rt_frame_launch(p, pd, shadow_slots, counted, set_rows));
-    HIP_TRY(hipGetLastError());
-    if (pd.retry && !p->primary_mode.in_flight && p->primary_mode.samples < 8 && ctx->opt_primary_persistent < 0) {
-        // this set's retry count, for the next sets' choice of primary launch (the set's compaction has cleared retry[0] and left the count in retry[1])
-        rt_pipeline::PrimaryMode &pm = p->primary_mode;
-        if (!pm.h_count) {
-            if (hipHostMalloc((void **)&pm.h_count, 64, hipHostMallocDefault) != hipSuccess) pm.h_count = nullptr;
-            else if (hipEventCreateWithFlags(&pm.landed, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(pm.h_count); pm.h_count = nullptr; pm.landed = nullptr; }
+}
+
+// how the primary stage of this set runs, and -- one tile per wave on a tree deeper than the LDS rows -- its retry list
+int choose_primary_stage(rt_pipeline *p, PipeDev &pd)
+{
+    rt_context *ctx = p->ctx;
+    pd.primary_persistent = p->primary_mode.choose(ctx, p->scene) ? 1u : 0u;
+    pd.retry = nullptr; pd.retry_cap = 0;
+    if (pd.sc.deep_stack && !pd.primary_persistent) {      // the primary launch keeps no rows beyond LDS: the list of the rays that would need one
+        const uint32_t want = ctx->opt_primary_retry_cap ? ctx->opt_primary_retry_cap : (1u << 20);
+        if (p->retry.bytes < (2 + (size_t)want) * 4) {
+            RT_TRY(p->retry.reserve((2 + (size_t)want) * 4));
+            HIP_TRY(hipMemsetAsync(p->retry.p, 0, 8, ctx->stream));
         }
-        if (pm.h_count && hipMemcpyAsync(pm.h_count, pd.retry + 1, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipEventRecord(pm.landed, st) == hipSuccess) {
-            pm.in_flight = true;
-            pm.asked_slots = cap;
-        }
+        pd.retry = p->retry.as<uint32_t>();
+        pd.retry_cap = want;
     }
+    return RT_OK;
+}
+
+// one frame, or one set of n_frames frames (frames == nullptr: the frame of the last rt_pipeline_update), over a region of the image
+int render_region(rt_pipeline *p, uint32_t width, uint32_t height, Region r, const rt_per_frame_constants *frames = nullptr, uint32_t n_frames = 1)
+{
+    RT_REQUIRE(p, "null pipeline");
+    RT_TRY(check_renderable(p, width, height, !frames, __func__));
+    if (!frames) { frames = &p->pfc; n_frames = 1; }
+    RT_REQUIRE(n_frames >= 1 && n_frames <= RT_MAX_BATCH, "batch size");
+    if (r.x1 > width) r.x1 = width;
+    if (!r.band_rows && r.y1 > height) r.y1 = height;      // (band mode: y counts the rank's packed rows, checked per pixel)
+    RT_REQUIRE(r.x0 < r.x1 && r.y0 < r.y1, "empty tile");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    p->rendered = false;
+    // RayGen early-out (ProgressiveRaytracing.hlsl:14-16): nothing is traced or written (batches: the caller has dropped such frames)
+    if (p->kind == RT_PIPELINE_PROGRESSIVE && frames[0].cameraParams.accumCount >= frames[0].options.maxIterations) {
+        memset(&p->stats, 0, sizeof p->stats);
+        return RT_OK;
+    }
+    RT_TRY(upload_materials(p));
+    SetPlan plan;
+    RT_TRY(plan_set(p, r.x1 - r.x0, r.y1 - r.y0, n_frames, p->kind == RT_PIPELINE_PROGRESSIVE && frames[0].options.showAmbientOcclusionOnly, __func__, &plan));
+    RT_TRY(reserve_set(p, plan));
+    p->counted_queues = plan.counted;
+    PipeDev pd;
+    bool set_rows = false;
+    RT_TRY(scene_for_set(p, n_frames, &pd.sc, &set_rows));
+    pd.n_frames = n_frames; pd.fcap = plan.fcap;
+    pd.shadow_compact = plan.compact ? 1u : 0u;
+    RT_TRY(prepare_lights(p, pd, plan, frames[0]));
+    RT_TRY(stage_set_constants(p, pd, frames));
+    fill_pipe_dev(p, pd, plan, r);
+    RT_TRY(choose_primary_stage(p, pd));
+    RT_TRY(rt_frame_launch(p, pd, plan, set_rows));
+    HIP_TRY(hipGetLastError());
+    if (pd.retry) p->primary_mode.sample(p->ctx, pd.retry + 1, plan.cap, p->ctx->stream);      // this set's retry count, for the next sets' choice of primary launch
     p->last_pd = pd;
     p->last_scene_gen = p->scene->generation;
-    p->last_tile[0] = x0; p->last_tile[1] = y0; p->last_tile[2] = x1; p->last_tile[3] = y1;
+    p->last_tile[0] = r.x0; p->last_tile[1] = r.y0; p->last_tile[2] = r.x1; p->last_tile[3] = r.y1;
     p->last_pixels = pd.n_pixels * n_frames;
     p->rendered = true;
     return RT_OK;
 }
 
 // n frames through shared sets of launches; band_rows != 0: only the rank's interleaved bands of every frame
-static int render_frames(rt_pipeline *p, uint32_t width, uint32_t height, const rt_per_frame_constants *constants, uint32_t n,
-                         uint32_t band_rows, uint32_t band_rank, uint32_t band_world)
+int render_frames(rt_pipeline *p, uint32_t width, uint32_t height, const rt_per_frame_constants *constants, uint32_t n,
+                  uint32_t band_rows, uint32_t band_rank, uint32_t band_world)
 {
     uint32_t band_count = 0;
     if (band_rows) {
         RT_TRY(rt_tile_bands(height, band_rows, band_rank, band_world, nullptr, nullptr, 0, &band_count));
         if (band_count == 0) n = 0;             // more ranks than bands: nothing to render here (the constants still become current)
     }
+    const Region region = band_rows ? Region{0, 0, width, band_count * band_rows, band_rows, band_rank, band_world} : Region{0, 0, width, height, 0, 0, 1};
     uint32_t batch_max = RT_MAX_BATCH;
     if (p->ctx->opt_batch_max >= 1 && p->ctx->opt_batch_max <= RT_MAX_BATCH) batch_max = p->ctx->opt_batch_max;
     // frames RayGen would leave at once (accumCount >= maxIterations, ProgressiveRaytracing.hlsl:14-16) are dropped here;
@@ -385,8 +358,7 @@ static int render_frames(rt_pipeline *p, uint32_t width, uint32_t height, const 
         // the queues grow with the batch: when the device cannot hold them, the same frames go through in smaller sets
         for (size_t at = 0; at < run.size();) {
             const size_t n_now = run.size() - at < batch_max ? run.size() - at : batch_max;
-            const int rc = band_rows ? render_region(p, width, height, 0, 0, width, band_count * band_rows, band_rows, band_rank, band_world, run.data() + at, (uint32_t)n_now)
-                                     : render_region(p, width, height, 0, 0, width, height, 0, 0, 1, run.data() + at, (uint32_t)n_now);
+            const int rc = render_region(p, width, height, region, run.data() + at, (uint32_t)n_now);
             if (rc == RT_ERR_OOM && n_now > 1) { batch_max = (uint32_t)(n_now / 2); continue; }
             if (rc != RT_OK) { run.clear(); return rc; }
             at += n_now;
@@ -403,9 +375,7 @@ static int render_frames(rt_pipeline *p, uint32_t width, uint32_t height, const 
     return flush();
 }
 
-}  // extern "C"
-
-static int flush_pending_now(rt_pipeline *p)
+int flush_pending_now(rt_pipeline *p)
 {
     if (p->pending.empty()) return RT_OK;
     std::vector<rt_per_frame_constants> frames;
@@ -416,6 +386,46 @@ static int flush_pending_now(rt_pipeline *p)
     const int rc = render_frames(p, p->width, p->height, frames.data(), (uint32_t)frames.size(), 0, 0, 1);
     p->pfc = keep;
     return rc;
+}
+
+// The head and the tail of the two counting calls (`who`): the last frame's queues must still stand; `words` counters are cleared, filled
+// by `launch` (rt_frame_count_work / rt_frame_count_walk) and brought back into h.
+int count_replay(rt_pipeline *p, const char *who, int (*launch)(rt_pipeline *, unsigned long long *), unsigned long long *h, size_t words)
+{
+    RT_TRY(rt_pipeline_flush_pending(p));
+    if (!p->rendered || !p->scene->built || p->scene->generation != p->last_scene_gen) { rt_set_error("%s: nothing rendered since the last change of scene, materials or output", who); return RT_ERR_STATE; }
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    RT_TRY(p->work.reserve(RT_STAGE_COUNT * RT_WALK_WORDS * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(p->work.p, 0, words * sizeof(unsigned long long), st));
+    RT_TRY(launch(p, p->work.as<unsigned long long>()));
+    HIP_TRY(hipMemcpyAsync(h, p->work.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+}  // namespace
+
+// The primary stage as a persistent launch that refills its lanes from a pool of tiles (instead of one tile per wave, dealt by the
+// hardware): pays where the rays of a tile part ways early -- two-level scenes, whose primary waves run at 0.48 of their lanes
+// (4096 instances at 4K: 1.39 -> 1.31 ms) -- and costs 13 % where they stay together (the single-level bench scene: 0.69 of the lanes
+// as it is).  The option primary_persistent = 0 / 1 overrides.  profiles/r04/c4_variants.txt, primary_persistent.txt
+// (single-level scenes: one tile per wave, unless this scene's retry lists said otherwise -- rt_pipeline::PrimaryMode)
+bool rt_pipeline::PrimaryMode::choose(const rt_context *ctx, const rt_scene *scene)
+{
+    if (gen != scene->generation) { gen = scene->generation; samples = 0; persistent = false; back.in_flight = false; }
+    if (back.landed()) {
+        samples++;
+        if ((double)back.read<uint32_t>() > 0.002 * (double)asked_slots) persistent = true;       // more than 0.2 % of the primary rays
+    }
+    return ctx->opt_primary_persistent < 0 ? (scene->two_level || persistent) : ctx->opt_primary_persistent != 0;
+}
+
+// (the set's compaction has cleared retry[0] and left the count in retry[1]: d_count)
+void rt_pipeline::PrimaryMode::sample(const rt_context *ctx, const uint32_t *d_count, uint32_t slots, hipStream_t st)
+{
+    if (back.in_flight || samples >= 8 || ctx->opt_primary_persistent >= 0) return;
+    if (back.send(d_count, 4, st)) asked_slots = slots;
 }
 
 // every entry point of the pipeline that renders, reads or changes what recorded frames would see calls this first
@@ -475,7 +485,7 @@ int rt_pipeline_get_deferred(const rt_pipeline *p, uint32_t *max_frames, uint32_
 int rt_pipeline_render_tile(rt_pipeline *p, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
 {
     RT_TRY(rt_pipeline_flush_pending(p));
-    return render_region(p, width, height, x0, y0, x1, y1, 0, 0, 1);
+    return render_region(p, width, height, Region{x0, y0, x1, y1, 0, 0, 1});
 }
 
 int rt_pipeline_render_bands(rt_pipeline *p, uint32_t width, uint32_t height, uint32_t band_rows, uint32_t rank, uint32_t world)
@@ -486,19 +496,14 @@ int rt_pipeline_render_bands(rt_pipeline *p, uint32_t width, uint32_t height, ui
     uint32_t n = 0;
     RT_TRY(rt_tile_bands(height, band_rows, rank, world, nullptr, nullptr, 0, &n));
     if (n == 0) return RT_OK;                   // more ranks than bands: nothing to render here
-    return render_region(p, width, height, 0, 0, width, n * band_rows, band_rows, rank, world);
+    return render_region(p, width, height, Region{0, 0, width, n * band_rows, band_rows, rank, world});
 }
 
 int rt_pipeline_render(rt_pipeline *p, uint32_t width, uint32_t height)
 {
     RT_REQUIRE(p, "null pipeline");
     if (p->deferred_max > 1 && p->kind == RT_PIPELINE_PROGRESSIVE) {
-        // the checks render_region would make now, so that a bad call fails where it is made and not at some later flush
-        if (!p->scene || !p->scene->built) { if (!rt_scene_stale_error(p->scene, "render")) rt_set_error("render: acceleration structures not built"); return RT_ERR_STATE; }
-        if (!p->accum) { rt_set_error("render: no output resource"); return RT_ERR_STATE; }
-        if (!p->have_pfc) { rt_set_error("render: update() has not been called"); return RT_ERR_STATE; }
-        if (p->mats.empty()) { rt_set_error("render: no material"); return RT_ERR_STATE; }
-        RT_REQUIRE(width == p->width && height == p->height, "width/height differ from the output resource");
+        RT_TRY(check_renderable(p, width, height, true, __func__));      // a bad call fails where it is made and not at some later flush
         if (p->pending.empty()) p->ctx->deferred.push_back(p);
         p->pending.push_back(p->pfc);
         p->rendered = false;                    // (nothing of the LAST frame is on the device yet: count_work / stats flush first)
@@ -555,31 +560,20 @@ int rt_pipeline_reserve_batch(rt_pipeline *p, uint32_t width, uint32_t height, u
 {
     RT_REQUIRE(p && width > 0 && height > 0 && frames >= 1 && frames <= RT_MAX_BATCH, "reserve_batch: bad argument");
     HIP_TRY(hipSetDevice(p->ctx->device));
-    const uint32_t fcap = ((width + 7u) / 8u) * ((height + 7u) / 8u) * 64u;
-    RT_REQUIRE((uint64_t)fcap * frames < 0x40000000ull, "batch: more than 2^30 pixel slots in one set of launches");
-    const bool ao_view = p->have_pfc && p->pfc.options.showAmbientOcclusionOnly != 0;
     // (a set whose worst case is over the budget sizes its levels by count as it goes: only the pixel slots are known now)
-    const uint32_t levels_now = frame_levels(p);
-    const size_t cap = (size_t)fcap * frames;
+    SetPlan plan;
+    RT_TRY(plan_set(p, width, height, frames, p->have_pfc && p->pfc.options.showAmbientOcclusionOnly != 0, __func__, &plan));
     // Any buffer this call grows is a buffer the last frame's replay calls (count_work, count_walk, read_primary_hits, ...) still hold
     // pointers to in last_pd: a reservation therefore ends what was "rendered" (the calls then refuse instead of
     // launching on freed memory).  Frames a deferred pipeline still holds are rendered first: they own the queues as they are.
     RT_TRY(rt_pipeline_flush_pending(p));
     p->rendered = false;
-    if (p->counters.bytes < POOL_OFFSET_WORDS * 4 + POOL_BYTES + PRIMARY_POOL_WORDS * 4) {
-        RT_TRY(p->counters.reserve(POOL_OFFSET_WORDS * 4 + POOL_BYTES + PRIMARY_POOL_WORDS * 4));
-        HIP_TRY(hipMemsetAsync(p->counters.p, 0, p->counters.bytes, p->ctx->stream));
-    }
-    if (worst_case_queue_bytes(cap, levels_now, p->max_shadow, ao_view ? 4u : 2u, !ao_view) > queue_budget(p)) RT_TRY(reserve_level_rays(p, 0, cap, levels_now > 1));
-    else RT_TRY(reserve_worst_case(p, cap, levels_now, p->max_shadow, ao_view ? 4u : 2u, !ao_view));
-    if (frames > 1) RT_TRY(p->batch_consts.reserve((sizeof(rt_per_frame_constants) + sizeof(LightRays)) * RT_MAX_BATCH));
+    RT_TRY(reserve_set(p, plan));
     if (p->scene && p->scene->built) {                 // the traversal kernels' global stack rows and the shadow cache's table as well
         SceneDev sc;
         RT_TRY(scene_for_set(p, frames, &sc));
-        LightRays only_allocate = no_light_rays();
-        only_allocate.on = 0xffffffffu;
-        RT_TRY(prepare_shadow_cache(p, only_allocate));
-        p->shadow_cache_dev = ShadowCacheDev{};
+        RT_TRY(prepare_shadow_cache(p, nullptr));
+        p->shadow_cache.dev = ShadowCacheDev{};
     }
     return RT_OK;
 }
@@ -589,7 +583,7 @@ int rt_pipeline_get_free_sphere(rt_pipeline *p, float *radius)
     RT_REQUIRE(p && radius, "get_free_sphere: null argument");
     *radius = 0.0f;
     rt_pipeline::FreeSphere &f = p->free_sphere;
-    if (!p->scene || !p->have_pfc || !f.landed) return RT_OK;
+    if (!p->scene || !p->have_pfc || !f.back.block) return RT_OK;
     HIP_TRY(hipSetDevice(p->ctx->device));
     free_sphere_poll(f);
     const float *lp = &p->pfc.pointLight.worldPos.x;
@@ -600,17 +594,8 @@ int rt_pipeline_get_free_sphere(rt_pipeline *p, float *radius)
 int rt_pipeline_count_work(rt_pipeline *p, rt_stage_work *out)
 {
     RT_REQUIRE(p && out, "null argument");
-    RT_TRY(rt_pipeline_flush_pending(p));
-    if (!p->rendered || !p->scene->built || p->scene->generation != p->last_scene_gen) { rt_set_error("count_work: nothing rendered since the last change of scene, materials or output"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    RT_TRY(p->work.reserve(RT_STAGE_COUNT * RT_WALK_WORDS * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(p->work.p, 0, RT_STAGE_COUNT * 3 * sizeof(unsigned long long), st));
-    unsigned long long *w = p->work.as<unsigned long long>();
-    RT_TRY(rt_frame_count_work(p, w));
     unsigned long long h[RT_STAGE_COUNT * 3];
-    HIP_TRY(hipMemcpyAsync(h, w, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    RT_TRY(count_replay(p, "count_work", rt_frame_count_work, h, RT_STAGE_COUNT * 3));
     for (int k = 0; k < RT_STAGE_COUNT; k++) { out[k].rays = h[3 * k]; out[k].nodes = h[3 * k + 1]; out[k].tris = h[3 * k + 2]; }
     return RT_OK;
 }
@@ -618,18 +603,8 @@ int rt_pipeline_count_work(rt_pipeline *p, rt_stage_work *out)
 int rt_pipeline_count_walk(rt_pipeline *p, rt_stage_walk *out)
 {
     RT_REQUIRE(p && out, "null argument");
-    RT_TRY(rt_pipeline_flush_pending(p));
-    if (!p->rendered || !p->scene->built || p->scene->generation != p->last_scene_gen) { rt_set_error("count_walk: nothing rendered since the last change of scene, materials or output"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    const size_t bytes = RT_STAGE_COUNT * RT_WALK_WORDS * sizeof(unsigned long long);
-    RT_TRY(p->work.reserve(bytes));
-    HIP_TRY(hipMemsetAsync(p->work.p, 0, bytes, st));
-    unsigned long long *w = p->work.as<unsigned long long>();
-    RT_TRY(rt_frame_count_walk(p, w));
     unsigned long long h[RT_STAGE_COUNT * RT_WALK_WORDS];
-    HIP_TRY(hipMemcpyAsync(h, w, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    RT_TRY(count_replay(p, "count_walk", rt_frame_count_walk, h, RT_STAGE_COUNT * RT_WALK_WORDS));
     for (int k = 0; k < RT_STAGE_COUNT; k++) {
         const unsigned long long *hk = h + RT_WALK_WORDS * k;
         out[k].rays = hk[0]; out[k].nodes_global = hk[1]; out[k].nodes_lds = hk[2];

@@ -1,7 +1,9 @@
-// devbuf_semantics.cpp -- DevBuf (the owning device allocation) and Carver (the build arena's slicer) of csrc/rt_internal.h on the host,
+// devbuf_semantics.cpp -- DevBuf (the owning device allocation), Carver (the build arena's slicer) and PinnedReadback (a page-locked block
+// + the event of the copy into it) of csrc/rt_internal.h on the host,
 // under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_devbuf_semantics.py).  The header is the product's own; the HIP
 // allocator behind it is restated here over malloc, with a count of live blocks and a refusal that can be armed, so that every path
 // of reserve / release / adopt / move runs without a device and a block freed twice or never is a sanitizer report or a wrong count.
+#include <sanitizer/asan_interface.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,6 +39,67 @@ extern "C" hipError_t hipGetLastError(void) { return hipSuccess; }
 extern "C" const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "error"; }
 void rt_set_error(const char *, ...) {}
 size_t &rt_alloc_limit_ref() { return g_limit; }
+
+// ... and the page-locked allocator, events and the asynchronous copy behind PinnedReadback: live counts, a refusal that can be armed on
+// each of the two creations, on the copy and on the record; a copy is carried out when a query first finds its event complete
+static std::set<void *> g_host, g_events;
+static int g_fail_host = 0, g_fail_event = 0, g_fail_copy = 0, g_fail_record = 0;
+static int g_host_frees = 0, g_event_destroys = 0;
+static bool g_event_complete = false;
+static struct { void *dst; const void *src; size_t bytes; } g_copy = {nullptr, nullptr, 0};
+
+extern "C" hipError_t hipHostMalloc(void **ptr, size_t size, unsigned int)
+{
+    if (g_fail_host > 0) { g_fail_host--; *ptr = nullptr; return hipErrorOutOfMemory; }
+    *ptr = malloc(size);
+    g_host.insert(*ptr);
+    return hipSuccess;
+}
+extern "C" hipError_t hipHostFree(void *ptr)
+{
+    if (!g_host.erase(ptr)) { fprintf(stderr, "hipHostFree of a block that is not live: %p\n", ptr); g_failures++; return hipErrorInvalidValue; }
+    g_host_frees++;
+    if (g_copy.dst == ptr) g_copy.dst = nullptr;       // (the owner has joined the stream: nothing lands any more)
+    ASAN_UNPOISON_MEMORY_REGION(ptr, 64);
+    free(ptr);
+    return hipSuccess;
+}
+extern "C" hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
+{
+    if (flags != hipEventDisableTiming) { fprintf(stderr, "an event that keeps time\n"); g_failures++; }
+    if (g_fail_event > 0) { g_fail_event--; *e = nullptr; return hipErrorOutOfMemory; }
+    *e = (hipEvent_t)malloc(1);
+    g_events.insert(*e);
+    return hipSuccess;
+}
+extern "C" hipError_t hipEventDestroy(hipEvent_t e)
+{
+    if (!g_events.erase(e)) { fprintf(stderr, "hipEventDestroy of an event that is not live: %p\n", (void *)e); g_failures++; return hipErrorInvalidValue; }
+    g_event_destroys++;
+    free(e);
+    return hipSuccess;
+}
+extern "C" hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t)
+{
+    if (g_fail_copy > 0) { g_fail_copy--; return hipErrorInvalidValue; }
+    if (kind != hipMemcpyDeviceToHost || !g_host.count(dst)) { fprintf(stderr, "a copy that is no read-back into a live block\n"); g_failures++; }
+    g_copy = {dst, src, bytes};
+    return hipSuccess;
+}
+extern "C" hipError_t hipEventRecord(hipEvent_t e, hipStream_t)
+{
+    if (g_fail_record > 0) { g_fail_record--; return hipErrorInvalidValue; }
+    if (!g_events.count(e)) { fprintf(stderr, "record of an event that is not live\n"); g_failures++; }
+    g_event_complete = false;
+    return hipSuccess;
+}
+extern "C" hipError_t hipEventQuery(hipEvent_t e)
+{
+    if (!g_events.count(e)) { fprintf(stderr, "query of an event that is not live\n"); g_failures++; return hipErrorInvalidValue; }
+    if (!g_event_complete) return hipErrorNotReady;
+    if (g_copy.dst) { memcpy(g_copy.dst, g_copy.src, g_copy.bytes); g_copy.dst = nullptr; }
+    return hipSuccess;
+}
 
 #define CHECK(cond)                                                             \
     do {                                                                        \
@@ -204,6 +267,86 @@ static void carver_slices()
     }
 }
 
+static void readback_creation_is_all_or_nothing()
+{
+    {
+        PinnedReadback r;
+        g_fail_event = 1;                                          // the block is there, the event is refused: the block goes back
+        CHECK(!r.ready() && r.block == nullptr && r.event == nullptr && g_host.empty() && g_events.empty() && g_host_frees == 1);
+        g_fail_host = 1;
+        CHECK(!r.ready() && r.block == nullptr && g_host.empty() && g_events.empty() && g_fail_event == 0);
+        uint32_t word = 7;
+        g_fail_host = 1;                                           // send() creates as well, and a refusal leaves nothing in flight
+        CHECK(!r.send(&word, 4, nullptr) && !r.in_flight && g_host.empty() && g_events.empty());
+        CHECK(r.ready() && r.block && r.event && g_host.size() == 1 && g_events.size() == 1);      // a later call tries again
+        void *const block = r.block;
+        CHECK(r.ready() && r.block == block && g_host.size() == 1 && g_events.size() == 1);        // and only once
+    }
+    CHECK(g_host.empty() && g_events.empty() && g_host_frees == 2 && g_event_destroys == 1);
+}
+
+static void readback_send_and_landed()
+{
+    PinnedReadback r;
+    uint32_t word = 0x12345678u;
+    CHECK(!r.landed());                                            // nothing made, nothing sent: no query of a null event
+    g_fail_copy = 1;
+    CHECK(!r.send(&word, 4, nullptr) && !r.in_flight && g_fail_copy == 0);
+    g_fail_record = 1;
+    CHECK(!r.send(&word, 4, nullptr) && !r.in_flight && g_fail_record == 0);
+    g_event_complete = true;
+    CHECK(!r.landed());                                            // ... whatever the event says
+    g_copy.dst = nullptr;
+    CHECK(r.send(&word, 4, nullptr) && r.in_flight);
+    CHECK(!r.landed() && !r.landed() && r.in_flight);              // not ready: false, as often as it is asked
+    g_event_complete = true;
+    CHECK(r.landed() && !r.in_flight && r.read<uint32_t>() == 0x12345678u);
+    CHECK(!r.landed() && !r.landed());                             // true once per flight
+    float f = 2.5f;
+    CHECK(r.send(&f, 4, nullptr) && !r.landed());
+    r.in_flight = false;                                           // a flight nobody asks about any more
+    g_event_complete = true;
+    CHECK(!r.in_flight && !r.landed());
+    CHECK(!r.send(&word, 65, nullptr) && !r.in_flight);            // the block holds 64 bytes
+}
+
+static void readback_moves_and_frees_once()
+{
+    const int frees = g_host_frees, destroys = g_event_destroys;
+    {
+        PinnedReadback a;
+        uint32_t word = 3;
+        CHECK(a.send(&word, 4, nullptr));
+        void *const block = a.block;
+        const hipEvent_t event = a.event;
+        PinnedReadback b(std::move(a));
+        CHECK(a.block == nullptr && a.event == nullptr && !a.in_flight);
+        CHECK(b.block == block && b.event == event && b.in_flight && g_host.size() == 1 && g_events.size() == 1);
+        PinnedReadback c;
+        CHECK(c.ready() && g_host.size() == 2);
+        c = std::move(b);                                          // move-assignment lets go of what it had
+        CHECK(g_host_frees == frees + 1 && g_event_destroys == destroys + 1 && c.block == block && c.in_flight && b.block == nullptr);
+        PinnedReadback &same = c;
+        c = std::move(same);
+        CHECK(c.block == block && g_host.size() == 1);
+        g_event_complete = true;
+        CHECK(!a.landed() && !b.landed() && c.landed() && c.read<uint32_t>() == 3);
+    }
+    CHECK(g_host.empty() && g_events.empty() && g_host_frees == frees + 2 && g_event_destroys == destroys + 2);
+}
+
+static void readback_dies_with_a_copy_in_flight()
+{
+    const int frees = g_host_frees;
+    {
+        PinnedReadback r;
+        uint32_t word = 9;
+        CHECK(r.send(&word, 4, nullptr) && !r.landed() && r.in_flight);
+        ASAN_POISON_MEMORY_REGION(r.block, 64);                    // a destructor that reads or writes the block is a sanitizer report
+    }
+    CHECK(g_host.empty() && g_events.empty() && g_host_frees == frees + 1);
+}
+
 int main()
 {
     scope_exit_frees();
@@ -214,7 +357,12 @@ int main()
     out_of_memory_then_retry();
     the_alloc_limit_is_honoured();
     carver_slices();
-    CHECK(g_live.empty());
-    printf("%d failures, %zu live allocations\n", g_failures, g_live.size());
-    return g_failures == 0 && g_live.empty() ? 0 : 1;
+    readback_creation_is_all_or_nothing();
+    readback_send_and_landed();
+    readback_moves_and_frees_once();
+    readback_dies_with_a_copy_in_flight();
+    const size_t live = g_live.size() + g_host.size() + g_events.size();
+    CHECK(live == 0);
+    printf("%d failures, %zu live allocations\n", g_failures, live);
+    return g_failures == 0 && live == 0 ? 0 : 1;
 }

@@ -1,10 +1,14 @@
-"""DevBuf, the owning device allocation every object of the library is made of, and Carver, which slices the build arena, under
-AddressSanitizer + UndefinedBehaviorSanitizer on the host.
+"""DevBuf, the owning device allocation every object of the library is made of, Carver, which slices the build arena, and
+PinnedReadback, the page-locked block + event a scalar comes back from the device through, under AddressSanitizer +
+UndefinedBehaviorSanitizer on the host.
 
 tests/cpp/devbuf_semantics.cpp includes the product's csrc/rt_internal.h and puts a malloc-backed allocator with a live-block count and
 an injectable refusal behind it: scope exit frees, a move leaves its source empty and frees once, move-assignment frees the old block,
 an adopted slice is never freed, a failed growth keeps the buffer, out-of-memory-then-retry ends with the new block or an empty buffer,
-the allocation limit holds, and a sizing run of the carver ends at the offset of the real one.  No device, no library: g++ only."""
+the allocation limit holds, and a sizing run of the carver ends at the offset of the real one.  The read-back (page-locked memory, events
+and the asynchronous copy restated the same way): creation is all or nothing and tried again, a failed send leaves nothing in flight,
+landed() is true once per flight, a move empties its source, destruction frees once and never touches the block.  No device, no
+library: g++ only."""
 import os
 import subprocess
 

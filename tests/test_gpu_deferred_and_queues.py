@@ -317,25 +317,44 @@ def test_failed_queue_growth_leaves_the_pipeline_usable(gpu, capi):
         capi.lib().rt_debug_set_alloc_limit(0)
 
 
-def test_reserve_batch_leaves_nothing_to_allocate(gpu, capi):
+def two_cornells(capi, gpu, W, H):
+    """a two-level scene: two instances of the Cornell box, one translated"""
+    m = capi.Model(gpu, path=CORNELL_OBJ)
+    sc = capi.Scene(gpu)
+    sc.add_model(m)
+    sc.add_model(m, np.array([1, 0, 0, 2.5, 0, 1, 0, 0, 0, 0, 1, -1.0], np.float32))
+    p = capi.Pipeline(gpu)
+    p.set_scene(sc)
+    p.add_material(T.default_material())
+    p.add_material(T.default_material())
+    p.set_environment_cube(scenes.sky_cubemap(16))
+    p.create_output(W, H)
+    p.build_acceleration_structures()
+    return p, cam_array(scenes.cornell_camera(), W / H)
+
+
+@pytest.mark.parametrize("case", ["atrium", "two_level"])
+def test_reserve_batch_leaves_nothing_to_allocate(gpu, capi, case):
     """rt_pipeline_reserve_batch(S) reserves EVERYTHING a set of S frames allocates -- queues, constants, the shadow cache's table
     and the traversal kernels' global stack rows (4.3 GB for 20 frames of 1080p; round 4: that one was missing, and on some boxes
     its hipMalloc took 126 ms inside the first set's render() call, i.e. inside bench.py's timed region).  With every device
     allocation forbidden after the call, a deferred set of S frames (after a smaller warm-up set, as bench.py issues them) must
-    still render, and to the same bits."""
-    W, H, S = 320, 180, 12
-    p, cam = atrium(capi, gpu, W, H)
-    pfcs = frames_of(capi, cam, 3 + S, W, H)
+    still render, and to the same bits.  The call and the render calls size a set by one plan (rt_pipeline_queues.h); the atrium takes it
+    through 4-byte shadow-cache entries and the one-tile-per-wave primary stage, the two-level scene through 8-byte entries, the
+    per-pixel entries and the persistent primary stage."""
+    make, W, H, S, warm = (atrium, 320, 180, 12, 3) if case == "atrium" else (two_cornells, 64, 48, 4, 2)
+    p, cam = make(capi, gpu, W, H)
+    pfcs = frames_of(capi, cam, warm + S, W, H)
     want, t1 = immediate(p, pfcs)
-    q, _ = atrium(capi, gpu, W, H)
+    q, _ = make(capi, gpu, W, H)
     q.reserve_batch(S)
     q.set_deferred(S)
-    for c in pfcs[:3]:                      # a smaller set first
+    for c in pfcs[:warm]:                   # a smaller set first
         q.update(c); q.render()
     q.flush()
     try:
         capi.lib().rt_debug_set_alloc_limit(1)
-        for c in pfcs[3:]:
+        for c in pfcs[warm:]:
             q.update(c); q.render()         # the S-th call renders the set
         assert q.deferred()[1] == 0
         capi.lib().rt_debug_set_alloc_limit(0)

@@ -149,3 +149,70 @@ def test_failed_builds_leak_nothing(gpu, capi):
             _ladder_of_failed_builds(capi, ctx, v, t, rays)
         finally:
             ctx.close()
+
+
+def _atrium_pipeline(capi, ctx, model, W, H):
+    sc = capi.Scene(ctx)
+    sc.add_model(model)
+    p = capi.Pipeline(ctx)
+    p.set_scene(sc)
+    p.add_material(T.default_material())
+    p.set_environment_cube(scenes.sky_cubemap(16))
+    p.create_output(W, H)
+    p.build_acceleration_structures()
+    return p
+
+
+def _five_frames(capi, p, pfcs, limit=0):
+    """frame 1 by render(), frames 2 - 5 as one render_batch, with device allocations above `limit` bytes refused: the image and the totals"""
+    try:
+        capi.lib().rt_debug_set_alloc_limit(limit)
+        p.update(pfcs[0])
+        p.render()
+        p.render_batch(pfcs[1:5])
+    finally:
+        capi.lib().rt_debug_set_alloc_limit(0)
+    return p.read_output(), p.totals()
+
+
+def test_failed_render_reservations_leak_nothing(gpu, capi):
+    """The ladder of the builds, for the render path: on a fresh pipeline, set up and built, device allocations above a limit are refused
+    (rt_debug_set_alloc_limit, 1 KiB walked up to 256 MiB in steps of 4x) while one render() and a render_batch of four frames reserve the
+    materials, counters, queues, totals, constants, shadow cache and retry list.  Every rung either reports RT_ERR_OOM or gives the image
+    and the ray totals of the unrestricted run bit for bit; afterwards the last pipeline still renders what an unrestricted one does and
+    the device's free memory is where it was.  The scene is the atrium of test_gpu_deferred_and_queues.py."""
+    from test_gpu_batch import frames_of
+    W, H = 64, 48
+    model = capi.Model(gpu, *scenes.sponza_class(seed=42))
+    cam = cam_array(scenes.sponza_camera(), W / H)
+    pfcs = frames_of(capi, cam, 8, W, H)
+    ref = _atrium_pipeline(capi, gpu, model, W, H)
+    want, want_totals = _five_frames(capi, ref, pfcs)
+    gc.collect()
+    gpu.synchronize()
+    base = free_bytes()
+    raised, rendered, p = [], [], None
+    for k in range(10):
+        if p is not None:
+            p.close()
+        p = _atrium_pipeline(capi, gpu, model, W, H)
+        try:
+            got, got_totals = _five_frames(capi, p, pfcs, 1024 * 4 ** k)
+        except capi.RtError as e:
+            assert e.code == RT_ERR_OOM, "rung %d (limit %d bytes): %r" % (k, 1024 * 4 ** k, e)
+            raised.append(k)
+            continue
+        assert np.array_equal(got, want), "rung %d: %d pixels differ" % (k, int((got != want).any(axis=2).sum()))
+        assert got_totals == want_totals, (k, got_totals, want_totals)
+        rendered.append(k)
+    assert raised and rendered and rendered[-1] == 9, (raised, rendered)
+    for c in pfcs[5:]:
+        for q in (p, ref):
+            q.update(c); q.render()
+    assert np.array_equal(p.read_output(), ref.read_output())
+    assert p.totals() == ref.totals()
+    p.close()
+    gc.collect()
+    gpu.synchronize()
+    leaked = base - free_bytes()
+    assert leaked < (8 << 20), "device memory shrank by %d bytes over the refused reservations of rungs %s" % (leaked, raised)
