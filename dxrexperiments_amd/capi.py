@@ -50,6 +50,7 @@ WIDE_STEP_ANYHIT, WIDE_STEP_DEEP, WIDE_STEP_LDS_TOP = 1, 2, 4
 WIDE_STEP_TOP_NODES = 128          # nodes of the LDS-resident top (csrc/rt_internal.h RT_TOP_NODES)
 NODE_EMPTY, NODE_NONE = 0x7FFFFFFE, -2 ** 31
 CUBE_SEAMLESS, CUBE_FACE_CLAMP = 0, 1
+MEM_HOST, MEM_DEVICE = 0, 1         # RT_MEM_HOST, RT_MEM_DEVICE (include/dxr_amd.h)
 DENOISER_PARAMS = np.dtype([("exposure", "<f4"), ("gamma", "<f4"), ("tonemap", "<u4"), ("gammaCorrect", "<u4"),
                             ("maxKernelSize", "<i4"), ("debugVisualize", "<u4")])
 
@@ -76,6 +77,9 @@ SIGNATURES = {
     "rt_model_create_from_arrays": (_i, [_p, _p, _u32, _p, _u32, _pp]),
     "rt_model_get_counts": (_i, [_p, _pu, _pu]),
     "rt_model_read_geometry": (_i, [_p, _p, _p]),
+    "rt_model_set_vertices": (_i, [_p, _u32, _u32, _p, _u32]),
+    "rt_model_set_positions": (_i, [_p, _u32, _u32, _p, _u32]),
+    "rt_model_recompute_normals": (_i, [_p]),
     "rt_model_retain": (_i, [_p]),
     "rt_model_destroy": (_i, [_p]),
     "rt_scene_create": (_i, [_p, _pp]),
@@ -391,6 +395,30 @@ class Model:
         i = np.empty((nt, 3), np.uint32)
         _check(lib().rt_model_read_geometry(self.h, _ptr(v), _ptr(i)))
         return v, i
+
+    # Extensions (the reference's RtModel never changes): a mesh that changes shape.  Every built scene that holds the model is stale until
+    # its update() or build(), which rebuilds the model's BLAS.
+    def set_vertices(self, verts, first=0):
+        """vertices first .. first + len(verts) - 1 (T.VERTEX records) from a host array"""
+        v = np.ascontiguousarray(verts, dtype=T.VERTEX).reshape(-1)
+        _check(lib().rt_model_set_vertices(self.h, first, v.shape[0], _ptr(v), MEM_HOST))
+
+    def set_positions(self, xyz, first=0):
+        """... their positions only (float32[n, 3]); the normals are kept"""
+        p = _f32(xyz, (-1, 3))
+        _check(lib().rt_model_set_positions(self.h, first, p.shape[0], _ptr(p), MEM_HOST))
+
+    def set_vertices_device(self, ptr, count, first=0):
+        """... from `count` vertex records in device memory (a DeviceBuffer's .ptr, or any device pointer): copied device to device"""
+        _check(lib().rt_model_set_vertices(self.h, first, count, C.c_void_p(ptr), MEM_DEVICE))
+
+    def set_positions_device(self, ptr, count, first=0):
+        """... from count x 3 floats in device memory"""
+        _check(lib().rt_model_set_positions(self.h, first, count, C.c_void_p(ptr), MEM_DEVICE))
+
+    def recompute_normals(self):
+        """every vertex normal from the current positions, on the device (include/dxr_amd.h states the sum)"""
+        _check(lib().rt_model_recompute_normals(self.h))
 
 
 class Scene:

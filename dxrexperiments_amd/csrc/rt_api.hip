@@ -4,6 +4,7 @@
 #include <cstring>
 #include <new>
 
+#include "rt_adjacency.h"
 #include "rt_trace_device.h"
 
 static thread_local std::string g_last_error;
@@ -75,6 +76,39 @@ __global__ void k_debug_sample(int kind, const uint32_t *__restrict__ seeds, con
     vout[3 * i] = o.x; vout[3 * i + 1] = o.y; vout[3 * i + 2] = o.z;
     if (pdf_brdf) { pdf_brdf[2 * i] = pdf; pdf_brdf[2 * i + 1] = brdf; }
     if (seeds_out) seeds_out[i] = s;
+}
+
+// ---- deforming meshes: new vertices for a model (rt_model_set_positions, rt_model_recompute_normals) ----
+
+// count x 3 floats into the positions of the 24-byte vertex records first .. first + count - 1; the normals stay
+__global__ void k_set_positions(rt_vertex *__restrict__ verts, uint32_t first, uint32_t count, const float *__restrict__ xyz)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    rt_float3 p;
+    p.x = xyz[3 * (size_t)k]; p.y = xyz[3 * (size_t)k + 1]; p.z = xyz[3 * (size_t)k + 2];
+    verts[(size_t)first + k].position = p;
+}
+
+// One lane per vertex: the sum of cross(p1 - p0, p2 - p0) over the triangles of its CSR run (rt_adjacency.h: ascending, each once), in that
+// order, normalised; a sum whose squared length is 0, inf or NaN gives (0, 0, 0).  No atomics: the order of an fp32 sum is part of the result.
+__global__ void k_vertex_normals(rt_vertex *__restrict__ verts, uint32_t n_verts, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ off,
+                                 const uint32_t *__restrict__ tris)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_verts) return;
+    f3 s = mk3(0.0f, 0.0f, 0.0f);
+    for (uint32_t e = off[v]; e < off[v + 1]; e++) {
+        const size_t t = tris[e];
+        const rt_float3 a = verts[idx[3 * t]].position, b = verts[idx[3 * t + 1]].position, c = verts[idx[3 * t + 2]].position;
+        const f3 p0 = mk3(a.x, a.y, a.z);
+        s = s + cross(mk3(b.x, b.y, b.z) - p0, mk3(c.x, c.y, c.z) - p0);
+    }
+    const float d = dot(s, s);
+    const f3 n = (d > 0.0f && d < __uint_as_float(0x7f800000u)) ? normalize(s) : mk3(0.0f, 0.0f, 0.0f);
+    rt_float3 out;
+    out.x = n.x; out.y = n.y; out.z = n.z;
+    verts[v].normal = out;
 }
 
 int upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
@@ -272,7 +306,12 @@ rt_model::~rt_model()
 rt_scene::~rt_scene()
 {
     (void)hipSetDevice(ctx->device);
-    for (SceneInstance &in : inst) rt_model_destroy(in.model);
+    for (SceneInstance &in : inst) {
+        std::vector<rt_scene *> &held = in.model->scenes;      // (the model outlives this: the scene retains it)
+        for (size_t k = 0; k < held.size(); k++)
+            if (held[k] == this) { held.erase(held.begin() + k); break; }
+        rt_model_destroy(in.model);
+    }
 }
 
 extern "C" {
@@ -421,9 +460,112 @@ int rt_model_get_counts(const rt_model *m, uint32_t *n_verts, uint32_t *n_tris)
     return RT_OK;
 }
 
+// A set has gone through its checks and is about to write d_verts: frames a deferred pipeline holds are rendered first (they see the
+// mesh as it was).
+static int model_before_set(rt_model *m)
+{
+    RT_TRY(use_device(m->ctx));
+    return rt_context_flush_deferred(m->ctx);
+}
+
+// ... and has been queued: the BLAS is older than the vertices, every built scene that holds the model is stale.
+static void model_changed(rt_model *m)
+{
+    m->geom_gen++;
+    m->built = false;         // rt_scene_update and rt_scene_build rebuild the BLAS (rt_build_blas)
+    for (rt_scene *s : m->scenes)
+        if (s->updatable) s->built = false;            // (never built, or instances added since: the next build reads the new vertices anyway)
+}
+
+static int model_set_range_check(const rt_model *m, const char *who, uint32_t first, uint32_t count)
+{
+    if (first > m->n_verts || count > m->n_verts - first) {
+        rt_set_error("%s: vertices %u .. %llu out of range: the model has %u", who, first, (unsigned long long)first + count, m->n_verts);
+        return RT_ERR_STATE;
+    }
+    return RT_OK;
+}
+
+int rt_model_set_vertices(rt_model *m, uint32_t first, uint32_t count, const rt_vertex *verts, uint32_t mem)
+{
+    RT_REQUIRE(m && (verts || count == 0), "null argument");
+    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
+    RT_TRY(model_set_range_check(m, "rt_model_set_vertices", first, count));
+    if (count == 0) return RT_OK;
+    RT_TRY(model_before_set(m));
+    hipStream_t st = m->ctx->stream;
+    rt_vertex *dst = m->d_verts.as<rt_vertex>() + first;
+    const size_t bytes = sizeof(rt_vertex) * (size_t)count;
+    if (mem == RT_MEM_DEVICE) {
+        HIP_TRY(hipMemcpyAsync(dst, verts, bytes, hipMemcpyDeviceToDevice, st));
+        m->h_verts_stale = true;
+    } else {
+        HIP_TRY(hipMemcpyAsync(dst, verts, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));             // (the caller's array is its own again when the call returns)
+        if (!m->h_verts_stale) memcpy(m->h_verts.data() + first, verts, bytes);
+    }
+    model_changed(m);
+    return RT_OK;
+}
+
+int rt_model_set_positions(rt_model *m, uint32_t first, uint32_t count, const float *xyz, uint32_t mem)
+{
+    RT_REQUIRE(m && (xyz || count == 0), "null argument");
+    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
+    RT_TRY(model_set_range_check(m, "rt_model_set_positions", first, count));
+    if (count == 0) return RT_OK;
+    rt_context *ctx = m->ctx;
+    RT_TRY(model_before_set(m));
+    const float *src = xyz;
+    if (mem == RT_MEM_HOST) {
+        RT_TRY(upload(ctx, ctx->scratch[0], xyz, 12 * (size_t)count));
+        src = ctx->scratch[0].as<float>();
+    }
+    k_set_positions<<<(count + 255u) / 256u, 256, 0, ctx->stream>>>(m->d_verts.as<rt_vertex>(), first, count, src);
+    HIP_TRY(hipGetLastError());
+    if (mem == RT_MEM_HOST) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (!m->h_verts_stale)
+            for (uint32_t k = 0; k < count; k++) memcpy(&m->h_verts[(size_t)first + k].position, xyz + 3 * (size_t)k, 12);
+    } else m->h_verts_stale = true;
+    model_changed(m);
+    return RT_OK;
+}
+
+int rt_model_recompute_normals(rt_model *m)
+{
+    RT_REQUIRE(m, "null model");
+    rt_context *ctx = m->ctx;
+    RT_TRY(model_before_set(m));
+    if (!m->adj_ready) {      // once per model: the index list never changes
+        std::vector<uint32_t> off, tris;
+        if (m->n_tris > 0x55555555u || !rt_build_adjacency(m->h_idx.data(), m->n_tris, m->n_verts, off, tris)) {
+            rt_set_error("rt_model_recompute_normals: no adjacency for %u triangles over %u vertices", m->n_tris, m->n_verts);
+            return RT_ERR_UNSUPPORTED;
+        }
+        RT_TRY(upload(ctx, m->adj_off, off.data(), 4 * off.size()));
+        RT_TRY(upload(ctx, m->adj_tris, tris.data(), 4 * tris.size()));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));    // (the vectors go out of scope)
+        m->adj_ready = true;
+    }
+    k_vertex_normals<<<(m->n_verts + 255u) / 256u, 256, 0, ctx->stream>>>(m->d_verts.as<rt_vertex>(), m->n_verts, m->d_idx.as<uint32_t>(),
+                                                                          m->adj_off.as<uint32_t>(), m->adj_tris.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    m->h_verts_stale = true;
+    model_changed(m);
+    return RT_OK;
+}
+
 int rt_model_read_geometry(const rt_model *m, rt_vertex *verts, uint32_t *indices)
 {
     RT_REQUIRE(m, "null model");
+    if (verts && m->h_verts_stale) {                   // vertices set from device memory: the host mirror follows on demand
+        rt_model *w = const_cast<rt_model *>(m);
+        RT_TRY(use_device(m->ctx));
+        HIP_TRY(hipMemcpyAsync(w->h_verts.data(), m->d_verts.p, sizeof(rt_vertex) * m->h_verts.size(), hipMemcpyDeviceToHost, m->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+        w->h_verts_stale = false;
+    }
     if (verts) memcpy(verts, m->h_verts.data(), sizeof(rt_vertex) * m->h_verts.size());
     if (indices) memcpy(indices, m->h_idx.data(), sizeof(uint32_t) * m->h_idx.size());
     return RT_OK;
@@ -469,6 +611,9 @@ int rt_scene_add_model(rt_scene *s, rt_model *m, const float transform3x4[12])
     memcpy(in.xform, transform3x4, sizeof in.xform);
     m->refs++;
     s->inst.push_back(in);
+    bool held = false;
+    for (rt_scene *o : m->scenes) held = held || o == s;
+    if (!held) m->scenes.push_back(s);
     s->built = false;
     s->updatable = false;     // the TLAS no longer stands for this instance list: only rt_scene_build brings the scene back
     s->generation++;
@@ -511,14 +656,29 @@ int rt_scene_update(rt_scene *s)
         rt_set_error("rt_scene_update: the scene has not been built since its last rt_scene_add_model (an update builds no BLAS: rt_scene_build)");
         return RT_ERR_STATE;
     }
-    if (s->pending.empty()) return RT_OK;             // nothing to apply: nothing launched, the generation stays
+    std::vector<uint32_t> changed;                    // instances whose model's vertices were set since their records were written
+    rt_scene_changed_instances(s, &changed);
+    if (s->pending.empty() && changed.empty()) return RT_OK;      // nothing to apply: nothing launched, the generation stays
     rt_context *ctx = s->ctx;
     RT_TRY(use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
     s->generation++;          // pipelines drop what they cached from the old geometry: shadow-cache occluders, per-pixel entries, the free sphere, the primary-mode samples
-    RT_TRY(rt_update_tlas(ctx, s));                   // (a failure leaves the scene stale and the transforms pending)
+    ScopedEvent e0;
+    HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventRecord(e0.e, ctx->stream));
+    if (!changed.empty()) {
+        // a changed model whose BLAS is older than its vertices: rebuilt by the build's own steps into the model's own buffers (one that
+        // another scene's update or build has rebuilt already is built: rt_build_blas returns at once)
+        for (uint32_t i : changed) RT_TRY(rt_build_blas(ctx, s->inst[i].model));
+        RT_TRY(rt_update_model_records(ctx, s, changed));
+        s->is_pending.resize(s->inst.size(), 0);
+        for (uint32_t i : changed)            // ... and take their world boxes over the new vertices, with the transforms they have
+            if (!s->is_pending[i]) { s->is_pending[i] = 1; s->pending.push_back(i); }
+    }
+    RT_TRY(rt_update_tlas(ctx, s, e0.e));             // (a failure leaves the scene stale, the transforms and the models pending)
     for (uint32_t i : s->pending) s->is_pending[i] = 0;
     s->pending.clear();
+    for (uint32_t i : changed) s->seen_geom[i] = s->inst[i].model->geom_gen;
     s->built = true;
     return RT_OK;
 }
@@ -561,6 +721,8 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     s->updatable = true;
     s->pending.clear();       // the build has read every stored transform
     s->is_pending.assign(s->inst.size(), 0);
+    s->seen_geom.resize(s->inst.size());               // ... and every model's vertices
+    for (size_t i = 0; i < s->inst.size(); i++) s->seen_geom[i] = s->inst[i].model->geom_gen;
     return RT_OK;
 }
 

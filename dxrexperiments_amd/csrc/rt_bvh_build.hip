@@ -982,6 +982,60 @@ __global__ void k_update_leaf_boxes(const InstanceRec *__restrict__ inst, Box6 *
     for (int c = 0; c < 3; c++) { boxes[i].lo[c] = inst[i].wlo[c]; boxes[i].hi[c] = inst[i].whi[c]; }
 }
 
+// A deformed model's BLAS has been rebuilt (rt_scene_update): what an instance record says about its model, as rt_build_tlas writes it on the
+// host.  DevBuf::reserve may have moved any of the arrays, and n_recs and the reference buffers come and go with the shape.
+struct ModelDesc {
+    const WNode *wide;
+    const TriRec *tris;
+    const rt_bvh_node *cnodes;
+    const rt_vertex *verts;
+    const uint32_t *indices;
+    const TriRec *normals;
+    const float *rec_boxes;
+    const uint32_t *ref_off;
+    const float *ref_boxes;
+    int root_code;
+    uint32_t n_prims, n_recs;
+    float bounds[6];             // the BLAS box: the instance's row of blas_bounds
+    uint32_t pad_;
+};
+static_assert(sizeof(ModelDesc) % 8 == 0, "an array of descriptors keeps its pointers aligned");
+
+ModelDesc model_desc(const rt_model *m)
+{
+    ModelDesc d;
+    d.wide = m->blas.wide.as<WNode>();
+    d.tris = m->tris.as<TriRec>();
+    d.cnodes = m->blas.nodes.as<rt_bvh_node>();
+    d.verts = m->d_verts.as<rt_vertex>();
+    d.indices = m->d_idx.as<uint32_t>();
+    d.normals = m->normals.as<TriRec>();
+    d.rec_boxes = m->rec_boxes.p ? m->rec_boxes.as<float>() : nullptr;
+    d.ref_off = m->ref_off.p ? m->ref_off.as<uint32_t>() : nullptr;
+    d.ref_boxes = m->ref_boxes.p ? m->ref_boxes.as<float>() : nullptr;
+    d.root_code = m->blas.root_code;
+    d.n_prims = m->n_tris;
+    d.n_recs = m->n_recs;
+    memcpy(d.bounds, m->blas.bounds, sizeof d.bounds);
+    d.pad_ = 0;
+    return d;
+}
+
+// one lane per affected instance: who = (instance, descriptor)
+__global__ void k_update_model_fields(InstanceRec *__restrict__ inst, float *__restrict__ blas_bounds, const ModelDesc *__restrict__ desc,
+                                      const uint2 *__restrict__ who, uint32_t n)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t i = who[k].x;
+    const ModelDesc &d = desc[who[k].y];
+    InstanceRec &r = inst[i];
+    r.wide = d.wide; r.tris = d.tris; r.cnodes = d.cnodes; r.verts = d.verts; r.indices = d.indices; r.normals = d.normals;
+    r.rec_boxes = d.rec_boxes; r.ref_off = d.ref_off; r.ref_boxes = d.ref_boxes;
+    r.root_code = d.root_code; r.n_prims = d.n_prims; r.n_recs = d.n_recs;
+    for (int c = 0; c < 6; c++) blas_bounds[6u * (size_t)i + c] = d.bounds[c];
+}
+
 // (+ the pending indices and transforms, their encoded boxes, the work list and its count)
 struct UpdateTemps : LbvhTemps {
     uint32_t *pend_idx;
@@ -1002,7 +1056,45 @@ void carve_update(Carver &c, uint32_t n, size_t n_pending, size_t max_items, Upd
 
 }  // namespace
 
-int rt_update_tlas(rt_context *ctx, rt_scene *s)
+int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &changed)
+{
+    hipStream_t st = ctx->stream;
+    std::vector<const rt_model *> models;              // the distinct models of `changed` (a handful: a linear search)
+    std::vector<uint2> who(changed.size());
+    for (size_t k = 0; k < changed.size(); k++) {
+        const rt_model *m = s->inst[changed[k]].model;
+        size_t at = 0;
+        while (at < models.size() && models[at] != m) at++;
+        if (at == models.size()) models.push_back(m);
+        who[k] = make_uint2(changed[k], (uint32_t)at);
+    }
+    std::vector<ModelDesc> desc(models.size());
+    for (size_t k = 0; k < models.size(); k++) desc[k] = model_desc(models[k]);
+    // the table and the list go up through a slice of the build arena: the update that follows carves the arena again, behind this kernel on
+    // the stream
+    const size_t desc_bytes = (sizeof(ModelDesc) * desc.size() + 255) & ~(size_t)255;
+    RT_TRY(ctx->build_arena.reserve(desc_bytes + sizeof(uint2) * who.size()));
+    ModelDesc *d_desc = ctx->build_arena.as<ModelDesc>();
+    uint2 *d_who = (uint2 *)(ctx->build_arena.as<char>() + desc_bytes);
+    HIP_TRY(hipMemcpyAsync(d_desc, desc.data(), sizeof(ModelDesc) * desc.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_who, who.data(), sizeof(uint2) * who.size(), hipMemcpyHostToDevice, st));
+    k_update_model_fields<<<grid_for(who.size(), UPD_BLOCK), UPD_BLOCK, 0, st>>>(s->d_inst.as<InstanceRec>(), s->blas_bounds.as<float>(), d_desc, d_who,
+                                                                                (uint32_t)who.size());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));                 // (the host vectors go out of scope; a reserve of the arena by the update frees this slice)
+    for (size_t k = 0; k < changed.size(); k++) {      // the host mirrors follow
+        const uint32_t i = changed[k];
+        const ModelDesc &d = desc[who[k].y];
+        InstanceRec &r = s->h_inst[i];
+        r.wide = d.wide; r.tris = d.tris; r.cnodes = d.cnodes; r.verts = d.verts; r.indices = d.indices; r.normals = d.normals;
+        r.rec_boxes = d.rec_boxes; r.ref_off = d.ref_off; r.ref_boxes = d.ref_boxes;
+        r.root_code = d.root_code; r.n_prims = d.n_prims; r.n_recs = d.n_recs;
+        memcpy(&s->h_blas_bounds[6 * (size_t)i], d.bounds, sizeof d.bounds);
+    }
+    return RT_OK;
+}
+
+int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started)
 {
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)s->inst.size();
@@ -1022,7 +1114,7 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s)
     ScopedEvent e0, e1;
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventCreate(&e1.e));
-    HIP_TRY(hipEventRecord(e0.e, st));
+    if (!started) HIP_TRY(hipEventRecord(e0.e, st));
     HIP_TRY(hipMemcpyAsync(t.pend_idx, s->pending.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
@@ -1042,13 +1134,17 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s)
     // the final join: it brings back the rewritten records' heads with the TLAS' depth and bounds
     HIP_TRY(hipMemcpyAsync(back.data(), s->update_back.p, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     RT_TRY(lbvh_collect(ctx, s->tlas));
-    HIP_TRY(hipEventElapsedTime(&s->update_ms, e0.e, e1.e));
+    HIP_TRY(hipEventElapsedTime(&s->update_ms, started ? started : e0.e, e1.e));
     for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[s->pending[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
+    // taken again over all models: a deformation changes depths and can create or remove split references
     uint32_t deepest = 0, canon = s->tlas.max_depth;
+    s->has_refs = false;
     for (uint32_t i = 0; i < n; i++) {
-        const BvhDev &b = s->inst[i].model->blas;
+        const rt_model *m = s->inst[i].model;
+        const BvhDev &b = m->blas;
         deepest = b.fast_depth > deepest ? b.fast_depth : deepest;
         canon = b.max_depth > canon ? b.max_depth : canon;
+        s->has_refs = s->has_refs || m->ref_off.p != nullptr;
     }
     s->two_level = !(n == 1 && (s->h_inst[0].flags & RT_INST_IDENTITY));
     s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;

@@ -314,6 +314,12 @@ struct rt_model {
     DevBuf ref_off, ref_boxes;   // uint32[n_tris + 1], float[6 refs]: the same boxes by primitive (canonical walk, LBVH layout)
     BvhDev blas;
     bool built = false;
+    // rt_model_set_vertices / _set_positions / _recompute_normals: a mesh that changes shape (never its counts or its index list)
+    uint64_t geom_gen = 0;       // bumped by every successful set: a scene records it per instance at build / update (rt_scene::seen_geom)
+    bool h_verts_stale = false;  // d_verts was written from device memory: rt_model_read_geometry downloads before it answers
+    std::vector<struct rt_scene *> scenes;   // the scenes that hold the model in some instance (each once): a set leaves the built ones stale
+    DevBuf adj_off, adj_tris;    // vertex -> triangle CSR of the index list (rt_adjacency.h), made by the first rt_model_recompute_normals
+    bool adj_ready = false;
     ~rt_model();                 // (rt_api.hip) selects the device before the buffers go
 };
 
@@ -341,6 +347,8 @@ struct rt_scene {
     std::vector<uint8_t> is_pending;     //   there are any the scene is STALE: built == false, nothing traces or reads it
     std::vector<float> h_blas_bounds;    // float[6 n]: the BLAS box of every instance's model, as uploaded to ...
     DevBuf blas_bounds;          // ... the box an instance set (back) to the identity takes (written by every build)
+    std::vector<uint64_t> seen_geom;     // per instance: its model's geom_gen when the records were last written (build / update); another
+                                         //   value now: the model's vertices changed since, the scene is STALE as with a pending transform
     DevBuf update_back;          // the first 20 words (inv, world box, flags) of the records an update rewrote, on their way to h_inst
     float update_ms = 0.0f;
     SceneDev dev() const
@@ -365,13 +373,35 @@ int rt_build_blas(rt_context *ctx, rt_model *m);
 int rt_build_tlas(rt_context *ctx, rt_scene *s);
 // after rt_build_tlas: the per-instance BLAS boxes rt_update_tlas reads on the device
 int rt_upload_blas_bounds(rt_context *ctx, rt_scene *s);
-// applies s->pending to the instance records, their world boxes and the TLAS, on the device
-int rt_update_tlas(rt_context *ctx, rt_scene *s);
+// applies s->pending to the instance records, their world boxes and the TLAS, on the device; `started`: an event the caller has recorded,
+// from which update_ms counts (nullptr: from here)
+int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started = nullptr);
+// the model fields of the records of `changed` (instances whose model was rebuilt) and their rows of blas_bounds, on the device; h_inst follows
+int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &changed);
 
-// A scene whose transforms were set and not applied yet: says so (the message names them) and returns true.
+// instances of an updatable scene whose model's vertices were set since the scene last wrote their records
+static inline size_t rt_scene_changed_instances(const rt_scene *s, std::vector<uint32_t> *which = nullptr)
+{
+    size_t n = 0;
+    if (!s->updatable || s->seen_geom.size() != s->inst.size()) return 0;
+    for (size_t i = 0; i < s->inst.size(); i++)
+        if (s->inst[i].model->geom_gen != s->seen_geom[i]) { n++; if (which) which->push_back((uint32_t)i); }
+    return n;
+}
+
+// A scene whose transforms or whose models' vertices were set and not applied yet: says so (the message names them) and returns true.
 static inline bool rt_scene_stale_error(const rt_scene *s, const char *who)
 {
-    if (!s || s->built || s->pending.empty()) return false;
+    if (!s || s->built) return false;
+    const size_t changed = rt_scene_changed_instances(s);
+    if (changed) {
+        char also[96] = "";
+        if (!s->pending.empty()) snprintf(also, sizeof also, " and %zu instance transform%s", s->pending.size(), s->pending.size() == 1 ? "" : "s");
+        rt_set_error("%s: new vertices of the model%s of %zu instance%s%s pending (rt_model_set_vertices / _set_positions / _recompute_normals): "
+                     "rt_scene_update or rt_scene_build applies them", who, changed == 1 ? "" : "s", changed, changed == 1 ? "" : "s", also);
+        return true;
+    }
+    if (s->pending.empty()) return false;
     rt_set_error("%s: %zu instance transform%s pending (rt_scene_set_instance_transform): rt_scene_update or rt_scene_build applies them", who,
                  s->pending.size(), s->pending.size() == 1 ? "" : "s");
     return true;

@@ -140,6 +140,21 @@ namespace DXRFramework
         uint32_t getNumVertices() const { uint32_t v = 0, t = 0; ThrowIfFailed(rt_model_get_counts(mHandle, &v, &t)); return v; }
         uint32_t getNumTriangles() const { uint32_t v = 0, t = 0; ThrowIfFailed(rt_model_get_counts(mHandle, &v, &t)); return t; }
 
+        // EXTENSIONS (the reference's RtModel never changes once created; its generators' `allowUpdate` / `updateOnly` path,
+        // Helpers/BottomLevelASGenerator.h:136-176, is never taken): new vertices for a mesh whose counts and index list stay.  setVertices:
+        // whole records; setPositions: count x 3 floats, normals kept; deviceMemory: the source is device memory (copied device to device).
+        // recomputeNormals: every normal from the current positions, on the device.  Every built scene that holds the model renders nothing
+        // until its update() (which rebuilds this model's BLAS) or build().
+        void setVertices(const rt_vertex *verts, uint32_t count, uint32_t first = 0, bool deviceMemory = false)
+        {
+            ThrowIfFailed(rt_model_set_vertices(mHandle, first, count, verts, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
+        }
+        void setPositions(const float *xyz, uint32_t count, uint32_t first = 0, bool deviceMemory = false)
+        {
+            ThrowIfFailed(rt_model_set_positions(mHandle, first, count, xyz, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
+        }
+        void recomputeNormals() { ThrowIfFailed(rt_model_recompute_normals(mHandle)); }
+
     private:
         RtModel(RtContext::SharedPtr ctx, rt_model *h) : mContext(ctx), mHandle(h) {}
         RtContext::SharedPtr mContext;
@@ -169,7 +184,8 @@ namespace DXRFramework
         rt_scene *getHandle(RtContext::SharedPtr context) { realize(context); return mHandle; }
         // EXTENSIONS (the reference's RtScene has neither; its generators' update path -- `updateOnly`, Helpers/TopLevelASGenerator.h:144-163 --
         // is never called).  setTransform: a new object-to-world matrix for an instance already added; on a built scene nothing renders
-        // until update() or build().  update(context): applies the transforms set since on the device (rt_scene_update); no BLAS is built.
+        // until update() or build().  update(context): applies the transforms set since on the device (rt_scene_update); no BLAS is built
+        // but those of models whose vertices were set since (RtModel::setVertices / setPositions / recomputeNormals).
         void setTransform(uint32_t index, const Matrix &transform)
         {
             if (index >= mInstances.size()) throw std::runtime_error("RtScene::setTransform: instance out of range");

@@ -149,13 +149,42 @@ int rt_scene_set_instance_transforms(rt_scene *s, uint32_t first, uint32_t count
  * instances, the TLAS -- and leaves the scene built.  Stands in for the generators' update path (`updateOnly` of
  * TopLevelASGenerator::Generate, libs/DXRFramework/Helpers/TopLevelASGenerator.h:144-163, and `allowUpdate` / `updateOnly` of
  * Helpers/BottomLevelASGenerator.h:136-176), which the reference's RtScene never calls.  The scene afterwards is, array for array, the
- * scene rt_scene_build gives for the same instance list (DESIGN.md "update == build").  It builds no BLAS: on a scene that has not been
- * built since its last rt_scene_add_model it fails (RT_ERR_STATE).  With nothing pending it returns RT_OK and changes nothing; otherwise
+ * scene rt_scene_build gives for the same instance list (DESIGN.md "update == build").  It builds no BLAS but those of models whose vertices
+ * were set (rt_model_set_vertices, below): on a scene that has not been built since its last rt_scene_add_model it fails (RT_ERR_STATE).  With nothing pending it returns RT_OK and changes nothing; otherwise
  * pipelines drop what they cached from the old geometry (shadow cache, free sphere, primary-mode samples) -- their accumulation buffers are
  * the caller's to clear (rt_pipeline_clear_output), as after a camera change. */
 int rt_scene_update(rt_scene *s);
-/* EXTENSION: milliseconds the last rt_scene_update spent on the GPU, as rt_scene_build_ms */
+/* EXTENSION: milliseconds the last rt_scene_update spent on the GPU (the BLAS rebuilds of deformed models included), as rt_scene_build_ms */
 int rt_scene_update_ms(const rt_scene *s, float *ms);
+
+/* Deforming meshes -- EXTENSIONS: the reference's RtModel is immutable once created (RtModel.h:13); its generators have the path
+ * (`allowUpdate` / `updateOnly` of libs/DXRFramework/Helpers/BottomLevelASGenerator.h:136-176), which RtModel::build never takes.
+ * rt_model_set_vertices / rt_model_set_positions overwrite vertices first .. first + count - 1 of the model's device array, on the context's
+ * stream: whole 24-byte records, or count x 3 floats of positions with the normals kept.  The vertex count and the index list never change.
+ * `mem` is RT_MEM_HOST or RT_MEM_DEVICE, as for rt_trace_batch; a device source (the output of a skinning, cloth or morph kernel) is copied
+ * device to device and nothing goes through the host.  A producer that wrote the source on ANOTHER stream is the caller's to order before the
+ * call; a context made with rt_context_create_on_stream on the producer's stream needs nothing.  Frames a deferred pipeline still holds are
+ * rendered first (they see the mesh as it was).  count == 0 returns RT_OK and changes nothing; a range beyond the model's vertices is
+ * RT_ERR_STATE; a null argument or an unknown `mem` is RT_ERR_INVALID_ARG.  rt_model_read_geometry returns the current vertices (after a
+ * device-side set: downloaded on demand).
+ * A successful set leaves the model CHANGED, and every built scene that holds it in any instance STALE, exactly as after
+ * rt_scene_set_instance_transform: rt_trace_batch, the render calls and the rt_scene_*_info / _read calls fail with RT_ERR_STATE (the message
+ * names the pending vertices) until rt_scene_update or rt_scene_build.  rt_scene_update then REBUILDS the BLAS of every changed model by the
+ * build's own steps, into the model's own buffers (once, however many scenes hold it), rewrites the model fields of its instances' records
+ * on the device, gives those instances their world boxes over the new vertices and rebuilds the TLAS; pending transforms are applied by the
+ * same call.  A BLAS is rebuilt, never refitted: after `set + update` the scene is, array for array -- every BLAS's canonical nodes, keys and
+ * parents, its production nodes and records, reference offsets and boxes, every instance record, the TLAS -- the scene rt_scene_build gives
+ * for the same instance list over fresh models created from the final vertex arrays (DESIGN.md "update == build").  A scene that was never
+ * built just reads the new vertices at its next build. */
+int rt_model_set_vertices(rt_model *m, uint32_t first, uint32_t count, const rt_vertex *verts, uint32_t mem);
+int rt_model_set_positions(rt_model *m, uint32_t first, uint32_t count, const float *xyz, uint32_t mem);   /* count x 3 floats, normals kept */
+/* EXTENSION (BottomLevelASGenerator.h:136-176 as above; for producers that write positions only): the normal of every vertex v from the
+ * current positions, on the device.  With s = (0, 0, 0): for every triangle that names v at any corner, in ascending order (one that names
+ * v more than once counts once), f = cross(p1 - p0, p2 - p0) with the corners in index order and s = s + f componentwise; with
+ * d = dot(s, s) = ((x x) + y y) + z z the normal is s * (1 / sqrt(d)) if 0 < d < inf, else (0, 0, 0).  fp32 throughout, no contraction, no
+ * atomics: the order is part of the result.  The vertex -> triangle table is built from the index list at the first call.  Marks the model
+ * changed as a setter does. */
+int rt_model_recompute_normals(rt_model *m);
 
 /* ---- raw TraceRay over a batch (HLSL TraceRay semantics, used by tests and
  *      the traversal benchmark; ProgressiveRaytracing.hlsl:34,53,
