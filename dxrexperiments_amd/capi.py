@@ -97,6 +97,9 @@ SIGNATURES = {
     "rt_scene_build_ms": (_i, [_p, C.POINTER(_f)]),
     "rt_scene_set_instance_transform": (_i, [_p, _u32, _p]),
     "rt_scene_set_instance_transforms": (_i, [_p, _u32, _u32, _p]),
+    "rt_scene_set_instance_mask": (_i, [_p, _u32, C.c_uint8]),
+    "rt_scene_set_instance_masks": (_i, [_p, _u32, _u32, _p]),
+    "rt_scene_get_instance_masks": (_i, [_p, _u32, _u32, _p]),
     "rt_scene_update": (_i, [_p]),
     "rt_scene_update_ms": (_i, [_p, C.POINTER(_f)]),
     "rt_trace_batch": (_i, [_p, _p, _p, _p, _sz, _u32, _u32, _u32, _p, _p, _p, _p, _p, _p, _p]),
@@ -466,6 +469,22 @@ class Scene:
         rows = [T.IDENTITY_3X4 if x is None else x for x in transforms]
         x = _f32(rows, (-1, 12)) if len(rows) else np.zeros((0, 12), np.float32)
         _check(lib().rt_scene_set_instance_transforms(self.h, first, x.shape[0], _ptr(x)))
+
+    def set_mask(self, i, mask):
+        """Extension: the InstanceMask byte of instance i (0xFF when added); the instance is visible to rays iff it is non-zero.  A change of
+        visibility leaves a built scene stale until update() or build()."""
+        _check(lib().rt_scene_set_instance_mask(self.h, i, int(mask) & 0xFF))
+
+    def set_masks(self, first, masks):
+        """... for instances first .. first + len(masks) - 1"""
+        m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+        _check(lib().rt_scene_set_instance_masks(self.h, first, m.shape[0], _ptr(m)))
+
+    def masks(self):
+        """the stored mask of every instance, uint8[num_instances]"""
+        m = np.empty(self.num_instances, np.uint8)
+        _check(lib().rt_scene_get_instance_masks(self.h, 0, m.shape[0], _ptr(m)))
+        return m
 
     def update(self):
         """Extension: applies the pending transforms on the device (instance records, world boxes, TLAS); the scene is then what build() gives"""

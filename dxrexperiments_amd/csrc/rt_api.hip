@@ -611,6 +611,7 @@ int rt_scene_add_model(rt_scene *s, rt_model *m, const float transform3x4[12])
     memcpy(in.xform, transform3x4, sizeof in.xform);
     m->refs++;
     s->inst.push_back(in);
+    s->masks.push_back(0xFF);  // InstanceMask of the reference's descriptors (TopLevelASGenerator.cpp:361)
     bool held = false;
     for (rt_scene *o : m->scenes) held = held || o == s;
     if (!held) m->scenes.push_back(s);
@@ -649,6 +650,51 @@ int rt_scene_set_instance_transform(rt_scene *s, uint32_t instance, const float 
     return rt_scene_set_instance_transforms(s, instance, 1, transform3x4);
 }
 
+// EXTENSION: the InstanceMask member of the instance descriptors (TopLevelASGenerator.cpp:344-362), which the reference fills with 0xFF, under the
+// inclusion mask 0xFF of its every TraceRay (ProgressiveRaytracing.hlsl:34,53, RaytracingCommon.hlsli:94, RealtimeRaytracing.hlsl:42,61)
+int rt_scene_set_instance_masks(rt_scene *s, uint32_t first, uint32_t count, const uint8_t *masks)
+{
+    RT_REQUIRE(s && (masks || count == 0), "null argument");
+    const size_t n = s->inst.size();
+    if (first > n || count > n - first) {
+        rt_set_error("rt_scene_set_instance_masks: instances %u .. %llu out of range: the scene has %zu", first, (unsigned long long)first + count, n);
+        return RT_ERR_STATE;
+    }
+    if (count == 0) return RT_OK;
+    RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
+    bool visibility = false;
+    for (uint32_t k = 0; k < count; k++) {
+        visibility = visibility || ((s->masks[first + k] != 0) != (masks[k] != 0));
+        s->masks[first + k] = masks[k];
+    }
+    if (!s->updatable || !visibility) return RT_OK;   // not built: the next build reads the stored masks; the same visibility: only the bytes change
+    s->masks_dirty = true;
+    s->built = false;         // stale until rt_scene_update or rt_scene_build, as with a pending transform
+    return RT_OK;
+}
+
+int rt_scene_set_instance_mask(rt_scene *s, uint32_t instance, uint8_t mask)
+{
+    RT_REQUIRE(s, "null scene");
+    if (instance >= s->inst.size()) {
+        rt_set_error("rt_scene_set_instance_mask: instance %u out of range: the scene has %zu", instance, s->inst.size());
+        return RT_ERR_STATE;
+    }
+    return rt_scene_set_instance_masks(s, instance, 1, &mask);
+}
+
+int rt_scene_get_instance_masks(const rt_scene *s, uint32_t first, uint32_t count, uint8_t *masks)
+{
+    RT_REQUIRE(s && (masks || count == 0), "null argument");
+    const size_t n = s->inst.size();
+    if (first > n || count > n - first) {
+        rt_set_error("rt_scene_get_instance_masks: instances %u .. %llu out of range: the scene has %zu", first, (unsigned long long)first + count, n);
+        return RT_ERR_STATE;
+    }
+    if (count) memcpy(masks, s->masks.data() + first, count);
+    return RT_OK;
+}
+
 int rt_scene_update(rt_scene *s)
 {
     RT_REQUIRE(s, "null scene");
@@ -658,10 +704,13 @@ int rt_scene_update(rt_scene *s)
     }
     std::vector<uint32_t> changed;                    // instances whose model's vertices were set since their records were written
     rt_scene_changed_instances(s, &changed);
-    if (s->pending.empty() && changed.empty()) return RT_OK;      // nothing to apply: nothing launched, the generation stays
+    if (s->pending.empty() && changed.empty() && !s->masks_dirty) return RT_OK;      // nothing to apply: nothing launched, the generation stays
     rt_context *ctx = s->ctx;
     RT_TRY(use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
+    // pending masks: the visible sub-list goes up if it differs from the one the TLAS stands for (no visible instance: refused here, with every
+    // pending thing kept -- showing one and updating again succeeds)
+    if (s->masks_dirty) RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_update", false));
     s->generation++;          // pipelines drop what they cached from the old geometry: shadow-cache occluders, per-pixel entries, the free sphere, the primary-mode samples
     ScopedEvent e0;
     HIP_TRY(hipEventCreate(&e0.e));
@@ -679,6 +728,7 @@ int rt_scene_update(rt_scene *s)
     for (uint32_t i : s->pending) s->is_pending[i] = 0;
     s->pending.clear();
     for (uint32_t i : changed) s->seen_geom[i] = s->inst[i].model->geom_gen;
+    s->masks_dirty = false;
     s->built = true;
     return RT_OK;
 }
@@ -705,6 +755,7 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     rt_context *ctx = s->ctx;
     RT_TRY(use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
+    RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_build", true));     // (no visible instance: refused as a scene without instances is)
     ScopedEvent e0, e1;
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventCreate(&e1.e));
@@ -719,7 +770,8 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     HIP_TRY(hipEventElapsedTime(&s->build_ms, e0.e, e1.e));
     s->built = true;
     s->updatable = true;
-    s->pending.clear();       // the build has read every stored transform
+    s->pending.clear();       // the build has read every stored transform and mask
+    s->masks_dirty = false;
     s->is_pending.assign(s->inst.size(), 0);
     s->seen_geom.resize(s->inst.size());               // ... and every model's vertices
     for (size_t i = 0; i < s->inst.size(); i++) s->seen_geom[i] = s->inst[i].model->geom_gen;

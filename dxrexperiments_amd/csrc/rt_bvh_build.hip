@@ -770,6 +770,78 @@ __global__ void k_instance_boxes_finish(InstanceRec *__restrict__ inst, const ui
     for (int c = 0; c < 3; c++) { boxes[i].lo[c] = r.wlo[c]; boxes[i].hi[c] = r.whi[c]; }
 }
 
+// ---- instance masks (rt_scene_set_instance_mask): the TLAS over the visible sub-list ----
+//
+// Stands in for the InstanceMask member of the instance descriptors (libs/DXRFramework/Helpers/TopLevelASGenerator.cpp:344-362, always 0xFF
+// there) under the inclusion mask 0xFF of every TraceRay of the reference.  `vis` holds the visible instances' indices in ascending order;
+// the LBVH is built over vis.size() leaves, and wherever it names the j-th of them the TLAS names vis[j].
+
+namespace {
+
+constexpr unsigned UPD_BLOCK = 256;
+
+// the world box of every visible instance, as it stands in its record -> the TLAS builder's leaf boxes (k_update_leaf_boxes / the tail of
+// k_instance_boxes_finish when something is hidden).  Read from the RECORDS, which nobody writes here: `boxes` may still hold the full list's
+__global__ void __launch_bounds__(UPD_BLOCK) k_visible_leaf_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ vis, uint32_t n_vis,
+                                                                 Box6 *__restrict__ boxes)
+{
+    const uint32_t j = blockIdx.x * UPD_BLOCK + threadIdx.x;
+    if (j >= n_vis) return;
+    const InstanceRec &r = inst[vis[j]];
+    for (int c = 0; c < 3; c++) { boxes[j].lo[c] = r.wlo[c]; boxes[j].hi[c] = r.whi[c]; }
+}
+
+// sub-list position -> instance index, in the canonical leaves' `left` and the low words of the sorted keys (vis is increasing: the keys stay
+// ascending).  k_lbvh_to_tree takes a TLAS leaf's code from `left`, so the four-wide layout comes out mapped
+__global__ void __launch_bounds__(UPD_BLOCK) k_map_visible(rt_bvh_node *__restrict__ nodes, uint64_t *__restrict__ keys, const uint32_t *__restrict__ vis,
+                                                          uint32_t n_vis)
+{
+    const uint32_t k = blockIdx.x * UPD_BLOCK + threadIdx.x;
+    if (k >= n_vis) return;
+    const uint64_t key = keys[k];
+    const uint32_t i = vis[(uint32_t)(key & 0xFFFFFFFFull)];
+    keys[k] = (key & 0xFFFFFFFF00000000ull) | i;
+    nodes[n_vis - 1 + k].left = i;
+}
+
+int map_visible_leaves(rt_context *ctx, rt_scene *s)
+{
+    const uint32_t nv = s->n_vis;
+    k_map_visible<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, ctx->stream>>>(s->tlas.nodes.as<rt_bvh_node>(), s->tlas.keys.as<uint64_t>(), s->d_vis.as<uint32_t>(), nv);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// room for the TLAS of all n instances, whatever part is visible at the build: an update that shows instances again allocates nothing
+int reserve_tlas_for(BvhDev &bv, uint32_t n)
+{
+    RT_TRY(bv.nodes.reserve(sizeof(rt_bvh_node) * (2 * (size_t)n - 1)));
+    RT_TRY(bv.keys.reserve(sizeof(uint64_t) * n));
+    RT_TRY(bv.parents.reserve(sizeof(uint32_t) * (2 * (size_t)n - 1)));
+    RT_TRY(bv.ranges.reserve(sizeof(uint2) * (n > 1 ? n - 1 : 1)));
+    RT_TRY(bv.wide.reserve(sizeof(WNode) * (size_t)(n > 1 ? n - 1 : 1)));
+    return RT_OK;
+}
+
+}  // namespace
+
+int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool force)
+{
+    const uint32_t n = (uint32_t)s->inst.size();
+    std::vector<uint32_t> vis;
+    vis.reserve(n);
+    for (uint32_t i = 0; i < n; i++)
+        if (s->masks[i]) vis.push_back(i);
+    if (vis.empty()) { rt_set_error("%s: no instance is visible: every instance mask is 0 (rt_scene_set_instance_mask)", who); return RT_ERR_STATE; }
+    if (!force && vis == s->vis) return RT_OK;
+    s->vis.swap(vis);                                  // (a member: alive whenever the copy runs)
+    s->n_vis = (uint32_t)s->vis.size();
+    if (s->n_vis == n) return RT_OK;                   // nothing hidden: nobody reads the list
+    RT_TRY(s->d_vis.reserve(sizeof(uint32_t) * (size_t)n));       // (for all of them at once: never grows again)
+    HIP_TRY(hipMemcpyAsync(s->d_vis.p, s->vis.data(), sizeof(uint32_t) * s->n_vis, hipMemcpyHostToDevice, ctx->stream));
+    return RT_OK;
+}
+
 int rt_build_tlas(rt_context *ctx, rt_scene *s)
 {
     hipStream_t st = ctx->stream;
@@ -836,12 +908,20 @@ int rt_build_tlas(rt_context *ctx, rt_scene *s)
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t i = 0; i < n; i++)
         for (int c = 0; c < 3; c++) { s->h_inst[i].wlo[c] = hb[i].lo[c]; s->h_inst[i].whi[c] = hb[i].hi[c]; }
+    // some instance hidden (rt_scene_set_instance_mask): the records above are the full list's, the TLAS is the one of the visible sub-list
+    const uint32_t nv = s->n_vis;
+    if (nv < n) {
+        RT_TRY(reserve_tlas_for(s->tlas, n));
+        k_visible_leaf_boxes<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, st>>>(s->d_inst.as<InstanceRec>(), s->d_vis.as<uint32_t>(), nv, t.boxes);
+    }
     k_init_bounds<<<1, 64, 0, st>>>(t.enc);
-    k_box_bounds<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, n, t.enc);
+    k_box_bounds<<<grid_for(nv, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, nv, t.enc);
     k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
-    RT_TRY(lbvh_from_boxes(ctx, s->tlas, n, t));
+    RT_TRY(lbvh_from_boxes(ctx, s->tlas, nv, t));
+    if (nv < n) RT_TRY(map_visible_leaves(ctx, s));
     // the TLAS is walked in the same four-wide layout (a single instance: the root is the leaf of instance 0)
     RT_TRY(rt_build_wide_from_lbvh(ctx, s->tlas, true, 1));
+    if (nv < n && nv == 1) s->tlas.root_code = ~(int)s->vis[0];       // (the one visible instance's own index)
     RT_TRY(lbvh_collect(ctx, s->tlas));
     // a step leaves at most three siblings behind; two-level walks add the TLAS path and the sentinel that marks the
     // bottom of a BLAS walk
@@ -879,7 +959,6 @@ int rt_upload_blas_bounds(rt_context *ctx, rt_scene *s)
 
 namespace {
 
-constexpr unsigned UPD_BLOCK = 256;
 constexpr unsigned UPD_BACK_WORDS = 20;      // inv[12], wlo[3], root_code, whi[3], flags: the head of an InstanceRec
 static_assert(offsetof(InstanceRec, flags) == 4 * (UPD_BACK_WORDS - 1), "the read-back of an update is the head of the record");
 
@@ -1115,24 +1194,33 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started)
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventCreate(&e1.e));
     if (!started) HIP_TRY(hipEventRecord(e0.e, st));
-    HIP_TRY(hipMemcpyAsync(t.pend_idx, s->pending.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
     InstanceRec *inst = s->d_inst.as<InstanceRec>();
-    k_update_records<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->blas_bounds.as<float>(), t.pend_idx, t.pend_xf, (uint32_t)np, t.pend_enc,
-                                                                   t.items, t.n_items, (uint32_t)max_items);
-    if (max_items) k_update_boxes<<<(uint32_t)max_items, BOUNDS_BLOCK, 0, st>>>(inst, t.pend_idx, t.pend_xf, t.items, t.n_items, t.pend_enc);
-    k_update_apply<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.pend_idx, (uint32_t)np, t.pend_enc, s->update_back.as<uint32_t>());
-    k_update_leaf_boxes<<<grid_for(n, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.boxes, n);
-    // from here on: rt_build_tlas' own steps, into the buffers the scene has (the same sizes: nothing is allocated)
+    if (np) {                                          // (none: an update of masks alone)
+        HIP_TRY(hipMemcpyAsync(t.pend_idx, s->pending.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
+        k_update_records<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->blas_bounds.as<float>(), t.pend_idx, t.pend_xf, (uint32_t)np, t.pend_enc,
+                                                                       t.items, t.n_items, (uint32_t)max_items);
+        if (max_items) k_update_boxes<<<(uint32_t)max_items, BOUNDS_BLOCK, 0, st>>>(inst, t.pend_idx, t.pend_xf, t.items, t.n_items, t.pend_enc);
+        k_update_apply<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.pend_idx, (uint32_t)np, t.pend_enc, s->update_back.as<uint32_t>());
+    }
+    // the records are the full list's, hidden instances' included; the leaves are the visible ones' (all n when nothing is hidden)
+    const uint32_t nv = s->n_vis;
+    if (nv < n)
+        k_visible_leaf_boxes<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->d_vis.as<uint32_t>(), nv, t.boxes);
+    else
+        k_update_leaf_boxes<<<grid_for(n, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.boxes, n);
+    // from here on: rt_build_tlas' own steps, into the buffers the scene has (the same sizes or smaller: nothing is allocated)
     k_init_bounds<<<1, 64, 0, st>>>(t.enc);
-    k_box_bounds<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, n, t.enc);
+    k_box_bounds<<<grid_for(nv, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, nv, t.enc);
     k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
-    RT_TRY(lbvh_from_boxes(ctx, s->tlas, n, t));
+    RT_TRY(lbvh_from_boxes(ctx, s->tlas, nv, t));
+    if (nv < n) RT_TRY(map_visible_leaves(ctx, s));
     RT_TRY(rt_build_wide_from_lbvh(ctx, s->tlas, true, 1));
+    if (nv < n && nv == 1) s->tlas.root_code = ~(int)s->vis[0];
     HIP_TRY(hipEventRecord(e1.e, st));
     // the final join: it brings back the rewritten records' heads with the TLAS' depth and bounds
-    HIP_TRY(hipMemcpyAsync(back.data(), s->update_back.p, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (np) HIP_TRY(hipMemcpyAsync(back.data(), s->update_back.p, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     RT_TRY(lbvh_collect(ctx, s->tlas));
     HIP_TRY(hipEventElapsedTime(&s->update_ms, started ? started : e0.e, e1.e));
     for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[s->pending[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
@@ -1150,7 +1238,7 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started)
     s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;
     if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); return RT_ERR_UNSUPPORTED; }
     if (ctx->verbose)
-        fprintf(stderr, "[dxr_amd] TLAS update: %zu of %u instances, depth %u; stack need %u; %s walk\n", np, n, s->tlas.max_depth, s->stack_need,
-                s->two_level ? "two-level" : "single-level");
+        fprintf(stderr, "[dxr_amd] TLAS update: %zu of %u instances, %u visible, depth %u; stack need %u; %s walk\n", np, n, nv, s->tlas.max_depth,
+                s->stack_need, s->two_level ? "two-level" : "single-level");
     return RT_OK;
 }

@@ -351,6 +351,14 @@ struct rt_scene {
                                          //   value now: the model's vertices changed since, the scene is STALE as with a pending transform
     DevBuf update_back;          // the first 20 words (inv, world box, flags) of the records an update rewrote, on their way to h_inst
     float update_ms = 0.0f;
+    // rt_scene_set_instance_mask(s): the InstanceMask byte of every instance (0xFF from rt_scene_add_model); every ray carries the reference's
+    // inclusion mask 0xFF, so an instance is VISIBLE iff its byte is non-zero.  Masks never touch a record: the TLAS is the one of the visible
+    // sub-list, whose leaves name the instances' own indices
+    std::vector<uint8_t> masks;          // per instance, as given
+    bool masks_dirty = false;            // a setter has changed some instance's visibility on an updatable scene: STALE, as with a pending transform
+    std::vector<uint32_t> vis;           // the visible instances, ascending, as the TLAS stands for them (written by a build / update)
+    DevBuf d_vis;                        // ... on the device: uploaded only by a build or update at which some visibility changed
+    uint32_t n_vis = 0;                  // how many; == inst.size(): nothing hidden, d_vis is not read and the builders launch what they always did
     SceneDev dev() const
     {
         SceneDev s;
@@ -373,6 +381,9 @@ int rt_build_blas(rt_context *ctx, rt_model *m);
 int rt_build_tlas(rt_context *ctx, rt_scene *s);
 // after rt_build_tlas: the per-instance BLAS boxes rt_update_tlas reads on the device
 int rt_upload_blas_bounds(rt_context *ctx, rt_scene *s);
+// the visible sub-list from s->masks into s->vis / d_vis / n_vis, uploaded if it differs from the one the scene has (or `force`: a build,
+// whose TLAS buffers may be new); RT_ERR_STATE, and nothing changed, if no instance is visible
+int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool force);
 // applies s->pending to the instance records, their world boxes and the TLAS, on the device; `started`: an event the caller has recorded,
 // from which update_ms counts (nullptr: from here)
 int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started = nullptr);
@@ -389,21 +400,27 @@ static inline size_t rt_scene_changed_instances(const rt_scene *s, std::vector<u
     return n;
 }
 
-// A scene whose transforms or whose models' vertices were set and not applied yet: says so (the message names them) and returns true.
+// A scene whose transforms, instance masks or models' vertices were set and not applied yet: says so (the message names them) and returns true.
 static inline bool rt_scene_stale_error(const rt_scene *s, const char *who)
 {
     if (!s || s->built) return false;
     const size_t changed = rt_scene_changed_instances(s);
+    const char *masks = s->updatable && s->masks_dirty ? " and instance masks" : "";
     if (changed) {
-        char also[96] = "";
-        if (!s->pending.empty()) snprintf(also, sizeof also, " and %zu instance transform%s", s->pending.size(), s->pending.size() == 1 ? "" : "s");
+        char also[128] = "";
+        if (!s->pending.empty()) snprintf(also, sizeof also, " and %zu instance transform%s%s", s->pending.size(), s->pending.size() == 1 ? "" : "s", masks);
+        else snprintf(also, sizeof also, "%s", masks);
         rt_set_error("%s: new vertices of the model%s of %zu instance%s%s pending (rt_model_set_vertices / _set_positions / _recompute_normals): "
                      "rt_scene_update or rt_scene_build applies them", who, changed == 1 ? "" : "s", changed, changed == 1 ? "" : "s", also);
         return true;
     }
-    if (s->pending.empty()) return false;
-    rt_set_error("%s: %zu instance transform%s pending (rt_scene_set_instance_transform): rt_scene_update or rt_scene_build applies them", who,
-                 s->pending.size(), s->pending.size() == 1 ? "" : "s");
+    if (s->pending.empty()) {
+        if (!masks[0]) return false;
+        rt_set_error("%s: instance masks pending (rt_scene_set_instance_mask): rt_scene_update or rt_scene_build applies them", who);
+        return true;
+    }
+    rt_set_error("%s: %zu instance transform%s%s pending (rt_scene_set_instance_transform): rt_scene_update or rt_scene_build applies them", who,
+                 s->pending.size(), s->pending.size() == 1 ? "" : "s", masks);
     return true;
 }
 

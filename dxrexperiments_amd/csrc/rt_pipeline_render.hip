@@ -393,6 +393,7 @@ int flush_pending_now(rt_pipeline *p)
 int count_replay(rt_pipeline *p, const char *who, int (*launch)(rt_pipeline *, unsigned long long *), unsigned long long *h, size_t words)
 {
     RT_TRY(rt_pipeline_flush_pending(p));
+    if (p->rendered && rt_scene_stale_error(p->scene, who)) return RT_ERR_STATE;       // (transforms, masks or vertices pending: the message names them)
     if (!p->rendered || !p->scene->built || p->scene->generation != p->last_scene_gen) { rt_set_error("%s: nothing rendered since the last change of scene, materials or output", who); return RT_ERR_STATE; }
     HIP_TRY(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;

@@ -171,7 +171,7 @@ namespace DXRFramework
         static SharedPtr create() { return SharedPtr(new RtScene()); }
         ~RtScene() { if (mHandle) rt_scene_destroy(mHandle); }
 
-        void addModel(RtModel::SharedPtr model, const Matrix &transform) { mInstances.push_back({model, transform}); }
+        void addModel(RtModel::SharedPtr model, const Matrix &transform) { mInstances.push_back({model, transform, 0xFF}); }
         RtModel::SharedPtr getModel(uint32_t index) const { return mInstances[index].model; }
         uint32_t getNumInstances() const { return static_cast<uint32_t>(mInstances.size()); }
 
@@ -196,6 +196,20 @@ namespace DXRFramework
                 ThrowIfFailed(rt_scene_set_instance_transform(mHandle, index, x));
             }
         }
+        // setInstanceMask / getInstanceMask: the InstanceMask byte of the instance descriptor (Helpers/TopLevelASGenerator.cpp:344-362, 0xFF in
+        // the reference); every ray carries the inclusion mask 0xFF, so an instance is hit iff its mask is non-zero.  A pool of instances
+        // added up front is shown and hidden with it; a change of visibility is applied by update() or build(), as a transform is.
+        void setInstanceMask(uint32_t index, uint8_t mask)
+        {
+            if (index >= mInstances.size()) throw std::runtime_error("RtScene::setInstanceMask: instance out of range");
+            mInstances[index].mask = mask;
+            if (index < mRealized) ThrowIfFailed(rt_scene_set_instance_mask(mHandle, index, mask));
+        }
+        uint8_t getInstanceMask(uint32_t index) const
+        {
+            if (index >= mInstances.size()) throw std::runtime_error("RtScene::getInstanceMask: instance out of range");
+            return mInstances[index].mask;
+        }
         void update(RtContext::SharedPtr context)
         {
             realize(context);
@@ -206,7 +220,7 @@ namespace DXRFramework
 
     private:
         RtScene() = default;
-        struct Node { RtModel::SharedPtr model; Matrix transform; };
+        struct Node { RtModel::SharedPtr model; Matrix transform; uint8_t mask; };
         // ONE rt_scene handle per RtScene for its whole life (a pipeline that was given the handle by setScene keeps
         // seeing the scene the caller keeps editing, as with the reference's shared RtScene object): instances added
         // since the last call are appended to it
@@ -220,6 +234,7 @@ namespace DXRFramework
                 float x[12];
                 mInstances[mRealized].transform.toInstanceTransform(x);
                 ThrowIfFailed(rt_scene_add_model(mHandle, mInstances[mRealized].model->getHandle(), x));
+                if (mInstances[mRealized].mask != 0xFF) ThrowIfFailed(rt_scene_set_instance_mask(mHandle, (uint32_t)mRealized, mInstances[mRealized].mask));
             }
         }
         std::vector<Node> mInstances;

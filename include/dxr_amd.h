@@ -157,6 +157,34 @@ int rt_scene_update(rt_scene *s);
 /* EXTENSION: milliseconds the last rt_scene_update spent on the GPU (the BLAS rebuilds of deformed models included), as rt_scene_build_ms */
 int rt_scene_update_ms(const rt_scene *s, float *ms);
 
+/* Instance masks -- EXTENSIONS: the InstanceMask member of the instance descriptor (libs/DXRFramework/Helpers/TopLevelASGenerator.cpp:344-362),
+ * which the reference fills with the constant 0xFF (line 361) and tests against the InstanceInclusionMask 0xFF of its every TraceRay
+ * (ProgressiveRaytracing.hlsl:34,53, RaytracingCommon.hlsli:94, RealtimeRaytracing.hlsl:42,61).  Every instance has an 8-bit mask, 0xFF when
+ * rt_scene_add_model adds it; every ray of this library (the two pipelines and rt_trace_batch) carries the inclusion mask 0xFF, so an instance
+ * is VISIBLE -- considered by rays -- iff its mask is non-zero.  The byte is stored and returned as given.  With a pool of instances added up
+ * front, "add" is "show" and "remove" is "hide": indices, and with them "material i <-> instance i", stay as they are.
+ * Arguments as for rt_scene_set_instance_transforms: a null argument is RT_ERR_INVALID_ARG, a range beyond the scene's instances RT_ERR_STATE,
+ * count == 0 returns RT_OK and changes nothing; a setter with count > 0 first renders the frames a deferred pipeline still holds (they see
+ * the scene as it was).  On a scene that is not updatable (never built, or instances added since the last build) a setter only stores the
+ * masks: the next rt_scene_build reads them.  On an updatable scene a call that changes the VISIBILITY of at least one instance (zero <->
+ * non-zero) leaves the scene STALE, as a pending transform does: rt_trace_batch, the render calls and the rt_scene_*_info / _read calls fail
+ * with RT_ERR_STATE (the message names the pending masks) until rt_scene_update or rt_scene_build.  A call that changes no instance's
+ * visibility (the value a mask has; one non-zero value for another) changes the stored bytes and nothing else: the scene stays built.
+ * rt_scene_update applies pending masks together with pending transforms and changed models, in one call, with one bump of the generation;
+ * rt_scene_build honours the stored masks the same way.  Either fails with RT_ERR_STATE when it would leave NO visible instance (the message
+ * says that no instance is visible), as rt_scene_build refuses a scene without instances; the scene stays stale and everything pending is
+ * kept, so that showing one instance and updating again succeeds.
+ * What the scene then is (DESIGN.md "update == build, with masks"): the instance records and world boxes are those of the FULL list, hidden
+ * instances included (rt_scene_instance_info answers for them; they follow their transforms and their models' vertices); the TLAS -- canonical
+ * nodes, sorted keys, parents, depth, four-wide layout -- is the TLAS of a fresh build over the visible sub-list in ascending index order,
+ * except that wherever that build names the j-th instance of the sub-list this one names the instance's own index (canonical leaves' `left`,
+ * the low 32 bits of the sorted keys, the wide nodes' leaf codes ~instance, root_code when one instance is visible);
+ * rt_scene_bvh_info(-1) reports n_prims = the number of visible instances.  With every mask non-zero both calls launch what they always did. */
+int rt_scene_set_instance_mask(rt_scene *s, uint32_t instance, uint8_t mask);
+int rt_scene_set_instance_masks(rt_scene *s, uint32_t first, uint32_t count, const uint8_t *masks);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362 as above): the stored masks of instances first .. first + count - 1, pending or applied */
+int rt_scene_get_instance_masks(const rt_scene *s, uint32_t first, uint32_t count, uint8_t *masks);
+
 /* Deforming meshes -- EXTENSIONS: the reference's RtModel is immutable once created (RtModel.h:13); its generators have the path
  * (`allowUpdate` / `updateOnly` of libs/DXRFramework/Helpers/BottomLevelASGenerator.h:136-176), which RtModel::build never takes.
  * rt_model_set_vertices / rt_model_set_positions overwrite vertices first .. first + count - 1 of the model's device array, on the context's
