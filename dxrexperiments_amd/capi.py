@@ -80,6 +80,9 @@ SIGNATURES = {
     "rt_model_set_vertices": (_i, [_p, _u32, _u32, _p, _u32]),
     "rt_model_set_positions": (_i, [_p, _u32, _u32, _p, _u32]),
     "rt_model_recompute_normals": (_i, [_p]),
+    "rt_model_set_skin": (_i, [_p, _u32, _u32, _p, _p]),
+    "rt_model_get_skin": (_i, [_p, _pu, _pu]),
+    "rt_model_set_bones": (_i, [_p, _p, _u32]),
     "rt_model_retain": (_i, [_p]),
     "rt_model_destroy": (_i, [_p]),
     "rt_scene_create": (_i, [_p, _pp]),
@@ -422,6 +425,39 @@ class Model:
     def recompute_normals(self):
         """every vertex normal from the current positions, on the device (include/dxr_amd.h states the sum)"""
         _check(lib().rt_model_recompute_normals(self.h))
+
+    # Extensions: skeletal animation.  A skin (bone indices and weights per vertex over the rest pose: the vertices as they are now) and,
+    # per frame, a bone palette from which the device writes every vertex (include/dxr_amd.h states the arithmetic).
+    def set_skin(self, bone_indices, weights, n_bones):
+        """bone_indices uint32[V, K], weights float32[V, K], 1 <= K <= 8; captures the rest pose; the vertices stay as they are"""
+        nv = self.counts()[0]
+        b = np.ascontiguousarray(bone_indices, dtype=np.uint32).reshape(nv, -1)
+        w = _f32(weights, (nv, -1))
+        if b.shape != w.shape:
+            raise RtError(-1, "set_skin: %s bone indices, %s weights" % (b.shape, w.shape))
+        _check(lib().rt_model_set_skin(self.h, b.shape[1], n_bones, _ptr(b), _ptr(w)))
+
+    def clear_skin(self):
+        """removes the skin; the vertices stay what the last pose made them"""
+        _check(lib().rt_model_set_skin(self.h, 0, 0, None, None))
+
+    def skin(self):
+        """(influences per vertex, bones); (0, 0): no skin"""
+        k, n = C.c_uint32(), C.c_uint32()
+        _check(lib().rt_model_get_skin(self.h, C.byref(k), C.byref(n)))
+        return k.value, n.value
+
+    def set_bones(self, bones):
+        """the palette float32[n_bones, 12] (3x4 row-major skinning matrices) from a host array: every vertex from the rest pose"""
+        p = _f32(bones, (-1, 12))
+        n = self.skin()[1]
+        if n and p.shape[0] != n:                        # (no skin: the library says so)
+            raise RtError(-1, "set_bones: %d matrices for a skin of %d bones" % (p.shape[0], n))
+        _check(lib().rt_model_set_bones(self.h, _ptr(p), MEM_HOST))
+
+    def set_bones_device(self, ptr):
+        """... from n_bones x 12 floats in device memory, used in place"""
+        _check(lib().rt_model_set_bones(self.h, C.c_void_p(ptr), MEM_DEVICE))
 
 
 class Scene:

@@ -5,6 +5,7 @@
 #include <new>
 
 #include "rt_adjacency.h"
+#include "rt_skin.h"
 #include "rt_trace_device.h"
 
 static thread_local std::string g_last_error;
@@ -109,6 +110,61 @@ __global__ void k_vertex_normals(rt_vertex *__restrict__ verts, uint32_t n_verts
     rt_float3 out;
     out.x = n.x; out.y = n.y; out.z = n.z;
     verts[v].normal = out;
+}
+
+// ---- skeletal animation: a model's vertices from its rest pose and a bone palette (rt_model_set_bones) ----
+
+// One lane per vertex; a wave reads and writes 64 consecutive 24-byte records and, per slot, 64 consecutive indices and weights (the skin is
+// slot major: rt_skin.h).  The 12 entries of the blended matrix are weight[0] * M[bone[0]], then + weight[k] * M[bone[k]] in slot order, every
+// slot evaluated; position and normal as include/dxr_amd.h states them, no FMA.  K is a template parameter: the slot loop is unrolled and B
+// lives in registers.  LDS: the palette (n_bones <= RT_SKIN_LDS_BONES) is copied into LDS by the whole block, coalesced, and gathered from
+// there; else the lanes gather it from global memory.  The arithmetic is the same statements either way: the same bytes.
+template <int K, bool LDS>
+__global__ void __launch_bounds__(256) k_skin_vertices(rt_vertex *__restrict__ verts, const rt_vertex *__restrict__ rest, uint32_t n_verts,
+                                                       const uint16_t *__restrict__ bone, const float *__restrict__ weight,
+                                                       const float *__restrict__ palette, uint32_t n_bones)
+{
+    __shared__ float s_palette[LDS ? 12u * RT_SKIN_LDS_BONES : 1u];
+    if (LDS) {
+        for (uint32_t e = threadIdx.x; e < 12u * n_bones; e += 256u) s_palette[e] = palette[e];
+        __syncthreads();
+    }
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= n_verts) return;
+    const float *pal = LDS ? s_palette : palette;
+    float B[12];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const size_t at = (size_t)k * n_verts + v;
+        const float w = weight[at];
+        const float *M = pal + 12u * (uint32_t)bone[at];
+#pragma unroll
+        for (int e = 0; e < 12; e++) {
+            const float t = w * M[e];
+            B[e] = k == 0 ? t : B[e] + t;
+        }
+    }
+    const rt_vertex r = rest[v];
+    const float x = r.position.x, y = r.position.y, z = r.position.z;
+    rt_vertex o;
+    o.position.x = ((B[0] * x + B[1] * y) + B[2] * z) + B[3];
+    o.position.y = ((B[4] * x + B[5] * y) + B[6] * z) + B[7];
+    o.position.z = ((B[8] * x + B[9] * y) + B[10] * z) + B[11];
+    const float nx = r.normal.x, ny = r.normal.y, nz = r.normal.z;
+    const f3 s = mk3((B[0] * nx + B[1] * ny) + B[2] * nz, (B[4] * nx + B[5] * ny) + B[6] * nz, (B[8] * nx + B[9] * ny) + B[10] * nz);
+    const float d = dot(s, s);
+    const f3 n = (d > 0.0f && d < __uint_as_float(0x7f800000u)) ? normalize(s) : mk3(0.0f, 0.0f, 0.0f);
+    o.normal.x = n.x; o.normal.y = n.y; o.normal.z = n.z;
+    verts[v] = o;
+}
+
+template <int K>
+void launch_skin(hipStream_t st, bool lds, rt_vertex *verts, const rt_vertex *rest, uint32_t n_verts, const uint16_t *bone, const float *weight,
+                 const float *palette, uint32_t n_bones)
+{
+    const uint32_t blocks = (n_verts + 255u) / 256u;
+    if (lds) k_skin_vertices<K, true><<<blocks, 256, 0, st>>>(verts, rest, n_verts, bone, weight, palette, n_bones);
+    else k_skin_vertices<K, false><<<blocks, 256, 0, st>>>(verts, rest, n_verts, bone, weight, palette, n_bones);
 }
 
 int upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
@@ -551,6 +607,85 @@ int rt_model_recompute_normals(rt_model *m)
     k_vertex_normals<<<(m->n_verts + 255u) / 256u, 256, 0, ctx->stream>>>(m->d_verts.as<rt_vertex>(), m->n_verts, m->d_idx.as<uint32_t>(),
                                                                           m->adj_off.as<uint32_t>(), m->adj_tris.as<uint32_t>());
     HIP_TRY(hipGetLastError());
+    m->h_verts_stale = true;
+    model_changed(m);
+    return RT_OK;
+}
+
+int rt_model_set_skin(rt_model *m, uint32_t influences, uint32_t n_bones, const uint32_t *bone_indices, const float *weights)
+{
+    RT_REQUIRE(m, "null model");
+    rt_context *ctx = m->ctx;
+    if (influences == 0) {    // no skin: the vertices stay as the last pose left them
+        RT_TRY(use_device(ctx));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (a kernel that reads the buffers may still be queued)
+        m->skin_k = m->skin_bones = 0;
+        m->skin_bone.release(); m->skin_weight.release(); m->skin_rest.release();
+        return RT_OK;
+    }
+    uint32_t bad_v = 0, bad_k = 0;
+    switch (rt_skin_validate(m->n_verts, influences, n_bones, bone_indices, weights, &bad_v, &bad_k)) {
+    case 0: break;
+    case 1: rt_set_error("rt_model_set_skin: null argument"); return RT_ERR_INVALID_ARG;
+    case 2: rt_set_error("rt_model_set_skin: %u influences per vertex: 1 .. %u are supported (0 removes the skin)", influences, RT_SKIN_MAX_INFLUENCES); return RT_ERR_INVALID_ARG;
+    case 3: rt_set_error("rt_model_set_skin: %u bones: 1 .. %u are supported", n_bones, RT_SKIN_MAX_BONES); return RT_ERR_INVALID_ARG;
+    default:
+        rt_set_error("rt_model_set_skin: vertex %u, slot %u names bone %u of %u", bad_v, bad_k, bone_indices[(size_t)bad_v * influences + bad_k], n_bones);
+        return RT_ERR_INVALID_ARG;
+    }
+    std::vector<uint16_t> bone;
+    std::vector<float> weight;
+    rt_skin_pack(m->n_verts, influences, bone_indices, weights, bone, weight);
+    RT_TRY(use_device(ctx));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (a skin that is replaced: a kernel that reads the old one may still be queued)
+    m->skin_k = m->skin_bones = 0;                      // (no skin until all of the new one is there)
+    RT_TRY(upload(ctx, m->skin_bone, bone.data(), sizeof(uint16_t) * bone.size()));
+    RT_TRY(upload(ctx, m->skin_weight, weight.data(), sizeof(float) * weight.size()));
+    const size_t bytes = sizeof(rt_vertex) * (size_t)m->n_verts;
+    RT_TRY(m->skin_rest.reserve(bytes));
+    HIP_TRY(hipMemcpyAsync(m->skin_rest.p, m->d_verts.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));       // the rest pose: the vertices as they are
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope)
+    m->skin_k = influences;
+    m->skin_bones = n_bones;
+    return RT_OK;             // the vertices are what they were: nothing changed, built scenes stay built
+}
+
+int rt_model_get_skin(const rt_model *m, uint32_t *influences, uint32_t *n_bones)
+{
+    RT_REQUIRE(m, "null model");
+    if (influences) *influences = m->skin_k;
+    if (n_bones) *n_bones = m->skin_bones;
+    return RT_OK;
+}
+
+int rt_model_set_bones(rt_model *m, const float *bones3x4, uint32_t mem)
+{
+    RT_REQUIRE(m && bones3x4, "null argument");
+    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
+    if (m->skin_k == 0) {
+        rt_set_error("rt_model_set_bones: the model has no skin (rt_model_set_skin gives it one)");
+        return RT_ERR_STATE;
+    }
+    rt_context *ctx = m->ctx;
+    RT_TRY(model_before_set(m));
+    const float *palette = bones3x4;
+    if (mem == RT_MEM_HOST) {
+        RT_TRY(upload(ctx, ctx->scratch[0], bones3x4, 48 * (size_t)m->skin_bones));
+        palette = ctx->scratch[0].as<float>();
+    }
+    const bool lds = m->skin_bones <= RT_SKIN_LDS_BONES;
+    rt_vertex *verts = m->d_verts.as<rt_vertex>();
+    const rt_vertex *rest = m->skin_rest.as<rt_vertex>();
+    const uint16_t *bone = m->skin_bone.as<uint16_t>();
+    const float *weight = m->skin_weight.as<float>();
+    switch (m->skin_k) {      // (every pose from the rest pose, the whole mesh)
+#define RT_SKIN_CASE(K) case K: launch_skin<K>(ctx->stream, lds, verts, rest, m->n_verts, bone, weight, palette, m->skin_bones); break
+    RT_SKIN_CASE(1); RT_SKIN_CASE(2); RT_SKIN_CASE(3); RT_SKIN_CASE(4); RT_SKIN_CASE(5); RT_SKIN_CASE(6); RT_SKIN_CASE(7); RT_SKIN_CASE(8);
+#undef RT_SKIN_CASE
+    default: rt_set_error("rt_model_set_bones: %u influences", m->skin_k); return RT_ERR_STATE;
+    }
+    HIP_TRY(hipGetLastError());
+    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again, and the scratch buffer anybody's)
     m->h_verts_stale = true;
     model_changed(m);
     return RT_OK;

@@ -320,7 +320,11 @@ struct rt_model {
     std::vector<struct rt_scene *> scenes;   // the scenes that hold the model in some instance (each once): a set leaves the built ones stale
     DevBuf adj_off, adj_tris;    // vertex -> triangle CSR of the index list (rt_adjacency.h), made by the first rt_model_recompute_normals
     bool adj_ready = false;
-    ~rt_model();                 // (rt_api.hip) selects the device before the buffers go
+    // rt_model_set_skin / rt_model_set_bones: skin_k == 0: no skin
+    uint32_t skin_k = 0, skin_bones = 0;     // influences per vertex, bones of a palette
+    DevBuf skin_bone, skin_weight;           // uint16[skin_k][n_verts], float[skin_k][n_verts]: slot major (rt_skin.h)
+    DevBuf skin_rest;                        // rt_vertex[n_verts]: the rest pose, d_verts as they were when the skin was set
+    ~rt_model();                // (rt_api.hip) selects the device before the buffers go
 };
 
 struct SceneInstance {

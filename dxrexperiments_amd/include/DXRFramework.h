@@ -155,6 +155,22 @@ namespace DXRFramework
         }
         void recomputeNormals() { ThrowIfFailed(rt_model_recompute_normals(mHandle)); }
 
+        // EXTENSIONS (the reference imports with aiProcess_PreTransformVertices and reads only mVertices / mNormals, RtModel.cpp:26, :38-45:
+        // it has no bones; the update path is the never-taken one, Helpers/BottomLevelASGenerator.h:136-176): skeletal animation.  setSkin:
+        // numVertices x influences bone indices and weights, vertex major, host arrays; the vertices as they are become the rest pose and stay
+        // as they are.  setBones: numBones x 12 floats of 3x4 row-major skinning matrices (pose x inverse bind); the device writes every vertex
+        // from the rest pose (include/dxr_amd.h states the arithmetic), and every built scene that holds the model renders nothing until its
+        // update() or build().  clearSkin: no skin any more, the vertices stay what the last pose made them.
+        void setSkin(const uint32_t *boneIndices, const float *weights, uint32_t influences, uint32_t numBones)
+        {
+            ThrowIfFailed(rt_model_set_skin(mHandle, influences, numBones, boneIndices, weights));
+        }
+        void clearSkin() { ThrowIfFailed(rt_model_set_skin(mHandle, 0, 0, nullptr, nullptr)); }
+        void setBones(const float *bones3x4, bool deviceMemory = false)
+        {
+            ThrowIfFailed(rt_model_set_bones(mHandle, bones3x4, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
+        }
+
     private:
         RtModel(RtContext::SharedPtr ctx, rt_model *h) : mContext(ctx), mHandle(h) {}
         RtContext::SharedPtr mContext;

@@ -214,6 +214,45 @@ int rt_model_set_positions(rt_model *m, uint32_t first, uint32_t count, const fl
  * changed as a setter does. */
 int rt_model_recompute_normals(rt_model *m);
 
+/* Skeletal animation -- EXTENSIONS: the reference imports with aiProcess_PreTransformVertices and reads only mVertices / mNormals
+ * (libs/DXRFramework/RtModel.cpp:26, :38-45), so it has no bones at all; the update path a pose would take is the generators' never-taken
+ * one (Helpers/BottomLevelASGenerator.h:136-176).  A model gets a SKIN, the caller sets a bone PALETTE per frame, a kernel writes the model's
+ * vertices from the two, and rt_scene_update does the rest as after any rt_model_set_vertices.
+ * A skin of a model with V vertices: `influences` = K slots per vertex, 1 <= K <= 8; n_bones, 1 <= n_bones <= 65536; bone_indices[v][k] <
+ * n_bones and weights[v][k], both V x K, vertex major (entry [v][k] at v * K + k), host arrays; and the REST POSE, a copy of the model's
+ * 24-byte vertex records as they are on the device when the skin is set.  The weights are fp32, taken as given, never renormalised.
+ * A palette: n_bones x 12 floats, 3x4 row-major matrices M_b in the layout of the instance transforms -- the caller's finished skinning
+ * matrices (current pose x inverse bind); the library knows no hierarchy.
+ * The definition, for vertex v with rest position (x, y, z) and rest normal (nx, ny, nz), fp32 throughout, no contraction, in this order:
+ *   blend   for each of the 12 entries e: B[e] = weights[v][0] * M_bone[v][0][e]; then for k = 1 .. K - 1 in slot order
+ *           B[e] = B[e] + weights[v][k] * M_bone[v][k][e].  Every slot is evaluated: a zero weight is not skipped.
+ *   position, per row r: p'_r = ((B[r][0] x + B[r][1] y) + B[r][2] z) + B[r][3]
+ *   normal  s_r = (B[r][0] nx + B[r][1] ny) + B[r][2] nz; d = dot(s, s) = ((sx sx) + sy sy) + sz sz; the normal is s * (1 / sqrt(d)) if
+ *           0 < d < inf, else (0, 0, 0): the rule of rt_model_recompute_normals.  It goes through the blended LINEAR part, not its inverse
+ *           transpose: exact for rotations and uniform scales.  With non-uniform scales call rt_model_recompute_normals afterwards.
+ * NaN, inf, negative weights and weights that do not sum to 1 are no errors: the result is what the arithmetic gives.
+ * rt_model_set_skin validates on the host: a null argument, influences outside 1 .. 8 or n_bones outside 1 .. 65536 is RT_ERR_INVALID_ARG;
+ * so is an index >= n_bones (the message names the vertex and the slot).  It stores the skin on the device and captures the rest pose, device
+ * to device on the context's stream.  It does NOT change the model's vertices: nothing is marked changed, built scenes stay built.  Calling it
+ * again replaces the skin and captures the rest pose anew from the vertices the model holds then.  influences == 0 (the other arguments are
+ * ignored) removes the skin and frees its buffers; the vertices stay what the last pose made them. */
+int rt_model_set_skin(rt_model *m, uint32_t influences, uint32_t n_bones,
+                      const uint32_t *bone_indices /* V x influences, vertex major */,
+                      const float *weights        /* V x influences */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the influences and bones of the model's skin; 0, 0: no skin */
+int rt_model_get_skin(const rt_model *m, uint32_t *influences, uint32_t *n_bones);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): every vertex of the model from the rest pose and this palette,
+ * by the definition above, on the device -- always the whole mesh and always from the rest pose, never from the previous pose.  `mem`:
+ * RT_MEM_HOST (the palette goes up through a scratch buffer and the stream is synchronised before the call returns, as for
+ * rt_model_set_positions) or RT_MEM_DEVICE (used in place, ordered on the context's stream; a producer on another stream is the caller's to
+ * order, and the palette must stay as it is until the stream has passed the call).  A null argument or an unknown `mem` is
+ * RT_ERR_INVALID_ARG; a model without a skin is RT_ERR_STATE (the message names rt_model_set_skin).  Otherwise it behaves as the setters
+ * above: frames a deferred pipeline still holds are rendered first, the model is left CHANGED and every built scene that holds it STALE
+ * (RT_ERR_STATE from what reads them, the message names the pending vertices) until rt_scene_update or rt_scene_build, which rebuild the BLAS.
+ * rt_model_set_vertices / rt_model_set_positions on a skinned model still write the current vertices and leave the rest pose alone: the next
+ * rt_model_set_bones overwrites what they wrote.  rt_model_read_geometry returns the skinned vertices. */
+int rt_model_set_bones(rt_model *m, const float *bones3x4 /* n_bones x 12 */, uint32_t mem /* RT_MEM_HOST | RT_MEM_DEVICE */);
+
 /* ---- raw TraceRay over a batch (HLSL TraceRay semantics, used by tests and
  *      the traversal benchmark; ProgressiveRaytracing.hlsl:34,53,
  *      RaytracingCommon.hlsli:94) ------------------------------------------- */
