@@ -756,21 +756,50 @@ int rt_scene_add_model(rt_scene *s, rt_model *m, const float transform3x4[12])
     return RT_OK;
 }
 
+static int scene_range_check(const rt_scene *s, const char *who, uint32_t first, uint32_t count)
+{
+    const size_t n = s->inst.size();
+    if (first > n || count > n - first) {
+        rt_set_error("%s: instances %u .. %llu out of range: the scene has %zu", who, first, (unsigned long long)first + count, n);
+        return RT_ERR_STATE;
+    }
+    return RT_OK;
+}
+
+// instance i joins the list the next update rewrites (once)
+static void scene_mark_pending(rt_scene *s, uint32_t i)
+{
+    s->is_pending.resize(s->inst.size(), 0);
+    if (!s->is_pending[i]) { s->is_pending[i] = 1; s->pending.push_back(i); }
+}
+
+// A build or an update has succeeded: every stored transform and mask has been read, and the vertices of the models of `changed` (an
+// update: exactly the instances whose generation differed; nullptr, a build: of every instance).  Nothing is pending, the scene is fresh.
+static void scene_applied(rt_scene *s, const std::vector<uint32_t> *changed)
+{
+    const size_t n = s->inst.size();
+    if (changed) {
+        for (uint32_t i : s->pending) s->is_pending[i] = 0;
+        for (uint32_t i : *changed) s->seen_geom[i] = s->inst[i].model->geom_gen;
+    } else {
+        s->is_pending.assign(n, 0);
+        s->seen_geom.resize(n);
+        for (size_t i = 0; i < n; i++) s->seen_geom[i] = s->inst[i].model->geom_gen;
+    }
+    s->pending.clear();
+    s->masks_dirty = false;
+    s->built = true;
+}
+
 int rt_scene_set_instance_transforms(rt_scene *s, uint32_t first, uint32_t count, const float *transforms3x4)
 {
     RT_REQUIRE(s && (transforms3x4 || count == 0), "null argument");
-    const size_t n = s->inst.size();
-    if (first > n || count > n - first) {
-        rt_set_error("rt_scene_set_instance_transforms: instances %u .. %llu out of range: the scene has %zu", first, (unsigned long long)first + count, n);
-        return RT_ERR_STATE;
-    }
+    RT_TRY(scene_range_check(s, "rt_scene_set_instance_transforms", first, count));
     if (count == 0) return RT_OK;
     RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
     for (uint32_t k = 0; k < count; k++) memcpy(s->inst[first + k].xform, transforms3x4 + 12 * (size_t)k, sizeof s->inst[0].xform);
     if (!s->updatable) return RT_OK;                  // never built (or instances added since): the next build reads the stored transforms
-    s->is_pending.resize(n, 0);
-    for (uint32_t i = first; i < first + count; i++)
-        if (!s->is_pending[i]) { s->is_pending[i] = 1; s->pending.push_back(i); }
+    for (uint32_t i = first; i < first + count; i++) scene_mark_pending(s, i);
     s->built = false;         // stale until rt_scene_update or rt_scene_build: nothing traces a half-applied state
     return RT_OK;
 }
@@ -790,11 +819,7 @@ int rt_scene_set_instance_transform(rt_scene *s, uint32_t instance, const float 
 int rt_scene_set_instance_masks(rt_scene *s, uint32_t first, uint32_t count, const uint8_t *masks)
 {
     RT_REQUIRE(s && (masks || count == 0), "null argument");
-    const size_t n = s->inst.size();
-    if (first > n || count > n - first) {
-        rt_set_error("rt_scene_set_instance_masks: instances %u .. %llu out of range: the scene has %zu", first, (unsigned long long)first + count, n);
-        return RT_ERR_STATE;
-    }
+    RT_TRY(scene_range_check(s, "rt_scene_set_instance_masks", first, count));
     if (count == 0) return RT_OK;
     RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
     bool visibility = false;
@@ -821,11 +846,7 @@ int rt_scene_set_instance_mask(rt_scene *s, uint32_t instance, uint8_t mask)
 int rt_scene_get_instance_masks(const rt_scene *s, uint32_t first, uint32_t count, uint8_t *masks)
 {
     RT_REQUIRE(s && (masks || count == 0), "null argument");
-    const size_t n = s->inst.size();
-    if (first > n || count > n - first) {
-        rt_set_error("rt_scene_get_instance_masks: instances %u .. %llu out of range: the scene has %zu", first, (unsigned long long)first + count, n);
-        return RT_ERR_STATE;
-    }
+    RT_TRY(scene_range_check(s, "rt_scene_get_instance_masks", first, count));
     if (count) memcpy(masks, s->masks.data() + first, count);
     return RT_OK;
 }
@@ -847,24 +868,21 @@ int rt_scene_update(rt_scene *s)
     // pending thing kept -- showing one and updating again succeeds)
     if (s->masks_dirty) RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_update", false));
     s->generation++;          // pipelines drop what they cached from the old geometry: shadow-cache occluders, per-pixel entries, the free sphere, the primary-mode samples
-    ScopedEvent e0;
+    ScopedEvent e0, e1;
     HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventCreate(&e1.e));
     HIP_TRY(hipEventRecord(e0.e, ctx->stream));
     if (!changed.empty()) {
         // a changed model whose BLAS is older than its vertices: rebuilt by the build's own steps into the model's own buffers (one that
         // another scene's update or build has rebuilt already is built: rt_build_blas returns at once)
         for (uint32_t i : changed) RT_TRY(rt_build_blas(ctx, s->inst[i].model));
         RT_TRY(rt_update_model_records(ctx, s, changed));
-        s->is_pending.resize(s->inst.size(), 0);
-        for (uint32_t i : changed)            // ... and take their world boxes over the new vertices, with the transforms they have
-            if (!s->is_pending[i]) { s->is_pending[i] = 1; s->pending.push_back(i); }
+        for (uint32_t i : changed) scene_mark_pending(s, i);      // ... and take their world boxes over the new vertices, with the transforms they have
     }
-    RT_TRY(rt_update_tlas(ctx, s, e0.e));             // (a failure leaves the scene stale, the transforms and the models pending)
-    for (uint32_t i : s->pending) s->is_pending[i] = 0;
-    s->pending.clear();
-    for (uint32_t i : changed) s->seen_geom[i] = s->inst[i].model->geom_gen;
-    s->masks_dirty = false;
-    s->built = true;
+    // (a failure leaves the scene stale, the transforms and the models pending); e1: behind the wide collapse, in front of the read-back
+    RT_TRY(rt_update_tlas(ctx, s, s->pending, "rt_scene_update", e1.e));
+    HIP_TRY(hipEventElapsedTime(&s->update_ms, e0.e, e1.e));
+    scene_applied(s, &changed);
     return RT_OK;
 }
 
@@ -899,17 +917,11 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     for (SceneInstance &in : s->inst) RT_TRY(rt_build_blas(ctx, in.model));
     s->updatable = false;
     RT_TRY(rt_build_tlas(ctx, s));
-    RT_TRY(rt_upload_blas_bounds(ctx, s));
     HIP_TRY(hipEventRecord(e1.e, ctx->stream));
     HIP_TRY(hipEventSynchronize(e1.e));
     HIP_TRY(hipEventElapsedTime(&s->build_ms, e0.e, e1.e));
-    s->built = true;
     s->updatable = true;
-    s->pending.clear();       // the build has read every stored transform and mask
-    s->masks_dirty = false;
-    s->is_pending.assign(s->inst.size(), 0);
-    s->seen_geom.resize(s->inst.size());               // ... and every model's vertices
-    for (size_t i = 0; i < s->inst.size(); i++) s->seen_geom[i] = s->inst[i].model->geom_gen;
+    scene_applied(s, nullptr);
     return RT_OK;
 }
 

@@ -453,19 +453,7 @@ void carve_blas(Carver &c, uint32_t n, BlasTemps &t)
     t.scan_bytes = (size_t)1 << 20;
     t.scan = c.take<char>(t.scan_bytes);
 }
-// (+ k_instance_boxes' work memory: per-instance encoded bounds, the forward transforms, the work list)
-struct TlasTemps : LbvhTemps {
-    uint32_t *inst_enc;
-    float *inst_xf;
-    uint2 *inst_items;
-};
-void carve_tlas(Carver &c, uint32_t n, size_t n_items, TlasTemps &t)
-{
-    carve_lbvh(c, n, t);
-    t.inst_enc = c.take<uint32_t>(6 * (size_t)n);
-    t.inst_xf = c.take<float>(12 * (size_t)n);
-    t.inst_items = c.take<uint2>(n_items);
-}
+// (the TLAS adds the work memory of its record and world-box kernels: TlasTemps, further down)
 template <class Temps, class Carve> int take_build_temps(rt_context *ctx, uint32_t n, Temps &t, Carve carve)
 {
     Carver sizing(nullptr);
@@ -723,53 +711,6 @@ int rt_build_blas(rt_context *ctx, rt_model *m)
     return rc;
 }
 
-// (invert3x4, the world-to-object matrix of an instance: rt_xform.h -- one text for this file's host and device code)
-
-// The world box of a transformed instance: the exact box of its triangles' transformed vertices (oracle_bvh.h
-// scene_build; the box of the BLAS box's eight transformed corners is up to 1.6x wider in footprint for a rotated mesh, and a third
-// of all instance entries of the 4096-instance frame were false ones, profiles/r04/tight_boxes.txt).  One block per work item =
-// (instance, chunk of INST_BOX_REFS vertex references); x' = ((m0 x + m1 y) + m2 z) + m3 as the oracle's xform_point; min / max
-// are order free, so the atomics cannot change a bit.
-constexpr unsigned INST_BOX_REFS = 4096;
-__global__ void __launch_bounds__(BOUNDS_BLOCK) k_instance_boxes(const InstanceRec *__restrict__ inst, const float *__restrict__ xf,
-                                                                const uint2 *__restrict__ items, uint32_t *__restrict__ enc)
-{
-    const uint2 it = items[blockIdx.x];
-    const InstanceRec &in = inst[it.x];
-    const float *m = xf + 12u * (size_t)it.x;
-    const uint32_t refs = 3u * in.n_prims;
-    const float inf = __uint_as_float(0x7f800000u);
-    Box6 b;
-    for (int c = 0; c < 3; c++) { b.lo[c] = inf; b.hi[c] = -inf; }
-    for (uint32_t k = it.y * INST_BOX_REFS + threadIdx.x; k < refs && k < (it.y + 1u) * INST_BOX_REFS; k += BOUNDS_BLOCK) {
-        const rt_float3 p = in.verts[in.indices[k]].position;
-        for (int r = 0; r < 3; r++) {
-            float w = m[4 * r + 0] * p.x;
-            w = w + m[4 * r + 1] * p.y;
-            w = w + m[4 * r + 2] * p.z;
-            w = w + m[4 * r + 3];
-            b.lo[r] = fminf(b.lo[r], w);
-            b.hi[r] = fmaxf(b.hi[r], w);
-        }
-    }
-    reduce_bounds(b, true, enc + 6u * (size_t)it.x);
-}
-__global__ void k_instance_boxes_init(uint32_t *enc, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 6u * n) enc[i] = (i % 6u) < 3u ? ENC_POS_INF : ENC_NEG_INF;
-}
-// ... into the instance records and the TLAS builder's leaf boxes (identity instances keep the box of their BLAS)
-__global__ void k_instance_boxes_finish(InstanceRec *__restrict__ inst, const uint32_t *__restrict__ enc, Box6 *__restrict__ boxes, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    InstanceRec &r = inst[i];
-    if (!(r.flags & RT_INST_IDENTITY))
-        for (int c = 0; c < 3; c++) { r.wlo[c] = f_dec(enc[6u * i + c]); r.whi[c] = f_dec(enc[6u * i + 3 + c]); }
-    for (int c = 0; c < 3; c++) { boxes[i].lo[c] = r.wlo[c]; boxes[i].hi[c] = r.whi[c]; }
-}
-
 // ---- instance masks (rt_scene_set_instance_mask): the TLAS over the visible sub-list ----
 //
 // Stands in for the InstanceMask member of the instance descriptors (libs/DXRFramework/Helpers/TopLevelASGenerator.cpp:344-362, always 0xFF
@@ -779,17 +720,6 @@ __global__ void k_instance_boxes_finish(InstanceRec *__restrict__ inst, const ui
 namespace {
 
 constexpr unsigned UPD_BLOCK = 256;
-
-// the world box of every visible instance, as it stands in its record -> the TLAS builder's leaf boxes (k_update_leaf_boxes / the tail of
-// k_instance_boxes_finish when something is hidden).  Read from the RECORDS, which nobody writes here: `boxes` may still hold the full list's
-__global__ void __launch_bounds__(UPD_BLOCK) k_visible_leaf_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ vis, uint32_t n_vis,
-                                                                 Box6 *__restrict__ boxes)
-{
-    const uint32_t j = blockIdx.x * UPD_BLOCK + threadIdx.x;
-    if (j >= n_vis) return;
-    const InstanceRec &r = inst[vis[j]];
-    for (int c = 0; c < 3; c++) { boxes[j].lo[c] = r.wlo[c]; boxes[j].hi[c] = r.whi[c]; }
-}
 
 // sub-list position -> instance index, in the canonical leaves' `left` and the low words of the sorted keys (vis is increasing: the keys stay
 // ascending).  k_lbvh_to_tree takes a TLAS leaf's code from `left`, so the four-wide layout comes out mapped
@@ -842,131 +772,26 @@ int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool for
     return RT_OK;
 }
 
-int rt_build_tlas(rt_context *ctx, rt_scene *s)
-{
-    hipStream_t st = ctx->stream;
-    const uint32_t n = (uint32_t)s->inst.size();
-    static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    s->h_inst.assign(n, InstanceRec());
-    std::vector<Box6> hb(n);
-    std::vector<uint2> items;          // (instance, chunk of its vertex references): the work list of k_instance_boxes
-    std::vector<float> xf;             // the forward transforms, for the same kernel (alive until the build's last synchronisation)
-    uint32_t deepest = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        rt_model *m = s->inst[i].model;
-        InstanceRec &r = s->h_inst[i];
-        const float *x = s->inst[i].xform;
-        bool identity = true;
-        for (int k = 0; k < 12; k++) identity = identity && (x[k] == ident[k]);
-        const float *bb = m->blas.bounds;
-        if (identity) {
-            memcpy(r.inv, x, sizeof r.inv);
-            for (int c = 0; c < 3; c++) { r.wlo[c] = bb[c]; r.whi[c] = bb[3 + c]; }
-        } else {
-            invert3x4(x, r.inv);
-            const float inf = __builtin_inff();
-            for (int c = 0; c < 3; c++) { r.wlo[c] = inf; r.whi[c] = -inf; }
-            // (the world box of a transformed instance comes from k_instance_boxes below: empty until then)
-        }
-        r.root_code = m->blas.root_code;
-        r.flags = identity ? RT_INST_IDENTITY : 0u;
-        r.wide = m->blas.wide.as<WNode>();
-        r.tris = m->tris.as<TriRec>();
-        r.cnodes = m->blas.nodes.as<rt_bvh_node>();
-        r.verts = m->d_verts.as<rt_vertex>();
-        r.indices = m->d_idx.as<uint32_t>();
-        r.normals = m->normals.as<TriRec>();
-        r.n_prims = m->n_tris;
-        r.n_recs = m->n_recs;
-        r.pad_ = 0;
-        r.material = i;
-        r.rec_boxes = m->rec_boxes.p ? m->rec_boxes.as<float>() : nullptr;
-        r.ref_off = m->ref_off.p ? m->ref_off.as<uint32_t>() : nullptr;
-        r.ref_boxes = m->ref_boxes.p ? m->ref_boxes.as<float>() : nullptr;
-        if (i == 0) s->has_refs = false;
-        s->has_refs = s->has_refs || m->ref_off.p != nullptr;
-        deepest = m->blas.fast_depth > deepest ? m->blas.fast_depth : deepest;
-        if (!identity)
-            for (uint32_t c = 0; c * INST_BOX_REFS < 3u * m->n_tris; c++) items.push_back(make_uint2(i, c));
-    }
-    TlasTemps t;
-    const size_t n_items = items.size();
-    RT_TRY(take_build_temps(ctx, n, t, [n, n_items](Carver &c, TlasTemps &tt) { carve_tlas(c, n, n_items, tt); }));
-    RT_TRY(s->d_inst.reserve(sizeof(InstanceRec) * (size_t)n));
-    HIP_TRY(hipMemcpyAsync(s->d_inst.p, s->h_inst.data(), sizeof(InstanceRec) * n, hipMemcpyHostToDevice, st));
-    // world boxes: of the transformed instances from their vertices, then all of them into the records and the leaf boxes
-    k_instance_boxes_init<<<grid_for(6 * n, 256), 256, 0, st>>>(t.inst_enc, n);        // (a transformed instance without triangles keeps the empty box)
-    if (!items.empty()) {
-        xf.resize(12 * (size_t)n);
-        for (uint32_t i = 0; i < n; i++) memcpy(&xf[12 * (size_t)i], s->inst[i].xform, 12 * sizeof(float));
-        HIP_TRY(hipMemcpyAsync(t.inst_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(t.inst_items, items.data(), items.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-        k_instance_boxes<<<(uint32_t)items.size(), BOUNDS_BLOCK, 0, st>>>(s->d_inst.as<InstanceRec>(), t.inst_xf, t.inst_items, t.inst_enc);
-    }
-    k_instance_boxes_finish<<<grid_for(n, 256), 256, 0, st>>>(s->d_inst.as<InstanceRec>(), t.inst_enc, t.boxes, n);
-    HIP_TRY(hipMemcpyAsync(hb.data(), t.boxes, sizeof(Box6) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t i = 0; i < n; i++)
-        for (int c = 0; c < 3; c++) { s->h_inst[i].wlo[c] = hb[i].lo[c]; s->h_inst[i].whi[c] = hb[i].hi[c]; }
-    // some instance hidden (rt_scene_set_instance_mask): the records above are the full list's, the TLAS is the one of the visible sub-list
-    const uint32_t nv = s->n_vis;
-    if (nv < n) {
-        RT_TRY(reserve_tlas_for(s->tlas, n));
-        k_visible_leaf_boxes<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, st>>>(s->d_inst.as<InstanceRec>(), s->d_vis.as<uint32_t>(), nv, t.boxes);
-    }
-    k_init_bounds<<<1, 64, 0, st>>>(t.enc);
-    k_box_bounds<<<grid_for(nv, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, nv, t.enc);
-    k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
-    RT_TRY(lbvh_from_boxes(ctx, s->tlas, nv, t));
-    if (nv < n) RT_TRY(map_visible_leaves(ctx, s));
-    // the TLAS is walked in the same four-wide layout (a single instance: the root is the leaf of instance 0)
-    RT_TRY(rt_build_wide_from_lbvh(ctx, s->tlas, true, 1));
-    if (nv < n && nv == 1) s->tlas.root_code = ~(int)s->vis[0];       // (the one visible instance's own index)
-    RT_TRY(lbvh_collect(ctx, s->tlas));
-    // a step leaves at most three siblings behind; two-level walks add the TLAS path and the sentinel that marks the
-    // bottom of a BLAS walk
-    s->two_level = !(n == 1 && (s->h_inst[0].flags & RT_INST_IDENTITY));
-    s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;
-    // the canonical traversal (parity / counting kernels and the deep-stack path of the fast one) keeps
-    // 128-entry private stacks per structure
-    uint32_t canon = s->tlas.max_depth;
-    for (uint32_t i = 0; i < n; i++) canon = s->inst[i].model->blas.max_depth > canon ? s->inst[i].model->blas.max_depth : canon;
-    if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); return RT_ERR_UNSUPPORTED; }
-    if (ctx->verbose)
-        fprintf(stderr, "[dxr_amd] TLAS %u instances depth %u; deepest BLAS layout depth %u (%s); stack need %u; %s walk\n", n,
-                s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
-    return RT_OK;
-}
-
-// ---- rt_scene_update: the transforms set since the last build, applied on the device ----
+// ---- the TLAS: instance list -> records -> world boxes -> tree, ONE path for rt_scene_build and rt_scene_update ----
 //
-// Stands in for the generators' update path (libs/DXRFramework/Helpers/TopLevelASGenerator.h:144-163 `updateOnly`), which the reference's
-// RtScene never calls.  The definition is "update == build": the canonical TLAS is a pure function of the instance boxes and every traversal
-// returns the same bits on any tree, so the TLAS is rebuilt -- by the build's own steps, into the scene's own buffers --
-// from boxes of which only the pending instances' are computed anew.  Only the pending transforms and their indices go up; the records are
-// rewritten, and the work list of the world boxes is made, on the device.
-
-// The BLAS box of every instance's model: what an instance set (back) to the identity takes as its world box.
-int rt_upload_blas_bounds(rt_context *ctx, rt_scene *s)
-{
-    const size_t n = s->inst.size();
-    s->h_blas_bounds.resize(6 * n);                    // (a member: alive whenever the copy runs)
-    for (size_t i = 0; i < n; i++) memcpy(&s->h_blas_bounds[6 * i], s->inst[i].model->blas.bounds, 6 * sizeof(float));
-    RT_TRY(s->blas_bounds.reserve(6 * n * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(s->blas_bounds.p, s->h_blas_bounds.data(), 6 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    return RT_OK;
-}
+// rt_scene_update stands in for the generators' update path (libs/DXRFramework/Helpers/TopLevelASGenerator.h:144-163 `updateOnly`), which the
+// reference's RtScene never calls.  The definition is "update == build", and it holds by construction: a build writes what only a build
+// knows (the model part of every record, rt_build_tlas) and then IS an update with every instance pending (rt_update_tlas).  The canonical
+// TLAS is a pure function of the instance boxes and every traversal returns the same bits on any tree, so the TLAS is
+// always rebuilt -- into the scene's own buffers -- from boxes of which only the listed instances' are computed anew.  Only the listed
+// transforms and their indices go up; the records are rewritten, and the work list of the world boxes is made, on the device.
 
 namespace {
 
 constexpr unsigned UPD_BACK_WORDS = 20;      // inv[12], wlo[3], root_code, whi[3], flags: the head of an InstanceRec
 static_assert(offsetof(InstanceRec, flags) == 4 * (UPD_BACK_WORDS - 1), "the read-back of an update is the head of the record");
+constexpr unsigned INST_BOX_REFS = 4096;     // vertex references of one work item of k_instance_boxes
 
-// One lane per pending instance: the record's inverse, flags and (empty or BLAS) box, as rt_build_tlas writes them on the host; and the
-// (slot, chunk of INST_BOX_REFS vertex references) work items of the transformed ones, compacted into `items`: a wave-wide prefix sum of
-// the lanes' chunk counts, ONE atomic per wave that has any (a ballot says so), every lane then writes its own run.  The order of the
-// list depends on the order of the atomics; the boxes made from it do not (min / max).  max_items = the chunks of all pending
-// instances, transformed or not: the host's bound of the list and the next launch's grid.
+// One lane per listed instance: the transform part of its record -- the inverse (invert3x4, rt_xform.h), the identity flag and the (empty or
+// BLAS) box; and the (slot, chunk of INST_BOX_REFS vertex references) work items of the transformed ones, compacted into `items`: a
+// wave-wide prefix sum of the lanes' chunk counts, ONE atomic per wave that has any (a ballot says so), every lane then writes its own run.
+// The order of the list depends on the order of the atomics; the boxes made from it do not (min / max).  max_items = the chunks of all
+// listed instances, transformed or not: the host's bound of the list and the next launch's grid.
 __global__ void __launch_bounds__(UPD_BLOCK) k_update_records(InstanceRec *__restrict__ inst, const float *__restrict__ blas_bounds,
                                                               const uint32_t *__restrict__ pend_idx, const float *__restrict__ pend_xf, uint32_t n_pending,
                                                               uint32_t *__restrict__ enc, uint2 *__restrict__ items, uint32_t *__restrict__ n_items,
@@ -990,7 +815,7 @@ __global__ void __launch_bounds__(UPD_BLOCK) k_update_records(InstanceRec *__res
         for (int c = 0; c < 3; c++) {
             r.wlo[c] = identity ? blas_bounds[6u * (size_t)i + c] : inf;     // (a transformed instance: empty until k_update_apply)
             r.whi[c] = identity ? blas_bounds[6u * (size_t)i + 3 + c] : -inf;
-            enc[6u * (size_t)slot + c] = ENC_POS_INF;
+            enc[6u * (size_t)slot + c] = ENC_POS_INF;                        // (one without triangles keeps the empty box)
             enc[6u * (size_t)slot + 3 + c] = ENC_NEG_INF;
         }
         r.flags = identity ? RT_INST_IDENTITY : 0u;
@@ -1012,11 +837,15 @@ __global__ void __launch_bounds__(UPD_BLOCK) k_update_records(InstanceRec *__res
         if (first + c < max_items) items[first + c] = make_uint2(slot, c);
 }
 
-// k_instance_boxes for the items of that list: the same arithmetic on the same vertex references, the transform and the encoded box by
-// pending slot.  The grid is the host's bound; blocks beyond the list's count have nothing to do.
-__global__ void __launch_bounds__(BOUNDS_BLOCK) k_update_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx,
-                                                              const float *__restrict__ pend_xf, const uint2 *__restrict__ items,
-                                                              const uint32_t *__restrict__ n_items, uint32_t *__restrict__ enc)
+// The world box of a transformed instance: the exact box of its triangles' transformed vertices (oracle_bvh.h
+// scene_build; the box of the BLAS box's eight transformed corners is up to 1.6x wider in footprint for a rotated mesh, and a third
+// of all instance entries of the 4096-instance frame were false ones, profiles/r04/tight_boxes.txt).  One block per work item =
+// (slot of the list, chunk of INST_BOX_REFS vertex references); x' = ((m0 x + m1 y) + m2 z) + m3 as the oracle's xform_point; min / max
+// are order free, so the atomics cannot change a bit.  The transform and the encoded box go by slot.  The grid is the host's bound; blocks
+// beyond the list's count have nothing to do.
+__global__ void __launch_bounds__(BOUNDS_BLOCK) k_instance_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx,
+                                                                const float *__restrict__ pend_xf, const uint2 *__restrict__ items,
+                                                                const uint32_t *__restrict__ n_items, uint32_t *__restrict__ enc)
 {
     if (blockIdx.x >= *n_items) return;                // (block-uniform)
     const uint2 it = items[blockIdx.x];
@@ -1040,7 +869,8 @@ __global__ void __launch_bounds__(BOUNDS_BLOCK) k_update_boxes(const InstanceRec
     reduce_bounds(b, true, enc + 6u * (size_t)it.x);
 }
 
-// the boxes into the records of the pending transformed instances; the head of every pending record into the read-back for h_inst
+// the boxes into the records of the listed transformed instances (identity instances keep the box of their BLAS); the head of every listed
+// record into the read-back for h_inst
 __global__ void k_update_apply(InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx, uint32_t n_pending,
                                const uint32_t *__restrict__ enc, uint32_t *__restrict__ back)
 {
@@ -1053,16 +883,20 @@ __global__ void k_update_apply(InstanceRec *__restrict__ inst, const uint32_t *_
     for (unsigned k = 0; k < UPD_BACK_WORDS; k++) back[UPD_BACK_WORDS * (size_t)slot + k] = head[k];
 }
 
-// every instance's box (an untouched one's as it stands in its record) -> the TLAS builder's leaf boxes
-__global__ void k_update_leaf_boxes(const InstanceRec *__restrict__ inst, Box6 *__restrict__ boxes, uint32_t n)
+// the world box of every visible instance, as it stands in its record (an untouched one's too) -> the TLAS builder's leaf boxes; vis == nullptr:
+// nothing is hidden, position j is instance j.  Read from the RECORDS, which nobody writes here: `boxes` may still hold another list's
+__global__ void __launch_bounds__(UPD_BLOCK) k_leaf_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ vis, uint32_t n_vis,
+                                                         Box6 *__restrict__ boxes)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int c = 0; c < 3; c++) { boxes[i].lo[c] = inst[i].wlo[c]; boxes[i].hi[c] = inst[i].whi[c]; }
+    const uint32_t j = blockIdx.x * UPD_BLOCK + threadIdx.x;
+    if (j >= n_vis) return;
+    const InstanceRec &r = inst[vis ? vis[j] : j];
+    for (int c = 0; c < 3; c++) { boxes[j].lo[c] = r.wlo[c]; boxes[j].hi[c] = r.whi[c]; }
 }
 
-// A deformed model's BLAS has been rebuilt (rt_scene_update): what an instance record says about its model, as rt_build_tlas writes it on the
-// host.  DevBuf::reserve may have moved any of the arrays, and n_recs and the reference buffers come and go with the shape.
+// The model part of an instance record: what the record says about its model.  A build writes it for every instance; after a deformed
+// model's BLAS has been rebuilt (rt_scene_update) DevBuf::reserve may have moved any of the arrays, and n_recs and the reference buffers
+// come and go with the shape.  The field list stands twice: in model_desc and in write_model_part.
 struct ModelDesc {
     const WNode *wide;
     const TriRec *tris;
@@ -1100,6 +934,15 @@ ModelDesc model_desc(const rt_model *m)
     return d;
 }
 
+// ... into a record and the instance's row of the BLAS boxes (device: d_inst / blas_bounds; host: h_inst / h_blas_bounds)
+__host__ __device__ inline void write_model_part(InstanceRec &r, float *bounds_row, const ModelDesc &d)
+{
+    r.wide = d.wide; r.tris = d.tris; r.cnodes = d.cnodes; r.verts = d.verts; r.indices = d.indices; r.normals = d.normals;
+    r.rec_boxes = d.rec_boxes; r.ref_off = d.ref_off; r.ref_boxes = d.ref_boxes;
+    r.root_code = d.root_code; r.n_prims = d.n_prims; r.n_recs = d.n_recs;
+    for (int c = 0; c < 6; c++) bounds_row[c] = d.bounds[c];
+}
+
 // one lane per affected instance: who = (instance, descriptor)
 __global__ void k_update_model_fields(InstanceRec *__restrict__ inst, float *__restrict__ blas_bounds, const ModelDesc *__restrict__ desc,
                                       const uint2 *__restrict__ who, uint32_t n)
@@ -1107,23 +950,21 @@ __global__ void k_update_model_fields(InstanceRec *__restrict__ inst, float *__r
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const uint32_t i = who[k].x;
-    const ModelDesc &d = desc[who[k].y];
-    InstanceRec &r = inst[i];
-    r.wide = d.wide; r.tris = d.tris; r.cnodes = d.cnodes; r.verts = d.verts; r.indices = d.indices; r.normals = d.normals;
-    r.rec_boxes = d.rec_boxes; r.ref_off = d.ref_off; r.ref_boxes = d.ref_boxes;
-    r.root_code = d.root_code; r.n_prims = d.n_prims; r.n_recs = d.n_recs;
-    for (int c = 0; c < 6; c++) blas_bounds[6u * (size_t)i + c] = d.bounds[c];
+    write_model_part(inst[i], blas_bounds + 6u * (size_t)i, desc[who[k].y]);
 }
 
-// (+ the pending indices and transforms, their encoded boxes, the work list and its count)
-struct UpdateTemps : LbvhTemps {
+// (+ the listed indices and transforms, their encoded boxes, the work list and its count).  LIFETIME: the phases of a build share the
+// arena -- lbvh_from_boxes reads these slices, then rt_build_wide_from_lbvh (as the PLOC phase of a BLAS) carves the SAME arena again from
+// its start.  So nothing here may be read behind the wide collapse: whatever has to outlive it, as the record heads on their way to h_inst
+// do, lives in a buffer of the scene's own (rt_scene::update_back).
+struct TlasTemps : LbvhTemps {
     uint32_t *pend_idx;
     float *pend_xf;
     uint32_t *pend_enc;
     uint2 *items;
     uint32_t *n_items;
 };
-void carve_update(Carver &c, uint32_t n, size_t n_pending, size_t max_items, UpdateTemps &t)
+void carve_tlas(Carver &c, uint32_t n, size_t n_pending, size_t max_items, TlasTemps &t)
 {
     carve_lbvh(c, n, t);
     t.pend_idx = c.take<uint32_t>(n_pending);
@@ -1161,70 +1002,57 @@ int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint
                                                                                 (uint32_t)who.size());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));                 // (the host vectors go out of scope; a reserve of the arena by the update frees this slice)
-    for (size_t k = 0; k < changed.size(); k++) {      // the host mirrors follow
-        const uint32_t i = changed[k];
-        const ModelDesc &d = desc[who[k].y];
-        InstanceRec &r = s->h_inst[i];
-        r.wide = d.wide; r.tris = d.tris; r.cnodes = d.cnodes; r.verts = d.verts; r.indices = d.indices; r.normals = d.normals;
-        r.rec_boxes = d.rec_boxes; r.ref_off = d.ref_off; r.ref_boxes = d.ref_boxes;
-        r.root_code = d.root_code; r.n_prims = d.n_prims; r.n_recs = d.n_recs;
-        memcpy(&s->h_blas_bounds[6 * (size_t)i], d.bounds, sizeof d.bounds);
-    }
+    for (size_t k = 0; k < changed.size(); k++)        // the host mirrors follow
+        write_model_part(s->h_inst[changed[k]], &s->h_blas_bounds[6 * (size_t)changed[k]], desc[who[k].y]);
     return RT_OK;
 }
 
-int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started)
+int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &list, const char *who, hipEvent_t queued)
 {
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)s->inst.size();
-    const size_t np = s->pending.size();
+    const size_t np = list.size();
     std::vector<float> xf(12 * np);                    // (alive, as the index list is, until the last synchronisation below)
     size_t max_items = 0;
     for (size_t k = 0; k < np; k++) {
-        const SceneInstance &in = s->inst[s->pending[k]];
+        const SceneInstance &in = s->inst[list[k]];
         memcpy(&xf[12 * k], in.xform, 12 * sizeof(float));
         max_items += (3 * (size_t)in.model->n_tris + INST_BOX_REFS - 1) / INST_BOX_REFS;
     }
-    if (max_items > 0x7fffffffu) { rt_set_error("rt_scene_update: %zu work items for the world boxes: the limit is 2^31 - 1", max_items); return RT_ERR_UNSUPPORTED; }
-    UpdateTemps t;
-    RT_TRY(take_build_temps(ctx, n, t, [n, np, max_items](Carver &c, UpdateTemps &ut) { carve_update(c, n, np, max_items, ut); }));
-    RT_TRY(s->update_back.reserve(sizeof(uint32_t) * UPD_BACK_WORDS * (size_t)n));     // (for all of them at once: never grows again)
+    if (max_items > 0x7fffffffu) { rt_set_error("%s: %zu work items for the world boxes: the limit is 2^31 - 1", who, max_items); return RT_ERR_UNSUPPORTED; }
+    TlasTemps t;
+    RT_TRY(take_build_temps(ctx, n, t, [n, np, max_items](Carver &c, TlasTemps &tt) { carve_tlas(c, n, np, max_items, tt); }));
+    // for all n at once, whatever part is listed or visible: allocated by a build, never again by an update
+    RT_TRY(reserve_tlas_for(s->tlas, n));
+    RT_TRY(s->update_back.reserve(sizeof(uint32_t) * UPD_BACK_WORDS * (size_t)n));
     std::vector<uint32_t> back(UPD_BACK_WORDS * np);
-    ScopedEvent e0, e1;
-    HIP_TRY(hipEventCreate(&e0.e));
-    HIP_TRY(hipEventCreate(&e1.e));
-    if (!started) HIP_TRY(hipEventRecord(e0.e, st));
     InstanceRec *inst = s->d_inst.as<InstanceRec>();
     if (np) {                                          // (none: an update of masks alone)
-        HIP_TRY(hipMemcpyAsync(t.pend_idx, s->pending.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.pend_idx, list.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
         k_update_records<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->blas_bounds.as<float>(), t.pend_idx, t.pend_xf, (uint32_t)np, t.pend_enc,
                                                                        t.items, t.n_items, (uint32_t)max_items);
-        if (max_items) k_update_boxes<<<(uint32_t)max_items, BOUNDS_BLOCK, 0, st>>>(inst, t.pend_idx, t.pend_xf, t.items, t.n_items, t.pend_enc);
+        if (max_items) k_instance_boxes<<<(uint32_t)max_items, BOUNDS_BLOCK, 0, st>>>(inst, t.pend_idx, t.pend_xf, t.items, t.n_items, t.pend_enc);
         k_update_apply<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.pend_idx, (uint32_t)np, t.pend_enc, s->update_back.as<uint32_t>());
     }
     // the records are the full list's, hidden instances' included; the leaves are the visible ones' (all n when nothing is hidden)
     const uint32_t nv = s->n_vis;
-    if (nv < n)
-        k_visible_leaf_boxes<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->d_vis.as<uint32_t>(), nv, t.boxes);
-    else
-        k_update_leaf_boxes<<<grid_for(n, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.boxes, n);
-    // from here on: rt_build_tlas' own steps, into the buffers the scene has (the same sizes or smaller: nothing is allocated)
+    k_leaf_boxes<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, nv < n ? s->d_vis.as<uint32_t>() : nullptr, nv, t.boxes);
     k_init_bounds<<<1, 64, 0, st>>>(t.enc);
     k_box_bounds<<<grid_for(nv, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, nv, t.enc);
     k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
     RT_TRY(lbvh_from_boxes(ctx, s->tlas, nv, t));
     if (nv < n) RT_TRY(map_visible_leaves(ctx, s));
+    // the TLAS is walked in the same four-wide layout (a single instance: the root is the leaf of that instance)
     RT_TRY(rt_build_wide_from_lbvh(ctx, s->tlas, true, 1));
-    if (nv < n && nv == 1) s->tlas.root_code = ~(int)s->vis[0];
-    HIP_TRY(hipEventRecord(e1.e, st));
+    if (nv < n && nv == 1) s->tlas.root_code = ~(int)s->vis[0];       // (the one visible instance's own index)
+    if (queued) HIP_TRY(hipEventRecord(queued, st));
     // the final join: it brings back the rewritten records' heads with the TLAS' depth and bounds
     if (np) HIP_TRY(hipMemcpyAsync(back.data(), s->update_back.p, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     RT_TRY(lbvh_collect(ctx, s->tlas));
-    HIP_TRY(hipEventElapsedTime(&s->update_ms, started ? started : e0.e, e1.e));
-    for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[s->pending[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
-    // taken again over all models: a deformation changes depths and can create or remove split references
+    for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[list[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
+    // the scene's summary, taken again over all models: a deformation changes depths and can create or remove split references
     uint32_t deepest = 0, canon = s->tlas.max_depth;
     s->has_refs = false;
     for (uint32_t i = 0; i < n; i++) {
@@ -1234,11 +1062,36 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started)
         canon = b.max_depth > canon ? b.max_depth : canon;
         s->has_refs = s->has_refs || m->ref_off.p != nullptr;
     }
+    // a step leaves at most three siblings behind; two-level walks add the TLAS path and the sentinel that marks the
+    // bottom of a BLAS walk
     s->two_level = !(n == 1 && (s->h_inst[0].flags & RT_INST_IDENTITY));
     s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;
+    // the canonical traversal (parity / counting kernels and the deep-stack path of the fast one) keeps
+    // 128-entry private stacks per structure
     if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); return RT_ERR_UNSUPPORTED; }
     if (ctx->verbose)
-        fprintf(stderr, "[dxr_amd] TLAS update: %zu of %u instances, %u visible, depth %u; stack need %u; %s walk\n", np, n, nv, s->tlas.max_depth,
-                s->stack_need, s->two_level ? "two-level" : "single-level");
+        fprintf(stderr, "[dxr_amd] %s: TLAS update, %zu of %u instances, %u visible, depth %u; deepest BLAS layout depth %u (%s); stack need %u; %s walk\n",
+                who, np, n, nv, s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
     return RT_OK;
+}
+
+int rt_build_tlas(rt_context *ctx, rt_scene *s)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)s->inst.size();
+    s->h_inst.assign(n, InstanceRec());
+    s->h_blas_bounds.resize(6 * (size_t)n);            // (members: alive whenever the copies run)
+    std::vector<uint32_t> all(n);                      // (alive until rt_update_tlas has joined the stream)
+    for (uint32_t i = 0; i < n; i++) {
+        InstanceRec &r = s->h_inst[i];
+        write_model_part(r, &s->h_blas_bounds[6 * (size_t)i], model_desc(s->inst[i].model));
+        r.pad_ = 0;
+        r.material = i;
+        all[i] = i;
+    }
+    RT_TRY(s->d_inst.reserve(sizeof(InstanceRec) * (size_t)n));
+    RT_TRY(s->blas_bounds.reserve(6 * (size_t)n * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(s->d_inst.p, s->h_inst.data(), sizeof(InstanceRec) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->blas_bounds.p, s->h_blas_bounds.data(), 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    return rt_update_tlas(ctx, s, all, "rt_scene_build", nullptr);
 }

@@ -353,7 +353,7 @@ struct rt_scene {
     DevBuf blas_bounds;          // ... the box an instance set (back) to the identity takes (written by every build)
     std::vector<uint64_t> seen_geom;     // per instance: its model's geom_gen when the records were last written (build / update); another
                                          //   value now: the model's vertices changed since, the scene is STALE as with a pending transform
-    DevBuf update_back;          // the first 20 words (inv, world box, flags) of the records an update rewrote, on their way to h_inst
+    DevBuf update_back;          // the first 20 words (inv, world box, flags) of the records rt_update_tlas rewrote, on their way to h_inst
     float update_ms = 0.0f;
     // rt_scene_set_instance_mask(s): the InstanceMask byte of every instance (0xFF from rt_scene_add_model); every ray carries the reference's
     // inclusion mask 0xFF, so an instance is VISIBLE iff its byte is non-zero.  Masks never touch a record: the TLAS is the one of the visible
@@ -382,15 +382,17 @@ struct rt_scene {
 
 // rt_bvh_build.hip
 int rt_build_blas(rt_context *ctx, rt_model *m);
+// the build's share of the TLAS: the model part of every record and the per-instance BLAS boxes, written on the host and uploaded; then
+// rt_update_tlas with every instance listed
 int rt_build_tlas(rt_context *ctx, rt_scene *s);
-// after rt_build_tlas: the per-instance BLAS boxes rt_update_tlas reads on the device
-int rt_upload_blas_bounds(rt_context *ctx, rt_scene *s);
 // the visible sub-list from s->masks into s->vis / d_vis / n_vis, uploaded if it differs from the one the scene has (or `force`: a build,
 // whose TLAS buffers may be new); RT_ERR_STATE, and nothing changed, if no instance is visible
 int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool force);
-// applies s->pending to the instance records, their world boxes and the TLAS, on the device; `started`: an event the caller has recorded,
-// from which update_ms counts (nullptr: from here)
-int rt_update_tlas(rt_context *ctx, rt_scene *s, hipEvent_t started = nullptr);
+// THE TLAS path of a build (list: every instance, 0 .. n-1) and of an update (s->pending): rewrites the transform part of the listed
+// instances' records and their world boxes, rebuilds the TLAS over the visible instances and takes the scene's summary, on the device.
+// `who` names the caller in messages.  It creates no event and reads no time; `queued` (or nullptr) is the caller's event, which it records
+// behind the wide collapse, in front of the read-back: where update_ms ends
+int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &list, const char *who, hipEvent_t queued);
 // the model fields of the records of `changed` (instances whose model was rebuilt) and their rows of blas_bounds, on the device; h_inst follows
 int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &changed);
 

@@ -1,6 +1,7 @@
-// rt_xform.h -- the instance transform's arithmetic, ONE text for the host (rt_build_tlas) and the device (k_update_records of
-// rt_scene_update): both run the same operations in the same order, without contraction, so a record written by either is the same bits.
-// Plain C++ as well (no HIP header needed): tests/cpp/invert3x4_sanitized.cpp compiles it for the CPU under the sanitizers.
+// rt_xform.h -- the instance transform's arithmetic.  The library runs it on the device only: k_update_records (rt_bvh_build.hip) writes
+// the transform part of every instance record, for rt_scene_build and rt_scene_update alike.  The one host user of invert3x4 is
+// tests/cpp/invert3x4_sanitized.cpp, which compiles this header with g++ for the CPU under the sanitizers: it stays plain C++ (no HIP
+// header needed), the same operations in the same order, without contraction.
 #pragma once
 
 #if defined(__HIPCC__)

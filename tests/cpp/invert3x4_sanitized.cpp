@@ -1,4 +1,4 @@
-// The instance transform's shared host / device text (dxrexperiments_amd/csrc/rt_xform.h) as a CPU program of its own, for
+// The instance transform's text (dxrexperiments_amd/csrc/rt_xform.h: device code, kept host-compilable) as a CPU program of its own, for
 // g++ -fsanitize=address,undefined (tests/test_scene_update_abi.py): reads n x 12 floats, writes n x 13 -- the fp32 adjugate / determinant
 // inverse of every matrix and whether it is the identity.  Every matrix lives in a heap block of exactly twelve floats, so that a read or
 // write past either end is a report.

@@ -217,6 +217,55 @@ def test_set_and_build_equals_set_and_update(gpu, capi):
     a.close(); b.close()
 
 
+# ---- a fresh build is an update with every instance listed ---------------------------------------------------------------------------
+FRESH_PATTERNS = {                                      # which instances carry a transform (the others are identity instances)
+    "all_transformed": lambda n, k: True,
+    "all_identity": lambda n, k: False,                 # the work list stays empty while the world-box grid is not
+    "first_wave_identity": lambda n, k: k >= 64,        # a whole first wave of k_update_records without work items: its early return
+    "alternating": lambda n, k: k % 2 == 1,
+    "last_transformed": lambda n, k: k == n - 1,
+}
+
+
+def fresh_xforms(n, pattern):
+    xf = random_xforms(n, 41, spread=6.0)
+    return [xf[k] if FRESH_PATTERNS[pattern](n, k) else None for k in range(n)]
+
+
+FRESH_CASES = [(n, p, 0) for n in (63, 64, 65, 130) for p in FRESH_PATTERNS] + [(130, "first_wave_identity", 64)]
+
+
+@pytest.mark.parametrize("n,pattern,hidden", FRESH_CASES)
+def test_fresh_build_compacts_its_work_list(gpu, capi, oracle, n, pattern, hidden):
+    """no setter, no update: the build itself runs the compaction of k_update_records over all n instances -- one wave less one, one wave, one
+    wave and one, three waves -- under every identity pattern: bvh(-1) and every instance_info == the oracle's.  The last case hides the
+    identity wave 0..63 before the build: the TLAS, in the sub-list's numbering, == the oracle's scene of the visible instances 64..129 (as
+    test_gpu_instance_masks compares it); every record, the hidden ones' too, == the oracle's scene of the full list"""
+    xf = fresh_xforms(n, pattern)
+    what = "fresh build n=%d %s, %d hidden" % (n, pattern, hidden)
+    gm = gpu_models(capi, gpu)
+    sc = capi.Scene(gpu)
+    for k, x in enumerate(xf):
+        sc.add_model(gm[k % 2], x)
+    if hidden:
+        sc.set_masks(0, np.array([0] * hidden + [0xFF] * (n - hidden), np.uint8))
+    sc.build()
+    got = arrays(sc, n)
+    full = oracle_scene(oracle, xf)
+    if not hidden:
+        assert_equals_oracle(got, full, n, what)
+    else:
+        from test_gpu_instance_masks import unmapped    # (that module imports this one)
+        assert hidden % 2 == 0                          # (the sub-list keeps "instance k = mesh k % 2")
+        vis = list(range(hidden, n))
+        assert got["keys"].shape[0] == len(vis)
+        assert_equals_oracle(unmapped(got, vis), oracle_scene(oracle, xf[hidden:]), len(vis), what)
+        for k in range(n):
+            ob, oi = full.instance_info(k)
+            assert np.array_equal(got["invs"][k], oi, equal_nan=True) and np.array_equal(got["boxes"][k], ob, equal_nan=True), (what, k, got["boxes"][k], ob)
+    sc.close()
+
+
 # ---- traversal -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("family", ("mirror", "stretch", "far"))
 def test_traversal_after_an_update(gpu, capi, oracle, family):

@@ -1,5 +1,5 @@
 """CPU-only side of rigid animation (rt_scene_set_instance_transform(s), rt_scene_update, rt_scene_update_ms): the exports, their binding and
-their citations; and the instance transform's arithmetic, which host and device share as ONE text (dxrexperiments_amd/csrc/rt_xform.h),
+their citations; and the instance transform's arithmetic, the device's own text kept host-compilable (dxrexperiments_amd/csrc/rt_xform.h),
 as a stand-alone CPU program under AddressSanitizer + UndefinedBehaviorSanitizer: the hard families' matrices through invert3x4 give the
 oracle's inverses bit for bit, without a report.  (The GPU side: tests/test_gpu_scene_update.py.)"""
 import ctypes as C
