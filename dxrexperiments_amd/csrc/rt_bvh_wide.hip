@@ -20,7 +20,8 @@
 // (the likelier occluder first), closest-hit rays sort them by entry distance (rt_wide_step.h).
 //
 // Exactness: plane = fma(q, scale, origin) is evaluated here with the same expression the traversal uses; every lo
-// plane is stepped down and every hi plane up until the decoded box CONTAINS the child's true box.  The slab test is
+// plane is stepped down and every hi plane up until the decoded box CONTAINS the child's true box, and back in where a
+// nearer plane still does: the planes are the tightest the grid has ("Quantiser").  The slab test is
 // monotone under box inclusion (DESIGN.md "Exactness rule"), so culling against the decoded boxes never loses a
 // candidate the canonical definition accepts.  An axis that cannot be quantised at all (non-finite or overflowing
 // extents: huge instance boxes, NaN / inf vertices) gets an infinite scale and q = 0 planes: the decoded planes are
@@ -280,9 +281,32 @@ __device__ bool quantise_axis(const Box6 *cb, uint32_t valid, int axis, float or
             fl = fl > 0.0f ? (fl < 255.0f ? fl : 255.0f) : 0.0f;            // (NaN -> 0)
             fh = fh > 0.0f ? (fh < 255.0f ? fh : 255.0f) : 0.0f;
             ql = (int)fl; qh = (int)fh;
-            while (ql > 0 && __builtin_fmaf((float)ql, scale, origin) > l) ql--;
-            while (qh < 255 && __builtin_fmaf((float)qh, scale, origin) < h) qh++;
-            if (__builtin_fmaf((float)ql, scale, origin) > l || __builtin_fmaf((float)qh, scale, origin) < h) ok = false;
+            float pl = __builtin_fmaf((float)ql, scale, origin), ph = __builtin_fmaf((float)qh, scale, origin);
+            while (ql > 0 && pl > l) { ql--; pl = __builtin_fmaf((float)ql, scale, origin); }
+            while (qh < 255 && ph < h) { qh++; ph = __builtin_fmaf((float)qh, scale, origin); }
+            // ... and back in where that is tighter: l - origin and h - origin round, so floor / ceil can start one step further out than
+            // the grid needs (the quotient is off by far less than a step, so the exact floor / ceil is at most one step in, and the plane
+            // behind it may round onto l / h itself: two planes to look at).  A byte moves to the farther of them that still holds
+            // the child and decodes to a DIFFERENT float -- not through planes that decode to the same one (zero extents, grids finer
+            // than the floats far from the origin): those bytes are as tight as they get.  (One fma and a compare for nearly every
+            // plane: the next one in is almost always past the child.)
+            if (ql < 255) {
+                const float p1 = __builtin_fmaf((float)(ql + 1), scale, origin);
+                if (p1 <= l) {
+                    const float p2 = __builtin_fmaf((float)(ql + 2), scale, origin);
+                    if (ql + 2 <= 255 && p2 <= l && p2 > pl) { ql += 2; pl = p2; }
+                    else if (p1 > pl) { ql += 1; pl = p1; }
+                }
+            }
+            if (qh > 0) {
+                const float p1 = __builtin_fmaf((float)(qh - 1), scale, origin);
+                if (p1 >= h) {
+                    const float p2 = __builtin_fmaf((float)(qh - 2), scale, origin);
+                    if (qh - 2 >= 0 && p2 >= h && p2 < ph) { qh -= 2; ph = p2; }
+                    else if (p1 < ph) { qh -= 1; ph = p1; }
+                }
+            }
+            if (pl > l || ph < h) ok = false;
         }
         lo8 |= (unsigned long long)ql << (8 * k);
         hi8 |= (unsigned long long)qh << (8 * k);

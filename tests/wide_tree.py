@@ -1,5 +1,6 @@
 """Independent reader of the production traversal layout (rt_scene_wide_read): decodes the wide quantised nodes with
-numpy, checks the invariants the traversal relies on, and prices the tree with the surface-area heuristic.
+numpy, checks the invariants the traversal relies on and that every child box is as tight as its node's grid allows (check_tightness), and
+prices the tree with the surface-area heuristic.
 
 Nothing here is shared with the builder (rt_bvh_wide.hip) or the traversal (rt_trace_wave.h): the layout is taken from
 the comment in include/dxr_amd.h.  Used by tests/test_gpu_wide_tree.py and tools/tree_quality.py."""
@@ -66,8 +67,80 @@ def levels_of(code):
     return level, refs
 
 
-def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True):
-    """Invariants of a wide tree.  leaf_lo / leaf_hi: true bounds per record (BLAS) or per instance (TLAS).
+def grid_planes(origin, scale):
+    """every plane fma(q, scale, origin), q = 0..255, of m grids: float32[m, 256], non-decreasing in q (the product is exact)"""
+    q = np.arange(256, dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return (q[None, :] * scale[:, None] + origin[:, None]).astype(np.float32)
+
+
+def finest_scale(ext):
+    """the smallest power of two s >= 2^-126 with 255 s >= ext, for finite float32 extents; found with exact float64 products"""
+    ext = ext.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.where(ext > 0, np.ceil(np.log2(np.where(ext > 0, ext, 1.0) / 255.0)), -126.0)
+    e = np.clip(e, -126.0, 127.0)
+    for _ in range(2):                                  # log2 may be one off at a power of two: settle with exact products
+        e = np.where((e > -126) & (255.0 * np.exp2(e - 1) >= ext), e - 1, e)
+        e = np.where((e < 127) & (255.0 * np.exp2(e) < ext), e + 1, e)
+    return np.exp2(e).astype(np.float32)
+
+
+def check_tightness(nodes, d, used, tlo, thi, chunk=2048):
+    """Asserted for every used slot on every axis with a finite scale (tlo / thi: the true bounds of every child):
+      * the decoded lo plane EQUALS the largest plane of the node's grid, fma(q, scale, origin) with q in 0..255, that is <= the child's true
+        lo, and the decoded hi plane the smallest one that is >= its true hi.  In plane values, not bytes: far from the origin neighbouring
+        bytes decode to the same float, and either byte is as tight;
+      * the scale is the smallest power of two s >= 2^-126 with 255 s >= ext (ext = the node's hi - origin in fp32) whose last plane,
+        fma(255, s, origin), reaches the node's hi.  Rounding can leave the last plane of the grid 255 s >= ext short of hi by an ulp; only
+        then is the grid one power of two coarser.
+    Returns the number of (node, axis) pairs on such a coarser grid."""
+    n = nodes.shape[0]
+    origin = nodes.view(np.float32)[:, 0:3]
+    scale = d["scale"]
+    doubled_axes = 0
+    for at in range(0, n, chunk):
+        sl = slice(at, min(n, at + chunk))
+        for a in range(3):
+            s, o = scale[sl, a], origin[sl, a]
+            fin = np.isfinite(s)
+            u = used[sl] & fin[:, None]
+            planes = grid_planes(o, np.where(fin, s, np.float32(1.0)))
+            for name, true, got in (("lo", tlo[sl, :, a], d["lo"][sl, :, a]), ("hi", thi[sl, :, a], d["hi"][sl, :, a])):
+                with np.errstate(invalid="ignore"):
+                    if name == "lo":
+                        side = planes[:, None, :] <= true[:, :, None]
+                        best = np.where(side, planes[:, None, :], -np.inf).max(axis=2)
+                    else:
+                        side = planes[:, None, :] >= true[:, :, None]
+                        best = np.where(side, planes[:, None, :], np.inf).min(axis=2)
+                    bad = u & np.isfinite(true) & (got != best)
+                if bad.any():
+                    k, slot = [int(x[0]) for x in np.nonzero(bad)]
+                    raise AssertionError("node %d, slot %d, axis %d: the %s plane is %r, the grid has %r next to the child's %r" % (
+                        at + k, slot, a, name, float(got[k, slot]), float(best[k, slot]), float(true[k, slot])))
+            # the grid itself
+            with np.errstate(invalid="ignore", over="ignore"):
+                node_hi = np.where(used[sl], thi[sl, :, a], -np.inf).max(axis=1).astype(np.float32)
+                ext = (node_hi - o).astype(np.float32)
+                ok_ext = fin & np.isfinite(ext) & (ext < np.float32(3.0e38))
+                want = finest_scale(np.where(ok_ext, ext, np.float32(0.0)))
+                first = want.copy()
+                for _ in range(8):
+                    short = (want * np.float32(255.0) + o).astype(np.float32) < node_hi
+                    want = np.where(short, want * np.float32(2.0), want)
+                bad = ok_ext & (s != want)
+                doubled_axes += int((ok_ext & (want != first)).sum())
+            if bad.any():
+                k = int(np.nonzero(bad)[0][0])
+                raise AssertionError("node %d, axis %d: scale %r, the finest grid across the extent %r that reaches its end is %r" % (
+                    at + k, a, float(s[k]), float(ext[k]), float(want[k])))
+    return doubled_axes
+
+
+def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True, doubled=None):
+    """Invariants of a wide tree.  leaf_lo / leaf_hi: true bounds per record (BLAS) or per instance (TLAS).  doubled: if given, the exact
+    number of (node, axis) grids that are coarser than their extent asks for (check_tightness).
     Returns a dict of statistics (largest_leaf: the most records any one leaf holds); raises AssertionError with a description on the first violation."""
     n = nodes.shape[0]
     if root_code < 0:
@@ -139,11 +212,16 @@ def check(nodes, root_code, leaf_lo, leaf_hi, n_leaf_items, blas=True):
     sc = d["scale"]
     mant, _ = np.frexp(sc[np.isfinite(sc)])
     assert np.all(mant == 0.5), "a scale that is not a power of two"
-    return {"nodes": n, "levels": int(level.max()) + 1, "children_per_node": float(used.sum()) / n,
+    # tightness, whatever builder made the tree: on every finitely scaled axis each plane of a used slot is the nearest plane of the node's
+    # grid on the child's side of it, and the grid is the finest power-of-two grid that reaches across the node
+    doubled_axes = check_tightness(nodes, d, used, tlo, thi)
+    if doubled is not None:
+        assert doubled_axes == doubled, "%d axes on a grid coarser than 255 s >= extent asks for, %d expected" % (doubled_axes, doubled)
+    return {"nodes": n, "levels": int(level.max()) + 1, "children_per_node": float(used.sum()) / n, "doubled_axes": doubled_axes,
             "leaf_children": int(leaf.sum()), "largest_leaf": int((((~code[leaf]) & 7) + 1).max()) if blas else 1, "decoded": d, "true_lo": tlo, "true_hi": thi, "level": level}
 
 
-def check_blas(sc, which, v, i):
+def check_blas(sc, which, v, i, doubled=None):
     """The BLAS of instance `which`'s model (capi.Scene.wide_read) against the mesh (v, i) it was built from: the records are the
     triangles bit for bit, every triangle -- or every reference of a split one (rt_refs.h) -- once, then check().
     Returns (statistics, nodes, root_code)."""
@@ -167,7 +245,7 @@ def check_blas(sc, which, v, i):
             hi = np.where((mark == 1)[:, None], rec_boxes[:, 3:], hi)
     tri = v["position"][i[prim]]                           # the record of primitive p holds p's vertices, bit for bit
     assert np.array_equal(recs[:, :9].reshape(-1, 3, 3), tri)
-    st = check(nodes, root, lo, hi, recs.shape[0], blas=True)
+    st = check(nodes, root, lo, hi, recs.shape[0], blas=True, doubled=doubled)
     return st, nodes, root
 
 
