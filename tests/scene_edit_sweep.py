@@ -1,0 +1,1009 @@
+#!/usr/bin/env python3
+"""Randomised sweep over SEQUENCES of scene edits: "update == build"  applied to 30 - 60 interleaved operations instead of
+one.  tests/test_gpu_scene_edit_sweep.py runs a bounded number of sequences under `pytest -m gpu`; by hand, on a GPU box, for as long as wanted:
+
+    python tests/scene_edit_sweep.py [sequences] [seed]
+
+A sequence draws two or three small models (the box meshes of test_gpu_scene_update, deform_cases.grid_mesh(9), one triangle, a grid that
+deform_cases.slivers pushes into and out of split references, a skinned grid), one or two scenes (the second shares a model with the first in
+about half of the sequences), 1 (identity), 2, 3, 5, 13 or 66 instances, and then operations by weight: rigid transforms by either setter (random,
+the identity, util.HARD_FAMILIES), masks (another non-zero value, hide, show again, hide all), the four vertex setters on sub-ranges from host
+and device memory, recompute_normals, set_skin / clear_skin / set_bones, add_model, build, update, a redundant update, calls that must be
+refused, and -- while a scene is stale -- probes of the readers that must refuse it.  About a third of the sequences run on a context of their
+own under option_cases.draw options.
+
+Every operation goes to the GPU library and to the shadow model of tests/scene_edit_model.py, and the return codes must agree.  Every successful
+update or build is a CHECKPOINT: the scene is compared, bit for bit, with a fresh GPU scene built over fresh models made from the shadow model's
+vertices and with a fresh oracle scene -- the TLAS (under the index mapping of test_gpu_instance_masks when instances are hidden), every
+instance record, every BLAS with its wide nodes, records and split references, masks() and every model's geometry(), 1,500 rays through
+test_gpu_trace.compare_all -- and at every third checkpoint and the last one of the first scene one more accumulated frame of a long-lived
+progressive pipeline (shadow cache on, a point light with a free sphere) and one frame of a long-lived realtime pipeline, images and ray counts.
+
+The plan of a sequence is a pure function of (seed, sequence number): plan_sequence() draws it on the shadow model alone, so that
+tests/test_scene_edit_stream.py can say on the CPU what the GPU test's seeds cover.  On a mismatch run() returns the seed, the sequence number
+and the operation log up to that point; `python tests/scene_edit_sweep.py N SEED` replays it."""
+import os
+import sys
+import types
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+import option_cases  # noqa: E402
+import scene_edit_model as M  # noqa: E402
+import skin_cases  # noqa: E402
+from deform_cases import grid_mesh, slivers  # noqa: E402
+from dxrexperiments_amd import rtypes as T, scenes  # noqa: E402
+from util import HARD_FAMILIES, hard_xforms, random_xforms, triangle_soup, world_box_of_vertices  # noqa: E402
+
+W, H = 48, 32
+DEPTH = (2, 2)
+N_RAYS = 750                            # aimed + as many random ones: 1,500 per checkpoint
+COUNTS = (1, 2, 3, 5, 13, 66)
+KINDS = ("box0", "box1", "grid9", "tri", "sliver_grid", "skin_grid")
+N_BONES = 6
+CAMERA = np.array([0, 3, 24, 0, 0, 0, 0, 1, 0, 0.8, W / H], np.float32)
+SCENE_OPS = ("set_transform", "set_transforms", "set_mask", "set_masks", "add_model", "build", "update", "probe")
+REFUSABLE = ("set_transform", "set_transforms", "set_mask", "set_masks", "set_vertices", "set_positions", "set_skin", "set_bones", "update", "build")
+ALL_KINDS = SCENE_OPS + ("set_vertices", "set_positions", "recompute_normals", "set_skin", "clear_skin", "set_bones")
+SUBSETS = [frozenset(x) for x in (("transforms",), ("masks",), ("vertices",), ("transforms", "masks"), ("transforms", "vertices"), ("masks", "vertices"),
+                                  ("transforms", "masks", "vertices"))]
+
+
+# ---- the shadow model takes an operation ---------------------------------------------------------------------------------------------------
+def apply_to_model(world, op):
+    """-> (code, for update / build what was applied: None when refused, a frozenset of kinds otherwise)"""
+    k = op["op"]
+    if k in SCENE_OPS:
+        s = world.scenes[op["s"]]
+        if k == "set_transform":
+            return s.set_transform(op["i"], op["x"]), None
+        if k == "set_transforms":
+            return s.set_transforms(op["first"], op["xs"]), None
+        if k == "set_mask":
+            return s.set_mask(op["i"], op["mask"]), None
+        if k == "set_masks":
+            return s.set_masks(op["first"], op["masks"]), None
+        if k == "add_model":
+            return s.add_model(op["m"], op["x"]), None
+        if k == "probe":
+            return (M.ERR_STATE if not s.readable() else M.OK), None
+        return s.update() if k == "update" else s.build()
+    m = world.models[op["m"]]
+    if k == "set_vertices":
+        return m.set_vertices(op["first"], op["verts"]), None
+    if k == "set_positions":
+        return m.set_positions(op["first"], op["xyz"]), None
+    if k == "recompute_normals":
+        return m.recompute_normals(), None
+    if k == "set_skin":
+        return m.set_skin(op["bones"], op["weights"], op["n_bones"]), None
+    if k == "clear_skin":
+        return m.clear_skin(), None
+    if k == "set_bones":
+        return m.set_bones(op["palette"]), None
+    raise KeyError(k)
+
+
+def describe(n, op):
+    """one line of the operation log: no arrays, everything that replays the call by hand"""
+    parts = []
+    for key, v in op.items():
+        if key in ("op", "expect", "applied", "checkpoint", "frames", "mat"):
+            continue
+        if isinstance(v, np.ndarray):
+            v = "%s%s" % (v.dtype.names and "verts" or v.dtype, list(v.shape))
+        elif isinstance(v, list) and v and isinstance(v[0], np.ndarray):
+            v = "[%d transforms]" % len(v)
+        parts.append("%s=%s" % (key, v))
+    tail = "" if "applied" not in op else " applied %s" % (op["applied"],)
+    return "%3d: %-17s %s -> %d%s" % (n, op["op"], " ".join(parts), op["expect"], tail)
+
+
+# ---- the plan: a pure function of (seed, sequence number) ---------------------------------------------------------------------------------------
+def mesh_of(kind, r):
+    if kind in ("box0", "box1"):                       # test_gpu_scene_update.box_meshes: 4,200 and 4,095 vertex references
+        return triangle_soup(1400, seed=31, extent=2.0, size=0.3) if kind == "box0" else triangle_soup(1365, seed=32, extent=2.0, size=0.3)
+    if kind == "grid9":
+        return grid_mesh(9)
+    if kind == "tri":
+        return triangle_soup(1, seed=int(r.integers(1 << 30)), extent=1.0, size=0.5)
+    if kind == "sliver_grid":                          # test_gpu_model_deform.unsplit_grid: none of its triangles is split
+        return scenes.displaced_grid(28, seed=7, extent=2.0)
+    return grid_mesh(11)
+
+
+class Planner:
+    def __init__(self, seed, it):
+        self.r = np.random.default_rng([int(seed), 0x65646974, int(it)])
+        ro = np.random.default_rng([int(seed), 0x6F707473, int(it)])       # the options: a generator of their own, as fuzz_parity's
+        self.options = option_cases.draw(ro) if ro.random() < 1.0 / 3.0 else {}
+        self.world = M.World()
+        self.ops = []
+        r = self.r
+        n_models = int(r.integers(2, 4))
+        self.kinds = [KINDS[int(k)] for k in r.choice(len(KINDS), size=n_models, replace=False)]
+        self.base = []
+        for kind in self.kinds:
+            v, idx = mesh_of(kind, r)
+            self.base.append(v.copy())
+            self.world.add_model(v, idx)
+        self.slivered = {m: 0 for m, kind in enumerate(self.kinds) if kind == "sliver_grid"}
+        two = bool(r.random() < 0.5)
+        self.shared = two and bool(r.random() < 0.5)
+        self.scene_models = [list(range(n_models)) if not two or self.shared else list(range(n_models - 1))]
+        if two:
+            self.scene_models.append([n_models - 1, 0] if self.shared else [n_models - 1])
+        self.mats = []
+        self.initial = []                               # per scene: the instance list before the first build
+        for s, models in enumerate(self.scene_models):
+            self.world.add_scene()
+            n = int(COUNTS[int(r.integers(len(COUNTS)))]) if s == 0 else int((1, 2, 3, 5)[int(r.integers(4))])
+            xf = random_xforms(n, seed=int(r.integers(1 << 30)), spread=6.0)
+            inst = [(models[k % len(models)], None if n == 1 or (n == 13 and k == 12) else xf[k]) for k in range(n)]
+            for mi, x in inst:
+                self.world.scenes[s].add_model(mi, x)
+            self.initial.append(inst)
+            if s == 0:
+                self.mats = [self.material() for _ in inst]
+
+    # -- draws
+    def material(self):
+        r = self.r
+        m = T.default_material()
+        m["albedo"][:3] = r.uniform(0.1, 0.9, 3)
+        m["specular"][:3] = r.uniform(0.0, 1.0, 3)
+        m["roughness"] = r.uniform(0.1, 0.9)
+        m["reflectivity"] = r.uniform(0.0, 1.0)
+        m["type"] = int(r.integers(0, 3))
+        return m
+
+    def xform(self, identity=0.15):
+        r = self.r
+        u = r.random()
+        if u < identity:
+            return None
+        if u < identity + 0.10:
+            return hard_xforms(HARD_FAMILIES[int(r.integers(len(HARD_FAMILIES)))], 4, seed=int(r.integers(1 << 30)))[int(r.integers(4))]
+        return random_xforms(1, seed=int(r.integers(1 << 30)), spread=6.0)[0]
+
+    def mem(self):
+        return "device" if self.r.random() < 0.5 else "host"
+
+    def emit(self, **op):
+        before = self.world.snapshot()
+        code, applied = apply_to_model(self.world, op)
+        op["expect"] = code
+        if op["op"] in ("update", "build"):
+            op["applied"] = None if applied is None else sorted(applied)
+        if code != M.OK:
+            assert self.world.snapshot() == before                 # rule 10, of the model itself
+        self.ops.append(op)
+        return code
+
+    def scene(self):
+        return int(self.r.integers(len(self.world.scenes)))
+
+    def model(self, s=None):
+        if s is None:
+            return int(self.r.integers(len(self.world.models)))
+        used = sorted(set(mi for mi, _ in self.world.scenes[s].inst))
+        return used[int(self.r.integers(len(used)))]
+
+    def maybe_probe(self, s):
+        if self.world.scenes[s].state == M.STALE and self.r.random() < 0.2:
+            self.emit(op="probe", s=s)
+
+    # -- single operations
+    def op_transform(self, s=None, i=None):
+        s = self.scene() if s is None else s
+        n = len(self.world.scenes[s].inst)
+        i = int(self.r.integers(n)) if i is None else i
+        self.emit(op="set_transform", s=s, i=i, x=self.xform(0.4 if n == 1 else 0.15))
+        self.maybe_probe(s)
+
+    def op_transforms(self, s=None):
+        s = self.scene() if s is None else s
+        n = len(self.world.scenes[s].inst)
+        first = int(self.r.integers(n))
+        count = int(self.r.integers(1, min(n - first, 8) + 1))
+        self.emit(op="set_transforms", s=s, first=first, xs=[self.xform() for _ in range(count)])
+        self.maybe_probe(s)
+
+    def op_mask(self, s=None):
+        s = self.scene() if s is None else s
+        sc = self.world.scenes[s]
+        i = int(self.r.integers(len(sc.inst)))
+        u = self.r.random()
+        if sc.masks[i] == 0:
+            mask = 0 if u < 0.15 else int(self.r.integers(1, 256))         # shown again (or hidden once more: no flip)
+        else:
+            mask = 0 if u < 0.5 and len(sc.visible()) > 1 else int(self.r.integers(1, 256))     # hidden, or one non-zero value for another
+        self.emit(op="set_mask", s=s, i=i, mask=mask)
+        self.maybe_probe(s)
+
+    def op_masks(self, s=None):
+        s = self.scene() if s is None else s
+        sc = self.world.scenes[s]
+        n = len(sc.inst)
+        first = int(self.r.integers(n))
+        count = int(self.r.integers(1, min(n - first, 8) + 1))
+        u = self.r.random()
+        if u < 0.3:                                      # visibility as it is, other bytes
+            masks = [0 if sc.masks[first + k] == 0 else int(self.r.integers(1, 256)) for k in range(count)]
+        elif u < 0.5:
+            masks = [0xFF] * count
+        else:
+            masks = [0 if self.r.random() < 0.5 else int(self.r.integers(1, 256)) for _ in range(count)]
+        self.emit(op="set_masks", s=s, first=first, masks=masks)
+        self.maybe_probe(s)
+
+    def vertex_range(self, m):
+        nv = len(self.world.models[m].verts)
+        if self.r.random() < 0.15:
+            return 0, nv
+        first = int(self.r.integers(1, nv))             # first > 0
+        return first, int(self.r.integers(1, nv - first + 1))
+
+    def op_vertices(self, m=None, positions=None):
+        m = self.model() if m is None else m
+        positions = bool(self.r.random() < 0.5) if positions is None else positions
+        mo = self.world.models[m]
+        if m in self.slivered and self.r.random() < 0.7:                     # the whole grid into, further into or out of split references
+            self.slivered[m] = {0: 16, 16: 8 if self.r.random() < 0.4 else 0, 8: 0}[self.slivered[m]]
+            new = slivers(self.base[m], mo.idx, self.slivered[m]) if self.slivered[m] else self.base[m].copy()
+            first, count = 0, len(new)
+            part = new
+        else:
+            first, count = self.vertex_range(m)
+            part = mo.verts[first:first + count].copy()
+            part["position"] += self.r.uniform(-0.3, 0.3, (count, 3)).astype(np.float32)
+            part["normal"] = -part["normal"]
+        if positions:
+            self.emit(op="set_positions", m=m, first=first, xyz=np.ascontiguousarray(part["position"]), mem=self.mem())
+        else:
+            self.emit(op="set_vertices", m=m, first=first, verts=part, mem=self.mem())
+        for s in range(len(self.world.scenes)):
+            self.maybe_probe(s)
+
+    def op_normals(self):
+        self.emit(op="recompute_normals", m=self.model())
+
+    def skin_model(self):
+        c = [m for m, kind in enumerate(self.kinds) if kind in ("skin_grid", "grid9")]
+        return c[int(self.r.integers(len(c)))] if c else None
+
+    def op_set_skin(self, m=None):
+        m = self.skin_model() if m is None else m
+        if m is None:
+            return self.op_transform()
+        nv = len(self.world.models[m].verts)
+        k = int((1, 4, 8)[int(self.r.integers(3))])
+        seed = int(self.r.integers(1 << 30))
+        self.emit(op="set_skin", m=m, bones=skin_cases.random_bones(nv, k, N_BONES, seed), weights=skin_cases.random_weights(nv, k, seed + 1, "convex"), n_bones=N_BONES)
+
+    def op_clear_skin(self):
+        m = self.skin_model()
+        if m is None:
+            return self.op_mask()
+        self.emit(op="clear_skin", m=m)
+
+    def op_set_bones(self, m=None):
+        m = self.skin_model() if m is None else m
+        if m is None or self.world.models[m].skin is None:
+            return self.op_set_skin(m)
+        self.emit(op="set_bones", m=m, palette=skin_cases.gentle_palette(N_BONES, int(self.r.integers(1 << 30))), mem=self.mem())
+        for s in range(len(self.world.scenes)):
+            self.maybe_probe(s)
+
+    def op_update(self, s=None):
+        s = self.scene() if s is None else s
+        sc = self.world.scenes[s]
+        how = "build" if sc.state == M.UNBUILT else "update"
+        if not sc.visible():
+            self.emit(op=how, s=s)                      # refused (rule 12)
+            self.emit(op="set_mask", s=s, i=int(self.r.integers(len(sc.inst))), mask=0xFF)
+        return self.emit(op=how, s=s)
+
+    def op_update_twice(self):
+        s = self.scene()
+        self.op_update(s)
+        self.emit(op="update", s=s)                     # nothing pending: rule 11
+
+    def op_build(self):
+        s = self.scene()
+        if self.world.scenes[s].visible():
+            self.emit(op="build", s=s)
+
+    def op_add_model(self):
+        """rare: an instance more, setters while the scene is not updatable (they only store), the refused update, the build"""
+        s = self.scene()
+        sc = self.world.scenes[s]
+        if len(sc.inst) >= 70:
+            return
+        mat = self.material() if s == 0 else None
+        self.emit(op="add_model", s=s, m=self.model(s), x=self.xform(), mat=mat)
+        self.op_transform(s)
+        self.op_mask(s)
+        if self.r.random() < 0.5:
+            self.op_vertices(self.model(s))
+        self.emit(op="update", s=s)                     # refused (rule 1)
+        if not sc.visible():
+            self.emit(op="build", s=s)                  # refused (rule 12)
+            self.emit(op="set_mask", s=s, i=0, mask=0x10)
+        self.emit(op="build", s=s)
+
+    def op_empty(self):
+        """count == 0: rule 6, also at first == n"""
+        s, m = self.scene(), self.model()
+        n, nv = len(self.world.scenes[s].inst), len(self.world.models[m].verts)
+        u = int(self.r.integers(4))
+        if u == 0:
+            self.emit(op="set_transforms", s=s, first=int(self.r.choice([0, n])), xs=[])
+        elif u == 1:
+            self.emit(op="set_masks", s=s, first=int(self.r.choice([0, n])), masks=[])
+        elif u == 2:
+            self.emit(op="set_vertices", m=m, first=int(self.r.choice([0, nv])), verts=np.zeros(0, M.VERTEX), mem=self.mem())
+        else:
+            self.emit(op="set_positions", m=m, first=int(self.r.choice([0, nv])), xyz=np.zeros((0, 3), np.float32), mem=self.mem())
+
+    def op_refused(self):
+        s, m = self.scene(), self.model()
+        n, mo = len(self.world.scenes[s].inst), self.world.models[m]
+        nv = len(mo.verts)
+        u = int(self.r.integers(8))
+        if u == 0:
+            self.emit(op="set_transform", s=s, i=n, x=self.xform())
+        elif u == 1:
+            self.emit(op="set_transforms", s=s, first=n - 1, xs=[self.xform(), self.xform()])
+        elif u == 2:
+            self.emit(op="set_mask", s=s, i=n + 3, mask=0)
+        elif u == 3:
+            self.emit(op="set_masks", s=s, first=n, masks=[0])
+        elif u == 4:
+            self.emit(op="set_vertices", m=m, first=nv, verts=mo.verts[:1].copy(), mem=self.mem())
+        elif u == 5:
+            self.emit(op="set_positions", m=m, first=nv - 1, xyz=np.zeros((2, 3), np.float32), mem=self.mem())
+        elif u == 6:
+            c = [k for k, x in enumerate(self.world.models) if x.skin is None]
+            if c:
+                self.emit(op="set_bones", m=c[int(self.r.integers(len(c)))], palette=skin_cases.identity_palette(N_BONES), mem="host")
+        else:                                           # a bone index out of range, or nine influences: the old skin stays (rule 9)
+            k = 9 if self.r.random() < 0.5 else 2
+            bones = np.zeros((nv, k), np.uint32)
+            if k == 2:
+                bones[nv - 1, 1] = N_BONES
+            self.emit(op="set_skin", m=m, bones=bones, weights=np.ones((nv, k), np.float32), n_bones=N_BONES)
+
+    # -- motifs: short scripted runs, for what single draws meet too rarely
+    def motif_hide_all(self):
+        """every mask zero with transforms and vertices pending: the update is refused and keeps them; one instance shown; all of it applied"""
+        s = self.scene()
+        sc = self.world.scenes[s]
+        if sc.state == M.UNBUILT:
+            return self.op_update(s)
+        self.op_transform(s)
+        self.op_vertices(self.model(s))
+        self.emit(op="set_masks", s=s, first=0, masks=[0] * len(sc.inst))
+        self.emit(op="update", s=s)
+        u = self.r.random()
+        if u < 0.5:
+            self.emit(op="update", s=s)                 # refused again: the first refusal dropped nothing
+        elif u < 0.75:
+            self.emit(op="build", s=s)
+        self.emit(op="probe", s=s)
+        self.emit(op="set_mask", s=s, i=int(self.r.integers(len(sc.inst))), mask=int(self.r.integers(1, 256)))
+        self.emit(op="update", s=s)
+        self.emit(op="set_masks", s=s, first=0, masks=[0xFF] * len(sc.inst))
+        self.emit(op="update", s=s)
+
+    def motif_hide_show(self):
+        s = self.scene()
+        sc = self.world.scenes[s]
+        vis = sc.visible()
+        if len(vis) < 2:
+            return self.op_mask(s)
+        i = vis[int(self.r.integers(len(vis)))]
+        self.emit(op="set_mask", s=s, i=i, mask=0)
+        self.emit(op="set_mask", s=s, i=i, mask=int(self.r.integers(1, 256)))
+        self.op_update(s)
+
+    def motif_set_twice(self):
+        s = self.scene()
+        i = int(self.r.integers(len(self.world.scenes[s].inst)))
+        self.op_transform(s, i)
+        self.op_transform(s, i)
+        if self.r.random() < 0.5:                       # ... an instance that is pending and also of a changed model
+            self.op_vertices(self.world.scenes[s].inst[i][0])
+        self.op_update(s)
+        self.op_transform(s, i)                         # set, applied and set again
+        self.op_update(s)
+
+    def motif_one_visible(self):
+        s = self.scene()
+        sc = self.world.scenes[s]
+        n = len(sc.inst)
+        if n < 2 or sc.state == M.UNBUILT:
+            return self.op_masks(s)
+        keep = int(self.r.integers(n))
+        self.emit(op="set_masks", s=s, first=0, masks=[0xFF if k == keep else 0 for k in range(n)])
+        self.op_update(s)
+        self.emit(op="set_masks", s=s, first=0, masks=[0xFF] * n)
+        self.op_update(s)
+
+    def motif_single(self):
+        """a single identity instance to transformed and back: between the single-level and the two-level scene"""
+        c = [s for s, sc in enumerate(self.world.scenes) if len(sc.inst) == 1]
+        if not c:
+            return self.op_transforms()
+        s = c[int(self.r.integers(len(c)))]
+        if self.world.scenes[s].inst[0][1] is None:
+            self.emit(op="set_transform", s=s, i=0, x=self.xform(0.0))
+            self.op_update(s)
+        self.emit(op="set_transform", s=s, i=0, x=None)
+        self.op_update(s)
+        self.emit(op="set_transform", s=s, i=0, x=self.xform(0.0))
+        self.op_update(s)
+
+    def motif_shared(self):
+        """the shared model changes; the two scenes come back in either order, by update or build"""
+        if not self.shared:
+            return self.op_vertices()
+        for s in (0, 1):
+            if self.world.scenes[s].state != M.FRESH:
+                self.op_update(s)
+        self.op_vertices(0)
+        for s in (0, 1):                                # both scenes are stale, whichever the model marked first
+            if self.world.scenes[s].state == M.STALE:
+                self.emit(op="probe", s=s)
+        order = (0, 1) if self.r.random() < 0.5 else (1, 0)
+        by_build = int(self.r.integers(3))              # 2: neither
+        for k, s in enumerate(order):
+            if k == by_build and self.world.scenes[s].visible():
+                self.emit(op="build", s=s)
+            else:
+                self.op_update(s)
+
+    def motif_skin_rest(self):
+        """set_skin, then set_vertices / set_positions (the current vertices, not the rest pose), then set_bones from the rest pose"""
+        m = self.skin_model()
+        if m is None:
+            return self.op_vertices()
+        self.op_set_skin(m)
+        self.op_vertices(m, positions=False)
+        if self.r.random() < 0.5:
+            self.op_update()
+        self.op_set_bones(m)
+        self.op_update()
+
+    def motif_combo(self):
+        """one update that applies a drawn subset of {transforms, masks, vertices}"""
+        s = self.scene()
+        sc = self.world.scenes[s]
+        if sc.state != M.FRESH:
+            self.op_update(s)
+        want = SUBSETS[int(self.r.integers(len(SUBSETS)))]
+        if len(sc.inst) < 2 and "masks" in want:
+            want = want - {"masks"} or frozenset(["transforms"])
+        if "transforms" in want:
+            self.op_transform(s)
+        if "vertices" in want:
+            self.op_vertices(self.model(s))
+        if "masks" in want:
+            vis = sc.visible()
+            hidden = [k for k in range(len(sc.inst)) if k not in vis]
+            if hidden and (len(vis) < 2 or self.r.random() < 0.5):
+                self.emit(op="set_mask", s=s, i=hidden[int(self.r.integers(len(hidden)))], mask=0xFF)
+            else:
+                self.emit(op="set_mask", s=s, i=vis[int(self.r.integers(len(vis)))], mask=0)
+        self.op_update(s)
+
+    TABLE = (("op_transform", 12), ("op_transforms", 7), ("op_mask", 8), ("op_masks", 6), ("op_vertices", 12), ("op_normals", 3), ("op_set_skin", 2),
+             ("op_clear_skin", 2), ("op_set_bones", 6), ("op_add_model", 1.5), ("op_build", 2), ("op_update", 12), ("op_update_twice", 3), ("op_refused", 9),
+             ("op_empty", 3), ("motif_hide_all", 2), ("motif_hide_show", 2), ("motif_set_twice", 2), ("motif_one_visible", 2), ("motif_single", 2),
+             ("motif_shared", 5), ("motif_skin_rest", 3), ("motif_combo", 5))
+
+    def plan(self):
+        r = self.r
+        for m, kind in enumerate(self.kinds):           # the skinned grid has its skin before the first build
+            if kind == "skin_grid":
+                self.op_set_skin(m)
+        for s in range(len(self.world.scenes)):
+            self.emit(op="build", s=s)
+        target = int(r.integers(30, 61))
+        names = [n for n, _ in self.TABLE]
+        weights = np.array([w for _, w in self.TABLE], np.float64)
+        weights /= weights.sum()
+        while len(self.ops) < target:
+            getattr(self, names[int(r.choice(len(names), p=weights))])()
+        for s, sc in enumerate(self.world.scenes):      # every scene ends fresh: the last checkpoint
+            if sc.state != M.FRESH:
+                self.op_update(s)
+        c = 0
+        last = max(n for n, op in enumerate(self.ops) if op["op"] in ("update", "build") and op["s"] == 0 and op["expect"] == M.OK)
+        for n, op in enumerate(self.ops):
+            op["checkpoint"] = op["op"] in ("update", "build") and op["expect"] == M.OK
+            op["frames"] = False
+            if op["checkpoint"] and op["s"] == 0:
+                op["frames"] = c % 3 == 0 or n == last
+                c += 1
+        # the point light of the frames: above every world box of the first scene as it starts, so that it has a free sphere to lose
+        top = max(float(world_box_of_vertices(self.base[mi], self.world.models[mi].idx, T.IDENTITY_3X4 if x is None else x)[4]) for mi, x in self.initial[0])
+        return types.SimpleNamespace(light=(1.0, top + 3.0, 4.0), ops=self.ops, kinds=self.kinds, options=self.options, shared=self.shared, mats=self.mats, initial=self.initial,
+                                     meshes=[(b, m.idx) for b, m in zip(self.base, self.world.models)])
+
+
+def plan_sequence(seed, it):
+    return Planner(seed, it).plan()
+
+
+def fresh_world(plan):
+    """the shadow model as it is before the plan's first operation"""
+    w = M.World()
+    for v, idx in plan.meshes:
+        w.add_model(v, idx)
+    for inst in plan.initial:
+        s = w.add_scene()
+        for mi, x in inst:
+            w.scenes[s].add_model(mi, x)
+    return w
+
+
+# ---- what a plan covers (tests/test_scene_edit_stream.py asserts the list over the GPU test's seeds) -------------------------------------------
+def events_of(plan):
+    """the set of things that happen in the plan, read off a replay on the shadow model"""
+    ev = set()
+    w = fresh_world(plan)
+    ns = len(w.scenes)
+    hidden_since = [set() for _ in range(ns)]           # instances hidden since the scene's last update / build
+    sets_since = [{} for _ in range(ns)]                # instance -> transform sets since then
+    was_built = [False] * ns
+    hide_all_refused = [False] * ns
+    skin_step = {}                                      # model -> 1: set_skin seen, 2: a vertex setter after it
+    waiting = {}                                        # shared model id -> (the scene that came back first, how)
+    slivers_on = set()
+    for op in plan.ops:
+        k = op["op"]
+        ok = op["expect"] == M.OK
+        if k != "probe":
+            ev.add(("ok" if ok else "refused", k))
+        sc = w.scenes[op["s"]] if k in SCENE_OPS else None
+        s = op.get("s")
+        if k in ("update", "build"):
+            before_vis = sc.applied_vis
+            pend_models = set(sc.pending_models)
+            pend_x = set(sc.pending_xforms)
+            kinds = sc.pending()
+            if not ok and sc.state != M.UNBUILT and not sc.visible() and {"transforms", "vertices"} <= kinds:
+                hide_all_refused[s] = True
+            if ok:
+                if k == "update":
+                    ev.add(("update applies", frozenset(op["applied"])) if op["applied"] else "no-op update")
+                    if hide_all_refused[s]:
+                        ev.add("all hidden refused with transforms and vertices pending, then applied")
+                    if any(c >= 2 for c in sets_since[s].values()):
+                        ev.add("one instance set twice before one update")
+                    if any(id(w.models[sc.inst[i][0]]) in pend_models for i in pend_x):
+                        ev.add("an instance pending and of a changed model")
+                hide_all_refused[s] = False
+                for mid in pend_models:
+                    other = [t for t in range(ns) if t != s and mid in w.scenes[t].pending_models]
+                    if other:
+                        waiting[mid] = (s, k)
+                    elif mid in waiting:
+                        first, how = waiting.pop(mid)
+                        if how == k == "update":
+                            ev.add("shared model: scene %d updated before scene %d" % (first, s))
+                        elif {how, k} == {"update", "build"}:
+                            ev.add("shared model: one scene back by build, the other by update")
+        code, _ = apply_to_model(w, op)
+        assert code == op["expect"]
+        if k in ("update", "build") and ok:
+            hidden_since[s], sets_since[s] = set(), {}
+            was_built[s] = True
+            if before_vis is not None:
+                if len(before_vis) > 1 and len(sc.applied_vis) == 1:
+                    ev.add("the visible count goes to 1")
+                if len(before_vis) == 1 and len(sc.applied_vis) > 1:
+                    ev.add("the visible count comes back from 1")
+            for m in plan_sliver_models(plan):         # (a checkpoint sees the references of the models its scene holds)
+                if any(mi == m for mi, _ in sc.inst) and plan.options.get("split_refs", 1) != 0:
+                    if sliver_state(w.models[m], plan.meshes[m][0]):
+                        slivers_on.add(m)
+                    elif m in slivers_on:
+                        slivers_on.discard(m)
+                        ev.add("split references come and go")
+        if not ok:
+            continue
+        if k in ("set_mask", "set_masks"):
+            first = op["i"] if k == "set_mask" else op["first"]
+            masks = [op["mask"]] if k == "set_mask" else op["masks"]
+            for j, mk in enumerate(masks):
+                if mk == 0:
+                    hidden_since[s].add(first + j)
+                elif first + j in hidden_since[s] and sc.state == M.STALE:
+                    ev.add("hidden and shown again with no update in between")
+        if k in ("set_transform", "set_transforms") and sc.state != M.UNBUILT:
+            first = op["i"] if k == "set_transform" else op["first"]
+            for j in range(1 if k == "set_transform" else len(op["xs"])):
+                sets_since[s][first + j] = sets_since[s].get(first + j, 0) + 1
+        if k in ("set_transform", "set_transforms", "set_mask", "set_masks") and sc.state == M.UNBUILT and was_built[s] and (k in ("set_transform", "set_mask") or len(op.get("xs", op.get("masks")))):
+            ev.add("a setter between add_model and build")
+        if k == "set_skin":
+            skin_step[op["m"]] = 1
+        elif k in ("set_vertices", "set_positions") and skin_step.get(op["m"]) == 1 and len(op.get("verts", op.get("xyz"))):
+            skin_step[op["m"]] = 2
+        elif k == "set_bones" and skin_step.get(op["m"]) == 2:
+            ev.add("set_vertices after set_skin, then set_bones")
+            skin_step[op["m"]] = 1
+        elif k == "clear_skin":
+            skin_step.pop(op["m"], None)
+    ev |= single_instance_events(plan)
+    return ev
+
+
+def plan_sliver_models(plan):
+    return [m for m, kind in enumerate(plan.kinds) if kind == "sliver_grid"]
+
+
+def sliver_state(model, base):
+    """True: some triangle's first corner stands (20, 17, 13) away from the base grid (deform_cases.slivers); False: none does"""
+    d = model.verts["position"] - base["position"]
+    return bool((np.abs(d).max(axis=1) > 10.0).any())
+
+
+def single_instance_events(plan):
+    """a scene of one instance: the transform each successful update / build reads, identity or not"""
+    ev = set()
+    w = fresh_world(plan)
+    last = {}
+    for op in plan.ops:
+        apply_to_model(w, op)
+        if op["op"] in ("update", "build") and op["expect"] == M.OK and len(w.scenes[op["s"]].inst) == 1:
+            now = w.scenes[op["s"]].inst[0][1] is None
+            if op["s"] in last and last[op["s"]] != now:
+                ev.add("a single instance back to the identity" if now else "a single identity instance transformed")
+            last[op["s"]] = now
+    return ev
+
+
+def required_events():
+    out = {("ok", k) for k in ALL_KINDS if k != "probe"} | {("refused", k) for k in REFUSABLE} | {("update applies", sub) for sub in SUBSETS}
+    return out | {"no-op update", "all hidden refused with transforms and vertices pending, then applied", "hidden and shown again with no update in between",
+                  "one instance set twice before one update", "an instance pending and of a changed model", "shared model: scene 0 updated before scene 1",
+                  "shared model: scene 1 updated before scene 0", "shared model: one scene back by build, the other by update", "the visible count goes to 1",
+                  "the visible count comes back from 1", "a single identity instance transformed", "a single instance back to the identity",
+                  "a setter between add_model and build", "set_vertices after set_skin, then set_bones", "split references come and go"}
+
+
+# ---- the GPU side -------------------------------------------------------------------------------------------------------------------------
+class GpuBackend:
+    """issues a plan's operations to the library and compares the scene at the checkpoints.  Everything a checkpoint needs from the existing
+    tests is imported here, so that the plan and its coverage can be looked at without a GPU."""
+
+    def __init__(self, capi, oracle, ctx, plan, tally):
+        import s2_truth
+        import test_gpu_instance_masks as masks_t
+        import test_gpu_model_deform as deform_t
+        import test_gpu_scene_update as update_t
+        from test_gpu_pipeline import make_oracle_scene
+        from test_gpu_trace import compare_all
+        self.capi, self.oracle, self.ctx, self.plan, self.tally = capi, oracle, ctx, plan, tally
+        self.S, self.masks_t, self.deform_t, self.update_t, self.make_oracle_scene, self.compare_all = s2_truth, masks_t, deform_t, update_t, make_oracle_scene, compare_all
+        self.models = [capi.Model(ctx, v, i) for v, i in plan.meshes]
+        self.scenes = []
+        for inst in plan.initial:
+            sc = capi.Scene(ctx)
+            for mi, x in inst:
+                sc.add_model(self.models[mi], x)
+            self.scenes.append(sc)
+        self.mats = list(plan.mats)
+        self.pipes = None               # (progressive, realtime), made at the first checkpoint of scene 0
+        self.acc = np.zeros((H, W, 4), np.float32)
+        self.frame = 0
+        self.work = None                # count_work() of the last progressive frame while no real update has followed it
+        self.had_refs = set()
+        self.env = scenes.sky_cubemap(8)
+        self.hosts = (capi.ProgressiveHost(77), capi.ProgressiveHost(78))
+
+    def close(self):
+        for p in self.pipes or ():
+            p.close()
+        for sc in self.scenes:
+            sc.close()
+        for m in self.models:
+            m.close()
+
+    def count(self, key):
+        self.tally[key] = self.tally.get(key, 0) + 1
+
+    def device(self, array, call):
+        buf = self.ctx.upload(np.ascontiguousarray(array))
+        try:
+            call(buf.ptr)
+            self.ctx.synchronize()
+        finally:
+            buf.close()
+
+    def issue(self, op):
+        k = op["op"]
+        if k in SCENE_OPS:
+            sc = self.scenes[op["s"]]
+            if k == "set_transform":
+                sc.set_transform(op["i"], op["x"])
+            elif k == "set_transforms":
+                sc.set_transforms(op["first"], op["xs"])
+            elif k == "set_mask":
+                sc.set_mask(op["i"], op["mask"])
+            elif k == "set_masks":
+                sc.set_masks(op["first"], op["masks"])
+            elif k == "add_model":
+                if op["s"] == 0:                        # materials go by instance index
+                    self.mats.append(op["mat"])
+                    for p in self.pipes or ():
+                        p.add_material(op["mat"])
+                sc.add_model(self.models[op["m"]], op["x"])
+            elif k == "build":
+                sc.build()
+            elif k == "update":
+                sc.update()
+            return
+        m = self.models[op["m"]]
+        dev = op.get("mem") == "device"
+        if k == "set_vertices":
+            if dev and len(op["verts"]):
+                self.device(op["verts"], lambda ptr: m.set_vertices_device(ptr, len(op["verts"]), op["first"]))
+            elif dev:
+                m.set_vertices_device(0, 0, op["first"])
+            else:
+                m.set_vertices(op["verts"], op["first"])
+        elif k == "set_positions":
+            if dev and len(op["xyz"]):
+                self.device(op["xyz"], lambda ptr: m.set_positions_device(ptr, len(op["xyz"]), op["first"]))
+            elif dev:
+                m.set_positions_device(0, 0, op["first"])
+            else:
+                m.set_positions(op["xyz"], op["first"])
+        elif k == "recompute_normals":
+            m.recompute_normals()
+        elif k == "set_skin":
+            m.set_skin(op["bones"], op["weights"], op["n_bones"])
+        elif k == "clear_skin":
+            m.clear_skin()
+        elif k == "set_bones":
+            if dev:
+                self.device(op["palette"], m.set_bones_device)
+            else:
+                m.set_bones(op["palette"])
+
+    def do(self, op):
+        """-> the return code of the call"""
+        if op["op"] == "probe":
+            return self.probe(op["s"])
+        try:
+            self.issue(op)
+            code = M.OK
+        except self.capi.RtError as e:
+            code = e.code
+        if op["op"] in ("update", "build", "add_model") and op["s"] == 0 and self.pipes and code == M.OK:
+            self.rule_11(op)
+        return code
+
+    def rule_11(self, op):
+        """a no-op update leaves count_work() answering what it answered; a real change of scene 0 makes it refuse until the next render"""
+        p = self.pipes[0]
+        if op["op"] == "update" and op["applied"] == []:
+            if self.work is not None:
+                assert p.count_work() == self.work, "count_work() after an update with nothing pending"
+                self.count("count_work after a no-op update")
+            return
+        self.work = None
+        try:
+            p.count_work()
+        except self.capi.RtError as e:
+            assert e.code == M.ERR_STATE
+            self.count("count_work refused after a real update")
+            return
+        raise AssertionError("count_work() answers after %s changed the scene and before a render" % op["op"])
+
+    def probe(self, s):
+        """rule 13: every reader refuses a stale scene"""
+        sc = self.scenes[s]
+        O = np.zeros((4, 4), np.float32)
+        D = np.zeros((4, 4), np.float32)
+        D[:, 2] = 1
+        D[:, 3] = 1e30
+        calls = [lambda: sc.bvh(-1), lambda: sc.wide_read(-1), lambda: sc.instance_info(0), lambda: sc.bvh(0), lambda: sc.wide_read(0), lambda: sc.refs(0),
+                 lambda: sc.trace(O, D), lambda: sc.trace(O, D, canonical=True)]
+        if s == 0 and self.pipes:
+            calls += [self.pipes[0].render, self.pipes[1].render]
+        self.count("probes")
+        code = M.ERR_STATE
+        for call in calls:              # (the scene's own arrays first, and no further than the first call that answers: nothing walks a half-applied state)
+            try:
+                call()
+                return M.OK
+            except self.capi.RtError as e:
+                code = e.code if e.code != M.ERR_STATE else code
+        return code
+
+    def checkpoint(self, n, op, world):
+        s = op["s"]
+        sc, ms = self.scenes[s], world.scenes[s]
+        what = "op %d (%s of scene %d)" % (n, op["op"], s)
+        inst, vis = list(ms.inst), ms.visible()
+        sub = [inst[k] for k in vis]
+        meshes = [(m.verts.copy(), m.idx) for m in world.models]
+        D = self.deform_t
+        # readers: masks() and every model's geometry(), whichever scene holds it
+        assert np.array_equal(sc.masks(), np.array(ms.masks, np.uint8)), "%s: masks()" % what
+        for mi, gm in enumerate(self.models):
+            assert gm.geometry()[0].tobytes() == meshes[mi][0].tobytes(), "%s: geometry() of model %d" % (what, mi)
+        # TLAS, instance records, BLAS: a fresh scene of the full list over fresh models, the oracle over the visible sub-list
+        got = D.all_arrays(sc, self.models, inst)
+        fresh, fm = D.own_scene(self.capi, self.ctx, meshes, inst)
+        try:
+            want = D.all_arrays(fresh, fm, inst)
+            osc = self.make_oracle_scene(self.oracle, meshes, sub)
+            if len(vis) == len(inst):
+                self.update_t.assert_bytes_equal(got, want, what + " vs a fresh GPU build over fresh models")
+                self.update_t.assert_equals_oracle(got, osc, len(inst), what)
+            else:
+                tlas = ("nodes", "keys", "parents", "depth", "wide", "root", "counts")
+                self.update_t.assert_bytes_equal({k: v for k, v in got.items() if k not in tlas}, {k: v for k, v in want.items() if k not in tlas},
+                                                 what + " vs a fresh GPU build of the full list over fresh models")
+                back = self.masks_t.unmapped(got, vis)
+                fsub = self.masks_t.scene_of(self.capi, self.ctx, fm, sub)
+                self.update_t.assert_bytes_equal(back, self.update_t.arrays(fsub, len(vis)), what + " vs a fresh GPU build of the visible sub-list")
+                fsub.close()
+                self.update_t.assert_equals_oracle(back, osc, len(vis), what)
+                self.count("checkpoints with hidden instances")
+            D.assert_blas_equals_oracle(got, osc, meshes, sub, what)
+        finally:
+            D.close_all(fresh, fm)
+        refs = {mi for mi in set(m for m, _ in inst) if got["model%d.ref_off" % mi] is not None}
+        if refs:
+            self.count("checkpoints with split references")
+        if (self.had_refs & set(m for m, _ in inst)) - refs:
+            self.count("checkpoints where split references are gone again")
+        self.had_refs = (self.had_refs - set(m for m, _ in inst)) | refs
+        # rays: closest, closest + cull, any-hit; production and canonical walk
+        sets = self.S.ray_sets(meshes, sub, None, N_RAYS, 1000 + n)
+        O = np.concatenate([sets["aimed"][0], sets["random"][0]])
+        Dr = np.concatenate([sets["aimed"][1], sets["random"][1]])
+        self.compare_all(types.SimpleNamespace(g=sc, o=self.masks_t.MappedOracle(osc, vis)), O, Dr, brute=False)
+        self.count("checkpoints")
+        if op["frames"]:
+            self.frames(what, osc, vis)
+
+    def frames(self, what, osc, vis):
+        capi = self.capi
+        if self.pipes is None:
+            pipes = []
+            for kind in (capi.PIPELINE_PROGRESSIVE, capi.PIPELINE_REALTIME):
+                p = capi.Pipeline(self.ctx, kind)
+                p.set_scene(self.scenes[0])
+                for m in self.mats:
+                    p.add_material(m)
+                p.set_environment_cube(self.env)
+                p.create_output(W, H)
+                p.set_depth_limits(*DEPTH)
+                pipes.append(p)
+            pipes[0].set_shadow_cache(16)
+            self.pipes = tuple(pipes)
+        first = self.frame == 0
+        self.frame += 1
+        omats = np.stack([self.mats[k] for k in vis])
+        p, rt = self.pipes
+        pfc = self.hosts[0].update(CAMERA, 0.0, self.frame, W, H)
+        pfc["pointLight"]["worldPos"][:3] = self.plan.light
+        p.update(pfc)
+        p.render()
+        self.acc, ost = osc.render(omats, pfc, W, H, accum=self.acc, env_faces=self.env, max_radiance_depth=DEPTH[0], max_shadow_depth=DEPTH[1], nthreads=8)
+        got = p.read_output()
+        assert np.array_equal(got, self.acc), "%s: progressive frame %d: %d pixels differ" % (what, self.frame, int((got != self.acc).any(axis=2).sum()))
+        gst = p.stats()
+        for key in ("rays_primary", "rays_secondary", "rays_shadow", "primary_hits", "secondary_hits"):
+            assert gst[key] == ost[key], (what, "progressive", key, gst[key], ost[key])
+        if first and self.plan.options.get("free_radius", 1) != 0:
+            assert p.free_sphere() > 0.0, "%s: the point light has no free sphere at the start: the sequence does not show that it is dropped" % what
+        self.work = p.count_work()
+        pfc = self.hosts[1].update_realtime(CAMERA, 0.0, self.frame, W, H)
+        pfc["pointLight"]["worldPos"][:3] = self.plan.light
+        rt.update(pfc)
+        rt.render()
+        d, ind, ost = osc.render_realtime(omats, pfc, W, H, env_faces=self.env, max_radiance_depth=DEPTH[0], max_shadow_depth=DEPTH[1], nthreads=8)
+        assert np.array_equal(rt.read_output(0), d) and np.array_equal(rt.read_output(1), ind), "%s: realtime frame %d" % (what, self.frame)
+        gst = rt.stats()
+        for key in ("rays_primary", "rays_secondary", "rays_shadow", "primary_hits", "secondary_hits"):
+            assert gst[key] == ost[key], (what, "realtime", key, gst[key], ost[key])
+        self.count("frame checkpoints")
+
+
+def execute(plan, backend, tally, log):
+    """-> None, or what differed.  The shadow model is stepped alongside; log takes one line per operation."""
+    world = fresh_world(plan)
+    for n, op in enumerate(plan.ops):
+        code, _ = apply_to_model(world, op)
+        assert code == op["expect"], "the plan does not replay"
+        log.append(describe(n, op))
+        try:
+            got = backend.do(op)
+            if got != code:
+                return "operation %d returned %d, the shadow model says %d" % (n, got, code)
+            key = ("ok " if code == M.OK else "refused ") + op["op"]
+            tally[key] = tally.get(key, 0) + 1
+            if op["checkpoint"]:
+                backend.checkpoint(n, op, world)
+        except (AssertionError, ValueError, RuntimeError) as e:          # (RuntimeError: a call of the checkpoint's own that the library refuses)
+            return "at operation %d: %s: %s" % (n, type(e).__name__, e)
+    return None
+
+
+def run(iters, seed, ctx, tally=None, log=None, verbose=False, backend=None, start=0):
+    """Sequences start .. iters - 1 of the seed.  Returns None when every one held, else the seed, the sequence number, what differed and the
+    operation log up to that point.  backend(plan, ctx, tally): the side the operations are issued to (default: the GPU library and the oracle)."""
+    tally = {} if tally is None else tally
+    for it in range(start, iters):
+        plan = plan_sequence(seed, it)
+        lines = []
+        own = None
+        if backend is None:
+            from dxrexperiments_amd import capi
+            from oracle import pyoracle
+            if plan.options:                            # a context of its own for the sequence, closed after it
+                own = capi.Context(0)
+                option_cases.apply(own, plan.options)
+            use = own if own is not None else ctx
+            if "shadow_cache_pixels" not in plan.options:
+                use.set_option("shadow_cache_pixels", 1)
+            b = GpuBackend(capi, pyoracle, use, plan, tally)
+        else:
+            b = backend(plan, ctx, tally)
+        try:
+            bad = execute(plan, b, tally, lines)
+        finally:
+            b.close()
+            if backend is None:
+                if own is not None:
+                    own.close()
+                elif "shadow_cache_pixels" not in plan.options:
+                    ctx.set_option("shadow_cache_pixels", -1)
+        tally["sequences"] = tally.get("sequences", 0) + 1
+        if log is not None:
+            log.extend(["sequence %d: models %s, options %s" % (it, plan.kinds, plan.options)] + lines)
+        if bad:
+            return "MISMATCH seed %d sequence %d (models %s, options %s): %s\n%s" % (seed, it, plan.kinds, plan.options, bad, "\n".join(lines))
+        if verbose:
+            print("ok sequence %d: %d operations, models %s, options %s" % (it, len(plan.ops), plan.kinds, plan.options), flush=True)
+    return None
+
+
+def main():
+    from dxrexperiments_amd import capi
+    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    tally = {}
+    ctx = capi.Context(0)
+    if len(sys.argv) > 3 and sys.argv[3] == "all":      # every sequence, whatever the ones before it gave: how many fail, and where first
+        failed = []
+        for it in range(iters):
+            bad = run(it + 1, seed, ctx, tally=tally, start=it)
+            if bad:
+                failed.append(it)
+                print("\n".join(bad.splitlines()[:1] + bad.splitlines()[-2:]))
+        print("tally:", {k: tally[k] for k in sorted(tally)})
+        print("scene edit sweep: seed %d: %d of %d sequences fail: %s" % (seed, len(failed), iters, failed))
+        sys.exit(1 if failed else 0)
+    bad = run(iters, seed, ctx, tally=tally, verbose=True)
+    print("tally:", {k: tally[k] for k in sorted(tally)})
+    if bad:
+        print(bad)
+        sys.exit(1)
+    print("scene edit sweep: %d sequences, seed %d, every checkpoint bit-exact" % (iters, seed))
+
+
+if __name__ == "__main__":
+    main()
