@@ -17,7 +17,7 @@ SRCS = $(CSRC)/rt_api.hip $(CSRC)/rt_bvh_build.hip $(CSRC)/rt_bvh_ploc.hip $(CSR
 HDRS = $(wildcard $(CSRC)/*.h) include/dxr_amd.h include/dxr_amd_types.h
 OBJS = $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 
-BIN = $(LIBDIR)/progressive $(LIBDIR)/realtime_denoise $(LIBDIR)/realtime_animated $(LIBDIR)/realtime_deform $(LIBDIR)/realtime_skinned $(LIBDIR)/realtime_visibility $(LIBDIR)/test_wrapper $(LIBDIR)/progressive_multi
+BIN = $(LIBDIR)/progressive $(LIBDIR)/realtime_denoise $(LIBDIR)/realtime_animated $(LIBDIR)/realtime_deform $(LIBDIR)/realtime_skinned $(LIBDIR)/realtime_morph $(LIBDIR)/realtime_visibility $(LIBDIR)/test_wrapper $(LIBDIR)/progressive_multi
 CXX ?= g++
 HOSTFLAGS = -O2 -std=c++17 -Wall -Iinclude -Idxrexperiments_amd/include
 HOSTLINK = -L$(LIBDIR) -ldxrexperiments_amd -L/opt/rocm/lib -Wl,-rpath,'$$ORIGIN' -Wl,-rpath-link,/opt/rocm/lib
@@ -43,6 +43,9 @@ $(LIBDIR)/realtime_deform: examples/realtime_deform.cpp $(LIB) $(wildcard dxrexp
 	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
 
 $(LIBDIR)/realtime_skinned: examples/realtime_skinned.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)
+	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
+
+$(LIBDIR)/realtime_morph: examples/realtime_morph.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)
 	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
 
 $(LIBDIR)/realtime_visibility: examples/realtime_visibility.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)

@@ -83,6 +83,9 @@ SIGNATURES = {
     "rt_model_set_skin": (_i, [_p, _u32, _u32, _p, _p]),
     "rt_model_get_skin": (_i, [_p, _pu, _pu]),
     "rt_model_set_bones": (_i, [_p, _p, _u32]),
+    "rt_model_set_morph_targets": (_i, [_p, _u32, _p, _p, _p, _p]),
+    "rt_model_get_morph_targets": (_i, [_p, _pu, _pu, _pu]),
+    "rt_model_set_morph_weights": (_i, [_p, _p, _u32]),
     "rt_model_retain": (_i, [_p]),
     "rt_model_destroy": (_i, [_p]),
     "rt_scene_create": (_i, [_p, _pp]),
@@ -458,6 +461,44 @@ class Model:
     def set_bones_device(self, ptr):
         """... from n_bones x 12 floats in device memory, used in place"""
         _check(lib().rt_model_set_bones(self.h, C.c_void_p(ptr), MEM_DEVICE))
+
+    # Extensions: morph targets.  Sparse per-vertex deltas over a base (the vertices as they are now; with a skin, its rest pose) and, per
+    # frame, one weight per target from which the device writes every vertex (include/dxr_amd.h states the arithmetic).
+    def set_morph_targets(self, offsets, indices, position_deltas, normal_deltas=None):
+        """offsets uint32[n_targets + 1], indices uint32[E] (ascending within a target), position_deltas float32[E, 3], normal_deltas
+        float32[E, 3] or None (positions only); captures the base; the vertices stay as they are"""
+        o = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        dp = _f32(position_deltas, (-1, 3))
+        dn = None if normal_deltas is None else _f32(normal_deltas, (-1, 3))
+        if len(o) < 2:
+            raise RtError(-1, "set_morph_targets: %d offsets (clear_morph_targets removes the targets)" % len(o))
+        if dp.shape[0] != len(i) or (dn is not None and dn.shape[0] != len(i)) or int(o[-1]) != len(i):
+            raise RtError(-1, "set_morph_targets: %d indices, %d position deltas, %s normal deltas, offsets end at %d"
+                          % (len(i), dp.shape[0], "no" if dn is None else dn.shape[0], int(o[-1])))
+        _check(lib().rt_model_set_morph_targets(self.h, len(o) - 1, _ptr(o), _ptr(i), _ptr(dp), None if dn is None else _ptr(dn)))
+
+    def clear_morph_targets(self):
+        """removes the targets; the vertices stay what the last call made them"""
+        _check(lib().rt_model_set_morph_targets(self.h, 0, None, None, None, None))
+
+    def morph_targets(self):
+        """(targets, entries, has normal deltas); (0, 0, False): none"""
+        t, e, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().rt_model_get_morph_targets(self.h, C.byref(t), C.byref(e), C.byref(n)))
+        return t.value, e.value, bool(n.value)
+
+    def set_morph_weights(self, w):
+        """float32[n_targets] from a host array: every vertex from the base (with a skin: into its rest pose)"""
+        a = _f32(w, (-1,))
+        n = self.morph_targets()[0]
+        if n and a.shape[0] != n:                        # (no targets: the library says so)
+            raise RtError(-1, "set_morph_weights: %d weights for %d targets" % (a.shape[0], n))
+        _check(lib().rt_model_set_morph_weights(self.h, _ptr(a), MEM_HOST))
+
+    def set_morph_weights_device(self, ptr):
+        """... from n_targets floats in device memory, used in place"""
+        _check(lib().rt_model_set_morph_weights(self.h, C.c_void_p(ptr), MEM_DEVICE))
 
 
 class Scene:

@@ -5,6 +5,7 @@
 #include <new>
 
 #include "rt_adjacency.h"
+#include "rt_morph.h"
 #include "rt_skin.h"
 #include "rt_trace_device.h"
 
@@ -165,6 +166,48 @@ void launch_skin(hipStream_t st, bool lds, rt_vertex *verts, const rt_vertex *re
     const uint32_t blocks = (n_verts + 255u) / 256u;
     if (lds) k_skin_vertices<K, true><<<blocks, 256, 0, st>>>(verts, rest, n_verts, bone, weight, palette, n_bones);
     else k_skin_vertices<K, false><<<blocks, 256, 0, st>>>(verts, rest, n_verts, bone, weight, palette, n_bones);
+}
+
+// ---- morph targets: a model's vertices from its base and a weight per target (rt_model_set_morph_weights) ----
+
+// One lane per vertex, a block of 256 is four whole slices of the SELL-64 layout (rt_morph.h).  A lane walks its own `count` cells, 64 apart:
+// at step j the lanes of a wave that still run read 64 consecutive 16-bit targets and 64 consecutive 12-byte deltas, and lanes whose run is
+// shorter sit masked until the widest lane of the wave is through (the padding of a slice is never read).  The weights are gathered from
+// global memory, 4 B per target and cache resident; no LDS staging -- the skin kernel's LDS palette was the slower path at its edge (DESIGN.md
+// section 7, round 9), and nobody has measured this kernel with one.  The sums are include/dxr_amd.h's: p = p + (w * dp) per component in
+// ascending target order, every entry evaluated, no FMA.  A vertex without entries is copied, all 24 bytes; without NORMALS so is every normal.
+// `dst` is the model's vertices or its skin's rest pose (the host chooses); `base` is never either.
+template <bool NORMALS>
+__global__ void __launch_bounds__(256) k_morph_vertices(rt_vertex *__restrict__ dst, const rt_vertex *__restrict__ base, uint32_t n_verts,
+                                                        const uint32_t *__restrict__ count, const uint32_t *__restrict__ slice_cell,
+                                                        const uint16_t *__restrict__ target, const float *__restrict__ dpos,
+                                                        const float *__restrict__ dnrm, const float *__restrict__ weights)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= n_verts) return;
+    rt_vertex o = base[v];
+    const uint32_t n = count[v];
+    if (n != 0u) {
+        size_t cell = (size_t)slice_cell[v >> 6] + (v & 63u);
+        f3 s = mk3(o.normal.x, o.normal.y, o.normal.z);
+        for (uint32_t j = 0; j < n; j++, cell += 64u) {
+            const float w = weights[target[cell]];
+            const float *dp = dpos + 3u * cell;
+            o.position.x = o.position.x + w * dp[0];
+            o.position.y = o.position.y + w * dp[1];
+            o.position.z = o.position.z + w * dp[2];
+            if (NORMALS) {
+                const float *dn = dnrm + 3u * cell;
+                s = mk3(s.x + w * dn[0], s.y + w * dn[1], s.z + w * dn[2]);
+            }
+        }
+        if (NORMALS) {
+            const float d = dot(s, s);
+            const f3 nn = (d > 0.0f && d < __uint_as_float(0x7f800000u)) ? normalize(s) : mk3(0.0f, 0.0f, 0.0f);
+            o.normal.x = nn.x; o.normal.y = nn.y; o.normal.z = nn.z;
+        }
+    }
+    dst[v] = o;
 }
 
 int upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
@@ -686,6 +729,104 @@ int rt_model_set_bones(rt_model *m, const float *bones3x4, uint32_t mem)
     }
     HIP_TRY(hipGetLastError());
     if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again, and the scratch buffer anybody's)
+    m->h_verts_stale = true;
+    model_changed(m);
+    return RT_OK;
+}
+
+int rt_model_set_morph_targets(rt_model *m, uint32_t n_targets, const uint32_t *target_offsets, const uint32_t *vertex_indices,
+                               const float *position_deltas, const float *normal_deltas)
+{
+    RT_REQUIRE(m, "null model");
+    rt_context *ctx = m->ctx;
+    if (n_targets == 0) {     // no targets: the vertices stay as the last weights left them
+        RT_TRY(use_device(ctx));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (a kernel that reads the buffers may still be queued)
+        m->morph_targets = m->morph_entries = 0;
+        m->morph_normals = false;
+        m->morph_count.release(); m->morph_slice.release(); m->morph_target.release();
+        m->morph_dpos.release(); m->morph_dnrm.release(); m->morph_base.release();
+        return RT_OK;
+    }
+    uint32_t bad_t = 0, bad_e = 0;
+    switch (rt_morph_validate(m->n_verts, n_targets, target_offsets, vertex_indices, position_deltas, &bad_t, &bad_e)) {
+    case 0: break;
+    case 1: rt_set_error("rt_model_set_morph_targets: null argument"); return RT_ERR_INVALID_ARG;
+    case 2: rt_set_error("rt_model_set_morph_targets: %u targets: up to %u are supported (0 removes them)", n_targets, RT_MORPH_MAX_TARGETS); return RT_ERR_INVALID_ARG;
+    case 3: rt_set_error("rt_model_set_morph_targets: target_offsets[0] is %u, not 0", target_offsets[0]); return RT_ERR_INVALID_ARG;
+    case 4:
+        rt_set_error("rt_model_set_morph_targets: target %u: its offsets decrease, %u to %u", bad_t, target_offsets[bad_t], target_offsets[bad_t + 1]);
+        return RT_ERR_INVALID_ARG;
+    case 5:
+        rt_set_error("rt_model_set_morph_targets: target %u, entry %u names vertex %u of %u", bad_t, bad_e, vertex_indices[bad_e], m->n_verts);
+        return RT_ERR_INVALID_ARG;
+    case 6:
+        rt_set_error("rt_model_set_morph_targets: target %u, entry %u names vertex %u after vertex %u: the indices of a target ascend strictly", bad_t,
+                     bad_e, vertex_indices[bad_e], vertex_indices[bad_e - 1]);
+        return RT_ERR_INVALID_ARG;
+    default:
+        rt_set_error("rt_model_set_morph_targets: the packed targets would take 2^32 cells or more");
+        return RT_ERR_UNSUPPORTED;
+    }
+    rt_morph_packed pk;
+    rt_morph_pack(m->n_verts, n_targets, target_offsets, vertex_indices, position_deltas, normal_deltas, pk);
+    RT_TRY(use_device(ctx));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (targets that are replaced: a kernel that reads the old ones may still be queued)
+    m->morph_targets = m->morph_entries = 0;            // (no targets until all of the new ones are there)
+    RT_TRY(upload(ctx, m->morph_count, pk.count.data(), sizeof(uint32_t) * pk.count.size()));
+    RT_TRY(upload(ctx, m->morph_slice, pk.slice_cell.data(), sizeof(uint32_t) * pk.slice_cell.size()));
+    RT_TRY(upload(ctx, m->morph_target, pk.target.data(), sizeof(uint16_t) * pk.target.size()));
+    RT_TRY(upload(ctx, m->morph_dpos, pk.dpos.data(), sizeof(float) * pk.dpos.size()));
+    RT_TRY(upload(ctx, m->morph_dnrm, pk.dnrm.data(), sizeof(float) * pk.dnrm.size()));
+    const size_t bytes = sizeof(rt_vertex) * (size_t)m->n_verts;
+    RT_TRY(m->morph_base.reserve(bytes));
+    const void *from = m->skin_k ? m->skin_rest.p : m->d_verts.p;            // the base: the skin's rest pose, or the vertices as they are
+    HIP_TRY(hipMemcpyAsync(m->morph_base.p, from, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope)
+    m->morph_targets = n_targets;
+    m->morph_entries = target_offsets[n_targets];
+    m->morph_normals = normal_deltas != nullptr;
+    return RT_OK;             // the vertices are what they were: nothing changed, built scenes stay built
+}
+
+int rt_model_get_morph_targets(const rt_model *m, uint32_t *n_targets, uint32_t *n_entries, uint32_t *has_normals)
+{
+    RT_REQUIRE(m, "null model");
+    if (n_targets) *n_targets = m->morph_targets;
+    if (n_entries) *n_entries = m->morph_entries;
+    if (has_normals) *has_normals = m->morph_normals ? 1u : 0u;
+    return RT_OK;
+}
+
+int rt_model_set_morph_weights(rt_model *m, const float *weights, uint32_t mem)
+{
+    RT_REQUIRE(m && weights, "null argument");
+    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
+    if (m->morph_targets == 0) {
+        rt_set_error("rt_model_set_morph_weights: the model has no morph targets (rt_model_set_morph_targets gives it some)");
+        return RT_ERR_STATE;
+    }
+    rt_context *ctx = m->ctx;
+    const bool skinned = m->skin_k != 0;                // the result is the skin's rest pose: no vertex changes before the next rt_model_set_bones
+    if (skinned) RT_TRY(use_device(ctx));
+    else RT_TRY(model_before_set(m));
+    const float *w = weights;
+    if (mem == RT_MEM_HOST) {
+        RT_TRY(upload(ctx, ctx->scratch[0], weights, sizeof(float) * (size_t)m->morph_targets));
+        w = ctx->scratch[0].as<float>();
+    }
+    rt_vertex *dst = skinned ? m->skin_rest.as<rt_vertex>() : m->d_verts.as<rt_vertex>();
+    const rt_vertex *base = m->morph_base.as<rt_vertex>();
+    const uint32_t blocks = (m->n_verts + 255u) / 256u;
+    if (m->morph_normals)     // (every result from the base, the whole mesh)
+        k_morph_vertices<true><<<blocks, 256, 0, ctx->stream>>>(dst, base, m->n_verts, m->morph_count.as<uint32_t>(), m->morph_slice.as<uint32_t>(),
+                                                                m->morph_target.as<uint16_t>(), m->morph_dpos.as<float>(), m->morph_dnrm.as<float>(), w);
+    else
+        k_morph_vertices<false><<<blocks, 256, 0, ctx->stream>>>(dst, base, m->n_verts, m->morph_count.as<uint32_t>(), m->morph_slice.as<uint32_t>(),
+                                                                 m->morph_target.as<uint16_t>(), m->morph_dpos.as<float>(), nullptr, w);
+    HIP_TRY(hipGetLastError());
+    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again, and the scratch buffer anybody's)
+    if (skinned) return RT_OK;
     m->h_verts_stale = true;
     model_changed(m);
     return RT_OK;

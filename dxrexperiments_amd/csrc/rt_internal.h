@@ -324,6 +324,12 @@ struct rt_model {
     uint32_t skin_k = 0, skin_bones = 0;     // influences per vertex, bones of a palette
     DevBuf skin_bone, skin_weight;           // uint16[skin_k][n_verts], float[skin_k][n_verts]: slot major (rt_skin.h)
     DevBuf skin_rest;                        // rt_vertex[n_verts]: the rest pose, d_verts as they were when the skin was set
+    // rt_model_set_morph_targets / rt_model_set_morph_weights: morph_targets == 0: no targets
+    uint32_t morph_targets = 0, morph_entries = 0;
+    bool morph_normals = false;              // the targets carry normal deltas (morph_dnrm is filled)
+    DevBuf morph_count, morph_slice;         // uint32[n_verts], uint32[ceil(n_verts / 64) + 1]: SELL-64 (rt_morph.h)
+    DevBuf morph_target, morph_dpos, morph_dnrm;       // uint16[cells], float[3 cells], float[3 cells]
+    DevBuf morph_base;                       // rt_vertex[n_verts]: the base, captured when the targets were set
     ~rt_model();                // (rt_api.hip) selects the device before the buffers go
 };
 

@@ -171,6 +171,25 @@ namespace DXRFramework
             ThrowIfFailed(rt_model_set_bones(mHandle, bones3x4, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
         }
 
+        // EXTENSIONS (the reference reads only mVertices / mNormals of an imported mesh, RtModel.cpp:26, :38-45, never its blend shapes; the
+        // update path is the never-taken one, Helpers/BottomLevelASGenerator.h:136-176): morph targets.  setMorphTargets: numTargets sparse
+        // targets, target major, host arrays -- target t owns entries targetOffsets[t] .. targetOffsets[t + 1] - 1, entry e adds
+        // positionDeltas[3 e ..] (and normalDeltas[3 e ..] unless null) to vertex vertexIndices[e]; the vertices as they are (with a skin: its
+        // rest pose) become the base and stay as they are.  setMorphWeights: numTargets weights; the device writes every vertex from the base
+        // (include/dxr_amd.h states the arithmetic) -- without a skin into the model's vertices, and every built scene that holds the model
+        // renders nothing until its update() or build(); with a skin into the skin's rest pose, which the next setBones poses.
+        // clearMorphTargets: no targets any more, the vertices stay what the last call made them.
+        void setMorphTargets(uint32_t numTargets, const uint32_t *targetOffsets, const uint32_t *vertexIndices, const float *positionDeltas,
+                             const float *normalDeltas = nullptr)
+        {
+            ThrowIfFailed(rt_model_set_morph_targets(mHandle, numTargets, targetOffsets, vertexIndices, positionDeltas, normalDeltas));
+        }
+        void clearMorphTargets() { ThrowIfFailed(rt_model_set_morph_targets(mHandle, 0, nullptr, nullptr, nullptr, nullptr)); }
+        void setMorphWeights(const float *weights, bool deviceMemory = false)
+        {
+            ThrowIfFailed(rt_model_set_morph_weights(mHandle, weights, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
+        }
+
     private:
         RtModel(RtContext::SharedPtr ctx, rt_model *h) : mContext(ctx), mHandle(h) {}
         RtContext::SharedPtr mContext;

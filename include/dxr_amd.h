@@ -253,6 +253,57 @@ int rt_model_get_skin(const rt_model *m, uint32_t *influences, uint32_t *n_bones
  * rt_model_set_bones overwrites what they wrote.  rt_model_read_geometry returns the skinned vertices. */
 int rt_model_set_bones(rt_model *m, const float *bones3x4 /* n_bones x 12 */, uint32_t mem /* RT_MEM_HOST | RT_MEM_DEVICE */);
 
+/* Morph targets -- EXTENSIONS: the reference reads only mVertices / mNormals of an imported mesh (libs/DXRFramework/RtModel.cpp:26, :38-45)
+ * and never its aiAnimMesh blend shapes; the update path a morphed mesh would take is the generators' never-taken one
+ * (Helpers/BottomLevelASGenerator.h:136-176).  A model gets TARGETS, sparse per-vertex deltas over a BASE; the caller sets one WEIGHT per target
+ * per frame, and a kernel writes every vertex as base + the weighted deltas.
+ * Targets are sparse and target major, host arrays: target t owns entries target_offsets[t] .. target_offsets[t + 1] - 1; entry e adds
+ * position_deltas[3 e ..] to vertex vertex_indices[e] and, with normal_deltas given, normal_deltas[3 e ..] to that vertex's normal.  A dense
+ * target simply lists every vertex; a target with no entries is legal.
+ * The definition, for vertex v with BASE position b and BASE normal n, fp32 throughout, every product and every sum one rounded operation,
+ * no contraction, in this order:
+ *   a vertex that no target names gets its base record copied bit for bit, all 24 bytes;
+ *   otherwise p = b and s = n, and for every entry that names v, in ascending target order, with w_t the weight of its target and dp, dn its
+ *   deltas, for each component c: p_c = p_c + (w_t * dp_c) and, with normal deltas, s_c = s_c + (w_t * dn_c).  Every entry is evaluated: a
+ *   zero weight is not skipped, so -0 + (+0 * d) is +0 (for a delta d >= +0), and a NaN weight reaches the vertex.
+ *   normal  with normal deltas d = dot(s, s) = ((sx sx) + sy sy) + sz sz and the normal is s * (1 / sqrt(d)) if 0 < d < inf, else (0, 0, 0):
+ *           the rule of rt_model_recompute_normals.  Without normal deltas the base normal is copied bit for bit.
+ * The weights are taken as given: NaN, inf, negative weights and weights above 1 are no errors.
+ * rt_model_set_morph_targets validates on the host, and nothing changes when it refuses: RT_ERR_INVALID_ARG for a null `m`; with
+ * n_targets > 0 for a null target_offsets, vertex_indices or position_deltas; for n_targets > 65536 (a target index is stored in 16 bits);
+ * for target_offsets[0] != 0 or offsets that decrease (the message names the target); for a vertex index >= V and for indices within one
+ * target that do not ascend strictly -- a target names a vertex at most once -- (the message names the target and the entry, the entry by its
+ * place in vertex_indices); RT_ERR_UNSUPPORTED for targets whose packed layout (64 cells per slice of 64 vertices and step of its longest
+ * run) would take 2^32 cells or more.  It stores the packed targets on the device and captures the BASE, device to device on the context's
+ * stream: on a model without a skin the model's vertices as they are then, on a model with a skin the skin's rest pose.  It changes no
+ * vertex and marks nothing changed: built scenes stay built.  Calling it again replaces the targets and captures the base anew.
+ * n_targets == 0 (the other arguments are ignored) removes the targets and frees their buffers; the vertices stay what the last call made
+ * them. */
+int rt_model_set_morph_targets(rt_model *m, uint32_t n_targets,
+                               const uint32_t *target_offsets   /* n_targets + 1 */,
+                               const uint32_t *vertex_indices   /* target_offsets[n_targets] */,
+                               const float *position_deltas     /* 3 floats per entry */,
+                               const float *normal_deltas       /* 3 floats per entry, or NULL: positions only */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the targets and entries of the model's morph targets and whether
+ * they carry normal deltas; each may be NULL; 0, 0, 0: none */
+int rt_model_get_morph_targets(const rt_model *m, uint32_t *n_targets, uint32_t *n_entries, uint32_t *has_normals);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): every vertex from the base and these n_targets weights, by the
+ * definition above, on the device -- always the whole mesh and always from the base, never from the previous result.  Where the result goes
+ * depends on whether the model has a skin when the call is made.
+ * NO SKIN: into the model's vertices, and the call behaves as rt_model_set_bones does: frames a deferred pipeline still holds are rendered
+ * first, the model is left CHANGED and every built scene that holds it STALE (RT_ERR_STATE from what reads them, the message names the
+ * pending vertices) until rt_scene_update or rt_scene_build, which rebuild the BLAS.  rt_model_read_geometry returns the morphed vertices.
+ * WITH A SKIN: into the skin's rest pose.  The model's vertices are not touched, nothing is marked changed, built scenes stay built and
+ * traceable, and the next rt_model_set_bones poses the morphed rest pose: a frame of a morphed, skinned character is
+ * rt_model_set_morph_weights, rt_model_set_bones, rt_scene_update.
+ * rt_model_set_skin itself is as it was and captures its rest pose from the model's vertices; giving a morphed model a skin later redirects
+ * later morph results to the new rest pose, removing the skin redirects them to the vertices again, and the morph base is recaptured by
+ * neither.  `mem` as for rt_model_set_bones: RT_MEM_HOST (the weights go up through a scratch buffer and the stream is synchronised before
+ * the call returns) or RT_MEM_DEVICE (used in place, ordered on the context's stream).  A null argument or an unknown `mem` is
+ * RT_ERR_INVALID_ARG; a model without targets is RT_ERR_STATE (the message names rt_model_set_morph_targets).  rt_model_set_vertices /
+ * rt_model_set_positions on a morphed model still write the current vertices and leave the base alone. */
+int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */, uint32_t mem /* RT_MEM_HOST | RT_MEM_DEVICE */);
+
 /* ---- raw TraceRay over a batch (HLSL TraceRay semantics, used by tests and
  *      the traversal benchmark; ProgressiveRaytracing.hlsl:34,53,
  *      RaytracingCommon.hlsli:94) ------------------------------------------- */
