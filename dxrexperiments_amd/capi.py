@@ -86,6 +86,18 @@ SIGNATURES = {
     "rt_model_set_morph_targets": (_i, [_p, _u32, _p, _p, _p, _p]),
     "rt_model_get_morph_targets": (_i, [_p, _pu, _pu, _pu]),
     "rt_model_set_morph_weights": (_i, [_p, _p, _u32]),
+    "rt_skeleton_create": (_i, [_p, _u32, _p, _p, _pp]),
+    "rt_skeleton_destroy": (_i, [_p]),
+    "rt_skeleton_get_info": (_i, [_p, _pu, _pu, _pu]),
+    "rt_skeleton_set_pose": (_i, [_p, _p, _u32]),
+    "rt_skeleton_add_clip": (_i, [_p, _u32, _p, _p, _pu]),
+    "rt_skeleton_clear_clips": (_i, [_p]),
+    "rt_skeleton_set_time": (_i, [_p, _u32, _f]),
+    "rt_skeleton_read_pose": (_i, [_p, _p]),
+    "rt_skeleton_read_joints": (_i, [_p, _p]),
+    "rt_skeleton_read_palette": (_i, [_p, _p]),
+    "rt_skeleton_get_palette_device_ptr": (_i, [_p, _pp]),
+    "rt_model_set_bones_from_skeleton": (_i, [_p, _p]),
     "rt_model_retain": (_i, [_p]),
     "rt_model_destroy": (_i, [_p]),
     "rt_scene_create": (_i, [_p, _pp]),
@@ -499,6 +511,90 @@ class Model:
     def set_morph_weights_device(self, ptr):
         """... from n_targets floats in device memory, used in place"""
         _check(lib().rt_model_set_morph_weights(self.h, C.c_void_p(ptr), MEM_DEVICE))
+
+    def set_bones_from(self, skeleton):
+        """set_bones_device with the palette of a posed Skeleton of as many joints as the skin has bones: nothing leaves the device"""
+        _check(lib().rt_model_set_bones_from_skeleton(self.h, skeleton.h))
+
+
+class Skeleton:
+    """Extension: a joint hierarchy posed on the device (include/dxr_amd.h "Posed skeletons").  parents int32[n_joints] (-1: a root, else a
+    joint before its child), inverse_bind float32[n_joints, 12]."""
+
+    def __init__(self, ctx, parents, inverse_bind):
+        self.ctx = ctx
+        p = np.ascontiguousarray(parents, dtype=np.int32).reshape(-1)
+        b = _f32(inverse_bind, (-1, 12))
+        if b.shape[0] != p.shape[0]:
+            raise RtError(-1, "Skeleton: %d parents, %d inverse bind matrices" % (p.shape[0], b.shape[0]))
+        h = C.c_void_p()
+        _check(lib().rt_skeleton_create(ctx.h, p.shape[0], _ptr(p), _ptr(b), C.byref(h)))
+        self.h = h
+        self.n_joints = p.shape[0]
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().rt_skeleton_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def info(self):
+        """(joints, levels, clips)"""
+        j, l, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().rt_skeleton_get_info(self.h, C.byref(j), C.byref(l), C.byref(c)))
+        return j.value, l.value, c.value
+
+    def set_pose(self, trs):
+        """float32[n_joints, 10] (tx ty tz  qx qy qz qw  sx sy sz) from a host array: world matrices and the palette on the device"""
+        a = _f32(trs, (-1, 10))
+        if a.shape[0] != self.n_joints:
+            raise RtError(-1, "set_pose: %d joints for a skeleton of %d" % (a.shape[0], self.n_joints))
+        _check(lib().rt_skeleton_set_pose(self.h, _ptr(a), MEM_HOST))
+
+    def set_pose_device(self, ptr):
+        """... from n_joints x 10 floats in device memory"""
+        _check(lib().rt_skeleton_set_pose(self.h, C.c_void_p(ptr), MEM_DEVICE))
+
+    def add_clip(self, times, trs):
+        """times float32[K] ascending strictly, trs float32[K, n_joints, 10]; returns the clip's id"""
+        t = _f32(times, (-1,))
+        a = _f32(trs, (-1, self.n_joints, 10))
+        if a.shape[0] != t.shape[0]:
+            raise RtError(-1, "add_clip: %d times, %d keys" % (t.shape[0], a.shape[0]))
+        clip = C.c_uint32()
+        _check(lib().rt_skeleton_add_clip(self.h, t.shape[0], _ptr(t), _ptr(a), C.byref(clip)))
+        return clip.value
+
+    def clear_clips(self):
+        _check(lib().rt_skeleton_clear_clips(self.h))
+
+    def set_time(self, clip, t):
+        """samples the clip at t and poses the skeleton with the result, all on the device"""
+        _check(lib().rt_skeleton_set_time(self.h, clip, float(t)))
+
+    def _read(self, fn, width):
+        out = np.empty((self.n_joints, width), np.float32)
+        _check(fn(self.h, _ptr(out)))
+        return out
+
+    def pose(self):
+        """the local pose last set or sampled: float32[n_joints, 10]"""
+        return self._read(lib().rt_skeleton_read_pose, 10)
+
+    def joints(self):
+        """the world matrices W_j: float32[n_joints, 12]"""
+        return self._read(lib().rt_skeleton_read_joints, 12)
+
+    def palette(self):
+        """the skinning matrices M_j = W_j o inverse_bind_j: float32[n_joints, 12]"""
+        return self._read(lib().rt_skeleton_read_palette, 12)
+
+    def palette_ptr(self):
+        """the palette in device memory (what Model.set_bones_device takes)"""
+        p = C.c_void_p()
+        _check(lib().rt_skeleton_get_palette_device_ptr(self.h, C.byref(p)))
+        return p.value
 
 
 class Scene:

@@ -333,6 +333,27 @@ struct rt_model {
     ~rt_model();                // (rt_api.hip) selects the device before the buffers go
 };
 
+// rt_skeleton_create (rt_skeleton.hip): a joint hierarchy, its current pose and the palette a skin reads
+struct SkeletonClip {
+    std::vector<float> times;    // n_keys, ascending strictly
+    DevBuf keys;                 // float[n_keys][10][n_joints]: component major within a key, so that the lanes of a wave read 64 consecutive floats
+};
+
+struct rt_skeleton {
+    rt_context *ctx = nullptr;
+    uint32_t n_joints = 0, n_levels = 0;
+    std::vector<uint32_t> level_offsets;     // n_levels + 1 (rt_skeleton.h)
+    DevBuf table;                // uint32[n_joints]: joint | parent << 16 in level order (rt_skeleton_pack_table)
+    DevBuf d_level_offsets;      // uint32[n_levels + 1]
+    DevBuf inverse_bind;         // float[n_joints][12]
+    DevBuf pose;                 // float[n_joints][10]: the local pose last set or sampled
+    DevBuf joints;               // float[n_joints][12]: W_j
+    DevBuf palette;              // float[n_joints][12]: M_j = W_j o inverse_bind_j, what rt_model_set_bones_from_skeleton hands to the skin kernel
+    bool posed = false;          // a pose has been set or sampled: joints and palette hold something
+    std::vector<SkeletonClip> clips;
+    ~rt_skeleton();              // (rt_skeleton.hip) selects the device and joins the stream before the buffers go
+};
+
 struct SceneInstance {
     rt_model *model;
     float xform[12];

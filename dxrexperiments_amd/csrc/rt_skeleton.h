@@ -1,0 +1,103 @@
+// rt_skeleton.h -- the host side of a skeleton (rt_skeleton_create, rt_skeleton_add_clip, rt_skeleton_set_time): validation of the caller's
+// arrays, the level table k_skeleton_pose walks, and the segment search of a clip.  Host code without HIP, as rt_skin.h is:
+// tests/cpp/skeleton_sanitized.cpp compiles it alone.
+#pragma once
+
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+
+#define RT_SKELETON_MAX_JOINTS 65536u    // the skin's bone limit (RT_SKIN_MAX_BONES): a joint is a bone, and fits 16 bits
+#define RT_SKELETON_POSE_FLOATS 10u      // a joint of a pose: tx ty tz  qx qy qz qw  sx sy sz
+#define RT_SKELETON_BLOCK 256u           // lanes of the one block that poses a skeleton
+
+// Skeletons of up to this many joints are posed with the world matrices W in LDS: 48 B per joint, component major (12 rows of this many
+// floats, so that the lanes of a wave that read their parents' entries read 64 different banks on a chain and one broadcast word on a star),
+// and beside them the level table and the level offsets, 4 B per joint each.  1024 joints take 48 KiB + 8 KiB = 56 KiB, inside the 64 KiB a
+// block may declare on every CDNA part and about a third of the 160 KiB of an MI355X CU: the one block of the pose kernel leaves room for the
+// skin kernel's blocks of 12 KiB that run on the same CU behind it.  A character has 50 - 300 joints and a crowd rig that shares one skeleton a few times that; what is
+// above 1024 is a stress case, and it keeps W in the joints' global array (L2 resident: 3 MiB at 65536 joints), at a global round trip per
+// level instead of an LDS one.
+#define RT_SKELETON_LDS_JOINTS 1024u
+
+// 0: the arguments describe a hierarchy.  Else what is wrong: 1 a null array, 2 n_joints outside 1 .. 65536, 3 a parent that is neither -1
+// nor < its joint (parents come before children) -- then *bad_joint names the first such joint.  Reads n_joints entries of `parents`.
+static inline int rt_skeleton_validate(uint32_t n_joints, const int32_t *parents, const float *inverse_bind, uint32_t *bad_joint)
+{
+    if (!parents || !inverse_bind) return 1;
+    if (n_joints < 1u || n_joints > RT_SKELETON_MAX_JOINTS) return 2;
+    for (uint32_t j = 0; j < n_joints; j++)
+        if (parents[j] < -1 || (int64_t)parents[j] >= (int64_t)j) {
+            if (bad_joint) *bad_joint = j;
+            return 3;
+        }
+    return 0;
+}
+
+// The level table of a validated hierarchy.  The level of a root is 0, of any other joint its parent's + 1.  `order`: the joints in level
+// order, ascending by index within a level (n_joints entries); `level_offsets`: level l owns order[level_offsets[l]] ..
+// order[level_offsets[l + 1] - 1] (levels + 1 entries, the last one n_joints).  Returns the number of levels.
+static inline uint32_t rt_skeleton_levels(uint32_t n_joints, const int32_t *parents, std::vector<uint32_t> &order, std::vector<uint32_t> &level_offsets)
+{
+    std::vector<uint32_t> level(n_joints, 0u);
+    uint32_t n_levels = 0;
+    for (uint32_t j = 0; j < n_joints; j++) {           // (parents come first: one pass)
+        level[j] = parents[j] < 0 ? 0u : level[(uint32_t)parents[j]] + 1u;
+        if (level[j] + 1u > n_levels) n_levels = level[j] + 1u;
+    }
+    level_offsets.assign((size_t)n_levels + 1u, 0u);
+    for (uint32_t j = 0; j < n_joints; j++) level_offsets[level[j] + 1u]++;
+    for (uint32_t l = 0; l < n_levels; l++) level_offsets[l + 1u] += level_offsets[l];
+    std::vector<uint32_t> at(level_offsets.begin(), level_offsets.end() - 1);
+    order.assign(n_joints, 0u);
+    for (uint32_t j = 0; j < n_joints; j++) order[at[level[j]]++] = j;       // (ascending j: stable within a level)
+    return n_levels;
+}
+
+// The table as k_skeleton_pose reads it: entry k = order[k] | parent << 16 (a joint and its parent both fit 16 bits; a root's parent field
+// is 0xFFFF, which no joint can have for a parent: parent < joint <= 65535).
+static inline void rt_skeleton_pack_table(const int32_t *parents, const std::vector<uint32_t> &order, std::vector<uint32_t> &table)
+{
+    table.resize(order.size());
+    for (size_t k = 0; k < order.size(); k++) {
+        const int32_t p = parents[order[k]];
+        table[k] = order[k] | ((p < 0 ? 0xFFFFu : (uint32_t)p) << 16);
+    }
+}
+
+// 0: the key times of a clip.  Else: 1 a null array, 2 n_keys == 0, 3 a time that is not finite, 4 a time that is not above the one before
+// it (the times ascend strictly) -- for 3 and 4 *bad_key names the first such key.
+static inline int rt_skeleton_validate_times(uint32_t n_keys, const float *times, uint32_t *bad_key)
+{
+    if (!times) return 1;
+    if (n_keys == 0u) return 2;
+    for (uint32_t k = 0; k < n_keys; k++) {
+        if (!isfinite(times[k])) {
+            if (bad_key) *bad_key = k;
+            return 3;
+        }
+        if (k > 0u && !(times[k] > times[k - 1u])) {
+            if (bad_key) *bad_key = k;
+            return 4;
+        }
+    }
+    return 0;
+}
+
+// The segment of validated key times that holds t (not NaN), and where t stands in it: one key, or t at or before the first, gives (0, 0);
+// t at or beyond the last (n_keys - 2, 1); otherwise i is the largest key with times[i] <= t and a = (t - times[i]) / (times[i + 1] -
+// times[i]), two fp32 differences and one fp32 quotient.
+static inline void rt_skeleton_segment(uint32_t n_keys, const float *times, float t, uint32_t *i_out, float *a_out)
+{
+    if (n_keys == 1u || t <= times[0]) { *i_out = 0u; *a_out = 0.0f; return; }
+    if (t >= times[n_keys - 1u]) { *i_out = n_keys - 2u; *a_out = 1.0f; return; }
+    uint32_t lo = 0u, hi = n_keys - 1u;                  // times[lo] <= t < times[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (times[mid] <= t) lo = mid; else hi = mid;
+    }
+    const float num = t - times[lo], den = times[lo + 1u] - times[lo];
+    *i_out = lo;
+    *a_out = num / den;
+}

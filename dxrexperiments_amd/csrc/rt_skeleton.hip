@@ -1,0 +1,377 @@
+// rt_skeleton.hip -- posed skeletons (include/dxr_amd.h "Posed skeletons"): a joint hierarchy whose local pose -- set by the caller or sampled
+// from a baked clip -- becomes world matrices and a skinning palette on the device.  The palette is what rt_model_set_bones(RT_MEM_DEVICE)
+// takes: rt_model_set_bones_from_skeleton hands it over and k_skin_vertices (rt_api.hip) runs unchanged.  No reference counterpart: the
+// reference imports with aiProcess_PreTransformVertices (libs/DXRFramework/RtModel.cpp:26), which drops bones and node animation.
+#include <cmath>
+#include <new>
+
+#include "rt_device_math.h"
+#include "rt_internal.h"
+#include "rt_skeleton.h"
+
+namespace {
+
+using namespace rtd;
+
+// The local matrix of a joint, T.R.S, from its ten floats tx ty tz  qx qy qz qw  sx sy sz: the quaternion as given, never normalised.
+RT_DEV void local_of(const float *__restrict__ trs, float L[12])
+{
+    const float x = trs[3], y = trs[4], z = trs[5], w = trs[6];
+    const float sx = trs[7], sy = trs[8], sz = trs[9];
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+    L[0] = (1.0f - 2.0f * (yy + zz)) * sx; L[1] = (2.0f * (xy - wz)) * sy;        L[2] = (2.0f * (xz + wy)) * sz;         L[3] = trs[0];
+    L[4] = (2.0f * (xy + wz)) * sx;        L[5] = (1.0f - 2.0f * (xx + zz)) * sy; L[6] = (2.0f * (yz - wx)) * sz;         L[7] = trs[1];
+    L[8] = (2.0f * (xz - wy)) * sx;        L[9] = (2.0f * (yz + wx)) * sy;        L[10] = (1.0f - 2.0f * (xx + yy)) * sz; L[11] = trs[2];
+}
+
+// C = A o B of two 3x4 affine matrices, grouped as the header groups it
+RT_DEV void compose(const float A[12], const float B[12], float C[12])
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const float a0 = A[4 * r], a1 = A[4 * r + 1], a2 = A[4 * r + 2], a3 = A[4 * r + 3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) C[4 * r + c] = (a0 * B[c] + a1 * B[4 + c]) + a2 * B[8 + c];
+        C[4 * r + 3] = ((a0 * B[3] + a1 * B[7]) + a2 * B[11]) + a3;
+    }
+}
+
+// ONE block poses a skeleton: no block ever waits on another.  Step 1, every joint at once: L from the pose, stored where W will stand (a
+// root's W is its L bit for bit).  Step 2, level by level from level 1, the lanes striding a level's joints and meeting at __syncthreads():
+// W_j = W_parent o L_j, in place -- a joint's parent stands in an earlier level, so nothing read in a level is written in it.  Step 3, every
+// joint at once: M_j = W_j o inverse_bind_j.  LDS (n_joints <= RT_SKELETON_LDS_JOINTS): W component major in LDS, and with it the level table
+// and the level offsets, so that a level costs LDS round trips only; else W in `joints` and the tables in global memory, a global round trip per
+// level.  The same statements either way: the same bytes.  `joints` is read back by other lanes than wrote it: not __restrict__.
+template <bool LDS>
+__global__ void __launch_bounds__(RT_SKELETON_BLOCK) k_skeleton_pose(const float *__restrict__ pose, const uint32_t *__restrict__ table,
+                                                                     const uint32_t *__restrict__ level_offsets, uint32_t n_levels, uint32_t n_joints,
+                                                                     const float *__restrict__ inverse_bind, float *joints, float *__restrict__ palette)
+{
+    constexpr uint32_t N = RT_SKELETON_LDS_JOINTS;
+    __shared__ float s_w[LDS ? 12u * N : 1u];
+    __shared__ uint32_t s_table[LDS ? N : 1u];
+    __shared__ uint32_t s_off[LDS ? N + 1u : 1u];
+    auto load = [&](uint32_t j, float M[12]) {
+#pragma unroll
+        for (int e = 0; e < 12; e++) M[e] = LDS ? s_w[e * N + j] : joints[12u * (size_t)j + e];
+    };
+    auto store = [&](uint32_t j, const float M[12]) {
+#pragma unroll
+        for (int e = 0; e < 12; e++) {
+            if (LDS) s_w[e * N + j] = M[e];
+            else joints[12u * (size_t)j + e] = M[e];
+        }
+    };
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t j = tid; j < n_joints; j += RT_SKELETON_BLOCK) {
+        float L[12];
+        local_of(pose + RT_SKELETON_POSE_FLOATS * (size_t)j, L);
+        store(j, L);
+        if (LDS) s_table[j] = table[j];
+    }
+    if (LDS)
+        for (uint32_t l = tid; l <= n_levels; l += RT_SKELETON_BLOCK) s_off[l] = level_offsets[l];
+    __syncthreads();
+    for (uint32_t l = 1; l < n_levels; l++) {            // (uniform: every lane passes every barrier)
+        const uint32_t begin = LDS ? s_off[l] : level_offsets[l], end = LDS ? s_off[l + 1u] : level_offsets[l + 1u];
+        for (uint32_t k = begin + tid; k < end; k += RT_SKELETON_BLOCK) {
+            const uint32_t entry = LDS ? s_table[k] : table[k];
+            const uint32_t j = entry & 0xFFFFu, p = entry >> 16;
+            float P[12], L[12], W[12];
+            load(p, P);
+            load(j, L);
+            compose(P, L, W);
+            store(j, W);
+        }
+        __syncthreads();
+    }
+    for (uint32_t j = tid; j < n_joints; j += RT_SKELETON_BLOCK) {
+        float W[12], B[12], M[12];
+        load(j, W);
+#pragma unroll
+        for (int e = 0; e < 12; e++) B[e] = inverse_bind[12u * (size_t)j + e];
+        compose(W, B, M);
+#pragma unroll
+        for (int e = 0; e < 12; e++) {
+            if (LDS) joints[12u * (size_t)j + e] = W[e];
+            palette[12u * (size_t)j + e] = M[e];
+        }
+    }
+}
+
+// One lane per joint: the local pose between two keys of a clip.  A key is component major (float[10][n_joints]): at every one of the twenty
+// loads the lanes of a wave read 64 consecutive floats.  Translation and scale A + (a * (B - A)); the quaternion the same after B has been
+// turned onto A's side (d < 0; a NaN d turns nothing), then normalised by the rule of rt_model_recompute_normals with (0, 0, 0, 1) where
+// that has no answer.  The pose is written as rt_skeleton_set_pose takes it, ten floats per joint.
+__global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict__ key_a, const float *__restrict__ key_b, uint32_t n_joints, float a,
+                                                         float *__restrict__ pose)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_joints) return;
+    float A[10], B[10], o[10];
+#pragma unroll
+    for (int c = 0; c < 10; c++) {
+        A[c] = key_a[(size_t)c * n_joints + j];
+        B[c] = key_b[(size_t)c * n_joints + j];
+    }
+    const float d = ((A[3] * B[3] + A[4] * B[4]) + A[5] * B[5]) + A[6] * B[6];
+    if (d < 0.0f) {
+#pragma unroll
+        for (int c = 3; c < 7; c++) B[c] = -B[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 10; c++) o[c] = A[c] + a * (B[c] - A[c]);
+    const float n = ((o[3] * o[3] + o[4] * o[4]) + o[5] * o[5]) + o[6] * o[6];
+    if (n > 0.0f && n < __uint_as_float(0x7f800000u)) {
+        const float inv = rsqrt_ieee(n);
+#pragma unroll
+        for (int c = 3; c < 7; c++) o[c] = o[c] * inv;
+    } else {
+        o[3] = 0.0f; o[4] = 0.0f; o[5] = 0.0f; o[6] = 1.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = o[c];
+}
+
+int use_device(const rt_context *ctx)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    return RT_OK;
+}
+
+int upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
+{
+    RT_TRY(b.reserve(bytes));
+    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return RT_OK;
+}
+
+// sk->pose holds a local pose: W and the palette from it, queued on the context's stream
+int pose_skeleton(rt_skeleton *sk)
+{
+    hipStream_t st = sk->ctx->stream;
+    const float *pose = sk->pose.as<float>(), *ib = sk->inverse_bind.as<float>();
+    const uint32_t *table = sk->table.as<uint32_t>(), *off = sk->d_level_offsets.as<uint32_t>();
+    if (sk->n_joints <= RT_SKELETON_LDS_JOINTS)
+        k_skeleton_pose<true><<<1, RT_SKELETON_BLOCK, 0, st>>>(pose, table, off, sk->n_levels, sk->n_joints, ib, sk->joints.as<float>(), sk->palette.as<float>());
+    else
+        k_skeleton_pose<false><<<1, RT_SKELETON_BLOCK, 0, st>>>(pose, table, off, sk->n_levels, sk->n_joints, ib, sk->joints.as<float>(), sk->palette.as<float>());
+    HIP_TRY(hipGetLastError());
+    sk->posed = true;
+    return RT_OK;
+}
+
+int require_pose(const rt_skeleton *sk, const char *who)
+{
+    if (sk->posed) return RT_OK;
+    rt_set_error("%s: the skeleton has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", who);
+    return RT_ERR_STATE;
+}
+
+int read_back(rt_skeleton *sk, const char *who, const DevBuf &from, float *to, size_t floats_per_joint)
+{
+    RT_TRY(require_pose(sk, who));
+    RT_TRY(use_device(sk->ctx));
+    HIP_TRY(hipMemcpyAsync(to, from.p, sizeof(float) * floats_per_joint * sk->n_joints, hipMemcpyDeviceToHost, sk->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(sk->ctx->stream));
+    return RT_OK;
+}
+
+}  // namespace
+
+rt_skeleton::~rt_skeleton()
+{
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);            // (a skin kernel that reads the palette, or a pose kernel, may still be queued)
+}
+
+extern "C" {
+
+int rt_skeleton_create(rt_context *ctx, uint32_t n_joints, const int32_t *parents, const float *inverse_bind, rt_skeleton **out)
+{
+    RT_REQUIRE(ctx && out, "null argument");
+    uint32_t bad = 0;
+    switch (rt_skeleton_validate(n_joints, parents, inverse_bind, &bad)) {
+    case 0: break;
+    case 1: rt_set_error("rt_skeleton_create: null argument"); return RT_ERR_INVALID_ARG;
+    case 2: rt_set_error("rt_skeleton_create: %u joints: 1 .. %u are supported", n_joints, RT_SKELETON_MAX_JOINTS); return RT_ERR_INVALID_ARG;
+    default:
+        rt_set_error("rt_skeleton_create: joint %u names parent %d: a parent is -1 (a root) or a joint before its child", bad, parents[bad]);
+        return RT_ERR_INVALID_ARG;
+    }
+    rt_skeleton *sk = new (std::nothrow) rt_skeleton();
+    if (!sk) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
+    sk->ctx = ctx;
+    rt_context_retain(ctx);
+    sk->n_joints = n_joints;
+    std::vector<uint32_t> order, table;
+    sk->n_levels = rt_skeleton_levels(n_joints, parents, order, sk->level_offsets);
+    rt_skeleton_pack_table(parents, order, table);
+    auto fill = [&]() -> int {
+        RT_TRY(use_device(ctx));
+        RT_TRY(upload(ctx, sk->table, table.data(), sizeof(uint32_t) * table.size()));
+        RT_TRY(upload(ctx, sk->d_level_offsets, sk->level_offsets.data(), sizeof(uint32_t) * sk->level_offsets.size()));
+        RT_TRY(upload(ctx, sk->inverse_bind, inverse_bind, 48 * (size_t)n_joints));
+        RT_TRY(sk->pose.reserve(sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)n_joints));
+        RT_TRY(sk->joints.reserve(48 * (size_t)n_joints));
+        RT_TRY(sk->palette.reserve(48 * (size_t)n_joints));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (the vectors go out of scope, the caller's array is its own again)
+        return RT_OK;
+    };
+    const int rc = fill();
+    if (rc != RT_OK) {
+        delete sk;
+        rt_context_release(ctx);
+        return rc;
+    }
+    *out = sk;
+    return RT_OK;
+}
+
+int rt_skeleton_destroy(rt_skeleton *sk)
+{
+    if (!sk) return RT_OK;
+    rt_context *ctx = sk->ctx;
+    delete sk;                // (joins the stream first: a skin kernel queued by rt_model_set_bones_from_skeleton reads a live palette)
+    rt_context_release(ctx);
+    return RT_OK;
+}
+
+int rt_skeleton_get_info(const rt_skeleton *sk, uint32_t *n_joints, uint32_t *n_levels, uint32_t *n_clips)
+{
+    RT_REQUIRE(sk, "null skeleton");
+    if (n_joints) *n_joints = sk->n_joints;
+    if (n_levels) *n_levels = sk->n_levels;
+    if (n_clips) *n_clips = (uint32_t)sk->clips.size();
+    return RT_OK;
+}
+
+int rt_skeleton_set_pose(rt_skeleton *sk, const float *trs, uint32_t mem)
+{
+    RT_REQUIRE(sk && trs, "null argument");
+    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
+    rt_context *ctx = sk->ctx;
+    RT_TRY(use_device(ctx));
+    const size_t bytes = sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)sk->n_joints;
+    // (the skeleton keeps the pose: rt_skeleton_read_pose answers from it, and a device source is the caller's again once the stream has passed the copy)
+    HIP_TRY(hipMemcpyAsync(sk->pose.p, trs, bytes, mem == RT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    RT_TRY(pose_skeleton(sk));
+    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again)
+    return RT_OK;
+}
+
+int rt_skeleton_add_clip(rt_skeleton *sk, uint32_t n_keys, const float *times, const float *trs, uint32_t *clip_out)
+{
+    RT_REQUIRE(sk && trs, "null argument");
+    uint32_t bad = 0;
+    switch (rt_skeleton_validate_times(n_keys, times, &bad)) {
+    case 0: break;
+    case 1: rt_set_error("rt_skeleton_add_clip: null argument"); return RT_ERR_INVALID_ARG;
+    case 2: rt_set_error("rt_skeleton_add_clip: a clip needs at least one key"); return RT_ERR_INVALID_ARG;
+    case 3: rt_set_error("rt_skeleton_add_clip: the time of key %u is not finite", bad); return RT_ERR_INVALID_ARG;
+    default:
+        rt_set_error("rt_skeleton_add_clip: key %u at %g after key %u at %g: the times ascend strictly", bad, (double)times[bad], bad - 1u, (double)times[bad - 1u]);
+        return RT_ERR_INVALID_ARG;
+    }
+    rt_context *ctx = sk->ctx;
+    const size_t nj = sk->n_joints, per_key = RT_SKELETON_POSE_FLOATS * nj;
+    std::vector<float> keys;
+    try {
+        keys.resize(per_key * n_keys);
+    } catch (const std::bad_alloc &) {
+        rt_set_error("out of host memory");
+        return RT_ERR_OOM;
+    }
+    for (size_t k = 0; k < n_keys; k++)                 // joint major -> component major within a key
+        for (size_t j = 0; j < nj; j++)
+            for (size_t c = 0; c < RT_SKELETON_POSE_FLOATS; c++) keys[k * per_key + c * nj + j] = trs[k * per_key + j * RT_SKELETON_POSE_FLOATS + c];
+    SkeletonClip clip;
+    clip.times.assign(times, times + n_keys);
+    RT_TRY(use_device(ctx));
+    RT_TRY(upload(ctx, clip.keys, keys.data(), sizeof(float) * keys.size()));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vector goes out of scope)
+    sk->clips.push_back(std::move(clip));               // (earlier clips keep their ids and their buffers)
+    if (clip_out) *clip_out = (uint32_t)sk->clips.size() - 1u;
+    return RT_OK;
+}
+
+int rt_skeleton_clear_clips(rt_skeleton *sk)
+{
+    RT_REQUIRE(sk, "null skeleton");
+    if (sk->clips.empty()) return RT_OK;
+    RT_TRY(use_device(sk->ctx));
+    HIP_TRY(hipStreamSynchronize(sk->ctx->stream));     // (a sampling kernel that reads a clip may still be queued)
+    sk->clips.clear();
+    return RT_OK;
+}
+
+int rt_skeleton_set_time(rt_skeleton *sk, uint32_t clip, float t)
+{
+    RT_REQUIRE(sk, "null skeleton");
+    RT_REQUIRE(!std::isnan(t), "the time is NaN");
+    if (clip >= sk->clips.size()) {
+        rt_set_error("rt_skeleton_set_time: clip %u: the skeleton has %zu (rt_skeleton_add_clip adds one)", clip, sk->clips.size());
+        return RT_ERR_STATE;
+    }
+    rt_context *ctx = sk->ctx;
+    const SkeletonClip &c = sk->clips[clip];
+    const uint32_t n_keys = (uint32_t)c.times.size();
+    uint32_t i = 0;
+    float a = 0.0f;
+    rt_skeleton_segment(n_keys, c.times.data(), t, &i, &a);
+    const size_t per_key = RT_SKELETON_POSE_FLOATS * (size_t)sk->n_joints;
+    const float *key_a = c.keys.as<float>() + per_key * i;
+    const float *key_b = n_keys == 1u ? key_a : key_a + per_key;
+    RT_TRY(use_device(ctx));
+    k_skeleton_sample<<<(sk->n_joints + 255u) / 256u, 256, 0, ctx->stream>>>(key_a, key_b, sk->n_joints, a, sk->pose.as<float>());
+    HIP_TRY(hipGetLastError());
+    return pose_skeleton(sk);
+}
+
+int rt_skeleton_read_pose(rt_skeleton *sk, float *trs)
+{
+    RT_REQUIRE(sk && trs, "null argument");
+    return read_back(sk, "rt_skeleton_read_pose", sk->pose, trs, RT_SKELETON_POSE_FLOATS);
+}
+
+int rt_skeleton_read_joints(rt_skeleton *sk, float *world3x4)
+{
+    RT_REQUIRE(sk && world3x4, "null argument");
+    return read_back(sk, "rt_skeleton_read_joints", sk->joints, world3x4, 12);
+}
+
+int rt_skeleton_read_palette(rt_skeleton *sk, float *palette3x4)
+{
+    RT_REQUIRE(sk && palette3x4, "null argument");
+    return read_back(sk, "rt_skeleton_read_palette", sk->palette, palette3x4, 12);
+}
+
+int rt_skeleton_get_palette_device_ptr(rt_skeleton *sk, void **ptr)
+{
+    RT_REQUIRE(sk && ptr, "null argument");
+    RT_TRY(require_pose(sk, "rt_skeleton_get_palette_device_ptr"));
+    *ptr = sk->palette.p;
+    return RT_OK;
+}
+
+int rt_model_set_bones_from_skeleton(rt_model *m, rt_skeleton *sk)
+{
+    RT_REQUIRE(m && sk, "null argument");
+    RT_TRY(require_pose(sk, "rt_model_set_bones_from_skeleton"));
+    if (m->skin_k == 0) {
+        rt_set_error("rt_model_set_bones_from_skeleton: the model has no skin (rt_model_set_skin gives it one)");
+        return RT_ERR_STATE;
+    }
+    if (m->skin_bones != sk->n_joints) {
+        rt_set_error("rt_model_set_bones_from_skeleton: a skin of %u bones and a skeleton of %u joints", m->skin_bones, sk->n_joints);
+        return RT_ERR_STATE;
+    }
+    if (m->ctx != sk->ctx) {
+        rt_set_error("rt_model_set_bones_from_skeleton: the model and the skeleton belong to different contexts");
+        return RT_ERR_STATE;
+    }
+    return rt_model_set_bones(m, sk->palette.as<float>(), RT_MEM_DEVICE);
+}
+
+}  // extern "C"

@@ -110,6 +110,44 @@ namespace DXRFramework
         rt_context *mHandle;
     };
 
+    // ---- RtSkeleton -- EXTENSION: the reference has no counterpart (it imports with aiProcess_PreTransformVertices, RtModel.cpp:26, which
+    // drops bones, node animation and all; the update path is the never-taken one, Helpers/BottomLevelASGenerator.h:136-176).  A joint
+    // hierarchy posed on the device: create: numJoints parents (-1: a root, else a joint before its child) and 3x4 row-major inverse bind
+    // matrices; setPose: numJoints x 10 floats tx ty tz  qx qy qz qw  sx sy sz; addClip: numKeys ascending key times and numKeys x numJoints
+    // x 10 floats, returns the clip's id; setTime: samples a clip and poses the skeleton with the result, nothing is uploaded
+    // (include/dxr_amd.h "Posed skeletons" states the arithmetic).  A skinned model takes the palette with setBones(skeleton).
+    class RtSkeleton
+    {
+    public:
+        using SharedPtr = std::shared_ptr<RtSkeleton>;
+
+        static SharedPtr create(RtContext::SharedPtr context, const int32_t *parents, const float *inverseBind3x4, uint32_t numJoints)
+        {
+            rt_skeleton *h = nullptr;
+            ThrowIfFailed(rt_skeleton_create(context->getHandle(), numJoints, parents, inverseBind3x4, &h));
+            return SharedPtr(new RtSkeleton(context, h));
+        }
+        ~RtSkeleton() { rt_skeleton_destroy(mHandle); }
+
+        rt_skeleton *getHandle() const { return mHandle; }
+        void setPose(const float *trs, bool deviceMemory = false)
+        {
+            ThrowIfFailed(rt_skeleton_set_pose(mHandle, trs, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
+        }
+        uint32_t addClip(const float *times, const float *trs, uint32_t numKeys)
+        {
+            uint32_t clip = 0;
+            ThrowIfFailed(rt_skeleton_add_clip(mHandle, numKeys, times, trs, &clip));
+            return clip;
+        }
+        void setTime(uint32_t clip, float t) { ThrowIfFailed(rt_skeleton_set_time(mHandle, clip, t)); }
+
+    private:
+        RtSkeleton(RtContext::SharedPtr ctx, rt_skeleton *h) : mContext(ctx), mHandle(h) {}
+        RtContext::SharedPtr mContext;
+        rt_skeleton *mHandle;
+    };
+
     // ---- RtModel (RtModel.h:9-40) ------------------------------------------------------
     class RtModel
     {
@@ -170,6 +208,9 @@ namespace DXRFramework
         {
             ThrowIfFailed(rt_model_set_bones(mHandle, bones3x4, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
         }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): the palette of a posed RtSkeleton of as many joints
+        // as the skin has bones, in place on the device
+        void setBones(const RtSkeleton::SharedPtr &skeleton) { ThrowIfFailed(rt_model_set_bones_from_skeleton(mHandle, skeleton->getHandle())); }
 
         // EXTENSIONS (the reference reads only mVertices / mNormals of an imported mesh, RtModel.cpp:26, :38-45, never its blend shapes; the
         // update path is the never-taken one, Helpers/BottomLevelASGenerator.h:136-176): morph targets.  setMorphTargets: numTargets sparse

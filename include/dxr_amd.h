@@ -36,6 +36,7 @@ typedef struct rt_context  rt_context;
 typedef struct rt_model    rt_model;
 typedef struct rt_scene    rt_scene;
 typedef struct rt_pipeline rt_pipeline;
+typedef struct rt_skeleton rt_skeleton;
 typedef struct rt_progressive_host rt_progressive_host;
 
 /* ---- library ------------------------------------------------------------- */
@@ -303,6 +304,84 @@ int rt_model_get_morph_targets(const rt_model *m, uint32_t *n_targets, uint32_t 
  * RT_ERR_INVALID_ARG; a model without targets is RT_ERR_STATE (the message names rt_model_set_morph_targets).  rt_model_set_vertices /
  * rt_model_set_positions on a morphed model still write the current vertices and leave the base alone. */
 int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */, uint32_t mem /* RT_MEM_HOST | RT_MEM_DEVICE */);
+
+/* Posed skeletons -- EXTENSIONS: the reference imports with aiProcess_PreTransformVertices (libs/DXRFramework/RtModel.cpp:26), which drops
+ * bones, node animation and all; the update path a pose would take is the generators' never-taken one
+ * (Helpers/BottomLevelASGenerator.h:136-176).  rt_model_set_bones above takes finished matrices and knows no hierarchy; the hierarchy lives
+ * HERE.  A SKELETON is n_joints joints, each with a parent that comes before it (or -1: a root) and an inverse bind matrix; a POSE is ten
+ * floats per joint, translation, rotation quaternion, scale; from a pose the device computes every joint's world matrix W_j and the PALETTE
+ * M_j that rt_model_set_bones takes, and keeps both; a CLIP is a baked pose per key time, sampled on the device from one float of time.  A
+ * frame of an animated character is rt_skeleton_set_time, rt_model_set_bones_from_skeleton, rt_scene_update, and no per-frame array crosses
+ * to the device; several models whose skins have n_joints bones may share one skeleton and one palette.
+ * The definition, fp32 throughout, every product and every sum one rounded operation, no contraction.  Values are taken as given: a
+ * quaternion is not normalised by rt_skeleton_set_pose, and NaN, inf, zero and negative scales are no errors.
+ *   local   L of a joint from t, q = (x, y, z, w), s:
+ *           xx = x*x, yy = y*y, zz = z*z, xy = x*y, xz = x*z, yz = y*z, wx = w*x, wy = w*y, wz = w*z
+ *           R00 = 1 - 2*(yy + zz)   R01 = 2*(xy - wz)       R02 = 2*(xz + wy)
+ *           R10 = 2*(xy + wz)       R11 = 1 - 2*(xx + zz)   R12 = 2*(yz - wx)
+ *           R20 = 2*(xz - wy)       R21 = 2*(yz + wx)       R22 = 1 - 2*(xx + yy)
+ *           L[r][c] = R[r][c] * s_c (T.R.S) and L[r][3] = t_r.  Column vectors, as the instance transforms: q = (0, 0, sqrt(1/2), sqrt(1/2))
+ *           turns +x into +y.
+ *   product C = A o B of two 3x4 affine matrices:
+ *           C[r][c] = (A[r][0] B[0][c] + A[r][1] B[1][c]) + A[r][2] B[2][c] for c < 3
+ *           C[r][3] = ((A[r][0] B[0][3] + A[r][1] B[1][3]) + A[r][2] B[2][3]) + A[r][3]
+ *   world   W_j = L_j for a root, bit for bit; otherwise W_j = W_parent(j) o L_j.  The recursion fixes the association: level by level, or
+ *           down a joint's chain from its root, the bits are the same.
+ *   palette M_j = W_j o inverse_bind_j, always multiplied, for an identity too.
+ *   sampling clip c of K keys at t.  The host finds the segment and passes two scalars (i, a): K == 1 or t <= times[0] gives i = 0, a = 0;
+ *           t >= times[K-1] gives i = K-2, a = 1; otherwise i is the largest key with times[i] <= t and
+ *           a = (t - times[i]) / (times[i+1] - times[i]) in fp32.  Looping is the caller's.  Per joint, with A = key i and B = key i+1 (B = A
+ *           when K == 1): every translation and scale component is A_c + (a * (B_c - A_c)).  The quaternion: d = ((Ax Bx + Ay By) + Az Bz) +
+ *           Aw Bw; if d < 0 every component of B is negated (the shortest path; a NaN d negates nothing); q_c = A_c + (a * (B_c - A_c));
+ *           n = ((qx qx + qy qy) + qz qz) + qw qw; q = q * (1 / sqrt(n)) if 0 < n < inf, else (0, 0, 0, 1): the rule of
+ *           rt_model_recompute_normals.  No slerp.  The result is the local pose, and it is posed as by rt_skeleton_set_pose.
+ * Validation is done on the host, and nothing changes when a call refuses.  Setting a pose touches no model and no scene.
+ * rt_skeleton_create: a null argument is RT_ERR_INVALID_ARG; so is n_joints outside 1 .. 65536 (the skin's bone limit), and a parent that is
+ * neither -1 nor < j -- parents come before children -- (the message names the joint).  inverse_bind: n_joints x 12, 3x4 row-major, as
+ * instance transforms.  The arrays are copied. */
+int rt_skeleton_create(rt_context *ctx, uint32_t n_joints,
+                       const int32_t *parents      /* n_joints; -1: a root */,
+                       const float *inverse_bind   /* n_joints x 12, 3x4 row-major, as instance transforms */,
+                       rt_skeleton **out);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): joins the context's stream first, so destroying a skeleton right
+ * after rt_model_set_bones_from_skeleton is legal: the skin kernel already queued reads a live palette. */
+int rt_skeleton_destroy(rt_skeleton *sk);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the joints, the levels of the hierarchy (a forest of roots: 1)
+ * and the clips; each may be NULL */
+int rt_skeleton_get_info(const rt_skeleton *sk, uint32_t *n_joints, uint32_t *n_levels, uint32_t *n_clips);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local pose, n_joints x 10 floats tx ty tz  qx qy qz qw
+ * sx sy sz, and from it W and the palette by the definition above, on the device, on the context's stream.  `mem` is RT_MEM_HOST (the
+ * stream is synchronised before the call returns) or RT_MEM_DEVICE (copied device to device into the skeleton's own pose, ordered on the
+ * context's stream), as for rt_model_set_bones; a null argument or an unknown `mem` is RT_ERR_INVALID_ARG. */
+int rt_skeleton_set_pose(rt_skeleton *sk, const float *trs /* n_joints x 10: tx ty tz  qx qy qz qw  sx sy sz */, uint32_t mem);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): a baked clip, one pose of every joint per key; host arrays.
+ * RT_ERR_INVALID_ARG for a null sk, times or trs, for n_keys == 0, for a time that is not finite and for times that do not ascend strictly
+ * (the message names the key).  *clip_out (may be NULL) is the clip's id; adding clips keeps earlier clip ids valid. */
+int rt_skeleton_add_clip(rt_skeleton *sk, uint32_t n_keys, const float *times /* n_keys */,
+                         const float *trs /* n_keys x n_joints x 10, key major */, uint32_t *clip_out);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): removes every clip; ids start at 0 again.  The pose stays. */
+int rt_skeleton_clear_clips(rt_skeleton *sk);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): samples clip `clip` at t and poses the skeleton with the result,
+ * by the definition above: two kernels on the context's stream, nothing is uploaded and nothing waits.  RT_ERR_INVALID_ARG for a NaN t
+ * (-inf and +inf are the first and the last key), RT_ERR_STATE for an unknown clip. */
+int rt_skeleton_set_time(rt_skeleton *sk, uint32_t clip, float t);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local pose last set or sampled.  This and the calls below
+ * that return what a pose made are RT_ERR_STATE before the first pose (the message names rt_skeleton_set_pose); the reads synchronise. */
+int rt_skeleton_read_pose(rt_skeleton *sk, float *trs /* n_joints x 10 */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): W_j, n_joints x 12: for attaching instances to joints
+ * (rt_scene_set_instance_transform) */
+int rt_skeleton_read_joints(rt_skeleton *sk, float *world3x4 /* n_joints x 12 */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): M_j, n_joints x 12 */
+int rt_skeleton_read_palette(rt_skeleton *sk, float *palette3x4 /* n_joints x 12 */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the palette where it lives, n_joints x 12 floats of device memory
+ * that every later pose overwrites on the context's stream and rt_skeleton_destroy frees */
+int rt_skeleton_get_palette_device_ptr(rt_skeleton *sk, void **ptr);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): poses a skinned model from the skeleton's palette.  A null argument
+ * is RT_ERR_INVALID_ARG; RT_ERR_STATE before the skeleton's first pose (the message names rt_skeleton_set_pose), for a model without a skin
+ * (the message names rt_model_set_skin), for a skin whose n_bones != n_joints (the message gives both numbers) and for a model and a skeleton
+ * of different contexts.  Otherwise it is exactly rt_model_set_bones(m, palette, RT_MEM_DEVICE): frames a deferred pipeline still holds are
+ * rendered first, the model is left CHANGED and every built scene that holds it STALE until rt_scene_update or rt_scene_build. */
+int rt_model_set_bones_from_skeleton(rt_model *m, rt_skeleton *sk);
 
 /* ---- raw TraceRay over a batch (HLSL TraceRay semantics, used by tests and
  *      the traversal benchmark; ProgressiveRaytracing.hlsl:34,53,
