@@ -1,12 +1,9 @@
-// rt_api.hip -- C-ABI entry points for context, model, scene and batch TraceRay
-// (include/dxr_amd.h).  Stand-ins for libs/DXRFramework/Rt{Context,Model,Scene}.
+// rt_api.hip -- C-ABI entry points for error state, debug options, context, device memory, scene and batch TraceRay, and the device
+// math probes (include/dxr_amd.h).  Stand-ins for libs/DXRFramework/Rt{Context,Scene}; the model is rt_model.hip.
 #include <cmath>
 #include <cstring>
 #include <new>
 
-#include "rt_adjacency.h"
-#include "rt_morph.h"
-#include "rt_skin.h"
 #include "rt_trace_device.h"
 
 static thread_local std::string g_last_error;
@@ -78,149 +75,6 @@ __global__ void k_debug_sample(int kind, const uint32_t *__restrict__ seeds, con
     vout[3 * i] = o.x; vout[3 * i + 1] = o.y; vout[3 * i + 2] = o.z;
     if (pdf_brdf) { pdf_brdf[2 * i] = pdf; pdf_brdf[2 * i + 1] = brdf; }
     if (seeds_out) seeds_out[i] = s;
-}
-
-// ---- deforming meshes: new vertices for a model (rt_model_set_positions, rt_model_recompute_normals) ----
-
-// count x 3 floats into the positions of the 24-byte vertex records first .. first + count - 1; the normals stay
-__global__ void k_set_positions(rt_vertex *__restrict__ verts, uint32_t first, uint32_t count, const float *__restrict__ xyz)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= count) return;
-    rt_float3 p;
-    p.x = xyz[3 * (size_t)k]; p.y = xyz[3 * (size_t)k + 1]; p.z = xyz[3 * (size_t)k + 2];
-    verts[(size_t)first + k].position = p;
-}
-
-// One lane per vertex: the sum of cross(p1 - p0, p2 - p0) over the triangles of its CSR run (rt_adjacency.h: ascending, each once), in that
-// order, normalised; a sum whose squared length is 0, inf or NaN gives (0, 0, 0).  No atomics: the order of an fp32 sum is part of the result.
-__global__ void k_vertex_normals(rt_vertex *__restrict__ verts, uint32_t n_verts, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ off,
-                                 const uint32_t *__restrict__ tris)
-{
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_verts) return;
-    f3 s = mk3(0.0f, 0.0f, 0.0f);
-    for (uint32_t e = off[v]; e < off[v + 1]; e++) {
-        const size_t t = tris[e];
-        const rt_float3 a = verts[idx[3 * t]].position, b = verts[idx[3 * t + 1]].position, c = verts[idx[3 * t + 2]].position;
-        const f3 p0 = mk3(a.x, a.y, a.z);
-        s = s + cross(mk3(b.x, b.y, b.z) - p0, mk3(c.x, c.y, c.z) - p0);
-    }
-    const float d = dot(s, s);
-    const f3 n = (d > 0.0f && d < __uint_as_float(0x7f800000u)) ? normalize(s) : mk3(0.0f, 0.0f, 0.0f);
-    rt_float3 out;
-    out.x = n.x; out.y = n.y; out.z = n.z;
-    verts[v].normal = out;
-}
-
-// ---- skeletal animation: a model's vertices from its rest pose and a bone palette (rt_model_set_bones) ----
-
-// One lane per vertex; a wave reads and writes 64 consecutive 24-byte records and, per slot, 64 consecutive indices and weights (the skin is
-// slot major: rt_skin.h).  The 12 entries of the blended matrix are weight[0] * M[bone[0]], then + weight[k] * M[bone[k]] in slot order, every
-// slot evaluated; position and normal as include/dxr_amd.h states them, no FMA.  K is a template parameter: the slot loop is unrolled and B
-// lives in registers.  LDS: the palette (n_bones <= RT_SKIN_LDS_BONES) is copied into LDS by the whole block, coalesced, and gathered from
-// there; else the lanes gather it from global memory.  The arithmetic is the same statements either way: the same bytes.
-template <int K, bool LDS>
-__global__ void __launch_bounds__(256) k_skin_vertices(rt_vertex *__restrict__ verts, const rt_vertex *__restrict__ rest, uint32_t n_verts,
-                                                       const uint16_t *__restrict__ bone, const float *__restrict__ weight,
-                                                       const float *__restrict__ palette, uint32_t n_bones)
-{
-    __shared__ float s_palette[LDS ? 12u * RT_SKIN_LDS_BONES : 1u];
-    if (LDS) {
-        for (uint32_t e = threadIdx.x; e < 12u * n_bones; e += 256u) s_palette[e] = palette[e];
-        __syncthreads();
-    }
-    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
-    if (v >= n_verts) return;
-    const float *pal = LDS ? s_palette : palette;
-    float B[12];
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        const size_t at = (size_t)k * n_verts + v;
-        const float w = weight[at];
-        const float *M = pal + 12u * (uint32_t)bone[at];
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            const float t = w * M[e];
-            B[e] = k == 0 ? t : B[e] + t;
-        }
-    }
-    const rt_vertex r = rest[v];
-    const float x = r.position.x, y = r.position.y, z = r.position.z;
-    rt_vertex o;
-    o.position.x = ((B[0] * x + B[1] * y) + B[2] * z) + B[3];
-    o.position.y = ((B[4] * x + B[5] * y) + B[6] * z) + B[7];
-    o.position.z = ((B[8] * x + B[9] * y) + B[10] * z) + B[11];
-    const float nx = r.normal.x, ny = r.normal.y, nz = r.normal.z;
-    const f3 s = mk3((B[0] * nx + B[1] * ny) + B[2] * nz, (B[4] * nx + B[5] * ny) + B[6] * nz, (B[8] * nx + B[9] * ny) + B[10] * nz);
-    const float d = dot(s, s);
-    const f3 n = (d > 0.0f && d < __uint_as_float(0x7f800000u)) ? normalize(s) : mk3(0.0f, 0.0f, 0.0f);
-    o.normal.x = n.x; o.normal.y = n.y; o.normal.z = n.z;
-    verts[v] = o;
-}
-
-template <int K>
-void launch_skin(hipStream_t st, bool lds, rt_vertex *verts, const rt_vertex *rest, uint32_t n_verts, const uint16_t *bone, const float *weight,
-                 const float *palette, uint32_t n_bones)
-{
-    const uint32_t blocks = (n_verts + 255u) / 256u;
-    if (lds) k_skin_vertices<K, true><<<blocks, 256, 0, st>>>(verts, rest, n_verts, bone, weight, palette, n_bones);
-    else k_skin_vertices<K, false><<<blocks, 256, 0, st>>>(verts, rest, n_verts, bone, weight, palette, n_bones);
-}
-
-// ---- morph targets: a model's vertices from its base and a weight per target (rt_model_set_morph_weights) ----
-
-// One lane per vertex, a block of 256 is four whole slices of the SELL-64 layout (rt_morph.h).  A lane walks its own `count` cells, 64 apart:
-// at step j the lanes of a wave that still run read 64 consecutive 16-bit targets and 64 consecutive 12-byte deltas, and lanes whose run is
-// shorter sit masked until the widest lane of the wave is through (the padding of a slice is never read).  The weights are gathered from
-// global memory, 4 B per target and cache resident; no LDS staging -- the skin kernel's LDS palette was the slower path at its edge (DESIGN.md
-// section 7, round 9), and nobody has measured this kernel with one.  The sums are include/dxr_amd.h's: p = p + (w * dp) per component in
-// ascending target order, every entry evaluated, no FMA.  A vertex without entries is copied, all 24 bytes; without NORMALS so is every normal.
-// `dst` is the model's vertices or its skin's rest pose (the host chooses); `base` is never either.
-template <bool NORMALS>
-__global__ void __launch_bounds__(256) k_morph_vertices(rt_vertex *__restrict__ dst, const rt_vertex *__restrict__ base, uint32_t n_verts,
-                                                        const uint32_t *__restrict__ count, const uint32_t *__restrict__ slice_cell,
-                                                        const uint16_t *__restrict__ target, const float *__restrict__ dpos,
-                                                        const float *__restrict__ dnrm, const float *__restrict__ weights)
-{
-    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
-    if (v >= n_verts) return;
-    rt_vertex o = base[v];
-    const uint32_t n = count[v];
-    if (n != 0u) {
-        size_t cell = (size_t)slice_cell[v >> 6] + (v & 63u);
-        f3 s = mk3(o.normal.x, o.normal.y, o.normal.z);
-        for (uint32_t j = 0; j < n; j++, cell += 64u) {
-            const float w = weights[target[cell]];
-            const float *dp = dpos + 3u * cell;
-            o.position.x = o.position.x + w * dp[0];
-            o.position.y = o.position.y + w * dp[1];
-            o.position.z = o.position.z + w * dp[2];
-            if (NORMALS) {
-                const float *dn = dnrm + 3u * cell;
-                s = mk3(s.x + w * dn[0], s.y + w * dn[1], s.z + w * dn[2]);
-            }
-        }
-        if (NORMALS) {
-            const float d = dot(s, s);
-            const f3 nn = (d > 0.0f && d < __uint_as_float(0x7f800000u)) ? normalize(s) : mk3(0.0f, 0.0f, 0.0f);
-            o.normal.x = nn.x; o.normal.y = nn.y; o.normal.z = nn.z;
-        }
-    }
-    dst[v] = o;
-}
-
-int upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
-{
-    RT_TRY(b.reserve(bytes));
-    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return RT_OK;
-}
-
-int use_device(const rt_context *ctx)
-{
-    HIP_TRY(hipSetDevice(ctx->device));
-    return RT_OK;
 }
 
 }  // namespace
@@ -397,11 +251,6 @@ rt_context::~rt_context()
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
-rt_model::~rt_model()
-{
-    if (ctx) (void)hipSetDevice(ctx->device);
-}
-
 rt_scene::~rt_scene()
 {
     (void)hipSetDevice(ctx->device);
@@ -418,7 +267,7 @@ extern "C" {
 int rt_context_synchronize(rt_context *ctx)
 {
     RT_REQUIRE(ctx, "null context");
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));          // frames a deferred pipeline still holds are part of "everything submitted"
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RT_OK;
@@ -437,7 +286,7 @@ int rt_context_get_stream(rt_context *ctx, void **hip_stream_out)
     // (a caller that asks for the stream is about to order its own work behind "everything submitted": the frames a deferred
     // pipeline still holds go onto the stream first -- ADVICE r4)
     *hip_stream_out = (void *)ctx->stream;
-    if (!ctx->deferred.empty()) { RT_TRY(use_device(ctx)); RT_TRY(rt_context_flush_deferred(ctx)); }
+    if (!ctx->deferred.empty()) { RT_TRY(rt_use_device(ctx)); RT_TRY(rt_context_flush_deferred(ctx)); }
     return RT_OK;
 }
 
@@ -451,7 +300,7 @@ int rt_context_get_device(rt_context *ctx, int *device_out)
 int rt_device_alloc(rt_context *ctx, size_t bytes, void **device_ptr)
 {
     RT_REQUIRE(ctx && device_ptr, "null argument");
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     hipError_t e = hipMalloc(device_ptr, bytes ? bytes : 16);
     if (e != hipSuccess) {
         rt_set_error("hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
@@ -463,7 +312,7 @@ int rt_device_alloc(rt_context *ctx, size_t bytes, void **device_ptr)
 int rt_device_free(rt_context *ctx, void *device_ptr)
 {
     RT_REQUIRE(ctx, "null context");
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (device_ptr) HIP_TRY(hipFree(device_ptr));
     return RT_OK;
@@ -472,7 +321,7 @@ int rt_device_free(rt_context *ctx, void *device_ptr)
 int rt_device_upload(rt_context *ctx, void *device_dst, const void *host_src, size_t bytes)
 {
     RT_REQUIRE(ctx && (bytes == 0 || (device_dst && host_src)), "null argument");
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     if (bytes) HIP_TRY(hipMemcpyAsync(device_dst, host_src, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RT_OK;
@@ -481,386 +330,10 @@ int rt_device_upload(rt_context *ctx, void *device_dst, const void *host_src, si
 int rt_device_download(rt_context *ctx, void *host_dst, const void *device_src, size_t bytes)
 {
     RT_REQUIRE(ctx && (bytes == 0 || (host_dst && device_src)), "null argument");
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));          // (device_src may be an output a deferred pipeline still owes frames to)
     if (bytes) HIP_TRY(hipMemcpyAsync(host_dst, device_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// ---- model -----------------------------------------------------------------------
-
-static int model_finish(rt_context *ctx, rt_model *m, rt_model **out)
-{
-    m->ctx = ctx;
-    rt_context_retain(ctx);
-    m->n_verts = (uint32_t)m->h_verts.size();
-    m->n_tris = (uint32_t)(m->h_idx.size() / 3);
-    for (uint32_t i : m->h_idx)
-        if (i >= m->n_verts) {
-            rt_set_error("index %u out of range (%u vertices)", i, m->n_verts);
-            delete m;
-            rt_context_release(ctx);
-            return RT_ERR_INVALID_ARG;
-        }
-    int rc = use_device(ctx);
-    if (rc == RT_OK) rc = upload(ctx, m->d_verts, m->h_verts.data(), sizeof(rt_vertex) * m->h_verts.size());
-    if (rc == RT_OK) rc = upload(ctx, m->d_idx, m->h_idx.data(), sizeof(uint32_t) * m->h_idx.size());
-    if (rc == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { rt_set_error("geometry upload failed"); rc = RT_ERR_HIP; }
-    if (rc != RT_OK) {
-        delete m;
-        rt_context_release(ctx);
-        return rc;
-    }
-    *out = m;
-    return RT_OK;
-}
-
-int rt_model_create_from_arrays(rt_context *ctx, const rt_vertex *verts, uint32_t n_verts, const uint32_t *indices,
-                                uint32_t n_tris, rt_model **out)
-{
-    RT_REQUIRE(ctx && verts && indices && out, "null argument");
-    RT_REQUIRE(n_verts > 0 && n_tris > 0, "a model needs at least one triangle");
-    rt_model *m = new (std::nothrow) rt_model();
-    if (!m) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    m->h_verts.assign(verts, verts + n_verts);
-    m->h_idx.assign(indices, indices + 3 * (size_t)n_tris);
-    return model_finish(ctx, m, out);
-}
-
-int rt_model_create_from_obj(rt_context *ctx, const char *path, rt_model **out)
-{
-    RT_REQUIRE(ctx && path && out, "null argument");
-    rt_model *m = new (std::nothrow) rt_model();
-    if (!m) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    int rc = rt_obj_parse(path, m->h_verts, m->h_idx);
-    if (rc != RT_OK) { delete m; return rc; }
-    return model_finish(ctx, m, out);
-}
-
-int rt_model_create_from_file(rt_context *ctx, const char *path, rt_model **out)
-{
-    RT_REQUIRE(ctx && path && out, "null argument");
-    const size_t n = strlen(path);
-    const bool fbx = n >= 4 && path[n - 4] == '.' && (path[n - 3] | 0x20) == 'f' && (path[n - 2] | 0x20) == 'b' && (path[n - 1] | 0x20) == 'x';
-    if (!fbx) return rt_model_create_from_obj(ctx, path, out);
-    rt_model *m = new (std::nothrow) rt_model();
-    if (!m) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    int rc = rt_fbx_parse(path, m->h_verts, m->h_idx);
-    if (rc != RT_OK) { delete m; return rc; }
-    return model_finish(ctx, m, out);
-}
-
-int rt_model_get_counts(const rt_model *m, uint32_t *n_verts, uint32_t *n_tris)
-{
-    RT_REQUIRE(m, "null model");
-    if (n_verts) *n_verts = m->n_verts;
-    if (n_tris) *n_tris = m->n_tris;
-    return RT_OK;
-}
-
-// A set has gone through its checks and is about to write d_verts: frames a deferred pipeline holds are rendered first (they see the
-// mesh as it was).
-static int model_before_set(rt_model *m)
-{
-    RT_TRY(use_device(m->ctx));
-    return rt_context_flush_deferred(m->ctx);
-}
-
-// ... and has been queued: the BLAS is older than the vertices, every built scene that holds the model is stale.
-static void model_changed(rt_model *m)
-{
-    m->geom_gen++;
-    m->built = false;         // rt_scene_update and rt_scene_build rebuild the BLAS (rt_build_blas)
-    for (rt_scene *s : m->scenes)
-        if (s->updatable) s->built = false;            // (never built, or instances added since: the next build reads the new vertices anyway)
-}
-
-static int model_set_range_check(const rt_model *m, const char *who, uint32_t first, uint32_t count)
-{
-    if (first > m->n_verts || count > m->n_verts - first) {
-        rt_set_error("%s: vertices %u .. %llu out of range: the model has %u", who, first, (unsigned long long)first + count, m->n_verts);
-        return RT_ERR_STATE;
-    }
-    return RT_OK;
-}
-
-int rt_model_set_vertices(rt_model *m, uint32_t first, uint32_t count, const rt_vertex *verts, uint32_t mem)
-{
-    RT_REQUIRE(m && (verts || count == 0), "null argument");
-    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
-    RT_TRY(model_set_range_check(m, "rt_model_set_vertices", first, count));
-    if (count == 0) return RT_OK;
-    RT_TRY(model_before_set(m));
-    hipStream_t st = m->ctx->stream;
-    rt_vertex *dst = m->d_verts.as<rt_vertex>() + first;
-    const size_t bytes = sizeof(rt_vertex) * (size_t)count;
-    if (mem == RT_MEM_DEVICE) {
-        HIP_TRY(hipMemcpyAsync(dst, verts, bytes, hipMemcpyDeviceToDevice, st));
-        m->h_verts_stale = true;
-    } else {
-        HIP_TRY(hipMemcpyAsync(dst, verts, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));             // (the caller's array is its own again when the call returns)
-        if (!m->h_verts_stale) memcpy(m->h_verts.data() + first, verts, bytes);
-    }
-    model_changed(m);
-    return RT_OK;
-}
-
-int rt_model_set_positions(rt_model *m, uint32_t first, uint32_t count, const float *xyz, uint32_t mem)
-{
-    RT_REQUIRE(m && (xyz || count == 0), "null argument");
-    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
-    RT_TRY(model_set_range_check(m, "rt_model_set_positions", first, count));
-    if (count == 0) return RT_OK;
-    rt_context *ctx = m->ctx;
-    RT_TRY(model_before_set(m));
-    const float *src = xyz;
-    if (mem == RT_MEM_HOST) {
-        RT_TRY(upload(ctx, ctx->scratch[0], xyz, 12 * (size_t)count));
-        src = ctx->scratch[0].as<float>();
-    }
-    k_set_positions<<<(count + 255u) / 256u, 256, 0, ctx->stream>>>(m->d_verts.as<rt_vertex>(), first, count, src);
-    HIP_TRY(hipGetLastError());
-    if (mem == RT_MEM_HOST) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (!m->h_verts_stale)
-            for (uint32_t k = 0; k < count; k++) memcpy(&m->h_verts[(size_t)first + k].position, xyz + 3 * (size_t)k, 12);
-    } else m->h_verts_stale = true;
-    model_changed(m);
-    return RT_OK;
-}
-
-int rt_model_recompute_normals(rt_model *m)
-{
-    RT_REQUIRE(m, "null model");
-    rt_context *ctx = m->ctx;
-    RT_TRY(model_before_set(m));
-    if (!m->adj_ready) {      // once per model: the index list never changes
-        std::vector<uint32_t> off, tris;
-        if (m->n_tris > 0x55555555u || !rt_build_adjacency(m->h_idx.data(), m->n_tris, m->n_verts, off, tris)) {
-            rt_set_error("rt_model_recompute_normals: no adjacency for %u triangles over %u vertices", m->n_tris, m->n_verts);
-            return RT_ERR_UNSUPPORTED;
-        }
-        RT_TRY(upload(ctx, m->adj_off, off.data(), 4 * off.size()));
-        RT_TRY(upload(ctx, m->adj_tris, tris.data(), 4 * tris.size()));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));    // (the vectors go out of scope)
-        m->adj_ready = true;
-    }
-    k_vertex_normals<<<(m->n_verts + 255u) / 256u, 256, 0, ctx->stream>>>(m->d_verts.as<rt_vertex>(), m->n_verts, m->d_idx.as<uint32_t>(),
-                                                                          m->adj_off.as<uint32_t>(), m->adj_tris.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    m->h_verts_stale = true;
-    model_changed(m);
-    return RT_OK;
-}
-
-int rt_model_set_skin(rt_model *m, uint32_t influences, uint32_t n_bones, const uint32_t *bone_indices, const float *weights)
-{
-    RT_REQUIRE(m, "null model");
-    rt_context *ctx = m->ctx;
-    if (influences == 0) {    // no skin: the vertices stay as the last pose left them
-        RT_TRY(use_device(ctx));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (a kernel that reads the buffers may still be queued)
-        m->skin_k = m->skin_bones = 0;
-        m->skin_bone.release(); m->skin_weight.release(); m->skin_rest.release();
-        return RT_OK;
-    }
-    uint32_t bad_v = 0, bad_k = 0;
-    switch (rt_skin_validate(m->n_verts, influences, n_bones, bone_indices, weights, &bad_v, &bad_k)) {
-    case 0: break;
-    case 1: rt_set_error("rt_model_set_skin: null argument"); return RT_ERR_INVALID_ARG;
-    case 2: rt_set_error("rt_model_set_skin: %u influences per vertex: 1 .. %u are supported (0 removes the skin)", influences, RT_SKIN_MAX_INFLUENCES); return RT_ERR_INVALID_ARG;
-    case 3: rt_set_error("rt_model_set_skin: %u bones: 1 .. %u are supported", n_bones, RT_SKIN_MAX_BONES); return RT_ERR_INVALID_ARG;
-    default:
-        rt_set_error("rt_model_set_skin: vertex %u, slot %u names bone %u of %u", bad_v, bad_k, bone_indices[(size_t)bad_v * influences + bad_k], n_bones);
-        return RT_ERR_INVALID_ARG;
-    }
-    std::vector<uint16_t> bone;
-    std::vector<float> weight;
-    rt_skin_pack(m->n_verts, influences, bone_indices, weights, bone, weight);
-    RT_TRY(use_device(ctx));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (a skin that is replaced: a kernel that reads the old one may still be queued)
-    m->skin_k = m->skin_bones = 0;                      // (no skin until all of the new one is there)
-    RT_TRY(upload(ctx, m->skin_bone, bone.data(), sizeof(uint16_t) * bone.size()));
-    RT_TRY(upload(ctx, m->skin_weight, weight.data(), sizeof(float) * weight.size()));
-    const size_t bytes = sizeof(rt_vertex) * (size_t)m->n_verts;
-    RT_TRY(m->skin_rest.reserve(bytes));
-    HIP_TRY(hipMemcpyAsync(m->skin_rest.p, m->d_verts.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));       // the rest pose: the vertices as they are
-    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope)
-    m->skin_k = influences;
-    m->skin_bones = n_bones;
-    return RT_OK;             // the vertices are what they were: nothing changed, built scenes stay built
-}
-
-int rt_model_get_skin(const rt_model *m, uint32_t *influences, uint32_t *n_bones)
-{
-    RT_REQUIRE(m, "null model");
-    if (influences) *influences = m->skin_k;
-    if (n_bones) *n_bones = m->skin_bones;
-    return RT_OK;
-}
-
-int rt_model_set_bones(rt_model *m, const float *bones3x4, uint32_t mem)
-{
-    RT_REQUIRE(m && bones3x4, "null argument");
-    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
-    if (m->skin_k == 0) {
-        rt_set_error("rt_model_set_bones: the model has no skin (rt_model_set_skin gives it one)");
-        return RT_ERR_STATE;
-    }
-    rt_context *ctx = m->ctx;
-    RT_TRY(model_before_set(m));
-    const float *palette = bones3x4;
-    if (mem == RT_MEM_HOST) {
-        RT_TRY(upload(ctx, ctx->scratch[0], bones3x4, 48 * (size_t)m->skin_bones));
-        palette = ctx->scratch[0].as<float>();
-    }
-    const bool lds = m->skin_bones <= RT_SKIN_LDS_BONES;
-    rt_vertex *verts = m->d_verts.as<rt_vertex>();
-    const rt_vertex *rest = m->skin_rest.as<rt_vertex>();
-    const uint16_t *bone = m->skin_bone.as<uint16_t>();
-    const float *weight = m->skin_weight.as<float>();
-    switch (m->skin_k) {      // (every pose from the rest pose, the whole mesh)
-#define RT_SKIN_CASE(K) case K: launch_skin<K>(ctx->stream, lds, verts, rest, m->n_verts, bone, weight, palette, m->skin_bones); break
-    RT_SKIN_CASE(1); RT_SKIN_CASE(2); RT_SKIN_CASE(3); RT_SKIN_CASE(4); RT_SKIN_CASE(5); RT_SKIN_CASE(6); RT_SKIN_CASE(7); RT_SKIN_CASE(8);
-#undef RT_SKIN_CASE
-    default: rt_set_error("rt_model_set_bones: %u influences", m->skin_k); return RT_ERR_STATE;
-    }
-    HIP_TRY(hipGetLastError());
-    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again, and the scratch buffer anybody's)
-    m->h_verts_stale = true;
-    model_changed(m);
-    return RT_OK;
-}
-
-int rt_model_set_morph_targets(rt_model *m, uint32_t n_targets, const uint32_t *target_offsets, const uint32_t *vertex_indices,
-                               const float *position_deltas, const float *normal_deltas)
-{
-    RT_REQUIRE(m, "null model");
-    rt_context *ctx = m->ctx;
-    if (n_targets == 0) {     // no targets: the vertices stay as the last weights left them
-        RT_TRY(use_device(ctx));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (a kernel that reads the buffers may still be queued)
-        m->morph_targets = m->morph_entries = 0;
-        m->morph_normals = false;
-        m->morph_count.release(); m->morph_slice.release(); m->morph_target.release();
-        m->morph_dpos.release(); m->morph_dnrm.release(); m->morph_base.release();
-        return RT_OK;
-    }
-    uint32_t bad_t = 0, bad_e = 0;
-    switch (rt_morph_validate(m->n_verts, n_targets, target_offsets, vertex_indices, position_deltas, &bad_t, &bad_e)) {
-    case 0: break;
-    case 1: rt_set_error("rt_model_set_morph_targets: null argument"); return RT_ERR_INVALID_ARG;
-    case 2: rt_set_error("rt_model_set_morph_targets: %u targets: up to %u are supported (0 removes them)", n_targets, RT_MORPH_MAX_TARGETS); return RT_ERR_INVALID_ARG;
-    case 3: rt_set_error("rt_model_set_morph_targets: target_offsets[0] is %u, not 0", target_offsets[0]); return RT_ERR_INVALID_ARG;
-    case 4:
-        rt_set_error("rt_model_set_morph_targets: target %u: its offsets decrease, %u to %u", bad_t, target_offsets[bad_t], target_offsets[bad_t + 1]);
-        return RT_ERR_INVALID_ARG;
-    case 5:
-        rt_set_error("rt_model_set_morph_targets: target %u, entry %u names vertex %u of %u", bad_t, bad_e, vertex_indices[bad_e], m->n_verts);
-        return RT_ERR_INVALID_ARG;
-    case 6:
-        rt_set_error("rt_model_set_morph_targets: target %u, entry %u names vertex %u after vertex %u: the indices of a target ascend strictly", bad_t,
-                     bad_e, vertex_indices[bad_e], vertex_indices[bad_e - 1]);
-        return RT_ERR_INVALID_ARG;
-    default:
-        rt_set_error("rt_model_set_morph_targets: the packed targets would take 2^32 cells or more");
-        return RT_ERR_UNSUPPORTED;
-    }
-    rt_morph_packed pk;
-    rt_morph_pack(m->n_verts, n_targets, target_offsets, vertex_indices, position_deltas, normal_deltas, pk);
-    RT_TRY(use_device(ctx));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (targets that are replaced: a kernel that reads the old ones may still be queued)
-    m->morph_targets = m->morph_entries = 0;            // (no targets until all of the new ones are there)
-    RT_TRY(upload(ctx, m->morph_count, pk.count.data(), sizeof(uint32_t) * pk.count.size()));
-    RT_TRY(upload(ctx, m->morph_slice, pk.slice_cell.data(), sizeof(uint32_t) * pk.slice_cell.size()));
-    RT_TRY(upload(ctx, m->morph_target, pk.target.data(), sizeof(uint16_t) * pk.target.size()));
-    RT_TRY(upload(ctx, m->morph_dpos, pk.dpos.data(), sizeof(float) * pk.dpos.size()));
-    RT_TRY(upload(ctx, m->morph_dnrm, pk.dnrm.data(), sizeof(float) * pk.dnrm.size()));
-    const size_t bytes = sizeof(rt_vertex) * (size_t)m->n_verts;
-    RT_TRY(m->morph_base.reserve(bytes));
-    const void *from = m->skin_k ? m->skin_rest.p : m->d_verts.p;            // the base: the skin's rest pose, or the vertices as they are
-    HIP_TRY(hipMemcpyAsync(m->morph_base.p, from, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope)
-    m->morph_targets = n_targets;
-    m->morph_entries = target_offsets[n_targets];
-    m->morph_normals = normal_deltas != nullptr;
-    return RT_OK;             // the vertices are what they were: nothing changed, built scenes stay built
-}
-
-int rt_model_get_morph_targets(const rt_model *m, uint32_t *n_targets, uint32_t *n_entries, uint32_t *has_normals)
-{
-    RT_REQUIRE(m, "null model");
-    if (n_targets) *n_targets = m->morph_targets;
-    if (n_entries) *n_entries = m->morph_entries;
-    if (has_normals) *has_normals = m->morph_normals ? 1u : 0u;
-    return RT_OK;
-}
-
-int rt_model_set_morph_weights(rt_model *m, const float *weights, uint32_t mem)
-{
-    RT_REQUIRE(m && weights, "null argument");
-    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
-    if (m->morph_targets == 0) {
-        rt_set_error("rt_model_set_morph_weights: the model has no morph targets (rt_model_set_morph_targets gives it some)");
-        return RT_ERR_STATE;
-    }
-    rt_context *ctx = m->ctx;
-    const bool skinned = m->skin_k != 0;                // the result is the skin's rest pose: no vertex changes before the next rt_model_set_bones
-    if (skinned) RT_TRY(use_device(ctx));
-    else RT_TRY(model_before_set(m));
-    const float *w = weights;
-    if (mem == RT_MEM_HOST) {
-        RT_TRY(upload(ctx, ctx->scratch[0], weights, sizeof(float) * (size_t)m->morph_targets));
-        w = ctx->scratch[0].as<float>();
-    }
-    rt_vertex *dst = skinned ? m->skin_rest.as<rt_vertex>() : m->d_verts.as<rt_vertex>();
-    const rt_vertex *base = m->morph_base.as<rt_vertex>();
-    const uint32_t blocks = (m->n_verts + 255u) / 256u;
-    if (m->morph_normals)     // (every result from the base, the whole mesh)
-        k_morph_vertices<true><<<blocks, 256, 0, ctx->stream>>>(dst, base, m->n_verts, m->morph_count.as<uint32_t>(), m->morph_slice.as<uint32_t>(),
-                                                                m->morph_target.as<uint16_t>(), m->morph_dpos.as<float>(), m->morph_dnrm.as<float>(), w);
-    else
-        k_morph_vertices<false><<<blocks, 256, 0, ctx->stream>>>(dst, base, m->n_verts, m->morph_count.as<uint32_t>(), m->morph_slice.as<uint32_t>(),
-                                                                 m->morph_target.as<uint16_t>(), m->morph_dpos.as<float>(), nullptr, w);
-    HIP_TRY(hipGetLastError());
-    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again, and the scratch buffer anybody's)
-    if (skinned) return RT_OK;
-    m->h_verts_stale = true;
-    model_changed(m);
-    return RT_OK;
-}
-
-int rt_model_read_geometry(const rt_model *m, rt_vertex *verts, uint32_t *indices)
-{
-    RT_REQUIRE(m, "null model");
-    if (verts && m->h_verts_stale) {                   // vertices set from device memory: the host mirror follows on demand
-        rt_model *w = const_cast<rt_model *>(m);
-        RT_TRY(use_device(m->ctx));
-        HIP_TRY(hipMemcpyAsync(w->h_verts.data(), m->d_verts.p, sizeof(rt_vertex) * m->h_verts.size(), hipMemcpyDeviceToHost, m->ctx->stream));
-        HIP_TRY(hipStreamSynchronize(m->ctx->stream));
-        w->h_verts_stale = false;
-    }
-    if (verts) memcpy(verts, m->h_verts.data(), sizeof(rt_vertex) * m->h_verts.size());
-    if (indices) memcpy(indices, m->h_idx.data(), sizeof(uint32_t) * m->h_idx.size());
-    return RT_OK;
-}
-
-int rt_model_retain(rt_model *m)
-{
-    RT_REQUIRE(m, "null model");
-    m->refs++;
-    return RT_OK;
-}
-
-int rt_model_destroy(rt_model *m)
-{
-    if (!m) return RT_OK;
-    if (--m->refs > 0) return RT_OK;
-    rt_context *ctx = m->ctx;
-    delete m;
-    rt_context_release(ctx);
     return RT_OK;
 }
 
@@ -1003,7 +476,7 @@ int rt_scene_update(rt_scene *s)
     rt_scene_changed_instances(s, &changed);
     if (s->pending.empty() && changed.empty() && !s->masks_dirty) return RT_OK;      // nothing to apply: nothing launched, the generation stays
     rt_context *ctx = s->ctx;
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
     // pending masks: the visible sub-list goes up if it differs from the one the TLAS stands for (no visible instance: refused here, with every
     // pending thing kept -- showing one and updating again succeeds)
@@ -1047,7 +520,7 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     RT_REQUIRE(s, "null scene");
     RT_REQUIRE(!s->inst.empty(), "scene has no instances");
     rt_context *ctx = s->ctx;
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
     RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_build", true));     // (no visible instance: refused as a scene without instances is)
     ScopedEvent e0, e1;
@@ -1098,7 +571,7 @@ int rt_scene_bvh_read(const rt_scene *s, int which, rt_bvh_node *nodes, uint64_t
 {
     const BvhDev *b = pick_bvh(s, which);
     if (!b) { if (!rt_scene_stale_error(s, "rt_scene_bvh_read")) rt_set_error("rt_scene_bvh_read: scene not built or index out of range"); return RT_ERR_STATE; }
-    RT_TRY(use_device(s->ctx));
+    RT_TRY(rt_use_device(s->ctx));
     const size_t nn = 2 * (size_t)b->n - 1;
     if (nodes) HIP_TRY(hipMemcpy(nodes, b->nodes.p, sizeof(rt_bvh_node) * nn, hipMemcpyDeviceToHost));
     if (sorted_keys) HIP_TRY(hipMemcpy(sorted_keys, b->keys.p, sizeof(uint64_t) * b->n, hipMemcpyDeviceToHost));
@@ -1127,7 +600,7 @@ int rt_scene_wide_read(const rt_scene *s, int which, void *nodes, void *records)
 {
     const BvhDev *b = pick_bvh(s, which);
     if (!b) { if (!rt_scene_stale_error(s, "rt_scene_wide_read")) rt_set_error("rt_scene_wide_read: scene not built or index out of range"); return RT_ERR_STATE; }
-    RT_TRY(use_device(s->ctx));
+    RT_TRY(rt_use_device(s->ctx));
     if (nodes && b->wide_n) HIP_TRY(hipMemcpy(nodes, b->wide.p, sizeof(WNode) * (size_t)b->wide_n, hipMemcpyDeviceToHost));
     if (records && which >= 0) HIP_TRY(hipMemcpy(records, s->inst[which].model->tris.p, sizeof(TriRec) * (size_t)s->inst[which].model->n_recs, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -1150,7 +623,7 @@ int rt_scene_refs_read(const rt_scene *s, int which, uint32_t *ref_off, float *r
     if (!b || which < 0) { if (!rt_scene_stale_error(s, "rt_scene_refs_read")) rt_set_error("rt_scene_refs_read: scene not built or index out of range"); return RT_ERR_STATE; }
     const rt_model *m = s->inst[which].model;
     if (!m->ref_off.p) { rt_set_error("rt_scene_refs_read: no triangle of this model is split"); return RT_ERR_STATE; }
-    RT_TRY(use_device(s->ctx));
+    RT_TRY(rt_use_device(s->ctx));
     uint32_t total = 0;
     HIP_TRY(hipMemcpy(&total, m->ref_off.as<uint32_t>() + m->n_tris, 4, hipMemcpyDeviceToHost));
     if (ref_off) HIP_TRY(hipMemcpy(ref_off, m->ref_off.p, 4 * ((size_t)m->n_tris + 1), hipMemcpyDeviceToHost));
@@ -1164,7 +637,7 @@ int rt_debug_wide_write(rt_scene *s, int which, const void *nodes, uint32_t n_no
 {
     const BvhDev *b = pick_bvh(s, which);
     if (!b || !nodes || n_nodes != b->wide_n) { rt_set_error("rt_debug_wide_write: scene not built, or a different node count"); return RT_ERR_STATE; }
-    RT_TRY(use_device(s->ctx));
+    RT_TRY(rt_use_device(s->ctx));
     HIP_TRY(hipMemcpy(b->wide.p, nodes, sizeof(WNode) * (size_t)n_nodes, hipMemcpyHostToDevice));
     return RT_OK;                                      // (same device pointers, same node count: nothing cached goes stale)
 }
@@ -1200,15 +673,15 @@ int rt_trace_batch(rt_context *ctx, const rt_scene *s, const float *origin_tmin,
     RT_REQUIRE(kernel == RT_TRACE_FAST || kernel == RT_TRACE_CANONICAL, "unknown kernel selector");
     if (n == 0) return RT_OK;
     RT_REQUIRE(origin_tmin && dir_tmax, "null ray arrays");
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     if (mem == RT_MEM_DEVICE) {
         TraceOut out = {t, u, v, prim, inst, cnt_nodes, cnt_tris};
         return rt_launch_trace(ctx, s, (const float4 *)origin_tmin, (const float4 *)dir_tmax, n, ray_flags, kernel, out);
     }
     RT_REQUIRE(mem == RT_MEM_HOST, "unknown memory selector");
     DevBuf *sb = ctx->scratch;
-    RT_TRY(upload(ctx, sb[0], origin_tmin, n * 16));
-    RT_TRY(upload(ctx, sb[1], dir_tmax, n * 16));
+    RT_TRY(rt_upload(ctx, sb[0], origin_tmin, n * 16));
+    RT_TRY(rt_upload(ctx, sb[1], dir_tmax, n * 16));
     void *host_out[7] = {t, u, v, prim, inst, cnt_nodes, cnt_tris};
     RT_TRY(sb[2].reserve(n * 4 * 7));
     char *base = sb[2].as<char>();
@@ -1228,7 +701,7 @@ int rt_trace_batch(rt_context *ctx, const rt_scene *s, const float *origin_tmin,
 int rt_trace_last_ms(rt_context *ctx, float *ms)
 {
     RT_REQUIRE(ctx && ms, "null argument");
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     HIP_TRY(hipEventSynchronize(ctx->ev1));
     HIP_TRY(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
     return RT_OK;
@@ -1240,10 +713,10 @@ int rt_debug_math(rt_context *ctx, int fn, const float *x, const float *y, float
 {
     RT_REQUIRE(ctx && x && out, "null argument");
     if (n == 0) return RT_OK;
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     DevBuf *sb = ctx->scratch;
-    RT_TRY(upload(ctx, sb[0], x, n * 4));
-    RT_TRY(upload(ctx, sb[1], y ? y : x, n * 4));
+    RT_TRY(rt_upload(ctx, sb[0], x, n * 4));
+    RT_TRY(rt_upload(ctx, sb[1], y ? y : x, n * 4));
     RT_TRY(sb[2].reserve(n * 4));
     k_debug_math<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(fn, sb[0].as<float>(), sb[1].as<float>(), sb[2].as<float>(), n);
     HIP_TRY(hipGetLastError());
@@ -1257,10 +730,10 @@ int rt_debug_sample(rt_context *ctx, int kind, const uint32_t *seeds, const floa
 {
     RT_REQUIRE(ctx && seeds && vec3_in && vec3_out, "null argument");
     if (n == 0) return RT_OK;
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     DevBuf *sb = ctx->scratch;
-    RT_TRY(upload(ctx, sb[0], seeds, n * 4));
-    RT_TRY(upload(ctx, sb[1], vec3_in, n * 12));
+    RT_TRY(rt_upload(ctx, sb[0], seeds, n * 4));
+    RT_TRY(rt_upload(ctx, sb[1], vec3_in, n * 12));
     RT_TRY(sb[2].reserve(n * 12));
     RT_TRY(sb[3].reserve(n * 8));
     RT_TRY(sb[4].reserve(n * 4));

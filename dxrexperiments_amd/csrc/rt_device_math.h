@@ -42,6 +42,13 @@ RT_DEV f3 cross(f3 a, f3 b)
 }
 RT_DEV float rsqrt_ieee(float x) { return 1.0f / __builtin_sqrtf(x); }
 RT_DEV f3 normalize(f3 v) { return v * rsqrt_ieee(dot(v, v)); }
+// the normal rule of include/dxr_amd.h (recomputed, skinned and morphed normals): with d = dot(s, s), s * (1 / sqrt(d)) if 0 < d < inf, else (0, 0, 0).
+// (& of two bools, no branch between the tests: one v_cmp_class, the instructions the three kernels had with && beside the math probes -- profiles/r15/model_split.txt)
+RT_DEV f3 unit_or_zero(f3 s)
+{
+    const float d = dot(s, s);
+    return ((d > 0.0f) & (d < __uint_as_float(0x7f800000u))) ? normalize(s) : mk3(0.0f, 0.0f, 0.0f);
+}
 RT_DEV float length(f3 v) { return __builtin_sqrtf(dot(v, v)); }
 RT_DEV float fmin2(float a, float b) { return __builtin_fminf(a, b); }   // v_min_f32: NaN-ignoring
 RT_DEV float fmax2(float a, float b) { return __builtin_fmaxf(a, b); }

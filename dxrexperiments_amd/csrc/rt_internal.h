@@ -286,6 +286,15 @@ struct rt_context {
     ~rt_context();               // (rt_api.hip) selects the device and joins the stream; pinned memory, events, an owned stream; then the buffers
 };
 
+static inline int rt_use_device(const rt_context *ctx) { HIP_TRY(hipSetDevice(ctx->device)); return RT_OK; }
+// `bytes` of a host array into a buffer grown to hold them, queued on the context's stream
+static inline int rt_upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
+{
+    RT_TRY(b.reserve(bytes));
+    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return RT_OK;
+}
+
 struct BvhDev {
     uint32_t n = 0;              // primitives
     uint32_t max_depth = 0;
@@ -298,6 +307,22 @@ struct BvhDev {
     uint32_t wide_n = 0;
     int root_code = -1;
     uint32_t fast_depth = 0;     // stack entries the traversal layout can need
+};
+
+// rt_model_set_skin / rt_model_set_bones: k == 0: no skin.  (An empty one assigned over it frees every buffer: nothing lists them.)
+struct ModelSkin {
+    uint32_t k = 0, bones = 0;   // influences per vertex, bones of a palette
+    DevBuf bone, weight;         // uint16[k][n_verts], float[k][n_verts]: slot major (rt_skin.h)
+    DevBuf rest;                 // rt_vertex[n_verts]: the rest pose, d_verts as they were when the skin was set
+};
+
+// rt_model_set_morph_targets / rt_model_set_morph_weights: targets == 0: no targets
+struct ModelMorph {
+    uint32_t targets = 0, entries = 0;
+    bool normals = false;        // the targets carry normal deltas (dnrm is filled)
+    DevBuf count, slice;         // uint32[n_verts], uint32[ceil(n_verts / 64) + 1]: SELL-64 (rt_morph.h)
+    DevBuf target, dpos, dnrm;   // uint16[cells], float[3 cells], float[3 cells]
+    DevBuf base;                 // rt_vertex[n_verts]: the base, captured when the targets were set
 };
 
 struct rt_model {
@@ -320,17 +345,9 @@ struct rt_model {
     std::vector<struct rt_scene *> scenes;   // the scenes that hold the model in some instance (each once): a set leaves the built ones stale
     DevBuf adj_off, adj_tris;    // vertex -> triangle CSR of the index list (rt_adjacency.h), made by the first rt_model_recompute_normals
     bool adj_ready = false;
-    // rt_model_set_skin / rt_model_set_bones: skin_k == 0: no skin
-    uint32_t skin_k = 0, skin_bones = 0;     // influences per vertex, bones of a palette
-    DevBuf skin_bone, skin_weight;           // uint16[skin_k][n_verts], float[skin_k][n_verts]: slot major (rt_skin.h)
-    DevBuf skin_rest;                        // rt_vertex[n_verts]: the rest pose, d_verts as they were when the skin was set
-    // rt_model_set_morph_targets / rt_model_set_morph_weights: morph_targets == 0: no targets
-    uint32_t morph_targets = 0, morph_entries = 0;
-    bool morph_normals = false;              // the targets carry normal deltas (morph_dnrm is filled)
-    DevBuf morph_count, morph_slice;         // uint32[n_verts], uint32[ceil(n_verts / 64) + 1]: SELL-64 (rt_morph.h)
-    DevBuf morph_target, morph_dpos, morph_dnrm;       // uint16[cells], float[3 cells], float[3 cells]
-    DevBuf morph_base;                       // rt_vertex[n_verts]: the base, captured when the targets were set
-    ~rt_model();                // (rt_api.hip) selects the device before the buffers go
+    ModelSkin skin;
+    ModelMorph morph;
+    ~rt_model();                // (rt_model.hip) selects the device before the buffers go
 };
 
 // rt_skeleton_create (rt_skeleton.hip): a joint hierarchy, its current pose and the palette a skin reads

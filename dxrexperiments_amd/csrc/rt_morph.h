@@ -1,5 +1,5 @@
 // rt_morph.h -- the morph targets of a model (rt_model_set_morph_targets): validation of the caller's sparse lists and their packing into the
-// layout k_morph_vertices reads.  Host code without HIP, as rt_skin.h and rt_adjacency.h are: tests/cpp/morph_sanitized.cpp compiles it alone.
+// layout k_morph_vertices (rt_model.hip) reads.  Host code without HIP, as rt_skin.h and rt_adjacency.h are: tests/cpp/morph_sanitized.cpp compiles it alone.
 #pragma once
 
 #include <stddef.h>

@@ -1,6 +1,6 @@
 // rt_skeleton.hip -- posed skeletons (include/dxr_amd.h "Posed skeletons"): a joint hierarchy whose local pose -- set by the caller or sampled
 // from a baked clip -- becomes world matrices and a skinning palette on the device.  The palette is what rt_model_set_bones(RT_MEM_DEVICE)
-// takes: rt_model_set_bones_from_skeleton hands it over and k_skin_vertices (rt_api.hip) runs unchanged.  No reference counterpart: the
+// takes: rt_model_set_bones_from_skeleton hands it over and k_skin_vertices (rt_model.hip) runs unchanged.  No reference counterpart: the
 // reference imports with aiProcess_PreTransformVertices (libs/DXRFramework/RtModel.cpp:26), which drops bones and node animation.
 #include <cmath>
 #include <new>
@@ -133,19 +133,6 @@ __global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict
     for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = o[c];
 }
 
-int use_device(const rt_context *ctx)
-{
-    HIP_TRY(hipSetDevice(ctx->device));
-    return RT_OK;
-}
-
-int upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
-{
-    RT_TRY(b.reserve(bytes));
-    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return RT_OK;
-}
-
 // sk->pose holds a local pose: W and the palette from it, queued on the context's stream
 int pose_skeleton(rt_skeleton *sk)
 {
@@ -171,7 +158,7 @@ int require_pose(const rt_skeleton *sk, const char *who)
 int read_back(rt_skeleton *sk, const char *who, const DevBuf &from, float *to, size_t floats_per_joint)
 {
     RT_TRY(require_pose(sk, who));
-    RT_TRY(use_device(sk->ctx));
+    RT_TRY(rt_use_device(sk->ctx));
     HIP_TRY(hipMemcpyAsync(to, from.p, sizeof(float) * floats_per_joint * sk->n_joints, hipMemcpyDeviceToHost, sk->ctx->stream));
     HIP_TRY(hipStreamSynchronize(sk->ctx->stream));
     return RT_OK;
@@ -209,10 +196,10 @@ int rt_skeleton_create(rt_context *ctx, uint32_t n_joints, const int32_t *parent
     sk->n_levels = rt_skeleton_levels(n_joints, parents, order, sk->level_offsets);
     rt_skeleton_pack_table(parents, order, table);
     auto fill = [&]() -> int {
-        RT_TRY(use_device(ctx));
-        RT_TRY(upload(ctx, sk->table, table.data(), sizeof(uint32_t) * table.size()));
-        RT_TRY(upload(ctx, sk->d_level_offsets, sk->level_offsets.data(), sizeof(uint32_t) * sk->level_offsets.size()));
-        RT_TRY(upload(ctx, sk->inverse_bind, inverse_bind, 48 * (size_t)n_joints));
+        RT_TRY(rt_use_device(ctx));
+        RT_TRY(rt_upload(ctx, sk->table, table.data(), sizeof(uint32_t) * table.size()));
+        RT_TRY(rt_upload(ctx, sk->d_level_offsets, sk->level_offsets.data(), sizeof(uint32_t) * sk->level_offsets.size()));
+        RT_TRY(rt_upload(ctx, sk->inverse_bind, inverse_bind, 48 * (size_t)n_joints));
         RT_TRY(sk->pose.reserve(sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)n_joints));
         RT_TRY(sk->joints.reserve(48 * (size_t)n_joints));
         RT_TRY(sk->palette.reserve(48 * (size_t)n_joints));
@@ -252,7 +239,7 @@ int rt_skeleton_set_pose(rt_skeleton *sk, const float *trs, uint32_t mem)
     RT_REQUIRE(sk && trs, "null argument");
     RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
     rt_context *ctx = sk->ctx;
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     const size_t bytes = sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)sk->n_joints;
     // (the skeleton keeps the pose: rt_skeleton_read_pose answers from it, and a device source is the caller's again once the stream has passed the copy)
     HIP_TRY(hipMemcpyAsync(sk->pose.p, trs, bytes, mem == RT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
@@ -288,8 +275,8 @@ int rt_skeleton_add_clip(rt_skeleton *sk, uint32_t n_keys, const float *times, c
             for (size_t c = 0; c < RT_SKELETON_POSE_FLOATS; c++) keys[k * per_key + c * nj + j] = trs[k * per_key + j * RT_SKELETON_POSE_FLOATS + c];
     SkeletonClip clip;
     clip.times.assign(times, times + n_keys);
-    RT_TRY(use_device(ctx));
-    RT_TRY(upload(ctx, clip.keys, keys.data(), sizeof(float) * keys.size()));
+    RT_TRY(rt_use_device(ctx));
+    RT_TRY(rt_upload(ctx, clip.keys, keys.data(), sizeof(float) * keys.size()));
     HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vector goes out of scope)
     sk->clips.push_back(std::move(clip));               // (earlier clips keep their ids and their buffers)
     if (clip_out) *clip_out = (uint32_t)sk->clips.size() - 1u;
@@ -300,7 +287,7 @@ int rt_skeleton_clear_clips(rt_skeleton *sk)
 {
     RT_REQUIRE(sk, "null skeleton");
     if (sk->clips.empty()) return RT_OK;
-    RT_TRY(use_device(sk->ctx));
+    RT_TRY(rt_use_device(sk->ctx));
     HIP_TRY(hipStreamSynchronize(sk->ctx->stream));     // (a sampling kernel that reads a clip may still be queued)
     sk->clips.clear();
     return RT_OK;
@@ -323,7 +310,7 @@ int rt_skeleton_set_time(rt_skeleton *sk, uint32_t clip, float t)
     const size_t per_key = RT_SKELETON_POSE_FLOATS * (size_t)sk->n_joints;
     const float *key_a = c.keys.as<float>() + per_key * i;
     const float *key_b = n_keys == 1u ? key_a : key_a + per_key;
-    RT_TRY(use_device(ctx));
+    RT_TRY(rt_use_device(ctx));
     k_skeleton_sample<<<(sk->n_joints + 255u) / 256u, 256, 0, ctx->stream>>>(key_a, key_b, sk->n_joints, a, sk->pose.as<float>());
     HIP_TRY(hipGetLastError());
     return pose_skeleton(sk);
@@ -359,12 +346,12 @@ int rt_model_set_bones_from_skeleton(rt_model *m, rt_skeleton *sk)
 {
     RT_REQUIRE(m && sk, "null argument");
     RT_TRY(require_pose(sk, "rt_model_set_bones_from_skeleton"));
-    if (m->skin_k == 0) {
+    if (m->skin.k == 0) {
         rt_set_error("rt_model_set_bones_from_skeleton: the model has no skin (rt_model_set_skin gives it one)");
         return RT_ERR_STATE;
     }
-    if (m->skin_bones != sk->n_joints) {
-        rt_set_error("rt_model_set_bones_from_skeleton: a skin of %u bones and a skeleton of %u joints", m->skin_bones, sk->n_joints);
+    if (m->skin.bones != sk->n_joints) {
+        rt_set_error("rt_model_set_bones_from_skeleton: a skin of %u bones and a skeleton of %u joints", m->skin.bones, sk->n_joints);
         return RT_ERR_STATE;
     }
     if (m->ctx != sk->ctx) {

@@ -1,5 +1,5 @@
 // rt_skin.h -- the skin of a model (rt_model_set_skin): validation of the caller's arrays and their packing into the layout k_skin_vertices
-// reads.  Host code without HIP, as rt_adjacency.h is: tests/cpp/skin_sanitized.cpp compiles it alone.
+// (rt_model.hip) reads.  Host code without HIP, as rt_adjacency.h is: tests/cpp/skin_sanitized.cpp compiles it alone.
 #pragma once
 
 #include <stddef.h>

@@ -285,6 +285,69 @@ def test_a_frame_through_a_pipeline_that_had_cached_the_old_shape(gpu, capi, ora
     close_all(sc, gm)
 
 
+def test_deferred_frames_see_the_mesh_they_were_accepted_with(gpu, capi, oracle):
+    """set_deferred(4), two frames recorded.  (a) no skin: set_morph_targets changes no vertex and renders nothing; set_morph_weights renders
+    the two frames before the first byte changes (they see the base); update, two more, read: the image == the oracle's frames 1 - 2 on the
+    base accumulated with 3 - 4 on the morphed blob.  (b) a skin and targets: set_morph_weights writes the rest pose only -- the recorded
+    frames stay recorded, the vertices stay byte for byte -- and the next set_bones renders them and gives skinned(morphed(base))"""
+    models, inst, mats, cam = light_scene()
+    env = scenes.sky_cubemap(8)
+    pfcs = frames_of(capi, cam, 4, W, H)
+    nv = len(models[0][0])
+    off, idx, dp, dn = soup_targets(nv, seed=50, scale=0.6)
+    w = M.weights(3, "convex", 55)
+    morphed = M.morphed(models[0][0], off, idx, dp, dn, w)
+    assert morphed.tobytes() != np.ascontiguousarray(models[0][0], T.VERTEX).tobytes()
+
+    def recording():
+        sc, gm = own_scene(capi, gpu, models, inst)
+        p = pipeline_over(capi, gpu, sc, mats, env)
+        p.set_depth_limits(3, 3)
+        p.set_deferred(4)
+        return sc, gm, p
+
+    def record(p, some):
+        for pfc in some:
+            p.update(pfc); p.render()
+        assert p.deferred() == (4, 2)
+
+    # (a)
+    sc, gm, p = recording()
+    record(p, pfcs[:2])
+    gm[0].set_morph_targets(off, idx, dp, dn)
+    assert p.deferred() == (4, 2), "set_morph_targets changes no vertex: nothing to render first"
+    blend(gpu, gm[0], w)
+    assert p.deferred() == (4, 0), "set_morph_weights did not render the recorded frames first"
+    sc.update()
+    record(p, pfcs[2:])
+    acc = np.zeros((H, W, 4), np.float32)
+    for osc, some in ((make_oracle_scene(oracle, models, inst), pfcs[:2]), (make_oracle_scene(oracle, [(morphed, models[0][1]), models[1]], inst), pfcs[2:])):
+        for pfc in some:
+            acc, _ = osc.render(np.stack(mats), pfc, W, H, accum=acc, env_faces=env, max_radiance_depth=3, max_shadow_depth=3, nthreads=8)
+    got = p.read_output()
+    assert np.array_equal(got, acc), "%d pixels differ" % int((got != acc).any(axis=2).sum())
+    p.close()
+    close_all(sc, gm)
+
+    # (b)
+    sc, gm, p = recording()
+    bones, sw, nb = K.random_bones(nv, 2, 5, 50), K.random_weights(nv, 2, 51), 5
+    gm[0].set_skin(bones, sw, nb)
+    gm[0].set_morph_targets(off, idx, dp, dn)
+    before = gm[0].geometry()[0].tobytes()
+    record(p, pfcs[:2])
+    blend(gpu, gm[0], w)
+    assert p.deferred() == (4, 2), "set_morph_weights on a skinned model changes no vertex: nothing to render first"
+    assert gm[0].geometry()[0].tobytes() == before, "set_morph_weights on a skinned model changed its vertices"
+    identity = K.identity_palette(nb)
+    pose(gpu, gm[0], identity)
+    assert p.deferred() == (4, 0), "set_bones did not render the recorded frames first"
+    sc.update()
+    assert gm[0].geometry()[0].tobytes() == K.skinned(morphed, bones, sw, identity).tobytes()
+    p.close()
+    close_all(sc, gm)
+
+
 # ---- a sequence of edits -------------------------------------------------------------------------------------------------------------------
 def test_a_sequence_of_edits_equals_the_build_of_its_final_state(gpu, capi, oracle):
     """a morphed, skinned model 0 in five instances of two models: weights A + bones P, update; a transform and a hidden instance, update;
