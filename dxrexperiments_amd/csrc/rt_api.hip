@@ -1,5 +1,5 @@
-// rt_api.hip -- C-ABI entry points for error state, debug options, context, device memory, scene and batch TraceRay, and the device
-// math probes (include/dxr_amd.h).  Stand-ins for libs/DXRFramework/Rt{Context,Scene}; the model is rt_model.hip.
+// rt_api.hip -- C-ABI entry points for error state, debug options, context, device memory and batch TraceRay, and the device
+// math probes (include/dxr_amd.h).  Stand-in for libs/DXRFramework/RtContext; the model is rt_model.hip, the scene rt_scene.hip.
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -232,8 +232,6 @@ int rt_context_destroy(rt_context *ctx)
 
 void rt_context_retain(rt_context *ctx) { if (ctx) ctx->refs++; }
 
-void rt_scene_retain(rt_scene *s) { if (s) s->refs++; }
-
 // The context lives until its handle AND every object created on it are gone.
 void rt_context_release(rt_context *ctx)
 {
@@ -249,17 +247,6 @@ rt_context::~rt_context()
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
-}
-
-rt_scene::~rt_scene()
-{
-    (void)hipSetDevice(ctx->device);
-    for (SceneInstance &in : inst) {
-        std::vector<rt_scene *> &held = in.model->scenes;      // (the model outlives this: the scene retains it)
-        for (size_t k = 0; k < held.size(); k++)
-            if (held[k] == this) { held.erase(held.begin() + k); break; }
-        rt_model_destroy(in.model);
-    }
 }
 
 extern "C" {
@@ -337,331 +324,6 @@ int rt_device_download(rt_context *ctx, void *host_dst, const void *device_src, 
     return RT_OK;
 }
 
-// ---- scene -----------------------------------------------------------------------
-
-int rt_scene_create(rt_context *ctx, rt_scene **out)
-{
-    RT_REQUIRE(ctx && out, "null argument");
-    rt_scene *s = new (std::nothrow) rt_scene();
-    if (!s) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    s->ctx = ctx;
-    rt_context_retain(ctx);
-    *out = s;
-    return RT_OK;
-}
-
-int rt_scene_add_model(rt_scene *s, rt_model *m, const float transform3x4[12])
-{
-    RT_REQUIRE(s && m && transform3x4, "null argument");
-    RT_REQUIRE(m->ctx == s->ctx, "model and scene belong to different contexts");
-    RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
-    SceneInstance in;
-    in.model = m;
-    memcpy(in.xform, transform3x4, sizeof in.xform);
-    m->refs++;
-    s->inst.push_back(in);
-    s->masks.push_back(0xFF);  // InstanceMask of the reference's descriptors (TopLevelASGenerator.cpp:361)
-    bool held = false;
-    for (rt_scene *o : m->scenes) held = held || o == s;
-    if (!held) m->scenes.push_back(s);
-    s->built = false;
-    s->updatable = false;     // the TLAS no longer stands for this instance list: only rt_scene_build brings the scene back
-    s->generation++;
-    return RT_OK;
-}
-
-static int scene_range_check(const rt_scene *s, const char *who, uint32_t first, uint32_t count)
-{
-    const size_t n = s->inst.size();
-    if (first > n || count > n - first) {
-        rt_set_error("%s: instances %u .. %llu out of range: the scene has %zu", who, first, (unsigned long long)first + count, n);
-        return RT_ERR_STATE;
-    }
-    return RT_OK;
-}
-
-// instance i joins the list the next update rewrites (once)
-static void scene_mark_pending(rt_scene *s, uint32_t i)
-{
-    s->is_pending.resize(s->inst.size(), 0);
-    if (!s->is_pending[i]) { s->is_pending[i] = 1; s->pending.push_back(i); }
-}
-
-// A build or an update has succeeded: every stored transform and mask has been read, and the vertices of the models of `changed` (an
-// update: exactly the instances whose generation differed; nullptr, a build: of every instance).  Nothing is pending, the scene is fresh.
-static void scene_applied(rt_scene *s, const std::vector<uint32_t> *changed)
-{
-    const size_t n = s->inst.size();
-    if (changed) {
-        for (uint32_t i : s->pending) s->is_pending[i] = 0;
-        for (uint32_t i : *changed) s->seen_geom[i] = s->inst[i].model->geom_gen;
-    } else {
-        s->is_pending.assign(n, 0);
-        s->seen_geom.resize(n);
-        for (size_t i = 0; i < n; i++) s->seen_geom[i] = s->inst[i].model->geom_gen;
-    }
-    s->pending.clear();
-    s->masks_dirty = false;
-    s->built = true;
-}
-
-int rt_scene_set_instance_transforms(rt_scene *s, uint32_t first, uint32_t count, const float *transforms3x4)
-{
-    RT_REQUIRE(s && (transforms3x4 || count == 0), "null argument");
-    RT_TRY(scene_range_check(s, "rt_scene_set_instance_transforms", first, count));
-    if (count == 0) return RT_OK;
-    RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
-    for (uint32_t k = 0; k < count; k++) memcpy(s->inst[first + k].xform, transforms3x4 + 12 * (size_t)k, sizeof s->inst[0].xform);
-    if (!s->updatable) return RT_OK;                  // never built (or instances added since): the next build reads the stored transforms
-    for (uint32_t i = first; i < first + count; i++) scene_mark_pending(s, i);
-    s->built = false;         // stale until rt_scene_update or rt_scene_build: nothing traces a half-applied state
-    return RT_OK;
-}
-
-int rt_scene_set_instance_transform(rt_scene *s, uint32_t instance, const float transform3x4[12])
-{
-    RT_REQUIRE(s && transform3x4, "null argument");
-    if (instance >= s->inst.size()) {
-        rt_set_error("rt_scene_set_instance_transform: instance %u out of range: the scene has %zu", instance, s->inst.size());
-        return RT_ERR_STATE;
-    }
-    return rt_scene_set_instance_transforms(s, instance, 1, transform3x4);
-}
-
-// EXTENSION: the InstanceMask member of the instance descriptors (TopLevelASGenerator.cpp:344-362), which the reference fills with 0xFF, under the
-// inclusion mask 0xFF of its every TraceRay (ProgressiveRaytracing.hlsl:34,53, RaytracingCommon.hlsli:94, RealtimeRaytracing.hlsl:42,61)
-int rt_scene_set_instance_masks(rt_scene *s, uint32_t first, uint32_t count, const uint8_t *masks)
-{
-    RT_REQUIRE(s && (masks || count == 0), "null argument");
-    RT_TRY(scene_range_check(s, "rt_scene_set_instance_masks", first, count));
-    if (count == 0) return RT_OK;
-    RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
-    bool visibility = false;
-    for (uint32_t k = 0; k < count; k++) {
-        visibility = visibility || ((s->masks[first + k] != 0) != (masks[k] != 0));
-        s->masks[first + k] = masks[k];
-    }
-    if (!s->updatable || !visibility) return RT_OK;   // not built: the next build reads the stored masks; the same visibility: only the bytes change
-    s->masks_dirty = true;
-    s->built = false;         // stale until rt_scene_update or rt_scene_build, as with a pending transform
-    return RT_OK;
-}
-
-int rt_scene_set_instance_mask(rt_scene *s, uint32_t instance, uint8_t mask)
-{
-    RT_REQUIRE(s, "null scene");
-    if (instance >= s->inst.size()) {
-        rt_set_error("rt_scene_set_instance_mask: instance %u out of range: the scene has %zu", instance, s->inst.size());
-        return RT_ERR_STATE;
-    }
-    return rt_scene_set_instance_masks(s, instance, 1, &mask);
-}
-
-int rt_scene_get_instance_masks(const rt_scene *s, uint32_t first, uint32_t count, uint8_t *masks)
-{
-    RT_REQUIRE(s && (masks || count == 0), "null argument");
-    RT_TRY(scene_range_check(s, "rt_scene_get_instance_masks", first, count));
-    if (count) memcpy(masks, s->masks.data() + first, count);
-    return RT_OK;
-}
-
-int rt_scene_update(rt_scene *s)
-{
-    RT_REQUIRE(s, "null scene");
-    if (!s->updatable) {
-        rt_set_error("rt_scene_update: the scene has not been built since its last rt_scene_add_model (an update builds no BLAS: rt_scene_build)");
-        return RT_ERR_STATE;
-    }
-    std::vector<uint32_t> changed;                    // instances whose model's vertices were set since their records were written
-    rt_scene_changed_instances(s, &changed);
-    if (s->pending.empty() && changed.empty() && !s->masks_dirty) return RT_OK;      // nothing to apply: nothing launched, the generation stays
-    rt_context *ctx = s->ctx;
-    RT_TRY(rt_use_device(ctx));
-    RT_TRY(rt_context_flush_deferred(ctx));
-    // pending masks: the visible sub-list goes up if it differs from the one the TLAS stands for (no visible instance: refused here, with every
-    // pending thing kept -- showing one and updating again succeeds)
-    if (s->masks_dirty) RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_update", false));
-    s->generation++;          // pipelines drop what they cached from the old geometry: shadow-cache occluders, per-pixel entries, the free sphere, the primary-mode samples
-    ScopedEvent e0, e1;
-    HIP_TRY(hipEventCreate(&e0.e));
-    HIP_TRY(hipEventCreate(&e1.e));
-    HIP_TRY(hipEventRecord(e0.e, ctx->stream));
-    if (!changed.empty()) {
-        // a changed model whose BLAS is older than its vertices: rebuilt by the build's own steps into the model's own buffers (one that
-        // another scene's update or build has rebuilt already is built: rt_build_blas returns at once)
-        for (uint32_t i : changed) RT_TRY(rt_build_blas(ctx, s->inst[i].model));
-        RT_TRY(rt_update_model_records(ctx, s, changed));
-        for (uint32_t i : changed) scene_mark_pending(s, i);      // ... and take their world boxes over the new vertices, with the transforms they have
-    }
-    // (a failure leaves the scene stale, the transforms and the models pending); e1: behind the wide collapse, in front of the read-back
-    RT_TRY(rt_update_tlas(ctx, s, s->pending, "rt_scene_update", e1.e));
-    HIP_TRY(hipEventElapsedTime(&s->update_ms, e0.e, e1.e));
-    scene_applied(s, &changed);
-    return RT_OK;
-}
-
-int rt_scene_update_ms(const rt_scene *s, float *ms)
-{
-    RT_REQUIRE(s && ms, "null argument");
-    *ms = s->update_ms;
-    return RT_OK;
-}
-
-int rt_scene_get_num_instances(const rt_scene *s, uint32_t *n)
-{
-    RT_REQUIRE(s && n, "null argument");
-    *n = (uint32_t)s->inst.size();
-    return RT_OK;
-}
-
-int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
-{
-    (void)hit_group_count;   // hit-group stride of the reference's shader table; material = f(instance) here
-    RT_REQUIRE(s, "null scene");
-    RT_REQUIRE(!s->inst.empty(), "scene has no instances");
-    rt_context *ctx = s->ctx;
-    RT_TRY(rt_use_device(ctx));
-    RT_TRY(rt_context_flush_deferred(ctx));
-    RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_build", true));     // (no visible instance: refused as a scene without instances is)
-    ScopedEvent e0, e1;
-    HIP_TRY(hipEventCreate(&e0.e));
-    HIP_TRY(hipEventCreate(&e1.e));
-    HIP_TRY(hipEventRecord(e0.e, ctx->stream));
-    s->generation++;          // device arrays are about to be reallocated: pipelines drop what they cached
-    for (SceneInstance &in : s->inst) RT_TRY(rt_build_blas(ctx, in.model));
-    s->updatable = false;
-    RT_TRY(rt_build_tlas(ctx, s));
-    HIP_TRY(hipEventRecord(e1.e, ctx->stream));
-    HIP_TRY(hipEventSynchronize(e1.e));
-    HIP_TRY(hipEventElapsedTime(&s->build_ms, e0.e, e1.e));
-    s->updatable = true;
-    scene_applied(s, nullptr);
-    return RT_OK;
-}
-
-int rt_scene_destroy(rt_scene *s)
-{
-    if (!s) return RT_OK;
-    if (--s->refs > 0) return RT_OK;
-    rt_context *ctx = s->ctx;
-    delete s;
-    rt_context_release(ctx);
-    return RT_OK;
-}
-
-static const BvhDev *pick_bvh(const rt_scene *s, int which)
-{
-    if (!s || !s->built) return nullptr;
-    if (which < 0) return &s->tlas;
-    if ((size_t)which >= s->inst.size()) return nullptr;
-    return &s->inst[which].model->blas;
-}
-
-int rt_scene_bvh_info(const rt_scene *s, int which, uint32_t *n_prims, uint32_t *n_nodes, uint32_t *max_depth)
-{
-    const BvhDev *b = pick_bvh(s, which);
-    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_bvh_info")) rt_set_error("rt_scene_bvh_info: scene not built or index out of range"); return RT_ERR_STATE; }
-    if (n_prims) *n_prims = b->n;
-    if (n_nodes) *n_nodes = 2 * b->n - 1;
-    if (max_depth) *max_depth = b->max_depth;
-    return RT_OK;
-}
-
-int rt_scene_bvh_read(const rt_scene *s, int which, rt_bvh_node *nodes, uint64_t *sorted_keys, uint32_t *parents)
-{
-    const BvhDev *b = pick_bvh(s, which);
-    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_bvh_read")) rt_set_error("rt_scene_bvh_read: scene not built or index out of range"); return RT_ERR_STATE; }
-    RT_TRY(rt_use_device(s->ctx));
-    const size_t nn = 2 * (size_t)b->n - 1;
-    if (nodes) HIP_TRY(hipMemcpy(nodes, b->nodes.p, sizeof(rt_bvh_node) * nn, hipMemcpyDeviceToHost));
-    if (sorted_keys) HIP_TRY(hipMemcpy(sorted_keys, b->keys.p, sizeof(uint64_t) * b->n, hipMemcpyDeviceToHost));
-    if (parents) HIP_TRY(hipMemcpy(parents, b->parents.p, sizeof(uint32_t) * nn, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_scene_wide_info(const rt_scene *s, int which, uint32_t *n_nodes, int32_t *root_code, uint32_t *n_records)
-{
-    const BvhDev *b = pick_bvh(s, which);
-    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_wide_info")) rt_set_error("rt_scene_wide_info: scene not built or index out of range"); return RT_ERR_STATE; }
-    if (n_nodes) *n_nodes = b->wide_n;
-    if (root_code) *root_code = b->root_code;
-    if (n_records) *n_records = which < 0 ? 0u : s->inst[which].model->n_recs;
-    return RT_OK;
-}
-
-int rt_wide_layout_info(uint32_t *width, uint32_t *node_bytes)
-{
-    if (width) *width = RT_WIDE;
-    if (node_bytes) *node_bytes = (uint32_t)sizeof(WNode);
-    return RT_OK;
-}
-
-int rt_scene_wide_read(const rt_scene *s, int which, void *nodes, void *records)
-{
-    const BvhDev *b = pick_bvh(s, which);
-    if (!b) { if (!rt_scene_stale_error(s, "rt_scene_wide_read")) rt_set_error("rt_scene_wide_read: scene not built or index out of range"); return RT_ERR_STATE; }
-    RT_TRY(rt_use_device(s->ctx));
-    if (nodes && b->wide_n) HIP_TRY(hipMemcpy(nodes, b->wide.p, sizeof(WNode) * (size_t)b->wide_n, hipMemcpyDeviceToHost));
-    if (records && which >= 0) HIP_TRY(hipMemcpy(records, s->inst[which].model->tris.p, sizeof(TriRec) * (size_t)s->inst[which].model->n_recs, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-/* the validation boxes of an instance's model (rt_refs.h): *n_refs = 0 when none of its triangles is split */
-int rt_scene_refs_info(const rt_scene *s, int which, uint32_t *n_tris, uint32_t *n_refs)
-{
-    const BvhDev *b = pick_bvh(s, which);
-    if (!b || which < 0) { if (!rt_scene_stale_error(s, "rt_scene_refs_info")) rt_set_error("rt_scene_refs_info: scene not built or index out of range"); return RT_ERR_STATE; }
-    const rt_model *m = s->inst[which].model;
-    if (n_tris) *n_tris = m->n_tris;
-    if (n_refs) *n_refs = m->ref_off.p ? (uint32_t)(m->ref_boxes.bytes / 24) : 0u;
-    return RT_OK;
-}
-
-int rt_scene_refs_read(const rt_scene *s, int which, uint32_t *ref_off, float *ref_boxes, float *record_boxes)
-{
-    const BvhDev *b = pick_bvh(s, which);
-    if (!b || which < 0) { if (!rt_scene_stale_error(s, "rt_scene_refs_read")) rt_set_error("rt_scene_refs_read: scene not built or index out of range"); return RT_ERR_STATE; }
-    const rt_model *m = s->inst[which].model;
-    if (!m->ref_off.p) { rt_set_error("rt_scene_refs_read: no triangle of this model is split"); return RT_ERR_STATE; }
-    RT_TRY(rt_use_device(s->ctx));
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpy(&total, m->ref_off.as<uint32_t>() + m->n_tris, 4, hipMemcpyDeviceToHost));
-    if (ref_off) HIP_TRY(hipMemcpy(ref_off, m->ref_off.p, 4 * ((size_t)m->n_tris + 1), hipMemcpyDeviceToHost));
-    if (ref_boxes) HIP_TRY(hipMemcpy(ref_boxes, m->ref_boxes.p, 24 * (size_t)total, hipMemcpyDeviceToHost));
-    if (record_boxes && m->rec_boxes.p) HIP_TRY(hipMemcpy(record_boxes, m->rec_boxes.p, 24 * (size_t)m->n_recs, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-/* layout experiments (tools/layout_estimate.py): replaces the node array by a renumbering of itself */
-int rt_debug_wide_write(rt_scene *s, int which, const void *nodes, uint32_t n_nodes)
-{
-    const BvhDev *b = pick_bvh(s, which);
-    if (!b || !nodes || n_nodes != b->wide_n) { rt_set_error("rt_debug_wide_write: scene not built, or a different node count"); return RT_ERR_STATE; }
-    RT_TRY(rt_use_device(s->ctx));
-    HIP_TRY(hipMemcpy(b->wide.p, nodes, sizeof(WNode) * (size_t)n_nodes, hipMemcpyHostToDevice));
-    return RT_OK;                                      // (same device pointers, same node count: nothing cached goes stale)
-}
-
-int rt_scene_instance_info(const rt_scene *s, uint32_t instance, float world_box[6], float world_to_object[12])
-{
-    RT_REQUIRE(s, "null scene");
-    if (!s->built || instance >= s->h_inst.size()) {
-        if (!rt_scene_stale_error(s, "rt_scene_instance_info")) rt_set_error("scene not built or instance out of range");
-        return RT_ERR_STATE;
-    }
-    const InstanceRec &r = s->h_inst[instance];
-    if (world_box) for (int c = 0; c < 3; c++) { world_box[c] = r.wlo[c]; world_box[3 + c] = r.whi[c]; }
-    if (world_to_object) memcpy(world_to_object, r.inv, sizeof r.inv);
-    return RT_OK;
-}
-
-int rt_scene_build_ms(const rt_scene *s, float *ms)
-{
-    RT_REQUIRE(s && ms, "null argument");
-    *ms = s->build_ms;
-    return RT_OK;
-}
-
 // ---- batch TraceRay ---------------------------------------------------------------
 
 int rt_trace_batch(rt_context *ctx, const rt_scene *s, const float *origin_tmin, const float *dir_tmax, size_t n,
@@ -669,7 +331,7 @@ int rt_trace_batch(rt_context *ctx, const rt_scene *s, const float *origin_tmin,
                    uint32_t *inst, uint32_t *cnt_nodes, uint32_t *cnt_tris)
 {
     RT_REQUIRE(ctx && s, "null argument");
-    if (!s->built) { if (!rt_scene_stale_error(s, "rt_trace_batch")) rt_set_error("rt_trace_batch: scene not built"); return RT_ERR_STATE; }
+    RT_TRY(rt_scene_require_built(s, "rt_trace_batch", "%s: scene not built"));
     RT_REQUIRE(kernel == RT_TRACE_FAST || kernel == RT_TRACE_CANONICAL, "unknown kernel selector");
     if (n == 0) return RT_OK;
     RT_REQUIRE(origin_tmin && dir_tmax, "null ray arrays");

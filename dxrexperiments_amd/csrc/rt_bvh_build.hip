@@ -1,10 +1,8 @@
-// rt_bvh_build.hip -- BLAS / TLAS construction on the GPU.
+// rt_bvh_build.hip -- the LBVH builder, which the TLAS shares (rt_lbvh.h, rt_scene.hip), and BLAS construction on the GPU.
 //
 // Stands in for what the reference enqueues through the Fallback Layer:
 //   RtModel::build  -> BottomLevelASGenerator::Generate -> BuildRaytracingAccelerationStructure
 //       (libs/DXRFramework/RtModel.cpp:86-118, Helpers/BottomLevelASGenerator.cpp:279-343)
-//   RtScene::build  -> TopLevelASGenerator::Generate    -> BuildRaytracingAccelerationStructure
-//       (libs/DXRFramework/RtScene.cpp:18-52, Helpers/TopLevelASGenerator.cpp:309-414)
 // The builder itself (source absent from the reference checkout) is this engine's
 // own: an LBVH whose every integer step is fully determined, so the CPU oracle and
 // these kernels produce identical node arrays:
@@ -15,7 +13,7 @@
 //   5. bottom-up AABB union (exact float min/max; order independent)
 //   6. traversal layout (rt_bvh_ploc.hip, rt_bvh_wide.hip): a better binary tree over the same leaves,
 //      collapsed into four-wide 64-B nodes; subtrees of <= leaf_max primitives become leaves.
-#include "rt_internal.h"
+#include "rt_lbvh.h"
 
 #include <chrono>
 
@@ -23,25 +21,8 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rt_refs.h"
-#include "rt_xform.h"
 
 namespace {
-
-struct Box6 { float lo[3]; float hi[3]; };
-
-// order-preserving float <-> uint map for atomicMin / atomicMax
-__device__ __forceinline__ uint32_t f_enc(float f)
-{
-    uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float f_dec(uint32_t k)
-{
-    uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(b);
-}
-#define ENC_POS_INF 0xFF800000u
-#define ENC_NEG_INF 0x007FFFFFu
 
 __device__ __forceinline__ float wave_min(float v)
 {
@@ -123,6 +104,38 @@ __global__ void k_box_bounds(const Box6 *__restrict__ boxes, uint32_t n, uint32_
 __global__ void k_decode_bounds(const uint32_t *enc, float *out)
 {
     if (threadIdx.x < 6) out[threadIdx.x] = f_dec(enc[threadIdx.x]);
+}
+
+// The world box of a transformed instance: the exact box of its triangles' transformed vertices (oracle_bvh.h
+// scene_build; the box of the BLAS box's eight transformed corners is up to 1.6x wider in footprint for a rotated mesh, and a third
+// of all instance entries of the 4096-instance frame were false ones, profiles/r04/tight_boxes.txt).  One block per work item =
+// (slot of the list, chunk of INST_BOX_REFS vertex references); x' = ((m0 x + m1 y) + m2 z) + m3 as the oracle's xform_point; min / max
+// are order free, so the atomics cannot change a bit.  The transform and the encoded box go by slot.  The grid is the host's bound; blocks
+// beyond the list's count have nothing to do.  (The scene's kernel, rt_scene.hip: here for the sake of its instructions, rt_lbvh.h.)
+__global__ void __launch_bounds__(BOUNDS_BLOCK) k_instance_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx,
+                                                                const float *__restrict__ pend_xf, const uint2 *__restrict__ items,
+                                                                const uint32_t *__restrict__ n_items, uint32_t *__restrict__ enc)
+{
+    if (blockIdx.x >= *n_items) return;                // (block-uniform)
+    const uint2 it = items[blockIdx.x];
+    const InstanceRec &in = inst[pend_idx[it.x]];
+    const float *m = pend_xf + 12u * (size_t)it.x;
+    const uint32_t refs = 3u * in.n_prims;
+    const float inf = __uint_as_float(0x7f800000u);
+    Box6 b;
+    for (int c = 0; c < 3; c++) { b.lo[c] = inf; b.hi[c] = -inf; }
+    for (uint32_t k = it.y * INST_BOX_REFS + threadIdx.x; k < refs && k < (it.y + 1u) * INST_BOX_REFS; k += BOUNDS_BLOCK) {
+        const rt_float3 p = in.verts[in.indices[k]].position;
+        for (int r = 0; r < 3; r++) {
+            float w = m[4 * r + 0] * p.x;
+            w = w + m[4 * r + 1] * p.y;
+            w = w + m[4 * r + 2] * p.z;
+            w = w + m[4 * r + 3];
+            b.lo[r] = fminf(b.lo[r], w);
+            b.hi[r] = fmaxf(b.hi[r], w);
+        }
+    }
+    reduce_bounds(b, true, enc + 6u * (size_t)it.x);
 }
 
 __device__ __forceinline__ uint32_t expand10(uint32_t v)
@@ -325,8 +338,6 @@ __global__ void k_normal_records(const rt_vertex *__restrict__ verts, const uint
     out[p] = t;
 }
 
-inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
-
 // 64-bit sum of n 32-bit counts (grid-stride; one atomic per wave)
 __global__ void k_sum64(const uint32_t *__restrict__ v, uint32_t n, unsigned long long *__restrict__ out)
 {
@@ -418,29 +429,7 @@ __global__ void k_ref_mark_records(TriRec *__restrict__ tris, uint32_t n, const 
     if (off[prim + 1] - off[prim] > 1u) tris[k].c.z = __uint_as_float(2u);
 }
 
-// Temporaries of an LBVH build over n primitives: slices of the context's build arena.  Every builder describes its slices once, to a
-// Carver; the arena is sized by running the same description without a base (and for the larger of the LBVH and the PLOC / collapse
-// phases, which run one after the other).
-struct LbvhTemps {
-    Box6 *boxes;
-    uint32_t *enc;               // encoded bounds (k_init_bounds .. k_decode_bounds)
-    float *bounds;
-    uint64_t *keys;              // unsorted Morton keys
-    void *sort; size_t sort_bytes;      // room for the radix sort's scratch: what rocPRIM asks for is only known from its query
-    uint32_t *refit_enc, *depth;
-};
-void carve_lbvh(Carver &c, uint32_t n, LbvhTemps &t)
-{
-    t.boxes = c.take<Box6>(n);
-    t.enc = c.take<uint32_t>(6);
-    t.bounds = c.take<float>(6);
-    t.keys = c.take<uint64_t>(n);
-    t.sort_bytes = 16 * (size_t)n + (4u << 20);
-    t.sort = c.take<char>(t.sort_bytes);
-    t.refit_enc = c.take<uint32_t>(8 * (2 * (size_t)n - 1));
-    t.depth = c.take<uint32_t>(1);
-}
-// (+ the reference count of every triangle, its scan and the scan's scratch)
+// the temporaries of a BLAS build: the LBVH's (rt_lbvh.h) + the reference count of every triangle, its scan and the scan's scratch
 struct BlasTemps : LbvhTemps {
     uint32_t *ref_count, *ref_off;      // n + 1 each
     void *scan; size_t scan_bytes;
@@ -453,25 +442,28 @@ void carve_blas(Carver &c, uint32_t n, BlasTemps &t)
     t.scan_bytes = (size_t)1 << 20;
     t.scan = c.take<char>(t.scan_bytes);
 }
-// (the TLAS adds the work memory of its record and world-box kernels: TlasTemps, further down)
-template <class Temps, class Carve> int take_build_temps(rt_context *ctx, uint32_t n, Temps &t, Carve carve)
-{
-    Carver sizing(nullptr);
-    carve(sizing, t);
-    const size_t ploc = rt_ploc_temp_bytes(n), wide = rt_wide_lbvh_temp_bytes(n);
-    size_t most = sizing.offset > ploc ? sizing.offset : ploc;
-    most = most > wide ? most : wide;
-    RT_TRY(ctx->build_arena.reserve(most));
-    Carver c(ctx->build_arena.p);
-    carve(c, t);
-    return RT_OK;
-}
 void drop_build_arena_if_large(rt_context *ctx)
 {
     if (ctx->build_arena.bytes > ((size_t)256 << 20)) ctx->build_arena.release();      // keep small arenas for the next build
 }
 
-// Steps 2..6 for a structure whose primitive boxes and bounds are already on the device.
+}  // namespace
+
+// ---- the builder's host entry points (rt_lbvh.h) ----
+
+void lbvh_queue_box_bounds(rt_context *ctx, uint32_t n, const LbvhTemps &t)
+{
+    k_init_bounds<<<1, 64, 0, ctx->stream>>>(t.enc);
+    k_box_bounds<<<grid_for(n, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, ctx->stream>>>(t.boxes, n, t.enc);
+    k_decode_bounds<<<1, 64, 0, ctx->stream>>>(t.enc, t.bounds);
+}
+
+void lbvh_queue_instance_boxes(rt_context *ctx, uint32_t max_items, const InstanceRec *inst, const uint32_t *pend_idx, const float *pend_xf, const uint2 *items,
+                               const uint32_t *n_items, uint32_t *enc)
+{
+    k_instance_boxes<<<max_items, BOUNDS_BLOCK, 0, ctx->stream>>>(inst, pend_idx, pend_xf, items, n_items, enc);
+}
+
 int lbvh_from_boxes(rt_context *ctx, BvhDev &bv, uint32_t n, const LbvhTemps &t)
 {
     hipStream_t st = ctx->stream;
@@ -516,7 +508,6 @@ int lbvh_from_boxes(rt_context *ctx, BvhDev &bv, uint32_t n, const LbvhTemps &t)
     return RT_OK;
 }
 
-// joins the stream and takes the depth and bounds lbvh_from_boxes queued for read-back
 int lbvh_collect(rt_context *ctx, BvhDev &bv)
 {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -528,6 +519,8 @@ int lbvh_collect(rt_context *ctx, BvhDev &bv)
 }
 
 // ---- the steps of a BLAS build (rt_build_blas) ----
+
+namespace {
 
 constexpr unsigned BB = 256;
 
@@ -709,389 +702,4 @@ int rt_build_blas(rt_context *ctx, rt_model *m)
     drop_build_arena_if_large(ctx);
     clock.mark("free");
     return rc;
-}
-
-// ---- instance masks (rt_scene_set_instance_mask): the TLAS over the visible sub-list ----
-//
-// Stands in for the InstanceMask member of the instance descriptors (libs/DXRFramework/Helpers/TopLevelASGenerator.cpp:344-362, always 0xFF
-// there) under the inclusion mask 0xFF of every TraceRay of the reference.  `vis` holds the visible instances' indices in ascending order;
-// the LBVH is built over vis.size() leaves, and wherever it names the j-th of them the TLAS names vis[j].
-
-namespace {
-
-constexpr unsigned UPD_BLOCK = 256;
-
-// sub-list position -> instance index, in the canonical leaves' `left` and the low words of the sorted keys (vis is increasing: the keys stay
-// ascending).  k_lbvh_to_tree takes a TLAS leaf's code from `left`, so the four-wide layout comes out mapped
-__global__ void __launch_bounds__(UPD_BLOCK) k_map_visible(rt_bvh_node *__restrict__ nodes, uint64_t *__restrict__ keys, const uint32_t *__restrict__ vis,
-                                                          uint32_t n_vis)
-{
-    const uint32_t k = blockIdx.x * UPD_BLOCK + threadIdx.x;
-    if (k >= n_vis) return;
-    const uint64_t key = keys[k];
-    const uint32_t i = vis[(uint32_t)(key & 0xFFFFFFFFull)];
-    keys[k] = (key & 0xFFFFFFFF00000000ull) | i;
-    nodes[n_vis - 1 + k].left = i;
-}
-
-int map_visible_leaves(rt_context *ctx, rt_scene *s)
-{
-    const uint32_t nv = s->n_vis;
-    k_map_visible<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, ctx->stream>>>(s->tlas.nodes.as<rt_bvh_node>(), s->tlas.keys.as<uint64_t>(), s->d_vis.as<uint32_t>(), nv);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-// room for the TLAS of all n instances, whatever part is visible at the build: an update that shows instances again allocates nothing
-int reserve_tlas_for(BvhDev &bv, uint32_t n)
-{
-    RT_TRY(bv.nodes.reserve(sizeof(rt_bvh_node) * (2 * (size_t)n - 1)));
-    RT_TRY(bv.keys.reserve(sizeof(uint64_t) * n));
-    RT_TRY(bv.parents.reserve(sizeof(uint32_t) * (2 * (size_t)n - 1)));
-    RT_TRY(bv.ranges.reserve(sizeof(uint2) * (n > 1 ? n - 1 : 1)));
-    RT_TRY(bv.wide.reserve(sizeof(WNode) * (size_t)(n > 1 ? n - 1 : 1)));
-    return RT_OK;
-}
-
-}  // namespace
-
-int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool force)
-{
-    const uint32_t n = (uint32_t)s->inst.size();
-    std::vector<uint32_t> vis;
-    vis.reserve(n);
-    for (uint32_t i = 0; i < n; i++)
-        if (s->masks[i]) vis.push_back(i);
-    if (vis.empty()) { rt_set_error("%s: no instance is visible: every instance mask is 0 (rt_scene_set_instance_mask)", who); return RT_ERR_STATE; }
-    if (!force && vis == s->vis) return RT_OK;
-    s->vis.swap(vis);                                  // (a member: alive whenever the copy runs)
-    s->n_vis = (uint32_t)s->vis.size();
-    if (s->n_vis == n) return RT_OK;                   // nothing hidden: nobody reads the list
-    RT_TRY(s->d_vis.reserve(sizeof(uint32_t) * (size_t)n));       // (for all of them at once: never grows again)
-    HIP_TRY(hipMemcpyAsync(s->d_vis.p, s->vis.data(), sizeof(uint32_t) * s->n_vis, hipMemcpyHostToDevice, ctx->stream));
-    return RT_OK;
-}
-
-// ---- the TLAS: instance list -> records -> world boxes -> tree, ONE path for rt_scene_build and rt_scene_update ----
-//
-// rt_scene_update stands in for the generators' update path (libs/DXRFramework/Helpers/TopLevelASGenerator.h:144-163 `updateOnly`), which the
-// reference's RtScene never calls.  The definition is "update == build", and it holds by construction: a build writes what only a build
-// knows (the model part of every record, rt_build_tlas) and then IS an update with every instance pending (rt_update_tlas).  The canonical
-// TLAS is a pure function of the instance boxes and every traversal returns the same bits on any tree, so the TLAS is
-// always rebuilt -- into the scene's own buffers -- from boxes of which only the listed instances' are computed anew.  Only the listed
-// transforms and their indices go up; the records are rewritten, and the work list of the world boxes is made, on the device.
-
-namespace {
-
-constexpr unsigned UPD_BACK_WORDS = 20;      // inv[12], wlo[3], root_code, whi[3], flags: the head of an InstanceRec
-static_assert(offsetof(InstanceRec, flags) == 4 * (UPD_BACK_WORDS - 1), "the read-back of an update is the head of the record");
-constexpr unsigned INST_BOX_REFS = 4096;     // vertex references of one work item of k_instance_boxes
-
-// One lane per listed instance: the transform part of its record -- the inverse (invert3x4, rt_xform.h), the identity flag and the (empty or
-// BLAS) box; and the (slot, chunk of INST_BOX_REFS vertex references) work items of the transformed ones, compacted into `items`: a
-// wave-wide prefix sum of the lanes' chunk counts, ONE atomic per wave that has any (a ballot says so), every lane then writes its own run.
-// The order of the list depends on the order of the atomics; the boxes made from it do not (min / max).  max_items = the chunks of all
-// listed instances, transformed or not: the host's bound of the list and the next launch's grid.
-__global__ void __launch_bounds__(UPD_BLOCK) k_update_records(InstanceRec *__restrict__ inst, const float *__restrict__ blas_bounds,
-                                                              const uint32_t *__restrict__ pend_idx, const float *__restrict__ pend_xf, uint32_t n_pending,
-                                                              uint32_t *__restrict__ enc, uint2 *__restrict__ items, uint32_t *__restrict__ n_items,
-                                                              uint32_t max_items)
-{
-    const uint32_t slot = blockIdx.x * UPD_BLOCK + threadIdx.x;
-    const unsigned lane = threadIdx.x & 63u;
-    uint32_t chunks = 0;
-    if (slot < n_pending) {
-        const uint32_t i = pend_idx[slot];
-        float m[12], inv[12];
-        for (int k = 0; k < 12; k++) m[k] = pend_xf[12u * (size_t)slot + k];
-        const bool identity = is_identity3x4(m);
-        InstanceRec &r = inst[i];
-        if (identity)
-            for (int k = 0; k < 12; k++) inv[k] = m[k];              // (the floats as given: a -0 stays one)
-        else
-            invert3x4(m, inv);
-        const float inf = __uint_as_float(0x7f800000u);
-        for (int k = 0; k < 12; k++) r.inv[k] = inv[k];
-        for (int c = 0; c < 3; c++) {
-            r.wlo[c] = identity ? blas_bounds[6u * (size_t)i + c] : inf;     // (a transformed instance: empty until k_update_apply)
-            r.whi[c] = identity ? blas_bounds[6u * (size_t)i + 3 + c] : -inf;
-            enc[6u * (size_t)slot + c] = ENC_POS_INF;                        // (one without triangles keeps the empty box)
-            enc[6u * (size_t)slot + 3 + c] = ENC_NEG_INF;
-        }
-        r.flags = identity ? RT_INST_IDENTITY : 0u;
-        if (!identity) chunks = (3u * r.n_prims + INST_BOX_REFS - 1u) / INST_BOX_REFS;
-    }
-    // (every lane of the block is here: the block is whole waves and nothing has returned)
-    if (__ballot(chunks != 0u) == 0ull) return;        // wave-uniform
-    uint32_t incl = chunks;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t below = __shfl_up(incl, o, 64);
-        if (lane >= (unsigned)o) incl += below;
-    }
-    const uint32_t total = __shfl(incl, 63, 64);
-    uint32_t base = 0;
-    if (lane == 63u) base = atomicAdd(n_items, total);
-    base = __shfl(base, 63, 64);
-    const uint32_t first = base + (incl - chunks);
-    for (uint32_t c = 0; c < chunks; c++)
-        if (first + c < max_items) items[first + c] = make_uint2(slot, c);
-}
-
-// The world box of a transformed instance: the exact box of its triangles' transformed vertices (oracle_bvh.h
-// scene_build; the box of the BLAS box's eight transformed corners is up to 1.6x wider in footprint for a rotated mesh, and a third
-// of all instance entries of the 4096-instance frame were false ones, profiles/r04/tight_boxes.txt).  One block per work item =
-// (slot of the list, chunk of INST_BOX_REFS vertex references); x' = ((m0 x + m1 y) + m2 z) + m3 as the oracle's xform_point; min / max
-// are order free, so the atomics cannot change a bit.  The transform and the encoded box go by slot.  The grid is the host's bound; blocks
-// beyond the list's count have nothing to do.
-__global__ void __launch_bounds__(BOUNDS_BLOCK) k_instance_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx,
-                                                                const float *__restrict__ pend_xf, const uint2 *__restrict__ items,
-                                                                const uint32_t *__restrict__ n_items, uint32_t *__restrict__ enc)
-{
-    if (blockIdx.x >= *n_items) return;                // (block-uniform)
-    const uint2 it = items[blockIdx.x];
-    const InstanceRec &in = inst[pend_idx[it.x]];
-    const float *m = pend_xf + 12u * (size_t)it.x;
-    const uint32_t refs = 3u * in.n_prims;
-    const float inf = __uint_as_float(0x7f800000u);
-    Box6 b;
-    for (int c = 0; c < 3; c++) { b.lo[c] = inf; b.hi[c] = -inf; }
-    for (uint32_t k = it.y * INST_BOX_REFS + threadIdx.x; k < refs && k < (it.y + 1u) * INST_BOX_REFS; k += BOUNDS_BLOCK) {
-        const rt_float3 p = in.verts[in.indices[k]].position;
-        for (int r = 0; r < 3; r++) {
-            float w = m[4 * r + 0] * p.x;
-            w = w + m[4 * r + 1] * p.y;
-            w = w + m[4 * r + 2] * p.z;
-            w = w + m[4 * r + 3];
-            b.lo[r] = fminf(b.lo[r], w);
-            b.hi[r] = fmaxf(b.hi[r], w);
-        }
-    }
-    reduce_bounds(b, true, enc + 6u * (size_t)it.x);
-}
-
-// the boxes into the records of the listed transformed instances (identity instances keep the box of their BLAS); the head of every listed
-// record into the read-back for h_inst
-__global__ void k_update_apply(InstanceRec *__restrict__ inst, const uint32_t *__restrict__ pend_idx, uint32_t n_pending,
-                               const uint32_t *__restrict__ enc, uint32_t *__restrict__ back)
-{
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= n_pending) return;
-    InstanceRec &r = inst[pend_idx[slot]];
-    if (!(r.flags & RT_INST_IDENTITY))
-        for (int c = 0; c < 3; c++) { r.wlo[c] = f_dec(enc[6u * (size_t)slot + c]); r.whi[c] = f_dec(enc[6u * (size_t)slot + 3 + c]); }
-    const uint32_t *head = reinterpret_cast<const uint32_t *>(&r);
-    for (unsigned k = 0; k < UPD_BACK_WORDS; k++) back[UPD_BACK_WORDS * (size_t)slot + k] = head[k];
-}
-
-// the world box of every visible instance, as it stands in its record (an untouched one's too) -> the TLAS builder's leaf boxes; vis == nullptr:
-// nothing is hidden, position j is instance j.  Read from the RECORDS, which nobody writes here: `boxes` may still hold another list's
-__global__ void __launch_bounds__(UPD_BLOCK) k_leaf_boxes(const InstanceRec *__restrict__ inst, const uint32_t *__restrict__ vis, uint32_t n_vis,
-                                                         Box6 *__restrict__ boxes)
-{
-    const uint32_t j = blockIdx.x * UPD_BLOCK + threadIdx.x;
-    if (j >= n_vis) return;
-    const InstanceRec &r = inst[vis ? vis[j] : j];
-    for (int c = 0; c < 3; c++) { boxes[j].lo[c] = r.wlo[c]; boxes[j].hi[c] = r.whi[c]; }
-}
-
-// The model part of an instance record: what the record says about its model.  A build writes it for every instance; after a deformed
-// model's BLAS has been rebuilt (rt_scene_update) DevBuf::reserve may have moved any of the arrays, and n_recs and the reference buffers
-// come and go with the shape.  The field list stands twice: in model_desc and in write_model_part.
-struct ModelDesc {
-    const WNode *wide;
-    const TriRec *tris;
-    const rt_bvh_node *cnodes;
-    const rt_vertex *verts;
-    const uint32_t *indices;
-    const TriRec *normals;
-    const float *rec_boxes;
-    const uint32_t *ref_off;
-    const float *ref_boxes;
-    int root_code;
-    uint32_t n_prims, n_recs;
-    float bounds[6];             // the BLAS box: the instance's row of blas_bounds
-    uint32_t pad_;
-};
-static_assert(sizeof(ModelDesc) % 8 == 0, "an array of descriptors keeps its pointers aligned");
-
-ModelDesc model_desc(const rt_model *m)
-{
-    ModelDesc d;
-    d.wide = m->blas.wide.as<WNode>();
-    d.tris = m->tris.as<TriRec>();
-    d.cnodes = m->blas.nodes.as<rt_bvh_node>();
-    d.verts = m->d_verts.as<rt_vertex>();
-    d.indices = m->d_idx.as<uint32_t>();
-    d.normals = m->normals.as<TriRec>();
-    d.rec_boxes = m->rec_boxes.p ? m->rec_boxes.as<float>() : nullptr;
-    d.ref_off = m->ref_off.p ? m->ref_off.as<uint32_t>() : nullptr;
-    d.ref_boxes = m->ref_boxes.p ? m->ref_boxes.as<float>() : nullptr;
-    d.root_code = m->blas.root_code;
-    d.n_prims = m->n_tris;
-    d.n_recs = m->n_recs;
-    memcpy(d.bounds, m->blas.bounds, sizeof d.bounds);
-    d.pad_ = 0;
-    return d;
-}
-
-// ... into a record and the instance's row of the BLAS boxes (device: d_inst / blas_bounds; host: h_inst / h_blas_bounds)
-__host__ __device__ inline void write_model_part(InstanceRec &r, float *bounds_row, const ModelDesc &d)
-{
-    r.wide = d.wide; r.tris = d.tris; r.cnodes = d.cnodes; r.verts = d.verts; r.indices = d.indices; r.normals = d.normals;
-    r.rec_boxes = d.rec_boxes; r.ref_off = d.ref_off; r.ref_boxes = d.ref_boxes;
-    r.root_code = d.root_code; r.n_prims = d.n_prims; r.n_recs = d.n_recs;
-    for (int c = 0; c < 6; c++) bounds_row[c] = d.bounds[c];
-}
-
-// one lane per affected instance: who = (instance, descriptor)
-__global__ void k_update_model_fields(InstanceRec *__restrict__ inst, float *__restrict__ blas_bounds, const ModelDesc *__restrict__ desc,
-                                      const uint2 *__restrict__ who, uint32_t n)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const uint32_t i = who[k].x;
-    write_model_part(inst[i], blas_bounds + 6u * (size_t)i, desc[who[k].y]);
-}
-
-// (+ the listed indices and transforms, their encoded boxes, the work list and its count).  LIFETIME: the phases of a build share the
-// arena -- lbvh_from_boxes reads these slices, then rt_build_wide_from_lbvh (as the PLOC phase of a BLAS) carves the SAME arena again from
-// its start.  So nothing here may be read behind the wide collapse: whatever has to outlive it, as the record heads on their way to h_inst
-// do, lives in a buffer of the scene's own (rt_scene::update_back).
-struct TlasTemps : LbvhTemps {
-    uint32_t *pend_idx;
-    float *pend_xf;
-    uint32_t *pend_enc;
-    uint2 *items;
-    uint32_t *n_items;
-};
-void carve_tlas(Carver &c, uint32_t n, size_t n_pending, size_t max_items, TlasTemps &t)
-{
-    carve_lbvh(c, n, t);
-    t.pend_idx = c.take<uint32_t>(n_pending);
-    t.pend_xf = c.take<float>(12 * n_pending);
-    t.pend_enc = c.take<uint32_t>(6 * n_pending);
-    t.items = c.take<uint2>(max_items);
-    t.n_items = c.take<uint32_t>(1);
-}
-
-}  // namespace
-
-int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &changed)
-{
-    hipStream_t st = ctx->stream;
-    std::vector<const rt_model *> models;              // the distinct models of `changed` (a handful: a linear search)
-    std::vector<uint2> who(changed.size());
-    for (size_t k = 0; k < changed.size(); k++) {
-        const rt_model *m = s->inst[changed[k]].model;
-        size_t at = 0;
-        while (at < models.size() && models[at] != m) at++;
-        if (at == models.size()) models.push_back(m);
-        who[k] = make_uint2(changed[k], (uint32_t)at);
-    }
-    std::vector<ModelDesc> desc(models.size());
-    for (size_t k = 0; k < models.size(); k++) desc[k] = model_desc(models[k]);
-    // the table and the list go up through a slice of the build arena: the update that follows carves the arena again, behind this kernel on
-    // the stream
-    const size_t desc_bytes = (sizeof(ModelDesc) * desc.size() + 255) & ~(size_t)255;
-    RT_TRY(ctx->build_arena.reserve(desc_bytes + sizeof(uint2) * who.size()));
-    ModelDesc *d_desc = ctx->build_arena.as<ModelDesc>();
-    uint2 *d_who = (uint2 *)(ctx->build_arena.as<char>() + desc_bytes);
-    HIP_TRY(hipMemcpyAsync(d_desc, desc.data(), sizeof(ModelDesc) * desc.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_who, who.data(), sizeof(uint2) * who.size(), hipMemcpyHostToDevice, st));
-    k_update_model_fields<<<grid_for(who.size(), UPD_BLOCK), UPD_BLOCK, 0, st>>>(s->d_inst.as<InstanceRec>(), s->blas_bounds.as<float>(), d_desc, d_who,
-                                                                                (uint32_t)who.size());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));                 // (the host vectors go out of scope; a reserve of the arena by the update frees this slice)
-    for (size_t k = 0; k < changed.size(); k++)        // the host mirrors follow
-        write_model_part(s->h_inst[changed[k]], &s->h_blas_bounds[6 * (size_t)changed[k]], desc[who[k].y]);
-    return RT_OK;
-}
-
-int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &list, const char *who, hipEvent_t queued)
-{
-    hipStream_t st = ctx->stream;
-    const uint32_t n = (uint32_t)s->inst.size();
-    const size_t np = list.size();
-    std::vector<float> xf(12 * np);                    // (alive, as the index list is, until the last synchronisation below)
-    size_t max_items = 0;
-    for (size_t k = 0; k < np; k++) {
-        const SceneInstance &in = s->inst[list[k]];
-        memcpy(&xf[12 * k], in.xform, 12 * sizeof(float));
-        max_items += (3 * (size_t)in.model->n_tris + INST_BOX_REFS - 1) / INST_BOX_REFS;
-    }
-    if (max_items > 0x7fffffffu) { rt_set_error("%s: %zu work items for the world boxes: the limit is 2^31 - 1", who, max_items); return RT_ERR_UNSUPPORTED; }
-    TlasTemps t;
-    RT_TRY(take_build_temps(ctx, n, t, [n, np, max_items](Carver &c, TlasTemps &tt) { carve_tlas(c, n, np, max_items, tt); }));
-    // for all n at once, whatever part is listed or visible: allocated by a build, never again by an update
-    RT_TRY(reserve_tlas_for(s->tlas, n));
-    RT_TRY(s->update_back.reserve(sizeof(uint32_t) * UPD_BACK_WORDS * (size_t)n));
-    std::vector<uint32_t> back(UPD_BACK_WORDS * np);
-    InstanceRec *inst = s->d_inst.as<InstanceRec>();
-    if (np) {                                          // (none: an update of masks alone)
-        HIP_TRY(hipMemcpyAsync(t.pend_idx, list.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
-        k_update_records<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->blas_bounds.as<float>(), t.pend_idx, t.pend_xf, (uint32_t)np, t.pend_enc,
-                                                                       t.items, t.n_items, (uint32_t)max_items);
-        if (max_items) k_instance_boxes<<<(uint32_t)max_items, BOUNDS_BLOCK, 0, st>>>(inst, t.pend_idx, t.pend_xf, t.items, t.n_items, t.pend_enc);
-        k_update_apply<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, t.pend_idx, (uint32_t)np, t.pend_enc, s->update_back.as<uint32_t>());
-    }
-    // the records are the full list's, hidden instances' included; the leaves are the visible ones' (all n when nothing is hidden)
-    const uint32_t nv = s->n_vis;
-    k_leaf_boxes<<<grid_for(nv, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, nv < n ? s->d_vis.as<uint32_t>() : nullptr, nv, t.boxes);
-    k_init_bounds<<<1, 64, 0, st>>>(t.enc);
-    k_box_bounds<<<grid_for(nv, BOUNDS_BLOCK), BOUNDS_BLOCK, 0, st>>>(t.boxes, nv, t.enc);
-    k_decode_bounds<<<1, 64, 0, st>>>(t.enc, t.bounds);
-    RT_TRY(lbvh_from_boxes(ctx, s->tlas, nv, t));
-    if (nv < n) RT_TRY(map_visible_leaves(ctx, s));
-    // the TLAS is walked in the same four-wide layout (a single instance: the root is the leaf of that instance)
-    RT_TRY(rt_build_wide_from_lbvh(ctx, s->tlas, true, 1));
-    if (nv < n && nv == 1) s->tlas.root_code = ~(int)s->vis[0];       // (the one visible instance's own index)
-    if (queued) HIP_TRY(hipEventRecord(queued, st));
-    // the final join: it brings back the rewritten records' heads with the TLAS' depth and bounds
-    if (np) HIP_TRY(hipMemcpyAsync(back.data(), s->update_back.p, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    RT_TRY(lbvh_collect(ctx, s->tlas));
-    for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[list[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
-    // the scene's summary, taken again over all models: a deformation changes depths and can create or remove split references
-    uint32_t deepest = 0, canon = s->tlas.max_depth;
-    s->has_refs = false;
-    for (uint32_t i = 0; i < n; i++) {
-        const rt_model *m = s->inst[i].model;
-        const BvhDev &b = m->blas;
-        deepest = b.fast_depth > deepest ? b.fast_depth : deepest;
-        canon = b.max_depth > canon ? b.max_depth : canon;
-        s->has_refs = s->has_refs || m->ref_off.p != nullptr;
-    }
-    // a step leaves at most three siblings behind; two-level walks add the TLAS path and the sentinel that marks the
-    // bottom of a BLAS walk
-    s->two_level = !(n == 1 && (s->h_inst[0].flags & RT_INST_IDENTITY));
-    s->stack_need = s->two_level ? s->tlas.fast_depth + 1 + deepest : deepest;
-    // the canonical traversal (parity / counting kernels and the deep-stack path of the fast one) keeps
-    // 128-entry private stacks per structure
-    if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); return RT_ERR_UNSUPPORTED; }
-    if (ctx->verbose)
-        fprintf(stderr, "[dxr_amd] %s: TLAS update, %zu of %u instances, %u visible, depth %u; deepest BLAS layout depth %u (%s); stack need %u; %s walk\n",
-                who, np, n, nv, s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
-    return RT_OK;
-}
-
-int rt_build_tlas(rt_context *ctx, rt_scene *s)
-{
-    hipStream_t st = ctx->stream;
-    const uint32_t n = (uint32_t)s->inst.size();
-    s->h_inst.assign(n, InstanceRec());
-    s->h_blas_bounds.resize(6 * (size_t)n);            // (members: alive whenever the copies run)
-    std::vector<uint32_t> all(n);                      // (alive until rt_update_tlas has joined the stream)
-    for (uint32_t i = 0; i < n; i++) {
-        InstanceRec &r = s->h_inst[i];
-        write_model_part(r, &s->h_blas_bounds[6 * (size_t)i], model_desc(s->inst[i].model));
-        r.pad_ = 0;
-        r.material = i;
-        all[i] = i;
-    }
-    RT_TRY(s->d_inst.reserve(sizeof(InstanceRec) * (size_t)n));
-    RT_TRY(s->blas_bounds.reserve(6 * (size_t)n * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(s->d_inst.p, s->h_inst.data(), sizeof(InstanceRec) * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->blas_bounds.p, s->h_blas_bounds.data(), 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    return rt_update_tlas(ctx, s, all, "rt_scene_build", nullptr);
 }

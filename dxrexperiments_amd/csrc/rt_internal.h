@@ -419,60 +419,21 @@ struct rt_scene {
         s.top_n = 0;
         return s;
     }
-    ~rt_scene();                 // (rt_api.hip) selects the device, lets go of the models it retains; then the buffers
+    ~rt_scene();                 // (rt_scene.hip) selects the device, lets go of the models it retains; then the buffers
 };
 
 // ---- internal entry points shared between translation units ---------------------
 
 // rt_bvh_build.hip
 int rt_build_blas(rt_context *ctx, rt_model *m);
-// the build's share of the TLAS: the model part of every record and the per-instance BLAS boxes, written on the host and uploaded; then
-// rt_update_tlas with every instance listed
-int rt_build_tlas(rt_context *ctx, rt_scene *s);
-// the visible sub-list from s->masks into s->vis / d_vis / n_vis, uploaded if it differs from the one the scene has (or `force`: a build,
-// whose TLAS buffers may be new); RT_ERR_STATE, and nothing changed, if no instance is visible
-int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool force);
-// THE TLAS path of a build (list: every instance, 0 .. n-1) and of an update (s->pending): rewrites the transform part of the listed
-// instances' records and their world boxes, rebuilds the TLAS over the visible instances and takes the scene's summary, on the device.
-// `who` names the caller in messages.  It creates no event and reads no time; `queued` (or nullptr) is the caller's event, which it records
-// behind the wide collapse, in front of the read-back: where update_ms ends
-int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &list, const char *who, hipEvent_t queued);
-// the model fields of the records of `changed` (instances whose model was rebuilt) and their rows of blas_bounds, on the device; h_inst follows
-int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &changed);
 
-// instances of an updatable scene whose model's vertices were set since the scene last wrote their records
-static inline size_t rt_scene_changed_instances(const rt_scene *s, std::vector<uint32_t> *which = nullptr)
-{
-    size_t n = 0;
-    if (!s->updatable || s->seen_geom.size() != s->inst.size()) return 0;
-    for (size_t i = 0; i < s->inst.size(); i++)
-        if (s->inst[i].model->geom_gen != s->seen_geom[i]) { n++; if (which) which->push_back((uint32_t)i); }
-    return n;
-}
-
-// A scene whose transforms, instance masks or models' vertices were set and not applied yet: says so (the message names them) and returns true.
-static inline bool rt_scene_stale_error(const rt_scene *s, const char *who)
-{
-    if (!s || s->built) return false;
-    const size_t changed = rt_scene_changed_instances(s);
-    const char *masks = s->updatable && s->masks_dirty ? " and instance masks" : "";
-    if (changed) {
-        char also[128] = "";
-        if (!s->pending.empty()) snprintf(also, sizeof also, " and %zu instance transform%s%s", s->pending.size(), s->pending.size() == 1 ? "" : "s", masks);
-        else snprintf(also, sizeof also, "%s", masks);
-        rt_set_error("%s: new vertices of the model%s of %zu instance%s%s pending (rt_model_set_vertices / _set_positions / _recompute_normals): "
-                     "rt_scene_update or rt_scene_build applies them", who, changed == 1 ? "" : "s", changed, changed == 1 ? "" : "s", also);
-        return true;
-    }
-    if (s->pending.empty()) {
-        if (!masks[0]) return false;
-        rt_set_error("%s: instance masks pending (rt_scene_set_instance_mask): rt_scene_update or rt_scene_build applies them", who);
-        return true;
-    }
-    rt_set_error("%s: %zu instance transform%s%s pending (rt_scene_set_instance_transform): rt_scene_update or rt_scene_build applies them", who,
-                 s->pending.size(), s->pending.size() == 1 ? "" : "s", masks);
-    return true;
-}
+// rt_scene.hip
+void rt_scene_retain(rt_scene *s);
+// new vertices of one of the scene's models have been queued (rt_model.hip): a fresh scene is stale until its update or build applies them
+void rt_scene_model_changed(rt_scene *s);
+// RT_OK for a built scene.  Otherwise RT_ERR_STATE and its message: what is pending -- transforms, instance masks, models' vertices -- or, if
+// nothing is, `not_built`, a format that may name `who` once
+int rt_scene_require_built(const rt_scene *s, const char *who, const char *not_built);
 
 // rt_bvh_ploc.hip
 // n_leaves / leaf_box6 / leaf_prim: the leaves to cluster in Morton order -- nullptr: the canonical leaves (one per triangle); else the
@@ -567,7 +528,6 @@ int rt_context_flush_deferred(rt_context *ctx);
 // rt_api.hip
 void rt_context_retain(rt_context *ctx);
 void rt_context_release(rt_context *ctx);
-void rt_scene_retain(rt_scene *s);
 
 // rt_obj.cpp, rt_fbx.cpp
 int rt_obj_parse(const char *path, std::vector<rt_vertex> &verts, std::vector<uint32_t> &idx);

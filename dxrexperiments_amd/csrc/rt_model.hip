@@ -177,8 +177,7 @@ void model_changed(rt_model *m)
 {
     m->geom_gen++;
     m->built = false;         // rt_scene_update and rt_scene_build rebuild the BLAS (rt_build_blas)
-    for (rt_scene *s : m->scenes)
-        if (s->updatable) s->built = false;            // (never built, or instances added since: the next build reads the new vertices anyway)
+    for (rt_scene *s : m->scenes) rt_scene_model_changed(s);
 }
 
 // `input`: the `floats` floats the launch reads, in host or device memory as `mem` says, or nullptr.  launch(const float *on_device) queues the

@@ -193,7 +193,7 @@ int scene_for_set(rt_pipeline *p, uint32_t n_frames, SceneDev *out, bool *sets_k
 // what every render call needs before it may record or render a frame (`own_frame`: the last update()'s); `who`: the entry point, as its messages name it
 int check_renderable(const rt_pipeline *p, uint32_t width, uint32_t height, bool own_frame, const char *who)
 {
-    if (!p->scene || !p->scene->built) { if (!rt_scene_stale_error(p->scene, "render")) rt_set_error("render: acceleration structures not built"); return RT_ERR_STATE; }
+    RT_TRY(rt_scene_require_built(p->scene, "render", "%s: acceleration structures not built"));
     if (!p->accum) { rt_set_error("render: no output resource"); return RT_ERR_STATE; }
     if (own_frame && !p->have_pfc) { rt_set_error("render: update() has not been called"); return RT_ERR_STATE; }
     if (p->mats.empty()) { rt_set_error("render: no material"); return RT_ERR_STATE; }
@@ -393,8 +393,9 @@ int flush_pending_now(rt_pipeline *p)
 int count_replay(rt_pipeline *p, const char *who, int (*launch)(rt_pipeline *, unsigned long long *), unsigned long long *h, size_t words)
 {
     RT_TRY(rt_pipeline_flush_pending(p));
-    if (p->rendered && rt_scene_stale_error(p->scene, who)) return RT_ERR_STATE;       // (transforms, masks or vertices pending: the message names them)
-    if (!p->rendered || !p->scene->built || p->scene->generation != p->last_scene_gen) { rt_set_error("%s: nothing rendered since the last change of scene, materials or output", who); return RT_ERR_STATE; }
+    const char *nothing = "%s: nothing rendered since the last change of scene, materials or output";
+    if (p->rendered) RT_TRY(rt_scene_require_built(p->scene, who, nothing));       // (transforms, masks or vertices pending: the message names them)
+    if (!p->rendered || p->scene->generation != p->last_scene_gen) { rt_set_error(nothing, who); return RT_ERR_STATE; }
     HIP_TRY(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
     RT_TRY(p->work.reserve(RT_STAGE_COUNT * RT_WALK_WORDS * sizeof(unsigned long long)));

@@ -1,4 +1,4 @@
-// rt_xform.h -- the instance transform's arithmetic.  The library runs it on the device only: k_update_records (rt_bvh_build.hip) writes
+// rt_xform.h -- the instance transform's arithmetic.  The library runs it on the device only: k_update_records (rt_scene.hip) writes
 // the transform part of every instance record, for rt_scene_build and rt_scene_update alike.  The one host user of invert3x4 is
 // tests/cpp/invert3x4_sanitized.cpp, which compiles this header with g++ for the CPU under the sanitizers: it stays plain C++ (no HIP
 // header needed), the same operations in the same order, without contraction.
