@@ -24,16 +24,41 @@ The rules (numbered as the sweep's log and DESIGN.md section 6 name them):
 15. set_vertices / set_positions after set_skin change the current vertices, not the rest pose; the next set_bones overwrites every vertex
     from the rest pose.
 16. geometry() always returns the current vertices.
-Vertex arithmetic is that of skin_cases.skinned and deform_cases.normals_of, each held byte for byte to its kernel by the feature's own tests."""
+Morph targets and posed skeletons (include/dxr_amd.h "Morph targets", "Posed skeletons").  A model has up to three hidden vertex arrays next to
+its current vertices -- the skin's rest pose, the morph base -- and no reader returns them: a wrong one shows through the next producer.
+17. set_morph_targets changes no vertex and leaves no scene stale.  It captures the BASE: the skin's rest pose if the model has a skin then,
+    otherwise the current vertices.  Calling it again replaces the targets and captures the base anew.
+18. A refused set_morph_targets returns ERR_INVALID_ARG and keeps the old targets and the old base: target_offsets[0] != 0, offsets that
+    decrease, a vertex index >= V, indices within a target that do not ascend strictly, more than 65536 targets.
+19. clear_morph_targets removes the targets; the vertices and the rest pose stay.
+20. set_morph_weights without targets returns ERR_STATE.
+21. set_morph_weights on a model without a skin: the vertices = morphed(base, ...), the whole mesh, always from the base; every built scene
+    that holds the model goes stale (as rule 4).
+22. set_morph_weights on a model with a skin: the REST POSE = morphed(base, ...); the vertices are untouched and no scene goes stale; the next
+    set_bones poses the morphed rest pose.
+23. set_skin captures its rest pose from the current vertices (rule 14) and never touches the morph base; it redirects later morph results
+    to the new rest pose.  clear_skin redirects them to the vertices.  Neither recaptures the base.
+24. set_vertices / set_positions / recompute_normals on a morphed model write the current vertices and leave the base alone.
+25. A skeleton holds parents, inverse binds, a pose, clips, and -- once posed -- world matrices and a palette.  set_pose, add_clip, clear_clips
+    and set_time touch no model and no scene.
+26. set_time on an unknown clip returns ERR_STATE, with a NaN time ERR_INVALID_ARG; add_clip with a time that is not finite or with times
+    that do not ascend strictly returns ERR_INVALID_ARG.  clear_clips makes ids start at 0 again and keeps the pose.
+27. set_bones_from(skeleton) returns ERR_STATE before the skeleton's first pose, for a model without a skin, and for a skin whose n_bones is
+    not the skeleton's n_joints; otherwise it is set_bones with the skeleton's palette AS IT IS AT THE CALL: a pose set before the update
+    does not reach the vertices.  A skeleton may be destroyed right after the call.
+Vertex arithmetic is that of skin_cases.skinned, deform_cases.normals_of, morph_cases.morphed, skeleton_cases.posed and skeleton_cases.sampled,
+each held byte for byte to its kernel by the feature's own tests."""
 import numpy as np
 
 from deform_cases import normals_of
-from skin_cases import skinned
+from morph_cases import morphed
+from skeleton_cases import posed, sampled
+from skin_cases import canonical_nans, skinned
 
 OK, ERR_INVALID_ARG, ERR_STATE = 0, -1, -4
 UNBUILT, FRESH, STALE = "never built since the last add", "fresh", "stale"
 VERTEX = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3)])          # include/dxr_amd_types.h rt_vertex: 24 bytes
-MAX_INFLUENCES, MAX_BONES = 8, 65536
+MAX_INFLUENCES, MAX_BONES, MAX_TARGETS = 8, 65536, 65536
 IDENTITY = None                                                             # an instance transform: None, or float32[12] (3x4 row major)
 
 
@@ -42,6 +67,7 @@ class Model:
         self.verts = np.array(verts, VERTEX, copy=True).reshape(-1)
         self.idx = np.array(idx, np.uint32, copy=True).reshape(-1, 3)
         self.skin = None                # or dict(rest=VERTEX[V], bones=uint32[V, K], weights=float32[V, K], n_bones=int)
+        self.morph = None               # or dict(base=VERTEX[V], offsets=uint32[T + 1], indices=uint32[E], dpos=float32[E, 3], dnrm=float32[E, 3] or None)
         self.scenes = []                # the scenes that hold the model
 
     # ---- the four vertex setters: rules 4, 6, 7, 15
@@ -101,8 +127,90 @@ class Model:
         self._changed()
         return OK
 
+    def set_bones_from(self, skeleton):                    # rule 27
+        if skeleton.palette is None or self.skin is None or self.skin["n_bones"] != len(skeleton.parents):
+            return ERR_STATE
+        return self.set_bones(skeleton.palette)
+
+    # ---- morph targets: rules 17 - 24
+    def set_morph_targets(self, offsets, indices, dpos, dnrm=None):
+        off = np.asarray(offsets, np.int64).reshape(-1)
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        if len(off) - 1 > MAX_TARGETS or off[0] != 0 or (np.diff(off) < 0).any() or (idx[:off[-1]] >= len(self.verts)).any():
+            return ERR_INVALID_ARG                             # rule 18
+        for t in range(len(off) - 1):
+            if (np.diff(idx[off[t]:off[t + 1]]) <= 0).any():
+                return ERR_INVALID_ARG
+        base = self.verts if self.skin is None else self.skin["rest"]
+        self.morph = dict(base=base.copy(), offsets=off.astype(np.uint32), indices=idx.astype(np.uint32), dpos=np.array(dpos, np.float32).reshape(-1, 3),
+                          dnrm=None if dnrm is None else np.array(dnrm, np.float32).reshape(-1, 3))
+        return OK
+
+    def clear_morph_targets(self):                         # rule 19
+        self.morph = None
+        return OK
+
+    def set_morph_weights(self, weights):
+        if self.morph is None:
+            return ERR_STATE                                   # rule 20
+        mo = self.morph
+        out = morphed(mo["base"], mo["offsets"], mo["indices"], mo["dpos"], mo["dnrm"], weights)
+        if self.skin is not None:
+            self.skin["rest"] = out                            # rule 22: nothing a scene reads has changed
+            return OK
+        self.verts[:] = out                                    # rule 21
+        self._changed()
+        return OK
+
     def geometry(self):                 # rule 16
         return self.verts
+
+    def skin_query(self):
+        """(influences, bones) as rt_model_get_skin answers"""
+        return (0, 0) if self.skin is None else (self.skin["bones"].shape[1], self.skin["n_bones"])
+
+    def morph_query(self):
+        """(targets, entries, has normal deltas) as rt_model_get_morph_targets answers"""
+        mo = self.morph
+        return (0, 0, False) if mo is None else (len(mo["offsets"]) - 1, int(mo["offsets"][-1]), mo["dnrm"] is not None)
+
+
+class Skeleton:                         # rules 25, 26
+    def __init__(self, parents, inverse_bind):
+        self.parents = np.array(parents, np.int32, copy=True).reshape(-1)
+        self.inverse_bind = np.array(inverse_bind, np.float32, copy=True).reshape(-1, 12)
+        self.pose = self.joints = self.palette = None       # float32[n, 10], [n, 12], [n, 12] once posed
+        self.clips = []                                     # [(times float32[K], keys float32[K, n, 10])]; the id is the place
+
+    def set_pose(self, trs):
+        self.pose = np.array(trs, np.float32, copy=True).reshape(len(self.parents), 10)
+        self.joints, self.palette = posed(self.parents, self.inverse_bind, self.pose)
+        return OK
+
+    def add_clip(self, times, keys):
+        times = np.asarray(times, np.float32).reshape(-1)
+        if len(times) == 0 or not np.isfinite(times).all() or (np.diff(times) <= 0).any():
+            return ERR_INVALID_ARG
+        self.clips.append((times.copy(), np.array(keys, np.float32, copy=True).reshape(len(times), len(self.parents), 10)))
+        return OK
+
+    def clear_clips(self):
+        self.clips = []
+        return OK
+
+    def set_time(self, clip, t):
+        if np.isnan(np.float32(t)):
+            return ERR_INVALID_ARG
+        if not 0 <= clip < len(self.clips):
+            return ERR_STATE
+        return self.set_pose(sampled(self.clips[clip][0], self.clips[clip][1], t))
+
+    def snapshot(self):
+        return (self.parents.tobytes(), self.inverse_bind.tobytes(), [(t.tobytes(), k.tobytes()) for t, k in self.clips], self.readers())
+
+    def readers(self):
+        """what read_pose, read_joints and read_palette return, NaNs canonical; None before the first pose"""
+        return None if self.pose is None else tuple(canonical_nans(a).tobytes() for a in (self.pose, self.joints, self.palette))
 
 
 class Scene:
@@ -208,11 +316,15 @@ class World:
     """models and scenes, and a version that moves with every change of state: two equal versions are the same state"""
 
     def __init__(self):
-        self.models, self.scenes = [], []
+        self.models, self.scenes, self.skeletons = [], [], []
 
     def add_model(self, verts, idx):
         self.models.append(Model(verts, idx))
         return len(self.models) - 1
+
+    def add_skeleton(self, parents, inverse_bind):
+        self.skeletons.append(Skeleton(parents, inverse_bind))
+        return len(self.skeletons) - 1
 
     def add_scene(self):
         self.scenes.append(Scene(self.models))
@@ -220,7 +332,15 @@ class World:
 
     def snapshot(self):
         """everything a refusal must leave as it was (rule 10), comparable with =="""
-        return ([(m.verts.tobytes(), None if m.skin is None else (m.skin["rest"].tobytes(), m.skin["bones"].tobytes(), m.skin["weights"].tobytes(), m.skin["n_bones"]))
-                 for m in self.models],
+        def morph(mo):
+            return None if mo is None else (mo["base"].tobytes(), mo["offsets"].tobytes(), mo["indices"].tobytes(), mo["dpos"].tobytes(), None if mo["dnrm"] is None else mo["dnrm"].tobytes())
+        return ([(m.verts.tobytes(), None if m.skin is None else (m.skin["rest"].tobytes(), m.skin["bones"].tobytes(), m.skin["weights"].tobytes(), m.skin["n_bones"]), morph(m.morph))
+                 for m in self.models], [k.snapshot() for k in self.skeletons],
                 [([(mi, None if x is None else np.asarray(x, np.float32).tobytes()) for mi, x in s.inst], list(s.masks), s.state, sorted(s.pending_xforms),
                   s.pending_masks, len(s.pending_models)) for s in self.scenes])
+
+    def readers(self):
+        """what the library's readers can return of the state -- geometry(), the skin and morph queries, masks(), whether a scene is readable,
+        a posed skeleton's arrays -- and nothing of the hidden arrays: the rest pose and the morph base"""
+        return ([(m.verts.tobytes(), m.skin_query(), m.morph_query()) for m in self.models], [k.readers() for k in self.skeletons],
+                [(list(s.masks), s.state) for s in self.scenes])

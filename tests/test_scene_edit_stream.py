@@ -14,6 +14,16 @@ from test_gpu_scene_edit_sweep import SEEDS, SEQUENCES
 OK, INVALID, STATE = M.OK, M.ERR_INVALID_ARG, M.ERR_STATE
 X = np.arange(12, dtype=np.float32)
 Y = X + 100
+# what the sweep required before morph targets and skeletons joined it: all of it stays required
+OLD_KINDS = {"set_transform", "set_transforms", "set_mask", "set_masks", "add_model", "build", "update", "probe", "set_vertices", "set_positions",
+             "recompute_normals", "set_skin", "clear_skin", "set_bones"}
+OLD_REFUSABLE = ("set_transform", "set_transforms", "set_mask", "set_masks", "set_vertices", "set_positions", "set_skin", "set_bones", "update", "build")
+OLD_EVENTS = ({("ok", k) for k in OLD_KINDS if k != "probe"} | {("refused", k) for k in OLD_REFUSABLE} | {("update applies", sub) for sub in sweep.SUBSETS}
+              | {"no-op update", "all hidden refused with transforms and vertices pending, then applied", "hidden and shown again with no update in between",
+                 "one instance set twice before one update", "an instance pending and of a changed model", "shared model: scene 0 updated before scene 1",
+                 "shared model: scene 1 updated before scene 0", "shared model: one scene back by build, the other by update", "the visible count goes to 1",
+                 "the visible count comes back from 1", "a single identity instance transformed", "a single instance back to the identity",
+                 "a setter between add_model and build", "set_vertices after set_skin, then set_bones", "split references come and go"})
 
 
 class ModelBackend:
@@ -82,7 +92,7 @@ def test_what_the_gpu_seeds_cover():
             plan = sweep.plan_sequence(seed, it)
             assert 2 <= len(plan.kinds) <= 3 and 1 <= len(plan.initial) <= 2 and len(plan.initial[0]) in sweep.COUNTS
             per_seed |= sweep.events_of(plan)
-        predicted.append("split references come and go" in per_seed)
+        predicted.append(sweep.per_seed_events() <= per_seed)
         events |= per_seed
         assert sweep.run(SEQUENCES, seed, None, tally=tally, backend=ModelBackend) is None
     missing = sweep.required_events() - events
@@ -97,9 +107,307 @@ def test_what_the_gpu_seeds_cover():
     plans = [sweep.plan_sequence(seed, it) for seed in SEEDS for it in range(SEQUENCES)]
     assert any(p.options for p in plans) and not all(p.options for p in plans)
     assert any(p.shared for p in plans) and {k for p in plans for k in p.kinds} == set(sweep.KINDS)
+    assert {p.normals for p in plans} == {True, False} and {p.n_joints for p in plans} == {sweep.N_BONES, sweep.WIDE_BONES}
+    assert any(p.shared and p.kinds[0] == "character" for p in plans)       # the model that two scenes hold is, somewhere, the character
+    assert sweep.required_events() >= OLD_EVENTS and set(sweep.ALL_KINDS) >= OLD_KINDS      # the list only grows
+
+
+# ---- mutants: a library with one rule of the morph targets and skeletons wrong ---------------------------------------------------------------
+class Readers(ModelBackend):
+    """a stand-in that is compared as the library is: through its return codes and, at a checkpoint, through what the readers return of the
+    models, the skeletons and the checkpoint's own scene.  The rest pose and the morph base are seen by nobody."""
+
+    def checkpoint(self, n, op, world):
+        mine, theirs = self.world.readers(), world.readers()
+        assert mine[:2] == theirs[:2] and mine[2][op["s"]] == theirs[2][op["s"]], "the readers differ"
+
+    def model(self, op):
+        return self.world.models[op["m"]]
+
+
+class RecapturesBase(Readers):
+    """(a) set_skin recaptures the morph base"""
+
+    def do(self, op):
+        code = super().do(op)
+        if op["op"] == "set_skin" and code == OK and self.model(op).morph is not None:
+            self.model(op).morph["base"] = self.model(op).verts.copy()
+        return code
+
+
+class RestMorphMarksStale(Readers):
+    """(b) a rest-pose morph marks the scenes stale"""
+
+    def do(self, op):
+        code = super().do(op)
+        if op["op"] == "set_morph_weights" and code == OK and self.model(op).skin is not None:
+            self.model(op)._changed()
+        return code
+
+
+class RestMorphWritesVertices(Readers):
+    """(c) a rest-pose morph also writes the current vertices"""
+
+    def do(self, op):
+        code = super().do(op)
+        if op["op"] == "set_morph_weights" and code == OK and self.model(op).skin is not None:
+            self.model(op).verts[:] = self.model(op).skin["rest"]
+        return code
+
+
+class Accumulates(Readers):
+    """(d) set_morph_weights works on the previous result instead of the base"""
+
+    def do(self, op):
+        code = super().do(op)
+        if op["op"] == "set_morph_weights" and code == OK:
+            m = self.model(op)
+            m.morph["base"] = (m.verts if m.skin is None else m.skin["rest"]).copy()
+        return code
+
+
+class LatePalette(Readers):
+    """(e) set_bones_from reads the palette when the scene is updated, not when it is called"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.late = {}
+
+    def do(self, op):
+        if op["op"] in ("update", "build"):
+            for m, k in list(self.late.items()):
+                mo, sk = self.world.models[m], self.world.skeletons[k]
+                if id(mo) in self.world.scenes[op["s"]].pending_models:
+                    if sk.palette is not None and mo.skin is not None and mo.skin["n_bones"] == len(sk.parents):
+                        mo.verts[:] = skin_cases.skinned(mo.skin["rest"], mo.skin["bones"], mo.skin["weights"], sk.palette)
+                    del self.late[m]
+        code = super().do(op)
+        if op["op"] == "set_bones_from" and code == OK:
+            self.late[op["m"]] = op["k"]
+        return code
+
+
+class RefusalDropsTargets(Readers):
+    """(f) a refused set_morph_targets drops the old targets"""
+
+    def do(self, op):
+        code = super().do(op)
+        if op["op"] == "set_morph_targets" and code != OK:
+            self.model(op).morph = None
+        return code
+
+
+class ClearSkinKeepsTheRedirection(Readers):
+    """(g) after clear_skin, morph results still go to the old rest pose: nowhere that anything reads"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.ghost = set()
+
+    def do(self, op):
+        if op["op"] == "set_morph_weights" and op["m"] in self.ghost and self.model(op).morph is not None:
+            return OK
+        code = super().do(op)
+        if op["op"] == "clear_skin" and code == OK:
+            self.ghost.add(op["m"])
+        if op["op"] == "set_skin" and code == OK:
+            self.ghost.discard(op["m"])
+        return code
+
+
+# where each mutant may show: a return code of the call itself or of a probe, or the readers at a checkpoint.  (a), (c), (d) and (g) change
+# only arrays that no reader returns.  With Planner.epilogue stubbed out every one of the seven is still reported for every seed, so none
+# is caught ONLY because of the epilogue -- but three reports come later: (a) and (g) pass the whole of seed 5's sequence 0 and (d) the
+# whole of seed 329's, where it is the epilogue's set_morph_weights / set_bones and the update behind them that show the drifted base; a later
+# sequence's motif (morph_then_skin, clear_skin_redirects) reports them then.  (c) and the others are reported at the same operation either way.
+MUTANTS = [(RecapturesBase, ("update", "build")), (RestMorphMarksStale, ("probe",)), (RestMorphWritesVertices, ("update", "build")),
+           (Accumulates, ("update", "build")), (LatePalette, ("update", "build")), (RefusalDropsTargets, ("set_morph_weights", "update", "build")),
+           (ClearSkinKeepsTheRedirection, ("probe", "update", "build"))]
+
+
+def test_every_mutant_of_the_new_rules_is_reported():
+    for mutant, where in MUTANTS:
+        for seed in SEEDS:
+            bad = sweep.run(SEQUENCES, seed, None, backend=mutant)
+            assert bad and bad.startswith("MISMATCH seed %d sequence" % seed), (mutant.__doc__, seed)
+            last = bad.splitlines()[-1]
+            assert last.split(":", 1)[1].split()[0] in where, (mutant.__doc__, seed, last)
+    for seed in SEEDS:                                     # the stand-in with every rule right is not
+        assert sweep.run(SEQUENCES, seed, None, backend=Readers) is None
 
 
 # ---- the shadow model, rule by rule -------------------------------------------------------------------------------------------------------------
+def one_target(m, entries, normals=None):
+    """one target over the model: entries [(vertex, (dx, dy, dz))]"""
+    return m.set_morph_targets([0, len(entries)], [v for v, _ in entries], np.array([d for _, d in entries], np.float32), normals)
+
+
+def moved(verts, **by):
+    """a copy of verts with float32 additions applied: moved(v, x=2.0) or moved(v, v2=(1, 0, 0))"""
+    out = verts.copy()
+    for key, d in by.items():
+        if key in "xyz":
+            out["position"][:, "xyz".index(key)] += np.float32(d)
+        else:
+            out["position"][int(key[1:])] += np.asarray(d, np.float32)
+    return out
+
+
+def shift_x(n_bones=1, by=2.0):
+    p = skin_cases.identity_palette(n_bones)
+    p[:, 3] = by
+    return p
+
+
+def test_morph_weights_without_a_skin_write_the_vertices_from_the_base():
+    w = world(side=4)
+    s, m = w.scenes[0], w.models[0]
+    s.build()
+    base = m.verts.copy()
+    assert m.set_morph_weights([1.0]) == STATE and m.morph_query() == (0, 0, False)                 # rule 20
+    assert one_target(m, [(2, (1, 0, 0)), (5, (0, 2, 0))]) == OK and m.morph_query() == (1, 2, False)
+    assert s.state == M.FRESH and m.geometry().tobytes() == base.tobytes()                          # rule 17
+    assert m.set_morph_weights([0.5]) == OK and s.state == M.STALE                                  # rule 21
+    assert m.geometry().tobytes() == moved(base, v2=(0.5, 0, 0), v5=(0, 1, 0)).tobytes()
+    assert s.update() == (OK, frozenset(["vertices"]))
+    assert m.set_morph_weights([2.0]) == OK                                                         # from the base, not from the last result
+    assert m.geometry().tobytes() == moved(base, v2=(2, 0, 0), v5=(0, 4, 0)).tobytes()
+    assert m.set_positions(7, [[9, 9, 9]]) == OK and m.recompute_normals() == OK                    # rule 24: the current vertices, not the base
+    assert m.set_morph_weights([1.0]) == OK                                                         # the whole mesh: vertex 7 and the normals too
+    assert m.geometry().tobytes() == moved(base, v2=(1, 0, 0), v5=(0, 2, 0)).tobytes()
+    s.update()
+    last = m.geometry().copy()
+    assert m.clear_morph_targets() == OK and s.state == M.FRESH and m.geometry().tobytes() == last.tobytes()        # rule 19
+    assert m.set_morph_weights([1.0]) == STATE
+
+
+def test_with_a_skin_the_weights_write_the_rest_pose_and_no_scene_goes_stale():
+    w = world(side=4)
+    s, m = w.scenes[0], w.models[0]
+    s.build()
+    R = m.verts.copy()
+    m.set_skin(np.zeros((16, 1), np.uint32), np.ones((16, 1), np.float32), 1)
+    assert one_target(m, [(2, (1, 0, 0))]) == OK                                                    # rule 17: the base is the rest pose, R
+    assert m.set_morph_weights([1.0]) == OK and s.state == M.FRESH and s.readable()                 # rule 22
+    assert m.geometry().tobytes() == R.tobytes() and m.skin["rest"].tobytes() == moved(R, v2=(1, 0, 0)).tobytes()
+    assert m.set_bones(shift_x()) == OK and s.state == M.STALE
+    P = moved(moved(R, v2=(1, 0, 0)), x=2.0)
+    assert m.geometry().tobytes() == P.tobytes()                                                    # the pose of the morphed rest pose
+    s.update()
+    m.set_skin(np.zeros((16, 1), np.uint32), np.ones((16, 1), np.float32), 1)                        # rule 23: the rest pose is P now, the base still R
+    assert m.skin["rest"].tobytes() == P.tobytes() and m.morph["base"].tobytes() == R.tobytes()
+    assert m.set_morph_weights([0.0]) == OK and m.skin["rest"].tobytes() == R.tobytes() and s.state == M.FRESH
+    m.set_bones(shift_x())
+    assert m.geometry().tobytes() == moved(R, x=2.0).tobytes()
+    s.update()
+    assert m.clear_skin() == OK and m.set_morph_weights([3.0]) == OK and s.state == M.STALE         # rule 23: to the vertices again, from R
+    assert m.geometry().tobytes() == moved(R, v2=(3, 0, 0)).tobytes()
+
+
+def test_targets_before_the_skin_keep_the_base_they_captured():
+    w = world(side=4)
+    s, m = w.scenes[0], w.models[0]
+    s.build()
+    A = m.verts.copy()
+    one_target(m, [(3, (0, 0, 1))])                                                                 # the base is A
+    assert m.set_positions(0, [[5, 5, 5]]) == OK
+    C = m.verts.copy()
+    m.set_skin(np.zeros((16, 1), np.uint32), np.ones((16, 1), np.float32), 1)                        # the rest pose is C
+    s.update()
+    assert m.skin["rest"].tobytes() == C.tobytes() and m.morph["base"].tobytes() == A.tobytes()      # rule 23
+    assert m.set_morph_weights([1.0]) == OK and s.state == M.FRESH and m.geometry().tobytes() == C.tobytes()
+    m.set_bones(shift_x(by=-1.0))
+    assert m.geometry().tobytes() == moved(moved(A, v3=(0, 0, 1)), x=-1.0).tobytes()                # vertex 0 is A's again: the rest pose was overwritten whole
+    one_target(m, [(3, (0, 0, 1))])                                                                 # set again: the base is the rest pose as the weights left it
+    assert m.set_morph_weights([1.0]) == OK and m.skin["rest"].tobytes() == moved(moved(A, v3=(0, 0, 1)), v3=(0, 0, 1)).tobytes()
+
+
+def test_targets_that_are_refused_leave_the_old_ones():
+    w = world(side=4)
+    s, m = w.scenes[0], w.models[0]
+    s.build()
+    assert one_target(m, [(2, (1, 0, 0)), (5, (0, 2, 0))], np.ones((2, 3), np.float32)) == OK and m.morph_query() == (1, 2, True)
+    m.set_positions(1, [[7, 7, 7]])
+    before = w.snapshot()
+    d = np.zeros((4, 3), np.float32)
+    for off, idx in (([1, 4], [0, 1, 2, 3]), ([0, 3, 2, 4], [0, 1, 2, 3]), ([0, 2, 4], [0, 1, 2, 16]), ([0, 2, 4], [0, 1, 3, 3]), ([0, 2, 4], [0, 1, 3, 2])):
+        assert m.set_morph_targets(off, idx, d) == INVALID and w.snapshot() == before, (off, idx)    # rules 18, 10
+    assert m.set_morph_targets(np.zeros(65538, np.uint32), [], d[:0]) == INVALID and w.snapshot() == before
+    assert m.set_morph_targets(np.zeros(65537, np.uint32), [], d[:0]) == OK and m.morph_query() == (65536, 0, False)
+    assert m.morph["base"][1]["position"].tolist() == [7, 7, 7]                                      # replaced: the base is captured anew
+
+
+def two_joints():
+    sk = M.Skeleton([-1, 0], skin_cases.identity_palette(2))
+    trs = np.zeros((2, 10), np.float32)
+    trs[:, 6] = 1                                           # q = (0, 0, 0, 1)
+    trs[:, 7:10] = 1
+    trs[0, 0], trs[1, 1] = 1, 2                             # the root one along x, its child two along y
+    return sk, trs
+
+
+def translation(x, y, z):
+    return [1, 0, 0, x, 0, 1, 0, y, 0, 0, 1, z]
+
+
+def test_a_skeleton_poses_samples_and_refuses():
+    w = world(side=4)
+    s, m = w.scenes[0], w.models[0]
+    s.build()
+    sk, trs = two_joints()
+    w.skeletons.append(sk)
+    before = w.snapshot()
+    assert sk.set_time(0, 0.0) == STATE and w.snapshot() == before                                  # rule 26: no clip yet
+    assert sk.readers() is None
+    assert sk.set_pose(trs) == OK and s.state == M.FRESH and m.geometry().tobytes() == before[0][0][0]       # rule 25
+    assert sk.joints.tolist() == [translation(1, 0, 0), translation(1, 2, 0)] and sk.palette.tolist() == sk.joints.tolist()
+    far = trs.copy()
+    far[0, 0] = 3
+    keys = np.stack([trs, far])
+    before = w.snapshot()
+    for times in ([0, np.nan], [0, np.inf], [-np.inf, 0], [1, 1], [1, 0], []):
+        assert sk.add_clip(np.array(times, np.float32), keys[:len(times)]) == INVALID and w.snapshot() == before
+    assert sk.add_clip([0, 1], keys) == OK and len(sk.clips) == 1 and s.state == M.FRESH
+    before = w.snapshot()
+    assert sk.set_time(0, np.nan) == INVALID and sk.set_time(1, 0.5) == STATE and w.snapshot() == before
+    assert sk.set_time(0, 0.5) == OK and sk.joints.tolist() == [translation(2, 0, 0), translation(2, 2, 0)] and sk.pose[0, 0] == 2
+    assert sk.set_time(0, -3.0) == OK and sk.joints[0].tolist() == translation(1, 0, 0)              # before the first key
+    assert sk.set_time(0, 1.0) == OK and sk.joints[1].tolist() == translation(3, 2, 0)               # on the last key
+    assert sk.set_time(0, np.inf) == OK and sk.joints[1].tolist() == translation(3, 2, 0)
+    assert sk.clear_clips() == OK and sk.pose[0, 0] == 3 and sk.set_time(0, 0.0) == STATE            # the pose stays; no clip 0 any more
+    assert sk.add_clip([5], keys[:1]) == OK and sk.set_time(0, 99.0) == OK and sk.pose[0, 0] == 1    # ids start at 0 again; one key: that key
+    assert s.state == M.FRESH and m.geometry().tobytes() == before[0][0][0]
+
+
+def test_set_bones_from_takes_the_palette_as_it_is_at_the_call():
+    w = world(side=4)
+    s, m = w.scenes[0], w.models[0]
+    s.build()
+    R = m.verts.copy()
+    sk, trs = two_joints()
+    w.skeletons.append(sk)
+    bones = np.zeros((16, 1), np.uint32)
+    bones[8:] = 1
+    before = w.snapshot()
+    assert m.set_bones_from(sk) == STATE                                                            # rule 27: no pose, and no skin either
+    sk.set_pose(trs)
+    assert m.set_bones_from(sk) == STATE                                                            # no skin
+    m.set_skin(np.zeros((16, 1), np.uint32), np.ones((16, 1), np.float32), 3)
+    assert m.set_bones_from(sk) == STATE and s.state == M.FRESH and m.geometry().tobytes() == R.tobytes()      # three bones, two joints
+    m.set_skin(bones, np.ones((16, 1), np.float32), 2)
+    fresh = M.Skeleton([-1, 0], skin_cases.identity_palette(2))
+    assert m.set_bones_from(fresh) == STATE                                                         # before that skeleton's first pose
+    assert m.set_bones_from(sk) == OK and s.state == M.STALE
+    want = R.copy()
+    want["position"][:, 0] += np.float32(1)                 # both joints stand one along x,
+    want["position"][8:, 1] += np.float32(2)                # the child two along y
+    assert m.geometry().tobytes() == want.tobytes()
+    trs[0, 0] = 50
+    assert sk.set_pose(trs) == OK and m.geometry().tobytes() == want.tobytes()                      # a later pose reaches no vertex
+    assert s.update() == (OK, frozenset(["vertices"])) and m.geometry().tobytes() == want.tobytes()
+
+
+# (rules 1 - 16)
 def test_setters_before_the_first_build_only_store():
     w = world()
     s = w.scenes[0]
