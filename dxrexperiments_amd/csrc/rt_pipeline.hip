@@ -201,12 +201,12 @@ __global__ void __launch_bounds__(CBLOCK) k_compact_level(PipeDev pd, int L)
 // closest-hit shading of the compacted hits of level L in emit mode: writes their shadow rays and the rays
 // of level L+1; slots a hit does not use are marked "not traced"
 // BATCH: the launch covers several frames; a hit takes the constants of the frame its pixel slot lies in
-// (LC >= 0: the level as a compile-time constant.  The batch kernels work on a per-thread copy of the arguments whose pfc
-// they replace; with a run-time level the copy's lv[] would be indexed dynamically and live in scratch memory.)
+// (LC >= 0: the level as a compile-time constant, from the time when the batch kernels replaced pfc in a per-thread copy of the arguments
+// and a run-time index into the copy's lv[] put it into scratch memory.  Since round 17 they copy the frame's constants alone -- fc,
+// rt_shade.h -- and the compiler makes the same code of it.)
 template <bool PRIMARY, bool BATCH, int LC>
-RT_DEV void shade_emit_body(const PipeDev &pd_arg, int level, uint32_t shadow_slots, uint32_t emit_next)
+RT_DEV void shade_emit_body(const PipeDev &pd, int level, uint32_t shadow_slots, uint32_t emit_next)
 {
-    PipeDev pd = pd_arg;
     const int L = PRIMARY ? 0 : (LC >= 0 ? LC : level);          // (depth 0 compiles to its own kernel: it alone samples indirect diffuse)
     __builtin_assume(PRIMARY || L >= 1);
     const uint32_t idx = blockIdx.x * PBLOCK + threadIdx.x;
@@ -214,9 +214,13 @@ RT_DEV void shade_emit_body(const PipeDev &pd_arg, int level, uint32_t shadow_sl
     const uint32_t slot = pd.lv[L].jlist[idx];
     const uint32_t q = L == 0 ? slot : pd.lv[L].pix[slot];
     uint32_t px, py, ql = q, frame = 0;
-    if (BATCH) { frame = slot_frame(pd, q, ql); pd.pfc = pd.pfcs[frame]; }
+    // (the hits of a wave come from several frames: a thread takes its frame's constants in one go, 188 B that arrive together --
+    //  read field by field where they are used they cost this memory-bound kernel 14 %)
+    rt_per_frame_constants own;
+    if (BATCH) { frame = slot_frame(pd, q, ql); own = pd.pfcs[frame]; }
+    const rt_per_frame_constants &fc = BATCH ? own : pd.pfc;
     (void)pix_xy(pd, ql, px, py);
-    const RayD r = L == 0 ? primary_ray(pd, px, py) : load_ray(pd.lv[L].O, pd.lv[L].D, slot);
+    const RayD r = L == 0 ? primary_ray(pd, fc.cameraParams, px, py) : load_ray(pd.lv[L].O, pd.lv[L].D, slot);
     const float4 h = pd.lv[L].hit[slot];
     if (!PRIMARY && !emit_next && pd.shadow_compact && !pd.skip_unlit) {
         // The LAST radiance level (round 4): its hits spawn nothing, so all the emit pass has to leave is where their two light
@@ -227,15 +231,15 @@ RT_DEV void shade_emit_body(const PipeDev &pd_arg, int level, uint32_t shadow_sl
         // hit: 3.7 M per 1080p frame, the emit kernel 0.065 -> 0.02 ms.)
         const f3 P = r.o + r.d * h.x;
         uint32_t mask = 3u;
-        if (pd.kind != RT_PIPELINE_REALTIME && pd.pfc.options.debug == 2) {
-            uint32_t seed = init_rand(px + py * pd.width, pd.pfc.cameraParams.frameCount);
+        if (pd.kind != RT_PIPELINE_REALTIME && fc.options.debug == 2) {
+            uint32_t seed = init_rand(px + py * pd.width, fc.cameraParams.frameCount);
             mask = next_rand(seed) < 0.5f ? 1u : 2u;
         }
         if ((uint32_t)L < pd.sh_levels) pd.sh_hits[pd.sh_cbase[L] + idx] = make_float4(P.x, P.y, P.z, __uint_as_float(mask | (frame << 8)));
         return;
     }
-    EmitIO io(pd, L, idx, q, frame);
-    (void)closest_hit(pd, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[L].inst[slot], (uint32_t)L, px + py * pd.width);
+    EmitIO io(pd, fc, L, idx, q, frame);
+    (void)closest_hit(pd, fc, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[L].inst[slot], (uint32_t)L, px + py * pd.width);
     io.finish_shadows(shadow_slots);
     if (emit_next) {
         if (L == 0) {
@@ -519,13 +523,13 @@ RT_DEV void add_totals(const uint32_t *__restrict__ counters, unsigned long long
 
 // what the frame's last kernel does with the colour of pixel slot q (RayGen's tail, ProgressiveRaytracing.hlsl:36-38 /
 // RealtimeRaytracing.hlsl:44-45)
-RT_DEV float4 accumulate(const PipeDev &pd, const float4 prev, const Shaded &sh)
+RT_DEV float4 accumulate(const PipeDev &pd, const rt_per_frame_constants &fc, const float4 prev, const Shaded &sh)
 {
     const f3 c = sh.color;
     const float4 cur = make_float4(fmax2(c.x, 0.0f), fmax2(c.y, 0.0f), fmax2(c.z, 0.0f), 1.0f);
     if (pd.accum_mode == RT_ACCUM_SUM) return make_float4(prev.x + cur.x, prev.y + cur.y, prev.z + cur.z, prev.w + cur.w);
-    const float n = (float)pd.pfc.cameraParams.accumCount;
-    const float n1 = (float)(pd.pfc.cameraParams.accumCount + 1u);
+    const float n = (float)fc.cameraParams.accumCount;
+    const float n1 = (float)(fc.cameraParams.accumCount + 1u);
     float4 m = make_float4((n * prev.x + cur.x) / n1, (n * prev.y + cur.y) / n1, (n * prev.z + cur.z) / n1, (n * prev.w + cur.w) / n1);
     // the reference's RGBA16F texture (src/DXRExperimentsApp.cpp:28): what the next frame reads back is this mean rounded to fp16
     if (pd.accum_f16 == 1u) m = make_float4(__half2float(__float2half_rn(m.x)), __half2float(__float2half_rn(m.y)), __half2float(__float2half_rn(m.z)), __half2float(__float2half_rn(m.w)));
@@ -540,10 +544,18 @@ RT_DEV void write_aovs(const PipeDev &pd, size_t pixel, const Shaded &sh)       
 
 // FLAT = false: one bounce at most, the secondary hits are shaded inline (ResolveIO<0, 1>); FLAT = true: their colours
 // come from k_shade_level (LevelResolveIO)
+// pfcs: the constants of the set's frames (PipeDev::pfcs once more, as an argument of its own: `const __restrict__` tells the compiler that no
+// store of this kernel reaches them, and with the frame the same for the whole wave every field of frame f is then fetched by a scalar load
+// where it is used.  Until round 17 each thread replaced pfc in a copy of the arguments: the frame's 47 dwords came by vector loads and
+// stayed in vector registers for as long as shade() needed them.)
+// Registers (round 17, profiles/r17/resolve_sets.txt): the set form of the one-bounce kernel took 116 VGPRs = four waves per SIMD against the
+// single-frame form's 88 = five.  Reading the constants in place leaves 101; the rest is what a pixel carries from frame to frame -- the
+// running value (4), its index (2), the parts of the primary ray that do not depend on the frame, its slot.  Capped at five waves (96) the
+// allocator then spills 12 B; with the pixel's index worked out again behind the loop it fits 96 with no scratch.  The other three forms
+// keep the occupancy they had (the cap is the number of waves they reached by themselves).
 template <bool FLAT, bool BATCH>
-__global__ void __launch_bounds__(PBLOCK) k_resolve(PipeDev pd_arg)
+__global__ void __launch_bounds__(PBLOCK) __attribute__((amdgpu_waves_per_eu(FLAT && !BATCH ? 6 : 5))) k_resolve(PipeDev pd, const rt_per_frame_constants *__restrict__ pfcs)
 {
-    PipeDev pd = pd_arg;
     const uint32_t ql = blockIdx.x * PBLOCK + threadIdx.x;
     if (ql == 0) add_totals(pd.counters, pd.totals, pd.n_pixels, pd.n_frames);      // every counter of the frame is final when this kernel starts
     if (ql >= pd.fcap) return;
@@ -551,52 +563,61 @@ __global__ void __launch_bounds__(PBLOCK) k_resolve(PipeDev pd_arg)
     if (!pix_xy(pd, ql, px, py)) return;
     // a batch: the frames of a pixel one after the other, in frame order, so that the running mean is the one S single
     // frames would have left (each frame with its own accumCount)
-    // (one bounce: the pixel's running value stays in registers from the first frame of the set to the last, resolve -4 %; the
-    //  level-by-level form would pay for the four registers with its fifth wave: profiles/r03/resolve_registers.txt)
+    // (one bounce: the pixel's running value stays in registers from the first frame of the set to the last, resolve -4 %:
+    //  profiles/r03/resolve_registers.txt; the level-by-level form reads and writes it frame by frame)
     const size_t pixel = (size_t)py * pd.width + px;
     const bool progressive = pd.kind != RT_PIPELINE_REALTIME;
     constexpr bool KEEP = BATCH && !FLAT;
     float4 acc = KEEP && progressive ? pd.accum[pixel] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    // (KEEP: the two registers of `pixel` are not carried through the frames -- the store behind them works the index out again from the
+    //  thread's slot, through a register the optimiser cannot see through, or it would keep the first computation alive)
+    auto pixel_again = [&]() -> size_t {
+        uint32_t slot = blockIdx.x * PBLOCK + threadIdx.x, x, y;
+        asm volatile("" : "+v"(slot));
+        (void)pix_xy(pd, slot, x, y);
+        return (size_t)y * pd.width + x;
+    };
     for (uint32_t f = 0; f < (BATCH ? pd.n_frames : 1u); f++) {
-        if (BATCH) pd.pfc = pd.pfcs[f];
+        const rt_per_frame_constants &fc = BATCH ? pfcs[f] : pd.pfc;
         const uint32_t q = frame_slot(pd, f, ql);
-        const RayD r = primary_ray(pd, px, py);
+        const RayD r = primary_ray(pd, fc.cameraParams, px, py);
         const float4 h = pd.lv[0].hit[q];
         Shaded sh;
         if (h.x == HIT_MISS) {
-            sh.color = sample_environment(pd, r.d);             // PrimaryMiss
+            sh.color = sample_environment(pd, fc, r.d);         // PrimaryMiss
             sh.aov_direct = sh.color;                           // RealtimeRaytracing.hlsl:119-126
             sh.aov_indirect = mk3(0.0f, 0.0f, 0.0f);
         } else if (FLAT) {
-            LevelResolveIO io(pd, 0, pd.lv[0].slot_j[q]);
-            sh = closest_hit_aov(pd, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[0].inst[q], 0u, px + py * pd.width);
+            LevelResolveIO io(pd, fc, 0, pd.lv[0].slot_j[q]);
+            sh = closest_hit_aov(pd, fc, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[0].inst[q], 0u, px + py * pd.width);
         } else {
-            ResolveIO<0, 1> io(pd, pd.lv[0].slot_j[q], px + py * pd.width);
-            sh = closest_hit_aov(pd, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[0].inst[q], 0u, px + py * pd.width);
+            ResolveIO<0, 1> io(pd, fc, pd.lv[0].slot_j[q], px + py * pd.width);
+            sh = closest_hit_aov(pd, fc, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[0].inst[q], 0u, px + py * pd.width);
         }
-        if (progressive) { acc = accumulate(pd, KEEP ? acc : pd.accum[pixel], sh); if (!KEEP) pd.accum[pixel] = acc; }
-        else write_aovs(pd, pixel, sh);
+        if (progressive) { acc = accumulate(pd, fc, KEEP ? acc : pd.accum[pixel], sh); if (!KEEP) pd.accum[pixel] = acc; }
+        else write_aovs(pd, KEEP ? pixel_again() : pixel, sh);
     }
-    if (KEEP && progressive) pd.accum[pixel] = acc;
+    if (KEEP && progressive) pd.accum[pixel_again()] = acc;
 }
 
 // deep paths: the colour of every hit of level L >= 1 (its shadow rays are traced, the hits of level L + 1 already shaded)
 template <bool BATCH, int LC>
-RT_DEV void shade_level_body(const PipeDev &pd_arg, int level)
+RT_DEV void shade_level_body(const PipeDev &pd, int level)
 {
-    PipeDev pd = pd_arg;
     const int L = LC >= 0 ? LC : level;
     const uint32_t idx = blockIdx.x * PBLOCK + threadIdx.x;
     if (idx >= pd.counters[C_NHIT + L]) return;
     const uint32_t slot = pd.lv[L].jlist[idx];
     const uint32_t q = pd.lv[L].pix[slot];
     uint32_t px, py, ql = q;
-    if (BATCH) pd.pfc = pd.pfcs[slot_frame(pd, q, ql)];
+    rt_per_frame_constants own;
+    if (BATCH) own = pd.pfcs[slot_frame(pd, q, ql)];
+    const rt_per_frame_constants &fc = BATCH ? own : pd.pfc;
     (void)pix_xy(pd, ql, px, py);
     const RayD r = load_ray(pd.lv[L].O, pd.lv[L].D, slot);
     const float4 h = pd.lv[L].hit[slot];
-    LevelResolveIO io(pd, L, idx);
-    const f3 c = closest_hit(pd, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[L].inst[slot], (uint32_t)L, px + py * pd.width);
+    LevelResolveIO io(pd, fc, L, idx);
+    const f3 c = closest_hit(pd, fc, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[L].inst[slot], (uint32_t)L, px + py * pd.width);
     pd.lv[L].color[slot] = make_float4(c.x, c.y, c.z, 0.0f);
 }
 template <bool BATCH>
@@ -758,10 +779,10 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
     }
     if (T) record(ev[EV_SHADOW], st);
     // (resolve: one thread per pixel slot of ONE frame; a batch's frames are accumulated in order inside the thread)
-    if (levels <= 1) k_resolve<false, BATCH><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);      // (level by level is slower here: 0.143 vs 0.118 ms at 1080p)
+    if (levels <= 1) k_resolve<false, BATCH><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd, pd.pfcs);      // (level by level is slower here: 0.143 vs 0.118 ms at 1080p)
     else {
         for (uint32_t l = levels; l >= 1; l--) k_shade_level<BATCH><<<blocks(pd.lv[l].hstride), PBLOCK, 0, st>>>(pd, (int)l);      // (one thread per hit of the level)
-        k_resolve<true, BATCH><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd);
+        k_resolve<true, BATCH><<<blocks(pd.fcap), PBLOCK, 0, st>>>(pd, pd.pfcs);
     }
     if (T) { record(ev[EV_RESOLVE], st); p->ring_levels[ring_slot] = (uint8_t)levels; p->ring_nframes[ring_slot] = (uint8_t)pd.n_frames; p->ring_pos++; }
     HIP_TRY(first_error);

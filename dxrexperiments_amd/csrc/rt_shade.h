@@ -84,9 +84,12 @@ RT_DEV f3 sample_cube(const PipeDev &pd, f3 d)
     return mk3(tx + (bx - tx) * wy, ty + (by - ty) * wy, tz + (bz - tz) * wy);
 }
 
-RT_DEV f3 sample_environment(const PipeDev &pd, f3 dir)
+// (fc: the constants of the frame that is being shaded -- PipeDev::pfc, or in a set of frames pfcs[frame].  Every shading function takes
+// them by reference next to the launch's arguments, so that no kernel has to copy the arguments to exchange their pfc: the resolve pass,
+// whose frame is the same for the whole wave, reads the fields in place by scalar loads; the per-hit passes hand in a copy of the 188 B)
+RT_DEV f3 sample_environment(const PipeDev &pd, const rt_per_frame_constants &fc, f3 dir)
 {
-    return sample_cube(pd, dir) * pd.pfc.options.environmentStrength;
+    return sample_cube(pd, dir) * fc.options.environmentStrength;
 }
 
 // Pixel slot q -> pixel.  Slots are laid out as 8x8 pixel tiles (64 consecutive slots = one
@@ -156,9 +159,9 @@ RT_DEV f3 hit_normal(const InstanceRec &in, uint32_t prim, float bu, float bv)
 
 // ---- lights (RaytracingCommon.hlsli:126-147), AO (:98-124)
 template <class IO>
-RT_DEV f3 directional_light(const PipeDev &pd, IO &io, f3 P, f3 N, uint32_t depth)
+RT_DEV f3 directional_light(const PipeDev &pd, const rt_per_frame_constants &fc, IO &io, f3 P, f3 N, uint32_t depth)
 {
-    const rt_directional_light_params &dl = pd.pfc.directionalLight;
+    const rt_directional_light_params &dl = fc.directionalLight;
     const f3 L = normalize(mk3(-dl.forwardDir.x, -dl.forwardDir.y, -dl.forwardDir.z));
     const float NoL = saturate(dot(N, L));
     // the reference traces this ray even when NoL == 0 (RaytracingCommon.hlsli:132-133); its visibility is then multiplied
@@ -168,9 +171,9 @@ RT_DEV f3 directional_light(const PipeDev &pd, IO &io, f3 P, f3 N, uint32_t dept
 }
 
 template <class IO>
-RT_DEV f3 point_light(const PipeDev &pd, IO &io, f3 P, f3 N, uint32_t depth)
+RT_DEV f3 point_light(const PipeDev &pd, const rt_per_frame_constants &fc, IO &io, f3 P, f3 N, uint32_t depth)
 {
-    const rt_point_light_params &pl = pd.pfc.pointLight;
+    const rt_point_light_params &pl = fc.pointLight;
     const f3 path = mk3(pl.worldPos.x, pl.worldPos.y, pl.worldPos.z) - P;
     const float dist = length(path);
     const f3 L = normalize(path);
@@ -181,13 +184,13 @@ RT_DEV f3 point_light(const PipeDev &pd, IO &io, f3 P, f3 N, uint32_t depth)
 }
 
 template <class IO>
-RT_DEV f3 ambient_occlusion(const PipeDev &pd, IO &io, f3 P, f3 N, uint32_t pix)
+RT_DEV f3 ambient_occlusion(const PipeDev &pd, const rt_per_frame_constants &fc, IO &io, f3 P, f3 N, uint32_t pix)
 {
     float visibility = 0.0f;
     uint32_t seed = io.pixel_seed(pix);      // initRand(pixel, frameCount): the shaders re-seed in every shade() call of the pixel
     for (int i = 0; i < 4; ++i) {
         f3 dir; float NoL, pdf;
-        if (pd.pfc.options.cosineHemisphereSampling) {
+        if (fc.options.cosineHemisphereSampling) {
             dir = cos_hemisphere(seed, N);
             NoL = saturate(dot(N, dir));
             pdf = NoL / HLSL_PI;
@@ -222,20 +225,20 @@ RT_DEV bool black_lobe(const IO &io, const rt_material_params &mp, uint32_t seed
 
 // ---- shade (ProgressiveRaytracing.hlsl:80-148) + evaluateIndirectDiffuse (:57-78)
 template <class IO>
-RT_DEV f3 shade(const PipeDev &pd, IO &io, const rt_material_params &mp, f3 P, f3 N, f3 D, uint32_t depth, uint32_t pix)
+RT_DEV f3 shade(const PipeDev &pd, const rt_per_frame_constants &fc, IO &io, const rt_material_params &mp, f3 P, f3 N, f3 D, uint32_t depth, uint32_t pix)
 {
-    const rt_debug_options &opt = pd.pfc.options;
-    if (opt.showAmbientOcclusionOnly) return ambient_occlusion(pd, io, P, N, pix);
+    const rt_debug_options &opt = fc.options;
+    if (opt.showAmbientOcclusionOnly) return ambient_occlusion(pd, fc, io, P, N, pix);
 
     uint32_t seed = io.pixel_seed(pix);      // initRand(pixel, frameCount): the shaders re-seed in every shade() call of the pixel
 
     f3 direct = mk3(0.0f, 0.0f, 0.0f);
     if (opt.debug == 2) {
-        if (next_rand(seed) < 0.5f) direct = direct + directional_light(pd, io, P, N, depth) * 2.0f;
-        else direct = direct + point_light(pd, io, P, N, depth) * 2.0f;
+        if (next_rand(seed) < 0.5f) direct = direct + directional_light(pd, fc, io, P, N, depth) * 2.0f;
+        else direct = direct + point_light(pd, fc, io, P, N, depth) * 2.0f;
     } else {
-        direct = direct + directional_light(pd, io, P, N, depth);
-        direct = direct + point_light(pd, io, P, N, depth);
+        direct = direct + directional_light(pd, fc, io, P, N, depth);
+        direct = direct + point_light(pd, fc, io, P, N, depth);
     }
 
     f3 indirect = mk3(0.0f, 0.0f, 0.0f);
@@ -291,13 +294,13 @@ RT_DEV f3 shade(const PipeDev &pd, IO &io, const rt_material_params &mp, f3 P, f
 // shadeAOV of the realtime pipeline (RealtimeRaytracing.hlsl:65-103): direct light + one Phong-lobe
 // bounce, split into the two AOVs the denoiser consumes (written at depth 0 only)
 template <class IO>
-RT_DEV f3 shade_aov(const PipeDev &pd, IO &io, const rt_material_params &mp, f3 P, f3 N, f3 D, uint32_t depth, uint32_t pix,
+RT_DEV f3 shade_aov(const PipeDev &pd, const rt_per_frame_constants &fc, IO &io, const rt_material_params &mp, f3 P, f3 N, f3 D, uint32_t depth, uint32_t pix,
                     f3 &aov_direct, f3 &aov_indirect)
 {
     uint32_t seed = io.pixel_seed(pix);      // initRand(pixel, frameCount): the shaders re-seed in every shade() call of the pixel
     f3 direct = mk3(0.0f, 0.0f, 0.0f);
-    direct = direct + directional_light(pd, io, P, N, depth);
-    direct = direct + point_light(pd, io, P, N, depth);
+    direct = direct + directional_light(pd, fc, io, P, N, depth);
+    direct = direct + point_light(pd, fc, io, P, N, depth);
     f3 fresnel = mk3(0.0f, 0.0f, 0.0f);
     f3 specular = mk3(0.0f, 0.0f, 0.0f);
     if (mp.type == 1u || mp.type == 2u) {
@@ -327,7 +330,7 @@ struct Shaded { f3 color, aov_direct, aov_indirect; };
 
 // PrimaryClosestHit (ProgressiveRaytracing.hlsl:150-158, RealtimeRaytracing.hlsl:105-117) for a stored hit
 template <class IO>
-RT_DEV Shaded closest_hit_aov(const PipeDev &pd, IO &io, const RayD &r, float t, float u, float v, uint32_t prim, uint32_t inst,
+RT_DEV Shaded closest_hit_aov(const PipeDev &pd, const rt_per_frame_constants &fc, IO &io, const RayD &r, float t, float u, float v, uint32_t prim, uint32_t inst,
                               uint32_t depth, uint32_t pix)
 {
     const InstanceRec &in = pd.sc.inst[inst];
@@ -337,16 +340,16 @@ RT_DEV Shaded closest_hit_aov(const PipeDev &pd, IO &io, const RayD &r, float t,
     Shaded s;
     s.aov_direct = mk3(0.0f, 0.0f, 0.0f);
     s.aov_indirect = mk3(0.0f, 0.0f, 0.0f);
-    if (pd.kind == RT_PIPELINE_REALTIME) s.color = shade_aov(pd, io, mp, P, N, r.d, depth, pix, s.aov_direct, s.aov_indirect);
-    else s.color = shade(pd, io, mp, P, N, r.d, depth, pix);
+    if (pd.kind == RT_PIPELINE_REALTIME) s.color = shade_aov(pd, fc, io, mp, P, N, r.d, depth, pix, s.aov_direct, s.aov_indirect);
+    else s.color = shade(pd, fc, io, mp, P, N, r.d, depth, pix);
     return s;
 }
 
 template <class IO>
-RT_DEV f3 closest_hit(const PipeDev &pd, IO &io, const RayD &r, float t, float u, float v, uint32_t prim, uint32_t inst,
+RT_DEV f3 closest_hit(const PipeDev &pd, const rt_per_frame_constants &fc, IO &io, const RayD &r, float t, float u, float v, uint32_t prim, uint32_t inst,
                       uint32_t depth, uint32_t pix)
 {
-    return closest_hit_aov(pd, io, r, t, u, v, prim, inst, depth, pix).color;
+    return closest_hit_aov(pd, fc, io, r, t, u, v, prim, inst, depth, pix).color;
 }
 
 RT_DEV void store_ray(float4 *O, float4 *D, size_t slot, f3 o, float tmin, f3 d, float tmax)
@@ -373,16 +376,17 @@ RT_DEV RayD load_ray(const float4 *O, const float4 *D, size_t slot)
 // emit pass at radiance depth L: shadow ray s -> shadow queue of level L, secondary ray -> ray queue of level L+1
 struct EmitIO {
     const PipeDev &pd;
+    const rt_per_frame_constants &fc;       // the constants of the hit's frame
     int L;
     uint32_t idx, q;            // compact hit index at level L, pixel slot
     uint32_t frame;             // frame of the batch the hit belongs to (single frames: 0)
     uint32_t shadow_mask, skip_mask, sec_mask;
     f3 shadow_origin;           // compact shadow queue: the hit point both light rays start from
-    RT_DEV EmitIO(const PipeDev &p, int level, uint32_t i, uint32_t qq, uint32_t f) : pd(p), L(level), idx(i), q(qq), frame(f), shadow_mask(0), skip_mask(0), sec_mask(0)
+    RT_DEV EmitIO(const PipeDev &p, const rt_per_frame_constants &c, int level, uint32_t i, uint32_t qq, uint32_t f) : pd(p), fc(c), L(level), idx(i), q(qq), frame(f), shadow_mask(0), skip_mask(0), sec_mask(0)
     {
         shadow_origin = mk3(0.0f, 0.0f, 0.0f);
     }
-    RT_DEV uint32_t pixel_seed(uint32_t pix) const { return init_rand(pix, pd.pfc.cameraParams.frameCount); }
+    RT_DEV uint32_t pixel_seed(uint32_t pix) const { return init_rand(pix, fc.cameraParams.frameCount); }
     RT_DEV bool secondary_is_black(uint32_t depth) const { return depth >= pd.max_rad || L >= MAXD; }      // secondary() below returns at once
     // matters = false: whatever this ray finds is multiplied by zero by the caller
     RT_DEV float shadow(int s, f3 o, f3 d, float tmin, float tmax, uint32_t depth, bool matters)
@@ -426,11 +430,12 @@ struct EmitIO {
 template <int L, int MAXL>
 struct ResolveIO {
     const PipeDev &pd;
+    const rt_per_frame_constants &fc;       // the constants of the pixel's frame
     uint32_t idx, pix;
     uint32_t seed0;             // initRand(pixel, frameCount): every shade() of the pixel starts from it, so the 16 rounds run once per
                                 //   pixel and not once per level of the inline recursion (-10 % of k_resolve's instructions)
-    RT_DEV ResolveIO(const PipeDev &p, uint32_t i, uint32_t px) : pd(p), idx(i), pix(px), seed0(init_rand(px, p.pfc.cameraParams.frameCount)) {}
-    RT_DEV ResolveIO(const PipeDev &p, uint32_t i, uint32_t px, uint32_t seed) : pd(p), idx(i), pix(px), seed0(seed) {}
+    RT_DEV ResolveIO(const PipeDev &p, const rt_per_frame_constants &c, uint32_t i, uint32_t px) : pd(p), fc(c), idx(i), pix(px), seed0(init_rand(px, c.cameraParams.frameCount)) {}
+    RT_DEV ResolveIO(const PipeDev &p, const rt_per_frame_constants &c, uint32_t i, uint32_t px, uint32_t seed) : pd(p), fc(c), idx(i), pix(px), seed0(seed) {}
     RT_DEV uint32_t pixel_seed(uint32_t) const { return seed0; }
     RT_DEV bool secondary_is_black(uint32_t depth) const { return L >= MAXL || depth >= pd.max_rad; }
     RT_DEV float shadow(int s, f3, f3, float, float, uint32_t depth, bool matters)
@@ -447,12 +452,12 @@ struct ResolveIO {
             if (depth >= pd.max_rad) return mk3(0.0f, 0.0f, 0.0f);
             const size_t slot = L == 0 ? (size_t)w * pd.lv[1].rstride + idx : idx;
             const float4 h = pd.lv[L + 1].hit[slot];
-            if (h.x == HIT_MISS) return sample_environment(pd, d);             // PrimaryMiss, :160-164
+            if (h.x == HIT_MISS) return sample_environment(pd, fc, d);             // PrimaryMiss, :160-164
             if (h.x == HIT_UNTRACED) return mk3(0.0f, 0.0f, 0.0f);
             RayD r;
             r.o = o; r.tmin = tmin; r.d = d; r.tmax = RAY_MAX_T;
-            ResolveIO<L + 1, MAXL> io(pd, pd.lv[L + 1].slot_j[slot], pix, seed0);
-            return closest_hit(pd, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[L + 1].inst[slot], depth + 1u, pix);
+            ResolveIO<L + 1, MAXL> io(pd, fc, pd.lv[L + 1].slot_j[slot], pix, seed0);
+            return closest_hit(pd, fc, io, r, h.x, h.y, h.z, __float_as_uint(h.w), pd.lv[L + 1].inst[slot], depth + 1u, pix);
         }
     }
 };
@@ -463,10 +468,11 @@ struct ResolveIO {
 // the recursion would have produced (same function, same inputs), so the image does not change by a bit.
 struct LevelResolveIO {
     const PipeDev &pd;
+    const rt_per_frame_constants &fc;       // the constants of the hit's frame
     int L;
     uint32_t idx;
-    RT_DEV LevelResolveIO(const PipeDev &p, int level, uint32_t i) : pd(p), L(level), idx(i) {}
-    RT_DEV uint32_t pixel_seed(uint32_t pix) const { return init_rand(pix, pd.pfc.cameraParams.frameCount); }
+    RT_DEV LevelResolveIO(const PipeDev &p, const rt_per_frame_constants &c, int level, uint32_t i) : pd(p), fc(c), L(level), idx(i) {}
+    RT_DEV uint32_t pixel_seed(uint32_t pix) const { return init_rand(pix, fc.cameraParams.frameCount); }
     RT_DEV bool secondary_is_black(uint32_t depth) const { return depth >= pd.max_rad || L >= MAXD; }
     RT_DEV float shadow(int s, f3, f3, float, float, uint32_t depth, bool matters)
     {
@@ -479,7 +485,7 @@ struct LevelResolveIO {
         if (depth >= pd.max_rad || L >= MAXD) return mk3(0.0f, 0.0f, 0.0f);
         const size_t slot = L == 0 ? (size_t)w * pd.lv[1].rstride + idx : idx;
         const float4 h = pd.lv[L + 1].hit[slot];
-        if (h.x == HIT_MISS) return sample_environment(pd, d);             // PrimaryMiss, :160-164
+        if (h.x == HIT_MISS) return sample_environment(pd, fc, d);             // PrimaryMiss, :160-164
         if (h.x == HIT_UNTRACED) return mk3(0.0f, 0.0f, 0.0f);
         const float4 c = pd.lv[L + 1].color[slot];
         return mk3(c.x, c.y, c.z);
