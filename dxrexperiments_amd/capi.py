@@ -183,6 +183,7 @@ SIGNATURES = {
     "rt_debug_set_alloc_limit": (_i, [_sz]),
     "rt_debug_set_option": (_i, [_p, C.c_char_p, C.c_char_p]),
     "rt_debug_read_secondary_ray": (_i, [_p, _u32, _p, _p]),
+    "rt_debug_read_primary_entries": (_i, [_p, _u32, _u32, _p, _p, _p]),
     "rt_camera_look": (_i, [_p, _p, _p, _p, _p]),
     "rt_camera_basis": (_i, [_p, _p, _f, _f, _p, _p, _p]),
     "rt_progressive_host_create": (_i, [_u32, _pp]),
@@ -950,6 +951,20 @@ class Pipeline:
         o = np.zeros(4, np.float32); d = np.zeros(4, np.float32)
         _check(lib().rt_debug_read_secondary_ray(self.h, int(index), _ptr(o), _ptr(d)))
         return o, d
+
+    def primary_entries(self, first_tile=0, count=None):
+        """The entry lists the last set of launches started its primary rays from (option primary_entries):
+        (codes int32[count, 33], tnear float32[count, 33], cut) for the tiles first_tile .. first_tile + count - 1 of the set's rectangle
+        (row-major; count=None: to the last tile); a list ends with the code 0x7FFFFFFE.  (None, None, 0) if the set ran without lists."""
+        n = C.c_uint32(0); cut = C.c_uint32(0)
+        _check(lib().rt_debug_read_primary_entries(self.h, 0, 0, None, C.byref(n), C.byref(cut)))
+        if n.value == 0:
+            return None, None, 0
+        if count is None:
+            count = n.value - first_tile
+        e = np.zeros((count, 33, 2), np.uint32)
+        _check(lib().rt_debug_read_primary_entries(self.h, int(first_tile), int(count), _ptr(e), None, None))
+        return e[:, :, 0].copy().view(np.int32), e[:, :, 1].copy().view(np.float32), int(cut.value)
 
     def count_walk(self):
         """What the PRODUCTION traversal fetched for the last frame per stage:

@@ -98,6 +98,25 @@ int rt_device_count(void)
 
 // ---- experiment / test knobs ------------------------------------------------------
 
+// The options of the primary stage's entry lists (rt_pipeline.hip, k_primary_entries).  Their tests are tests/test_gpu_primary_entries.py,
+// which runs every value of each against primary_entries=0 bit for bit.  1: the name is one of them (*rc: the result).
+static bool entry_list_option(rt_context *c, const std::string &name, bool is_int, long iv, int *rc)
+{
+    const bool which[3] = {name == "primary_entries", name == "primary_entries_cut", name == "primary_entries_cap"};
+    if (!which[0] && !which[1] && !which[2]) return false;
+    *rc = RT_ERR_INVALID_ARG;
+    if (!is_int) { rt_set_error("rt_debug_set_option: option '%s' takes a whole number", name.c_str()); return true; }
+    if ((which[0] && (iv < -1 || iv > 1)) || (which[1] && (iv < 0 || iv > 128)) || (which[2] && (iv < 0 || iv > 32))) {
+        rt_set_error("rt_debug_set_option: value %ld out of range for '%s'", iv, name.c_str());
+        return true;
+    }
+    if (which[0]) c->opt_primary_entries = (int)iv;
+    else if (which[1]) c->opt_primary_entries_cut = (uint32_t)iv;
+    else c->opt_primary_entries_cap = (uint32_t)iv;
+    *rc = RT_OK;
+    return true;
+}
+
 extern "C" int rt_debug_set_option(rt_context *c, const char *name, const char *value)
 {
     RT_REQUIRE(c && name && value, "null argument");
@@ -115,6 +134,8 @@ extern "C" int rt_debug_set_option(rt_context *c, const char *name, const char *
     const bool value_ok = n == "fast_bvh" || (wants_float ? is_num : is_int);
     bool known = false;
     auto is = [&](bool match) { known = known || match; return match && value_ok; };
+    int rc_entries = RT_OK;
+    if (entry_list_option(c, n, is_int, iv, &rc_entries)) return rc_entries;
     if (is(n == "lds_top")) c->lds_top = iv != 0;
     else if (is(n == "lds_stack_rows")) { if (iv != 0 && iv != RT_LDS_STACK_ROWS && iv != RT_LDS_STACK_ROWS_TEST) return bad(); c->lds_stack_rows = (uint32_t)iv; }
     else if (is(n == "persistent_blocks_per_cu")) { if (iv < 0 || iv > 16) return bad(); c->blocks_per_cu_override = (uint32_t)iv; }

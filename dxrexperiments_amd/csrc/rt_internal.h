@@ -279,6 +279,9 @@ struct rt_context {
     bool opt_split_refs = true;             // split_refs=0: no triangle is held as several references (the builder of rounds 1 - 4; the CANDIDATE RULE still
                                             //   follows rt_refs.h -- results do not depend on this option)
     uint32_t opt_primary_retry_cap = 0;     // primary_retry_cap: entries of the primary launch's retry list (0: 2^20; tests: a few, so that the list overflows)
+    int opt_primary_entries = -1;           // primary_entries: primary rays start from per-tile entry lists (-1: sets of 4 frames or more of single-level scenes with an LDS top whose primary launch is not persistent)
+    uint32_t opt_primary_entries_cut = 0;   // primary_entries_cut: the lists cut the tree below its first n nodes (0: RT_TOP_NODES)
+    uint32_t opt_primary_entries_cap = 0;   // primary_entries_cap: entries a list may hold before it falls back to a coarser cut (0: RT_ENTRY_CAP; tests: 1)
     size_t opt_queue_budget_mb = 0;         // queue_budget_mb: worst-case queue bytes a set may reserve up front (0: a quarter of the device)
     double opt_dist_check_seconds = 5.0;    // dist_check_seconds: how long rt_dist_create waits for the other ranks' device ids
     std::vector<struct rt_pipeline *> deferred;      // pipelines holding frames that render() has accepted and not rendered yet

@@ -86,6 +86,14 @@ struct ShadowCacheDev {
 
 #define RT_MAX_BATCH 32u                // frames one set of launches renders (rt_pipeline_render_batch)
 
+// The primary stage's entry lists (k_primary_entries, rt_pipeline.hip): per 8x8 tile of the launch's rectangle
+// RT_ENTRY_STRIDE entries of 8 B, (child code, bits of tnear), sorted by tnear and closed by (RT_NODE_EMPTY, +inf); at most
+// RT_ENTRY_CAP entries in front of the sentinel.  264 B per tile: 8.6 MB at 1080p, written once per set of launches.
+#define RT_ENTRY_CAP 32u
+#define RT_ENTRY_STRIDE (RT_ENTRY_CAP + 1u)
+#define RT_ENTRY_MIN_FRAMES 4u          // option primary_entries=-1: the sets that are long enough to pay for their lists
+#define RT_ENTRY_CUT_MAX 128u           // the deepest cut: the list kernel keeps the nodes above it in LDS (8 KiB), as the walks keep the top
+
 struct PipeDev {
     SceneDev sc;
     rt_per_frame_constants pfc;         // the frame's constants (a batch: of its first frame; kernels take pfcs[frame])
@@ -244,6 +252,14 @@ struct rt_pipeline {
         bool choose(const rt_context *ctx, const rt_scene *scene);      // the coming set's primary stage: true = persistent; a count that has landed is weighed first
         void sample(const rt_context *ctx, const uint32_t *d_count, uint32_t slots, hipStream_t st);      // behind the set: its retry count, of `slots` pixel slots, starts its way back
     } primary_mode;
+    // The primary stage's entry lists (k_primary_entries): whether the set at hand -- or, for the counting re-walks, the last one -- starts its
+    // primary rays from them, the cut through the tree and the entries a list may hold (options primary_entries, primary_entries_cut,
+    // primary_entries_cap), and the lists of the last set (RT_ENTRY_STRIDE entries per tile of its rectangle; never reused by a later set)
+    struct PrimaryEntries {
+        DevBuf lists;
+        bool on = false;
+        uint32_t cut = 0, cap = RT_ENTRY_CAP;
+    } primary_entries;
     uint64_t ring_pos = 0;             // frames recorded since enable / reset
     DevBuf totals, work;
     PipeDev last_pd;

@@ -280,10 +280,31 @@ void fill_pipe_dev(const rt_pipeline *p, PipeDev &pd, const SetPlan &plan, const
 }
 
 // how the primary stage of this set runs, and -- one tile per wave on a tree deeper than the LDS rows -- its retry list
-int choose_primary_stage(rt_pipeline *p, PipeDev &pd)
+int choose_primary_stage(rt_pipeline *p, PipeDev &pd, const rt_per_frame_constants *frames)
 {
     rt_context *ctx = p->ctx;
     pd.primary_persistent = p->primary_mode.choose(ctx, p->scene) ? 1u : 0u;
+    // entry lists (k_primary_entries): a tile's 64 directions must be the same in every frame of the set
+    rt_pipeline::PrimaryEntries &pe = p->primary_entries;
+    // (auto: sets of at least RT_ENTRY_MIN_FRAMES frames.  The list kernel takes about 0.1 ms at 1080p and a frame's walk gains 0.07 ms: a
+    // single frame with lists is 0.04 ms SLOWER than without, a set of 32 frames 2.2 ms faster: profiles/r18/primary_entries.txt)
+    pe.on = !p->scene->two_level && !pd.primary_persistent &&
+            (ctx->opt_primary_entries < 0 ? pd.sc.top_n != 0 && pd.n_frames >= RT_ENTRY_MIN_FRAMES : ctx->opt_primary_entries != 0);
+    for (uint32_t f = 1; pe.on && f < pd.n_frames; f++)
+        pe.on = memcmp(&frames[f].cameraParams.U, &frames[0].cameraParams.U, sizeof frames[0].cameraParams.U) == 0 &&
+                memcmp(&frames[f].cameraParams.V, &frames[0].cameraParams.V, sizeof frames[0].cameraParams.V) == 0 &&
+                memcmp(&frames[f].cameraParams.W, &frames[0].cameraParams.W, sizeof frames[0].cameraParams.W) == 0;
+    // (the walk's source divides chunk by frames and tile by tiles_x with 32-bit reciprocals: PrimaryEntrySrcT.  plan_set's limit of 2^30 slots
+    // bounds chunks x frames; tiles x tiles_x it bounds only for images up to 8192 tiles wide or so, hence the second test)
+    if ((uint64_t)(pd.cap >> 6) * pd.n_frames >= 0x100000000ull || (uint64_t)(pd.fcap >> 6) * pd.tiles_x >= 0x100000000ull) pe.on = false;
+    if (pe.on) {
+        const uint32_t n_nodes = p->scene->inst[0].model->blas.wide_n;
+        pe.cut = ctx->opt_primary_entries_cut ? ctx->opt_primary_entries_cut : (uint32_t)RT_TOP_NODES;
+        if (pe.cut > n_nodes) pe.cut = n_nodes;
+        if (pe.cut > RT_ENTRY_CUT_MAX) pe.cut = RT_ENTRY_CUT_MAX;
+        pe.cap = ctx->opt_primary_entries_cap ? ctx->opt_primary_entries_cap : RT_ENTRY_CAP;
+        RT_TRY(pe.lists.reserve((size_t)(pd.fcap >> 6) * RT_ENTRY_STRIDE * sizeof(uint2)));
+    }
     pd.retry = nullptr; pd.retry_cap = 0;
     if (pd.sc.deep_stack && !pd.primary_persistent) {      // the primary launch keeps no rows beyond LDS: the list of the rays that would need one
         const uint32_t want = ctx->opt_primary_retry_cap ? ctx->opt_primary_retry_cap : (1u << 20);
@@ -327,7 +348,7 @@ int render_region(rt_pipeline *p, uint32_t width, uint32_t height, Region r, con
     RT_TRY(prepare_lights(p, pd, plan, frames[0]));
     RT_TRY(stage_set_constants(p, pd, frames));
     fill_pipe_dev(p, pd, plan, r);
-    RT_TRY(choose_primary_stage(p, pd));
+    RT_TRY(choose_primary_stage(p, pd, frames));
     RT_TRY(rt_frame_launch(p, pd, plan, set_rows));
     HIP_TRY(hipGetLastError());
     if (pd.retry) p->primary_mode.sample(p->ctx, pd.retry + 1, plan.cap, p->ctx->stream);      // this set's retry count, for the next sets' choice of primary launch
@@ -632,6 +653,22 @@ int rt_debug_read_secondary_ray(rt_pipeline *p, uint32_t index, float origin_tmi
     const size_t slot = (size_t)(index / n) * p->last_pd.lv[1].rstride + index % n;
     HIP_TRY(hipMemcpy(origin_tmin, p->last_pd.lv[1].O + slot, 16, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(dir_tmax, p->last_pd.lv[1].D + slot, 16, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_debug_read_primary_entries(rt_pipeline *p, uint32_t first_tile, uint32_t count, uint32_t *entries, uint32_t *n_tiles, uint32_t *cut)
+{
+    RT_REQUIRE(p, "null pipeline");
+    RT_TRY(rt_pipeline_flush_pending(p));
+    if (!p->rendered) { rt_set_error("nothing rendered yet"); return RT_ERR_STATE; }
+    const uint32_t tiles = p->primary_entries.on ? p->last_pd.fcap >> 6 : 0u;
+    if (n_tiles) *n_tiles = tiles;
+    if (cut) *cut = p->primary_entries.on ? p->primary_entries.cut : 0u;
+    if (!entries || count == 0) return RT_OK;
+    RT_REQUIRE(first_tile < tiles && count <= tiles - first_tile, "tile out of range");
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    HIP_TRY(hipMemcpy(entries, p->primary_entries.lists.as<uint2>() + (size_t)first_tile * RT_ENTRY_STRIDE, (size_t)count * RT_ENTRY_STRIDE * sizeof(uint2), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

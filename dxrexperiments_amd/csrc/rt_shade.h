@@ -96,10 +96,10 @@ RT_DEV f3 sample_environment(const PipeDev &pd, const rt_per_frame_constants &fc
 // wave = one 8x8 screen tile), so a wave's primary rays -- and, through the order-preserving
 // compaction, the secondary and shadow rays spawned from them -- share BVH nodes.  Slots of
 // partial tiles that fall outside the rectangle are invalid.
-RT_DEV bool pix_xy(const PipeDev &pd, uint32_t q, uint32_t &px, uint32_t &py)
+// (tile_x, tile_y: the tile's place in the rectangle, for a caller that has them already; w: the slot inside the tile)
+RT_DEV bool pix_xy_in_tile(const PipeDev &pd, uint32_t tile_x, uint32_t tile_y, uint32_t w, uint32_t &px, uint32_t &py)
 {
-    const uint32_t t = q >> 6, w = q & 63u;
-    const uint32_t lx = (t % pd.tiles_x) * 8u + (w & 7u), ly = (t / pd.tiles_x) * 8u + (w >> 3);
+    const uint32_t lx = tile_x * 8u + (w & 7u), ly = tile_y * 8u + (w >> 3);
     px = pd.x0 + lx;
     if (pd.band_rows) {         // rows of the rectangle = this rank's interleaved bands, packed (rt_pipeline_render_bands)
         py = ((ly / pd.band_rows) * pd.band_world + pd.band_rank) * pd.band_rows + ly % pd.band_rows;
@@ -107,6 +107,11 @@ RT_DEV bool pix_xy(const PipeDev &pd, uint32_t q, uint32_t &px, uint32_t &py)
     }
     py = pd.y0 + ly;
     return lx < pd.tw && ly < pd.th;
+}
+RT_DEV bool pix_xy(const PipeDev &pd, uint32_t q, uint32_t &px, uint32_t &py)
+{
+    const uint32_t t = q >> 6, w = q & 63u;
+    return pix_xy_in_tile(pd, t % pd.tiles_x, t / pd.tiles_x, w, px, py);
 }
 
 // ---- RayGen (ProgressiveRaytracing.hlsl:18-32)

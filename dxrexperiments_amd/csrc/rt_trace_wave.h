@@ -135,6 +135,18 @@ RT_DEV bool node_is_internal(int node) { return node >= 0 && node < RT_NODE_EMPT
 template <class S, class = void> struct src_has_cache { static constexpr bool value = false; };
 template <class S> struct src_has_cache<S, decltype((void)&S::has_first_candidates)> { static constexpr bool value = true; };
 
+// A ray source may hand every 64-slot chunk of its rays a LIST OF ENTRY NODES to start from instead of the root (the primary launch's
+// per-tile lists, k_primary_entries in rt_pipeline.hip: the subtrees below a cut through the top of the tree that the tile's rays can
+// reach at all, nearest first): uint32_t first_entry(slot) -> the index of the first entry of the slot's list; uint2 entry(index) ->
+// (child code, bits of a lower bound of the distance at which any of the chunk's rays enters its box); a list ends with the code
+// RT_NODE_EMPTY.  The walk keeps the index of the lane's NEXT entry in an LDS row of its own -- the row behind the stack rows, where the
+// walks from the root keep the top of the tree: a walk from entries never steps on a node of the top (or reads it from global memory, where a
+// list had to fall back to a coarser cut), so the table is not loaded -- and takes it up when its stack runs empty.  (The last stack row, where the
+// any-hit walks park their cache slot, would not do: a walk that needs the row overwrites it, and a lost entry index is a lost subtree.)
+// Single-level closest-hit walks only.
+template <class S, class = void> struct src_has_entries { static constexpr bool value = false; };
+template <class S> struct src_has_entries<S, decltype((void)&S::has_entry_lists)> { static constexpr bool value = true; };
+
 RT_DEV unsigned long long lanemask_lt()
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -184,6 +196,7 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
     // running best hit -- which then never changes before the ray ends -- out of the registers
     const bool first = ANYHIT ? true : (flags & RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH) != 0;
     const bool cull = (flags & RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES) != 0;
+    constexpr bool ENTRIES = src_has_entries<Src>::value && !TWO_LEVEL && !ANYHIT;
     LaneStack<STACK, BLOCK> st;
     st.lds = smem + threadIdx.x;
     st.threads = gridDim.x * BLOCK;
@@ -196,14 +209,14 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
     // the LDS-resident top of the tree: smem rows STACK .. STACK + RT_TOP_ROWS - 1 hold nodes 0 .. top_n - 1 (breadth-first
     // numbering) of the structure a ray starts in: the BLAS of a single-level scene, the TLAS of a two-level one
     int *topl = smem + STACK * BLOCK;
-    if (sc.top_n != 0) {
+    if (!ENTRIES && sc.top_n != 0) {
         const int *src_top = (const int *)(TWO_LEVEL ? sc.tlas_wide : blas_nodes0);
         for (uint32_t i = threadIdx.x; i < sc.top_n * RT_TOP_WORDS; i += BLOCK) topl[i] = src_top[(i / RT_TOP_WORDS) * (uint32_t)(sizeof(WNode) / 4) + i % RT_TOP_WORDS];
     }
     const int *const top_cur = topl;
-    if (sc.top_n != 0) __syncthreads();
+    if (!ENTRIES && sc.top_n != 0) __syncthreads();
     const int root0 = TWO_LEVEL ? sc.tlas_root_code : in0->root_code;
-    uint32_t top_lim = sc.top_n;                  // node indices below this are read from LDS (two-level: 0 while inside a BLAS)
+    uint32_t top_lim = ENTRIES ? 0u : sc.top_n;   // node indices below this are read from LDS (two-level: 0 while inside a BLAS; a walk from entry lists: none)
 
     bool alive = false;
     bool exhausted = false;          // wave-uniform: the global pool has nothing left
@@ -316,6 +329,11 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
                     cur.o = r.o; cur.d = r.d; cur.ri = wri;
                     node = root0;
                     sp = 0;
+                    if constexpr (ENTRIES) {      // the first entry of the chunk's list (an empty list: the ray ends in the leaf phase, a miss)
+                        const uint32_t k = src.first_entry(chunk_next);      // (wave-uniform: the chunk's list)
+                        node = (int)src.entry(k).x;
+                        st.lds[STACK * BLOCK] = (int)(node != RT_NODE_EMPTY ? k + 1u : k);      // (never past the end of the list: nothing is written behind it)
+                    }
                     if (TWO_LEVEL) { nodes = sc.tlas_wide; in_blas = false; top_lim = sc.top_n; }
                     bool occluded_at_once = false;
                     if constexpr (REFILL_TESTS) {
@@ -409,7 +427,9 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
         if (alive && !node_is_internal(node)) {
             bool pop = true;
             if (COUNT && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec())) wv_leaf++;
-            if (node == RT_NODE_EMPTY) {
+            if (ENTRIES && node == RT_NODE_EMPTY) {
+                pop = false;            // (a walk from an entry list: what comes next is decided behind the pops, below)
+            } else if (node == RT_NODE_EMPTY) {
                 sink.store(idx, ANYHIT ? make_miss(r) : best, true);
                 alive = false;
                 pop = false;
@@ -477,6 +497,24 @@ RT_DEV void trace_wave(const SceneDev &sc, const Src &src, const Sink &sink, uin
                     else node = st.read(sp);
                 }
                 else node = RT_NODE_EMPTY;
+            }
+            if constexpr (ENTRIES) {
+                // the stack is empty -- the node loop's last pop or this phase's found nothing beneath: on to the next entry of the list, unless the
+                // list ends here or the entry -- and with it, the list being sorted by tnear, every later one -- begins beyond what the ray still looks
+                // for.  (tnear is a lower bound of what wide_step takes for the box's entry distance from any ray of the tile: the step in front
+                // of the box culls it by this very test, and a candidate inside it stands at or behind its entry distance)
+                if (alive && node == RT_NODE_EMPTY) {
+                    const uint32_t k = (uint32_t)st.lds[STACK * BLOCK];
+                    const uint2 e = src.entry(k);
+                    if ((int)e.x != RT_NODE_EMPTY && __uint_as_float(e.y) <= best.t * RT_SLAB_SLACK) {
+                        node = (int)e.x;
+                        st.lds[STACK * BLOCK] = (int)(k + 1u);
+                    } else {
+                        sink.store(idx, best, true);
+                        alive = false;
+                        if (COUNT) { const unsigned long long w = ((unsigned long long)(wk_glob + wk_top - wk_ray0) << 32) | idx; wk_longest = w > wk_longest ? w : wk_longest; }
+                    }
+                }
             }
         }
         if constexpr (NO_DEEP) {

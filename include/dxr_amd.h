@@ -648,6 +648,11 @@ int rt_debug_math(rt_context *ctx, int fn, const float *x, const float *y, float
 int rt_debug_sample(rt_context *ctx, int kind, const uint32_t *seeds, const float *vec3_in, float exponent,
                     float *vec3_out, float *pdf_brdf, uint32_t *seeds_out, size_t n);
 int rt_debug_read_secondary_ray(rt_pipeline *p, uint32_t index, float origin_tmin[4], float dir_tmax[4]);   /* tools/longest_walk.py */
+/* The entry lists the last set of launches started its primary rays from (option primary_entries): *n_tiles = 8x8 tiles of the set's rectangle,
+ * row-major (0: the set ran without lists), *cut = the cut the lists were made with.  entries (may be NULL): for the tiles first_tile ..
+ * first_tile + count - 1, 33 pairs each of (int32 child code as in rt_scene_wide_read's nodes, float32 bits of tnear); a list ends with
+ * the code 0x7FFFFFFE.  tests/test_gpu_primary_entries.py */
+int rt_debug_read_primary_entries(rt_pipeline *p, uint32_t first_tile, uint32_t count, uint32_t *entries, uint32_t *n_tiles, uint32_t *cut);
 /* Experiment and test knobs of a context, in ONE place (round 5; rounds 1 - 4 read 19 environment variables where they were used).
  * Defaults are the measured best; nothing here changes a result bit -- only which kernels and layouts produce it.  The library
  * reads exactly one environment variable for its behaviour, once, in rt_context_create: RT_DEBUG_OPTIONS="name=value,name=value",
@@ -672,6 +677,12 @@ int rt_debug_read_secondary_ray(rt_pipeline *p, uint32_t index, float origin_tmi
  *                            cause): the LBVH is collapsed instead
  *   primary_retry_cap=n      entries of the retry list behind the one-tile-per-wave primary launch (0: 2^20; tests make it overflow)
  *   queue_budget_mb=n        worst-case queue bytes a set may reserve up front (0: a quarter of the device's memory)
+ *   primary_entries=-1|0|1   primary rays start from their 8x8 tile's list of entry nodes, made once per set of launches, instead of the root
+ *                            (-1: sets of at least 4 frames of single-level scenes with lds_top=1 whose primary launch is not persistent -- a
+ *                            shorter set does not pay for its lists; a set whose frames do not share the camera's U, V, W runs without
+ *                            lists whatever the option says)
+ *   primary_entries_cut=0..128   the lists cut the tree below its first n breadth-first nodes (0: 128)
+ *   primary_entries_cap=0..32    entries a list may hold before its tile falls back to a coarser cut, at last to the root (0: 32; tests: 1)
  *   dist_check_seconds=x     how long rt_dist_create waits for the other ranks' device ids (5)
  * Every value but fast_bvh's must be a number in full ("true", "4x", "" are RT_ERR_INVALID_ARG, not 0); RT_DEBUG_OPTIONS items must be name=value. */
 int rt_debug_set_option(rt_context *ctx, const char *name, const char *value);
