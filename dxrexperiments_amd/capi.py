@@ -98,6 +98,7 @@ SIGNATURES = {
     "rt_skeleton_read_palette": (_i, [_p, _p]),
     "rt_skeleton_get_palette_device_ptr": (_i, [_p, _pp]),
     "rt_model_set_bones_from_skeleton": (_i, [_p, _p]),
+    "rt_skeleton_get_joints_device_ptr": (_i, [_p, _pp]),
     "rt_model_retain": (_i, [_p]),
     "rt_model_destroy": (_i, [_p]),
     "rt_scene_create": (_i, [_p, _pp]),
@@ -115,6 +116,11 @@ SIGNATURES = {
     "rt_scene_build_ms": (_i, [_p, C.POINTER(_f)]),
     "rt_scene_set_instance_transform": (_i, [_p, _u32, _p]),
     "rt_scene_set_instance_transforms": (_i, [_p, _u32, _u32, _p]),
+    "rt_scene_set_instance_transforms_mem": (_i, [_p, _u32, _u32, _p, _u32]),
+    "rt_scene_get_instance_transforms": (_i, [_p, _u32, _u32, _p]),
+    "rt_scene_attach_instances": (_i, [_p, _u32, _u32, _p, _p, _p]),
+    "rt_scene_detach_instances": (_i, [_p, _u32, _u32]),
+    "rt_scene_get_instance_attachment": (_i, [_p, _u32, _pp, _pu]),
     "rt_scene_set_instance_mask": (_i, [_p, _u32, C.c_uint8]),
     "rt_scene_set_instance_masks": (_i, [_p, _u32, _u32, _p]),
     "rt_scene_get_instance_masks": (_i, [_p, _u32, _u32, _p]),
@@ -597,6 +603,12 @@ class Skeleton:
         _check(lib().rt_skeleton_get_palette_device_ptr(self.h, C.byref(p)))
         return p.value
 
+    def joints_ptr(self):
+        """the world matrices W_j in device memory, n_joints x 12 floats (what Scene.attach composes from)"""
+        p = C.c_void_p()
+        _check(lib().rt_skeleton_get_joints_device_ptr(self.h, C.byref(p)))
+        return p.value
+
 
 class Scene:
     """RtScene (libs/DXRFramework/RtScene.h:14-37)."""
@@ -643,6 +655,43 @@ class Scene:
         rows = [T.IDENTITY_3X4 if x is None else x for x in transforms]
         x = _f32(rows, (-1, 12)) if len(rows) else np.zeros((0, 12), np.float32)
         _check(lib().rt_scene_set_instance_transforms(self.h, first, x.shape[0], _ptr(x)))
+
+    def set_transforms_device(self, first, ptr, count):
+        """Extension: ... from count x 12 floats in device memory, copied on the context's stream: nothing is downloaded and nothing waits"""
+        _check(lib().rt_scene_set_instance_transforms_mem(self.h, first, count, C.c_void_p(ptr), MEM_DEVICE))
+
+    def transforms(self, first=0, count=None):
+        """the twelve floats the scene holds for instances first .. first + count - 1 (None: to the last), pending or applied: float32[count, 12]"""
+        n = self.num_instances - first if count is None else count
+        out = np.empty((n, 12), np.float32)
+        _check(lib().rt_scene_get_instance_transforms(self.h, first, n, _ptr(out)))
+        return out
+
+    def attach(self, first, skeleton, joints, locals=None):
+        """Extension: instances first .. first + len(joints) - 1 follow joints[k] of a Skeleton: at every update() or build() that applies a
+        pose their transform is W_joint o locals[k] (float32[len(joints), 12]; None: W_joint itself), composed on the device.  The scene keeps
+        the skeleton alive."""
+        j = np.ascontiguousarray(joints, dtype=np.uint32).reshape(-1)
+        x = None if locals is None else _f32(locals, (-1, 12))
+        if x is not None and x.shape[0] != j.shape[0]:
+            raise RtError(-1, "attach: %d joints, %d local matrices" % (j.shape[0], x.shape[0]))
+        _check(lib().rt_scene_attach_instances(self.h, first, j.shape[0], skeleton.h, _ptr(j), None if x is None else _ptr(x)))
+        held = self.__dict__.setdefault("_skeletons", {})
+        held[skeleton.h.value] = skeleton
+
+    def detach(self, first, count=1):
+        """Extension: the instances keep the transform their last update() or build() gave them and follow no joint any more"""
+        _check(lib().rt_scene_detach_instances(self.h, first, count))
+
+    def attachment(self, i):
+        """(Skeleton, joint) of an attached instance -- the Skeleton object attach() was given, or its handle if this wrapper never saw it --
+        or None"""
+        sk, joint = C.c_void_p(), C.c_uint32()
+        _check(lib().rt_scene_get_instance_attachment(self.h, i, C.byref(sk), C.byref(joint)))
+        if not sk.value:
+            return None
+        known = self.__dict__.get("_skeletons", {}).get(sk.value)
+        return (known if known is not None and known.h else sk.value), joint.value
 
     def set_mask(self, i, mask):
         """Extension: the InstanceMask byte of instance i (0xFF when added); the instance is visible to rays iff it is non-zero.  A change of

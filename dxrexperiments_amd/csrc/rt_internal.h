@@ -361,6 +361,8 @@ struct SkeletonClip {
 
 struct rt_skeleton {
     rt_context *ctx = nullptr;
+    int refs = 1;                // handle + every scene that has instances attached to it (once per scene)
+    uint64_t pose_count = 0;     // bumped by every pose set or sampled: a scene records it per attached instance at build / update (SceneAttach::seen)
     uint32_t n_joints = 0, n_levels = 0;
     std::vector<uint32_t> level_offsets;     // n_levels + 1 (rt_skeleton.h)
     DevBuf table;                // uint32[n_joints]: joint | parent << 16 in level order (rt_skeleton_pack_table)
@@ -377,6 +379,12 @@ struct rt_skeleton {
 struct SceneInstance {
     rt_model *model;
     float xform[12];
+};
+
+// rt_scene_attach_instances: the binding of one instance (rt_scene::att; the device reads att_words / att_local / att_w)
+struct SceneAttach {
+    rt_skeleton *sk = nullptr;   // nullptr: not attached.  Retained by the scene, once per scene (rt_scene::skeletons)
+    uint64_t seen = 0;           // sk->pose_count when the scene last applied a pose to this instance (0: never)
 };
 
 struct rt_scene {
@@ -410,6 +418,15 @@ struct rt_scene {
     std::vector<uint32_t> vis;           // the visible instances, ascending, as the TLAS stands for them (written by a build / update)
     DevBuf d_vis;                        // ... on the device: uploaded only by a build or update at which some visibility changed
     uint32_t n_vis = 0;                  // how many; == inst.size(): nothing hidden, d_vis is not read and the builders launch what they always did
+    // rt_scene_set_instance_transforms_mem(RT_MEM_DEVICE) / rt_scene_attach_instances: transforms that come from device memory
+    DevBuf d_xf;                         // float[12 n]: the transform of every DEVICE-HELD instance (set from device memory, or composed from a joint)
+    std::vector<uint8_t> xf_on_dev;      // per instance: d_xf holds its transform and SceneInstance::xform is older (until an update's join or a build's)
+    DevBuf xf_back;                      // the device-sourced transforms an update listed, slot by slot, on their way to SceneInstance::xform
+    std::vector<SceneAttach> att;        // per instance (or shorter: instances added since the last attachment have none)
+    std::vector<uint32_t> att_words;     // per instance: the binding as the device reads it (rt_attach.h), 0: not attached ...
+    std::vector<float> att_local;        // ... its local matrix, float[12] per instance ...
+    DevBuf d_att_words, d_att_local, d_att_w;    // ... and both on the device, with the skeleton's W array (const float *) of every attached instance
+    std::vector<rt_skeleton *> skeletons;        // the skeletons the scene retains: every one some instance is or was attached to, each once
     SceneDev dev() const
     {
         SceneDev s;
@@ -437,6 +454,9 @@ void rt_scene_model_changed(rt_scene *s);
 // RT_OK for a built scene.  Otherwise RT_ERR_STATE and its message: what is pending -- transforms, instance masks, models' vertices -- or, if
 // nothing is, `not_built`, a format that may name `who` once
 int rt_scene_require_built(const rt_scene *s, const char *who, const char *not_built);
+
+// rt_skeleton.hip
+void rt_skeleton_retain(rt_skeleton *sk);
 
 // rt_bvh_ploc.hip
 // n_leaves / leaf_box6 / leaf_prim: the leaves to cluster in Morton order -- nullptr: the canonical leaves (one per triangle); else the

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <new>
 
+#include "rt_attach.h"
 #include "rt_lbvh.h"
 #include "rt_xform.h"
 
@@ -42,6 +43,9 @@ void scene_build_begins(rt_scene *s) { s->updatable = false; }
 void scene_applied(rt_scene *s, const std::vector<uint32_t> *changed)
 {
     const size_t n = s->inst.size();
+    // the attached instances it listed (an update: the pending ones; a build: all) now stand where their skeleton's current pose puts them
+    for (size_t i = 0; i < s->att.size(); i++)
+        if (s->att[i].sk && (!changed || s->is_pending[i])) s->att[i].seen = s->att[i].sk->pose_count;
     if (changed) {
         for (uint32_t i : s->pending) s->is_pending[i] = 0;
         for (uint32_t i : *changed) s->seen_geom[i] = s->inst[i].model->geom_gen;
@@ -64,6 +68,67 @@ size_t scene_changed_instances(const rt_scene *s, std::vector<uint32_t> *which =
     for (size_t i = 0; i < s->inst.size(); i++)
         if (s->inst[i].model->geom_gen != s->seen_geom[i]) { n++; if (which) which->push_back((uint32_t)i); }
     return n;
+}
+
+// ---- transforms that come from device memory: set there (rt_scene_set_instance_transforms_mem) or composed from a joint (rt_scene_attach_instances) ----
+
+bool scene_attached(const rt_scene *s, size_t i) { return i < s->att.size() && s->att[i].sk != nullptr; }
+bool scene_on_device(const rt_scene *s, size_t i) { return i < s->xf_on_dev.size() && s->xf_on_dev[i] != 0; }
+
+// attached instances of an updatable scene whose skeleton has been posed since the scene last applied it, and that are not pending already
+size_t scene_posed_instances(const rt_scene *s, std::vector<uint32_t> *which)
+{
+    size_t n = 0;
+    if (!s->updatable) return 0;
+    for (size_t i = 0; i < s->att.size(); i++) {
+        const SceneAttach &a = s->att[i];
+        if (!a.sk || !a.sk->posed || a.sk->pose_count == a.seen) continue;
+        if (i < s->is_pending.size() && s->is_pending[i]) continue;
+        n++;
+        if (which) which->push_back((uint32_t)i);
+    }
+    return n;
+}
+
+// an update or a build composes every attached instance it lists from W: refused, with nothing changed, while some skeleton has no pose
+int scene_require_poses(const rt_scene *s, const char *who)
+{
+    for (size_t i = 0; i < s->att.size(); i++)
+        if (s->att[i].sk && !s->att[i].sk->posed) {
+            rt_set_error("%s: instance %zu is attached to a skeleton that has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", who, i);
+            return RT_ERR_STATE;
+        }
+    return RT_OK;
+}
+
+// a transform setter whose range holds an attached instance is refused: the joint says where it stands
+int scene_refuse_attached(const rt_scene *s, const char *who, uint32_t first, uint32_t count)
+{
+    uint32_t i = 0;
+    if (!rt_attach_range_holds(s->att_words.data(), s->att_words.size(), first, count, &i)) return RT_OK;
+    rt_set_error("%s: instance %u is attached to joint %u of a skeleton, which gives it its transform (rt_scene_detach_instances lets it go)", who, i,
+                 s->att_words[i] & RT_ATTACH_JOINT_MASK);
+    return RT_ERR_STATE;
+}
+
+// d_xf for all of the scene's instances: reserved once (again only after rt_scene_add_model has made the list longer; what it held then comes
+// down to the host copies first -- DevBuf::reserve keeps no contents -- the one place where a setter waits)
+int reserve_device_transforms(rt_context *ctx, rt_scene *s)
+{
+    const size_t n = s->inst.size();
+    s->xf_on_dev.resize(n, 0);
+    if (s->d_xf.bytes >= 48 * n) return RT_OK;
+    std::vector<float> down(12 * n);
+    bool any = false;
+    for (size_t i = 0; i < n; i++)
+        if (s->xf_on_dev[i] && 48 * (i + 1) <= s->d_xf.bytes) {
+            HIP_TRY(hipMemcpyAsync(&down[12 * i], s->d_xf.as<char>() + 48 * i, 48, hipMemcpyDeviceToHost, ctx->stream));
+            any = true;
+        }
+    if (any) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++)
+        if (s->xf_on_dev[i]) { memcpy(s->inst[i].xform, &down[12 * i], 48); s->xf_on_dev[i] = 0; }
+    return s->d_xf.reserve(48 * n);
 }
 
 // A scene whose transforms, instance masks or models' vertices were set and not applied yet: says so (the message names them) and returns true.
@@ -195,6 +260,47 @@ int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool for
 // TLAS is a pure function of the instance boxes and every traversal returns the same bits on any tree, so the TLAS is
 // always rebuilt -- into the scene's own buffers -- from boxes of which only the listed instances' are computed anew.  Only the listed
 // transforms and their indices go up; the records are rewritten, and the work list of the world boxes is made, on the device.
+
+// One lane per listed instance whose transform the device holds or makes (`idx`: their run of the listed indices, n of them; `pend_xf` and
+// `back`: their run of the listed transforms and the copy that outlives the arena).  An attached instance (words[i] has RT_ATTACH_BOUND, rt_attach.h):
+// T = W_joint o local by compose3x4, always multiplied, or T = W_joint bit for bit when it has no local matrix; T goes into the scene's device
+// storage d_xf too, from where on it is a transform set from device memory.  Any other: the twelve floats d_xf holds for it.  A lane reads and
+// writes the rows of its own instance only, and an instance is listed once.  The grid's last wave may be partial: these lanes meet nowhere.
+__global__ void __launch_bounds__(UPD_BLOCK) k_gather_transforms(const uint32_t *__restrict__ idx, uint32_t n, const uint32_t *__restrict__ words,
+                                                                 uint32_t n_words, const float *__restrict__ local, const float *const *__restrict__ w_of,
+                                                                 float *d_xf, float *__restrict__ pend_xf, float *__restrict__ back)
+{
+    const uint32_t k = blockIdx.x * UPD_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t i = idx[k];
+    const uint32_t word = i < n_words ? words[i] : 0u;     // (instances added after the last attachment have no word)
+    float T[12];
+    if (word & RT_ATTACH_BOUND) {
+        const float *W = w_of[i] + 12u * (size_t)(word & RT_ATTACH_JOINT_MASK);
+        float A[12];
+#pragma unroll
+        for (int e = 0; e < 12; e++) A[e] = W[e];
+        if (word & RT_ATTACH_LOCAL) {
+            float B[12];
+#pragma unroll
+            for (int e = 0; e < 12; e++) B[e] = local[12u * (size_t)i + e];
+            compose3x4(A, B, T);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 12; e++) T[e] = A[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 12; e++) d_xf[12u * (size_t)i + e] = T[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 12; e++) T[e] = d_xf[12u * (size_t)i + e];
+    }
+#pragma unroll
+    for (int e = 0; e < 12; e++) {
+        pend_xf[12u * (size_t)k + e] = T[e];
+        back[12u * (size_t)k + e] = T[e];
+    }
+}
 
 constexpr unsigned UPD_BACK_WORDS = 20;      // inv[12], wlo[3], root_code, whi[3], flags: the head of an InstanceRec
 static_assert(offsetof(InstanceRec, flags) == 4 * (UPD_BACK_WORDS - 1), "the read-back of an update is the head of the record");
@@ -390,16 +496,31 @@ int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint
 // instances' records and their world boxes, rebuilds the TLAS over the visible instances and takes the scene's summary, on the device.
 // `who` names the caller in messages.  It creates no event and reads no time; `queued` (or nullptr) is the caller's event, which it records
 // behind the wide collapse, in front of the read-back: where update_ms ends
-int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &list, const char *who, hipEvent_t queued)
+int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &listed, const char *who, hipEvent_t queued)
 {
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)s->inst.size();
-    const size_t np = list.size();
-    std::vector<float> xf(12 * np);                    // (alive, as the index list is, until the last synchronisation below)
+    const size_t np = listed.size();
+    // The listed instances in two runs: first those whose transform the host holds, nh of them, whose floats go up as they always did; then
+    // those whose transform the device holds or makes (set from device memory, attached to a joint), nd of them, whose slots
+    // k_gather_transforms fills.  The slot order decides nothing (k_update_records): every slot is written before that kernel reads it.
+    // (the scene's device storage first, for all n: should the list have grown since it was reserved, what it held comes down to the host
+    // copies and those instances are host-sourced below)
+    bool from_device = false;
+    for (uint32_t i : listed) from_device = from_device || scene_attached(s, i) || scene_on_device(s, i);
+    if (from_device) RT_TRY(reserve_device_transforms(ctx, s));
+    std::vector<uint32_t> list;                        // (alive, as xf is, until the last synchronisation below)
+    list.reserve(np);
+    for (uint32_t i : listed)
+        if (!scene_attached(s, i) && !scene_on_device(s, i)) list.push_back(i);
+    const size_t nh = list.size(), nd = np - nh;
+    for (uint32_t i : listed)
+        if (scene_attached(s, i) || scene_on_device(s, i)) list.push_back(i);
+    std::vector<float> xf(12 * nh);
     size_t max_items = 0;
     for (size_t k = 0; k < np; k++) {
         const SceneInstance &in = s->inst[list[k]];
-        memcpy(&xf[12 * k], in.xform, 12 * sizeof(float));
+        if (k < nh) memcpy(&xf[12 * k], in.xform, 12 * sizeof(float));
         max_items += (3 * (size_t)in.model->n_tris + INST_BOX_REFS - 1) / INST_BOX_REFS;
     }
     if (max_items > 0x7fffffffu) { rt_set_error("%s: %zu work items for the world boxes: the limit is 2^31 - 1", who, max_items); return RT_ERR_UNSUPPORTED; }
@@ -409,10 +530,19 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &li
     RT_TRY(reserve_tlas_for(s->tlas, n));
     RT_TRY(s->update_back.reserve(sizeof(uint32_t) * UPD_BACK_WORDS * (size_t)n));
     std::vector<uint32_t> back(UPD_BACK_WORDS * np);
+    std::vector<float> back_xf(12 * nd);
+    if (nd) RT_TRY(s->xf_back.reserve(48 * (size_t)n));
     InstanceRec *inst = s->d_inst.as<InstanceRec>();
     if (np) {                                          // (none: an update of masks alone)
         HIP_TRY(hipMemcpyAsync(t.pend_idx, list.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        if (nh) HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        if (nd) {
+            k_gather_transforms<<<grid_for(nd, UPD_BLOCK), UPD_BLOCK, 0, st>>>(t.pend_idx + nh, (uint32_t)nd, s->d_att_words.as<uint32_t>(),
+                                                                              (uint32_t)s->att_words.size(), s->d_att_local.as<float>(),
+                                                                              (const float *const *)s->d_att_w.p, s->d_xf.as<float>(), t.pend_xf + 12 * nh,
+                                                                              s->xf_back.as<float>());
+            HIP_TRY(hipGetLastError());
+        }
         HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
         k_update_records<<<grid_for(np, UPD_BLOCK), UPD_BLOCK, 0, st>>>(inst, s->blas_bounds.as<float>(), t.pend_idx, t.pend_xf, (uint32_t)np, t.pend_enc,
                                                                        t.items, t.n_items, (uint32_t)max_items);
@@ -431,8 +561,15 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &li
     if (queued) HIP_TRY(hipEventRecord(queued, st));
     // the final join: it brings back the rewritten records' heads with the TLAS' depth and bounds
     if (np) HIP_TRY(hipMemcpyAsync(back.data(), s->update_back.p, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    // ... and, with them, the transforms the device held or made: the host copy follows here, behind everything queued
+    if (nd) HIP_TRY(hipMemcpyAsync(back_xf.data(), s->xf_back.p, back_xf.size() * sizeof(float), hipMemcpyDeviceToHost, st));
     RT_TRY(lbvh_collect(ctx, s->tlas));
     for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[list[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
+    for (size_t k = 0; k < nd; k++) {
+        const uint32_t i = list[nh + k];
+        memcpy(s->inst[i].xform, &back_xf[12 * k], 12 * sizeof(float));
+        if (i < s->xf_on_dev.size()) s->xf_on_dev[i] = 0;      // (d_xf holds the same floats: either source serves the next update)
+    }
     // the scene's summary, taken again over all models: a deformation changes depths and can create or remove split references
     uint32_t deepest = 0, canon = s->tlas.max_depth;
     s->has_refs = false;
@@ -494,6 +631,7 @@ rt_scene::~rt_scene()
             if (held[k] == this) { held.erase(held.begin() + k); break; }
         rt_model_destroy(in.model);
     }
+    for (rt_skeleton *sk : skeletons) rt_skeleton_destroy(sk);     // (joins the stream when the scene held the last reference)
 }
 
 void rt_scene_model_changed(rt_scene *s)
@@ -545,8 +683,12 @@ int rt_scene_set_instance_transforms(rt_scene *s, uint32_t first, uint32_t count
     RT_REQUIRE(s && (transforms3x4 || count == 0), "null argument");
     RT_TRY(scene_range_check(s, "rt_scene_set_instance_transforms", first, count));
     if (count == 0) return RT_OK;
+    RT_TRY(scene_refuse_attached(s, "rt_scene_set_instance_transforms", first, count));
     RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
-    for (uint32_t k = 0; k < count; k++) memcpy(s->inst[first + k].xform, transforms3x4 + 12 * (size_t)k, sizeof s->inst[0].xform);
+    for (uint32_t k = 0; k < count; k++) {
+        memcpy(s->inst[first + k].xform, transforms3x4 + 12 * (size_t)k, sizeof s->inst[0].xform);
+        if (first + k < s->xf_on_dev.size()) s->xf_on_dev[first + k] = 0;     // (the host holds it again)
+    }
     if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the stored transforms)
     return RT_OK;
 }
@@ -556,6 +698,125 @@ int rt_scene_set_instance_transform(rt_scene *s, uint32_t instance, const float 
     RT_REQUIRE(s && transform3x4, "null argument");
     RT_TRY(scene_range_check(s, __func__, instance, 1, true));
     return rt_scene_set_instance_transforms(s, instance, 1, transform3x4);
+}
+
+// EXTENSION: the Transform member of the instance descriptors (TopLevelASGenerator.cpp:344-362) from device memory: the floats stay where they
+// are until the update's kernels read them (k_gather_transforms)
+int rt_scene_set_instance_transforms_mem(rt_scene *s, uint32_t first, uint32_t count, const float *transforms3x4, uint32_t mem)
+{
+    RT_REQUIRE(s && (transforms3x4 || count == 0), "null argument");
+    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
+    if (mem == RT_MEM_HOST) return rt_scene_set_instance_transforms(s, first, count, transforms3x4);
+    RT_TRY(scene_range_check(s, __func__, first, count));
+    if (count == 0) return RT_OK;
+    RT_TRY(scene_refuse_attached(s, __func__, first, count));
+    rt_context *ctx = s->ctx;
+    RT_TRY(rt_use_device(ctx));
+    RT_TRY(rt_context_flush_deferred(ctx));          // frames accepted before this change see the scene as it was
+    RT_TRY(reserve_device_transforms(ctx, s));
+    // (ordered on the context's stream: the caller's array is its own again once the stream has passed this copy)
+    HIP_TRY(hipMemcpyAsync(s->d_xf.as<float>() + 12 * (size_t)first, transforms3x4, 48 * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream));
+    for (uint32_t k = 0; k < count; k++) s->xf_on_dev[first + k] = 1;
+    if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the stored transforms)
+    return RT_OK;
+}
+
+int rt_scene_get_instance_transforms(const rt_scene *s, uint32_t first, uint32_t count, float *transforms3x4)
+{
+    RT_REQUIRE(s && (transforms3x4 || count == 0), "null argument");
+    RT_TRY(scene_range_check(s, __func__, first, count));
+    bool waits = false;
+    for (uint32_t k = 0; k < count;) {
+        if (!scene_on_device(s, first + k)) {
+            memcpy(transforms3x4 + 12 * (size_t)k, s->inst[first + k].xform, 48);
+            k++;
+            continue;
+        }
+        uint32_t run = 1;                              // device-held ones come down run by run, on demand
+        while (k + run < count && scene_on_device(s, first + k + run)) run++;
+        if (!waits) RT_TRY(rt_use_device(s->ctx));
+        HIP_TRY(hipMemcpyAsync(transforms3x4 + 12 * (size_t)k, s->d_xf.as<float>() + 12 * (size_t)(first + k), 48 * (size_t)run, hipMemcpyDeviceToHost,
+                               s->ctx->stream));
+        waits = true;
+        k += run;
+    }
+    if (waits) HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return RT_OK;
+}
+
+int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_skeleton *sk, const uint32_t *joints, const float *local3x4)
+{
+    RT_REQUIRE(s && sk && (joints || count == 0), "null argument");
+    uint32_t bad = 0;
+    switch (rt_attach_validate((uint32_t)s->inst.size(), first, count, sk->n_joints, joints, &bad)) {
+    case 0: break;
+    case 1: rt_set_error("rt_scene_attach_instances: null argument"); return RT_ERR_INVALID_ARG;
+    case 2: return scene_range_check(s, __func__, first, count);
+    default:
+        rt_set_error("rt_scene_attach_instances: entry %u names joint %u: the skeleton has %u", bad, joints[bad], sk->n_joints);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (sk->ctx != s->ctx) { rt_set_error("rt_scene_attach_instances: the scene and the skeleton belong to different contexts"); return RT_ERR_STATE; }
+    if (count == 0) return RT_OK;
+    rt_context *ctx = s->ctx;
+    RT_TRY(rt_use_device(ctx));
+    RT_TRY(rt_context_flush_deferred(ctx));          // frames accepted before this change see the scene as it was
+    const size_t n = s->inst.size();
+    // the bindings of all n instances as they will stand, beside the ones the scene has: nothing changes if the device refuses
+    std::vector<uint32_t> words(s->att_words);
+    std::vector<float> local(s->att_local);
+    std::vector<const float *> w_of(n, nullptr);
+    words.resize(n, 0u);
+    local.resize(12 * n, 0.0f);
+    rt_attach_pack(count, joints, local3x4 != nullptr, words.data() + first);
+    if (local3x4) memcpy(&local[12 * (size_t)first], local3x4, 48 * (size_t)count);
+    for (size_t i = 0; i < n; i++)
+        if (i >= first && i < (size_t)first + count) w_of[i] = sk->joints.as<float>();
+        else if (scene_attached(s, i)) w_of[i] = s->att[i].sk->joints.as<float>();
+    RT_TRY(reserve_device_transforms(ctx, s));         // (where the composed transforms will stand)
+    // for all n at once; a longer list than the arrays were made for: everything goes up again (DevBuf::reserve keeps no contents)
+    const bool all = s->d_att_words.bytes < 4 * n || s->att_words.size() != n;
+    RT_TRY(s->d_att_words.reserve(4 * n));
+    RT_TRY(s->d_att_local.reserve(48 * n));
+    RT_TRY(s->d_att_w.reserve(sizeof(const float *) * n));
+    const size_t a = all ? 0 : first, c = all ? n : count;
+    HIP_TRY(hipMemcpyAsync(s->d_att_words.as<uint32_t>() + a, &words[a], 4 * c, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_att_local.as<float>() + 12 * a, &local[12 * a], 48 * c, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync((const float **)s->d_att_w.p + a, &w_of[a], sizeof(const float *) * c, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope, the caller's arrays are its own again)
+    s->att_words.swap(words);
+    s->att_local.swap(local);
+    s->att.resize(n);
+    bool held = false;
+    for (rt_skeleton *o : s->skeletons) held = held || o == sk;
+    if (!held) { s->skeletons.push_back(sk); rt_skeleton_retain(sk); }      // (as the scene retains its models; let go of when the scene goes)
+    for (uint32_t k = 0; k < count; k++) { s->att[first + k].sk = sk; s->att[first + k].seen = 0; }
+    if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the binding)
+    return RT_OK;
+}
+
+int rt_scene_detach_instances(rt_scene *s, uint32_t first, uint32_t count)
+{
+    RT_REQUIRE(s, "null scene");
+    RT_TRY(scene_range_check(s, __func__, first, count));
+    uint32_t from = 0;
+    if (!rt_attach_range_holds(s->att_words.data(), s->att_words.size(), first, count, &from)) return RT_OK;      // none attached: nothing to do
+    const uint32_t end = (uint32_t)((size_t)first + count < s->att_words.size() ? (size_t)first + count : s->att_words.size());
+    RT_TRY(rt_use_device(s->ctx));
+    // (a word of 0 is "not attached": the instance keeps the floats its last update or build gave it, in the host copy and in d_xf alike)
+    HIP_TRY(hipMemsetAsync(s->d_att_words.as<uint32_t>() + from, 0, 4 * (size_t)(end - from), s->ctx->stream));
+    for (uint32_t i = from; i < end; i++) { s->att_words[i] = 0u; s->att[i].sk = nullptr; s->att[i].seen = 0; }
+    return RT_OK;
+}
+
+int rt_scene_get_instance_attachment(const rt_scene *s, uint32_t instance, rt_skeleton **sk, uint32_t *joint)
+{
+    RT_REQUIRE(s, "null scene");
+    RT_TRY(scene_range_check(s, __func__, instance, 1, true));
+    const bool bound = scene_attached(s, instance);
+    if (sk) *sk = bound ? s->att[instance].sk : nullptr;
+    if (joint) *joint = bound ? s->att_words[instance] & RT_ATTACH_JOINT_MASK : 0u;
+    return RT_OK;
 }
 
 // EXTENSION: the InstanceMask member of the instance descriptors (TopLevelASGenerator.cpp:344-362), which the reference fills with 0xFF, under the
@@ -600,10 +861,14 @@ int rt_scene_update(rt_scene *s)
     }
     std::vector<uint32_t> changed;                    // instances whose model's vertices were set since their records were written
     scene_changed_instances(s, &changed);
-    if (s->pending.empty() && changed.empty() && !s->masks_dirty) return RT_OK;      // nothing to apply: nothing launched, the generation stays
+    std::vector<uint32_t> posed;                      // attached instances whose skeleton has been posed since the scene last applied it
+    scene_posed_instances(s, &posed);
+    if (s->pending.empty() && changed.empty() && !s->masks_dirty && posed.empty()) return RT_OK;      // nothing to apply: nothing launched, the generation stays
     rt_context *ctx = s->ctx;
     RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
+    // an attachment to a skeleton that has no pose yet: refused here, with every pending thing kept, as below
+    RT_TRY(scene_require_poses(s, "rt_scene_update"));
     // pending masks: the visible sub-list goes up if it differs from the one the TLAS stands for (no visible instance: refused here, with every
     // pending thing kept -- showing one and updating again succeeds)
     if (s->masks_dirty) RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_update", false));
@@ -618,6 +883,11 @@ int rt_scene_update(rt_scene *s)
         for (uint32_t i : changed) RT_TRY(rt_build_blas(ctx, s->inst[i].model));
         RT_TRY(rt_update_model_records(ctx, s, changed));
         for (uint32_t i : changed) scene_mark_pending(s, i);      // ... and take their world boxes over the new vertices, with the transforms they have
+    }
+    if (!posed.empty()) {
+        // the new pose is applied with everything else, in this one call: its instances join the list, the scene is stale until it has succeeded
+        for (uint32_t i : posed) scene_mark_pending(s, i);
+        s->built = false;
     }
     // (a failure leaves the scene stale, the transforms and the models pending); e1: behind the wide collapse, in front of the read-back
     RT_TRY(rt_update_tlas(ctx, s, s->pending, "rt_scene_update", e1.e));
@@ -648,6 +918,7 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     rt_context *ctx = s->ctx;
     RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));
+    RT_TRY(scene_require_poses(s, "rt_scene_build"));                 // (an attachment to a skeleton without a pose: refused with everything kept)
     RT_TRY(rt_scene_apply_masks(ctx, s, "rt_scene_build", true));     // (no visible instance: refused as a scene without instances is)
     ScopedEvent e0, e1;
     HIP_TRY(hipEventCreate(&e0.e));

@@ -145,6 +145,7 @@ int pose_skeleton(rt_skeleton *sk)
         k_skeleton_pose<false><<<1, RT_SKELETON_BLOCK, 0, st>>>(pose, table, off, sk->n_levels, sk->n_joints, ib, sk->joints.as<float>(), sk->palette.as<float>());
     HIP_TRY(hipGetLastError());
     sk->posed = true;
+    sk->pose_count++;         // (scenes with instances attached to a joint compare it with the count they last applied: rt_scene_update)
     return RT_OK;
 }
 
@@ -165,6 +166,8 @@ int read_back(rt_skeleton *sk, const char *who, const DevBuf &from, float *to, s
 }
 
 }  // namespace
+
+void rt_skeleton_retain(rt_skeleton *sk) { if (sk) sk->refs++; }
 
 rt_skeleton::~rt_skeleton()
 {
@@ -219,6 +222,7 @@ int rt_skeleton_create(rt_context *ctx, uint32_t n_joints, const int32_t *parent
 int rt_skeleton_destroy(rt_skeleton *sk)
 {
     if (!sk) return RT_OK;
+    if (--sk->refs > 0) return RT_OK;                   // (a scene with instances attached to it holds it: they keep their last transform)
     rt_context *ctx = sk->ctx;
     delete sk;                // (joins the stream first: a skin kernel queued by rt_model_set_bones_from_skeleton reads a live palette)
     rt_context_release(ctx);
@@ -339,6 +343,14 @@ int rt_skeleton_get_palette_device_ptr(rt_skeleton *sk, void **ptr)
     RT_REQUIRE(sk && ptr, "null argument");
     RT_TRY(require_pose(sk, "rt_skeleton_get_palette_device_ptr"));
     *ptr = sk->palette.p;
+    return RT_OK;
+}
+
+int rt_skeleton_get_joints_device_ptr(rt_skeleton *sk, void **ptr)
+{
+    RT_REQUIRE(sk && ptr, "null argument");
+    RT_TRY(require_pose(sk, "rt_skeleton_get_joints_device_ptr"));
+    *ptr = sk->joints.p;
     return RT_OK;
 }
 

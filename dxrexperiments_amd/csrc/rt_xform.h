@@ -50,3 +50,17 @@ RT_HOST_DEVICE static inline void invert3x4(const float m[12], float o[12])
     for (int k = 0; k < 12; k++)
         if (o[k] != o[k]) o[k] = __builtin_nanf("");
 }
+
+// C = A o B of two 3x4 affine matrices, grouped as include/dxr_amd.h "Posed skeletons" groups it (the statements of `compose`, rt_skeleton.hip):
+// what k_gather_transforms (rt_scene.hip) makes the transform of an attached instance with, T = W_joint o local
+RT_HOST_DEVICE static inline void compose3x4(const float A[12], const float B[12], float C[12])
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    for (int r = 0; r < 3; r++) {
+        const float a0 = A[4 * r], a1 = A[4 * r + 1], a2 = A[4 * r + 2], a3 = A[4 * r + 3];
+        for (int c = 0; c < 3; c++) C[4 * r + c] = (a0 * B[c] + a1 * B[4 + c]) + a2 * B[8 + c];
+        C[4 * r + 3] = ((a0 * B[3] + a1 * B[7]) + a2 * B[11]) + a3;
+    }
+}

@@ -130,6 +130,7 @@ namespace DXRFramework
         ~RtSkeleton() { rt_skeleton_destroy(mHandle); }
 
         rt_skeleton *getHandle() const { return mHandle; }
+        RtContext::SharedPtr getContext() const { return mContext; }
         void setPose(const float *trs, bool deviceMemory = false)
         {
             ThrowIfFailed(rt_skeleton_set_pose(mHandle, trs, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
@@ -291,6 +292,35 @@ namespace DXRFramework
             realize(context);
             ThrowIfFailed(rt_scene_update(mHandle));
         }
+        // EXTENSIONS (the reference's only statement of a transform is addModel, RtScene.h:30; what these write is the Transform member of the
+        // instance descriptor, Helpers/TopLevelASGenerator.cpp:344-362, applied by the generators' never-taken update path,
+        // Helpers/TopLevelASGenerator.h:144-163): transforms that come from the device (include/dxr_amd.h "Attached instances").
+        // setTransforms: count x 12 floats, 3x4 row-major, for instances first .. first + count - 1 of a scene that build(), update() or
+        // getHandle() has bound to a context; deviceMemory: the source is device memory, copied device to device on the context's stream --
+        // nothing is downloaded and nothing waits.  getTransforms: the floats the scene holds, pending or applied.  attach: the instances
+        // follow joints[k] of the skeleton -- at every update() or build() that applies a pose their transform is W_joint o locals[k]
+        // (locals == nullptr: W_joint itself), composed on the device: a frame is RtSkeleton::setTime, RtScene::update.  The scene keeps the
+        // skeleton alive.  detach: the instances keep the transform their last update() or build() gave them.
+        void setTransforms(uint32_t first, uint32_t count, const float *transforms3x4, bool deviceMemory = false)
+        {
+            requireRealized("RtScene::setTransforms", first, count);
+            ThrowIfFailed(rt_scene_set_instance_transforms_mem(mHandle, first, count, transforms3x4, deviceMemory ? RT_MEM_DEVICE : RT_MEM_HOST));
+        }
+        void getTransforms(uint32_t first, uint32_t count, float *transforms3x4) const
+        {
+            requireRealized("RtScene::getTransforms", first, count);
+            ThrowIfFailed(rt_scene_get_instance_transforms(mHandle, first, count, transforms3x4));
+        }
+        void attach(uint32_t first, uint32_t count, RtSkeleton::SharedPtr skeleton, const uint32_t *joints, const float *locals = nullptr)
+        {
+            realize(skeleton->getContext());
+            ThrowIfFailed(rt_scene_attach_instances(mHandle, first, count, skeleton->getHandle(), joints, locals));
+        }
+        void detach(uint32_t first, uint32_t count)
+        {
+            requireRealized("RtScene::detach", first, count);
+            ThrowIfFailed(rt_scene_detach_instances(mHandle, first, count));
+        }
         float getUpdateMilliseconds() const { float ms = 0; if (mHandle) rt_scene_update_ms(mHandle, &ms); return ms; }
         float getBuildMilliseconds() const { float ms = 0; if (mHandle) rt_scene_build_ms(mHandle, &ms); return ms; }
 
@@ -312,6 +342,11 @@ namespace DXRFramework
                 ThrowIfFailed(rt_scene_add_model(mHandle, mInstances[mRealized].model->getHandle(), x));
                 if (mInstances[mRealized].mask != 0xFF) ThrowIfFailed(rt_scene_set_instance_mask(mHandle, (uint32_t)mRealized, mInstances[mRealized].mask));
             }
+        }
+        void requireRealized(const char *who, uint32_t first, uint32_t count) const
+        {
+            if (!mHandle || size_t(first) + count > mRealized)
+                throw std::runtime_error(std::string(who) + ": instances beyond those the scene has bound to a context (build() or getHandle() first)");
         }
         std::vector<Node> mInstances;
         RtContext::SharedPtr mContext;

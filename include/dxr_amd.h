@@ -383,6 +383,69 @@ int rt_skeleton_get_palette_device_ptr(rt_skeleton *sk, void **ptr);
  * rendered first, the model is left CHANGED and every built scene that holds it STALE until rt_scene_update or rt_scene_build. */
 int rt_model_set_bones_from_skeleton(rt_model *m, rt_skeleton *sk);
 
+/* Attached instances -- EXTENSIONS: instance transforms that come from the device.  The reference's only statement of a transform is addModel
+ * (RtScene.h:30); what these calls write is the Transform member of the instance descriptor
+ * (libs/DXRFramework/Helpers/TopLevelASGenerator.cpp:344-362), and the path that applies it is the generators' never-taken update path
+ * (`updateOnly` of TopLevelASGenerator::Generate, Helpers/TopLevelASGenerator.h:144-163), as for rt_scene_update.
+ * DEVICE-SOURCED TRANSFORMS.  rt_scene_set_instance_transforms_mem with RT_MEM_HOST is exactly rt_scene_set_instance_transforms.  With
+ * RT_MEM_DEVICE the count x 12 floats are copied device to device, on the context's stream, into storage the scene owns -- for all of the
+ * scene's instances, reserved once (again only when rt_scene_add_model has made the list longer since; what it held then comes down to the host
+ * first) -- so the caller's array is free again once the stream has passed the call; a producer on another stream is the caller's to order, as
+ * for rt_model_set_vertices.  Nothing is downloaded and nothing waits.  Arguments, refusals, the flush of deferred frames and the STALE rule
+ * are exactly those of the host setter: a null argument is RT_ERR_INVALID_ARG, a range beyond the instances RT_ERR_STATE, count == 0 a
+ * no-op, on a scene that is not updatable the floats are only stored (the next rt_scene_build reads them); an unknown `mem` is
+ * RT_ERR_INVALID_ARG.  rt_scene_update and rt_scene_build fill those instances' slots of the listed transforms from the scene's device
+ * storage, with a kernel; host-set instances keep the upload they have; the host copy of the transforms follows in the final join that the
+ * update already has (the read-back of the record heads): no new synchronisation goes in front of the kernels.
+ * ATTACHMENTS.  An attached instance i with joint j of skeleton sk gets, at every rt_scene_update or rt_scene_build that applies a pose, the
+ * transform T_i = W_j o local_i, computed on the device with the product C = A o B exactly as "Posed skeletons" above states it: fp32
+ * throughout, every product and every sum one rounded operation, no contraction, always multiplied, for an identity too.  With local3x4 ==
+ * NULL, T_i = W_j bit for bit.  Values are taken as given: NaN, inf and zero scales are no errors, as for any instance transform.  From there
+ * on T_i is exactly a transform set by rt_scene_set_instance_transforms_mem(RT_MEM_DEVICE): the identity test on the composed floats, the
+ * inverse, the world box, the TLAS; after the update the scene is, array for array, the scene a fresh rt_scene_build gives for the same
+ * instance list with T_i passed to rt_scene_add_model (DESIGN.md "update == build, with attachments").  A skeleton of roots only, with a
+ * clip, is keyframed rigid animation of instances: a frame is rt_skeleton_set_time, rt_scene_update.
+ * Attaching stores the binding; `joints` and `local3x4` are copied to the device once (the call synchronises the stream, as
+ * rt_skeleton_create does).  On an updatable scene it marks the instances pending and the scene STALE, as a transform setter does; on a scene
+ * that is not updatable the next build reads it.  Attaching changes no stored transform: rt_scene_get_instance_transforms returns the old floats
+ * until an update or build has applied a pose, and the composed ones afterwards.  Attaching again replaces the binding.
+ * Posing a skeleton touches no model and no scene: a built scene stays built and traceable in the state of its last update.  The skeleton
+ * counts its poses, and rt_scene_update treats every attached instance whose skeleton has been posed since the scene last applied it as
+ * pending -- such an update is no longer the "nothing pending" no-op -- and applies the pose together with pending transforms, masks and
+ * changed models, in one call, with one bump of the generation, after the frames a deferred pipeline still holds.  An update or build with
+ * an attachment to a skeleton that has no pose yet is RT_ERR_STATE (the message names rt_skeleton_set_pose) and everything pending is kept, as
+ * when no instance is visible.  A transform setter of either kind, host or _mem, whose range holds an attached instance is RT_ERR_STATE (the
+ * message names the instance and rt_scene_detach_instances) and nothing changes.  Detaching keeps the transform that the last update or build
+ * gave the instance and marks nothing; detaching an instance that is not attached is a no-op.
+ * rt_scene_attach_instances refuses, and nothing changes when a call refuses: a null argument (s, sk, joints) is RT_ERR_INVALID_ARG; so is
+ * a joint >= n_joints (the message names the entry and both numbers); a range beyond the instances is RT_ERR_STATE; so is a skeleton of another
+ * context.  count == 0 is a no-op.
+ * Lifetime: the scene retains an attached skeleton as it retains its models, until the scene itself goes; rt_skeleton_destroy drops the
+ * caller's reference, and the attached instances then simply keep their last transform.  Several scenes, and several instances, may attach to
+ * one skeleton, each with its own record of the pose it last applied. */
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): rt_scene_set_instance_transforms from
+ * host or device memory */
+int rt_scene_set_instance_transforms_mem(rt_scene *s, uint32_t first, uint32_t count, const float *transforms3x4 /* count x 12 */,
+                                         uint32_t mem /* RT_MEM_HOST | RT_MEM_DEVICE */);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): the twelve floats the scene holds for
+ * each of instances first .. first + count - 1, pending or applied, into a host array.  Device-held ones are downloaded on demand: only then
+ * does the call synchronise. */
+int rt_scene_get_instance_transforms(const rt_scene *s, uint32_t first, uint32_t count, float *transforms3x4 /* host, count x 12 */);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): attaches instances first .. first +
+ * count - 1 to joints[k] of `sk`, with local3x4[k] (NULL: none) as above */
+int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_skeleton *sk,
+                              const uint32_t *joints /* count */, const float *local3x4 /* count x 12, or NULL */);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): lets instances first .. first + count
+ * - 1 go; a range beyond the instances is RT_ERR_STATE */
+int rt_scene_detach_instances(rt_scene *s, uint32_t first, uint32_t count);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): *sk = the skeleton instance `instance`
+ * is attached to (NULL: none) and *joint its joint; either pointer may be NULL; an instance out of range is RT_ERR_STATE */
+int rt_scene_get_instance_attachment(const rt_scene *s, uint32_t instance, rt_skeleton **sk /* NULL: none */, uint32_t *joint);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above; RtModel.cpp:26 and
+ * BottomLevelASGenerator.h:136-176 as for the skeleton's other calls): W_j where it lives, n_joints x 12 floats of device memory that every
+ * later pose overwrites on the context's stream, as rt_skeleton_get_palette_device_ptr; RT_ERR_STATE before the first pose */
+int rt_skeleton_get_joints_device_ptr(rt_skeleton *sk, void **ptr);
+
 /* ---- raw TraceRay over a batch (HLSL TraceRay semantics, used by tests and
  *      the traversal benchmark; ProgressiveRaytracing.hlsl:34,53,
  *      RaytracingCommon.hlsli:94) ------------------------------------------- */
