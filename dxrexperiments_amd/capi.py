@@ -93,6 +93,10 @@ SIGNATURES = {
     "rt_skeleton_add_clip": (_i, [_p, _u32, _p, _p, _pu]),
     "rt_skeleton_clear_clips": (_i, [_p]),
     "rt_skeleton_set_time": (_i, [_p, _u32, _f]),
+    "rt_skeleton_add_mask": (_i, [_p, _p, _pu]),
+    "rt_skeleton_clear_masks": (_i, [_p]),
+    "rt_skeleton_get_num_masks": (_i, [_p, _pu]),
+    "rt_skeleton_set_blend": (_i, [_p, _u32, _p]),
     "rt_skeleton_read_pose": (_i, [_p, _p]),
     "rt_skeleton_read_joints": (_i, [_p, _p]),
     "rt_skeleton_read_palette": (_i, [_p, _p]),
@@ -579,6 +583,44 @@ class Skeleton:
     def set_time(self, clip, t):
         """samples the clip at t and poses the skeleton with the result, all on the device"""
         _check(lib().rt_skeleton_set_time(self.h, clip, float(t)))
+
+    def add_mask(self, weights):
+        """weights float32[n_joints], one per joint, for the layers of set_blend; returns the mask's id"""
+        w = _f32(weights, (-1,))
+        if w.shape[0] != self.n_joints:
+            raise RtError(-1, "add_mask: %d weights for a skeleton of %d joints" % (w.shape[0], self.n_joints))
+        mask = C.c_uint32()
+        _check(lib().rt_skeleton_add_mask(self.h, _ptr(w), C.byref(mask)))
+        return mask.value
+
+    def clear_masks(self):
+        _check(lib().rt_skeleton_clear_masks(self.h))
+
+    def n_masks(self):
+        n = C.c_uint32()
+        _check(lib().rt_skeleton_get_num_masks(self.h, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def layers(layers):
+        """rtypes.SKELETON_LAYER[n] from a list of (clip, time, weight, mask=None, mode="blend") tuples or dicts of those names.  clip None
+        or "current" is the pose the skeleton holds (layer 0 only); mode "blend" | "additive", or its number."""
+        modes = {"blend": T.LAYER_BLEND, "additive": T.LAYER_ADDITIVE}
+        out = np.zeros(len(layers), T.SKELETON_LAYER)
+        for k, layer in enumerate(layers):
+            if isinstance(layer, dict):
+                layer = (layer["clip"], layer.get("time", 0.0), layer.get("weight", 1.0), layer.get("mask"), layer.get("mode", "blend"))
+            clip, time, weight, mask, mode = (tuple(layer) + (0.0, 1.0, None, "blend")[len(layer) - 1:])[:5]
+            out[k] = (T.SKELETON_CURRENT_POSE if clip is None or clip == "current" else clip, time, weight,
+                      T.SKELETON_NO_MASK if mask is None else mask, modes.get(mode, mode))
+        return out
+
+    def set_blend(self, layers):
+        """blends and layers clips on the device and poses the skeleton with the result: a list of (clip, time, weight, mask=None,
+        mode="blend") tuples or dicts (Skeleton.layers), or an array of rtypes.SKELETON_LAYER"""
+        a = layers if isinstance(layers, np.ndarray) and layers.dtype == T.SKELETON_LAYER else self.layers(layers)
+        a = np.ascontiguousarray(a)
+        _check(lib().rt_skeleton_set_blend(self.h, a.shape[0], _ptr(a)))
 
     def _read(self, fn, width):
         out = np.empty((self.n_joints, width), np.float32)

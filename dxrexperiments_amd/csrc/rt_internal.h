@@ -373,6 +373,7 @@ struct rt_skeleton {
     DevBuf palette;              // float[n_joints][12]: M_j = W_j o inverse_bind_j, what rt_model_set_bones_from_skeleton hands to the skin kernel
     bool posed = false;          // a pose has been set or sampled: joints and palette hold something
     std::vector<SkeletonClip> clips;
+    std::vector<DevBuf> masks;   // rt_skeleton_add_mask: float[n_joints] each, one weight per joint of a blend layer (rt_skeleton_set_blend)
     ~rt_skeleton();              // (rt_skeleton.hip) selects the device and joins the stream before the buffers go
 };
 

@@ -1,12 +1,14 @@
-// rt_skeleton.h -- the host side of a skeleton (rt_skeleton_create, rt_skeleton_add_clip, rt_skeleton_set_time): validation of the caller's
-// arrays, the level table k_skeleton_pose walks, and the segment search of a clip.  Host code without HIP, as rt_skin.h is:
-// tests/cpp/skeleton_sanitized.cpp compiles it alone.
+// rt_skeleton.h -- the host side of a skeleton (rt_skeleton_create, rt_skeleton_add_clip, rt_skeleton_set_time, rt_skeleton_set_blend):
+// validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip and the check of a layer list.  Host
+// code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp and tests/cpp/skeleton_blend_sanitized.cpp compile it alone.
 #pragma once
 
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
+
+#include "../../include/dxr_amd_types.h"     // rt_skeleton_layer and its constants
 
 #define RT_SKELETON_MAX_JOINTS 65536u    // the skin's bone limit (RT_SKIN_MAX_BONES): a joint is a bone, and fits 16 bits
 #define RT_SKELETON_POSE_FLOATS 10u      // a joint of a pose: tx ty tz  qx qy qz qw  sx sy sz
@@ -100,4 +102,42 @@ static inline void rt_skeleton_segment(uint32_t n_keys, const float *times, floa
     const float num = t - times[lo], den = times[lo + 1u] - times[lo];
     *i_out = lo;
     *a_out = num / den;
+}
+
+// 0: the layers describe a blend of a skeleton with n_clips clips and n_masks masks that is posed or not.  Else what is wrong, and
+// *bad_layer names the first such layer (0 for 1 and 2): 1 a null array, 2 n_layers outside 1 .. RT_SKELETON_MAX_LAYERS, 3 an unknown mode,
+// 4 an additive layer 0, 5 RT_SKELETON_CURRENT_POSE on a layer other than 0, 6 a NaN time on a layer that samples, 7 an unknown clip,
+// 8 an unknown mask (the base layer's mask is not read, and not checked), 9 RT_SKELETON_CURRENT_POSE on a skeleton without a pose.  1 .. 6
+// are the caller's arguments (RT_ERR_INVALID_ARG), 7 .. 9 the skeleton's state (RT_ERR_STATE); every layer is held to 3 .. 6 before any
+// layer is held to 7 .. 9.  Reads n_layers entries of `layers`, and nothing when it says 1 or 2.
+static inline int rt_skeleton_validate_layers(uint32_t n_layers, const rt_skeleton_layer *layers, uint32_t n_clips, uint32_t n_masks, bool posed,
+                                              uint32_t *bad_layer)
+{
+    if (bad_layer) *bad_layer = 0u;
+    if (!layers) return 1;
+    if (n_layers < 1u || n_layers > RT_SKELETON_MAX_LAYERS) return 2;
+    for (uint32_t k = 0; k < n_layers; k++) {
+        const rt_skeleton_layer &l = layers[k];
+        int what = 0;
+        if (l.mode != RT_LAYER_BLEND && l.mode != RT_LAYER_ADDITIVE) what = 3;
+        else if (k == 0u && l.mode != RT_LAYER_BLEND) what = 4;
+        else if (k > 0u && l.clip == RT_SKELETON_CURRENT_POSE) what = 5;
+        else if (l.clip != RT_SKELETON_CURRENT_POSE && isnan(l.time)) what = 6;
+        if (what) {
+            if (bad_layer) *bad_layer = k;
+            return what;
+        }
+    }
+    for (uint32_t k = 0; k < n_layers; k++) {
+        const rt_skeleton_layer &l = layers[k];
+        int what = 0;
+        if (l.clip == RT_SKELETON_CURRENT_POSE) what = posed ? 0 : 9;
+        else if (l.clip >= n_clips) what = 7;
+        if (!what && k > 0u && l.mask != RT_SKELETON_NO_MASK && l.mask >= n_masks) what = 8;
+        if (what) {
+            if (bad_layer) *bad_layer = k;
+            return what;
+        }
+    }
+    return 0;
 }

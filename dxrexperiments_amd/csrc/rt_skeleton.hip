@@ -99,16 +99,25 @@ __global__ void __launch_bounds__(RT_SKELETON_BLOCK) k_skeleton_pose(const float
     }
 }
 
-// One lane per joint: the local pose between two keys of a clip.  A key is component major (float[10][n_joints]): at every one of the twenty
-// loads the lanes of a wave read 64 consecutive floats.  Translation and scale A + (a * (B - A)); the quaternion the same after B has been
-// turned onto A's side (d < 0; a NaN d turns nothing), then normalised by the rule of rt_model_recompute_normals with (0, 0, 0, 1) where
-// that has no answer.  The pose is written as rt_skeleton_set_pose takes it, ten floats per joint.
-__global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict__ key_a, const float *__restrict__ key_b, uint32_t n_joints, float a,
-                                                         float *__restrict__ pose)
+// The quaternion q[0 .. 3] = (x, y, z, w) normalised by the rule of rt_model_recompute_normals, with (0, 0, 0, 1) where that has no answer
+RT_DEV void unit_or_identity(float q[4])
 {
-    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= n_joints) return;
-    float A[10], B[10], o[10];
+    const float n = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+    if (n > 0.0f && n < __uint_as_float(0x7f800000u)) {
+        const float inv = rsqrt_ieee(n);
+#pragma unroll
+        for (int c = 0; c < 4; c++) q[c] = q[c] * inv;
+    } else {
+        q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f; q[3] = 1.0f;
+    }
+}
+
+// The local pose of joint j between two keys of a clip.  A key is component major (float[10][n_joints]): at every one of the twenty loads the
+// lanes of a wave read 64 consecutive floats.  Translation and scale A + (a * (B - A)); the quaternion the same after B has been turned onto
+// A's side (d < 0; a NaN d turns nothing), then normalised.
+RT_DEV void sample_joint(const float *__restrict__ key_a, const float *__restrict__ key_b, uint32_t n_joints, uint32_t j, float a, float o[10])
+{
+    float A[10], B[10];
 #pragma unroll
     for (int c = 0; c < 10; c++) {
         A[c] = key_a[(size_t)c * n_joints + j];
@@ -121,16 +130,96 @@ __global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict
     }
 #pragma unroll
     for (int c = 0; c < 10; c++) o[c] = A[c] + a * (B[c] - A[c]);
-    const float n = ((o[3] * o[3] + o[4] * o[4]) + o[5] * o[5]) + o[6] * o[6];
-    if (n > 0.0f && n < __uint_as_float(0x7f800000u)) {
-        const float inv = rsqrt_ieee(n);
-#pragma unroll
-        for (int c = 3; c < 7; c++) o[c] = o[c] * inv;
-    } else {
-        o[3] = 0.0f; o[4] = 0.0f; o[5] = 0.0f; o[6] = 1.0f;
-    }
+    unit_or_identity(o + 3);
+}
+
+// One lane per joint: the local pose between two keys of a clip, written as rt_skeleton_set_pose takes it, ten floats per joint.
+__global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict__ key_a, const float *__restrict__ key_b, uint32_t n_joints, float a,
+                                                         float *__restrict__ pose)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_joints) return;
+    float o[10];
+    sample_joint(key_a, key_b, n_joints, j, a, o);
 #pragma unroll
     for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = o[c];
+}
+
+// A layer of a blend as the kernel reads it, and the table of them that travels by value as the kernel's argument: wave uniform, so it comes
+// through scalar loads and the branch on the mode is a scalar branch.
+struct BlendLayer {
+    const float *key_a, *key_b;          // the two keys about the layer's time (layer 0: nullptr = the pose the skeleton holds) ...
+    const float *ref_a, *ref_b;          // ... and the clip's first two keys: the reference pose of an additive layer is sampled from them at a = 0
+    const float *mask;                   // float[n_joints], or nullptr: none
+    float a, weight;
+    uint32_t mode, pad;
+};
+struct BlendTable {
+    BlendLayer layer[RT_SKELETON_MAX_LAYERS];
+};
+
+// the Hamilton product r = p (x) q of quaternions (x, y, z, w), grouped as the header groups it
+RT_DEV void hamilton(const float p[4], const float q[4], float r[4])
+{
+    r[0] = ((p[3] * q[0] + p[0] * q[3]) + p[1] * q[2]) - p[2] * q[1];
+    r[1] = ((p[3] * q[1] - p[0] * q[2]) + p[1] * q[3]) + p[2] * q[0];
+    r[2] = ((p[3] * q[2] + p[0] * q[1]) - p[1] * q[0]) + p[2] * q[3];
+    r[3] = ((p[3] * q[3] - p[0] * q[0]) - p[1] * q[1]) - p[2] * q[2];
+}
+
+// One lane per joint: the layers of a blend accumulated into the local pose (include/dxr_amd.h "Posed skeletons", blending).  P starts as
+// layer 0's sample, or as the stored pose, which this lane alone reads and overwrites; every later layer is sampled as k_skeleton_sample
+// samples and blended or added with w = weight (* mask[j]).  The loop over the layers and the branch on a layer's mode are uniform; P, S and
+// R live in registers, and there is no LDS.  `pose` is read and written in place: not __restrict__.
+__global__ void __launch_bounds__(256) k_skeleton_blend(const BlendTable table, uint32_t n_layers, uint32_t n_joints, float *pose)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_joints) return;
+    float P[10];
+    if (table.layer[0].key_a) sample_joint(table.layer[0].key_a, table.layer[0].key_b, n_joints, j, table.layer[0].a, P);
+    else {
+#pragma unroll
+        for (int c = 0; c < 10; c++) P[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c];
+    }
+    for (uint32_t k = 1; k < n_layers; k++) {
+        const BlendLayer &l = table.layer[k];
+        float S[10];
+        sample_joint(l.key_a, l.key_b, n_joints, j, l.a, S);
+        const float w = l.mask ? l.weight * l.mask[j] : l.weight;
+        if (l.mode == RT_LAYER_ADDITIVE) {
+            float R[10], cr[4], D[4], E[4], q[4];
+            sample_joint(l.ref_a, l.ref_b, n_joints, j, 0.0f, R);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                P[c] = P[c] + w * (S[c] - R[c]);
+                P[7 + c] = P[7 + c] + w * (S[7 + c] - R[7 + c]);
+            }
+            cr[0] = -R[3]; cr[1] = -R[4]; cr[2] = -R[5]; cr[3] = R[6];
+            hamilton(cr, S + 3, D);
+            if (D[3] < 0.0f) {
+#pragma unroll
+                for (int c = 0; c < 4; c++) D[c] = -D[c];
+            }
+            E[0] = w * D[0]; E[1] = w * D[1]; E[2] = w * D[2];
+            E[3] = 1.0f + w * (D[3] - 1.0f);
+            unit_or_identity(E);
+            hamilton(P + 3, E, q);
+            unit_or_identity(q);
+#pragma unroll
+            for (int c = 0; c < 4; c++) P[3 + c] = q[c];
+        } else {
+            const float d = ((P[3] * S[3] + P[4] * S[4]) + P[5] * S[5]) + P[6] * S[6];
+            if (d < 0.0f) {
+#pragma unroll
+                for (int c = 3; c < 7; c++) S[c] = -S[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 10; c++) P[c] = P[c] + w * (S[c] - P[c]);
+            unit_or_identity(P + 3);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = P[c];
 }
 
 // sk->pose holds a local pose: W and the palette from it, queued on the context's stream
@@ -316,6 +405,85 @@ int rt_skeleton_set_time(rt_skeleton *sk, uint32_t clip, float t)
     const float *key_b = n_keys == 1u ? key_a : key_a + per_key;
     RT_TRY(rt_use_device(ctx));
     k_skeleton_sample<<<(sk->n_joints + 255u) / 256u, 256, 0, ctx->stream>>>(key_a, key_b, sk->n_joints, a, sk->pose.as<float>());
+    HIP_TRY(hipGetLastError());
+    return pose_skeleton(sk);
+}
+
+int rt_skeleton_add_mask(rt_skeleton *sk, const float *weights, uint32_t *mask_out)
+{
+    RT_REQUIRE(sk && weights, "null argument");
+    rt_context *ctx = sk->ctx;
+    DevBuf mask;
+    RT_TRY(rt_use_device(ctx));
+    RT_TRY(rt_upload(ctx, mask, weights, sizeof(float) * (size_t)sk->n_joints));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the caller's array is its own again)
+    sk->masks.push_back(std::move(mask));               // (earlier masks keep their ids and their buffers)
+    if (mask_out) *mask_out = (uint32_t)sk->masks.size() - 1u;
+    return RT_OK;
+}
+
+int rt_skeleton_clear_masks(rt_skeleton *sk)
+{
+    RT_REQUIRE(sk, "null skeleton");
+    if (sk->masks.empty()) return RT_OK;
+    RT_TRY(rt_use_device(sk->ctx));
+    HIP_TRY(hipStreamSynchronize(sk->ctx->stream));     // (a blend kernel that reads a mask may still be queued)
+    sk->masks.clear();
+    return RT_OK;
+}
+
+int rt_skeleton_get_num_masks(const rt_skeleton *sk, uint32_t *n)
+{
+    RT_REQUIRE(sk && n, "null argument");
+    *n = (uint32_t)sk->masks.size();
+    return RT_OK;
+}
+
+int rt_skeleton_set_blend(rt_skeleton *sk, uint32_t n_layers, const rt_skeleton_layer *layers)
+{
+    RT_REQUIRE(sk && layers, "null argument");
+    const uint32_t n_clips = (uint32_t)sk->clips.size(), n_masks = (uint32_t)sk->masks.size();
+    uint32_t bad = 0;
+    const int what = rt_skeleton_validate_layers(n_layers, layers, n_clips, n_masks, sk->posed, &bad);
+    switch (what) {
+    case 0: break;
+    case 1: rt_set_error("rt_skeleton_set_blend: null argument"); return RT_ERR_INVALID_ARG;
+    case 2: rt_set_error("rt_skeleton_set_blend: %u layers: 1 .. %u are supported", n_layers, RT_SKELETON_MAX_LAYERS); return RT_ERR_INVALID_ARG;
+    case 3: rt_set_error("rt_skeleton_set_blend: layer %u has mode %u: RT_LAYER_BLEND (0) or RT_LAYER_ADDITIVE (1)", bad, layers[bad].mode); return RT_ERR_INVALID_ARG;
+    case 4: rt_set_error("rt_skeleton_set_blend: layer 0 is additive: the base layer is RT_LAYER_BLEND"); return RT_ERR_INVALID_ARG;
+    case 5: rt_set_error("rt_skeleton_set_blend: layer %u names RT_SKELETON_CURRENT_POSE: only layer 0 may", bad); return RT_ERR_INVALID_ARG;
+    case 6: rt_set_error("rt_skeleton_set_blend: the time of layer %u is NaN", bad); return RT_ERR_INVALID_ARG;
+    case 7:
+        rt_set_error("rt_skeleton_set_blend: layer %u names clip %u: the skeleton has %u (rt_skeleton_add_clip adds one)", bad, layers[bad].clip, n_clips);
+        return RT_ERR_STATE;
+    case 8:
+        rt_set_error("rt_skeleton_set_blend: layer %u names mask %u: the skeleton has %u (rt_skeleton_add_mask adds one)", bad, layers[bad].mask, n_masks);
+        return RT_ERR_STATE;
+    default:
+        rt_set_error("rt_skeleton_set_blend: layer %u names RT_SKELETON_CURRENT_POSE: the skeleton has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", bad);
+        return RT_ERR_STATE;
+    }
+    rt_context *ctx = sk->ctx;
+    const size_t per_key = RT_SKELETON_POSE_FLOATS * (size_t)sk->n_joints;
+    BlendTable table = {};
+    for (uint32_t k = 0; k < n_layers; k++) {
+        const rt_skeleton_layer &l = layers[k];
+        BlendLayer &b = table.layer[k];
+        b.weight = l.weight;
+        b.mode = l.mode;
+        if (l.clip == RT_SKELETON_CURRENT_POSE) continue;            // (layer 0 only: key_a stays null, the kernel starts from sk->pose)
+        const SkeletonClip &c = sk->clips[l.clip];
+        const uint32_t n_keys = (uint32_t)c.times.size();
+        uint32_t i = 0;
+        rt_skeleton_segment(n_keys, c.times.data(), l.time, &i, &b.a);
+        b.ref_a = c.keys.as<float>();
+        b.ref_b = n_keys == 1u ? b.ref_a : b.ref_a + per_key;
+        b.key_a = b.ref_a + per_key * i;
+        b.key_b = n_keys == 1u ? b.key_a : b.key_a + per_key;
+        if (k > 0u && l.mask != RT_SKELETON_NO_MASK) b.mask = sk->masks[l.mask].as<float>();
+    }
+    RT_TRY(rt_use_device(ctx));
+    k_skeleton_blend<<<(sk->n_joints + 255u) / 256u, 256, 0, ctx->stream>>>(table, n_layers, sk->n_joints, sk->pose.as<float>());
     HIP_TRY(hipGetLastError());
     return pose_skeleton(sk);
 }

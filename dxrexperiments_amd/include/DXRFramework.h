@@ -142,6 +142,17 @@ namespace DXRFramework
             return clip;
         }
         void setTime(uint32_t clip, float t) { ThrowIfFailed(rt_skeleton_set_time(mHandle, clip, t)); }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): clips blended and layered on the device.  addMask:
+        // numJoints weights, one per joint, returns the mask's id; setBlend: 1 .. RT_SKELETON_MAX_LAYERS layers (rt_skeleton_layer: clip,
+        // time, weight, mask, mode), sampled, accumulated and posed on the device, nothing is uploaded
+        uint32_t addMask(const float *weights)
+        {
+            uint32_t mask = 0;
+            ThrowIfFailed(rt_skeleton_add_mask(mHandle, weights, &mask));
+            return mask;
+        }
+        void clearMasks() { ThrowIfFailed(rt_skeleton_clear_masks(mHandle)); }
+        void setBlend(const rt_skeleton_layer *layers, uint32_t numLayers) { ThrowIfFailed(rt_skeleton_set_blend(mHandle, numLayers, layers)); }
 
     private:
         RtSkeleton(RtContext::SharedPtr ctx, rt_skeleton *h) : mContext(ctx), mHandle(h) {}

@@ -32,6 +32,14 @@ MATERIAL_PARAMS = np.dtype([
 
 BVH_NODE = np.dtype([("bmin", "<f4", 3), ("left", "<u4"), ("bmax", "<f4", 3), ("right", "<u4")])
 
+# rt_skeleton_layer (include/dxr_amd_types.h): one layer of rt_skeleton_set_blend
+SKELETON_LAYER = np.dtype([("clip", "<u4"), ("time", "<f4"), ("weight", "<f4"), ("mask", "<u4"), ("mode", "<u4")])
+SKELETON_MAX_LAYERS = 8
+SKELETON_CURRENT_POSE = 0xFFFFFFFF
+SKELETON_NO_MASK = 0xFFFFFFFF
+LAYER_BLEND, LAYER_ADDITIVE = 0, 1
+
+assert SKELETON_LAYER.itemsize == 20
 assert VERTEX.itemsize == 24 and CAMERA_PARAMS.itemsize == 80 and DEBUG_OPTIONS.itemsize == 44
 assert PER_FRAME_CONSTANTS.itemsize == 188 and MATERIAL_PARAMS.itemsize == 64 and BVH_NODE.itemsize == 32
 

@@ -335,6 +335,30 @@ int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */
  *           Aw Bw; if d < 0 every component of B is negated (the shortest path; a NaN d negates nothing); q_c = A_c + (a * (B_c - A_c));
  *           n = ((qx qx + qy qy) + qz qz) + qw qw; q = q * (1 / sqrt(n)) if 0 < n < inf, else (0, 0, 0, 1): the rule of
  *           rt_model_recompute_normals.  No slerp.  The result is the local pose, and it is posed as by rt_skeleton_set_pose.
+ *   blending (rt_skeleton_set_blend): an ordered list of 1 .. RT_SKELETON_MAX_LAYERS (8) LAYERS (rt_skeleton_layer, dxr_amd_types.h), each a
+ *           clip, a time, a weight, a MASK (one float per joint, taken as given; RT_SKELETON_NO_MASK: none) and a mode.  fp32 throughout,
+ *           every product and every sum one rounded operation, no contraction, values taken as given: a weight is not clamped, NaN and inf
+ *           are no errors.  S_k is the pose that layer k's clip gives at its time by the sampling rule above, whole: the segment search on
+ *           the host, the lerp, the shortest-path flip, the normalisation with its (0, 0, 0, 1) fallback.  The accumulated pose P, per joint j:
+ *           layer 0 is the base: P = S_0 bit for bit; with clip == RT_SKELETON_CURRENT_POSE, P is the pose the skeleton holds as it stands
+ *           (what rt_skeleton_read_pose returns; it is read and overwritten by the same lane, in place).  The base layer's weight and mask
+ *           are not read, and its mode must be RT_LAYER_BLEND.
+ *           layers k >= 1: w = weight_k without a mask, else w = weight_k * mask_k[j], one product.
+ *           RT_LAYER_BLEND: every translation and scale component P_c = P_c + (w * (S_c - P_c)).  The quaternion:
+ *           d = ((Px Sx + Py Sy) + Pz Sz) + Pw Sw; if d < 0 every component of S is negated (a NaN d negates nothing);
+ *           q_c = P_c + (w * (S_c - P_c)); then normalised by the rule above: n = ((qx qx + qy qy) + qz qz) + qw qw,
+ *           q * (1 / sqrt(n)) if 0 < n < inf, else (0, 0, 0, 1).
+ *           RT_LAYER_ADDITIVE: the reference pose R of an additive clip is what rt_skeleton_set_time(clip, -inf) gives: the sampling rule
+ *           with (i, a) = (0, 0), normalisation included.  Translation and scale: P_c = P_c + (w * (S_c - R_c)).  The rotation, in the
+ *           joint's local frame: D = conj(R_q) (x) S_q; if D_w < 0 every component of D is negated (a NaN negates nothing);
+ *           E_xyz = w * D_xyz and E_w = 1 + (w * (D_w - 1)); E normalised by the rule; P_q = P_q (x) E; P_q normalised by the rule.
+ *           conj(q) = (-x, -y, -z, w), and the Hamilton product p (x) q is grouped
+ *             x = ((pw qx + px qw) + py qz) - pz qy      y = ((pw qy - px qz) + py qw) + pz qx
+ *             z = ((pw qz + px qy) - py qx) + pz qw      w = ((pw qw - px qx) - py qy) - pz qz
+ *           The result is written as the skeleton's local pose, ten floats per joint, and posed exactly as rt_skeleton_set_pose poses: the
+ *           pose is counted once, and rt_skeleton_read_pose, the palette, the joints and attached instances all follow.  A blend is
+ *           stateless, as rt_skeleton_set_time is: a call leaves nothing behind but the pose.  No slerp, no per-channel key times, no
+ *           state machine: the caller moves the weights.
  * Validation is done on the host, and nothing changes when a call refuses.  Setting a pose touches no model and no scene.
  * rt_skeleton_create: a null argument is RT_ERR_INVALID_ARG; so is n_joints outside 1 .. 65536 (the skin's bone limit), and a parent that is
  * neither -1 nor < j -- parents come before children -- (the message names the joint).  inverse_bind: n_joints x 12, 3x4 row-major, as
@@ -365,6 +389,25 @@ int rt_skeleton_clear_clips(rt_skeleton *sk);
  * by the definition above: two kernels on the context's stream, nothing is uploaded and nothing waits.  RT_ERR_INVALID_ARG for a NaN t
  * (-inf and +inf are the first and the last key), RT_ERR_STATE for an unknown clip. */
 int rt_skeleton_set_time(rt_skeleton *sk, uint32_t clip, float t);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): a mask for the layers of a blend, one float per joint, taken as
+ * given.  The array is copied and stored on the device (the call synchronises the stream, as rt_skeleton_add_clip does).  *mask_out (may be
+ * NULL) is the mask's id; adding masks keeps earlier mask ids valid.  A null sk or weights is RT_ERR_INVALID_ARG. */
+int rt_skeleton_add_mask(rt_skeleton *sk, const float *weights /* n_joints, host */, uint32_t *mask_out);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): removes every mask, after joining the context's stream (a blend
+ * already queued reads live masks); ids start at 0 again.  The pose stays. */
+int rt_skeleton_clear_masks(rt_skeleton *sk);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the masks the skeleton holds; a null argument is
+ * RT_ERR_INVALID_ARG */
+int rt_skeleton_get_num_masks(const rt_skeleton *sk, uint32_t *n);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): blends and layers clips by the definition above ("blending") and
+ * poses the skeleton with the result: two kernels on the context's stream, the blend and the pose; nothing is uploaded and nothing waits --
+ * the segment, `a`, the weights and the modes of the layers travel as kernel arguments.  Validation runs on the host before anything is
+ * queued, and nothing changes when the call refuses; the message names the layer.  RT_ERR_INVALID_ARG: a null argument, n_layers outside
+ * 1 .. 8, a NaN time on a layer that samples (-inf and +inf are the first and the last key), an unknown mode, an additive layer 0,
+ * RT_SKELETON_CURRENT_POSE on a layer other than 0.  RT_ERR_STATE: an unknown clip or mask id (the message names the layer and how many
+ * there are), RT_SKELETON_CURRENT_POSE before the first pose (the message names rt_skeleton_set_pose).  Every layer is held to the first
+ * group before any is held to the second.  One layer without a mask is rt_skeleton_set_time, bit for bit. */
+int rt_skeleton_set_blend(rt_skeleton *sk, uint32_t n_layers, const rt_skeleton_layer *layers /* n_layers, host */);
 /* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local pose last set or sampled.  This and the calls below
  * that return what a pose made are RT_ERR_STATE before the first pose (the message names rt_skeleton_set_pose); the reads synchronise. */
 int rt_skeleton_read_pose(rt_skeleton *sk, float *trs /* n_joints x 10 */);

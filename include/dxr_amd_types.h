@@ -180,6 +180,20 @@ typedef struct rt_stage_walk {
     uint64_t node_lines;         /* the node part of `lines`: distinct 64-B node lines per wave step, summed             */
 } rt_stage_walk;
 
+/* One layer of a pose blend (rt_skeleton_set_blend; include/dxr_amd.h "Posed skeletons", "blending"). */
+#define RT_SKELETON_MAX_LAYERS    8u
+#define RT_SKELETON_CURRENT_POSE  0xFFFFFFFFu  /* layer 0's `clip`: the pose the skeleton holds now */
+#define RT_SKELETON_NO_MASK       0xFFFFFFFFu
+#define RT_LAYER_BLEND            0u
+#define RT_LAYER_ADDITIVE         1u
+typedef struct rt_skeleton_layer {
+    uint32_t clip;               /* a clip id; layer 0 only: RT_SKELETON_CURRENT_POSE                         */
+    float    time;               /* sampled exactly as rt_skeleton_set_time samples; ignored for RT_SKELETON_CURRENT_POSE */
+    float    weight;             /* taken as given: not clamped, NaN and inf are no errors                   */
+    uint32_t mask;               /* RT_SKELETON_NO_MASK or a mask id (rt_skeleton_add_mask)                  */
+    uint32_t mode;               /* RT_LAYER_BLEND | RT_LAYER_ADDITIVE                                       */
+} rt_skeleton_layer;
+
 /* Status codes returned by every export. */
 #define RT_OK                 0
 #define RT_ERR_INVALID_ARG   -1
@@ -200,6 +214,7 @@ static_assert(sizeof(rt_debug_options) == 44, "DebugOptions is 44 B");
 static_assert(sizeof(rt_per_frame_constants) == 188, "PerFrameConstants is 188 B");
 static_assert(sizeof(rt_material_params) == 64, "MaterialParams is 64 B");
 static_assert(sizeof(rt_bvh_node) == 32, "BVH node is 32 B");
+static_assert(sizeof(rt_skeleton_layer) == 20, "a blend layer is 20 B");
 #endif
 
 #endif /* DXR_AMD_TYPES_H */

@@ -1,0 +1,270 @@
+"""CPU-only side of blended and layered clips (rt_skeleton_add_mask, rt_skeleton_clear_masks, rt_skeleton_get_num_masks,
+rt_skeleton_set_blend): the exports, their binding, the layer record and its numpy dtype, their citations and the header's statement of the
+definition, the C++ mirror and the example; null arguments refused without a device; the host's check of a layer list
+(dxrexperiments_amd/csrc/rt_skeleton.h: rt_skeleton_validate_layers) as a stand-alone CPU program under AddressSanitizer +
+UndefinedBehaviorSanitizer against its Python restatement; and the numpy restatement of the definition (tests/skeleton_blend_cases.py) against
+what it states, in float64.  (The GPU side: tests/test_gpu_skeleton_blend.py.)"""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+
+import skeleton_blend_cases as B
+import skeleton_cases as S
+from dxrexperiments_amd import rtypes as T
+
+ROOT = S.ROOT
+F = np.float32
+NEW = ("rt_skeleton_add_mask", "rt_skeleton_clear_masks", "rt_skeleton_get_num_masks", "rt_skeleton_set_blend")
+
+
+def test_exports_and_their_argument_types(capi):
+    u32, p, pu = C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)
+    want = {"rt_skeleton_add_mask": [p, p, pu], "rt_skeleton_clear_masks": [p], "rt_skeleton_get_num_masks": [p, pu], "rt_skeleton_set_blend": [p, u32, p]}
+    lib = capi.lib()
+    for name in NEW:
+        res, args = capi.SIGNATURES[name]
+        assert res is C.c_int and args == want[name], name
+        fn = getattr(lib, name)
+        assert fn.restype is C.c_int and list(fn.argtypes) == want[name], name
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
+    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
+    assert set(NEW) <= exported, set(NEW) - exported
+    for method in ("add_mask", "clear_masks", "n_masks", "set_blend", "layers"):
+        assert callable(getattr(capi.Skeleton, method)), method
+
+
+def test_the_layer_record_is_20_bytes(tmp_path, capi):
+    """sizeof(rt_skeleton_layer) == 20 with the members where the numpy dtype puts them, the constants are the header's, and
+    Skeleton.layers fills the record from tuples and dicts"""
+    src = tmp_path / "layer.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "dxr_amd_types.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %u %u %u %u %u\\n", '
+                   "sizeof(rt_skeleton_layer), offsetof(rt_skeleton_layer, clip), offsetof(rt_skeleton_layer, time), offsetof(rt_skeleton_layer, weight), "
+                   "offsetof(rt_skeleton_layer, mask), offsetof(rt_skeleton_layer, mode), RT_SKELETON_MAX_LAYERS, RT_SKELETON_CURRENT_POSE, RT_SKELETON_NO_MASK, "
+                   "RT_LAYER_BLEND, RT_LAYER_ADDITIVE); return 0; }\n")
+    exe = tmp_path / "layer"
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    got = [int(x) for x in subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout.split()]
+    d = T.SKELETON_LAYER
+    assert d.itemsize == 20 and got[0] == 20
+    assert got[1:6] == [d.fields[name][1] for name in ("clip", "time", "weight", "mask", "mode")]
+    assert [d.fields[name][0] for name in ("clip", "time", "weight", "mask", "mode")] == [np.dtype("<u4"), np.dtype("<f4"), np.dtype("<f4"), np.dtype("<u4"), np.dtype("<u4")]
+    assert got[6:] == [T.SKELETON_MAX_LAYERS, T.SKELETON_CURRENT_POSE, T.SKELETON_NO_MASK, T.LAYER_BLEND, T.LAYER_ADDITIVE] == [8, 0xFFFFFFFF, 0xFFFFFFFF, 0, 1]
+    types = open(os.path.join(ROOT, "include", "dxr_amd_types.h")).read()
+    assert re.search(r"static_assert\(sizeof\(rt_skeleton_layer\) == 20,", types)
+    a = capi.Skeleton.layers([(2, 0.5), (1, 0.25, 0.75), (0, 1.0, -0.5, 3, "additive"), {"clip": None, "weight": 2.0}, {"clip": 4, "time": 3.0, "mask": 1, "mode": "additive"}])
+    assert a.dtype == d and a.tolist() == [(2, 0.5, 1.0, 0xFFFFFFFF, 0), (1, 0.25, 0.75, 0xFFFFFFFF, 0), (0, 1.0, -0.5, 3, 1), (0xFFFFFFFF, 0.0, 2.0, 0xFFFFFFFF, 0),
+                                          (4, 3.0, 1.0, 1, 1)]
+
+
+def test_declarations_cite_what_they_stand_in_for():
+    """each export is declared under a comment marked EXTENSION with the citation the neighbouring skeleton exports carry; the header states
+    the definition in full; DESIGN.md no longer calls blending out of scope; the C++ mirror has the methods; the example exists and is built"""
+    text = open(os.path.join(ROOT, "include", "dxr_amd.h")).read()
+    for name in NEW:
+        at = re.search(r"^int %s\s*\(" % name, text, flags=re.M)
+        assert at, name
+        near = re.findall(r"/\*.*?\*/", text[:at.start()], flags=re.S)[-1]
+        assert "EXTENSION" in near and "RtModel.cpp:26" in near and "BottomLevelASGenerator.h:136-176" in near, name
+    assert re.search(r"^int rt_skeleton_add_mask\(rt_skeleton \*sk, const float \*weights /\* n_joints, host \*/, uint32_t \*mask_out\);", text, flags=re.M)
+    assert re.search(r"^int rt_skeleton_clear_masks\(rt_skeleton \*sk\);", text, flags=re.M)
+    assert re.search(r"^int rt_skeleton_get_num_masks\(const rt_skeleton \*sk, uint32_t \*n\);", text, flags=re.M)
+    assert re.search(r"^int rt_skeleton_set_blend\(rt_skeleton \*sk, uint32_t n_layers, const rt_skeleton_layer \*layers /\* n_layers, host \*/\);", text, flags=re.M)
+    block = re.sub(r"\s+", " ", text[text.index("Posed skeletons"):text.index("int rt_model_set_bones_from_skeleton")].replace("\n * ", " "))
+    for words in ("1 .. RT_SKELETON_MAX_LAYERS (8)", "layer 0 is the base: P = S_0 bit for bit", "RT_SKELETON_CURRENT_POSE", "read and overwritten by the same lane",
+                  "w = weight_k * mask_k[j], one product", "P_c = P_c + (w * (S_c - P_c))", "d = ((Px Sx + Py Sy) + Pz Sz) + Pw Sw",
+                  "q * (1 / sqrt(n)) if 0 < n < inf, else (0, 0, 0, 1)", "rt_skeleton_set_time(clip, -inf)", "(i, a) = (0, 0), normalisation included",
+                  "P_c = P_c + (w * (S_c - R_c))", "D = conj(R_q) (x) S_q", "if D_w < 0 every component of D is negated", "E_xyz = w * D_xyz and E_w = 1 + (w * (D_w - 1))",
+                  "P_q = P_q (x) E", "conj(q) = (-x, -y, -z, w)", "x = ((pw qx + px qw) + py qz) - pz qy", "y = ((pw qy - px qz) + py qw) + pz qx",
+                  "z = ((pw qz + px qy) - py qx) + pz qw", "w = ((pw qw - px qx) - py qy) - pz qz", "posed exactly as rt_skeleton_set_pose poses",
+                  "a weight is not clamped", "the message names the layer", "the message names the layer and how many there are", "an additive layer 0",
+                  "nothing is uploaded and nothing waits", "keeps earlier mask ids valid", "ids start at 0 again"):
+        assert words in block, words
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "a caller who blends sets the blended pose" not in design and "k_skeleton_blend" in design
+    mirror = open(os.path.join(ROOT, "dxrexperiments_amd", "include", "DXRFramework.h")).read()
+    sk = mirror[mirror.index("class RtSkeleton"):mirror.index("class RtModel")]
+    for sig in (r"uint32_t addMask\(const float \*weights\)", r"void clearMasks\(\)", r"void setBlend\(const rt_skeleton_layer \*layers, uint32_t numLayers\)"):
+        assert re.search(sig, sk), sig
+    above = sk[:sk.index("uint32_t addMask")].split("void setTime")[1]
+    assert "EXTENSION" in above and "RtModel.cpp:26" in above and "BottomLevelASGenerator.h:136-176" in above
+    example = open(os.path.join(ROOT, "examples", "realtime_blend.cpp")).read()
+    for words in ("RtSkeleton::create(", "addClip(", "addMask(", "setBlend(layers, LAYERS)", "setBones(skeleton)", "->update(context)", "RT_LAYER_ADDITIVE", "JOINTS = 4"):
+        assert words in example, words
+    make = open(os.path.join(ROOT, "Makefile")).read()
+    assert "$(LIBDIR)/realtime_blend" in make.split("BIN =")[1].splitlines()[0] and "examples/realtime_blend.cpp" in make
+    header = open(os.path.join(ROOT, "dxrexperiments_amd", "csrc", "rt_skeleton.h")).read()
+    assert "static inline int rt_skeleton_validate_layers(" in header
+    assert "hip" not in re.sub(r"//.*", "", header).lower(), "rt_skeleton.h is host code without HIP"
+
+
+def test_null_handles_and_null_arrays_are_refused(capi):
+    """argument checks need no device"""
+    lib = capi.lib()
+    x = np.zeros(16, np.float32)
+    layers = capi.Skeleton.layers([(0, 0.0)])
+    px, pl = x.ctypes.data_as(C.c_void_p), layers.ctypes.data_as(C.c_void_p)
+    u = C.c_uint32(7)
+    fake = C.c_void_p(8)                                 # (a non-null handle that the checks must not follow)
+    for rc in (lib.rt_skeleton_add_mask(None, px, C.byref(u)), lib.rt_skeleton_add_mask(fake, None, C.byref(u)), lib.rt_skeleton_clear_masks(None),
+               lib.rt_skeleton_get_num_masks(None, C.byref(u)), lib.rt_skeleton_get_num_masks(fake, None), lib.rt_skeleton_set_blend(None, 1, pl),
+               lib.rt_skeleton_set_blend(fake, 1, None)):
+        assert rc == -1
+        assert b"null" in lib.rt_last_error()
+    assert u.value == 7
+
+
+# ---- rt_skeleton_validate_layers under sanitizers ------------------------------------------------------------------------------------------
+def layer_cases():
+    """(records, n_records, n_clips, n_masks, posed, null): every refusal on its own, on the first, a middle and the last layer; two refusals
+    in one list (an argument's comes before a state's, whichever layer holds it); 0, 9 and 2^32 - 1 layers with no record to read; a null
+    list; and 400 generated lists"""
+    N, NAN = 0xFFFFFFFF, float("nan")
+    ok = (0, 0.5, 1.0, N, 0)
+    out = []
+
+    def add(records, n_clips=3, n_masks=2, posed=True, n_layers=None, null=False):
+        n_layers = len(records) if n_layers is None else n_layers
+        out.append((list(records), n_layers, n_clips, n_masks, posed, null))
+
+    for n in range(1, 9):
+        add([ok] * n)
+    add([], n_layers=0); add([], n_layers=9); add([], n_layers=N); add([], n_layers=1, null=True)
+    for at in (0, 3, 7):
+        for bad in ((0, 0.5, 1.0, N, 2), (0, 0.5, 1.0, N, N), (0, NAN, 1.0, N, 0), (3, 0.5, 1.0, N, 0), (N - 1, 0.5, 1.0, N, 0), (0, 0.5, 1.0, 2, 0), (0, 0.5, 1.0, N - 1, 1),
+                    (0, 0.5, 1.0, N, 1), (N, 0.5, 1.0, N, 0), (N, NAN, NAN, N, 0)):
+            records = [ok] * 8
+            records[at] = bad
+            add(records)
+            add(records, posed=False)
+            add(records, n_clips=0, n_masks=0)
+    add([(N, NAN, 1.0, 5, 0)], n_clips=0, n_masks=0)                           # the current pose: its time and mask are not read
+    add([(N, NAN, 1.0, 5, 0)], n_clips=0, n_masks=0, posed=False)
+    add([(7, 0.0, 1.0, N, 0), (0, 0.0, 1.0, N, 0), (0, NAN, 1.0, N, 0)])       # an unknown clip on layer 0, a NaN time on layer 2: the NaN is named
+    add([(0, 0.0, 1.0, 9, 0), (0, 0.0, 1.0, 9, 0)])                            # the base layer's mask is not read: layer 1's is
+    add([(0, 0.0, NAN, N, 0), (0, np.inf, np.inf, N, 1), (0, -np.inf, -0.0, 1, 0)])      # weights and infinite times are no errors
+    rng = np.random.default_rng(5)
+    for _ in range(400):
+        n = int(rng.integers(1, 9))
+        records = []
+        for k in range(n):
+            clip = int(rng.choice([0, 1, 2, 3, N, N - 1], p=[0.3, 0.3, 0.25, 0.05, 0.05 if k else 0.1, 0.05 if k else 0.0]))
+            records.append((clip, float(rng.choice([0.0, 1.5, -np.inf, np.inf, NAN], p=[0.3, 0.3, 0.15, 0.15, 0.1])), float(rng.choice(B.WEIGHTS + (NAN,))),
+                            int(rng.choice([N, 0, 1, 2], p=[0.5, 0.2, 0.2, 0.1])), int(rng.choice([0, 1, 2], p=[0.55, 0.4, 0.05]))))
+        add(records, posed=bool(rng.integers(0, 2)))
+    return out
+
+
+def test_layer_lists_under_asan_ubsan(tmp_path):
+    """the program's (code, layer) == the Python restatement's for every case; a list the validator must not read has no record behind its
+    pointer, so that reading it is a report; no report"""
+    out_dir = os.path.join(ROOT, "build_san")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "skeleton_blend_sanitized")
+    src = os.path.join(ROOT, "tests", "cpp", "skeleton_blend_sanitized.cpp")
+    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", src, "-o", exe],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-3000:]
+    cases = layer_cases()
+    blob = b""
+    for records, n_layers, n_clips, n_masks, posed, null in cases:
+        a = np.array(records, T.SKELETON_LAYER) if records else np.zeros(0, T.SKELETON_LAYER)
+        blob += np.array([n_layers, len(a), n_clips, n_masks, int(posed), int(null)], np.uint32).tobytes() + a.tobytes()
+    (tmp_path / "in.bin").write_bytes(blob)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and "%d cases, 0 sanitizer reports" % len(cases) in r.stdout and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    got = np.frombuffer((tmp_path / "out.bin").read_bytes(), np.uint32).reshape(-1, 2)
+    assert len(got) == len(cases)
+    seen = set()
+    for (records, n_layers, n_clips, n_masks, posed, null), (what, layer) in zip(cases, got):
+        if null:
+            want = (1, 0)
+        elif n_layers != len(records):
+            want = (2, 0)
+        else:
+            want = B.validate(records, n_clips, n_masks, posed)
+        assert (int(what), int(layer)) == want, (records, n_clips, n_masks, posed, want)
+        seen.add(want[0])
+    assert seen == set(range(10)), "a refusal no case reaches"
+
+
+# ---- the restatement is what it states -----------------------------------------------------------------------------------------------------
+def unit_clip(n, seed, n_keys=2):
+    parents = S.hierarchy("random", n, seed)
+    return S.clip(parents, n_keys, seed + 1, "unit")
+
+
+def test_a_blend_is_the_normalised_lerp():
+    """with unit keys a two-layer RT_LAYER_BLEND of weight w is, to 1e-6, the normalised lerp (towards the nearer of S and -S) and the plain
+    lerp of translation and scale, computed in float64 from the two sampled poses; with a mask the weight is w * mask[j]"""
+    n = 257
+    a, b = unit_clip(n, 1), unit_clip(n, 2)
+    mask = B.masks_for(n, 3)[0]
+    for w in (0.0, 0.25, 0.5, 1.0):
+        for m in (None, 0):
+            P = B.blended([a, b], [mask], [(0, 0.3), (1, 0.6, w, m, B.BLEND)])
+            assert P.dtype == F and P.shape == (n, 10)
+            A, Bq = S.sampled(*a, 0.3).astype(np.float64), S.sampled(*b, 0.6).astype(np.float64)
+            wj = (w * (mask.astype(np.float64) if m is not None else np.ones(n)))[:, None]
+            sign = np.where((A[:, 3:7] * Bq[:, 3:7]).sum(axis=1) < 0, -1.0, 1.0)[:, None]
+            q = A[:, 3:7] + wj * (sign * Bq[:, 3:7] - A[:, 3:7])
+            q /= np.linalg.norm(q, axis=1, keepdims=True)
+            assert np.abs(P[:, 3:7] - q).max() < 1e-6, (w, m)
+            for cols in (slice(0, 3), slice(7, 10)):
+                assert np.abs(P[:, cols] - (A[:, cols] + wj * (Bq[:, cols] - A[:, cols]))).max() < 1e-6, (w, m)
+    # one layer is the sample, bit for bit; weight 0 leaves the base but for the normalisation, weight 1 gives the layer's pose
+    assert B.blended([a], [], [(0, 0.3)]).tobytes() == S.sampled(*a, 0.3).tobytes()
+    assert np.abs(B.blended([a, b], [], [(0, 0.3), (1, 0.6, 1.0)])[:, 3:7] - np.where((sign < 0), -1, 1) * S.sampled(*b, 0.6)[:, 3:7]).max() < 1e-6
+
+
+def test_an_additive_layer_at_its_first_key_adds_nothing():
+    """an additive layer whose time is its clip's first key has S == R: translation and scale are bit-identical (w * 0 == 0 for the finite
+    weights) and the rotation stays within 1e-6 (D is the identity up to rounding); at another time, weight 1 turns the base by conj(R) S in
+    the joint's local frame, as float64 has it"""
+    n = 257
+    a, b = unit_clip(n, 4), unit_clip(n, 5, n_keys=3)
+    base = S.sampled(*a, 0.2)
+    for w in B.WEIGHTS:
+        P = B.blended([a, b], [], [(0, 0.2), (1, float(b[0][0]), w, None, B.ADDITIVE)])
+        assert P[:, 0:3].tobytes() == base[:, 0:3].tobytes() and P[:, 7:10].tobytes() == base[:, 7:10].tobytes(), w
+        assert np.abs(P[:, 3:7].astype(np.float64) - base[:, 3:7]).max() < 1e-6, w
+    t = float(b[0][1])
+    P = B.blended([a, b], [], [(0, 0.2), (1, t, 1.0, None, B.ADDITIVE)])
+    R, Sk = S.sampled(*b, -np.inf).astype(np.float64), S.sampled(*b, t).astype(np.float64)
+
+    def ham(p, q):
+        px, py, pz, pw = p.T
+        qx, qy, qz, qw = q.T
+        return np.stack([pw * qx + px * qw + py * qz - pz * qy, pw * qy - px * qz + py * qw + pz * qx, pw * qz + px * qy - py * qx + pz * qw,
+                         pw * qw - px * qx - py * qy - pz * qz], axis=1)
+
+    D = ham(R[:, 3:7] * [-1, -1, -1, 1], Sk[:, 3:7])
+    D *= np.where(D[:, 3:4] < 0, -1.0, 1.0)
+    want = ham(base[:, 3:7].astype(np.float64), D)
+    assert np.abs(P[:, 3:7] - want).max() < 1e-6
+    assert np.abs(P[:, 0:3] - (base[:, 0:3] + (Sk[:, 0:3] - R[:, 0:3]))).max() < 1e-6
+    # the Hamilton product of the restatement: i j = k, and a quarter turn about z twice is a half turn
+    i, j = np.array([[1, 0, 0, 0]], F), np.array([[0, 1, 0, 0]], F)
+    assert B.hamilton(i, j).tolist() == [[0, 0, 1, 0]] and B.hamilton(j, i).tolist() == [[0, 0, -1, 0]]
+    h = F(np.sqrt(0.5))
+    assert np.abs(B.hamilton(np.array([[0, 0, h, h]], F), np.array([[0, 0, h, h]], F)) - [[0, 0, 1, 0]]).max() < 1e-6
+    assert B.normalised(np.array([[0, 0, 0, 0], [np.inf, 0, 0, 1], [np.nan, 0, 0, 1], [1e30, 0, 0, 0], [0, 3, 0, 4]], F)).tolist() == [[0, 0, 0, 1]] * 4 + [[0, F(3) * (F(1) / np.sqrt(F(25))), 0, F(4) * (F(1) / np.sqrt(F(25)))]]
+
+
+def test_what_the_cases_are_there_for():
+    """layer lists of 8 use every weight and both modes, with and without masks; the first mask tells neighbouring joints apart"""
+    parents = S.hierarchy("random", 65, 1)
+    clips = [S.clip(parents, k, 10 + k) for k in (1, 2, 3, 17)]
+    seen = set()
+    for seed in range(6):
+        layers = B.layer_list(8, clips, 3, seed)
+        assert len(layers) == 8 and layers[0][4] == B.BLEND
+        assert set(l[2] for l in layers[1:]) == set(B.WEIGHTS)
+        seen |= set((l[4], l[3] is None) for l in layers[1:])
+    assert seen == {(B.BLEND, True), (B.BLEND, False), (B.ADDITIVE, True), (B.ADDITIVE, False)}
+    m = B.masks_for(65, 2)[0]
+    assert len(np.unique(m)) == 65 and m.dtype == F
