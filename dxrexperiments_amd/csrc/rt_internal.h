@@ -343,7 +343,7 @@ struct rt_model {
     BvhDev blas;
     bool built = false;
     // rt_model_set_vertices / _set_positions / _recompute_normals: a mesh that changes shape (never its counts or its index list)
-    uint64_t geom_gen = 0;       // bumped by every successful set: a scene records it per instance at build / update (rt_scene::seen_geom)
+    uint64_t geom_gen = 0;       // bumped by every successful set: a scene records it per instance at build / update (SceneInstance::seen_geom)
     bool h_verts_stale = false;  // d_verts was written from device memory: rt_model_read_geometry downloads before it answers
     std::vector<struct rt_scene *> scenes;   // the scenes that hold the model in some instance (each once): a set leaves the built ones stale
     DevBuf adj_off, adj_tris;    // vertex -> triangle CSR of the index list (rt_adjacency.h), made by the first rt_model_recompute_normals
@@ -362,7 +362,7 @@ struct SkeletonClip {
 struct rt_skeleton {
     rt_context *ctx = nullptr;
     int refs = 1;                // handle + every scene that has instances attached to it (once per scene)
-    uint64_t pose_count = 0;     // bumped by every pose set or sampled: a scene records it per attached instance at build / update (SceneAttach::seen)
+    uint64_t pose_count = 0;     // bumped by every pose set or sampled: a scene records it per attached instance at build / update (SceneInstance::seen_pose)
     uint32_t n_joints = 0, n_levels = 0;
     std::vector<uint32_t> level_offsets;     // n_levels + 1 (rt_skeleton.h)
     DevBuf table;                // uint32[n_joints]: joint | parent << 16 in level order (rt_skeleton_pack_table)
@@ -377,17 +377,26 @@ struct rt_skeleton {
     ~rt_skeleton();              // (rt_skeleton.hip) selects the device and joins the stream before the buffers go
 };
 
+// Where an instance's transform comes from.  Host: SceneInstance::xform is the truth.  Device: set from device memory, rt_scene::d_xf holds it and
+// xform is older until an update's join or a build's.  Joint: attached, every update or build that lists it composes it from its skeleton's W
+enum class XfSource : uint8_t { Host, Device, Joint };
+
+// THE host-side statement about one instance; what the device reads of it stands in rt_scene's contiguous arrays, one entry per instance
 struct SceneInstance {
-    rt_model *model;
+    rt_model *model = nullptr;   // retained by the scene
     float xform[12];
+    uint8_t mask = 0xFF;         // the InstanceMask byte, as given (0xFF from rt_scene_add_model): visible iff non-zero
+    bool pending = false;        // listed in rt_scene::pending
+    XfSource source = XfSource::Host;
+    uint64_t seen_geom = 0;      // its model's geom_gen when its record was last written (build / update); another value now: the model's
+                                 //   vertices changed since, the scene is STALE as with a pending transform
+    rt_skeleton *sk = nullptr;   // source == Joint: the skeleton, retained by the scene once (rt_scene::skeletons); else nullptr
+    uint64_t seen_pose = 0;      // sk->pose_count when the scene last applied a pose to this instance (0: never)
 };
 
-// rt_scene_attach_instances: the binding of one instance (rt_scene::att; the device reads att_words / att_local / att_w)
-struct SceneAttach {
-    rt_skeleton *sk = nullptr;   // nullptr: not attached.  Retained by the scene, once per scene (rt_scene::skeletons)
-    uint64_t seen = 0;           // sk->pose_count when the scene last applied a pose to this instance (0: never)
-};
-
+// The records and the binding mirrors (inst, att_words, att_local) have exactly inst.size() entries at every entry point: rt_scene_add_model
+// lengthens them together and nothing else does.  h_inst and h_blas_bounds are a build's output, one entry per instance of an updatable scene;
+// the device arrays are sized for all instances at once (rt_scene.hip).
 struct rt_scene {
     rt_context *ctx = nullptr;
     int refs = 1;                // handle + every pipeline it is set on
@@ -403,27 +412,21 @@ struct rt_scene {
     bool has_refs = false;       // some model of the scene holds triangles as several references (rt_refs.h)
     // rt_scene_set_instance_transform(s) / rt_scene_update: rigid animation without a rebuild of the instance list
     bool updatable = false;      // the TLAS stands for THIS instance list (built, and no rt_scene_add_model since): an update can apply transforms
-    std::vector<uint32_t> pending;       // instances whose transform a setter has changed since the last build / update (each once); while
-    std::vector<uint8_t> is_pending;     //   there are any the scene is STALE: built == false, nothing traces or reads it
+    std::vector<uint32_t> pending;       // instances whose transform a setter has changed since the last build / update (each once:
+                                         //   SceneInstance::pending); while there are any the scene is STALE: built == false, nothing traces or reads it
     std::vector<float> h_blas_bounds;    // float[6 n]: the BLAS box of every instance's model, as uploaded to ...
     DevBuf blas_bounds;          // ... the box an instance set (back) to the identity takes (written by every build)
-    std::vector<uint64_t> seen_geom;     // per instance: its model's geom_gen when the records were last written (build / update); another
-                                         //   value now: the model's vertices changed since, the scene is STALE as with a pending transform
     DevBuf update_back;          // the first 20 words (inv, world box, flags) of the records rt_update_tlas rewrote, on their way to h_inst
     float update_ms = 0.0f;
-    // rt_scene_set_instance_mask(s): the InstanceMask byte of every instance (0xFF from rt_scene_add_model); every ray carries the reference's
-    // inclusion mask 0xFF, so an instance is VISIBLE iff its byte is non-zero.  Masks never touch a record: the TLAS is the one of the visible
-    // sub-list, whose leaves name the instances' own indices
-    std::vector<uint8_t> masks;          // per instance, as given
+    // rt_scene_set_instance_mask(s): every ray carries the reference's inclusion mask 0xFF, so an instance is VISIBLE iff its mask byte is
+    // non-zero.  Masks never touch a record: the TLAS is the one of the visible sub-list, whose leaves name the instances' own indices
     bool masks_dirty = false;            // a setter has changed some instance's visibility on an updatable scene: STALE, as with a pending transform
     std::vector<uint32_t> vis;           // the visible instances, ascending, as the TLAS stands for them (written by a build / update)
     DevBuf d_vis;                        // ... on the device: uploaded only by a build or update at which some visibility changed
     uint32_t n_vis = 0;                  // how many; == inst.size(): nothing hidden, d_vis is not read and the builders launch what they always did
     // rt_scene_set_instance_transforms_mem(RT_MEM_DEVICE) / rt_scene_attach_instances: transforms that come from device memory
-    DevBuf d_xf;                         // float[12 n]: the transform of every DEVICE-HELD instance (set from device memory, or composed from a joint)
-    std::vector<uint8_t> xf_on_dev;      // per instance: d_xf holds its transform and SceneInstance::xform is older (until an update's join or a build's)
+    DevBuf d_xf;                         // float[12 n]: the transform of every instance whose source is Device or Joint (the latter: as last composed)
     DevBuf xf_back;                      // the device-sourced transforms an update listed, slot by slot, on their way to SceneInstance::xform
-    std::vector<SceneAttach> att;        // per instance (or shorter: instances added since the last attachment have none)
     std::vector<uint32_t> att_words;     // per instance: the binding as the device reads it (rt_attach.h), 0: not attached ...
     std::vector<float> att_local;        // ... its local matrix, float[12] per instance ...
     DevBuf d_att_words, d_att_local, d_att_w;    // ... and both on the device, with the skeleton's W array (const float *) of every attached instance

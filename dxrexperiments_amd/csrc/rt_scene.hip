@@ -13,17 +13,14 @@
 
 namespace {
 
-// ---- fresh or stale: built, updatable, pending / is_pending, masks_dirty and seen_geom (rt_internal.h) are written here, nowhere else ----
+// ---- fresh or stale: rt_scene's built, updatable, pending and masks_dirty, and the records' pending and seen_geom (rt_internal.h), are written
+// ---- in this block, nowhere else ----
 
 // rt_scene_add_model: the TLAS no longer stands for this instance list, only rt_scene_build brings the scene back
 void scene_list_changed(rt_scene *s) { s->built = false; s->updatable = false; }
 
 // instance i joins the list the next update rewrites (once)
-void scene_mark_pending(rt_scene *s, uint32_t i)
-{
-    s->is_pending.resize(s->inst.size(), 0);
-    if (!s->is_pending[i]) { s->is_pending[i] = 1; s->pending.push_back(i); }
-}
+void scene_mark_pending(rt_scene *s, uint32_t i) { if (!s->inst[i].pending) { s->inst[i].pending = true; s->pending.push_back(i); } }
 
 // a setter has stored new transforms for `count` instances of an updatable scene
 void scene_transforms_changed(rt_scene *s, uint32_t first, uint32_t count)
@@ -32,8 +29,18 @@ void scene_transforms_changed(rt_scene *s, uint32_t first, uint32_t count)
     s->built = false;         // stale until rt_scene_update or rt_scene_build: nothing traces a half-applied state
 }
 
+// rt_scene_update has found the skeletons of these attached instances posed anew: they join the list, the scene is stale until it has succeeded
+void scene_poses_changed(rt_scene *s, const std::vector<uint32_t> &posed)
+{
+    for (uint32_t i : posed) scene_mark_pending(s, i);
+    if (!posed.empty()) s->built = false;
+}
+
 // a setter has changed some instance's visibility on an updatable scene: stale until rt_scene_update or rt_scene_build, as with a pending transform
 void scene_masks_changed(rt_scene *s) { s->masks_dirty = true; s->built = false; }
+
+// new vertices of one of the scene's models have been queued (never built, or instances added since: the next build reads them anyway)
+void scene_vertices_changed(rt_scene *s) { if (s->updatable) s->built = false; }
 
 // rt_scene_build is about to rewrite the records and the TLAS: if it fails from here on, only another build brings the scene back
 void scene_build_begins(rt_scene *s) { s->updatable = false; }
@@ -42,18 +49,14 @@ void scene_build_begins(rt_scene *s) { s->updatable = false; }
 // update: exactly the instances whose generation differed; nullptr, a build: of every instance).  Nothing is pending, the scene is fresh.
 void scene_applied(rt_scene *s, const std::vector<uint32_t> *changed)
 {
-    const size_t n = s->inst.size();
-    // the attached instances it listed (an update: the pending ones; a build: all) now stand where their skeleton's current pose puts them
-    for (size_t i = 0; i < s->att.size(); i++)
-        if (s->att[i].sk && (!changed || s->is_pending[i])) s->att[i].seen = s->att[i].sk->pose_count;
+    // the attached instances it listed now stand where their skeleton's current pose puts them
+    const auto listed = [](SceneInstance &in) { if (in.source == XfSource::Joint) in.seen_pose = in.sk->pose_count; in.pending = false; };
     if (changed) {
-        for (uint32_t i : s->pending) s->is_pending[i] = 0;
-        for (uint32_t i : *changed) s->seen_geom[i] = s->inst[i].model->geom_gen;
+        for (uint32_t i : s->pending) listed(s->inst[i]);
+        for (uint32_t i : *changed) s->inst[i].seen_geom = s->inst[i].model->geom_gen;
     } else {
+        for (SceneInstance &in : s->inst) { listed(in); in.seen_geom = in.model->geom_gen; }
         s->updatable = true;
-        s->is_pending.assign(n, 0);
-        s->seen_geom.resize(n);
-        for (size_t i = 0; i < n; i++) s->seen_geom[i] = s->inst[i].model->geom_gen;
     }
     s->pending.clear();
     s->masks_dirty = false;
@@ -64,37 +67,48 @@ void scene_applied(rt_scene *s, const std::vector<uint32_t> *changed)
 size_t scene_changed_instances(const rt_scene *s, std::vector<uint32_t> *which = nullptr)
 {
     size_t n = 0;
-    if (!s->updatable || s->seen_geom.size() != s->inst.size()) return 0;
+    if (!s->updatable) return 0;
     for (size_t i = 0; i < s->inst.size(); i++)
-        if (s->inst[i].model->geom_gen != s->seen_geom[i]) { n++; if (which) which->push_back((uint32_t)i); }
+        if (s->inst[i].model->geom_gen != s->inst[i].seen_geom) { n++; if (which) which->push_back((uint32_t)i); }
     return n;
 }
 
-// ---- transforms that come from device memory: set there (rt_scene_set_instance_transforms_mem) or composed from a joint (rt_scene_attach_instances) ----
+// ---- the instance list and its bindings: scene_add_instance lengthens the records and the binding mirrors (rt_internal.h), together; nothing else does ----
 
-bool scene_attached(const rt_scene *s, size_t i) { return i < s->att.size() && s->att[i].sk != nullptr; }
-bool scene_on_device(const rt_scene *s, size_t i) { return i < s->xf_on_dev.size() && s->xf_on_dev[i] != 0; }
+void scene_add_instance(rt_scene *s, rt_model *m, const float xform[12])
+{
+    SceneInstance in;                                  // (mask 0xFF: InstanceMask of the reference's descriptors, TopLevelASGenerator.cpp:361)
+    in.model = m;
+    memcpy(in.xform, xform, sizeof in.xform);
+    s->inst.push_back(in);
+    s->att_words.resize(s->inst.size(), 0u);
+    s->att_local.resize(12 * s->inst.size(), 0.0f);
+}
+
+// instance i follows a joint of sk (which the scene retains: rt_scene::skeletons); `word`: the binding as the device reads it (rt_attach.h)
+void scene_bind(rt_scene *s, uint32_t i, rt_skeleton *sk, uint32_t word)
+{
+    SceneInstance &in = s->inst[i];
+    in.source = sk ? XfSource::Joint : XfSource::Host; in.sk = sk; in.seen_pose = 0; s->att_words[i] = word;
+}
+
+// ... and no longer: it keeps the floats its last update or build gave it, which the host copy holds
+void scene_unbind(rt_scene *s, uint32_t i) { scene_bind(s, i, nullptr, 0u); }
 
 // attached instances of an updatable scene whose skeleton has been posed since the scene last applied it, and that are not pending already
-size_t scene_posed_instances(const rt_scene *s, std::vector<uint32_t> *which)
+void scene_posed_instances(const rt_scene *s, std::vector<uint32_t> &which)
 {
-    size_t n = 0;
-    if (!s->updatable) return 0;
-    for (size_t i = 0; i < s->att.size(); i++) {
-        const SceneAttach &a = s->att[i];
-        if (!a.sk || !a.sk->posed || a.sk->pose_count == a.seen) continue;
-        if (i < s->is_pending.size() && s->is_pending[i]) continue;
-        n++;
-        if (which) which->push_back((uint32_t)i);
+    for (size_t i = 0; s->updatable && !s->skeletons.empty() && i < s->inst.size(); i++) {      // (no skeleton: nobody has ever been attached)
+        const SceneInstance &in = s->inst[i];
+        if (in.source == XfSource::Joint && !in.pending && in.sk->posed && in.sk->pose_count != in.seen_pose) which.push_back((uint32_t)i);
     }
-    return n;
 }
 
 // an update or a build composes every attached instance it lists from W: refused, with nothing changed, while some skeleton has no pose
 int scene_require_poses(const rt_scene *s, const char *who)
 {
-    for (size_t i = 0; i < s->att.size(); i++)
-        if (s->att[i].sk && !s->att[i].sk->posed) {
+    for (size_t i = 0; !s->skeletons.empty() && i < s->inst.size(); i++)
+        if (s->inst[i].source == XfSource::Joint && !s->inst[i].sk->posed) {
             rt_set_error("%s: instance %zu is attached to a skeleton that has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", who, i);
             return RT_ERR_STATE;
         }
@@ -111,47 +125,62 @@ int scene_refuse_attached(const rt_scene *s, const char *who, uint32_t first, ui
     return RT_ERR_STATE;
 }
 
-// d_xf for all of the scene's instances: reserved once (again only after rt_scene_add_model has made the list longer; what it held then comes
-// down to the host copies first -- DevBuf::reserve keeps no contents -- the one place where a setter waits)
-int reserve_device_transforms(rt_context *ctx, rt_scene *s)
+// What d_xf holds for the device-held instances of a range, on its way to their host copies: theirs once the caller has joined the stream
+// (*any: there is something to wait for), and they are host-sourced from here on
+int scene_bring_down(rt_context *ctx, rt_scene *s, size_t first, size_t count, bool *any)
+{
+    for (size_t i = first; i < first + count; i++)
+        if (s->inst[i].source == XfSource::Device) {
+            HIP_TRY(hipMemcpyAsync(s->inst[i].xform, s->d_xf.as<float>() + 12 * i, 48, hipMemcpyDeviceToHost, ctx->stream));
+            s->inst[i].source = XfSource::Host;
+            *any = true;
+        }
+    return RT_OK;
+}
+
+// d_xf and the three binding arrays for ALL of the scene's instances (k_gather_transforms indexes them by instance): reserved once, and again
+// only after rt_scene_add_model has made the list longer (DevBuf::reserve keeps no contents).  What d_xf held then comes down to the host
+// copies first and those instances are host-sourced from there on -- the one place where a setter waits; the bindings go up again from their
+// host mirrors and the records' skeletons, and a scene that has any waits for that too.  d_xf grows last: its size says that all four stand.
+int scene_reserve_device(rt_context *ctx, rt_scene *s)
 {
     const size_t n = s->inst.size();
-    s->xf_on_dev.resize(n, 0);
     if (s->d_xf.bytes >= 48 * n) return RT_OK;
-    std::vector<float> down(12 * n);
-    bool any = false;
+    bool held = false, bound = false;
+    RT_TRY(scene_bring_down(ctx, s, 0, n, &held));
+    if (held) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::vector<const float *> w_of(n, nullptr);
     for (size_t i = 0; i < n; i++)
-        if (s->xf_on_dev[i] && 48 * (i + 1) <= s->d_xf.bytes) {
-            HIP_TRY(hipMemcpyAsync(&down[12 * i], s->d_xf.as<char>() + 48 * i, 48, hipMemcpyDeviceToHost, ctx->stream));
-            any = true;
-        }
-    if (any) HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; i++)
-        if (s->xf_on_dev[i]) { memcpy(s->inst[i].xform, &down[12 * i], 48); s->xf_on_dev[i] = 0; }
+        if (s->inst[i].source == XfSource::Joint) { w_of[i] = s->inst[i].sk->joints.as<float>(); bound = true; }
+    RT_TRY(s->d_att_words.reserve(4 * n));
+    RT_TRY(s->d_att_local.reserve(48 * n));
+    RT_TRY(s->d_att_w.reserve(sizeof(const float *) * n));
+    if (bound) {
+        HIP_TRY(hipMemcpyAsync(s->d_att_words.p, s->att_words.data(), 4 * n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_att_local.p, s->att_local.data(), 48 * n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_att_w.p, w_of.data(), sizeof(const float *) * n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (w_of goes out of scope; the mirrors are the host's to change again)
+    } else      // nobody is attached: every word is 0, and the other two arrays are read for attached instances only
+        HIP_TRY(hipMemsetAsync(s->d_att_words.p, 0, 4 * n, ctx->stream));
     return s->d_xf.reserve(48 * n);
 }
 
-// A scene whose transforms, instance masks or models' vertices were set and not applied yet: says so (the message names them) and returns true.
+// A scene whose transforms, instance masks or models' vertices were set and not applied yet: says so (the message names them, joined by " and ",
+// and the setter of the first) and returns true.
 bool scene_stale_error(const rt_scene *s, const char *who)
 {
     if (!s || s->built) return false;
-    const size_t changed = scene_changed_instances(s);
-    const char *masks = s->updatable && s->masks_dirty ? " and instance masks" : "";
-    if (changed) {
-        char also[128] = "";
-        if (!s->pending.empty()) snprintf(also, sizeof also, " and %zu instance transform%s%s", s->pending.size(), s->pending.size() == 1 ? "" : "s", masks);
-        else snprintf(also, sizeof also, "%s", masks);
-        rt_set_error("%s: new vertices of the model%s of %zu instance%s%s pending (rt_model_set_vertices / _set_positions / _recompute_normals): "
-                     "rt_scene_update or rt_scene_build applies them", who, changed == 1 ? "" : "s", changed, changed == 1 ? "" : "s", also);
-        return true;
-    }
-    if (s->pending.empty()) {
-        if (!masks[0]) return false;
-        rt_set_error("%s: instance masks pending (rt_scene_set_instance_mask): rt_scene_update or rt_scene_build applies them", who);
-        return true;
-    }
-    rt_set_error("%s: %zu instance transform%s%s pending (rt_scene_set_instance_transform): rt_scene_update or rt_scene_build applies them", who,
-                 s->pending.size(), s->pending.size() == 1 ? "" : "s", masks);
+    const size_t changed = scene_changed_instances(s), moved = s->pending.size();
+    const bool masks = s->updatable && s->masks_dirty;
+    if (!changed && !moved && !masks) return false;
+    char what[192];
+    int at = 0;
+    if (changed)
+        at += snprintf(what + at, sizeof what - at, "new vertices of the model%s of %zu instance%s", changed == 1 ? "" : "s", changed, changed == 1 ? "" : "s");
+    if (moved) at += snprintf(what + at, sizeof what - at, "%s%zu instance transform%s", at ? " and " : "", moved, moved == 1 ? "" : "s");
+    if (masks) snprintf(what + at, sizeof what - at, "%sinstance masks", at ? " and " : "");
+    rt_set_error("%s: %s pending (%s): rt_scene_update or rt_scene_build applies them", who, what,
+                 changed ? "rt_model_set_vertices / _set_positions / _recompute_normals" : moved ? "rt_scene_set_instance_transform" : "rt_scene_set_instance_mask");
     return true;
 }
 
@@ -233,7 +262,7 @@ int reserve_tlas_for(BvhDev &bv, uint32_t n)
     return RT_OK;
 }
 
-// the visible sub-list from s->masks into s->vis / d_vis / n_vis, uploaded if it differs from the one the scene has (or `force`: a build,
+// the visible sub-list from the records' masks into s->vis / d_vis / n_vis, uploaded if it differs from the one the scene has (or `force`: a build,
 // whose TLAS buffers may be new); RT_ERR_STATE, and nothing changed, if no instance is visible
 int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool force)
 {
@@ -241,7 +270,7 @@ int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool for
     std::vector<uint32_t> vis;
     vis.reserve(n);
     for (uint32_t i = 0; i < n; i++)
-        if (s->masks[i]) vis.push_back(i);
+        if (s->inst[i].mask) vis.push_back(i);
     if (vis.empty()) { rt_set_error("%s: no instance is visible: every instance mask is 0 (rt_scene_set_instance_mask)", who); return RT_ERR_STATE; }
     if (!force && vis == s->vis) return RT_OK;
     s->vis.swap(vis);                                  // (a member: alive whenever the copy runs)
@@ -267,13 +296,13 @@ int rt_scene_apply_masks(rt_context *ctx, rt_scene *s, const char *who, bool for
 // storage d_xf too, from where on it is a transform set from device memory.  Any other: the twelve floats d_xf holds for it.  A lane reads and
 // writes the rows of its own instance only, and an instance is listed once.  The grid's last wave may be partial: these lanes meet nowhere.
 __global__ void __launch_bounds__(UPD_BLOCK) k_gather_transforms(const uint32_t *__restrict__ idx, uint32_t n, const uint32_t *__restrict__ words,
-                                                                 uint32_t n_words, const float *__restrict__ local, const float *const *__restrict__ w_of,
-                                                                 float *d_xf, float *__restrict__ pend_xf, float *__restrict__ back)
+                                                                 const float *__restrict__ local, const float *const *__restrict__ w_of, float *d_xf,
+                                                                 float *__restrict__ pend_xf, float *__restrict__ back)
 {
     const uint32_t k = blockIdx.x * UPD_BLOCK + threadIdx.x;
     if (k >= n) return;
     const uint32_t i = idx[k];
-    const uint32_t word = i < n_words ? words[i] : 0u;     // (instances added after the last attachment have no word)
+    const uint32_t word = words[i];                        // (the binding arrays cover every instance: scene_reserve_device)
     float T[12];
     if (word & RT_ATTACH_BOUND) {
         const float *W = w_of[i] + 12u * (size_t)(word & RT_ATTACH_JOINT_MASK);
@@ -492,31 +521,27 @@ int rt_update_model_records(rt_context *ctx, rt_scene *s, const std::vector<uint
     return RT_OK;
 }
 
-// THE TLAS path of a build (list: every instance, 0 .. n-1) and of an update (s->pending): rewrites the transform part of the listed
-// instances' records and their world boxes, rebuilds the TLAS over the visible instances and takes the scene's summary, on the device.
-// `who` names the caller in messages.  It creates no event and reads no time; `queued` (or nullptr) is the caller's event, which it records
-// behind the wide collapse, in front of the read-back: where update_ms ends
-int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &listed, const char *who, hipEvent_t queued)
+// The listed instances in two runs: first those whose transform the host holds (returns how many), whose floats go up as they always did; then
+// those whose transform the device holds or makes, whose slots k_gather_transforms fills.  The slot order decides nothing (k_update_records).
+size_t partition_by_source(const rt_scene *s, const std::vector<uint32_t> &listed, std::vector<uint32_t> &list)
+{
+    std::vector<uint32_t> rest;
+    list.reserve(listed.size());
+    for (uint32_t i : listed) (s->inst[i].source == XfSource::Host ? list : rest).push_back(i);
+    const size_t nh = list.size();
+    list.insert(list.end(), rest.begin(), rest.end());
+    return nh;
+}
+
+// Everything an update queues, and its one join: the transforms of `list` (nh of them from the host: partition_by_source) into their records
+// and world boxes, the TLAS over the visible instances, the read-backs.  It creates no event and reads no time; `queued` (or nullptr) is the
+// caller's event, which it records behind the wide collapse, in front of the read-back: where update_ms ends
+int queue_tlas_update(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &list, size_t nh, const char *who, hipEvent_t queued)
 {
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)s->inst.size();
-    const size_t np = listed.size();
-    // The listed instances in two runs: first those whose transform the host holds, nh of them, whose floats go up as they always did; then
-    // those whose transform the device holds or makes (set from device memory, attached to a joint), nd of them, whose slots
-    // k_gather_transforms fills.  The slot order decides nothing (k_update_records): every slot is written before that kernel reads it.
-    // (the scene's device storage first, for all n: should the list have grown since it was reserved, what it held comes down to the host
-    // copies and those instances are host-sourced below)
-    bool from_device = false;
-    for (uint32_t i : listed) from_device = from_device || scene_attached(s, i) || scene_on_device(s, i);
-    if (from_device) RT_TRY(reserve_device_transforms(ctx, s));
-    std::vector<uint32_t> list;                        // (alive, as xf is, until the last synchronisation below)
-    list.reserve(np);
-    for (uint32_t i : listed)
-        if (!scene_attached(s, i) && !scene_on_device(s, i)) list.push_back(i);
-    const size_t nh = list.size(), nd = np - nh;
-    for (uint32_t i : listed)
-        if (scene_attached(s, i) || scene_on_device(s, i)) list.push_back(i);
-    std::vector<float> xf(12 * nh);
+    const size_t np = list.size(), nd = np - nh;
+    std::vector<float> xf(12 * nh);                    // (alive, as list is, until the last synchronisation below)
     size_t max_items = 0;
     for (size_t k = 0; k < np; k++) {
         const SceneInstance &in = s->inst[list[k]];
@@ -538,9 +563,8 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &li
         if (nh) HIP_TRY(hipMemcpyAsync(t.pend_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
         if (nd) {
             k_gather_transforms<<<grid_for(nd, UPD_BLOCK), UPD_BLOCK, 0, st>>>(t.pend_idx + nh, (uint32_t)nd, s->d_att_words.as<uint32_t>(),
-                                                                              (uint32_t)s->att_words.size(), s->d_att_local.as<float>(),
-                                                                              (const float *const *)s->d_att_w.p, s->d_xf.as<float>(), t.pend_xf + 12 * nh,
-                                                                              s->xf_back.as<float>());
+                                                                              s->d_att_local.as<float>(), (const float *const *)s->d_att_w.p,
+                                                                              s->d_xf.as<float>(), t.pend_xf + 12 * nh, s->xf_back.as<float>());
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemsetAsync(t.n_items, 0, sizeof(uint32_t), st));
@@ -566,11 +590,17 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &li
     RT_TRY(lbvh_collect(ctx, s->tlas));
     for (size_t k = 0; k < np; k++) memcpy((void *)&s->h_inst[list[k]], &back[UPD_BACK_WORDS * k], sizeof(uint32_t) * UPD_BACK_WORDS);
     for (size_t k = 0; k < nd; k++) {
-        const uint32_t i = list[nh + k];
-        memcpy(s->inst[i].xform, &back_xf[12 * k], 12 * sizeof(float));
-        if (i < s->xf_on_dev.size()) s->xf_on_dev[i] = 0;      // (d_xf holds the same floats: either source serves the next update)
+        SceneInstance &in = s->inst[list[nh + k]];
+        memcpy(in.xform, &back_xf[12 * k], 12 * sizeof(float));
+        if (in.source == XfSource::Device) in.source = XfSource::Host;      // (d_xf holds the same floats: either source serves the next update)
     }
-    // the scene's summary, taken again over all models: a deformation changes depths and can create or remove split references
+    return RT_OK;
+}
+
+// the scene's summary, taken again over all models: a deformation changes depths and can create or remove split references
+int take_scene_summary(rt_context *ctx, rt_scene *s, const char *who, size_t n_listed)
+{
+    const uint32_t n = (uint32_t)s->inst.size();
     uint32_t deepest = 0, canon = s->tlas.max_depth;
     s->has_refs = false;
     for (uint32_t i = 0; i < n; i++) {
@@ -589,8 +619,22 @@ int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &li
     if (canon >= 127) { rt_set_error("acceleration structure %u levels deep: the limit is 126", canon); return RT_ERR_UNSUPPORTED; }
     if (ctx->verbose)
         fprintf(stderr, "[dxr_amd] %s: TLAS update, %zu of %u instances, %u visible, depth %u; deepest BLAS layout depth %u (%s); stack need %u; %s walk\n",
-                who, np, n, nv, s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
+                who, n_listed, n, s->n_vis, s->tlas.max_depth, deepest, ctx->use_ploc ? "PLOC" : "LBVH", s->stack_need, s->two_level ? "two-level" : "single-level");
     return RT_OK;
+}
+
+// THE TLAS path of a build (listed: every instance, 0 .. n-1) and of an update (s->pending): the listed instances' records and world boxes,
+// the TLAS over the visible instances, the scene's summary.  `who` names the caller in messages; `queued`: queue_tlas_update
+int rt_update_tlas(rt_context *ctx, rt_scene *s, const std::vector<uint32_t> &listed, const char *who, hipEvent_t queued)
+{
+    // (the device storage first: should the list have grown since, what d_xf held comes down and is host-sourced in the partition)
+    bool from_device = false;                          // (a scene without device storage has no such instance)
+    for (size_t k = 0; s->d_xf.bytes && !from_device && k < listed.size(); k++) from_device = s->inst[listed[k]].source != XfSource::Host;
+    if (from_device) RT_TRY(scene_reserve_device(ctx, s));
+    std::vector<uint32_t> list;
+    const size_t nh = partition_by_source(s, listed, list);
+    RT_TRY(queue_tlas_update(ctx, s, list, nh, who, queued));
+    return take_scene_summary(ctx, s, who, list.size());
 }
 
 // the build's share of the TLAS: the model part of every record and the per-instance BLAS boxes, written on the host and uploaded; then
@@ -599,7 +643,7 @@ int rt_build_tlas(rt_context *ctx, rt_scene *s)
 {
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)s->inst.size();
-    s->h_inst.assign(n, InstanceRec());
+    s->h_inst.assign(n, InstanceRec());                // (the build's output, as vis is: one entry per instance of an updatable scene)
     s->h_blas_bounds.resize(6 * (size_t)n);            // (members: alive whenever the copies run)
     std::vector<uint32_t> all(n);                      // (alive until rt_update_tlas has joined the stream)
     for (uint32_t i = 0; i < n; i++) {
@@ -634,10 +678,7 @@ rt_scene::~rt_scene()
     for (rt_skeleton *sk : skeletons) rt_skeleton_destroy(sk);     // (joins the stream when the scene held the last reference)
 }
 
-void rt_scene_model_changed(rt_scene *s)
-{
-    if (s->updatable) s->built = false;                // (never built, or instances added since: the next build reads the new vertices anyway)
-}
+void rt_scene_model_changed(rt_scene *s) { scene_vertices_changed(s); }
 
 int rt_scene_require_built(const rt_scene *s, const char *who, const char *not_built)
 {
@@ -664,12 +705,8 @@ int rt_scene_add_model(rt_scene *s, rt_model *m, const float transform3x4[12])
     RT_REQUIRE(s && m && transform3x4, "null argument");
     RT_REQUIRE(m->ctx == s->ctx, "model and scene belong to different contexts");
     RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
-    SceneInstance in;
-    in.model = m;
-    memcpy(in.xform, transform3x4, sizeof in.xform);
     m->refs++;
-    s->inst.push_back(in);
-    s->masks.push_back(0xFF);  // InstanceMask of the reference's descriptors (TopLevelASGenerator.cpp:361)
+    scene_add_instance(s, m, transform3x4);
     bool held = false;
     for (rt_scene *o : m->scenes) held = held || o == s;
     if (!held) m->scenes.push_back(s);
@@ -687,7 +724,7 @@ int rt_scene_set_instance_transforms(rt_scene *s, uint32_t first, uint32_t count
     RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
     for (uint32_t k = 0; k < count; k++) {
         memcpy(s->inst[first + k].xform, transforms3x4 + 12 * (size_t)k, sizeof s->inst[0].xform);
-        if (first + k < s->xf_on_dev.size()) s->xf_on_dev[first + k] = 0;     // (the host holds it again)
+        s->inst[first + k].source = XfSource::Host;      // (none of them is attached: the host holds it again)
     }
     if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the stored transforms)
     return RT_OK;
@@ -713,10 +750,10 @@ int rt_scene_set_instance_transforms_mem(rt_scene *s, uint32_t first, uint32_t c
     rt_context *ctx = s->ctx;
     RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));          // frames accepted before this change see the scene as it was
-    RT_TRY(reserve_device_transforms(ctx, s));
+    RT_TRY(scene_reserve_device(ctx, s));
     // (ordered on the context's stream: the caller's array is its own again once the stream has passed this copy)
     HIP_TRY(hipMemcpyAsync(s->d_xf.as<float>() + 12 * (size_t)first, transforms3x4, 48 * (size_t)count, hipMemcpyDeviceToDevice, ctx->stream));
-    for (uint32_t k = 0; k < count; k++) s->xf_on_dev[first + k] = 1;
+    for (uint32_t k = 0; k < count; k++) s->inst[first + k].source = XfSource::Device;      // (none of them is attached)
     if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the stored transforms)
     return RT_OK;
 }
@@ -727,13 +764,13 @@ int rt_scene_get_instance_transforms(const rt_scene *s, uint32_t first, uint32_t
     RT_TRY(scene_range_check(s, __func__, first, count));
     bool waits = false;
     for (uint32_t k = 0; k < count;) {
-        if (!scene_on_device(s, first + k)) {
+        if (s->inst[first + k].source != XfSource::Device) {
             memcpy(transforms3x4 + 12 * (size_t)k, s->inst[first + k].xform, 48);
             k++;
             continue;
         }
         uint32_t run = 1;                              // device-held ones come down run by run, on demand
-        while (k + run < count && scene_on_device(s, first + k + run)) run++;
+        while (k + run < count && s->inst[first + k + run].source == XfSource::Device) run++;
         if (!waits) RT_TRY(rt_use_device(s->ctx));
         HIP_TRY(hipMemcpyAsync(transforms3x4 + 12 * (size_t)k, s->d_xf.as<float>() + 12 * (size_t)(first + k), 48 * (size_t)run, hipMemcpyDeviceToHost,
                                s->ctx->stream));
@@ -761,36 +798,23 @@ int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_sk
     rt_context *ctx = s->ctx;
     RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_context_flush_deferred(ctx));          // frames accepted before this change see the scene as it was
-    const size_t n = s->inst.size();
-    // the bindings of all n instances as they will stand, beside the ones the scene has: nothing changes if the device refuses
-    std::vector<uint32_t> words(s->att_words);
-    std::vector<float> local(s->att_local);
-    std::vector<const float *> w_of(n, nullptr);
-    words.resize(n, 0u);
-    local.resize(12 * n, 0.0f);
-    rt_attach_pack(count, joints, local3x4 != nullptr, words.data() + first);
-    if (local3x4) memcpy(&local[12 * (size_t)first], local3x4, 48 * (size_t)count);
-    for (size_t i = 0; i < n; i++)
-        if (i >= first && i < (size_t)first + count) w_of[i] = sk->joints.as<float>();
-        else if (scene_attached(s, i)) w_of[i] = s->att[i].sk->joints.as<float>();
-    RT_TRY(reserve_device_transforms(ctx, s));         // (where the composed transforms will stand)
-    // for all n at once; a longer list than the arrays were made for: everything goes up again (DevBuf::reserve keeps no contents)
-    const bool all = s->d_att_words.bytes < 4 * n || s->att_words.size() != n;
-    RT_TRY(s->d_att_words.reserve(4 * n));
-    RT_TRY(s->d_att_local.reserve(48 * n));
-    RT_TRY(s->d_att_w.reserve(sizeof(const float *) * n));
-    const size_t a = all ? 0 : first, c = all ? n : count;
-    HIP_TRY(hipMemcpyAsync(s->d_att_words.as<uint32_t>() + a, &words[a], 4 * c, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_att_local.as<float>() + 12 * a, &local[12 * a], 48 * c, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync((const float **)s->d_att_w.p + a, &w_of[a], sizeof(const float *) * c, hipMemcpyHostToDevice, ctx->stream));
+    // the device first -- the only steps that can refuse -- then, behind the wait, the host: nothing changes if the device refuses
+    RT_TRY(scene_reserve_device(ctx, s));              // (where the composed transforms will stand, and the bindings of every instance)
+    std::vector<uint32_t> words(count);
+    std::vector<const float *> w_of(count, sk->joints.as<float>());
+    rt_attach_pack(count, joints, local3x4 != nullptr, words.data());
+    HIP_TRY(hipMemcpyAsync(s->d_att_words.as<uint32_t>() + first, words.data(), 4 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    if (local3x4)                                      // (without one the rows stay: nobody reads them)
+        HIP_TRY(hipMemcpyAsync(s->d_att_local.as<float>() + 12 * (size_t)first, local3x4, 48 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync((const float **)s->d_att_w.p + first, w_of.data(), sizeof(const float *) * count, hipMemcpyHostToDevice, ctx->stream));
+    bool held = false;                                 // (one set from device memory and not applied yet keeps those floats until an update)
+    RT_TRY(scene_bring_down(ctx, s, first, count, &held));
     HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope, the caller's arrays are its own again)
-    s->att_words.swap(words);
-    s->att_local.swap(local);
-    s->att.resize(n);
-    bool held = false;
+    held = false;
     for (rt_skeleton *o : s->skeletons) held = held || o == sk;
     if (!held) { s->skeletons.push_back(sk); rt_skeleton_retain(sk); }      // (as the scene retains its models; let go of when the scene goes)
-    for (uint32_t k = 0; k < count; k++) { s->att[first + k].sk = sk; s->att[first + k].seen = 0; }
+    if (local3x4) memcpy(&s->att_local[12 * (size_t)first], local3x4, 48 * (size_t)count);
+    for (uint32_t k = 0; k < count; k++) scene_bind(s, first + k, sk, words[k]);
     if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the binding)
     return RT_OK;
 }
@@ -799,13 +823,13 @@ int rt_scene_detach_instances(rt_scene *s, uint32_t first, uint32_t count)
 {
     RT_REQUIRE(s, "null scene");
     RT_TRY(scene_range_check(s, __func__, first, count));
-    uint32_t from = 0;
+    uint32_t from = 0, last = 0;
     if (!rt_attach_range_holds(s->att_words.data(), s->att_words.size(), first, count, &from)) return RT_OK;      // none attached: nothing to do
-    const uint32_t end = (uint32_t)((size_t)first + count < s->att_words.size() ? (size_t)first + count : s->att_words.size());
     RT_TRY(rt_use_device(s->ctx));
-    // (a word of 0 is "not attached": the instance keeps the floats its last update or build gave it, in the host copy and in d_xf alike)
-    HIP_TRY(hipMemsetAsync(s->d_att_words.as<uint32_t>() + from, 0, 4 * (size_t)(end - from), s->ctx->stream));
-    for (uint32_t i = from; i < end; i++) { s->att_words[i] = 0u; s->att[i].sk = nullptr; s->att[i].seen = 0; }
+    for (uint32_t i = from; i < first + count; i++)
+        if (s->inst[i].source == XfSource::Joint) { scene_unbind(s, i); last = i; }
+    // from the first attached one to the last, which the device arrays cover whatever has been added since (a word of 0 is "not attached")
+    HIP_TRY(hipMemsetAsync(s->d_att_words.as<uint32_t>() + from, 0, 4 * (size_t)(last - from + 1), s->ctx->stream));
     return RT_OK;
 }
 
@@ -813,8 +837,8 @@ int rt_scene_get_instance_attachment(const rt_scene *s, uint32_t instance, rt_sk
 {
     RT_REQUIRE(s, "null scene");
     RT_TRY(scene_range_check(s, __func__, instance, 1, true));
-    const bool bound = scene_attached(s, instance);
-    if (sk) *sk = bound ? s->att[instance].sk : nullptr;
+    const bool bound = s->inst[instance].source == XfSource::Joint;
+    if (sk) *sk = bound ? s->inst[instance].sk : nullptr;
     if (joint) *joint = bound ? s->att_words[instance] & RT_ATTACH_JOINT_MASK : 0u;
     return RT_OK;
 }
@@ -829,8 +853,8 @@ int rt_scene_set_instance_masks(rt_scene *s, uint32_t first, uint32_t count, con
     RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
     bool visibility = false;
     for (uint32_t k = 0; k < count; k++) {
-        visibility = visibility || ((s->masks[first + k] != 0) != (masks[k] != 0));
-        s->masks[first + k] = masks[k];
+        visibility = visibility || ((s->inst[first + k].mask != 0) != (masks[k] != 0));
+        s->inst[first + k].mask = masks[k];
     }
     // (not built: the next build reads the stored masks; the same visibility: only the bytes change)
     if (s->updatable && visibility) scene_masks_changed(s);
@@ -848,7 +872,7 @@ int rt_scene_get_instance_masks(const rt_scene *s, uint32_t first, uint32_t coun
 {
     RT_REQUIRE(s && (masks || count == 0), "null argument");
     RT_TRY(scene_range_check(s, "rt_scene_get_instance_masks", first, count));
-    if (count) memcpy(masks, s->masks.data() + first, count);
+    for (uint32_t k = 0; k < count; k++) masks[k] = s->inst[first + k].mask;
     return RT_OK;
 }
 
@@ -862,7 +886,7 @@ int rt_scene_update(rt_scene *s)
     std::vector<uint32_t> changed;                    // instances whose model's vertices were set since their records were written
     scene_changed_instances(s, &changed);
     std::vector<uint32_t> posed;                      // attached instances whose skeleton has been posed since the scene last applied it
-    scene_posed_instances(s, &posed);
+    scene_posed_instances(s, posed);
     if (s->pending.empty() && changed.empty() && !s->masks_dirty && posed.empty()) return RT_OK;      // nothing to apply: nothing launched, the generation stays
     rt_context *ctx = s->ctx;
     RT_TRY(rt_use_device(ctx));
@@ -884,11 +908,7 @@ int rt_scene_update(rt_scene *s)
         RT_TRY(rt_update_model_records(ctx, s, changed));
         for (uint32_t i : changed) scene_mark_pending(s, i);      // ... and take their world boxes over the new vertices, with the transforms they have
     }
-    if (!posed.empty()) {
-        // the new pose is applied with everything else, in this one call: its instances join the list, the scene is stale until it has succeeded
-        for (uint32_t i : posed) scene_mark_pending(s, i);
-        s->built = false;
-    }
+    scene_poses_changed(s, posed);
     // (a failure leaves the scene stale, the transforms and the models pending); e1: behind the wide collapse, in front of the read-back
     RT_TRY(rt_update_tlas(ctx, s, s->pending, "rt_scene_update", e1.e));
     HIP_TRY(hipEventElapsedTime(&s->update_ms, e0.e, e1.e));
@@ -1031,7 +1051,7 @@ int rt_debug_wide_write(rt_scene *s, int which, const void *nodes, uint32_t n_no
 int rt_scene_instance_info(const rt_scene *s, uint32_t instance, float world_box[6], float world_to_object[12])
 {
     RT_REQUIRE(s, "null scene");
-    if (!s->built || instance >= s->h_inst.size()) return scene_refuse(s, __func__, "scene not built or instance out of range");
+    if (!s->built || instance >= s->inst.size()) return scene_refuse(s, __func__, "scene not built or instance out of range");
     const InstanceRec &r = s->h_inst[instance];
     if (world_box) for (int c = 0; c < 3; c++) { world_box[c] = r.wlo[c]; world_box[3 + c] = r.whi[c]; }
     if (world_to_object) memcpy(world_to_object, r.inv, sizeof r.inv);

@@ -645,6 +645,287 @@ def test_a_seeded_sequence_of_edits(gpu, capi, oracle):
         x.close()
 
 
+# ---- a list that grows after an attachment or a device set ---------------------------------------------------------------------------------
+N0, N1 = 5, 7
+
+
+def grown_after_attachment(capi, gpu, oracle):
+    """5 instances built; 1-2 attached with local matrices and 3 without, posed, updated; two more added and the scene built with no further attach
+    call; a second pose, updated.  Every step checked.  Instance 6 is added where joint 1 of a second skeleton stands.  Returns the scene, both
+    skeletons with their W, the transforms held and what the three are bound by"""
+    gm = gpu_models(capi, gpu)
+    parents = [hierarchy("random", 6, seed=1), hierarchy("chain", 3, seed=2)]
+    sks = [skeleton_of(capi, gpu, p) for p in parents]
+
+    def posed_by(k, seed):
+        trs = pose("unit", parents[k], seed=seed)
+        trs[:, 0:3] *= F(3.0)
+        sks[k].set_pose(trs)
+        return posed(parents[k], K.inverse_binds(len(parents[k]), 5), trs)[0]
+
+    W2 = posed_by(1, 91)
+    start = rows(random_xforms(N1, 3, spread=6.0))
+    start[6] = W2[1]
+    joints = np.array([4, 0, 2], np.uint32)
+    local = random_locals(2, 33)
+
+    def composed(W):
+        return np.concatenate([transforms_of(W, joints[:2], local), transforms_of(W, joints[2:], None)])
+
+    sc = gpu_scene(capi, gpu, list(start[:N0]))
+    sc.attach(1, sks[0], joints[:2], local)
+    sc.attach(3, sks[0], joints[2:])
+    W = posed_by(0, 92)
+    sc.update()
+    held = start.copy()
+    held[1:4] = composed(W)
+    check_equals_build(capi, gpu, oracle, sc, held[:N0], "attached, before the list grows")
+    for k in (5, 6):
+        sc.add_model(gm[k % 2], start[k])
+    assert same_bits(sc.transforms(), held), "adding instances changes no stored transform"
+    sc.build()
+    check_equals_build(capi, gpu, oracle, sc, held, "attach, lengthen, build")
+    for i in range(3):
+        assert sc.attachment(1 + i) == (sks[0], int(joints[i])), i
+    assert all(sc.attachment(i) is None for i in (0, 4, 5, 6))
+    W = posed_by(0, 93)
+    sc.update()
+    moved = composed(W)
+    assert not (moved == held[1:4]).all(axis=1).any(), "the second pose moves all three"
+    held[1:4] = moved
+    check_equals_build(capi, gpu, oracle, sc, held, "attach, lengthen, build, pose, update")
+    return sc, sks, parents, W2, held
+
+
+def test_attach_then_lengthen_then_build(gpu, capi, oracle):
+    """the bindings of 1-3 outlive two rt_scene_add_model and the build behind them: the build composes them, attachment() still answers, the new
+    instances have none, and the next pose moves the three and nothing else"""
+    sc, sks, _, _, _ = grown_after_attachment(capi, gpu, oracle)
+    sc.close()
+    for sk in sks:
+        sk.close()
+
+
+def test_lengthen_then_attach_into_the_new_tail(gpu, capi, oracle):
+    """on that scene: instance 6 attached to a second skeleton, instance 5 set from a device array: one update == a fresh build.  Instance 6 was
+    added where its joint stands, so transforms() gives the same bytes before and after the update, for all 7, whichever side holds them; the
+    second skeleton's next pose then moves 6 alone"""
+    sc, sks, parents, W2, held = grown_after_attachment(capi, gpu, oracle)
+    new = rows(random_xforms(1, 61, spread=6.0))
+    dev = gpu.upload(new)
+    sc.attach(6, sks[1], [1])
+    sc.set_transforms_device(5, dev.ptr, 1)
+    held[5] = new[0]
+    assert sc.attachment(6) == (sks[1], 1) and sc.attachment(5) is None and sc.attachment(3) == (sks[0], 2)
+    with pytest.raises(capi.RtError, match="2 instance transforms pending"):
+        sc.bvh(-1)
+    before = sc.transforms()
+    assert same_bits(before, held), "pending: the device-set floats come down on demand"
+    sc.update()
+    assert same_bits(sc.transforms(), before), "transforms() before and after the update"
+    check_equals_build(capi, gpu, oracle, sc, held, "lengthen, attach into the tail, device set")
+    trs = pose("unit", parents[1], seed=94)
+    trs[:, 0:3] *= F(3.0)
+    sks[1].set_pose(trs)
+    sc.update()
+    held[6] = posed(parents[1], K.inverse_binds(3, 5), trs)[0][1]
+    assert not same_bits(held[6], W2[1])
+    check_equals_build(capi, gpu, oracle, sc, held, "the second skeleton posed again")
+    sc.close(); dev.close()
+    for sk in sks:
+        sk.close()
+
+
+def test_device_held_then_lengthen_on_a_built_scene(gpu, capi, oracle):
+    """built, 1-3 set from device memory and left pending, two instances added: update is refused, transforms() still brings the three down from
+    the device, and the build reads them"""
+    start = rows(random_xforms(N1, 3, spread=6.0))
+    new = rows(random_xforms(3, 62, spread=6.0))
+    gm = gpu_models(capi, gpu)
+    sc = gpu_scene(capi, gpu, list(start[:N0]))
+    dev = gpu.upload(new)
+    sc.set_transforms_device(1, dev.ptr, 3)
+    for k in (5, 6):
+        sc.add_model(gm[k % 2], start[k])
+    with pytest.raises(capi.RtError, match=r"rt_scene_update: the scene has not been built since its last rt_scene_add_model \(an update builds no BLAS: "
+                                           r"rt_scene_build\)") as e:
+        sc.update()
+    assert e.value.code == -4
+    final = start.copy()
+    final[1:4] = new
+    assert same_bits(sc.transforms(), final)
+    assert same_bits(sc.transforms(1, 3), new) and same_bits(sc.transforms(3, 3), final[3:6])
+    sc.build()
+    check_equals_build(capi, gpu, oracle, sc, final, "device set, lengthen, build")
+    sc.close(); dev.close()
+
+
+def test_a_seeded_sequence_of_edits_with_a_growing_list(gpu, capi, oracle):
+    """test_a_seeded_sequence_of_edits' ops and its model of the state, on a list that grows: every 13th step adds an instance and builds (a
+    build applies what an update applies).  5 instances at first, 8 after the three growths; the scene == a fresh build of the model's state
+    after every update and every build"""
+    n, nj = N0, 6
+    r = np.random.default_rng(2025)
+    parents = [hierarchy("random", nj, seed=1), hierarchy("roots", nj, seed=2)]
+    sks = [skeleton_of(capi, gpu, p) for p in parents]
+    gm = gpu_models(capi, gpu)
+    Ws = []
+    for k in range(2):
+        trs = pose("unit", parents[k], seed=70 + k)
+        sks[k].set_pose(trs)
+        Ws.append(posed(parents[k], K.inverse_binds(nj, 5), trs)[0])
+    held = rows(random_xforms(n, 3, spread=6.0))
+    masks = np.full(n, 0xFF, np.uint8)
+    bound = [None] * n                                    # (skeleton index, joint, local or None)
+    sc = gpu_scene(capi, gpu, list(held))
+    keep = []
+    updates = growths = 0
+
+    def applied(what):
+        for i in range(n):
+            if bound[i] is not None:
+                k, joint, local = bound[i]
+                held[i] = transforms_of(Ws[k], np.array([joint]), None if local is None else local.reshape(1, 12))[0]
+        check_equals_build(capi, gpu, oracle, sc, held, what, None if masks.all() else masks)
+
+    for step in range(40):
+        op = "grow" if step % 13 == 6 else "update" if step % 4 == 3 else ("attach", "detach", "pose", "host", "device", "mask")[int(r.integers(0, 6))]
+        first = int(r.integers(0, n))
+        count = int(r.integers(1, min(4, n - first) + 1))
+        if op == "attach":
+            k = int(r.integers(0, 2))
+            joints = r.integers(0, nj, count).astype(np.uint32)
+            local = random_locals(count, 100 + step) if r.integers(0, 2) else None
+            sc.attach(first, sks[k], joints, local)
+            for i in range(count):
+                bound[first + i] = (k, int(joints[i]), None if local is None else local[i])
+        elif op == "detach":
+            sc.detach(first, count)
+            for i in range(first, first + count):
+                bound[i] = None
+        elif op == "pose":
+            k = int(r.integers(0, 2))
+            trs = pose("unit", parents[k], seed=200 + step)
+            trs[:, 0:3] *= F(3.0)
+            sks[k].set_pose(trs)
+            Ws[k] = posed(parents[k], K.inverse_binds(nj, 5), trs)[0]
+        elif op in ("host", "device"):
+            new = rows(random_xforms(count, 300 + step, spread=6.0))
+            if op == "host":
+                call = lambda: sc.set_transforms(first, new)
+            else:
+                keep.append(gpu.upload(new))
+                call = lambda: sc.set_transforms_device(first, keep[-1].ptr, count)
+            if any(bound[i] is not None for i in range(first, first + count)):
+                with pytest.raises(capi.RtError, match="rt_scene_detach_instances"):
+                    call()
+            else:
+                call()
+                held[first:first + count] = new
+        elif op == "mask":
+            m = masks.copy()
+            m[first:first + count] = r.choice(np.array([0, 0xFF, 1], np.uint8), count)
+            if m.any():
+                masks = m
+                sc.set_masks(0, masks)
+        elif op == "grow":
+            x = rows(random_xforms(1, 400 + step, spread=6.0))
+            sc.add_model(gm[n % 2], x[0])
+            held = np.concatenate([held, x])
+            masks = np.append(masks, np.uint8(0xFF))
+            bound.append(None)
+            n += 1
+            assert sc.attachment(n - 1) is None and sc.masks()[n - 1] == 0xFF
+            with pytest.raises(capi.RtError, match="has not been built since its last rt_scene_add_model"):
+                sc.update()
+            sc.build()
+            growths += 1
+            applied("step %d, a build of %d instances" % (step, n))
+        else:
+            sc.update()
+            updates += 1
+            applied("step %d" % step)
+        if op not in ("update", "grow"):
+            for i in range(n):
+                got = sc.attachment(i)
+                assert (got is None) == (bound[i] is None) and (got is None or got == (sks[bound[i][0]], bound[i][1])), (step, i)
+    assert updates >= 8 and growths >= 3 and n == N0 + growths
+    sc.close()
+    for x in sks + keep:
+        x.close()
+
+
+def test_refusals_at_the_edge_of_a_grown_list(gpu, capi, oracle):
+    """1-3 attached on a built scene, two instances added: a host set and a device set over 3-5 -- an attached instance, a free one and a new one
+    -- are refused as ever and change nothing; detaching 2-6, a range that reaches into the new tail, is OK and lets 2 and 3 go"""
+    start = rows(random_xforms(N1, 3, spread=6.0))
+    new = rows(random_xforms(3, 63, spread=6.0))
+    gm = gpu_models(capi, gpu)
+    parents = hierarchy("chain", 4, seed=0)
+    sk = skeleton_of(capi, gpu, parents)
+    trs = pose("unit", parents, seed=2)
+    trs[:, 0:3] *= F(3.0)
+    sk.set_pose(trs)
+    W, _ = posed(parents, K.inverse_binds(4, 5), trs)
+    joints = np.array([3, 1, 2], np.uint32)
+    sc = gpu_scene(capi, gpu, list(start[:N0]))
+    sc.attach(1, sk, joints)
+    for k in (5, 6):
+        sc.add_model(gm[k % 2], start[k])
+    dev = gpu.upload(new)
+    bindings = [None, (sk, 3), (sk, 1), (sk, 2), None, None, None]
+    for call in (lambda: sc.set_transforms(3, new), lambda: sc.set_transforms_device(3, dev.ptr, 3)):
+        with pytest.raises(capi.RtError, match=r"instance 3 is attached to joint 2 of a skeleton, which gives it its transform "
+                                               r"\(rt_scene_detach_instances lets it go\)") as e:
+            call()
+        assert e.value.code == -4
+        assert same_bits(sc.transforms(), start), "a refused setter changed a transform"
+        assert [sc.attachment(i) for i in range(N1)] == bindings
+    sc.detach(2, 5)
+    assert [sc.attachment(i) for i in range(N1)] == [None, (sk, 3)] + [None] * 5
+    sc.set_transforms(3, new)                             # (free again)
+    sc.build()
+    final = start.copy()
+    final[1] = W[3]
+    final[3:6] = new
+    check_equals_build(capi, gpu, oracle, sc, final, "after the refusals, the detachment and a build")
+    sc.close(); sk.close(); dev.close()
+
+
+def test_device_set_then_attached_before_any_update(gpu, capi, oracle):
+    """an instance set from device memory and attached before an update has applied the floats keeps them -- transforms() and, once detached
+    again, the update -- and attached it takes the joint's, its device-set neighbours theirs"""
+    start = rows(random_xforms(N0, 3, spread=6.0))
+    new = [rows(random_xforms(3, 64 + k, spread=6.0)) for k in range(2)]
+    parents = hierarchy("chain", 3, seed=0)
+    sk = skeleton_of(capi, gpu, parents)
+    trs = pose("unit", parents, seed=7)
+    trs[:, 0:3] *= F(3.0)
+    sk.set_pose(trs)
+    W, _ = posed(parents, K.inverse_binds(3, 5), trs)
+    sc = gpu_scene(capi, gpu, list(start))
+    devs = [gpu.upload(x) for x in new]
+    held = start.copy()
+    sc.set_transforms_device(1, devs[0].ptr, 3)
+    held[1:4] = new[0]
+    sc.attach(2, sk, [1])
+    assert same_bits(sc.transforms(), held), "attaching changes no stored transform, wherever it is stored"
+    sc.detach(2)
+    assert same_bits(sc.transforms(), held) and sc.attachment(2) is None
+    sc.update()
+    check_equals_build(capi, gpu, oracle, sc, held, "device set, attached, detached, updated")
+    sc.set_transforms_device(1, devs[1].ptr, 3)
+    held[1:4] = new[1]
+    sc.attach(2, sk, [1])
+    assert same_bits(sc.transforms(), held)
+    sc.update()
+    held[2] = W[1]
+    check_equals_build(capi, gpu, oracle, sc, held, "device set, attached, updated")
+    sc.close(); sk.close()
+    for d in devs:
+        d.close()
+
+
 # ---- the example -------------------------------------------------------------------------------------------------------------------------
 def fnv1a(raw):
     h = 2166136261
