@@ -97,6 +97,7 @@ SIGNATURES = {
     "rt_skeleton_clear_masks": (_i, [_p]),
     "rt_skeleton_get_num_masks": (_i, [_p, _pu]),
     "rt_skeleton_set_blend": (_i, [_p, _u32, _p]),
+    "rt_skeleton_solve_ik": (_i, [_p, _u32, _p]),
     "rt_skeleton_read_pose": (_i, [_p, _p]),
     "rt_skeleton_read_joints": (_i, [_p, _p]),
     "rt_skeleton_read_palette": (_i, [_p, _p]),
@@ -621,6 +622,26 @@ class Skeleton:
         a = layers if isinstance(layers, np.ndarray) and layers.dtype == T.SKELETON_LAYER else self.layers(layers)
         a = np.ascontiguousarray(a)
         _check(lib().rt_skeleton_set_blend(self.h, a.shape[0], _ptr(a)))
+
+    @staticmethod
+    def constraints(constraints):
+        """rtypes.SKELETON_IK[n] from a list of (kind, joint, target, pole, weight=1.0) tuples or dicts of those names.  kind "two_bone" |
+        "aim", or its number; target float[3] in skeleton space; pole float[3]: the pole of a two-bone chain, the axis of an aim."""
+        kinds = {"two_bone": T.IK_TWO_BONE, "aim": T.IK_AIM}
+        out = np.zeros(len(constraints), T.SKELETON_IK)
+        for k, c in enumerate(constraints):
+            if isinstance(c, dict):
+                c = (c["kind"], c["joint"], c["target"], c["pole"], c.get("weight", 1.0))
+            kind, joint, target, pole, weight = (tuple(c) + (1.0,))[:5]
+            out[k] = (kinds.get(kind, kind), joint, tuple(float(x) for x in target), tuple(float(x) for x in pole), weight)
+        return out
+
+    def solve_ik(self, constraints):
+        """solves two-bone reach and aim constraints against the pose the skeleton holds, on the device, and poses the skeleton with the
+        result: a list of (kind, joint, target, pole, weight=1.0) tuples or dicts (Skeleton.constraints), or an array of rtypes.SKELETON_IK"""
+        a = constraints if isinstance(constraints, np.ndarray) and constraints.dtype == T.SKELETON_IK else self.constraints(constraints)
+        a = np.ascontiguousarray(a)
+        _check(lib().rt_skeleton_solve_ik(self.h, a.shape[0], _ptr(a)))
 
     def _read(self, fn, width):
         out = np.empty((self.n_joints, width), np.float32)

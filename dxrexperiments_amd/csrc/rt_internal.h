@@ -365,6 +365,7 @@ struct rt_skeleton {
     uint64_t pose_count = 0;     // bumped by every pose set or sampled: a scene records it per attached instance at build / update (SceneInstance::seen_pose)
     uint32_t n_joints = 0, n_levels = 0;
     std::vector<uint32_t> level_offsets;     // n_levels + 1 (rt_skeleton.h)
+    std::vector<int32_t> parents;            // n_joints, as rt_skeleton_create took them: rt_skeleton_solve_ik finds a constraint's chain and checks independence with them
     DevBuf table;                // uint32[n_joints]: joint | parent << 16 in level order (rt_skeleton_pack_table)
     DevBuf d_level_offsets;      // uint32[n_levels + 1]
     DevBuf inverse_bind;         // float[n_joints][12]

@@ -1,6 +1,7 @@
 // rt_skeleton.h -- the host side of a skeleton (rt_skeleton_create, rt_skeleton_add_clip, rt_skeleton_set_time, rt_skeleton_set_blend):
-// validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip and the check of a layer list.  Host
-// code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp and tests/cpp/skeleton_blend_sanitized.cpp compile it alone.
+// validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip, the check of a layer list and the
+// check of a list of IK constraints (rt_skeleton_solve_ik).  Host code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp,
+// tests/cpp/skeleton_blend_sanitized.cpp and tests/cpp/ik_sanitized.cpp compile it alone.
 #pragma once
 
 #include <math.h>
@@ -8,7 +9,7 @@
 #include <stdint.h>
 #include <vector>
 
-#include "../../include/dxr_amd_types.h"     // rt_skeleton_layer and its constants
+#include "../../include/dxr_amd_types.h"     // rt_skeleton_layer, rt_skeleton_ik and their constants
 
 #define RT_SKELETON_MAX_JOINTS 65536u    // the skin's bone limit (RT_SKIN_MAX_BONES): a joint is a bone, and fits 16 bits
 #define RT_SKELETON_POSE_FLOATS 10u      // a joint of a pose: tx ty tz  qx qy qz qw  sx sy sz
@@ -140,4 +141,54 @@ static inline int rt_skeleton_validate_layers(uint32_t n_layers, const rt_skelet
         }
     }
     return 0;
+}
+
+// 0: the constraints describe one solve of a skeleton of n_joints joints with these parents, posed or not.  Else what is wrong, and bad[0]
+// names the first such constraint (0 for 1 and 2): 1 a null array, 2 n outside 1 .. RT_SKELETON_MAX_IK, 3 an unknown kind, 4 a joint
+// >= n_joints, 5 a two-bone tip with fewer than two ancestors (bad[2]: the joint), 6 a NaN weight, 7 two constraints that are not
+// independent, 8 a skeleton without a pose.  1 .. 7 are the caller's arguments (RT_ERR_INVALID_ARG), 8 the skeleton's state (RT_ERR_STATE);
+// every constraint is held to 3 .. 6, in that order, before any pair is held to 7, and 7 before 8.
+// Independence: a two-bone constraint WRITES the parent b of its tip and b's parent a, an aim its joint; every constraint READS its joint and
+// all of that joint's ancestors.  For 7 the readers are walked in order, each from its joint up to its root; the first joint met that another
+// constraint writes is bad[2], the reader bad[1], the lowest such writer bad[0].  (Two constraints that write the same joint are caught by
+// this: a constraint reads what it writes.)  Reads n entries of `constraints`, and nothing when it says 1 or 2; `bad` may be null.
+static inline int rt_skeleton_validate_ik(uint32_t n, const rt_skeleton_ik *constraints, uint32_t n_joints, const int32_t *parents, bool posed, uint32_t bad[3])
+{
+    uint32_t none[3];
+    if (!bad) bad = none;
+    bad[0] = bad[1] = bad[2] = 0u;
+    if (!constraints || !parents) return 1;
+    if (n < 1u || n > RT_SKELETON_MAX_IK) return 2;
+    for (uint32_t k = 0; k < n; k++) {
+        const rt_skeleton_ik &c = constraints[k];
+        int what = 0;
+        if (c.kind != RT_IK_TWO_BONE && c.kind != RT_IK_AIM) what = 3;
+        else if (c.joint >= n_joints) what = 4;
+        else if (c.kind == RT_IK_TWO_BONE && (parents[c.joint] < 0 || parents[parents[c.joint]] < 0)) what = 5;
+        else if (isnan(c.weight)) what = 6;
+        if (what) {
+            bad[0] = k;
+            if (what == 4 || what == 5) bad[2] = c.joint;
+            return what;
+        }
+    }
+    uint32_t written[2u * RT_SKELETON_MAX_IK], writer[2u * RT_SKELETON_MAX_IK], n_written = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        const rt_skeleton_ik &c = constraints[k];
+        if (c.kind == RT_IK_TWO_BONE) {
+            const uint32_t b = (uint32_t)parents[c.joint];
+            written[n_written] = (uint32_t)parents[b]; writer[n_written++] = k;
+            written[n_written] = b; writer[n_written++] = k;
+        } else {
+            written[n_written] = c.joint; writer[n_written++] = k;
+        }
+    }
+    for (uint32_t k = 0; k < n; k++)
+        for (int32_t j = (int32_t)constraints[k].joint; j >= 0; j = parents[j])
+            for (uint32_t e = 0; e < n_written; e++)     // (ascending by writer)
+                if (written[e] == (uint32_t)j && writer[e] != k) {
+                    bad[0] = writer[e]; bad[1] = k; bad[2] = (uint32_t)j;
+                    return 7;
+                }
+    return posed ? 0 : 8;
 }

@@ -153,6 +153,10 @@ namespace DXRFramework
         }
         void clearMasks() { ThrowIfFailed(rt_skeleton_clear_masks(mHandle)); }
         void setBlend(const rt_skeleton_layer *layers, uint32_t numLayers) { ThrowIfFailed(rt_skeleton_set_blend(mHandle, numLayers, layers)); }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): 1 .. RT_SKELETON_MAX_IK two-bone reach and aim
+        // constraints (rt_skeleton_ik: kind, joint, target, pole, weight) solved on the device against the pose the skeleton holds, and the
+        // skeleton posed with the result; nothing is uploaded.  The constraints of one call are independent; dependent ones take two calls
+        void solveIK(const rt_skeleton_ik *constraints, uint32_t count) { ThrowIfFailed(rt_skeleton_solve_ik(mHandle, count, constraints)); }
 
     private:
         RtSkeleton(RtContext::SharedPtr ctx, rt_skeleton *h) : mContext(ctx), mHandle(h) {}

@@ -38,8 +38,12 @@ SKELETON_MAX_LAYERS = 8
 SKELETON_CURRENT_POSE = 0xFFFFFFFF
 SKELETON_NO_MASK = 0xFFFFFFFF
 LAYER_BLEND, LAYER_ADDITIVE = 0, 1
+SKELETON_IK = np.dtype([("kind", "<u4"), ("joint", "<u4"), ("target", "<f4", (3,)), ("pole", "<f4", (3,)), ("weight", "<f4")])
+SKELETON_MAX_IK = 32
+IK_TWO_BONE, IK_AIM = 0, 1
 
 assert SKELETON_LAYER.itemsize == 20
+assert SKELETON_IK.itemsize == 36
 assert VERTEX.itemsize == 24 and CAMERA_PARAMS.itemsize == 80 and DEBUG_OPTIONS.itemsize == 44
 assert PER_FRAME_CONSTANTS.itemsize == 188 and MATERIAL_PARAMS.itemsize == 64 and BVH_NODE.itemsize == 32
 

@@ -359,6 +359,50 @@ int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */
  *           pose is counted once, and rt_skeleton_read_pose, the palette, the joints and attached instances all follow.  A blend is
  *           stateless, as rt_skeleton_set_time is: a call leaves nothing behind but the pose.  No slerp, no per-channel key times, no
  *           state machine: the caller moves the weights.
+ *   inverse kinematics (rt_skeleton_solve_ik): 1 .. RT_SKELETON_MAX_IK (32) CONSTRAINTS (rt_skeleton_ik, dxr_amd_types.h) solved in closed
+ *           form against the pose the skeleton holds; each rewrites rotation quaternions of that local pose.  fp32 throughout, every
+ *           product and every sum one rounded operation, no contraction, values taken as given: a weight is not clamped, NaN and inf are
+ *           no errors.  Only + - * / sqrt, comparisons and selects: no acos, no sin.  A clamp is a comparison and a select, never fmin or
+ *           fmax, so a NaN takes the same path everywhere, and every NaN written leaves as the quiet NaN 0x7FC00000.  The Hamilton product,
+ *           conj and the normalisation rule with its (0, 0, 0, 1) fallback are those of "blending" above.  On 3-vectors:
+ *             u.v = (ux vx + uy vy) + uz vz      u x v = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx)
+ *             unit(v) = v * (1 / sqrt(v.v)) if 0 < v.v < inf, else the zero vector and NO ANSWER
+ *             rot(q, v) = (v + (w * t)) + (q_xyz x t) with t = 2 * (q_xyz x v)
+ *             perp(u) = unit(u x e), e the coordinate axis on which |u| is smallest, the lowest index on a tie
+ *             between(u, v), for unit u and v: s = u + v; if s.s < 1e-6, or unit(s) has no answer, the half turn (perp(u), 0) as it stands;
+ *               otherwise, with h = unit(s), the quaternion (u x h, u.h) normalised by the rule.  (The half vector stays well conditioned
+ *               up to the half turn; (u x v, 1 + u.v) does not.)
+ *             turn(a, b) = between(unit(a), unit(b)), and the identity (0, 0, 0, 1) where either has no answer
+ *             M(p) of a 3x4 matrix and a point: M(p)_r = ((M[r][0] px + M[r][1] py) + M[r][2] pz) + M[r][3], the product's last column
+ *           PARENT SPACE.  A two-bone constraint names its TIP c; b = parent(c) is the middle joint, a = parent(b) the chain's root.  An aim
+ *           names the joint j it turns.  Where a (or j) is a root of the skeleton, target and pole are used as given, bit for bit.
+ *           Otherwise, with p its parent and I = inverse(W_p) -- the adjugate / determinant inverse of the instance transforms, every NaN
+ *           of I the quiet NaN; W_p as the skeleton's joints hold it, the pose before this call -- T = I(target) and P = I(pole).  An aim's
+ *           axis is not transformed: it lives in the joint's own frame.
+ *           TWO-BONE.  1: A and B are the stored quaternions of a and b, normalised by the rule.  2: pa = t_a, pb = L_a(t_b),
+ *           pc = L_a(L_b(t_c)), L_a and L_b by "local" from (t_a, A, s_a) and (t_b, B, s_b).  3: l1 = sqrt((pb - pa).(pb - pa)),
+ *           l2 = sqrt((pc - pb).(pc - pb)), g = T - pa, n = unit(g), d = sqrt(g.g).  4: lo = |l1 - l2|, hi = l1 + l2; if d < lo then
+ *           d = lo; then if d > hi then d = hi.  5: if n has no answer, or not d > 0, or not l1 > 0, or not l2 > 0, the solved rotations
+ *           are A and B themselves.  6: otherwise x = ((l1 l1 - l2 l2) + d d) / (2 d); hh = l1 l1 - x x; h = sqrt(hh if hh > 0 else 0);
+ *           m = unit(k - n * (k.n)) with k = P - pa; if that has no answer the same with k = pb - pa; if that has none either, perp(n);
+ *           pb' = (pa + n * x) + m * h and pc' = pa + n * d; Da = turn(pb - pa, pb' - pa); A' = normalised(Da (x) A);
+ *           b1 = pa + rot(Da, pb - pa) and c1 = pa + rot(Da, pc - pa); Db = turn(c1 - b1, pc' - b1);
+ *           B' = normalised((conj(A') (x) (Db (x) A')) (x) B).
+ *           AIM.  Q is the stored quaternion of j, normalised; v = unit(rot(Q, axis)) and w = unit(T - t_j); if either has no answer
+ *           Q' = Q, otherwise Q' = normalised(between(v, w) (x) Q).
+ *           WEIGHT.  Each written quaternion goes from the normalised input A towards the solved A' by the RT_LAYER_BLEND rule:
+ *           d = ((Ax A'x + Ay A'y) + Az A'z) + Aw A'w; if d < 0 every component of A' is negated; q_c = A_c + (weight * (A'_c - A_c)),
+ *           normalised by the rule.  A weight of 0 therefore writes normalised(A): the stored quaternion, normalised (and once more, by the rule).
+ *           A two-bone constraint writes the quaternions of a and b, an aim that of j.  Every translation, every scale, and the rotation
+ *           of every joint that no constraint turns keep their bits.  All constraints of one call are solved side by side from the same
+ *           input pose, so they must be INDEPENDENT: every constraint reads its tip (its aimed joint) and all of that joint's ancestors,
+ *           and no joint written by one constraint may be read by another.  Four limbs of one body pass; an aim on a hand whose arm is
+ *           solved in the same call does not: that is two calls, the second seeing the first's pose.  The result is posed exactly as
+ *           rt_skeleton_set_pose poses, and the pose is counted once.
+ *           Geometry: the tip reaches the clamped target exactly, up to rounding, when a and b carry uniform scale; ancestors may be any
+ *           invertible affine matrices.  Under non-uniform scale on a or b the answer is still this definition, but the tip's position is
+ *           approximate.  Twist about the bones is whatever the input pose had.  No joint limits, no chains longer than two bones, no CCD
+ *           or FABRIK.
  * Validation is done on the host, and nothing changes when a call refuses.  Setting a pose touches no model and no scene.
  * rt_skeleton_create: a null argument is RT_ERR_INVALID_ARG; so is n_joints outside 1 .. 65536 (the skin's bone limit), and a parent that is
  * neither -1 nor < j -- parents come before children -- (the message names the joint).  inverse_bind: n_joints x 12, 3x4 row-major, as
@@ -408,6 +452,17 @@ int rt_skeleton_get_num_masks(const rt_skeleton *sk, uint32_t *n);
  * there are), RT_SKELETON_CURRENT_POSE before the first pose (the message names rt_skeleton_set_pose).  Every layer is held to the first
  * group before any is held to the second.  One layer without a mask is rt_skeleton_set_time, bit for bit. */
 int rt_skeleton_set_blend(rt_skeleton *sk, uint32_t n_layers, const rt_skeleton_layer *layers /* n_layers, host */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): solves n (1 .. 32) two-bone reach and aim constraints against the
+ * pose the skeleton holds -- from rt_skeleton_set_pose, _set_time, _set_blend or an earlier _solve_ik -- by the definition above ("inverse
+ * kinematics"), rewrites the rotation quaternions of the joints it turns and poses the skeleton with the result: two kernels on the context's
+ * stream, the solve and the pose; nothing is uploaded and nothing waits -- the constraints travel as a kernel argument.  Stateless, as a blend
+ * is.  A frame is _set_blend or _set_time, _solve_ik, rt_model_set_bones_from_skeleton, rt_scene_update.  Validation runs on the host before
+ * anything is queued, and nothing changes when the call refuses; the message names the constraint.  RT_ERR_INVALID_ARG: a null argument, n
+ * outside 1 .. 32, an unknown kind, a joint >= n_joints (the message gives both numbers), a two-bone tip with fewer than two ancestors (the
+ * message names the joint and says why), a NaN weight, two constraints that are not independent (the message names both constraints and the
+ * shared joint).  RT_ERR_STATE: the skeleton has no pose yet (the message names rt_skeleton_set_pose).  Every constraint is held to the first
+ * group before the state is looked at. */
+int rt_skeleton_solve_ik(rt_skeleton *sk, uint32_t n, const rt_skeleton_ik *constraints /* n, host */);
 /* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local pose last set or sampled.  This and the calls below
  * that return what a pose made are RT_ERR_STATE before the first pose (the message names rt_skeleton_set_pose); the reads synchronise. */
 int rt_skeleton_read_pose(rt_skeleton *sk, float *trs /* n_joints x 10 */);

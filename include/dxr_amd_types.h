@@ -194,6 +194,18 @@ typedef struct rt_skeleton_layer {
     uint32_t mode;               /* RT_LAYER_BLEND | RT_LAYER_ADDITIVE                                       */
 } rt_skeleton_layer;
 
+/* One constraint of an inverse-kinematics solve (rt_skeleton_solve_ik; include/dxr_amd.h "Posed skeletons", "inverse kinematics"). */
+#define RT_SKELETON_MAX_IK 32u
+#define RT_IK_TWO_BONE 0u
+#define RT_IK_AIM      1u
+typedef struct rt_skeleton_ik {
+    uint32_t kind;       /* RT_IK_TWO_BONE | RT_IK_AIM */
+    uint32_t joint;      /* two-bone: the TIP c; its parent b is the middle joint, b's parent a the chain's root.  aim: the joint that is turned */
+    float    target[3];  /* skeleton space: the space the W_j of rt_skeleton_read_joints live in */
+    float    pole[3];    /* two-bone: a point in skeleton space the middle joint bends towards.  aim: the axis, in the joint's own frame, that is to point at the target */
+    float    weight;     /* taken as given, not clamped */
+} rt_skeleton_ik;
+
 /* Status codes returned by every export. */
 #define RT_OK                 0
 #define RT_ERR_INVALID_ARG   -1
@@ -215,6 +227,7 @@ static_assert(sizeof(rt_per_frame_constants) == 188, "PerFrameConstants is 188 B
 static_assert(sizeof(rt_material_params) == 64, "MaterialParams is 64 B");
 static_assert(sizeof(rt_bvh_node) == 32, "BVH node is 32 B");
 static_assert(sizeof(rt_skeleton_layer) == 20, "a blend layer is 20 B");
+static_assert(sizeof(rt_skeleton_ik) == 36, "an IK constraint is 36 B");
 #endif
 
 #endif /* DXR_AMD_TYPES_H */
