@@ -46,13 +46,43 @@ its current vertices -- the skin's rest pose, the morph base -- and no reader re
 27. set_bones_from(skeleton) returns ERR_STATE before the skeleton's first pose, for a model without a skin, and for a skin whose n_bones is
     not the skeleton's n_joints; otherwise it is set_bones with the skeleton's palette AS IT IS AT THE CALL: a pose set before the update
     does not reach the vertices.  A skeleton may be destroyed right after the call.
-Vertex arithmetic is that of skin_cases.skinned, deform_cases.normals_of, morph_cases.morphed, skeleton_cases.posed and skeleton_cases.sampled,
-each held byte for byte to its kernel by the feature's own tests."""
+Device-sourced transforms, attached instances, blends and inverse kinematics (include/dxr_amd.h "Attached instances", "blending", "inverse
+kinematics"; DESIGN.md "update == build, with attachments").  A binding is (skeleton OBJECT, joint, local or none, the count of that
+skeleton's poses that the scene last applied); a skeleton counts its poses.
+28. set_transforms_mem(host) is set_transforms; with device memory the floats, arguments, refusals and the STALE rule are the same.
+    transforms() returns the floats held, pending or applied.
+29. attach(first, skeleton, joints, locals | None) refuses a range beyond the instances (ERR_STATE) first, then a joint >= n_joints
+    (ERR_INVALID_ARG); count 0 is a no-op.  A refused call changes nothing.
+30. A successful attach stores the binding and changes no stored transform.  On an updatable scene it marks those instances pending and the
+    scene stale; on an unbuilt scene it only stores.  Attaching again replaces the binding, and a call without locals clears the earlier
+    local.  attachment(i) answers (skeleton, joint) or None.
+31. A transform setter of either kind whose range (count > 0) holds an attached instance is ERR_STATE and changes nothing.
+32. detach keeps the floats the last successful update or build gave the instance and marks nothing; detaching unattached instances is a
+    no-op; a range beyond the instances is ERR_STATE.
+33. Posing a skeleton, by any of its producers, touches no scene: a fresh scene stays fresh and readable.  The next update of a scene with
+    an instance attached to that skeleton is nevertheless a real update: pending() then holds "poses".
+34. A successful update or build gives EVERY attached instance, hidden ones too, compose(W[joint], local), or W[joint] bit for bit without a
+    local; W is the skeleton's joints as they are at the update, not at the attach.  A composed transform whose twelve floats are the
+    identity's is the identity for everything downstream (the fresh build is handed the floats and decides as the update did).
+35. update or build with an attachment to a skeleton that has never been posed is ERR_STATE and keeps everything pending, also together
+    with rule 12.
+36. A binding refers to the skeleton object, not to its slot: after "destroy right behind set_bones_from" the attached instances keep
+    following nobody, poses of the replacement do not move them, and attachment(i) still answers the old skeleton.
+37. add_mask / clear_masks / num_masks: ids start at 0, clearing restarts them, the pose stays.
+38. set_blend: return codes by skeleton_blend_cases.validate (2 - 6 ERR_INVALID_ARG, 7 - 9 ERR_STATE); a refusal leaves pose, joints and
+    palette as they were; otherwise pose = blended(...), `current` being the pose held, posed as set_pose poses.
+39. solve_ik: return codes by ik_cases.validate (2 - 7 ERR_INVALID_ARG, 8 ERR_STATE); otherwise pose = ik_cases.solved(parents, pose, the
+    joints before the call, constraints), posed.
+40. Each successful set_pose, set_time, set_blend and solve_ik counts as exactly one pose for rule 33; a refused one counts as none.
+Vertex arithmetic is that of skin_cases.skinned, deform_cases.normals_of, morph_cases.morphed, skeleton_cases.posed, skeleton_cases.sampled,
+skeleton_cases.compose, skeleton_blend_cases.blended and ik_cases.solved, each held byte for byte to its kernel by the feature's own tests."""
 import numpy as np
 
 from deform_cases import normals_of
 from morph_cases import morphed
-from skeleton_cases import posed, sampled
+import ik_cases
+import skeleton_blend_cases
+from skeleton_cases import compose, posed, sampled
 from skin_cases import canonical_nans, skinned
 
 OK, ERR_INVALID_ARG, ERR_STATE = 0, -1, -4
@@ -60,6 +90,17 @@ UNBUILT, FRESH, STALE = "never built since the last add", "fresh", "stale"
 VERTEX = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3)])          # include/dxr_amd_types.h rt_vertex: 24 bytes
 MAX_INFLUENCES, MAX_BONES, MAX_TARGETS = 8, 65536, 65536
 IDENTITY = None                                                             # an instance transform: None, or float32[12] (3x4 row major)
+IDENTITY_FLOATS = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
+
+
+def floats_of(x):
+    """the twelve floats of an instance transform"""
+    return IDENTITY_FLOATS if x is None else np.asarray(x, np.float32).reshape(12)
+
+
+def is_identity(x):
+    """the floats are the identity's (rule 34): what makes a one-instance scene single-level"""
+    return x is None or bool(np.array_equal(floats_of(x), IDENTITY_FLOATS))
 
 
 class Model:
@@ -181,11 +222,42 @@ class Skeleton:                         # rules 25, 26
         self.inverse_bind = np.array(inverse_bind, np.float32, copy=True).reshape(-1, 12)
         self.pose = self.joints = self.palette = None       # float32[n, 10], [n, 12], [n, 12] once posed
         self.clips = []                                     # [(times float32[K], keys float32[K, n, 10])]; the id is the place
+        self.masks = []                                     # [float32[n]]; the id is the place (rule 37)
+        self.poses = 0                                      # how many times it has been posed (rule 40)
+        self.uid = None                                     # which skeleton object this is: World numbers them as they are made (rule 36)
 
     def set_pose(self, trs):
         self.pose = np.array(trs, np.float32, copy=True).reshape(len(self.parents), 10)
         self.joints, self.palette = posed(self.parents, self.inverse_bind, self.pose)
+        self.poses += 1
         return OK
+
+    def add_mask(self, weights):                        # rule 37
+        self.masks.append(np.array(weights, np.float32, copy=True).reshape(len(self.parents)))
+        return OK
+
+    def clear_masks(self):
+        self.masks = []
+        return OK
+
+    def num_masks(self):
+        return len(self.masks)
+
+    def set_blend(self, layers):
+        """layers: [(clip or None for the current pose, time, weight, mask or None, mode)]: rule 38"""
+        B = skeleton_blend_cases
+        records = [(B.CURRENT_POSE if c is None else c, t, w, B.NO_MASK if m is None else m, mode) for c, t, w, m, mode in layers]
+        what = B.validate(records, len(self.clips), len(self.masks), self.pose is not None)[0]
+        if what:
+            return ERR_INVALID_ARG if what <= 6 else ERR_STATE
+        return self.set_pose(B.blended(self.clips, self.masks, layers, current=self.pose))
+
+    def solve_ik(self, constraints):
+        """constraints: [(kind, joint, target, pole, weight)]: rule 39"""
+        what = ik_cases.validate(constraints, self.parents, self.pose is not None)[0]
+        if what:
+            return ERR_INVALID_ARG if what <= 7 else ERR_STATE
+        return self.set_pose(ik_cases.solved(self.parents, self.pose, self.joints, constraints))
 
     def add_clip(self, times, keys):
         times = np.asarray(times, np.float32).reshape(-1)
@@ -206,7 +278,8 @@ class Skeleton:                         # rules 25, 26
         return self.set_pose(sampled(self.clips[clip][0], self.clips[clip][1], t))
 
     def snapshot(self):
-        return (self.parents.tobytes(), self.inverse_bind.tobytes(), [(t.tobytes(), k.tobytes()) for t, k in self.clips], self.readers())
+        return (self.parents.tobytes(), self.inverse_bind.tobytes(), [(t.tobytes(), k.tobytes()) for t, k in self.clips], self.readers(),
+                [m.tobytes() for m in self.masks], self.poses, self.uid)
 
     def readers(self):
         """what read_pose, read_joints and read_palette return, NaNs canonical; None before the first pose"""
@@ -223,6 +296,8 @@ class Scene:
         self.pending_masks = False      # a setter flipped some instance's visibility since then
         self.pending_models = set()     # id() of the models whose vertices were set since then
         self.applied_vis = None         # the visible sub-list the TLAS stands for
+        self.att = {}                   # instance -> dict(sk=Skeleton, joint=int, local=float32[12] or None,
+        #                                                   seen=the skeleton's poses at the last apply, or None)
 
     def add_model(self, mi, xform=IDENTITY):
         self.inst.append((mi, xform))
@@ -244,6 +319,8 @@ class Scene:
     def set_transforms(self, first, xforms):
         if self._range(first, len(xforms)) != OK:
             return ERR_STATE
+        if any(first + k in self.att for k in range(len(xforms))):
+            return ERR_STATE                                   # rule 31
         for k, x in enumerate(xforms):
             self.inst[first + k] = (self.inst[first + k][0], None if x is None else np.array(x, np.float32).reshape(12))
         if xforms and self.state != UNBUILT:                   # rules 1, 2, 6
@@ -253,6 +330,47 @@ class Scene:
 
     def set_transform(self, i, x):
         return self.set_transforms(i, [x]) if i < len(self.inst) else ERR_STATE
+
+    def set_transforms_mem(self, first, xforms, mem):       # rule 28: where the floats come from changes nothing
+        assert mem in ("host", "device")
+        return self.set_transforms(first, xforms)
+
+    def transforms(self):
+        """float32[n, 12]: the floats held, pending or applied"""
+        return np.array([floats_of(x) for _, x in self.inst], np.float32).reshape(-1, 12)
+
+    def attach(self, first, skeleton, joints, locals=None):  # rules 29, 30
+        joints = [int(j) for j in np.asarray(joints).reshape(-1)]
+        if self._range(first, len(joints)) != OK:
+            return ERR_STATE
+        if any(j >= len(skeleton.parents) for j in joints):
+            return ERR_INVALID_ARG
+        for k, j in enumerate(joints):
+            local = None if locals is None else np.array(np.asarray(locals, np.float32).reshape(-1, 12)[k], np.float32, copy=True)
+            self.att[first + k] = dict(sk=skeleton, joint=j, local=local, seen=None)
+        if joints and self.state != UNBUILT:
+            self.state = STALE
+            self.pending_xforms.update(range(first, first + len(joints)))
+        return OK
+
+    def detach(self, first, count):                         # rule 32
+        if self._range(first, count) != OK:
+            return ERR_STATE
+        for i in range(first, first + count):
+            self.att.pop(i, None)
+        return OK
+
+    def attachment(self, i):
+        a = self.att.get(i)
+        return None if a is None else (a["sk"], a["joint"])
+
+    def unposed(self):
+        """an instance is attached to a skeleton that has never been posed (rule 35)"""
+        return any(a["sk"].pose is None for a in self.att.values())
+
+    def posed_since(self):
+        """the attached instances whose skeleton has been posed since the scene last applied it (rule 33)"""
+        return sorted(i for i, a in self.att.items() if a["sk"].pose is not None and a["seen"] != a["sk"].poses)
 
     def set_masks(self, first, masks):
         masks = [int(m) & 0xFF for m in masks]
@@ -272,7 +390,7 @@ class Scene:
         return [k for k, m in enumerate(self.masks) if m]
 
     def pending(self):
-        """the kinds of edit the next update applies: a subset of {"transforms", "masks", "vertices"}"""
+        """the kinds of edit the next update applies: a subset of {"transforms", "masks", "vertices", "poses"}"""
         kinds = set()
         if self.pending_xforms:
             kinds.add("transforms")
@@ -280,6 +398,8 @@ class Scene:
             kinds.add("masks")
         if self.pending_models:
             kinds.add("vertices")
+        if self.posed_since():
+            kinds.add("poses")
         return frozenset(kinds)
 
     def update(self):
@@ -289,21 +409,28 @@ class Scene:
         kinds = self.pending()
         if not kinds:
             return OK, kinds                                   # rule 11
-        if not self.visible():
-            return ERR_STATE, None                             # rule 12: everything pending kept
+        if not self.visible() or self.unposed():
+            return ERR_STATE, None                             # rules 12, 35: everything pending kept
         self._applied()
         return OK, kinds
 
     def build(self):
         if not self.inst:
             return ERR_INVALID_ARG, None
-        if not self.visible():
-            return ERR_STATE, None                             # rule 12
+        if not self.visible() or self.unposed():
+            return ERR_STATE, None                             # rules 12, 35
         kinds = self.pending()
-        self._applied()
+        self._applied(everything=True)
         return OK, kinds
 
-    def _applied(self):
+    def _applied(self, everything=False):
+        for i, a in self.att.items():                          # rule 34: W as it is now; an instance that has seen this pose holds its floats already
+            if not everything and a["seen"] == a["sk"].poses:
+                continue
+            w = a["sk"].joints[a["joint"]]
+            x = w.copy() if a["local"] is None else compose(w, a["local"])[0]
+            self.inst[i] = (self.inst[i][0], np.array(x, np.float32).reshape(12))
+            a["seen"] = a["sk"].poses
         self._clear_pending()
         self.state = FRESH
         self.applied_vis = self.visible()
@@ -317,14 +444,26 @@ class World:
 
     def __init__(self):
         self.models, self.scenes, self.skeletons = [], [], []
+        self.made = 0                   # skeleton objects made so far: the next one's uid
 
     def add_model(self, verts, idx):
         self.models.append(Model(verts, idx))
         return len(self.models) - 1
 
     def add_skeleton(self, parents, inverse_bind):
-        self.skeletons.append(Skeleton(parents, inverse_bind))
+        self.skeletons.append(self._skeleton(parents, inverse_bind))
         return len(self.skeletons) - 1
+
+    def _skeleton(self, parents, inverse_bind):
+        sk = Skeleton(parents, inverse_bind)
+        sk.uid, self.made = self.made, self.made + 1
+        return sk
+
+    def replace_skeleton(self, k):
+        """the skeleton of slot k is destroyed; a new one of the same joints, never posed, without clips or masks, takes the slot.  Scenes
+        that hold instances attached to the old one keep it (rule 36)"""
+        old = self.skeletons[k]
+        self.skeletons[k] = self._skeleton(old.parents, old.inverse_bind)
 
     def add_scene(self):
         self.scenes.append(Scene(self.models))
@@ -337,10 +476,15 @@ class World:
         return ([(m.verts.tobytes(), None if m.skin is None else (m.skin["rest"].tobytes(), m.skin["bones"].tobytes(), m.skin["weights"].tobytes(), m.skin["n_bones"]), morph(m.morph))
                  for m in self.models], [k.snapshot() for k in self.skeletons],
                 [([(mi, None if x is None else np.asarray(x, np.float32).tobytes()) for mi, x in s.inst], list(s.masks), s.state, sorted(s.pending_xforms),
-                  s.pending_masks, len(s.pending_models)) for s in self.scenes])
+                  s.pending_masks, len(s.pending_models),
+                  sorted((i, a["sk"].uid, a["sk"].poses, a["joint"], None if a["local"] is None else a["local"].tobytes(), a["seen"])
+                         for i, a in s.att.items()))
+                 for s in self.scenes], self.made)
 
     def readers(self):
         """what the library's readers can return of the state -- geometry(), the skin and morph queries, masks(), whether a scene is readable,
-        a posed skeleton's arrays -- and nothing of the hidden arrays: the rest pose and the morph base"""
-        return ([(m.verts.tobytes(), m.skin_query(), m.morph_query()) for m in self.models], [k.readers() for k in self.skeletons],
-                [(list(s.masks), s.state) for s in self.scenes])
+        a posed skeleton's arrays and its mask count, a scene's transforms() and attachments -- and nothing of the hidden arrays: the rest
+        pose and the morph base, the local matrices and what a scene has seen of a skeleton's poses"""
+        return ([(m.verts.tobytes(), m.skin_query(), m.morph_query()) for m in self.models], [(k.readers(), k.num_masks()) for k in self.skeletons],
+                [(list(s.masks), s.state, s.transforms().tobytes(), [a and (a[0].uid, a[1]) for a in map(s.attachment, range(len(s.inst)))])
+                 for s in self.scenes])

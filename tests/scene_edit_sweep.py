@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised sweep over SEQUENCES of scene edits: "update == build"  applied to 30 - 60 interleaved operations instead of
+"""Randomised sweep over SEQUENCES of scene edits: "update == build"  applied to some 30 - 75 interleaved operations instead of
 one.  tests/test_gpu_scene_edit_sweep.py runs a bounded number of sequences under `pytest -m gpu`; by hand, on a GPU box, for as long as wanted:
 
     python tests/scene_edit_sweep.py [sequences] [seed]
@@ -28,6 +28,33 @@ and the morph base cannot be read back, so every plan ends with an EPILOGUE: for
 set_morph_weights, then one set_bones, then the updates -- a hidden array that drifted anywhere in the sequence reaches geometry() and the last
 checkpoint.
 
+Transforms from device memory, attached instances, blends and inverse kinematics ride along too (rules 28 - 40).  The new kinds:
+set_transforms_mem (host or device memory), attach (instances to joints of the sequence's skeleton, with local matrices of random_xforms or
+without), detach, skeleton_add_mask / skeleton_clear_masks (skeleton_blend_cases.masks_for), skeleton_set_blend (layer lists of
+skeleton_blend_cases.layer_list over the skeleton's clips and masks: 1 - 8 layers, both modes, its WEIGHTS, the base sometimes the pose the
+skeleton holds) and skeleton_solve_ik (1 - 3 independent constraints: a two-bone tip among the joints that have two ancestors, otherwise an
+aim; targets and poles 0.5 - 3 from the origin, weights of ik_cases.WEIGHTS).  Poses stay gentle: no NaN or inf family.  A transform setter
+draws an attached instance -- which refuses it -- only now and then.  A binding holds the skeleton OBJECT: after "destroy right behind
+set_bones_from" the instances attached to the old skeleton follow nobody, and the backend compares attachment(i) by handle.  An update or
+build of a scene attached to a skeleton that has no pose is refused, so op_update sometimes lets it be refused and then poses the skeleton (by
+any of the four producers, each counted as one pose), sometimes poses it first.  Motifs: pose_only_update (a fresh scene, a pose, a probe
+that must SUCCEED, an update that applies {"poses"} alone), posed_and_changed (one instance attached and of a model whose vertices are
+pending), attached_hidden (hide an attached instance, pose, update, show, update), attached_single (a one-instance scene follows a root
+posed to the identity exactly, away from it and back), pose_while_refused (hide all, pose, the refused update, show one, the update applies
+all of it), unposed_then_posed (attach to the replacement of a destroyed skeleton, the refused update -- and the blend on the current pose and
+the solve that are refused for want of a pose --, a pose, the update), destroyed_under_attachment (set_bones_from destroys the skeleton that
+an instance follows; a pose of the replacement and an update that must be the no-op), two_scenes_one_skeleton (a shared model, both scenes
+attached, one pose, the updates in either order), character_and_props (a frame is set_blend, solve_ik, set_bones_from, update, the same
+skeleton posing the character and carrying instances), grown_with_bindings (an attachment and a device set, add_model -- then sometimes an
+attach, a device set or a detach that reaches the new instance --, the build, a pose, the update), detach_keeps (detach between a pose and
+the update: the first pose stays; attach and detach with no update between: the old floats stay), blend_on_current (solve_ik, then a blend
+whose base is the current pose), reattach_without_local.  Refusals are drawn in turn from a place that moves with the sequence number, so a
+handful of sequences meets every one.  The EPILOGUE also gives every skeleton that a scene is attached to and that has no pose one pose,
+so that no sequence ends on a refused update.  A checkpoint compares, besides the above, transforms() of the scene and of every other fresh
+scene with the model's floats, attachment(i) of every instance, and every skeleton's mask count; the fresh scene it builds is handed the
+composed transforms (DESIGN.md "update == build, with attachments"); and the first scene renders its frames also behind every update whose
+only cause was a pose.
+
 Every operation goes to the GPU library and to the shadow model of tests/scene_edit_model.py, and the return codes must agree.  Every successful
 update or build is a CHECKPOINT: the scene is compared, bit for bit, with a fresh GPU scene built over fresh models made from the shadow model's
 vertices and with a fresh oracle scene -- the TLAS (under the index mapping of test_gpu_instance_masks when instances are hidden), every
@@ -47,9 +74,11 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
+import ik_cases  # noqa: E402
 import morph_cases  # noqa: E402
 import option_cases  # noqa: E402
 import scene_edit_model as M  # noqa: E402
+import skeleton_blend_cases  # noqa: E402
 import skeleton_cases  # noqa: E402
 import skin_cases  # noqa: E402
 from deform_cases import grid_mesh, slivers  # noqa: E402
@@ -67,10 +96,13 @@ N_BONES = 6
 WIDE_BONES = skin_cases.lds_bones() + 1                                 # a palette that does not fit the skin kernel's LDS
 WEIGHT_FAMILIES = ("convex", "zeros", "wild")                           # (no nan_inf: a NaN vertex is the deform tests' subject and would blind the rays)
 CAMERA = np.array([0, 3, 24, 0, 0, 0, 0, 1, 0, 0.8, W / H], np.float32)
-SCENE_OPS = ("set_transform", "set_transforms", "set_mask", "set_masks", "add_model", "build", "update", "probe")
-SKELETON_OPS = ("skeleton_set_pose", "skeleton_add_clip", "skeleton_clear_clips", "skeleton_set_time")
+SCENE_OPS = ("set_transform", "set_transforms", "set_mask", "set_masks", "add_model", "build", "update", "probe", "set_transforms_mem", "attach", "detach")
+SKELETON_OPS = ("skeleton_set_pose", "skeleton_add_clip", "skeleton_clear_clips", "skeleton_set_time", "skeleton_add_mask", "skeleton_clear_masks",
+                "skeleton_set_blend", "skeleton_solve_ik")
+POSE_OPS = ("skeleton_set_pose", "skeleton_set_time", "skeleton_set_blend", "skeleton_solve_ik")       # each counts as one pose (rule 40)
 REFUSABLE = ("set_transform", "set_transforms", "set_mask", "set_masks", "set_vertices", "set_positions", "set_skin", "set_bones", "update", "build",
-             "set_morph_targets", "set_morph_weights", "skeleton_set_time", "skeleton_add_clip", "set_bones_from")
+             "set_morph_targets", "set_morph_weights", "skeleton_set_time", "skeleton_add_clip", "set_bones_from", "set_transforms_mem", "attach", "detach",
+             "skeleton_set_blend", "skeleton_solve_ik")
 ALL_KINDS = SCENE_OPS + ("set_vertices", "set_positions", "recompute_normals", "set_skin", "clear_skin", "set_bones", "set_morph_targets", "clear_morph_targets",
                          "set_morph_weights") + SKELETON_OPS + ("set_bones_from",)
 # why a call of a new kind is refused (op["why"]): each of these is required of the GPU test's seeds
@@ -78,11 +110,29 @@ REFUSALS = (("set_morph_targets", "target_offsets[0] != 0"), ("set_morph_targets
             ("set_morph_targets", "indices do not ascend strictly"), ("set_morph_targets", "65537 targets"), ("set_morph_weights", "no targets"),
             ("skeleton_set_time", "unknown clip"), ("skeleton_set_time", "NaN time"), ("skeleton_add_clip", "a time that is not finite"),
             ("skeleton_add_clip", "times do not ascend strictly"), ("set_bones_from", "before the first pose"), ("set_bones_from", "no skin"),
-            ("set_bones_from", "n_bones != n_joints"))
+            ("set_bones_from", "n_bones != n_joints"),
+            # rules 28 - 40
+            ("attach", "beyond the instances"), ("attach", "a joint >= n_joints"), ("attach", "beyond the instances and a joint >= n_joints"),
+            ("set_transform", "over an attached instance"), ("set_transforms", "over an attached range"),
+            ("set_transforms_mem", "over an attached range, from device"), ("detach", "beyond the instances"),
+            ("update", "an unposed attachment"), ("build", "an unposed attachment"),
+            ("skeleton_set_blend", "9 layers"), ("skeleton_set_blend", "additive layer 0"), ("skeleton_set_blend", "the current pose on layer 1"),
+            ("skeleton_set_blend", "NaN time"), ("skeleton_set_blend", "unknown clip"), ("skeleton_set_blend", "unknown mask"),
+            ("skeleton_set_blend", "the current pose before the first pose"), ("skeleton_set_blend", "an unknown clip and a NaN time"),
+            ("skeleton_solve_ik", "33 constraints"), ("skeleton_solve_ik", "unknown kind"), ("skeleton_solve_ik", "a joint >= n_joints"),
+            ("skeleton_solve_ik", "a tip without two ancestors"), ("skeleton_solve_ik", "NaN weight"), ("skeleton_solve_ik", "two dependent constraints"),
+            ("skeleton_solve_ik", "no pose yet"))
 MOTIFS = ("morph_then_skin", "skin_then_morph", "reskin_posed", "retarget", "rest_morph_keeps_fresh", "clear_skin_redirects", "character_frame",
-          "skeleton_mismatch", "shared_character")
-SUBSETS = [frozenset(x) for x in (("transforms",), ("masks",), ("vertices",), ("transforms", "masks"), ("transforms", "vertices"), ("masks", "vertices"),
-                                  ("transforms", "masks", "vertices"))]
+          "skeleton_mismatch", "shared_character",
+          "pose_only_update", "posed_and_changed", "attached_hidden", "attached_single", "pose_while_refused", "unposed_then_posed",
+          "destroyed_under_attachment", "two_scenes_one_skeleton", "character_and_props", "grown_with_bindings", "detach_keeps", "blend_on_current",
+          "reattach_without_local")
+EDIT_KINDS = ("transforms", "masks", "vertices", "poses")
+SUBSETS = [frozenset(k for b, k in enumerate(EDIT_KINDS) if n >> b & 1) for n in range(1, 16)]      # every non-empty subset
+# what a GPU checkpoint counts of rules 28 - 40: predicted per seed by events_of(), asserted per seed by the GPU test
+TALLY_KEYS = ("checkpoints with an attached instance", "checkpoints after a pose-only update", "checkpoints with a hidden attached instance",
+              "checkpoints after a blend", "checkpoints after a solve", "checkpoints with instances held by a destroyed skeleton",
+              "frame checkpoints after a pose-only update")
 
 
 # ---- the shadow model takes an operation ---------------------------------------------------------------------------------------------------
@@ -103,6 +153,12 @@ def apply_to_model(world, op):
             return s.add_model(op["m"], op["x"]), None
         if k == "probe":
             return (M.ERR_STATE if not s.readable() else M.OK), None
+        if k == "set_transforms_mem":
+            return s.set_transforms_mem(op["first"], op["xs"], op["mem"]), None
+        if k == "attach":                               # the skeleton OBJECT that stands in the slot now (rule 36)
+            return s.attach(op["first"], world.skeletons[op["k"]], op["joints"], op["locals"]), None
+        if k == "detach":
+            return s.detach(op["first"], op["count"]), None
         return s.update() if k == "update" else s.build()
     if k in SKELETON_OPS:
         sk = world.skeletons[op["k"]]
@@ -112,6 +168,14 @@ def apply_to_model(world, op):
             return sk.add_clip(op["times"], op["keys"]), None
         if k == "skeleton_clear_clips":
             return sk.clear_clips(), None
+        if k == "skeleton_add_mask":
+            return sk.add_mask(op["weights"]), None
+        if k == "skeleton_clear_masks":
+            return sk.clear_masks(), None
+        if k == "skeleton_set_blend":
+            return sk.set_blend(op["layers"]), None
+        if k == "skeleton_solve_ik":
+            return sk.solve_ik(op["constraints"]), None
         return sk.set_time(op["clip"], op["t"]), None
     m = world.models[op["m"]]
     if k == "set_morph_targets":
@@ -124,7 +188,7 @@ def apply_to_model(world, op):
         sk = world.skeletons[op["k"]]
         code = m.set_bones_from(sk)
         if code == M.OK and op.get("destroy"):            # the skeleton is destroyed right behind the call; a new one, never posed, takes its place
-            world.skeletons[op["k"]] = M.Skeleton(sk.parents, sk.inverse_bind)
+            world.replace_skeleton(op["k"])
         return code, None
     if k == "set_vertices":
         return m.set_vertices(op["first"], op["verts"]), None
@@ -145,12 +209,14 @@ def describe(n, op):
     """one line of the operation log: no arrays, everything that replays the call by hand"""
     parts = []
     for key, v in op.items():
-        if key in ("op", "expect", "applied", "checkpoint", "frames", "mat"):
+        if key in ("op", "expect", "applied", "checkpoint", "frames", "mat", "updated_first"):
             continue
         if isinstance(v, np.ndarray):
             v = "%s%s" % (v.dtype.names and "verts" or v.dtype, list(v.shape))
-        elif isinstance(v, list) and v and isinstance(v[0], np.ndarray):
+        elif isinstance(v, list) and v and (isinstance(v[0], np.ndarray) or (key == "xs" and v[0] is None)):
             v = "[%d transforms]" % len(v)
+        elif key == "constraints" and len(v) > 3:
+            v = "[%d constraints]" % len(v)
         parts.append("%s=%s" % (key, v))
     tail = "" if "applied" not in op else " applied %s" % (op["applied"],)
     return "%3d: %-17s %s -> %d%s" % (n, op["op"], " ".join(parts), op["expect"], tail)
@@ -191,6 +257,7 @@ class Planner:
         self.options = option_cases.draw(ro) if ro.random() < 1.0 / 3.0 else {}
         self.world = M.World()
         self.ops = []
+        self.next_refusal = 3 * int(seed) + 5 * int(it)     # op_refused walks its list from here: neighbouring sequences, neighbouring stretches
         r = self.r
         n_models = int(r.integers(2, 4))
         self.kinds = [KINDS[int(k)] for k in r.choice(len(KINDS), size=n_models, replace=False, p=KIND_WEIGHTS)]
@@ -277,16 +344,14 @@ class Planner:
     def op_transform(self, s=None, i=None):
         s = self.scene() if s is None else s
         n = len(self.world.scenes[s].inst)
-        i = int(self.r.integers(n)) if i is None else i
-        self.emit(op="set_transform", s=s, i=i, x=self.xform(0.4 if n == 1 else 0.15))
+        i = self.pick_instance(s) if i is None else i
+        self.emit(op="set_transform", s=s, i=i, x=self.xform(0.4 if n == 1 else 0.15), **self.over(s, i, 1, "over an attached instance"))
         self.maybe_probe(s)
 
     def op_transforms(self, s=None):
         s = self.scene() if s is None else s
-        n = len(self.world.scenes[s].inst)
-        first = int(self.r.integers(n))
-        count = int(self.r.integers(1, min(n - first, 8) + 1))
-        self.emit(op="set_transforms", s=s, first=first, xs=[self.xform() for _ in range(count)])
+        first, count = self.pick_range(s)
+        self.emit(op="set_transforms", s=s, first=first, xs=[self.xform() for _ in range(count)], **self.over(s, first, count, "over an attached range"))
         self.maybe_probe(s)
 
     def op_mask(self, s=None):
@@ -463,10 +528,376 @@ class Planner:
         for s in range(len(self.world.scenes)):
             self.maybe_probe(s)
 
+    # -- masks, blends and inverse kinematics of the skeleton (rules 37 - 40)
+    def op_skeleton_add_mask(self, k=0):
+        if len(self.world.skeletons[k].masks) >= 3:
+            return self.emit(op="skeleton_clear_masks", k=k)
+        masks = skeleton_blend_cases.masks_for(self.n_joints, int(self.r.integers(1 << 30)))
+        self.emit(op="skeleton_add_mask", k=k, weights=masks[int(self.r.integers(len(masks)))])
+
+    def op_skeleton_clear_masks(self, k=0):
+        self.emit(op="skeleton_clear_masks", k=k)
+
+    def draw_layers(self, k=0, n_layers=None, current=None):
+        """a layer list in the manner of skeleton_blend_cases.layer_list over the skeleton's clips and masks (one of each is added where
+        there is none); current: the base is the pose the skeleton holds (None: drawn, where it holds one)"""
+        sk = self.world.skeletons[k]
+        if not sk.clips or (len(sk.clips) == 1 and self.r.random() < 0.5):
+            self.op_skeleton_add_clip(k)
+        if not sk.masks:
+            self.op_skeleton_add_mask(k)
+        n_layers = int((1, 2, 2, 3, 4, 8)[int(self.r.integers(6))]) if n_layers is None else n_layers
+        layers = skeleton_blend_cases.layer_list(n_layers, sk.clips, len(sk.masks), int(self.r.integers(1 << 30)))
+        current = (sk.pose is not None and self.r.random() < 0.3) if current is None else current
+        if current:
+            layers[0] = (None, 0.0, 1.0, None, skeleton_blend_cases.BLEND)
+        return layers
+
+    def op_skeleton_set_blend(self, k=0, n_layers=None, current=None):
+        self.emit(op="skeleton_set_blend", k=k, layers=self.draw_layers(k, n_layers, current))
+
+    def draw_constraints(self, k=0, n=None):
+        """1 - 3 independent constraints: a two-bone tip among the joints that have two ancestors (an aim where there are none), targets and
+        poles 0.5 - 3 from the origin, weights of ik_cases.WEIGHTS"""
+        parents = self.skeletons[k][0]
+        tips = [j for j in range(self.n_joints) if parents[j] >= 0 and parents[parents[j]] >= 0]
+        n = int(self.r.integers(1, 4)) if n is None else n
+        out = []
+        for _ in range(4 * n):
+            if len(out) == n:
+                break
+            two = bool(tips) and self.r.random() < 0.6
+            joint = tips[int(self.r.integers(len(tips)))] if two else int(self.r.integers(self.n_joints))
+            target, pole = (tuple(float(np.float32(x)) for x in ik_cases._units(1, self.r)[0] * self.r.uniform(0.5, 3.0)) for _ in range(2))
+            c = (ik_cases.TWO_BONE if two else ik_cases.AIM, joint, target, pole, ik_cases.WEIGHTS[int(self.r.integers(len(ik_cases.WEIGHTS)))])
+            if ik_cases.validate(out + [c], parents, True)[0] == 0:         # independent of those drawn before it
+                out.append(c)
+        return out
+
+    def op_skeleton_solve_ik(self, k=0):
+        if self.world.skeletons[k].pose is None:
+            self.op_skeleton_set_time(k) if self.r.random() < 0.5 else self.op_skeleton_set_pose(k)
+        self.emit(op="skeleton_solve_ik", k=k, constraints=self.draw_constraints(k))
+
+    def pose_any(self, k=0):
+        """exactly one pose, by any of the four producers"""
+        u = self.r.random()
+        if u < 0.25:
+            self.op_skeleton_set_pose(k)
+        elif u < 0.5:
+            self.op_skeleton_set_time(k)
+        elif u < 0.75 or self.world.skeletons[k].pose is None:
+            self.op_skeleton_set_blend(k)
+        else:
+            self.op_skeleton_solve_ik(k)
+
+    # -- transforms from device memory and attached instances (rules 28 - 36)
+    def attached(self, s, current=False):
+        """the attached instances of a scene; current: those that follow the skeleton that stands in slot 0 now"""
+        return sorted(i for i, a in self.world.scenes[s].att.items() if not current or a["sk"] is self.world.skeletons[0])
+
+    def over(self, s, first, count, why):
+        """the `why` of a transform setter that rule 31 refuses"""
+        sc = self.world.scenes[s]
+        return {"why": why} if first + count <= len(sc.inst) and any(first + k in sc.att for k in range(count)) else {}
+
+    def pick_instance(self, s):
+        """any instance; an attached one (whose setters are refused) only now and then"""
+        sc = self.world.scenes[s]
+        i = int(self.r.integers(len(sc.inst)))
+        free = [k for k in range(len(sc.inst)) if k not in sc.att]
+        if i in sc.att and free and self.r.random() < 0.75:
+            i = free[int(self.r.integers(len(free)))]
+        return i
+
+    def pick_range(self, s, most=8):
+        sc = self.world.scenes[s]
+        first = self.pick_instance(s)
+        count = int(self.r.integers(1, min(len(sc.inst) - first, most) + 1))
+        if first not in sc.att and self.r.random() < 0.75:      # ... and most ranges stop in front of the next attached instance
+            count = next((k for k in range(1, count) if first + k in sc.att), count)
+        return first, count
+
+    def op_transforms_mem(self, s=None, mem=None):
+        s = self.scene() if s is None else s
+        first, count = self.pick_range(s)
+        mem = self.mem() if mem is None else mem
+        self.emit(op="set_transforms_mem", s=s, first=first, xs=[self.xform() for _ in range(count)], mem=mem,
+                  **self.over(s, first, count, "over an attached range, from " + mem))
+        self.maybe_probe(s)
+
+    def op_attach(self, s=None, first=None, joints=None, local=None):
+        """instances first .. to joints of the skeleton in slot 0, with local matrices (random_xforms, as the instances' own) or without"""
+        s = self.scene() if s is None else s
+        n = len(self.world.scenes[s].inst)
+        first = int(self.r.integers(n)) if first is None else first
+        if joints is None:
+            joints = self.r.integers(self.n_joints, size=int(self.r.integers(1, min(n - first, 3) + 1)))
+        joints = np.asarray(joints, np.uint32).reshape(-1)
+        local = bool(self.r.random() < 0.6) if local is None else local
+        locals_ = random_xforms(len(joints), seed=int(self.r.integers(1 << 30)), spread=6.0) if local else None
+        self.emit(op="attach", s=s, first=first, k=0, joints=joints, locals=locals_)
+        self.maybe_probe(s)
+
+    def op_detach(self, s=None):
+        s = self.scene() if s is None else s
+        n, att = len(self.world.scenes[s].inst), self.attached(s)
+        first = att[int(self.r.integers(len(att)))] if att and self.r.random() < 0.8 else int(self.r.integers(n))
+        self.emit(op="detach", s=s, first=first, count=int(self.r.integers(1, min(n - first, 3) + 1)))
+
+    def settle(self, s):
+        """the scene fresh and with no pose to apply"""
+        sc = self.world.scenes[s]
+        if sc.state != M.FRESH or sc.pending():
+            self.op_update(s)
+
+    def ensure_attached(self, s, settle=True):
+        """-> an instance of the scene that follows the skeleton standing in slot 0: attached now if none does; the scene then settled"""
+        att = self.attached(s, current=True)
+        if att:
+            i = att[int(self.r.integers(len(att)))]
+        else:
+            i = int(self.r.integers(len(self.world.scenes[s].inst)))
+            self.op_attach(s, first=i, joints=[int(self.r.integers(self.n_joints))])
+        if settle:
+            self.settle(s)
+        return i
+
+    def applied(self):
+        """what the update or build just emitted applied, as a set; None when it was refused"""
+        a = self.ops[-1].get("applied")
+        return None if a is None else set(a)
+
+    # -- motifs of rules 28 - 40
+    def motif_pose_only_update(self):
+        """a fresh scene, a pose, a probe that must succeed, an update that applies the pose alone"""
+        s = self.scene()
+        self.ensure_attached(s)
+        self.pose_any()
+        self.emit(op="probe", s=s)
+        if self.ops[-1]["expect"] == M.OK and self.op_update(s) == M.OK and self.applied() == {"poses"}:
+            self.done("pose_only_update")
+
+    def motif_posed_and_changed(self):
+        """one instance both attached and of a model whose vertices are pending"""
+        s = self.scene()
+        i = self.ensure_attached(s)
+        self.pose_any()
+        self.op_vertices(self.world.scenes[s].inst[i][0])
+        if self.op_update(s) == M.OK and {"poses", "vertices"} <= self.applied():
+            self.done("posed_and_changed")
+
+    def motif_attached_hidden(self):
+        """an attached instance hidden, a pose, an update (the hidden instance is composed all the same), shown again, an update"""
+        s = self.scene()
+        sc = self.world.scenes[s]
+        i = self.ensure_attached(s)
+        if sc.masks[i] == 0 or len(sc.visible()) < 2:
+            return
+        self.emit(op="set_mask", s=s, i=i, mask=0)
+        self.pose_any()
+        first = self.op_update(s)
+        self.emit(op="set_mask", s=s, i=i, mask=int(self.r.integers(1, 256)))
+        if self.op_update(s) == M.OK and first == M.OK:
+            self.done("attached_hidden")
+
+    def identity_pose(self):
+        """a gentle pose whose joint 0, a root, is the identity exactly"""
+        trs = gentle_poses(1, self.n_joints, int(self.r.integers(1 << 30)))[0]
+        trs[0] = (0, 0, 0, 0, 0, 0, 1, 1, 1, 1)
+        return trs
+
+    def motif_attached_single(self):
+        """a one-instance scene follows a root, without a local: posed to the identity exactly (single-level), away from it, and back"""
+        c = [s for s, sc in enumerate(self.world.scenes) if len(sc.inst) == 1]
+        if not c:
+            return self.op_attach()
+        s = c[int(self.r.integers(len(c)))]
+        self.emit(op="attach", s=s, first=0, k=0, joints=np.zeros(1, np.uint32), locals=None)
+        seen = []
+        for trs in (self.identity_pose(), None, self.identity_pose()):
+            if trs is None:
+                self.op_skeleton_set_pose()
+            else:
+                self.emit(op="skeleton_set_pose", k=0, trs=trs, mem=self.mem())
+            if self.op_update(s) != M.OK:
+                return
+            seen.append(M.is_identity(self.world.scenes[s].inst[0][1]))
+        if seen == [True, False, True]:
+            self.done("attached_single")
+
+    def motif_pose_while_refused(self):
+        """every instance hidden, a pose, the refused update, one instance shown, an update that applies all of it"""
+        s = self.scene()
+        sc = self.world.scenes[s]
+        self.ensure_attached(s)
+        self.emit(op="set_masks", s=s, first=0, masks=[0] * len(sc.inst))
+        self.pose_any()
+        self.emit(op="update", s=s)
+        refused = self.ops[-1]["expect"] != M.OK
+        self.emit(op="set_mask", s=s, i=int(self.r.integers(len(sc.inst))), mask=int(self.r.integers(1, 256)))
+        self.emit(op="update", s=s)
+        if refused and self.applied() is not None and {"poses", "masks"} <= self.applied():
+            self.done("pose_while_refused")
+        self.emit(op="set_masks", s=s, first=0, masks=[0xFF] * len(sc.inst))
+        self.op_update(s)
+
+    def destroy_skeleton(self):
+        """set_bones_from with the skeleton destroyed right behind it -> whether the slot now holds an unposed replacement"""
+        if self.skin_model() is None:
+            return False
+        self.op_set_bones_from(destroy=True)
+        return self.world.skeletons[0].pose is None
+
+    def motif_unposed_then_posed(self):
+        """an instance attached to the replacement of a destroyed skeleton: the update is refused until the replacement has a pose"""
+        if not self.destroy_skeleton():
+            return self.op_attach()
+        s = self.scene()
+        sc = self.world.scenes[s]
+        if sc.state == M.UNBUILT:
+            self.op_update(s)
+        i = int(self.r.integers(len(sc.inst)))
+        self.op_attach(s, first=i, joints=[int(self.r.integers(self.n_joints))])
+        u = self.r.random()
+        if u < 0.4:
+            self.refused_new("skeleton_set_blend", "the current pose before the first pose")
+        elif u < 0.8:
+            self.refused_new("skeleton_solve_ik", "no pose yet")
+        self.emit(op="update", s=s, why="an unposed attachment")
+        refused = self.ops[-1]["expect"] != M.OK
+        if self.r.random() < 0.5 and sc.visible():
+            self.emit(op="build", s=s, why="an unposed attachment")
+        self.pose_any()
+        if self.op_update(s) == M.OK and refused:
+            self.done("unposed_then_posed")
+
+    def motif_destroyed_under_attachment(self):
+        """set_bones_from with the skeleton destroyed behind it while an instance is attached to that skeleton; a pose of the replacement
+        and an update that must move nobody"""
+        s = self.scene()
+        i = self.ensure_attached(s)
+        old = self.world.scenes[s].att[i]["sk"]
+        if not self.destroy_skeleton():
+            return
+        self.settle(s)
+        before = self.world.scenes[s].transforms().tobytes()
+        self.op_skeleton_set_pose()
+        self.emit(op="update", s=s)
+        sc = self.world.scenes[s]
+        if self.applied() == set() and sc.att.get(i, {}).get("sk") is old and sc.transforms().tobytes() == before:
+            self.done("destroyed_under_attachment")
+
+    def motif_two_scenes_one_skeleton(self):
+        """both scenes of a shared model attached to the skeleton; one pose; the updates in either order, each applying it"""
+        if not self.shared:
+            return self.op_attach()
+        for s in (0, 1):
+            self.ensure_attached(s)
+        self.pose_any()
+        order = (0, 1) if self.r.random() < 0.5 else (1, 0)
+        got = []
+        for s in order:
+            self.emit(op="update", s=s)
+            got.append(self.applied())
+        if all(g is not None and "poses" in g for g in got):
+            self.done("two_scenes_one_skeleton")
+            self.ops[-1]["updated_first"] = order[0]
+
+    def motif_character_and_props(self):
+        """the skeleton that poses a character also carries attached instances: a frame is set_blend, solve_ik, set_bones_from, update"""
+        m = self.skeleton_model()
+        if m is None:
+            m = self.skin_model()
+            if m is None:
+                return self.op_attach()
+            self.op_set_skin(m, self.n_joints)
+        s = self.scene_of(m)
+        if s is None:
+            return
+        self.ensure_attached(s)
+        self.op_skeleton_set_blend()
+        self.op_skeleton_solve_ik()
+        self.emit(op="set_bones_from", m=m, k=0, destroy=False)
+        if self.op_update(s) == M.OK and {"poses", "vertices"} <= self.applied():
+            self.done("character_and_props")
+
+    def motif_grown_with_bindings(self):
+        """an attachment and a device set, then add_model (sometimes followed by an attach, a device set or a detach that reaches the new
+        instance), the build, a pose, the update"""
+        s = self.scene()
+        sc = self.world.scenes[s]
+        if len(sc.inst) >= 70 or len(sc.inst) < 2:
+            return self.op_attach()
+        i = self.ensure_attached(s, settle=False)
+        free = [k for k in range(len(sc.inst)) if k not in sc.att]
+        if not free:
+            return
+        self.emit(op="set_transforms_mem", s=s, first=free[int(self.r.integers(len(free)))], xs=[self.xform(0.0)], mem="device")
+        self.emit(op="add_model", s=s, m=self.model(s), x=self.xform(), mat=self.material() if s == 0 else None)
+        u, new = self.r.random(), len(sc.inst) - 1        # before the build: the first call that needs the device arrays sizes them again
+        if u < 0.3:
+            self.op_attach(s, first=new, joints=[int(self.r.integers(self.n_joints))])
+        elif u < 0.55:
+            self.emit(op="set_transforms_mem", s=s, first=new, xs=[self.xform(0.0)], mem="device")
+        elif u < 0.75 and new - 1 != i:                    # ... or none does: a detach over the old list's end and the new instance
+            self.emit(op="detach", s=s, first=new - 1, count=2)
+        if self.op_update(s) != M.OK or self.ops[-1]["op"] != "build":
+            return
+        self.pose_any()
+        if self.op_update(s) == M.OK and "poses" in self.applied() and i in sc.att:
+            self.done("grown_with_bindings")
+
+    def motif_detach_keeps(self):
+        """attach, update, pose, detach BEFORE the update: the instance stays where the first pose put it; then attach and detach with no
+        update in between: the instance stays where it was"""
+        s = self.scene()
+        i = self.ensure_attached(s)
+        at_first = self.world.scenes[s].transforms()[i].tobytes()
+        self.pose_any()
+        self.emit(op="detach", s=s, first=i, count=1)
+        self.emit(op="update", s=s)
+        kept = self.ops[-1]["expect"] == M.OK and self.world.scenes[s].transforms()[i].tobytes() == at_first
+        # ... and attached and let go with no update in between: attaching changed no stored transform, so there is nothing else to keep
+        sc = self.world.scenes[s]
+        free = [k for k in range(len(sc.inst)) if k not in sc.att]
+        if not free:
+            return
+        j = free[int(self.r.integers(len(free)))]
+        held = sc.transforms()[j].tobytes()
+        self.op_attach(s, first=j, joints=[int(self.r.integers(self.n_joints))])
+        self.emit(op="detach", s=s, first=j, count=1)
+        if self.op_update(s) == M.OK and kept and sc.transforms()[j].tobytes() == held:
+            self.done("detach_keeps")
+
+    def motif_blend_on_current(self):
+        """solve_ik, then a blend whose base is the current pose: the pose that the solve left"""
+        self.op_skeleton_solve_ik()
+        self.op_skeleton_set_blend(n_layers=int(self.r.integers(2, 5)), current=True)
+        blend = self.ops[-1]
+        s = self.scene()
+        if self.op_update(s) == M.OK and blend["expect"] == M.OK:
+            self.done("blend_on_current")
+
+    def motif_reattach_without_local(self):
+        """attached with a local matrix, applied, attached again without: W_joint bit for bit"""
+        s = self.scene()
+        i = int(self.r.integers(len(self.world.scenes[s].inst)))
+        joint = int(self.r.integers(self.n_joints))
+        self.op_attach(s, first=i, joints=[joint], local=True)
+        self.settle(s)
+        self.op_attach(s, first=i, joints=[joint if self.r.random() < 0.5 else int(self.r.integers(self.n_joints))], local=False)
+        if self.op_update(s) == M.OK:
+            self.done("reattach_without_local")
+
     def op_update(self, s=None):
         s = self.scene() if s is None else s
         sc = self.world.scenes[s]
         how = "build" if sc.state == M.UNBUILT else "update"
+        if sc.unposed():                                # (only the skeleton in slot 0 can be unposed: a destroyed one has posed a model)
+            if self.r.random() < 0.5:
+                self.emit(op=how, s=s, why="an unposed attachment")         # refused (rule 35)
+            self.pose_any()
         if not sc.visible():
             self.emit(op=how, s=s)                      # refused (rule 12)
             self.emit(op="set_mask", s=s, i=int(self.r.integers(len(sc.inst))), mask=0xFF)
@@ -480,6 +911,8 @@ class Planner:
     def op_build(self):
         s = self.scene()
         if self.world.scenes[s].visible():
+            if self.world.scenes[s].unposed():
+                self.pose_any()
             self.emit(op="build", s=s)
 
     def op_add_model(self):
@@ -498,14 +931,23 @@ class Planner:
         if not sc.visible():
             self.emit(op="build", s=s)                  # refused (rule 12)
             self.emit(op="set_mask", s=s, i=0, mask=0x10)
+        if sc.unposed():
+            self.emit(op="build", s=s, why="an unposed attachment")         # refused (rule 35)
+            self.pose_any()
         self.emit(op="build", s=s)
 
     def op_empty(self):
         """count == 0: rule 6, also at first == n"""
         s, m = self.scene(), self.model()
         n, nv = len(self.world.scenes[s].inst), len(self.world.models[m].verts)
-        u = int(self.r.integers(4))
-        if u == 0:
+        u = int(self.r.integers(7))
+        if u == 4:
+            self.emit(op="set_transforms_mem", s=s, first=int(self.r.choice([0, n])), xs=[], mem=self.mem())
+        elif u == 5:                                      # (a joint list of none: the skeleton may be unposed, nothing is bound)
+            self.emit(op="attach", s=s, first=int(self.r.choice([0, n])), k=0, joints=np.zeros(0, np.uint32), locals=None)
+        elif u == 6:
+            self.emit(op="detach", s=s, first=int(self.r.choice([0, n])), count=0)
+        elif u == 0:
             self.emit(op="set_transforms", s=s, first=int(self.r.choice([0, n])), xs=[])
         elif u == 1:
             self.emit(op="set_masks", s=s, first=int(self.r.choice([0, n])), masks=[])
@@ -518,7 +960,10 @@ class Planner:
         s, m = self.scene(), self.model()
         n, mo = len(self.world.scenes[s].inst), self.world.models[m]
         nv = len(mo.verts)
-        u = int(self.r.integers(8 + len(REFUSALS)))
+        if self.r.random() < 0.6:                       # in turn, so that a handful of sequences meets every one; or any
+            u, self.next_refusal = self.next_refusal % (8 + len(REFUSALS)), self.next_refusal + 1
+        else:
+            u = int(self.r.integers(8 + len(REFUSALS)))
         if u >= 8:
             return self.refused_new(*REFUSALS[u - 8])
         if u == 0:
@@ -584,6 +1029,89 @@ class Planner:
             else:
                 times[2] = times[int(r.integers(2))]   # equal to its neighbour, or before it
             self.emit(op="skeleton_add_clip", k=0, times=times, keys=gentle_poses(3, self.n_joints, int(r.integers(1 << 30))), why=why)
+        elif kind == "attach":
+            s = self.scene()
+            n = len(self.world.scenes[s].inst)
+            beyond, bad = "beyond" in why, "joint" in why
+            first, count = (n - 1, 2) if beyond else (int(r.integers(n)), 1)
+            joints = r.integers(self.n_joints, size=count).astype(np.uint32)
+            if bad:                                     # (with both faults the range wins: ERR_STATE)
+                joints[-1] = self.n_joints + int(r.integers(3))
+            locals_ = random_xforms(count, seed=int(r.integers(1 << 30)), spread=6.0) if r.random() < 0.5 else None
+            self.emit(op="attach", s=s, first=first, k=0, joints=joints, locals=locals_, why=why)
+        elif kind == "detach":
+            s = self.scene()
+            n = len(self.world.scenes[s].inst)
+            first, count = ((n - 1, 2), (n + 1, 0), (n, 1))[int(r.integers(3))]
+            self.emit(op="detach", s=s, first=first, count=count, why=why)
+        elif kind in ("set_transform", "set_transforms", "set_transforms_mem"):       # rule 31: where some instance is attached
+            c = [s for s, sc in enumerate(self.world.scenes) if sc.att]
+            if not c:
+                return
+            s = c[int(r.integers(len(c)))]
+            att = self.attached(s)
+            i = att[int(r.integers(len(att)))]
+            first = max(i - int(r.integers(2)), 0)       # the attached instance first in the range, or last
+            xs = [self.xform() for _ in range(i - first + 1)]
+            if kind == "set_transform":
+                self.emit(op=kind, s=s, i=i, x=xs[0], why=why)
+            elif kind == "set_transforms":
+                self.emit(op=kind, s=s, first=first, xs=xs, why=why)
+            else:
+                self.emit(op=kind, s=s, first=first, xs=xs, mem="device", why=why)
+        elif kind in ("update", "build"):               # rule 35: where some instance follows a skeleton without a pose
+            c = [s for s, sc in enumerate(self.world.scenes) if sc.unposed() and (kind == "build" or sc.state != M.UNBUILT)]
+            if c:
+                self.emit(op=kind, s=c[int(r.integers(len(c)))], why=why)
+        elif kind == "skeleton_set_blend":
+            B = skeleton_blend_cases
+            sk = self.world.skeletons[0]
+            if why == "the current pose before the first pose":
+                if sk.pose is None:
+                    self.emit(op=kind, k=0, layers=[(None, 0.0, 1.0, None, B.BLEND)], why=why)
+                return
+            layers = self.draw_layers(0, n_layers=3, current=False)
+            k = int(r.integers(3))
+            nan = float("nan")
+            if why == "9 layers":
+                layers = (layers * 3)[:9]
+            elif why == "additive layer 0":
+                layers[0] = layers[0][:4] + (B.ADDITIVE,)
+            elif why == "the current pose on layer 1":
+                layers[1] = (None,) + layers[1][1:]
+            elif why == "NaN time":
+                layers[k] = (layers[k][0], nan) + layers[k][2:]
+            elif why == "unknown clip":
+                layers[k] = (len(sk.clips) + int(r.integers(2)),) + layers[k][1:]
+            elif why == "unknown mask":                 # (not on layer 0: its mask is not read)
+                k = 1 + int(r.integers(2))
+                layers[k] = layers[k][:3] + (len(sk.masks) + int(r.integers(2)),) + layers[k][4:]
+            else:                                       # a fault of the second group on layer 0, one of the first on layer 1: ERR_INVALID_ARG
+                layers[0] = (len(sk.clips),) + layers[0][1:]
+                layers[1] = (layers[1][0], nan) + layers[1][2:]
+            self.emit(op=kind, k=0, layers=layers, why=why)
+        elif kind == "skeleton_solve_ik":               # (the first group is held to before the state: these are refused with or without a pose)
+            sk = self.world.skeletons[0]
+            parents = self.skeletons[0][0]
+            if why == "no pose yet":
+                if sk.pose is None:
+                    self.emit(op=kind, k=0, constraints=self.draw_constraints(0, 1), why=why)
+                return
+            cs = self.draw_constraints(0)
+            if why == "33 constraints":
+                cs = [(ik_cases.AIM, 0) + cs[0][2:]] * 33
+            elif why == "unknown kind":
+                cs[-1] = (2 + int(r.integers(5)),) + cs[-1][1:]
+            elif why == "a joint >= n_joints":
+                cs[-1] = (cs[-1][0], self.n_joints + int(r.integers(2))) + cs[-1][2:]
+            elif why == "a tip without two ancestors":
+                short = [j for j in range(self.n_joints) if parents[j] < 0 or parents[parents[j]] < 0]
+                cs[-1] = (ik_cases.TWO_BONE, short[int(r.integers(len(short)))]) + cs[-1][2:]
+            elif why == "NaN weight":
+                cs[-1] = cs[-1][:4] + (float("nan"),)
+            else:                                       # an aim on the first constraint's joint: it writes (or reads) what the first reads (or writes)
+                cs = [cs[0], (ik_cases.AIM, cs[0][1]) + cs[0][2:]]
+            self.emit(op=kind, k=0, constraints=cs, why=why)
         elif why == "before the first pose":
             m = self.skeleton_model()
             if m is not None and self.world.skeletons[0].palette is None:
@@ -880,7 +1408,7 @@ class Planner:
         self.op_update()
 
     def motif_combo(self):
-        """one update that applies a drawn subset of {transforms, masks, vertices}"""
+        """one update that applies a drawn subset of {transforms, masks, vertices, poses}"""
         s = self.scene()
         sc = self.world.scenes[s]
         if sc.state != M.FRESH:
@@ -888,8 +1416,15 @@ class Planner:
         want = SUBSETS[int(self.r.integers(len(SUBSETS)))]
         if len(sc.inst) < 2 and "masks" in want:
             want = want - {"masks"} or frozenset(["transforms"])
+        if "poses" in want:                             # an instance that follows the skeleton, applied; then the pose
+            self.ensure_attached(s)
+            self.pose_any()
         if "transforms" in want:
-            self.op_transform(s)
+            free = [k for k in range(len(sc.inst)) if k not in sc.att]
+            if free:
+                self.op_transform(s, free[int(self.r.integers(len(free)))])
+            else:                                       # every instance is attached: attaching is what marks one pending
+                self.op_attach(s)
         if "vertices" in want:
             self.op_vertices(self.model(s))
         if "masks" in want:
@@ -902,20 +1437,29 @@ class Planner:
         self.op_update(s)
 
     TABLE = (("op_transform", 12), ("op_transforms", 7), ("op_mask", 8), ("op_masks", 6), ("op_vertices", 12), ("op_normals", 3), ("op_set_skin", 2),
-             ("op_clear_skin", 2), ("op_set_bones", 6), ("op_add_model", 1.5), ("op_build", 2), ("op_update", 12), ("op_update_twice", 3), ("op_refused", 22),
+             ("op_clear_skin", 2), ("op_set_bones", 6), ("op_add_model", 1.5), ("op_build", 2), ("op_update", 12), ("op_update_twice", 3), ("op_refused", 36),
              ("op_empty", 3), ("motif_hide_all", 2), ("motif_hide_show", 2), ("motif_set_twice", 2), ("motif_one_visible", 2), ("motif_single", 2),
              ("motif_shared", 5), ("motif_skin_rest", 3), ("motif_combo", 5), ("op_set_morph_targets", 2), ("op_clear_morph_targets", 1), ("op_set_morph_weights", 6),
              ("op_skeleton_set_pose", 2), ("op_skeleton_add_clip", 2), ("op_skeleton_clear_clips", 1), ("op_skeleton_set_time", 3), ("op_set_bones_from", 5),
              ("motif_morph_then_skin", 2), ("motif_skin_then_morph", 2), ("motif_reskin_posed", 2), ("motif_retarget", 2), ("motif_rest_morph_keeps_fresh", 3),
-             ("motif_clear_skin_redirects", 2), ("motif_character_frame", 5), ("motif_skeleton_mismatch", 1.5), ("motif_shared_character", 2))
+             ("motif_clear_skin_redirects", 2), ("motif_character_frame", 5), ("motif_skeleton_mismatch", 2), ("motif_shared_character", 3),
+             ("op_transforms_mem", 9), ("op_attach", 6), ("op_detach", 5), ("op_skeleton_add_mask", 1.5), ("op_skeleton_clear_masks", 1.5),
+             ("op_skeleton_set_blend", 4), ("op_skeleton_solve_ik", 4), ("motif_pose_only_update", 3), ("motif_posed_and_changed", 2.5),
+             ("motif_attached_hidden", 2.5), ("motif_attached_single", 3), ("motif_pose_while_refused", 2.5), ("motif_unposed_then_posed", 3),
+             ("motif_destroyed_under_attachment", 3), ("motif_two_scenes_one_skeleton", 12), ("motif_character_and_props", 3),
+             ("motif_grown_with_bindings", 3.5), ("motif_detach_keeps", 2.5), ("motif_blend_on_current", 2.5), ("motif_reattach_without_local", 2.5))
 
     def epilogue(self):
-        """the rest pose and the morph base cannot be read back: one more producer over each, so that what they hold reaches geometry()"""
+        """the rest pose and the morph base cannot be read back: one more producer over each, so that what they hold reaches geometry().
+        And every skeleton that a scene is attached to and that has no pose gets one, so that no sequence ends on a refused update (only
+        the one in slot 0 can lack it)"""
         for m, mo in enumerate(self.world.models):
             if mo.morph is not None:
                 self.op_set_morph_weights(m)
             if mo.skin is not None:
                 self.op_set_bones(m)
+        if any(sc.unposed() for sc in self.world.scenes):
+            self.pose_any()
 
     def plan(self):
         r = self.r
@@ -938,7 +1482,7 @@ class Planner:
             getattr(self, names[int(r.choice(len(names), p=weights))])()
         self.epilogue()
         for s, sc in enumerate(self.world.scenes):      # every scene ends fresh: the last checkpoint
-            if sc.state != M.FRESH:
+            if sc.state != M.FRESH or sc.pending():
                 self.op_update(s)
         c = 0
         last = max(n for n, op in enumerate(self.ops) if op["op"] in ("update", "build") and op["s"] == 0 and op["expect"] == M.OK)
@@ -946,7 +1490,7 @@ class Planner:
             op["checkpoint"] = op["op"] in ("update", "build") and op["expect"] == M.OK
             op["frames"] = False
             if op["checkpoint"] and op["s"] == 0:
-                op["frames"] = c % 3 == 0 or n == last
+                op["frames"] = c % 3 == 0 or n == last or op["applied"] == ["poses"]      # (the frames behind an update whose only cause was a pose)
                 c += 1
         # the point light of the frames: above every world box of the first scene as it starts, so that it has a free sphere to lose
         top = max(float(world_box_of_vertices(self.base[mi], self.world.models[mi].idx, T.IDENTITY_3X4 if x is None else x)[4]) for mi, x in self.initial[0])
@@ -990,6 +1534,8 @@ def events_of(plan):
     morph_step = {}                                     # model -> 1: set_morph_weights seen, 2: recompute_normals after it
     producer = {}                                       # model -> the kind of call that last wrote its vertices
     from_skeleton = {}                                  # model -> False: posed by set_bones_from and not yet applied, True: ... and the skeleton has moved on
+    device_held = [set() for _ in range(ns)]            # per scene: the instances whose floats came from device memory
+    since = {"blend": False, "solve": False}            # a blend / a solve has posed the skeleton since the last checkpoint
     for op in plan.ops:
         k = op["op"]
         ok = op["expect"] == M.OK
@@ -1003,6 +1549,19 @@ def events_of(plan):
                 ev.add("targets refused on a model that has targets")
         if "motif" in op:
             ev.add(("motif", op["motif"]))
+        if k == "update" and op.get("motif") == "two_scenes_one_skeleton":
+            ev.add("two scenes, one pose: scene %d updated first" % op["updated_first"])
+        if ok and k in ("skeleton_set_blend", "skeleton_solve_ik"):
+            since["blend" if k == "skeleton_set_blend" else "solve"] = True
+            if k == "skeleton_set_blend" and op["layers"][0][0] is None:
+                ev.add("a blend on the current pose")
+        if ok and k in ("set_transform", "set_transforms", "set_transforms_mem"):
+            rng = range(op["i"], op["i"] + 1) if k == "set_transform" else range(op["first"], op["first"] + len(op["xs"]))
+            device_held[op["s"]] = (device_held[op["s"]] | set(rng)) if op.get("mem") == "device" else (device_held[op["s"]] - set(rng))
+        if k == "add_model" and w.scenes[op["s"]].att and device_held[op["s"]]:
+            ev.add("add_model on a scene with device-held and attached instances")
+            if plan.options:
+                ev.add("add_model on a scene with device-held and attached instances, under options")
         if k == "set_morph_weights" and ok:
             mo = w.models[op["m"]]
             ev.add("weights into the rest pose" if mo.skin is not None else "weights into the vertices")
@@ -1032,7 +1591,7 @@ def events_of(plan):
                     ev.add("a palette wider than the LDS palette")
                 if op.get("destroy"):
                     ev.add("a skeleton destroyed right after set_bones_from")
-        if ok and k in ("skeleton_set_pose", "skeleton_set_time"):
+        if ok and k in POSE_OPS:
             from_skeleton = {m: True for m in from_skeleton}
         if ok and k == "set_morph_targets":
             ev.add("targets with normal deltas" if op["dnrm"] is not None else "targets without normal deltas")
@@ -1053,6 +1612,22 @@ def events_of(plan):
             if not ok and sc.state != M.UNBUILT and not sc.visible() and {"transforms", "vertices"} <= kinds:
                 hide_all_refused[s] = True
             if ok:
+                if any(id(w.models[sc.inst[i][0]]) in pend_models for i in sc.posed_since()):
+                    ev.add("an attached instance posed and of a changed model")
+                if sc.att:
+                    ev.add("checkpoints with an attached instance")
+                    if any(sc.masks[i] == 0 for i in sc.att):
+                        ev.add("checkpoints with a hidden attached instance")
+                    if any(all(a["sk"] is not x for x in w.skeletons) for a in sc.att.values()):
+                        ev.add("checkpoints with instances held by a destroyed skeleton")
+                if op["applied"] == ["poses"]:
+                    ev.add("checkpoints after a pose-only update")
+                    if op["frames"]:
+                        ev.add("frame checkpoints after a pose-only update")
+                for name in ("blend", "solve"):
+                    if since[name]:
+                        ev.add("checkpoints after a " + name)
+                        since[name] = False
                 if k == "update":
                     ev.add(("update applies", frozenset(op["applied"])) if op["applied"] else "no-op update")
                     if hide_all_refused[s]:
@@ -1141,7 +1716,7 @@ def single_instance_events(plan):
     for op in plan.ops:
         apply_to_model(w, op)
         if op["op"] in ("update", "build") and op["expect"] == M.OK and len(w.scenes[op["s"]].inst) == 1:
-            now = w.scenes[op["s"]].inst[0][1] is None
+            now = M.is_identity(w.scenes[op["s"]].inst[0][1])
             if op["s"] in last and last[op["s"]] != now:
                 ev.add("a single instance back to the identity" if now else "a single identity instance transformed")
             last[op["s"]] = now
@@ -1158,19 +1733,24 @@ def required_events():
 
 
 def new_events():
-    """what morph targets and skeletons add to the list"""
+    """what morph targets and skeletons, and then device transforms, attachments, blends and inverse kinematics, add to the list"""
     return {("refused", k, why) for k, why in REFUSALS} | {("motif", name) for name in MOTIFS} | {
         "targets with normal deltas", "targets without normal deltas", "a target set with an empty target", "a vertex named by every target",
         "vertices named by no target", "weights from device memory", "weights into the rest pose", "weights into the vertices",
         "a palette wider than the LDS palette", "rest-pose morph on a fresh scene", "rest-pose morph on a shared model with one scene stale",
         "a probe of a fresh scene succeeds", "recompute_normals between a morph and a pose", "an update that applies vertices produced by set_bones_from",
-        "the skeleton moves on between set_bones_from and the update", "a skeleton destroyed right after set_bones_from"}
+        "the skeleton moves on between set_bones_from and the update", "a skeleton destroyed right after set_bones_from",
+        # rules 28 - 40
+        "an attached instance posed and of a changed model", "two scenes, one pose: scene 0 updated first", "two scenes, one pose: scene 1 updated first",
+        "a blend on the current pose", "add_model on a scene with device-held and attached instances",
+        "add_model on a scene with device-held and attached instances, under options"} | set(TALLY_KEYS)
 
 
 def per_seed_events():
     """what the GPU test asserts of every seed's own tally, so every seed's plans must hold it"""
     return {"split references come and go", "an update that applies vertices produced by set_bones_from", "rest-pose morph on a fresh scene",
-            "a probe of a fresh scene succeeds", "a skeleton destroyed right after set_bones_from", "targets refused on a model that has targets"}
+            "a probe of a fresh scene succeeds", "a skeleton destroyed right after set_bones_from",
+            "targets refused on a model that has targets"} | set(TALLY_KEYS)
 
 
 # ---- the GPU side -------------------------------------------------------------------------------------------------------------------------
@@ -1190,6 +1770,10 @@ class GpuBackend:
         self.models = [capi.Model(ctx, v, i) for v, i in plan.meshes]
         self.skeletons = [capi.Skeleton(ctx, p, ib) for p, ib in plan.skeletons]
         self.posed_from, self.rest_morphed = set(), set()       # models since their last checkpoint: posed by set_bones_from, morphed into the rest pose
+        self.bound = [dict() for _ in plan.initial]             # per scene: instance -> (handle, serial) of the skeleton it was attached to (rule 36)
+        self.serial = [0 for _ in self.skeletons]               # per slot: how many skeletons have stood there before this one; an address
+        self.retired = set()                                    # may come back, a (slot, serial) does not.  Those destroyed so far
+        self.since = {"blend": False, "solve": False}           # a blend / a solve has posed the skeleton since the last checkpoint
         self.scenes = []
         for inst in plan.initial:
             sc = capi.Scene(ctx)
@@ -1248,6 +1832,25 @@ class GpuBackend:
                 sc.build()
             elif k == "update":
                 sc.update()
+            elif k == "set_transforms_mem":
+                rows = np.ascontiguousarray([M.floats_of(x) for x in op["xs"]], np.float32).reshape(-1, 12)
+                if op["mem"] == "device":               # (count 0: a live pointer all the same)
+                    self.device(rows if len(rows) else np.zeros((1, 12), np.float32), lambda ptr: sc.set_transforms_device(op["first"], ptr, len(rows)))
+                else:                                   # host memory through the same entry point: the binding has no wrapper of it
+                    rc = self.capi.lib().rt_scene_set_instance_transforms_mem(sc.h, op["first"], len(rows), rows.ctypes.data_as(self.capi.C.c_void_p),
+                                                                              self.capi.MEM_HOST)
+                    if rc != 0:
+                        raise self.capi.RtError(rc, self.capi.lib().rt_last_error().decode())
+            elif k == "attach":
+                sk = self.skeletons[op["k"]]
+                sc.attach(op["first"], sk, op["joints"], op["locals"])
+                self.ctx.synchronize()
+                for i in range(op["first"], op["first"] + len(op["joints"])):         # (attached again: the earlier entry is replaced)
+                    self.bound[op["s"]][i] = (sk.h.value, (op["k"], self.serial[op["k"]]))
+            elif k == "detach":
+                sc.detach(op["first"], op["count"])
+                for i in range(op["first"], op["first"] + op["count"]):
+                    self.bound[op["s"]].pop(i, None)
             return
         dev = op.get("mem") == "device"
         if k in SKELETON_OPS:
@@ -1262,6 +1865,17 @@ class GpuBackend:
                 assert clip == sk.info()[2] - 1, "add_clip returned id %d with %d clips" % (clip, sk.info()[2])
             elif k == "skeleton_clear_clips":
                 sk.clear_clips()
+            elif k == "skeleton_add_mask":
+                mask = sk.add_mask(op["weights"])
+                assert mask == sk.n_masks() - 1, "add_mask returned id %d with %d masks" % (mask, sk.n_masks())
+            elif k == "skeleton_clear_masks":
+                sk.clear_masks()
+            elif k == "skeleton_set_blend":
+                sk.set_blend(op["layers"])
+                self.since["blend"] = True
+            elif k == "skeleton_solve_ik":
+                sk.solve_ik(op["constraints"])
+                self.since["solve"] = True
             else:
                 sk.set_time(op["clip"], op["t"])
             return
@@ -1291,6 +1905,8 @@ class GpuBackend:
             m.set_bones_from(self.skeletons[op["k"]])
             self.posed_from.add(op["m"])
             if op.get("destroy"):                       # legal right behind the call: the skin kernel already queued reads a live palette
+                self.retired.add((op["k"], self.serial[op["k"]]))
+                self.serial[op["k"]] += 1
                 self.skeletons[op["k"]].close()
                 self.skeletons[op["k"]] = self.capi.Skeleton(self.ctx, *self.plan.skeletons[op["k"]])
                 self.count("skeletons destroyed right after set_bones_from")
@@ -1411,6 +2027,31 @@ class GpuBackend:
                 for name, got_k, want_k in (("read_pose", gk.pose(), mk.pose), ("read_joints", gk.joints(), mk.joints), ("palette", gk.palette(), mk.palette)):
                     assert canon(got_k).tobytes() == canon(want_k).tobytes(), "%s: %s of skeleton %d" % (what, name, ki)
                 self.count("checkpoints with a posed skeleton")
+            assert gk.n_masks() == mk.num_masks(), "%s: %d masks of skeleton %d" % (what, gk.n_masks(), ki)
+        # transforms() of this scene and of every other scene that is fresh; the attachments by handle (rule 36)
+        for t, (gs, mt) in enumerate(zip(self.scenes, world.scenes)):
+            if t == s or mt.state == M.FRESH:
+                assert gs.transforms().tobytes() == mt.transforms().tobytes(), "%s: transforms() of scene %d" % (what, t)
+        for i in range(len(ms.inst)):
+            got_a, want_a = sc.attachment(i), ms.attachment(i)
+            if got_a is not None:                       # (a live Skeleton of the binding's, or the bare handle of one that was destroyed)
+                got_a = (got_a[0] if isinstance(got_a[0], int) else got_a[0].h.value, got_a[1])
+            want_h = None if want_a is None else (self.bound[s][i][0], want_a[1])
+            assert got_a == want_h, "%s: attachment(%d) is %s, bound was %s" % (what, i, got_a, want_h)
+        if ms.att:
+            self.count("checkpoints with an attached instance")
+            if any(ms.masks[i] == 0 for i in ms.att):
+                self.count("checkpoints with a hidden attached instance")
+            if any(self.bound[s][i][1] in self.retired for i in ms.att):
+                self.count("checkpoints with instances held by a destroyed skeleton")
+        if op["applied"] == ["poses"]:
+            self.count("checkpoints after a pose-only update")
+            if op["frames"]:
+                self.count("frame checkpoints after a pose-only update")
+        for name in ("blend", "solve"):
+            if self.since[name]:
+                self.count("checkpoints after a " + name)
+                self.since[name] = False
         here = set(mi for mi, _ in ms.inst)
         if self.posed_from & here:
             self.count("checkpoints after set_bones_from")

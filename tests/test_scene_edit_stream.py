@@ -1,12 +1,15 @@
 """tests/scene_edit_sweep.py and tests/scene_edit_model.py without a GPU.  The sweep's plans are drawn on the shadow model alone, so what the seeds
 and counts of tests/test_gpu_scene_edit_sweep.py cover can be said here: every operation kind succeeds and every refusable one is refused, an
-update applies each non-empty subset of {transforms, masks, vertices}, and the interleavings the sweep exists for all occur.  The GPU classes are
-replaced by a stand-in that obeys a second shadow model, in the manner of tests/test_fuzz_stream.py, so that run() walks its sequences; and the
-shadow model itself is held to hand-written outcomes, rule by rule (the numbers are those of scene_edit_model's docstring)."""
+update applies each non-empty subset of {transforms, masks, vertices, poses}, and the interleavings the sweep exists for all occur.  The GPU
+classes are replaced by a stand-in that obeys a second shadow model, in the manner of tests/test_fuzz_stream.py, so that run() walks its
+sequences; and the shadow model itself is held to hand-written outcomes, rule by rule (the numbers are those of scene_edit_model's docstring)."""
 import numpy as np
 
+import ik_cases
 import scene_edit_model as M
 import scene_edit_sweep as sweep
+import skeleton_blend_cases
+import skeleton_cases
 import skin_cases
 from deform_cases import grid_mesh, normals_of
 from test_gpu_scene_edit_sweep import SEEDS, SEQUENCES
@@ -18,7 +21,9 @@ Y = X + 100
 OLD_KINDS = {"set_transform", "set_transforms", "set_mask", "set_masks", "add_model", "build", "update", "probe", "set_vertices", "set_positions",
              "recompute_normals", "set_skin", "clear_skin", "set_bones"}
 OLD_REFUSABLE = ("set_transform", "set_transforms", "set_mask", "set_masks", "set_vertices", "set_positions", "set_skin", "set_bones", "update", "build")
-OLD_EVENTS = ({("ok", k) for k in OLD_KINDS if k != "probe"} | {("refused", k) for k in OLD_REFUSABLE} | {("update applies", sub) for sub in sweep.SUBSETS}
+OLD_SUBSETS = [frozenset(x) for x in (("transforms",), ("masks",), ("vertices",), ("transforms", "masks"), ("transforms", "vertices"), ("masks", "vertices"),
+                                      ("transforms", "masks", "vertices"))]
+OLD_EVENTS = ({("ok", k) for k in OLD_KINDS if k != "probe"} | {("refused", k) for k in OLD_REFUSABLE} | {("update applies", sub) for sub in OLD_SUBSETS}
               | {"no-op update", "all hidden refused with transforms and vertices pending, then applied", "hidden and shown again with no update in between",
                  "one instance set twice before one update", "an instance pending and of a changed model", "shared model: scene 0 updated before scene 1",
                  "shared model: scene 1 updated before scene 0", "shared model: one scene back by build, the other by update", "the visible count goes to 1",
@@ -40,6 +45,7 @@ class ModelBackend:
         assert self.world.scenes[op["s"]].readable()
         self.tally["checkpoints"] = self.tally.get("checkpoints", 0) + 1
         self.tally["frame checkpoints"] = self.tally.get("frame checkpoints", 0) + bool(op["frames"])
+        assert self.world.readers() == world.readers()
 
     def close(self):
         pass
@@ -110,9 +116,15 @@ def test_what_the_gpu_seeds_cover():
     assert {p.normals for p in plans} == {True, False} and {p.n_joints for p in plans} == {sweep.N_BONES, sweep.WIDE_BONES}
     assert any(p.shared and p.kinds[0] == "character" for p in plans)       # the model that two scenes hold is, somewhere, the character
     assert sweep.required_events() >= OLD_EVENTS and set(sweep.ALL_KINDS) >= OLD_KINDS      # the list only grows
+    # ... by rules 28 - 40: the seven kinds, every refusal and motif, every subset with "poses" in it, what the GPU test tallies
+    new = {("ok", k) for k in ("set_transforms_mem", "attach", "detach", "skeleton_add_mask", "skeleton_clear_masks", "skeleton_set_blend",
+                               "skeleton_solve_ik")}
+    new |= {("refused", k, why) for k, why in sweep.REFUSALS} | {("motif", m) for m in sweep.MOTIFS} | {("update applies", sub) for sub in sweep.SUBSETS}
+    assert len(sweep.SUBSETS) == 15 and len(sweep.MOTIFS) == 22 and len(sweep.REFUSALS) == 37 and new | set(sweep.TALLY_KEYS) <= sweep.required_events()
+    assert set(sweep.TALLY_KEYS) <= sweep.per_seed_events()
 
 
-# ---- mutants: a library with one rule of the morph targets and skeletons wrong ---------------------------------------------------------------
+# ---- mutants: a library with one rule of the morph targets and skeletons, or of attachments, blends and solves, wrong ---------------------
 class Readers(ModelBackend):
     """a stand-in that is compared as the library is: through its return codes and, at a checkpoint, through what the readers return of the
     models, the skeletons and the checkpoint's own scene.  The rest pose and the morph base are seen by nobody."""
@@ -120,6 +132,8 @@ class Readers(ModelBackend):
     def checkpoint(self, n, op, world):
         mine, theirs = self.world.readers(), world.readers()
         assert mine[:2] == theirs[:2] and mine[2][op["s"]] == theirs[2][op["s"]], "the readers differ"
+        for a, b in zip(mine[2], theirs[2]):               # transforms() of every other scene that is fresh
+            assert b[1] != M.FRESH or a[2] == b[2], "transforms() of another scene differ"
 
     def model(self, op):
         return self.world.models[op["m"]]
@@ -216,13 +230,205 @@ class ClearSkinKeepsTheRedirection(Readers):
 
 
 # where each mutant may show: a return code of the call itself or of a probe, or the readers at a checkpoint.  (a), (c), (d) and (g) change
-# only arrays that no reader returns.  With Planner.epilogue stubbed out every one of the seven is still reported for every seed, so none
-# is caught ONLY because of the epilogue -- but three reports come later: (a) and (g) pass the whole of seed 5's sequence 0 and (d) the
-# whole of seed 329's, where it is the epilogue's set_morph_weights / set_bones and the update behind them that show the drifted base; a later
-# sequence's motif (morph_then_skin, clear_skin_redirects) reports them then.  (c) and the others are reported at the same operation either way.
+# only arrays that no reader returns.  With the producers of Planner.epilogue stubbed out every one of the seven is still reported for every
+# seed, so none is caught ONLY because of the epilogue -- the seeds were chosen so -- but some reports come in a later sequence, the plans
+# being other plans once the epilogue's draws are gone: (b) for seed 242, (d) for all three seeds, (f) for seed 46.
+class Attachments(Readers):
+    """the mutants of rules 28 - 40 look at the stand-in's own scene and skeleton"""
+
+    def scene(self, op):
+        return self.world.scenes[op["s"]]
+
+    def skeleton(self, op):
+        return self.world.skeletons[op["k"]]
+
+
+class PoseAloneIsNoUpdate(Attachments):
+    """(h) an update treats "only a pose since last time" as a no-op"""
+
+    def do(self, op):
+        if op["op"] == "update" and self.scene(op).state != M.UNBUILT and self.scene(op).pending() == {"poses"}:
+            return OK
+        return super().do(op)
+
+
+class SolveDoesNotCount(Attachments):
+    """(i) solve_ik does not count as a pose"""
+    kind = "skeleton_solve_ik"
+
+    def do(self, op):
+        code = super().do(op)
+        if op["op"] == self.kind and code == OK:
+            self.skeleton(op).poses -= 1
+        return code
+
+
+class BlendDoesNotCount(SolveDoesNotCount):
+    """(i) set_blend does not count as a pose"""
+    kind = "skeleton_set_blend"
+
+
+class DetachRestores(Attachments):
+    """(j) detach restores the transform held before the attachment"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.held = {}
+
+    def do(self, op):
+        sc = self.scene(op) if op["op"] in ("attach", "detach") else None
+        before = None if sc is None else (dict(sc.att), list(sc.inst))
+        code = super().do(op)
+        if code == OK and op["op"] == "attach":
+            for i in range(op["first"], op["first"] + len(op["joints"])):
+                if i not in before[0]:
+                    self.held[(op["s"], i)] = before[1][i][1]
+        if code == OK and op["op"] == "detach":
+            for i in range(op["first"], op["first"] + op["count"]):
+                if i in before[0]:
+                    sc.inst[i] = (sc.inst[i][0], self.held.pop((op["s"], i)))
+        return code
+
+
+class AttachWritesAtOnce(Attachments):
+    """(k) attach writes the composed transform at once"""
+
+    def do(self, op):
+        code = super().do(op)
+        if code == OK and op["op"] == "attach" and self.skeleton(op).pose is not None:
+            sc = self.scene(op)
+            for i in range(op["first"], op["first"] + len(op["joints"])):
+                a = sc.att[i]
+                w = a["sk"].joints[a["joint"]]
+                sc.inst[i] = (sc.inst[i][0], w.copy() if a["local"] is None else skeleton_cases.compose(w, a["local"])[0])
+        return code
+
+
+class ComposesFromTheJointsAtTheAttach(Attachments):
+    """(l) an update composes from W as it was at the attach"""
+
+    def do(self, op):
+        code = super().do(op)
+        if code == OK and op["op"] == "attach" and self.skeleton(op).pose is not None:
+            for i in range(op["first"], op["first"] + len(op["joints"])):
+                self.scene(op).att[i]["w0"] = self.skeleton(op).joints.copy()
+        if code == OK and op["op"] in ("update", "build"):
+            sc = self.scene(op)
+            for i, a in sc.att.items():
+                if a.get("w0") is not None:
+                    w = a["w0"][a["joint"]]
+                    sc.inst[i] = (sc.inst[i][0], w.copy() if a["local"] is None else skeleton_cases.compose(w, a["local"])[0])
+        return code
+
+
+class RefusedBlendStillPoses(Attachments):
+    """(m) a refused blend still poses"""
+
+    def do(self, op):
+        code = super().do(op)
+        sk = self.skeleton(op) if op["op"] == "skeleton_set_blend" else None
+        if sk is not None and code != OK and sk.clips:
+            sk.set_pose(skeleton_cases.sampled(sk.clips[0][0], sk.clips[0][1], -np.inf))
+        return code
+
+
+class BlendReadsThePoseBeforeTheSolve(Attachments):
+    """(n) a blend on the current pose reads the pose before the preceding solve"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.before_solve = None
+
+    def do(self, op):
+        solve = op["op"] == "skeleton_solve_ik"
+        held = self.skeleton(op).pose if solve else None
+        code = super().do(op)
+        if code == OK and op["op"] == "skeleton_set_blend" and op["layers"][0][0] is None and self.before_solve is not None:
+            sk = self.skeleton(op)
+            sk.poses -= 1
+            sk.set_pose(skeleton_blend_cases.blended(sk.clips, sk.masks, op["layers"], current=self.before_solve))
+        if code == OK and op["op"] in sweep.POSE_OPS:
+            self.before_solve = held.copy() if solve and held is not None else None
+        if code == OK and op["op"] == "set_bones_from" and op.get("destroy"):
+            self.before_solve = None
+        return code
+
+
+class FollowsTheReplacement(Attachments):
+    """(o) instances of a destroyed skeleton follow its replacement"""
+
+    def do(self, op):
+        old = self.world.skeletons[op["k"]] if op["op"] == "set_bones_from" else None
+        code = super().do(op)
+        if old is not None and self.world.skeletons[op["k"]] is not old:
+            for sc in self.world.scenes:
+                for a in sc.att.values():
+                    if a["sk"] is old:
+                        a["sk"], a["seen"] = self.world.skeletons[op["k"]], None
+        return code
+
+
+class SetterOverAnAttachedRange(Attachments):
+    """(p) a transform setter over an attached range is accepted and wins the next update"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.won = {}                                      # (scene, instance) -> the floats a setter gave an attached instance
+
+    def do(self, op):
+        code = super().do(op)
+        sc = self.scene(op) if op["op"] in sweep.SCENE_OPS else None
+        if code != OK and op["op"] in ("set_transform", "set_transforms", "set_transforms_mem"):
+            first, n = (op["i"], 1) if op["op"] == "set_transform" else (op["first"], len(op["xs"]))
+            if first + n <= len(sc.inst):                    # refused for the attachment alone: taken, as if nobody were attached there
+                held = {i: sc.att.pop(i) for i in range(first, first + n) if i in sc.att}
+                code = super().do(op)
+                for i, a in held.items():
+                    sc.att[i] = a
+                    self.won[(op["s"], i)] = sc.inst[i][1]
+        if code == OK and op["op"] in ("update", "build"):  # ... and the joint does not take the instance back
+            for (s, i) in [k for k in self.won if k[0] == op["s"]]:
+                sc.inst[i] = (sc.inst[i][0], self.won.pop((s, i)))
+        return code
+
+
+class RefusedUpdateRecordsThePose(Attachments):
+    """(q) a refused update (nothing visible, or an unposed attachment) still records the pose as applied, so the pose is lost"""
+
+    def do(self, op):
+        code = super().do(op)
+        if code != OK and op["op"] in ("update", "build") and self.scene(op).state != M.UNBUILT:
+            for a in self.scene(op).att.values():
+                a["seen"] = a["sk"].poses
+        return code
+
+
+class ReattachKeepsTheLocal(Attachments):
+    """(r) re-attaching without locals keeps the old local"""
+
+    def do(self, op):
+        old = {i: a["local"] for i, a in self.scene(op).att.items()} if op["op"] == "attach" else {}
+        code = super().do(op)
+        if code == OK and op["op"] == "attach" and op["locals"] is None:
+            for i in range(op["first"], op["first"] + len(op["joints"])):
+                if old.get(i) is not None:
+                    self.scene(op).att[i]["local"] = old[i]
+        return code
+
+
 MUTANTS = [(RecapturesBase, ("update", "build")), (RestMorphMarksStale, ("probe",)), (RestMorphWritesVertices, ("update", "build")),
            (Accumulates, ("update", "build")), (LatePalette, ("update", "build")), (RefusalDropsTargets, ("set_morph_weights", "update", "build")),
-           (ClearSkinKeepsTheRedirection, ("probe", "update", "build"))]
+           (ClearSkinKeepsTheRedirection, ("probe", "update", "build")),
+           # rules 28 - 40.  (h), (i), (l), (q) and (r) leave an attached instance where it was or put it elsewhere: transforms() at the update
+           # itself; (j) and (k) change floats that the next update or build of the scene shows; (m) and (n) change the skeleton's pose: every
+           # checkpoint reads it, and a call that needs a pose (or must be refused for want of one) answers otherwise; (o): the update is
+           # refused for the replacement's missing pose, or moves the instances; (p): the setter's code, before any update could show more
+           (PoseAloneIsNoUpdate, ("update",)), (SolveDoesNotCount, ("update",)), (BlendDoesNotCount, ("update",)), (DetachRestores, ("update", "build")),
+           (AttachWritesAtOnce, ("update", "build")), (ComposesFromTheJointsAtTheAttach, ("update", "build")),
+           (RefusedBlendStillPoses, ("update", "build", "set_bones_from", "skeleton_set_blend", "skeleton_solve_ik")),
+           (BlendReadsThePoseBeforeTheSolve, ("update", "build")), (FollowsTheReplacement, ("update", "build")),
+           (SetterOverAnAttachedRange, ("set_transform", "set_transforms", "set_transforms_mem")), (RefusedUpdateRecordsThePose, ("update", "build")),
+           (ReattachKeepsTheLocal, ("update", "build"))]
 
 
 def test_every_mutant_of_the_new_rules_is_reported():
@@ -405,6 +611,216 @@ def test_set_bones_from_takes_the_palette_as_it_is_at_the_call():
     trs[0, 0] = 50
     assert sk.set_pose(trs) == OK and m.geometry().tobytes() == want.tobytes()                      # a later pose reaches no vertex
     assert s.update() == (OK, frozenset(["vertices"])) and m.geometry().tobytes() == want.tobytes()
+
+
+# (rules 28 - 40)
+def row(x, y, z):
+    return np.array(translation(x, y, z), np.float32)
+
+
+def attached_world(n_instances=3, n_scenes=1):
+    """world() and a skeleton of two joints in slot 0: posed with `trs`, the root stands at (1, 0, 0) and its child at (1, 2, 0)"""
+    w = world(n_instances, n_scenes)
+    w.add_skeleton([-1, 0], skin_cases.identity_palette(2))
+    return w, w.scenes[0], w.skeletons[0], two_joints()[1]
+
+
+def test_transforms_from_device_memory_are_the_host_setter():
+    w = world()
+    s = w.scenes[0]
+    s.build()
+    assert s.set_transforms_mem(1, [Y, None], "device") == OK and s.state == M.STALE and s.pending() == {"transforms"}           # rule 28
+    assert s.transforms().tolist() == [M.IDENTITY_FLOATS.tolist(), Y.tolist(), M.IDENTITY_FLOATS.tolist()]
+    before = w.snapshot()
+    assert s.set_transforms_mem(2, [Y, Y], "device") == STATE and s.set_transforms_mem(4, [], "host") == STATE and w.snapshot() == before
+    assert s.set_transforms_mem(3, [], "device") == OK and w.snapshot() == before
+    assert s.update() == (OK, frozenset(["transforms"])) and s.transforms()[1].tolist() == Y.tolist()
+    assert s.set_transforms_mem(0, [Y], "host") == OK and s.transforms()[0].tolist() == Y.tolist() and s.state == M.STALE
+
+
+def test_attach_refuses_the_range_before_the_joint():
+    w, s, sk, trs = attached_world()
+    s.build()
+    before = w.snapshot()
+    assert s.attach(2, sk, [0, 1]) == STATE and s.attach(4, sk, []) == STATE                        # rule 29: beyond the instances
+    assert s.attach(0, sk, [2]) == INVALID and s.attach(1, sk, [0, 2], [X, X]) == INVALID           # a joint >= n_joints
+    assert s.attach(2, sk, [0, 5]) == STATE                                                         # both: the range wins
+    assert s.attach(3, sk, []) == OK and s.attach(0, sk, []) == OK                                  # count 0
+    assert w.snapshot() == before and s.state == M.FRESH and s.attachment(0) is None                # rule 10
+
+
+def test_an_attached_instance_follows_its_joint_at_the_update():
+    w, s, sk, trs = attached_world()
+    s.build()
+    assert s.attach(1, sk, [1]) == OK and s.state == M.STALE and s.pending() == {"transforms"}      # rule 30: pending, and no float changed
+    assert s.transforms()[1].tolist() == X.tolist() and s.attachment(1) == (sk, 1) and s.attachment(0) is None
+    before = w.snapshot()
+    assert s.update() == (STATE, None) and s.build() == (STATE, None) and w.snapshot() == before    # rule 35: no pose yet
+    assert sk.set_pose(trs) == OK and s.state == M.STALE and s.pending() == {"transforms", "poses"}
+    assert s.update() == (OK, frozenset(["transforms", "poses"]))
+    assert s.transforms()[1].tobytes() == row(1, 2, 0).tobytes() and s.transforms()[2].tolist() == (X * 2).tolist()     # rule 34: W bit for bit
+    far = trs.copy()
+    far[0, 0] = 3
+    assert sk.set_pose(far) == OK and s.state == M.FRESH and s.readable() and s.pending() == {"poses"}      # rule 33
+    assert s.transforms()[1].tobytes() == row(1, 2, 0).tobytes()
+    assert s.update() == (OK, frozenset(["poses"])) and s.transforms()[1].tobytes() == row(3, 2, 0).tobytes()
+    assert s.update() == (OK, frozenset())                                                          # rule 11: counted once
+    assert s.attach(1, sk, [0], [row(0, 0, 5)]) == OK and s.transforms()[1].tobytes() == row(3, 2, 0).tobytes()       # attached again: replaced
+    assert s.update() == (OK, frozenset(["transforms", "poses"])) and s.transforms()[1].tobytes() == row(3, 0, 5).tobytes() and s.attachment(1) == (sk, 0)
+    assert s.attach(1, sk, [0]) == OK and s.update()[0] == OK and s.transforms()[1].tobytes() == row(3, 0, 0).tobytes()  # without locals: the local is gone
+
+
+def test_an_attachment_on_an_unbuilt_scene_only_stores():
+    w, s, sk, trs = attached_world()
+    assert s.attach(0, sk, [0, 1], [row(0, 0, 1), row(0, 0, 2)]) == OK and s.state == M.UNBUILT and not s.pending()         # rule 30
+    assert s.transforms()[0].tolist() == M.IDENTITY_FLOATS.tolist()
+    assert s.build() == (STATE, None)                                                               # rule 35
+    sk.set_pose(trs)
+    assert s.build()[0] == OK and s.transforms()[:2].tolist() == [row(1, 0, 1).tolist(), row(1, 2, 2).tolist()]
+
+
+def test_the_joints_are_those_at_the_update_not_at_the_attach():
+    w, s, sk, trs = attached_world()
+    s.build()
+    sk.set_pose(trs)
+    s.attach(2, sk, [0])
+    far = trs.copy()
+    far[0, 0] = 7
+    sk.set_pose(far)
+    assert s.update()[0] == OK and s.transforms()[2].tobytes() == row(7, 0, 0).tobytes()            # rule 34
+
+
+def test_a_composed_identity_is_the_identity():
+    w, s, sk, trs = attached_world(n_instances=1)
+    s.build()
+    s.attach(0, sk, [0])
+    trs[0, 0] = 0
+    sk.set_pose(trs)
+    assert s.update()[0] == OK and s.inst[0][1] is not None and M.is_identity(s.inst[0][1])         # rule 34
+    sk.set_pose(two_joints()[1])
+    assert s.update()[0] == OK and not M.is_identity(s.inst[0][1])
+
+
+def test_transform_setters_over_an_attached_range_are_refused():
+    w, s, sk, trs = attached_world()
+    s.build()
+    s.attach(1, sk, [0])
+    before = w.snapshot()
+    for call in (lambda: s.set_transform(1, Y), lambda: s.set_transforms(0, [Y, Y]), lambda: s.set_transforms(1, [Y, Y]),
+                 lambda: s.set_transforms_mem(1, [Y], "device"), lambda: s.set_transforms_mem(0, [Y, Y, Y], "host")):
+        assert call() == STATE and w.snapshot() == before                                           # rule 31
+    assert s.set_transforms(1, []) == OK and w.snapshot() == before                                 # (count 0 holds nobody)
+    assert s.set_transform(0, Y) == OK and s.set_transforms_mem(2, [Y], "device") == OK
+
+
+def test_detach_keeps_what_the_last_update_gave():
+    w, s, sk, trs = attached_world()
+    s.build()
+    s.attach(1, sk, [1])
+    sk.set_pose(trs)
+    s.update()
+    far = trs.copy()
+    far[0, 0] = 3
+    sk.set_pose(far)
+    before = w.snapshot()
+    assert s.detach(2, 2) == STATE and s.detach(4, 0) == STATE and w.snapshot() == before           # rule 32
+    assert s.detach(0, 1) == OK and s.detach(3, 0) == OK and w.snapshot() == before                 # nobody attached there: a no-op
+    assert s.detach(0, 3) == OK and s.attachment(1) is None and s.state == M.FRESH and not s.pending()
+    assert s.update() == (OK, frozenset()) and s.transforms()[1].tobytes() == row(1, 2, 0).tobytes()        # the first pose, not the second
+    assert s.set_transform(1, Y) == OK                                                              # ... and the setters take it again
+    s.update()
+    assert s.attach(2, sk, [0]) == OK and s.detach(2, 1) == OK                                      # let go before any update: the floats never changed
+    assert s.update()[0] == OK and s.transforms()[2].tolist() == (X * 2).tolist()
+
+
+def test_a_refused_update_keeps_the_pose_pending_too():
+    w, s, sk, trs = attached_world()
+    s.build()
+    s.attach(1, sk, [0])
+    sk.set_pose(trs)
+    s.update()
+    s.set_masks(0, [0, 0, 0])
+    far = trs.copy()
+    far[0, 0] = 3
+    sk.set_pose(far)
+    before = w.snapshot()
+    assert s.update() == (STATE, None) and w.snapshot() == before                                   # rules 12, 35
+    s.set_mask(0, 1)
+    assert s.update() == (OK, frozenset(["masks", "poses"])) and s.transforms()[1].tobytes() == row(3, 0, 0).tobytes()      # the hidden instance too
+
+
+def test_a_binding_holds_the_skeleton_not_its_slot():
+    w, a, sk, trs = attached_world(n_scenes=2)
+    b = w.scenes[1]
+    for s in (a, b):
+        s.build()
+        s.attach(1, sk, [0])
+    sk.set_pose(trs)
+    assert a.update()[0] == OK and b.pending() == {"transforms", "poses"} and b.update()[0] == OK
+    far = trs.copy()
+    far[0, 0] = 3
+    sk.set_pose(far)                                                                                # one pose, two scenes: each keeps its own record
+    assert b.update() == (OK, frozenset(["poses"])) and a.pending() == {"poses"} and a.transforms()[1].tobytes() == row(1, 0, 0).tobytes()
+    assert a.update() == (OK, frozenset(["poses"])) and a.transforms()[1].tobytes() == row(3, 0, 0).tobytes()
+    w.replace_skeleton(0)                                                                           # rule 36: destroyed; a new one in the slot
+    new = w.skeletons[0]
+    assert new is not sk and new.pose is None and new.uid != sk.uid and a.attachment(1) == (sk, 0)
+    new.set_pose(trs)
+    assert a.pending() == frozenset() and a.update() == (OK, frozenset()) and a.transforms()[1].tobytes() == row(3, 0, 0).tobytes()
+    assert a.attach(2, new, [1]) == OK and a.update()[0] == OK and a.transforms()[2].tobytes() == row(1, 2, 0).tobytes()
+
+
+def test_masks_and_blends():
+    B = skeleton_blend_cases
+    w, s, sk, trs = attached_world()
+    far = trs.copy()
+    far[0, 0] = 3
+    assert sk.add_clip([0, 1], np.stack([trs, far])) == OK
+    assert sk.num_masks() == 0 and sk.add_mask([1, 0]) == OK and sk.num_masks() == 1                # rule 37
+    assert sk.clear_masks() == OK and sk.num_masks() == 0 and sk.add_mask([1, 0]) == OK and sk.add_mask([0, 1]) == OK and sk.num_masks() == 2
+    base, nan = (0, 0.0, 1.0, None, B.BLEND), float("nan")
+    assert sk.set_blend([(None, 0.0, 1.0, None, B.BLEND)]) == STATE and sk.readers() is None and sk.poses == 0      # rule 38: no pose to be current
+    assert sk.set_blend([(None, 0.0, 1.0, None, B.BLEND), (0, nan, 1.0, None, B.BLEND)]) == INVALID                 # the first group first
+    assert sk.set_blend([base]) == OK and sk.pose.tobytes() == trs.tobytes() and sk.poses == 1                      # one layer: set_time
+    before = w.snapshot()
+    for layers, code in (([base] * 9, INVALID), ([], INVALID), ([(0, 0.0, 1.0, None, B.ADDITIVE)], INVALID), ([base, (None, 0.0, 1.0, None, B.BLEND)], INVALID),
+                         ([base, (0, nan, 1.0, None, B.BLEND)], INVALID), ([(1, 0.0, 1.0, None, B.BLEND)], STATE), ([base, (0, 0.0, 1.0, 2, B.BLEND)], STATE),
+                         ([(1, 0.0, 1.0, None, B.BLEND), (0, nan, 1.0, None, B.BLEND)], INVALID)):
+        assert sk.set_blend(layers) == code and w.snapshot() == before, layers                      # rules 38, 40: a refusal poses nothing, counts nothing
+    assert sk.set_blend([(None, 0.0, 1.0, None, B.BLEND), (0, 1.0, 0.5, 0, B.BLEND)]) == OK and sk.poses == 2       # the current pose, half way to the last key
+    assert sk.pose[0, 0] == 2 and sk.pose[1].tobytes() == trs[1].tobytes()                          # where the mask is 1; the child's weight is 0
+    assert sk.joints.tolist() == [translation(2, 0, 0), translation(2, 2, 0)] and sk.num_masks() == 2
+
+
+def test_solve_ik_refuses_and_solves():
+    w, s, sk, trs = attached_world()
+    aim = (ik_cases.AIM, 0, (0.0, 2.0, 0.0), (1.0, 0.0, 0.0), 1.0)
+    assert sk.solve_ik([aim]) == STATE and sk.poses == 0                                            # rule 39: no pose yet
+    assert sk.solve_ik([aim[:4] + (float("nan"),)]) == INVALID                                      # ... but the first group is held to first
+    trs[0, 0] = 0
+    sk.set_pose(trs)
+    before = w.snapshot()
+    for cs in ([aim] * 33, [], [(7,) + aim[1:]], [(ik_cases.AIM, 2) + aim[2:]], [(ik_cases.TWO_BONE, 1) + aim[2:]], [aim[:4] + (float("nan"),)],
+               [aim, aim], [aim, (ik_cases.AIM, 1) + aim[2:]]):
+        assert sk.solve_ik(cs) == INVALID and w.snapshot() == before, cs                            # rules 39, 40
+    want = ik_cases.solved(sk.parents, sk.pose, sk.joints, [aim])
+    assert sk.solve_ik([aim]) == OK and sk.poses == 2 and sk.pose.tobytes() == want.tobytes()
+    assert sk.pose[:, [0, 1, 2, 7, 8, 9]].tobytes() == trs[:, [0, 1, 2, 7, 8, 9]].tobytes() and sk.pose[1].tobytes() == trs[1].tobytes()
+    assert np.allclose(sk.joints[0].reshape(3, 4)[:, 0], [0, 1, 0], atol=1e-6)                      # the root's +x now points at the target
+
+
+def test_every_producer_counts_as_one_pose():
+    w, s, sk, trs = attached_world()
+    s.build()
+    s.attach(1, sk, [0])
+    sk.add_clip([0, 1], np.stack([trs, trs]))
+    B = skeleton_blend_cases
+    for n, pose in enumerate((lambda: sk.set_pose(trs), lambda: sk.set_time(0, 0.5), lambda: sk.set_blend([(0, 0.5, 1.0, None, B.BLEND)]),
+                              lambda: sk.solve_ik([(ik_cases.AIM, 1, (0.0, 2.0, 0.0), (1.0, 0.0, 0.0), 0.25)]))):
+        assert pose() == OK and sk.poses == n + 1 and "poses" in s.pending()                        # rule 40
+        assert s.update()[0] == OK and s.update() == (OK, frozenset())
+    assert sk.set_time(0, float("nan")) == INVALID and sk.set_time(3, 0.0) == STATE and sk.solve_ik([]) == INVALID and sk.set_blend([]) == INVALID
+    assert sk.poses == 4 and s.update() == (OK, frozenset())                                        # a refused one counts as none
 
 
 # (rules 1 - 16)
