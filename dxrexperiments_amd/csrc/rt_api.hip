@@ -181,11 +181,11 @@ static int context_create(int device, void *stream, bool own, rt_context **out)
     c->own_stream = own;
     if (own) {
         hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { rt_set_error("hipStreamCreate: %s", hipGetErrorString(e)); delete c; return RT_ERR_HIP; }
+        if (e != hipSuccess) { rt_set_error("hipStreamCreate: %s", hipGetErrorString(e)); rt_context_release(c); return RT_ERR_HIP; }
     } else c->stream = (hipStream_t)stream;
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
         rt_set_error("hipEventCreate failed");
-        delete c;          // (the stream and the first event go with it)
+        rt_context_release(c);         // (the stream and the first event go with it)
         return RT_ERR_HIP;
     }
     hipDeviceProp_t prop;
@@ -250,15 +250,6 @@ int rt_context_destroy(rt_context *ctx)
 }
 
 }  // extern "C"
-
-void rt_context_retain(rt_context *ctx) { if (ctx) ctx->refs++; }
-
-// The context lives until its handle AND every object created on it are gone.
-void rt_context_release(rt_context *ctx)
-{
-    if (!ctx || --ctx->refs > 0) return;
-    delete ctx;
-}
 
 rt_context::~rt_context()
 {

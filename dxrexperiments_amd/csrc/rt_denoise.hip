@@ -198,8 +198,9 @@ __global__ void k_denoise_f16(const float4 *__restrict__ in, ushort4 *__restrict
 
 }  // namespace
 
-struct rt_denoiser {
-    rt_context *ctx = nullptr;
+struct rt_denoiser : rt_handle {
+    using rt_handle::rt_handle;
+    static constexpr bool joins_stream = true;
     rt_denoiser_params prm;
     uint32_t width = 0, height = 0, format = RT_FORMAT_R32G32B32A32_FLOAT;
     DevBuf out[2], half_out;        // out[0] = pass H, out[1] = pass V (the result, DenoiseCompositor.h:23)
@@ -207,8 +208,6 @@ struct rt_denoiser {
     bool dispatched = false;
     ~rt_denoiser()
     {
-        (void)hipSetDevice(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
     }
@@ -219,28 +218,19 @@ extern "C" {
 int rt_denoiser_create(rt_context *ctx, rt_denoiser **out)
 {
     RT_REQUIRE(ctx && out, "null argument");
-    rt_denoiser *d = new (std::nothrow) rt_denoiser();
-    if (!d) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    d->ctx = ctx;
-    rt_context_retain(ctx);
+    rt_made<rt_denoiser> d;
+    RT_TRY(rt_make(ctx, d));
     d->prm.exposure = 1.0f;          // src/DenoiseCompositor.cpp:44-49
     d->prm.gamma = 2.2f;
     d->prm.tonemap = 1;
     d->prm.gammaCorrect = 0;
     d->prm.maxKernelSize = 12;
     d->prm.debugVisualize = 0;
-    *out = d;
+    *out = d.release();
     return RT_OK;
 }
 
-int rt_denoiser_destroy(rt_denoiser *d)
-{
-    if (!d) return RT_OK;
-    rt_context *ctx = d->ctx;
-    delete d;
-    rt_context_release(ctx);
-    return RT_OK;
-}
+int rt_denoiser_destroy(rt_denoiser *d) { return rt_release(d); }
 
 int rt_denoiser_get_params(rt_denoiser *d, rt_denoiser_params **params)
 {
@@ -254,7 +244,7 @@ int rt_denoiser_create_output(rt_denoiser *d, uint32_t format, uint32_t width, u
     RT_REQUIRE(d, "null denoiser");
     RT_REQUIRE(width > 0 && height > 0, "empty output");
     RT_REQUIRE(format == RT_FORMAT_R32G32B32A32_FLOAT || format == RT_FORMAT_R16G16B16A16_FLOAT, "unsupported output format");
-    HIP_TRY(hipSetDevice(d->ctx->device));
+    RT_TRY(rt_use_device(d->ctx));
     for (DevBuf &b : d->out) RT_TRY(b.reserve((size_t)width * height * 16));
     d->width = width; d->height = height; d->format = format;
     return RT_OK;
@@ -269,7 +259,7 @@ int rt_denoiser_dispatch(rt_denoiser *d, const void *direct_lighting, const void
         rt_set_error("maxKernelSize %d outside 0..%d (the filter's tile halo)", d->prm.maxKernelSize, MAX_EXTENT);
         return RT_ERR_INVALID_ARG;
     }
-    HIP_TRY(hipSetDevice(d->ctx->device));
+    RT_TRY(rt_use_device(d->ctx));
     hipStream_t st = d->ctx->stream;
     if (!d->ev0) { HIP_TRY(hipEventCreate(&d->ev0)); HIP_TRY(hipEventCreate(&d->ev1)); }
     DenoiseArgs a;
@@ -301,7 +291,7 @@ static int denoiser_read(rt_denoiser *d, int which, void *host, size_t bytes)
 {
     RT_REQUIRE(d && host, "null argument");
     if (!d->dispatched) { rt_set_error("nothing dispatched yet"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(d->ctx->device));
+    RT_TRY(rt_use_device(d->ctx));
     hipStream_t st = d->ctx->stream;
     const size_t npix = (size_t)d->width * d->height;
     if (d->format == RT_FORMAT_R16G16B16A16_FLOAT) {
@@ -324,7 +314,7 @@ int rt_denoiser_last_ms(rt_denoiser *d, float *ms)
 {
     RT_REQUIRE(d && ms, "null argument");
     if (!d->dispatched) { rt_set_error("nothing dispatched yet"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(d->ctx->device));
+    RT_TRY(rt_use_device(d->ctx));
     HIP_TRY(hipEventSynchronize(d->ev1));
     HIP_TRY(hipEventElapsedTime(ms, d->ev0, d->ev1));
     return RT_OK;

@@ -180,8 +180,9 @@ int check_one_device_per_rank(const rt_context *ctx, int rank, int world, const 
 
 }  // namespace
 
-struct rt_dist {
-    rt_context *ctx = nullptr;
+struct rt_dist : rt_handle {
+    using rt_handle::rt_handle;
+    static constexpr bool joins_stream = true;
     Rccl *lib = nullptr;
     nccl_comm comm = nullptr;
     int rank = 0, world = 1;
@@ -191,8 +192,6 @@ struct rt_dist {
     bool timed = false;                // an event pair brackets the last collective
     ~rt_dist()
     {
-        (void)hipSetDevice(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
         if (comm) (void)lib->comm_destroy(comm);
         if (!rendezvous_file.empty()) unlink(rendezvous_file.c_str());
         if (ev0) (void)hipEventDestroy(ev0);
@@ -257,17 +256,16 @@ int rt_dist_create(rt_context *ctx, int rank, int world, const void *id128, rt_d
     RT_REQUIRE(world >= 1 && rank >= 0 && rank < world, "rank outside [0, world)");
     Rccl *lib;
     RT_TRY(load_rccl(&lib));
-    HIP_TRY(hipSetDevice(ctx->device));
-    rt_dist *d = new (std::nothrow) rt_dist();
-    if (!d) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    d->ctx = ctx; d->lib = lib; d->rank = rank; d->world = world;
+    RT_TRY(rt_use_device(ctx));
+    rt_made<rt_dist> d;
+    RT_TRY(rt_make(ctx, d));
+    d->lib = lib; d->rank = rank; d->world = world;
     {
         const int chk = check_one_device_per_rank(ctx, rank, world, id128, &d->rendezvous_file);
         if (chk != RT_OK) {
             // (this rank's entry stays: the other rank on the same device has to find it to fail the same way instead of
             // waiting for RCCL; the next rendezvous on this node sweeps it)
             d->rendezvous_file.clear();
-            delete d;
             return chk;
         }
     }
@@ -277,23 +275,14 @@ int rt_dist_create(rt_context *ctx, int rank, int world, const void *id128, rt_d
     if (rc != 0) {
         rt_set_error("ncclCommInitRank(rank %d of %d): %s", rank, world, lib->error_string ? lib->error_string(rc) : "RCCL error");
         d->comm = nullptr;
-        delete d;
         return RT_ERR_HIP;
     }
     if (hipEventCreate(&d->ev0) != hipSuccess || hipEventCreate(&d->ev1) != hipSuccess) { d->ev0 = nullptr; d->ev1 = nullptr; }
-    rt_context_retain(ctx);
-    *out = d;
+    *out = d.release();
     return RT_OK;
 }
 
-int rt_dist_destroy(rt_dist *d)
-{
-    if (!d) return RT_OK;
-    rt_context *ctx = d->ctx;
-    delete d;
-    rt_context_release(ctx);
-    return RT_OK;
-}
+int rt_dist_destroy(rt_dist *d) { return rt_release(d); }
 
 int rt_dist_get_rank(const rt_dist *d, int *rank, int *world)
 {
@@ -306,7 +295,7 @@ int rt_dist_all_reduce_sum(rt_dist *d, void *device_f32, size_t count)
 {
     RT_REQUIRE(d && device_f32, "null argument");
     RT_TRY(rt_context_flush_deferred(d->ctx));        // frames a deferred pipeline still holds belong to the image that is exchanged
-    HIP_TRY(hipSetDevice(d->ctx->device));
+    RT_TRY(rt_use_device(d->ctx));
     d->timed = false;
     if (d->ev0) HIP_TRY(hipEventRecord(d->ev0, d->ctx->stream));
     NCCL_TRY(d->lib, d->lib->all_reduce(device_f32, device_f32, count, NCCL_FLOAT, NCCL_SUM, d->comm, d->ctx->stream));
@@ -319,7 +308,7 @@ int rt_dist_last_collective_ms(rt_dist *d, float *ms)
     RT_REQUIRE(d && ms, "null argument");
     *ms = 0.0f;
     if (!d->timed) { rt_set_error("rt_dist_last_collective_ms: no collective has been issued"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(d->ctx->device));
+    RT_TRY(rt_use_device(d->ctx));
     HIP_TRY(hipEventSynchronize(d->ev1));
     HIP_TRY(hipEventElapsedTime(ms, d->ev0, d->ev1));
     return RT_OK;
@@ -339,7 +328,7 @@ int rt_dist_gather_bands(rt_dist *d, void *device_rgba32f, uint32_t width, uint3
     uint32_t slots = 0;
     size_t floats = 0;
     RT_TRY(rt_tile_gather_layout(width, height, band_rows, (uint32_t)d->world, &slots, &floats));
-    HIP_TRY(hipSetDevice(d->ctx->device));
+    RT_TRY(rt_use_device(d->ctx));
     hipStream_t st = d->ctx->stream;
     const size_t chunk_pixels = floats / 4;
     d->timed = false;

@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <memory>
+#include <new>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -44,7 +46,7 @@ size_t &rt_alloc_limit_ref();
 static inline size_t rt_alloc_limit() { return rt_alloc_limit_ref(); }
 
 // Owning device allocation; grows on demand, never shrinks.  Frees itself when it goes out of scope and moves, never copies: an owner
-// lists no buffers to release, it only selects the device (and joins its stream) before its members die.  None has static or thread storage
+// lists no buffers to release, and rt_release (below, with rt_handle) selects the device before its members die.  None has static or thread storage
 // duration: a hipFree after the runtime has shut down is not acceptable.
 struct DevBuf {
     void *p = nullptr;
@@ -241,7 +243,7 @@ struct SceneDev {
 #define RT_PINNED_WORDS 128
 #define RT_PINNED_LBVH 64
 struct rt_context {
-    int refs = 1;                // handle + every model / scene / pipeline created on it
+    int refs = 1;                // handle + every object created on it (rt_handle); touched by rt_context_retain / _release only
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -290,6 +292,43 @@ struct rt_context {
 };
 
 static inline int rt_use_device(const rt_context *ctx) { HIP_TRY(hipSetDevice(ctx->device)); return RT_OK; }
+
+// The context lives until its handle AND every object created on it are gone.
+static inline void rt_context_retain(rt_context *ctx) { if (ctx) ctx->refs++; }
+static inline void rt_context_release(rt_context *ctx) { if (ctx && --ctx->refs == 0) delete ctx; }
+
+// What every host object but the context is: made on a context, which it retains until its OWN members are gone (a base's destructor runs
+// after the derived members'), and counted: its handle + whoever rt_retain()s it.  A type says with `joins_stream` whether its last
+// release waits for the context's stream (queued work may still read its buffers) before the object dies.
+struct rt_handle {
+    rt_context *const ctx;
+    int refs = 1;
+    explicit rt_handle(rt_context *c) : ctx(c) { rt_context_retain(c); }
+    rt_handle(const rt_handle &) = delete;
+    rt_handle &operator=(const rt_handle &) = delete;
+protected:
+    ~rt_handle() { rt_context_release(ctx); }
+};
+
+template <class T> void rt_retain(T *x) { x->refs++; }
+// every *_destroy, and the one way out of a *_create that fails: the last reference selects the device, joins, deletes
+template <class T> int rt_release(T *x)
+{
+    if (!x || --x->refs > 0) return RT_OK;
+    (void)hipSetDevice(x->ctx->device);
+    if (T::joins_stream) (void)hipStreamSynchronize(x->ctx->stream);
+    delete x;
+    return RT_OK;
+}
+// an object between `new` and `*out = x.release()`
+struct rt_releaser { template <class T> void operator()(T *x) const { (void)rt_release(x); } };
+template <class T> using rt_made = std::unique_ptr<T, rt_releaser>;
+template <class T> int rt_make(rt_context *ctx, rt_made<T> &x)
+{
+    x.reset(new (std::nothrow) T(ctx));
+    if (!x) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
+    return RT_OK;
+}
 // `bytes` of a host array into a buffer grown to hold them, queued on the context's stream
 static inline int rt_upload(rt_context *ctx, DevBuf &b, const void *host, size_t bytes)
 {
@@ -328,9 +367,9 @@ struct ModelMorph {
     DevBuf base;                 // rt_vertex[n_verts]: the base, captured when the targets were set
 };
 
-struct rt_model {
-    rt_context *ctx = nullptr;
-    int refs = 1;
+struct rt_model : rt_handle {
+    using rt_handle::rt_handle;  // refs: handle + rt_model_retain + every instance of a scene
+    static constexpr bool joins_stream = false;
     uint32_t n_verts = 0, n_tris = 0;
     std::vector<rt_vertex> h_verts;
     std::vector<uint32_t> h_idx;
@@ -350,7 +389,6 @@ struct rt_model {
     bool adj_ready = false;
     ModelSkin skin;
     ModelMorph morph;
-    ~rt_model();                // (rt_model.hip) selects the device before the buffers go
 };
 
 // rt_skeleton_create (rt_skeleton.hip): a joint hierarchy, its current pose and the palette a skin reads
@@ -359,9 +397,9 @@ struct SkeletonClip {
     DevBuf keys;                 // float[n_keys][10][n_joints]: component major within a key, so that the lanes of a wave read 64 consecutive floats
 };
 
-struct rt_skeleton {
-    rt_context *ctx = nullptr;
-    int refs = 1;                // handle + every scene that has instances attached to it (once per scene)
+struct rt_skeleton : rt_handle {
+    using rt_handle::rt_handle;  // refs: handle + every scene that has instances attached to it (once per scene)
+    static constexpr bool joins_stream = true;       // a skin kernel that reads the palette, or a pose kernel, may still be queued
     uint64_t pose_count = 0;     // bumped by every pose set or sampled: a scene records it per attached instance at build / update (SceneInstance::seen_pose)
     uint32_t n_joints = 0, n_levels = 0;
     std::vector<uint32_t> level_offsets;     // n_levels + 1 (rt_skeleton.h)
@@ -375,7 +413,6 @@ struct rt_skeleton {
     bool posed = false;          // a pose has been set or sampled: joints and palette hold something
     std::vector<SkeletonClip> clips;
     std::vector<DevBuf> masks;   // rt_skeleton_add_mask: float[n_joints] each, one weight per joint of a blend layer (rt_skeleton_set_blend)
-    ~rt_skeleton();              // (rt_skeleton.hip) selects the device and joins the stream before the buffers go
 };
 
 // Where an instance's transform comes from.  Host: SceneInstance::xform is the truth.  Device: set from device memory, rt_scene::d_xf holds it and
@@ -398,9 +435,9 @@ struct SceneInstance {
 // The records and the binding mirrors (inst, att_words, att_local) have exactly inst.size() entries at every entry point: rt_scene_add_model
 // lengthens them together and nothing else does.  h_inst and h_blas_bounds are a build's output, one entry per instance of an updatable scene;
 // the device arrays are sized for all instances at once (rt_scene.hip).
-struct rt_scene {
-    rt_context *ctx = nullptr;
-    int refs = 1;                // handle + every pipeline it is set on
+struct rt_scene : rt_handle {
+    using rt_handle::rt_handle;  // refs: handle + every pipeline it is set on
+    static constexpr bool joins_stream = false;
     std::vector<SceneInstance> inst;
     std::vector<InstanceRec> h_inst;
     DevBuf d_inst;
@@ -444,7 +481,7 @@ struct rt_scene {
         s.top_n = 0;
         return s;
     }
-    ~rt_scene();                 // (rt_scene.hip) selects the device, lets go of the models it retains; then the buffers
+    ~rt_scene();                 // (rt_scene.hip) lets go of the models and skeletons it retains; then the buffers
 };
 
 // ---- internal entry points shared between translation units ---------------------
@@ -453,15 +490,11 @@ struct rt_scene {
 int rt_build_blas(rt_context *ctx, rt_model *m);
 
 // rt_scene.hip
-void rt_scene_retain(rt_scene *s);
 // new vertices of one of the scene's models have been queued (rt_model.hip): a fresh scene is stale until its update or build applies them
 void rt_scene_model_changed(rt_scene *s);
 // RT_OK for a built scene.  Otherwise RT_ERR_STATE and its message: what is pending -- transforms, instance masks, models' vertices -- or, if
 // nothing is, `not_built`, a format that may name `who` once
 int rt_scene_require_built(const rt_scene *s, const char *who, const char *not_built);
-
-// rt_skeleton.hip
-void rt_skeleton_retain(rt_skeleton *sk);
 
 // rt_bvh_ploc.hip
 // n_leaves / leaf_box6 / leaf_prim: the leaves to cluster in Morton order -- nullptr: the canonical leaves (one per triangle); else the
@@ -552,10 +585,6 @@ size_t rt_ploc_temp_bytes(uint32_t n);
 
 // rt_pipeline.hip: renders the frames every deferred pipeline of the context still holds (rt_pipeline_set_deferred)
 int rt_context_flush_deferred(rt_context *ctx);
-
-// rt_api.hip
-void rt_context_retain(rt_context *ctx);
-void rt_context_release(rt_context *ctx);
 
 // rt_obj.cpp, rt_fbx.cpp
 int rt_obj_parse(const char *path, std::vector<rt_vertex> &verts, std::vector<uint32_t> &idx);

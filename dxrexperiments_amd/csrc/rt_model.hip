@@ -141,25 +141,18 @@ __global__ void __launch_bounds__(256) k_morph_vertices(rt_vertex *__restrict__ 
     dst[v] = o;
 }
 
-int model_finish(rt_context *ctx, rt_model *m, rt_model **out)
+int model_finish(rt_made<rt_model> &m, rt_model **out)
 {
-    m->ctx = ctx;
-    rt_context_retain(ctx);
+    rt_context *ctx = m->ctx;
     m->n_verts = (uint32_t)m->h_verts.size();
     m->n_tris = (uint32_t)(m->h_idx.size() / 3);
-    int rc = RT_OK;
     for (uint32_t i : m->h_idx)
-        if (i >= m->n_verts) { rt_set_error("index %u out of range (%u vertices)", i, m->n_verts); rc = RT_ERR_INVALID_ARG; break; }
-    if (rc == RT_OK) rc = rt_use_device(ctx);
-    if (rc == RT_OK) rc = rt_upload(ctx, m->d_verts, m->h_verts.data(), sizeof(rt_vertex) * m->h_verts.size());
-    if (rc == RT_OK) rc = rt_upload(ctx, m->d_idx, m->h_idx.data(), sizeof(uint32_t) * m->h_idx.size());
-    if (rc == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { rt_set_error("geometry upload failed"); rc = RT_ERR_HIP; }
-    if (rc != RT_OK) {
-        delete m;
-        rt_context_release(ctx);
-        return rc;
-    }
-    *out = m;
+        if (i >= m->n_verts) { rt_set_error("index %u out of range (%u vertices)", i, m->n_verts); return RT_ERR_INVALID_ARG; }
+    RT_TRY(rt_use_device(ctx));
+    RT_TRY(rt_upload(ctx, m->d_verts, m->h_verts.data(), sizeof(rt_vertex) * m->h_verts.size()));
+    RT_TRY(rt_upload(ctx, m->d_idx, m->h_idx.data(), sizeof(uint32_t) * m->h_idx.size()));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rt_set_error("geometry upload failed"); return RT_ERR_HIP; }
+    *out = m.release();
     return RT_OK;
 }
 
@@ -251,11 +244,6 @@ int model_detach(rt_model *m, A &attachment)
 
 }  // namespace
 
-rt_model::~rt_model()
-{
-    if (ctx) (void)hipSetDevice(ctx->device);
-}
-
 extern "C" {
 
 int rt_model_create_from_arrays(rt_context *ctx, const rt_vertex *verts, uint32_t n_verts, const uint32_t *indices,
@@ -263,21 +251,20 @@ int rt_model_create_from_arrays(rt_context *ctx, const rt_vertex *verts, uint32_
 {
     RT_REQUIRE(ctx && verts && indices && out, "null argument");
     RT_REQUIRE(n_verts > 0 && n_tris > 0, "a model needs at least one triangle");
-    rt_model *m = new (std::nothrow) rt_model();
-    if (!m) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
+    rt_made<rt_model> m;
+    RT_TRY(rt_make(ctx, m));
     m->h_verts.assign(verts, verts + n_verts);
     m->h_idx.assign(indices, indices + 3 * (size_t)n_tris);
-    return model_finish(ctx, m, out);
+    return model_finish(m, out);
 }
 
 int rt_model_create_from_obj(rt_context *ctx, const char *path, rt_model **out)
 {
     RT_REQUIRE(ctx && path && out, "null argument");
-    rt_model *m = new (std::nothrow) rt_model();
-    if (!m) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    int rc = rt_obj_parse(path, m->h_verts, m->h_idx);
-    if (rc != RT_OK) { delete m; return rc; }
-    return model_finish(ctx, m, out);
+    rt_made<rt_model> m;
+    RT_TRY(rt_make(ctx, m));
+    RT_TRY(rt_obj_parse(path, m->h_verts, m->h_idx));
+    return model_finish(m, out);
 }
 
 int rt_model_create_from_file(rt_context *ctx, const char *path, rt_model **out)
@@ -286,11 +273,10 @@ int rt_model_create_from_file(rt_context *ctx, const char *path, rt_model **out)
     const size_t n = strlen(path);
     const bool fbx = n >= 4 && path[n - 4] == '.' && (path[n - 3] | 0x20) == 'f' && (path[n - 2] | 0x20) == 'b' && (path[n - 1] | 0x20) == 'x';
     if (!fbx) return rt_model_create_from_obj(ctx, path, out);
-    rt_model *m = new (std::nothrow) rt_model();
-    if (!m) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    int rc = rt_fbx_parse(path, m->h_verts, m->h_idx);
-    if (rc != RT_OK) { delete m; return rc; }
-    return model_finish(ctx, m, out);
+    rt_made<rt_model> m;
+    RT_TRY(rt_make(ctx, m));
+    RT_TRY(rt_fbx_parse(path, m->h_verts, m->h_idx));
+    return model_finish(m, out);
 }
 
 int rt_model_get_counts(const rt_model *m, uint32_t *n_verts, uint32_t *n_tris)
@@ -492,19 +478,11 @@ int rt_model_read_geometry(const rt_model *m, rt_vertex *verts, uint32_t *indice
 int rt_model_retain(rt_model *m)
 {
     RT_REQUIRE(m, "null model");
-    m->refs++;
+    rt_retain(m);
     return RT_OK;
 }
 
-int rt_model_destroy(rt_model *m)
-{
-    if (!m) return RT_OK;
-    if (--m->refs > 0) return RT_OK;
-    rt_context *ctx = m->ctx;
-    delete m;
-    rt_context_release(ctx);
-    return RT_OK;
-}
+int rt_model_destroy(rt_model *m) { return rt_release(m); }
 
 }  // extern "C"
 

@@ -173,8 +173,9 @@ using namespace rtp;
 
 // ---- host object ------------------------------------------------------------------------
 
-struct rt_pipeline {
-    rt_context *ctx = nullptr;
+struct rt_pipeline : rt_handle {
+    using rt_handle::rt_handle;
+    static constexpr bool joins_stream = true;
     uint32_t kind = RT_PIPELINE_PROGRESSIVE;
     DevBuf aov_own;                    // realtime: second output (indirect specular); the first lives in accum_own
     rt_scene *scene = nullptr;
@@ -268,7 +269,7 @@ struct rt_pipeline {
     uint32_t last_pixels = 0;
     bool rendered = false;
     uint32_t last_scene_gen = 0;       // generation of the scene last_pd was filled from
-    ~rt_pipeline();                    // (rt_pipeline_host.hip) selects the device and joins the stream; the ring's events, the scene it retains; then the members
+    ~rt_pipeline();                    // (rt_pipeline_host.hip) the ring's events, the scene it retains; then the members
 };
 
 // renders the frames a deferred pipeline holds (rt_pipeline.hip); every entry point that reads or changes what they see calls it first

@@ -33,21 +33,19 @@ int rt_pipeline_create(rt_context *ctx, uint32_t kind, rt_pipeline **out)
 {
     RT_REQUIRE(ctx && out, "null argument");
     RT_REQUIRE(kind == RT_PIPELINE_PROGRESSIVE || kind == RT_PIPELINE_REALTIME, "unknown pipeline kind");
-    rt_pipeline *p = new (std::nothrow) rt_pipeline();
-    if (!p) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    p->ctx = ctx;
+    rt_made<rt_pipeline> p;
+    RT_TRY(rt_make(ctx, p));
     p->kind = kind;
-    rt_context_retain(ctx);
     memset(&p->pfc, 0, sizeof p->pfc);
     memset(&p->stats, 0, sizeof p->stats);
-    *out = p;
+    *out = p.release();
     return RT_OK;
 }
 
 int rt_pipeline_destroy(rt_pipeline *p)
 {
     if (!p) return RT_OK;
-    (void)hipSetDevice(p->ctx->device);
+    (void)rt_use_device(p->ctx);
     {   // Frames accepted and not rendered yet: an output in caller memory (rt_pipeline_bind_output) outlives the pipeline, so
         // they are rendered into it first; with an output of its own nothing could read them any more and they die here.
         if (!p->pending.empty() && p->accum && p->accum != p->accum_own.as<float4>()) (void)rt_pipeline_flush_pending(p);
@@ -55,18 +53,13 @@ int rt_pipeline_destroy(rt_pipeline *p)
         for (size_t k = 0; k < reg.size(); k++) if (reg[k] == p) { reg.erase(reg.begin() + (long)k); break; }
         p->pending.clear();
     }
-    rt_context *ctx = p->ctx;
-    delete p;
-    rt_context_release(ctx);
-    return RT_OK;
+    return rt_release(p);
 }
 
 }  // extern "C"
 
 rt_pipeline::~rt_pipeline()
 {
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
     for (hipEvent_t e : ring) if (e) (void)hipEventDestroy(e);
     if (scene) rt_scene_destroy(scene);
 }
@@ -84,7 +77,7 @@ int rt_pipeline_set_scene(rt_pipeline *p, rt_scene *s)
     RT_REQUIRE(p && s, "null argument");
     RT_REQUIRE(s->ctx == p->ctx, "scene belongs to a different context");
     RT_TRY(rt_pipeline_flush_pending(p));
-    rt_scene_retain(s);
+    rt_retain(s);
     if (p->scene) rt_scene_destroy(p->scene);
     p->scene = s;
     p->rendered = false;        // last_pd holds device pointers of the previous scene
@@ -122,7 +115,7 @@ int rt_pipeline_set_environment_cube(rt_pipeline *p, const float *faces, uint32_
 {
     RT_REQUIRE(p && faces && size > 0, "bad argument");
     RT_TRY(rt_pipeline_flush_pending(p));
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     const size_t bytes = (size_t)6 * size * size * 16;
     RT_TRY(p->d_env.reserve(bytes));
     HIP_TRY(hipMemcpyAsync(p->d_env.p, faces, bytes, hipMemcpyHostToDevice, p->ctx->stream));
@@ -164,7 +157,7 @@ int rt_pipeline_create_output(rt_pipeline *p, uint32_t format, uint32_t width, u
     RT_REQUIRE(width > 0 && height > 0, "empty output");
     RT_REQUIRE(format == RT_FORMAT_R32G32B32A32_FLOAT || format == RT_FORMAT_R16G16B16A16_FLOAT, "unsupported output format");
     RT_TRY(rt_pipeline_flush_pending(p));
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     RT_TRY(p->accum_own.reserve((size_t)width * height * 16));
     if (p->kind == RT_PIPELINE_REALTIME) RT_TRY(p->aov_own.reserve((size_t)width * height * 16));     // kNumOutputResources = 2
     p->accum = p->accum_own.as<float4>();
@@ -256,7 +249,7 @@ int rt_pipeline_clear_output(rt_pipeline *p)
     RT_REQUIRE(p, "null pipeline");
     RT_TRY(rt_pipeline_flush_pending(p));
     if (!p->accum) { rt_set_error("no output resource"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipMemsetAsync(p->accum, 0, (size_t)p->width * p->height * 16, p->ctx->stream));
     if (p->aov_own.p) HIP_TRY(hipMemsetAsync(p->aov_own.p, 0, (size_t)p->width * p->height * 16, p->ctx->stream));
     return RT_OK;
@@ -293,7 +286,7 @@ int rt_pipeline_read_output_n(rt_pipeline *p, uint32_t id, void *host, size_t by
     RT_TRY(rt_pipeline_flush_pending(p));
     const float4 *src = id == 0 ? p->accum : p->aov_own.as<float4>();
     if (!src) { rt_set_error("no output resource"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     const size_t npix = (size_t)p->width * p->height;
     hipStream_t st = p->ctx->stream;
     if (p->format == RT_FORMAT_R16G16B16A16_FLOAT) {
@@ -317,7 +310,7 @@ int rt_pipeline_write_output(rt_pipeline *p, const void *host_rgba32f, size_t by
     RT_TRY(rt_pipeline_flush_pending(p));
     if (!p->accum) { rt_set_error("no output resource"); return RT_ERR_STATE; }
     RT_REQUIRE(bytes == (size_t)p->width * p->height * 16, "host buffer must be width*height*16 bytes (RGBA32F)");
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipMemcpyAsync(p->accum, host_rgba32f, bytes, hipMemcpyHostToDevice, p->ctx->stream));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     return RT_OK;
@@ -332,7 +325,7 @@ int rt_pipeline_save_checkpoint(rt_pipeline *p, const rt_progressive_host *h, co
     RT_TRY(rt_pipeline_flush_pending(p));
     if (!p->accum) { rt_set_error("no output resource"); return RT_ERR_STATE; }
     RT_REQUIRE(p->kind == RT_PIPELINE_PROGRESSIVE, "checkpoint: only the progressive pipeline accumulates");
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     const size_t bytes = (size_t)p->width * p->height * 16;
     std::vector<char> img(bytes), state;
     HIP_TRY(hipMemcpyAsync(img.data(), p->accum, bytes, hipMemcpyDeviceToHost, p->ctx->stream));
@@ -392,7 +385,7 @@ int rt_pipeline_enable_timing(rt_pipeline *p, int frames)
     RT_REQUIRE(p, "null pipeline");
     RT_REQUIRE(frames >= 0 && frames <= 4096, "timing ring holds 0..4096 frames");
     RT_TRY(rt_pipeline_flush_pending(p));
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     for (hipEvent_t e : p->ring) if (e) (void)hipEventDestroy(e);
     p->ring.assign((size_t)frames * EV_COUNT, nullptr);
@@ -438,7 +431,7 @@ int rt_pipeline_get_stats(rt_pipeline *p, rt_stats *out)
 {
     RT_REQUIRE(p && out, "null argument");
     RT_TRY(rt_pipeline_flush_pending(p));
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     memset(out, 0, sizeof *out);
     if (!p->rendered) return RT_OK;
@@ -465,7 +458,7 @@ int rt_pipeline_get_totals(rt_pipeline *p, rt_stats *out)
 {
     RT_REQUIRE(p && out, "null argument");
     RT_TRY(rt_pipeline_flush_pending(p));
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     memset(out, 0, sizeof *out);
     if (!p->totals.p) return RT_OK;
@@ -492,7 +485,7 @@ int rt_pipeline_reset_totals(rt_pipeline *p)
 {
     RT_REQUIRE(p, "null pipeline");
     RT_TRY(rt_pipeline_flush_pending(p));
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     if (p->totals.p) HIP_TRY(hipMemsetAsync(p->totals.p, 0, 8 * sizeof(unsigned long long), p->ctx->stream));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->ring_pos = 0;

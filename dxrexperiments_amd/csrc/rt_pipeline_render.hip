@@ -328,7 +328,7 @@ int render_region(rt_pipeline *p, uint32_t width, uint32_t height, Region r, con
     if (r.x1 > width) r.x1 = width;
     if (!r.band_rows && r.y1 > height) r.y1 = height;      // (band mode: y counts the rank's packed rows, checked per pixel)
     RT_REQUIRE(r.x0 < r.x1 && r.y0 < r.y1, "empty tile");
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     p->rendered = false;
     // RayGen early-out (ProgressiveRaytracing.hlsl:14-16): nothing is traced or written (batches: the caller has dropped such frames)
     if (p->kind == RT_PIPELINE_PROGRESSIVE && frames[0].cameraParams.accumCount >= frames[0].options.maxIterations) {
@@ -417,7 +417,7 @@ int count_replay(rt_pipeline *p, const char *who, int (*launch)(rt_pipeline *, u
     const char *nothing = "%s: nothing rendered since the last change of scene, materials or output";
     if (p->rendered) RT_TRY(rt_scene_require_built(p->scene, who, nothing));       // (transforms, masks or vertices pending: the message names them)
     if (!p->rendered || p->scene->generation != p->last_scene_gen) { rt_set_error(nothing, who); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     hipStream_t st = p->ctx->stream;
     RT_TRY(p->work.reserve(RT_STAGE_COUNT * RT_WALK_WORDS * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(p->work.p, 0, words * sizeof(unsigned long long), st));
@@ -582,7 +582,7 @@ int rt_pipeline_get_queue_memory(rt_pipeline *p, size_t *bytes_reserved, uint32_
 int rt_pipeline_reserve_batch(rt_pipeline *p, uint32_t width, uint32_t height, uint32_t frames)
 {
     RT_REQUIRE(p && width > 0 && height > 0 && frames >= 1 && frames <= RT_MAX_BATCH, "reserve_batch: bad argument");
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     // (a set whose worst case is over the budget sizes its levels by count as it goes: only the pixel slots are known now)
     SetPlan plan;
     RT_TRY(plan_set(p, width, height, frames, p->have_pfc && p->pfc.options.showAmbientOcclusionOnly != 0, __func__, &plan));
@@ -607,7 +607,7 @@ int rt_pipeline_get_free_sphere(rt_pipeline *p, float *radius)
     *radius = 0.0f;
     rt_pipeline::FreeSphere &f = p->free_sphere;
     if (!p->scene || !p->have_pfc || !f.back.block) return RT_OK;
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     free_sphere_poll(f);
     const float *lp = &p->pfc.pointLight.worldPos.x;
     if (f.known_gen == p->scene->generation && memcmp(f.known_lp, lp, sizeof f.known_lp) == 0) *radius = f.known_radius;
@@ -645,7 +645,7 @@ int rt_debug_read_secondary_ray(rt_pipeline *p, uint32_t index, float origin_tmi
     RT_REQUIRE(p && origin_tmin && dir_tmax, "null argument");
     RT_TRY(rt_pipeline_flush_pending(p));
     if (!p->rendered) { rt_set_error("nothing rendered yet"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     uint32_t n = 0;
     HIP_TRY(hipMemcpy(&n, p->last_pd.counters + C_NHIT, 4, hipMemcpyDeviceToHost));
@@ -666,7 +666,7 @@ int rt_debug_read_primary_entries(rt_pipeline *p, uint32_t first_tile, uint32_t 
     if (cut) *cut = p->primary_entries.on ? p->primary_entries.cut : 0u;
     if (!entries || count == 0) return RT_OK;
     RT_REQUIRE(first_tile < tiles && count <= tiles - first_tile, "tile out of range");
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     HIP_TRY(hipMemcpy(entries, p->primary_entries.lists.as<uint2>() + (size_t)first_tile * RT_ENTRY_STRIDE, (size_t)count * RT_ENTRY_STRIDE * sizeof(uint2), hipMemcpyDeviceToHost));
     return RT_OK;
@@ -677,7 +677,7 @@ int rt_pipeline_read_primary_hits(rt_pipeline *p, float *t, uint32_t *prim, uint
     RT_REQUIRE(p, "null pipeline");
     RT_TRY(rt_pipeline_flush_pending(p));
     if (!p->rendered) { rt_set_error("nothing rendered yet"); return RT_ERR_STATE; }
-    HIP_TRY(hipSetDevice(p->ctx->device));
+    RT_TRY(rt_use_device(p->ctx));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     const PipeDev &pd = p->last_pd;
     const size_t cap = pd.cap;
@@ -702,7 +702,7 @@ int rt_debug_sample_cube(rt_context *ctx, const float *faces, uint32_t size, uin
     RT_REQUIRE(ctx && faces && dirs && out && size > 0, "bad argument");
     RT_REQUIRE(filter == RT_CUBE_SEAMLESS || filter == RT_CUBE_FACE_CLAMP, "unknown cube-map filter");
     if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
+    RT_TRY(rt_use_device(ctx));
     DevBuf *sb = ctx->scratch;
     const size_t fb = (size_t)6 * size * size * 16;
     RT_TRY(sb[0].reserve(fb)); RT_TRY(sb[1].reserve(n * 12)); RT_TRY(sb[2].reserve(n * 12));

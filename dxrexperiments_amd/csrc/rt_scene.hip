@@ -664,11 +664,8 @@ int rt_build_tlas(rt_context *ctx, rt_scene *s)
 
 // ---- what the rest of the library asks of a scene (rt_internal.h) ----
 
-void rt_scene_retain(rt_scene *s) { if (s) s->refs++; }
-
 rt_scene::~rt_scene()
 {
-    (void)hipSetDevice(ctx->device);
     for (SceneInstance &in : inst) {
         std::vector<rt_scene *> &held = in.model->scenes;      // (the model outlives this: the scene retains it)
         for (size_t k = 0; k < held.size(); k++)
@@ -692,11 +689,9 @@ extern "C" {
 int rt_scene_create(rt_context *ctx, rt_scene **out)
 {
     RT_REQUIRE(ctx && out, "null argument");
-    rt_scene *s = new (std::nothrow) rt_scene();
-    if (!s) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    s->ctx = ctx;
-    rt_context_retain(ctx);
-    *out = s;
+    rt_made<rt_scene> s;
+    RT_TRY(rt_make(ctx, s));
+    *out = s.release();
     return RT_OK;
 }
 
@@ -705,7 +700,7 @@ int rt_scene_add_model(rt_scene *s, rt_model *m, const float transform3x4[12])
     RT_REQUIRE(s && m && transform3x4, "null argument");
     RT_REQUIRE(m->ctx == s->ctx, "model and scene belong to different contexts");
     RT_TRY(rt_context_flush_deferred(s->ctx));       // frames accepted before this change see the scene as it was
-    m->refs++;
+    rt_retain(m);
     scene_add_instance(s, m, transform3x4);
     bool held = false;
     for (rt_scene *o : m->scenes) held = held || o == s;
@@ -812,7 +807,7 @@ int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_sk
     HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope, the caller's arrays are its own again)
     held = false;
     for (rt_skeleton *o : s->skeletons) held = held || o == sk;
-    if (!held) { s->skeletons.push_back(sk); rt_skeleton_retain(sk); }      // (as the scene retains its models; let go of when the scene goes)
+    if (!held) { s->skeletons.push_back(sk); rt_retain(sk); }      // (as the scene retains its models; let go of when the scene goes)
     if (local3x4) memcpy(&s->att_local[12 * (size_t)first], local3x4, 48 * (size_t)count);
     for (uint32_t k = 0; k < count; k++) scene_bind(s, first + k, sk, words[k]);
     if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the binding)
@@ -955,15 +950,7 @@ int rt_scene_build(rt_scene *s, uint32_t hit_group_count)
     return RT_OK;
 }
 
-int rt_scene_destroy(rt_scene *s)
-{
-    if (!s) return RT_OK;
-    if (--s->refs > 0) return RT_OK;
-    rt_context *ctx = s->ctx;
-    delete s;
-    rt_context_release(ctx);
-    return RT_OK;
-}
+int rt_scene_destroy(rt_scene *s) { return rt_release(s); }
 
 int rt_scene_bvh_info(const rt_scene *s, int which, uint32_t *n_prims, uint32_t *n_nodes, uint32_t *max_depth)
 {

@@ -309,15 +309,6 @@ int read_back(rt_skeleton *sk, const char *who, const DevBuf &from, float *to, s
 
 }  // namespace
 
-void rt_skeleton_retain(rt_skeleton *sk) { if (sk) sk->refs++; }
-
-rt_skeleton::~rt_skeleton()
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);            // (a skin kernel that reads the palette, or a pose kernel, may still be queued)
-}
-
 extern "C" {
 
 int rt_skeleton_create(rt_context *ctx, uint32_t n_joints, const int32_t *parents, const float *inverse_bind, rt_skeleton **out)
@@ -332,45 +323,27 @@ int rt_skeleton_create(rt_context *ctx, uint32_t n_joints, const int32_t *parent
         rt_set_error("rt_skeleton_create: joint %u names parent %d: a parent is -1 (a root) or a joint before its child", bad, parents[bad]);
         return RT_ERR_INVALID_ARG;
     }
-    rt_skeleton *sk = new (std::nothrow) rt_skeleton();
-    if (!sk) { rt_set_error("out of host memory"); return RT_ERR_OOM; }
-    sk->ctx = ctx;
-    rt_context_retain(ctx);
+    std::vector<uint32_t> order, table;                 // (before sk: a failed creation joins the stream while what it was uploading is still there)
+    rt_made<rt_skeleton> sk;
+    RT_TRY(rt_make(ctx, sk));
     sk->n_joints = n_joints;
     sk->parents.assign(parents, parents + n_joints);
-    std::vector<uint32_t> order, table;
     sk->n_levels = rt_skeleton_levels(n_joints, parents, order, sk->level_offsets);
     rt_skeleton_pack_table(parents, order, table);
-    auto fill = [&]() -> int {
-        RT_TRY(rt_use_device(ctx));
-        RT_TRY(rt_upload(ctx, sk->table, table.data(), sizeof(uint32_t) * table.size()));
-        RT_TRY(rt_upload(ctx, sk->d_level_offsets, sk->level_offsets.data(), sizeof(uint32_t) * sk->level_offsets.size()));
-        RT_TRY(rt_upload(ctx, sk->inverse_bind, inverse_bind, 48 * (size_t)n_joints));
-        RT_TRY(sk->pose.reserve(sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)n_joints));
-        RT_TRY(sk->joints.reserve(48 * (size_t)n_joints));
-        RT_TRY(sk->palette.reserve(48 * (size_t)n_joints));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (the vectors go out of scope, the caller's array is its own again)
-        return RT_OK;
-    };
-    const int rc = fill();
-    if (rc != RT_OK) {
-        delete sk;
-        rt_context_release(ctx);
-        return rc;
-    }
-    *out = sk;
+    RT_TRY(rt_use_device(ctx));
+    RT_TRY(rt_upload(ctx, sk->table, table.data(), sizeof(uint32_t) * table.size()));
+    RT_TRY(rt_upload(ctx, sk->d_level_offsets, sk->level_offsets.data(), sizeof(uint32_t) * sk->level_offsets.size()));
+    RT_TRY(rt_upload(ctx, sk->inverse_bind, inverse_bind, 48 * (size_t)n_joints));
+    RT_TRY(sk->pose.reserve(sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)n_joints));
+    RT_TRY(sk->joints.reserve(48 * (size_t)n_joints));
+    RT_TRY(sk->palette.reserve(48 * (size_t)n_joints));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope, the caller's array is its own again)
+    *out = sk.release();
     return RT_OK;
 }
 
-int rt_skeleton_destroy(rt_skeleton *sk)
-{
-    if (!sk) return RT_OK;
-    if (--sk->refs > 0) return RT_OK;                   // (a scene with instances attached to it holds it: they keep their last transform)
-    rt_context *ctx = sk->ctx;
-    delete sk;                // (joins the stream first: a skin kernel queued by rt_model_set_bones_from_skeleton reads a live palette)
-    rt_context_release(ctx);
-    return RT_OK;
-}
+// (a scene with instances attached to it holds it: they keep their last transform)
+int rt_skeleton_destroy(rt_skeleton *sk) { return rt_release(sk); }
 
 int rt_skeleton_get_info(const rt_skeleton *sk, uint32_t *n_joints, uint32_t *n_levels, uint32_t *n_clips)
 {

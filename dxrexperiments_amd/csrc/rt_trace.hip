@@ -113,7 +113,7 @@ extern "C" int rt_debug_wide_step(rt_context *ctx, const void *nodes, uint32_t n
     if (lds_top) RT_REQUIRE(n_nodes <= RT_TOP_NODES, "the LDS-resident top holds RT_TOP_NODES nodes at most");
     for (size_t i = 0; i < n; i++) RT_REQUIRE(node_index[i] >= 0 && (uint32_t)node_index[i] < n_nodes, "node index out of range");
     if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
+    RT_TRY(rt_use_device(ctx));
     hipStream_t st = ctx->stream;
     DevBuf *sb = ctx->scratch;
     const unsigned grid = (unsigned)((n + TRACE_BLOCK - 1) / TRACE_BLOCK);

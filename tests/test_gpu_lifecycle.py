@@ -25,6 +25,12 @@ def cycle(capi, gpu, order):
     sc = capi.Scene(gpu)
     sc.add_model(model)
     sc.add_model(model, scenes.instance_grid(2)[1])
+    # a chain of four joints, each half a unit above its parent; the second instance follows the third joint
+    sk = capi.Skeleton(gpu, np.array([-1, 0, 1, 2], np.int32), np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (4, 1)))
+    sk.set_pose(np.tile(np.array([0, 0.5, 0, 0, 0, 0, 1, 1, 1, 1], np.float32), (4, 1)))
+    sc.attach(1, sk, [2], scenes.instance_grid(2)[1:2])
+    skinned = capi.Model(gpu, v, t)
+    skinned.set_skin(np.arange(v.shape[0], dtype=np.uint32).reshape(-1, 1) % 4, np.ones((v.shape[0], 1), np.float32), 4)
     p = capi.Pipeline(gpu)
     p.set_scene(sc)
     p.add_material(T.default_material())
@@ -42,15 +48,17 @@ def cycle(capi, gpu, order):
     assert np.isfinite(img).all()
     dn = capi.Denoiser(gpu)
     dn.create_output(160, 96)
-    objs = {"pipeline": p, "scene": sc, "model": model, "denoiser": dn, "host": host}
+    skinned.set_bones_from(sk)          # queued, not waited for: the skeleton's holders are this kernel and the scene when the handles go
+    objs = {"pipeline": p, "scene": sc, "model": model, "denoiser": dn, "host": host, "skeleton": sk}
     for name in order:
         objs.pop(name).close()
+    skinned.close()
     return img
 
 
 def test_no_device_memory_leak_and_any_destroy_order(gpu, capi):
-    orders = [("pipeline", "scene", "model", "denoiser", "host"), ("model", "scene", "pipeline", "host", "denoiser"),
-              ("scene", "denoiser", "model", "host", "pipeline")]
+    orders = [("skeleton", "pipeline", "scene", "model", "denoiser", "host"), ("model", "scene", "pipeline", "host", "denoiser", "skeleton"),
+              ("scene", "denoiser", "model", "skeleton", "host", "pipeline")]
     first = cycle(capi, gpu, orders[0])
     gc.collect()
     gpu.synchronize()
@@ -62,6 +70,46 @@ def test_no_device_memory_leak_and_any_destroy_order(gpu, capi):
     gpu.synchronize()
     leaked = base - free_bytes()
     assert leaked < (8 << 20), "device memory shrank by %d bytes over 30 create/destroy cycles" % leaked
+
+
+def context_first_cycle(capi, order):
+    """a context whose own handle goes first: the objects made on it keep it alive, still render, and the last of them takes it along"""
+    v, t = scenes.blob_mesh(level=2)
+    ctx = capi.Context(0)
+    model = capi.Model(ctx, v, t)
+    sc = capi.Scene(ctx)
+    sc.add_model(model)
+    p = capi.Pipeline(ctx)
+    p.set_scene(sc)
+    p.add_material(T.default_material())
+    p.set_environment_cube(scenes.sky_cubemap(8))
+    p.create_output(64, 64)
+    p.build_acceleration_structures()
+    host = capi.ProgressiveHost(1)
+    ctx.close()
+    p.update(host.update(cam_array(dict(eye=(0, 1, 6), at=(0, 0, 0), up=(0, 1, 0), fov=0.8), 1.0), 0.0, 1, 64, 64))
+    p.render()
+    img = p.read_output()
+    assert np.isfinite(img).all()
+    objs = {"pipeline": p, "scene": sc, "model": model}
+    for name in order:
+        objs.pop(name).close()
+    host.close()
+    return img
+
+
+def test_context_handle_closed_first_leaks_nothing(gpu, capi):
+    orders = [("pipeline", "scene", "model"), ("model", "scene", "pipeline"), ("scene", "model", "pipeline")]
+    first = context_first_cycle(capi, orders[0])
+    gc.collect()
+    gpu.synchronize()
+    base = free_bytes()
+    for k in range(30):
+        assert np.array_equal(context_first_cycle(capi, orders[k % 3]), first)
+    gc.collect()
+    gpu.synchronize()
+    leaked = base - free_bytes()
+    assert leaked < (8 << 20), "device memory shrank by %d bytes over 30 cycles whose context handle went first" % leaked
 
 
 RT_ERR_OOM = -5                                                  # include/dxr_amd_types.h
