@@ -98,7 +98,7 @@ int rt_device_count(void)
 
 // ---- experiment / test knobs ------------------------------------------------------
 
-// The options of the primary stage's entry lists (rt_pipeline.hip, k_primary_entries).  Their tests are tests/test_gpu_primary_entries.py,
+// The options of the primary stage's entry lists (rt_pipeline_entries.hip: k_primary_entries and its policy).  Their tests are tests/test_gpu_primary_entries.py,
 // which runs every value of each against primary_entries=0 bit for bit.  1: the name is one of them (*rc: the result).
 static bool entry_list_option(rt_context *c, const std::string &name, bool is_int, long iv, int *rc)
 {

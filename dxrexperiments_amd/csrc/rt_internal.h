@@ -583,7 +583,7 @@ static inline uint32_t rt_lds_stack_rows(const rt_context *ctx)
 // rt_bvh_ploc.hip
 size_t rt_ploc_temp_bytes(uint32_t n);
 
-// rt_pipeline.hip: renders the frames every deferred pipeline of the context still holds (rt_pipeline_set_deferred)
+// rt_pipeline_render.hip: renders the frames every deferred pipeline of the context still holds (rt_pipeline_set_deferred)
 int rt_context_flush_deferred(rt_context *ctx);
 
 // rt_obj.cpp, rt_fbx.cpp

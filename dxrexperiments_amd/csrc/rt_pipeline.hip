@@ -24,18 +24,16 @@
 // atomic per 1024-thread block; diffuse and specular secondaries sit in separate
 // batches so waves stay as coherent as the sampling allows.
 //
-// This file: the stage kernels, the launch sequence of a frame (or of a set of frames) and the launches of the counting re-walks.
-// rt_shade.h: the shaders as device functions.  rt_pipeline_dev.h: PipeDev and the host object.  rt_pipeline_queues.h: queue memory.
+// This file: the stage kernels and the launch sequence of a frame (or of a set of frames).
+// rt_pipeline_rays.h: the ray sources and sinks of the stages.  rt_shade.h: the shaders as device functions.
+// rt_pipeline_dev.h: PipeDev and the host object.  rt_pipeline_queues.h: queue memory.
+// rt_pipeline_entries.hip: the primary stage's entry lists (policy, kernel, launch, read-back).
 // rt_pipeline_render.hip: the render calls (regions, sets of frames, deferred mode), the shadow cache's and the free sphere's host side.
+// rt_pipeline_inspect.hip: the calls that replay the last frame's queues (work and walk counting, read-backs).
 // rt_pipeline_host.hip: creation, setters, outputs, checkpoints, timing and statistics.
 #include <hip/hip_fp16.h>
 
-#include <array>
-#include <new>
-#include <utility>
-
-#include "rt_shade.h"
-#include "rt_pipeline_queues.h"
+#include "rt_pipeline_rays.h"
 
 using namespace rtd;
 
@@ -46,96 +44,6 @@ constexpr int CBLOCK = 1024;
 
 // ---- kernels -------------------------------------------------------------------------
 
-// primary stage: raygen is the ray source, the level-0 hit records the sink (indexed by pixel slot)
-// BATCH = false: one frame, the code of round 2; true: the slot's frame picks the camera (also right for one frame)
-// PD: a source built inside a kernel refers to the kernel's own argument; one that IS a kernel argument (k_count_queue) holds the frame by value
-template <bool BATCH, class PD = const PipeDev &>
-struct PrimarySrcT {
-    PD pd;
-    RT_DEV uint32_t count() const { return pd.cap; }
-    RT_DEV uint32_t flags() const { return RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES; }      // ProgressiveRaytracing.hlsl:34
-    RT_DEV bool load(uint32_t q, RayD &r) const
-    {
-        uint32_t px, py;
-        if (BATCH && pd.n_frames > 1u) {         // (a kernel argument: the branch is uniform)
-            // 64 consecutive slots = one tile = one chunk of a wave: the frame is the same for every lane that loads here
-            uint32_t ql;
-            const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot_frame(pd, q, ql));
-            const bool valid = pix_xy(pd, ql, px, py);
-            r = primary_ray(pd, pd.pfcs[f].cameraParams, px, py);
-            return valid;
-        }
-        const bool valid = pix_xy(pd, q, px, py);
-        r = primary_ray(pd, px, py);
-        return valid;
-    }
-    // (NO_DEEP launches, rt_trace_wave.h) the walk of pixel slot q would need a stack row beyond the LDS ones: k_primary_retry takes it from here
-    RT_DEV void overflow(uint32_t q) const
-    {
-        const uint32_t k = atomicAdd(&pd.retry[0], 1u);
-        if (k < pd.retry_cap) pd.retry[2u + k] = q;
-    }
-};
-// ... with the per-tile entry lists k_primary_entries has made for this set (rt_trace_wave.h, src_has_entries): 64 consecutive slots are
-// one tile of one frame, and the frames of a set share the tile's list.  BATCH here says that the launch HAS several frames (pfcs)
-template <bool BATCH>
-struct PrimaryEntrySrcT : PrimarySrcT<BATCH> {
-    const uint2 *__restrict__ entries;
-    // floor(2^32 / n_frames) + 1, floor(2^32 / tiles_x) + 1: chunk / n_frames and tile / tiles_x by one scalar mul_hi each (exact while
-    // chunks * n_frames and tiles * tiles_x stay below 2^32, which the host checks before it turns the lists on); the divisions' own
-    // reciprocals would be three vector registers that live through the whole walk
-    uint32_t frames_magic, tiles_x_magic;
-    static constexpr bool has_entry_lists = true;
-    // chunk c of the slots = tile c / n_frames, frame c mod n_frames (slot_frame); the chunk is the same for the whole wave
-    RT_DEV uint32_t chunk_tile(uint32_t q, uint32_t &f) const
-    {
-        const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(q >> 6));
-        if (!BATCH) { f = 0u; return c; }
-        const uint32_t tile = __umulhi(c, frames_magic);
-        f = c - tile * this->pd.n_frames;
-        return tile;
-    }
-    RT_DEV bool load(uint32_t q, RayD &r) const
-    {
-        uint32_t px, py, f;
-        const uint32_t tile = chunk_tile(q, f);
-        const uint32_t tile_y = this->pd.tiles_x == 1u ? tile : __umulhi(tile, tiles_x_magic);      // (2^32 / 1 + 1 is no 32-bit reciprocal)
-        const bool valid = pix_xy_in_tile(this->pd, tile - tile_y * this->pd.tiles_x, tile_y, q & 63u, px, py);
-        r = BATCH ? primary_ray(this->pd, this->pd.pfcs[f].cameraParams, px, py) : primary_ray(this->pd, px, py);
-        return valid;
-    }
-    RT_DEV uint32_t first_entry(uint32_t q) const { uint32_t f; return chunk_tile(q, f) * RT_ENTRY_STRIDE; }
-    RT_DEV uint2 entry(uint32_t k) const { return entries[k]; }
-};
-typedef PrimarySrcT<true> PrimarySrc;                   // (the walk-counting kernel)
-typedef PrimarySrcT<true, PipeDev> PrimarySrcByValue;   // (the canonical re-trace, rt_frame_count_work)
-// The pixel slots the one-tile-per-wave primary launch gave up (PipeDev::retry), as a ray source for a persistent launch WITH rows beyond
-// LDS; a list that overflowed stands for every slot.  Slots come in any order here: every lane finds its own frame.
-struct PrimaryRetrySrc {
-    const PipeDev &pd;
-    RT_DEV uint32_t count() const { const uint32_t n = pd.retry[0]; return n <= pd.retry_cap ? n : pd.cap; }
-    RT_DEV uint32_t flags() const { return RT_RAY_FLAG_CULL_BACK_FACING_TRIANGLES; }
-    RT_DEV bool load(uint32_t i, RayD &r, uint32_t &ticket) const
-    {
-        const uint32_t q = pd.retry[0] <= pd.retry_cap ? pd.retry[2u + i] : i;
-        ticket = q;
-        uint32_t px, py, ql;
-        const uint32_t f = slot_frame(pd, q, ql);
-        const bool valid = pix_xy(pd, ql, px, py);
-        r = pd.n_frames > 1u ? primary_ray(pd, pd.pfcs[f].cameraParams, px, py) : primary_ray(pd, px, py);
-        return valid;
-    }
-};
-struct PrimarySink {
-    const PipeDev &pd;
-    RT_DEV void store(uint32_t q, const HitD &h, bool) const
-    {
-        const bool hit = h.inst != RT_NO_HIT;
-        pd.lv[0].hit[q] = make_float4(hit ? h.t : HIT_MISS, h.u, h.v, __uint_as_float(h.prim));
-        pd.lv[0].inst[q] = h.inst;
-    }
-};
-
 // (see RT_LDS_STACK_ROWS_SETS: the single-level instantiations with that many stack rows are compiled for seven waves per SIMD,
 // the 18-row ones for the six their LDS allows (the any-hit kernel with the shadow cache would take 81 registers otherwise);
 // the two-level ones for five -- they take 88 - 96 registers by themselves, except the primary stage of a set (99: a fourth wave lost
@@ -143,17 +51,28 @@ struct PrimarySink {
 #ifndef RT_WAVES_PER_EU
 #define RT_WAVES_PER_EU __attribute__((amdgpu_waves_per_eu(TWO_LEVEL ? 5 : RT_ROWS(STACK) == RT_LDS_STACK_ROWS_SETS ? 7 : RT_ROWS(STACK) == RT_LDS_STACK_ROWS ? 6 : 1)))
 #endif
+// the frame's counters and chunk pools start at zero: its first kernel clears them (nothing there uses them, every later
+// kernel of the frame does) instead of a 20-KB fill launch of its own
+RT_DEV void clear_frame_counters(const PipeDev &pd)
+{
+    if (blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < (uint32_t)(POOL_OFFSET_WORDS + POOL_BYTES / 4); i += PBLOCK) pd.counters[i] = 0u;
+}
+// rays a wave of a persistent launch takes from its queue at a time: the long launches of a set of frames (the seven-wave single-level
+// kernels) take more, its any-hit launch more still (RT_POOL_CHUNK*, rt_trace_wave.h)
+constexpr uint32_t pool_chunk(int stack, bool two_level, bool anyhit)
+{
+    return !two_level && RT_ROWS(stack) == RT_LDS_STACK_ROWS_SETS ? (anyhit ? RT_POOL_CHUNK_SETS_ANYHIT : RT_POOL_CHUNK_SETS) : RT_POOL_CHUNK;
+}
+
 // PERSIST = false: one 8x8 tile per wave, dealt by the hardware dispatcher -- one thread per pixel slot, so this launch keeps NO stack rows
 // beyond LDS (NO_DEEP: a ray that would need one goes to PipeDev::retry and k_primary_retry walks it); true: a persistent launch that refills
 // its lanes from a pool of tiles (two-level scenes), with rows by resident thread like the other persistent launches
 template <int STACK, bool TWO_LEVEL, bool BATCH, bool PERSIST>
 __global__ void __launch_bounds__(PBLOCK) RT_WAVES_PER_EU k_primary(PipeDev pd)
 {
-    __shared__ int smem[(RT_ROWS(STACK) + RT_TOP_ROWS(PBLOCK)) * PBLOCK];
-    // the frame's counters and chunk pools start at zero: its first kernel clears them (nothing here uses them, every later
-    // kernel of the frame does) instead of a 20-KB fill launch of its own
-    if (blockIdx.x == 0)
-        for (uint32_t i = threadIdx.x; i < (uint32_t)(POOL_OFFSET_WORDS + POOL_BYTES / 4); i += PBLOCK) pd.counters[i] = 0u;
+    __shared__ int smem[walk_lds_words(RT_ROWS(STACK))];
+    clear_frame_counters(pd);
     PrimarySrcT<BATCH> src = {pd};
     PrimarySink sink = {pd};
     if (PERSIST) trace_wave<RT_ROWS(STACK), PBLOCK, TWO_LEVEL, 64u, false, false, false, RT_REFS(STACK)>(pd.sc, src, sink, pd.pools + POOL_BYTES / 4, smem, nullptr);
@@ -165,7 +84,7 @@ __global__ void __launch_bounds__(PBLOCK) RT_WAVES_PER_EU k_primary(PipeDev pd)
 template <int STACK, bool TWO_LEVEL>
 __global__ void __launch_bounds__(PBLOCK) RT_WAVES_PER_EU k_primary_retry(PipeDev pd)
 {
-    __shared__ int smem[(RT_ROWS(STACK) + RT_TOP_ROWS(PBLOCK)) * PBLOCK];
+    __shared__ int smem[walk_lds_words(RT_ROWS(STACK))];
     if (pd.retry[0] == 0u) return;
     PrimaryRetrySrc src = {pd};
     PrimarySink sink = {pd};
@@ -178,197 +97,11 @@ __global__ void __launch_bounds__(PBLOCK) RT_WAVES_PER_EU k_primary_retry(PipeDe
 template <int STACK, bool BATCH, bool TWO_LEVEL = false>
 __global__ void __launch_bounds__(PBLOCK) RT_WAVES_PER_EU k_primary_from_entries(PipeDev pd, const uint2 *__restrict__ entries, uint32_t frames_magic, uint32_t tiles_x_magic)
 {
-    __shared__ int smem[(RT_ROWS(STACK) + 1) * PBLOCK];
-    if (blockIdx.x == 0)
-        for (uint32_t i = threadIdx.x; i < (uint32_t)(POOL_OFFSET_WORDS + POOL_BYTES / 4); i += PBLOCK) pd.counters[i] = 0u;
+    __shared__ int smem[walk_lds_words(RT_ROWS(STACK), true)];
+    clear_frame_counters(pd);
     PrimaryEntrySrcT<BATCH> src = {{pd}, entries, frames_magic, tiles_x_magic};
     PrimarySink sink = {pd};
     trace_wave<RT_ROWS(STACK), PBLOCK, false, 64u, false, false, true, RT_REFS(STACK)>(pd.sc, src, sink, nullptr, smem, nullptr);
-}
-
-// ---- the entry lists of the primary stage ("entry lists") -------------------------------------------------------
-// Once per set of launches, for every 8x8 tile of the launch's rectangle: which children below a cut through the top of the tree can
-// ANY ray of the tile, in ANY frame of the set, be made to enter by the walk's own culling?  The 64 directions of a tile depend on the
-// pixels alone and are the same in every frame (the host has checked that the frames share U, V, W bit for bit; otherwise the set runs
-// without lists); the eye moves with the frame's jitter.  So the tile is the set of rays {o + t d : o in [olo, ohi], d in [dlo, dhi]}
-// per axis, and a box is tested with an interval form of the slab test:
-//   per axis whose direction interval excludes zero (mirrored so that d > 0: near plane lo, far plane hi),
-//       tn = (lo - ohi) * (lo - ohi >= 0 ? 1 / dhi : 1 / dlo) - M        <= the near distance of every ray of the tile
-//       tf = (hi - olo) * (hi - olo >= 0 ? 1 / dlo : 1 / dhi) + M        >= the far distance of every ray of the tile
-//   LO = max(tn.., tmin = 0), HI = min(tf.., tmax);  the tile may hit the box iff  LO <= HI * RT_SLAB_SLACK.
-// An axis whose interval contains zero, comes closer to it than 1e-12, or is not finite does not cull (tn = -inf, tf = +inf), and a NaN
-// (an axis the builder could not quantise) is ignored by max / min as in wide_step.  Boxes are decoded as wide_step's exact path decodes
-// them, fma(q, scale, origin).
-// The margin.  What has to pass here is every box that wide_step lets some ray of the tile enter.  Its exact path (steep rays) runs the
-// canonical slab test on the decoded box: each plane distance (p - o) * inv has two roundings, <= 2^-23 |t|.  Its quantised-frame path
-// takes t(q) -+ D with |t(q) - canonical| <= D, so its near distance is >= canonical - 2 D and its far distance <= canonical + 2 D, where
-//   D = 2^-20 (|B| + |inv| (|origin| + 255 scale)) + 1e-37,  |B| = |(origin - o) inv|.
-// Over the tile |inv| <= 1 / dlo and |origin - o| <= max(|origin - olo|, |origin - ohi|) =: w, so
-//   Dmax = 2^-20 / dlo * (w + |origin| + 255 scale) + 1e-37  >=  every ray's D,  and  >= 2^-20 |t| for every plane of the node
-// (|p - o| <= w + 255 scale).  The arithmetic here adds four roundings of its own per bound (the difference, the reciprocal, the product,
-// the subtraction of M: <= 2^-22 |t| <= Dmax / 4), and the intervals themselves are widened by 2^-20 of their ends before use, which moves
-// a bound by less than 2^-19 |t| <= 2 Dmax.  M = 6 Dmax covers the sum (2 + 1/4 + 2) with room.  The same LO, being a lower bound of what
-// either path of wide_step computes as the box's entry distance for any ray of the tile (and of the canonical entry distance), is the
-// entry's tnear.
-// The pass: nodes are numbered breadth first, children behind their parents, so one sweep over nodes 0 .. cut - 1 with a flag per node
-// ("some ray of the tile may step on it") finds every child that hangs below the cut -- a node with index >= cut, or a leaf -- under a
-// flagged parent.  Those are the entries; they are sorted by tnear (ties: the smaller HI first) when the sweep is over.  A tile with
-// more than `cap` of them runs the sweep again with a quarter of the cut, in the end with the root alone.
-// Both families of kernels stay live by design: k_primary / k_walk_primary, untouched, walk from the root (sets shorter than four frames by
-// default, sets whose frames differ in U, V, W, two-level scenes, the persistent launch, primary_entries=0), k_primary_from_entries /
-// k_walk_primary_from_entries walk from lists.  A trait inside k_primary would have saved the second template and changed the mangled names
-// and the register allocation of the first; this way the off path is the parent's code, instruction for instruction.
-// The launch: FOUR lanes per tile, one per child slot of the node at hand, 64 tiles (8 x 8 neighbours: what none of a wave's 8 x 2 can
-// reach is skipped by the wave) per block; the nodes above the cut are copied into LDS once per block and read from there by all.  (One
-// lane per tile reading the nodes from global memory, the first form, took 0.3 ms at 1080p -- one memory round trip per node and half
-// the SIMDs empty; profiles/r18/primary_entries.txt.)  The lanes of a tile share its flags, its count and its list; whatever decides
-// the control flow is the same in all four.
-constexpr int EBLOCK = 256, ETILES = EBLOCK / 4;
-__global__ void __launch_bounds__(EBLOCK) k_primary_entries(PipeDev pd, uint2 *__restrict__ entries, uint32_t cut, uint32_t cap)
-{
-    __shared__ float4 top[RT_ENTRY_CUT_MAX * 4u];
-    __shared__ uint32_t flag[(RT_ENTRY_CUT_MAX / 32u) * ETILES];     // [word][tile]
-    __shared__ uint2 list[RT_ENTRY_CAP * ETILES];                    // [entry][tile]: (code, tnear)
-    __shared__ float list_hi[RT_ENTRY_CAP * ETILES];
-    const uint32_t lane = threadIdx.x & 63u, k = threadIdx.x & 3u, tb = threadIdx.x >> 2;
-    const uint32_t tiles_x = pd.tiles_x, tiles_y = (pd.fcap >> 6) / tiles_x;
-    const uint32_t bw = (tiles_x + 7u) / 8u;
-    const uint32_t tx = (blockIdx.x % bw) * 8u + (tb & 7u), ty = (blockIdx.x / bw) * 8u + (tb >> 3);
-    const bool valid = tx < tiles_x && ty < tiles_y;
-    const uint32_t tile = ty * tiles_x + tx;
-    const InstanceRec *in0 = pd.sc.inst;
-    const int root = in0->root_code;
-    const float inf = __uint_as_float(0x7f800000u);
-    const float k20 = 9.5367431640625e-07f;      // 2^-20
-    const bool cuttable = root == 0 && cut != 0u;      // (a structure that is one leaf has no node to cut through)
-    if (cuttable) {
-        const float4 *__restrict__ nodes = (const float4 *)in0->wide;
-        for (uint32_t i = threadIdx.x; i < cut * 4u; i += EBLOCK) top[i] = nodes[i];
-    }
-    __syncthreads();
-
-    // the tile: direction intervals from the 64 slots (whatever pixel a slot of a partial tile names; 16 per lane), eye intervals from
-    // the frames (one per lane of the wave)
-    float dlo[3] = {inf, inf, inf}, dhi[3] = {-inf, -inf, -inf}, olo[3] = {inf, inf, inf}, ohi[3] = {-inf, -inf, -inf};
-    const rt_camera_params &cam0 = pd.n_frames > 1u ? pd.pfcs[0].cameraParams : pd.pfc.cameraParams;
-    int finite = 1;
-    for (uint32_t w = k * 16u; w < k * 16u + 16u; w++) {
-        uint32_t px, py;
-        (void)pix_xy(pd, (valid ? tile : 0u) * 64u + w, px, py);
-        const RayD r = primary_ray(pd, cam0, px, py);
-        const float d[3] = {r.d.x, r.d.y, r.d.z};
-        for (int a = 0; a < 3; a++) {
-            dlo[a] = fmin2(dlo[a], d[a]); dhi[a] = fmax2(dhi[a], d[a]);
-            if (!(__builtin_fabsf(d[a]) <= 3.0e38f)) finite = 0;
-        }
-    }
-    if (lane < pd.n_frames) {
-        const RayD r = primary_ray(pd, pd.n_frames > 1u ? pd.pfcs[lane].cameraParams : pd.pfc.cameraParams, pd.x0, pd.y0);
-        const float o[3] = {r.o.x, r.o.y, r.o.z};
-        for (int a = 0; a < 3; a++) {
-            olo[a] = o[a]; ohi[a] = o[a];
-            if (!(__builtin_fabsf(o[a]) <= 3.0e38f)) finite = 0;
-        }
-    }
-    for (int a = 0; a < 3; a++) {
-        for (int o = 1; o <= 2; o <<= 1) { dlo[a] = fmin2(dlo[a], __shfl_xor(dlo[a], o, 64)); dhi[a] = fmax2(dhi[a], __shfl_xor(dhi[a], o, 64)); }
-        for (int o = 1; o < 64; o <<= 1) { olo[a] = fmin2(olo[a], __shfl_xor(olo[a], o, 64)); ohi[a] = fmax2(ohi[a], __shfl_xor(ohi[a], o, 64)); }
-    }
-    if (__ballot(finite == 0) != 0ull) finite = 0;      // (one bad lane: no axis of any tile of the wave culls)
-    // per axis, mirrored so that the directions are positive: sgn = 0: the axis does not cull
-    float sgn[3], eo_lo[3], eo_hi[3], inv_lo[3], inv_hi[3];
-    for (int a = 0; a < 3; a++) {
-        const float lo_w = olo[a] - (__builtin_fabsf(olo[a]) * k20 + 1.0e-30f), hi_w = ohi[a] + (__builtin_fabsf(ohi[a]) * k20 + 1.0e-30f);
-        sgn[a] = !finite ? 0.0f : dlo[a] > 1.0e-12f ? 1.0f : dhi[a] < -1.0e-12f ? -1.0f : 0.0f;
-        const float m_lo = sgn[a] < 0.0f ? -dhi[a] : dlo[a], m_hi = sgn[a] < 0.0f ? -dlo[a] : dhi[a];      // 0 < m_lo <= m_hi
-        inv_hi[a] = 1.0f / (m_lo - m_lo * k20);
-        inv_lo[a] = 1.0f / (m_hi + m_hi * k20);
-        eo_lo[a] = sgn[a] < 0.0f ? -hi_w : lo_w;
-        eo_hi[a] = sgn[a] < 0.0f ? -lo_w : hi_w;
-    }
-
-    // The four lanes of a tile talk through LDS with no barrier between them.  That relies on two things and on nothing else: a gfx9 wave
-    // runs its lanes in lock-step and its LDS operations complete in program order, so a flag that lane k == 0 initialises (a volatile store)
-    // or that any lane sets (atomicOr) is in LDS before the same wave's next volatile read of it; and a child's index is greater than its
-    // parent's (breadth-first numbering), so the sweep reads a node's flag only after every step that can set it.  The lists are read
-    // behind the block's barrier.  `pending`, `overflow`, `count` and `on` are per-lane copies of PER-TILE values: the four lanes compute each
-    // from the same flags and from the same ballot masked to their own quad, so they agree by construction, and every branch on them is one
-    // the quad takes together.
-    volatile uint32_t *vflag = flag;
-    const unsigned long long quad = 0xFull << (lane & ~3u);
-    bool pending = valid && cuttable;
-    uint32_t count = 0;
-    for (uint32_t c = cut; __ballot(pending) != 0ull && c != 0u; c >>= 2) {
-        bool overflow = false;
-        if (pending) {
-            if (k == 0u) for (uint32_t w = 0; w < (c + 31u) / 32u; w++) vflag[w * ETILES + tb] = w == 0u ? 1u : 0u;
-            count = 0;
-        }
-        for (uint32_t i = 0; i < c; i++) {
-            const bool on = pending && !overflow && ((vflag[(i >> 5) * ETILES + tb] >> (i & 31u)) & 1u) != 0u;
-            if (__ballot(on) == 0ull) continue;
-            const float4 q0 = top[4u * i], q1 = top[4u * i + 1u], q2 = top[4u * i + 2u], q3 = top[4u * i + 3u];
-            const float org[3] = {q0.x, q0.y, q0.z}, scl[3] = {q0.w, q2.z, q2.w};
-            const uint32_t lob[3] = {__float_as_uint(q1.x), __float_as_uint(q1.z), __float_as_uint(q2.x)};
-            const uint32_t hib[3] = {__float_as_uint(q1.y), __float_as_uint(q1.w), __float_as_uint(q2.y)};
-            const int code = k == 0u ? __float_as_int(q3.x) : k == 1u ? __float_as_int(q3.y) : k == 2u ? __float_as_int(q3.z) : __float_as_int(q3.w);
-            float LO = 0.0f, HI = RAY_MAX_T;
-            for (int a = 0; a < 3; a++) {
-                if (sgn[a] == 0.0f) continue;
-                const float w = fmax2(__builtin_fabsf(org[a] - olo[a]), __builtin_fabsf(org[a] - ohi[a]));
-                const float margin = 6.0f * ((w + __builtin_fabsf(org[a]) + 255.0f * scl[a]) * inv_hi[a] * k20 + 1.0e-37f);
-                const float bl = __builtin_fmaf((float)((lob[a] >> (8u * k)) & 0xffu), scl[a], org[a]);
-                const float bh = __builtin_fmaf((float)((hib[a] >> (8u * k)) & 0xffu), scl[a], org[a]);
-                const float pn = sgn[a] < 0.0f ? -bh : bl, pf = sgn[a] < 0.0f ? -bl : bh;
-                const float nn = pn - eo_hi[a], nf = pf - eo_lo[a];
-                const float tn = nn * (nn >= 0.0f ? inv_lo[a] : inv_hi[a]) - margin;
-                const float tf = nf * (nf >= 0.0f ? inv_hi[a] : inv_lo[a]) + margin;
-                LO = fmax2(LO, tn);
-                HI = fmin2(HI, tf);
-            }
-            const bool hit = on && code != RT_NODE_NONE && LO <= HI * RT_SLAB_SLACK;
-            const bool above = hit && code >= 0 && (uint32_t)code < c;
-            if (above) atomicOr(&flag[((uint32_t)code >> 5) * ETILES + tb], 1u << ((uint32_t)code & 31u));
-            const bool entry = hit && !above;
-            const unsigned long long mine = __ballot(entry) & quad;
-            const uint32_t n_new = (uint32_t)__popcll(mine);
-            if (count + n_new > cap) overflow = true;
-            else {
-                if (entry) {
-                    const uint32_t at = count + (uint32_t)__popcll(mine & lanemask_lt());
-                    list[at * ETILES + tb] = make_uint2((uint32_t)code, __float_as_uint(LO));
-                    list_hi[at * ETILES + tb] = HI;
-                }
-                count += n_new;
-            }
-        }
-        pending = pending && overflow;
-    }
-    __syncthreads();
-    if (!valid || k != 0u) return;
-    uint2 *out = entries + (size_t)tile * RT_ENTRY_STRIDE;
-    if (pending || !cuttable) {      // the coarsest list: the root, from the ray's start
-        out[0] = make_uint2((uint32_t)root, 0u);
-        count = 1;
-    } else {
-        for (uint32_t j = 1; j < count; j++) {      // insertion sort by (tnear, HI): a handful of entries per tile
-            const uint2 e = list[j * ETILES + tb];
-            const float eh = list_hi[j * ETILES + tb], et = __uint_as_float(e.y);
-            uint32_t at = j;
-            while (at > 0u) {
-                const uint2 b = list[(at - 1u) * ETILES + tb];
-                const float bh = list_hi[(at - 1u) * ETILES + tb], bt = __uint_as_float(b.y);
-                if (bt < et || (bt == et && bh <= eh)) break;
-                list[at * ETILES + tb] = b;
-                list_hi[at * ETILES + tb] = bh;
-                at--;
-            }
-            list[at * ETILES + tb] = e;
-            list_hi[at * ETILES + tb] = eh;
-        }
-        for (uint32_t j = 0; j < count; j++) out[j] = list[j * ETILES + tb];
-    }
-    out[count] = make_uint2((uint32_t)RT_NODE_EMPTY, 0x7f800000u);
 }
 
 // Compaction of the hits of level L (they get shaded).  Level 0 runs over the pixel slots, level 1 over its two batches,
@@ -488,266 +221,22 @@ __global__ void __launch_bounds__(PBLOCK) k_shade_emit(PipeDev pd, int level, ui
     else shade_emit_body<PRIMARY, BATCH, MAXD>(pd, level, shadow_slots, emit_next);
 }
 
-// a ray queue of `batches` batches of *count rays; batch b lives at [b*stride, b*stride + *count): the radiance rays of a level
-// (level 1: the diffuse and the specular batch of the primary hits)
-struct QueueSrc {
-    const float4 *O, *D;
-    const uint32_t *count_ptr;
-    uint32_t stride, batches, fl;
-    RT_DEV uint32_t n() const { return *count_ptr; }
-    RT_DEV uint32_t count() const { return n() * batches; }
-    RT_DEV uint32_t flags() const { return fl; }
-    // ray i of the queue = ray k of batch b.  At most two batches: a compare against the (wave-uniform) count instead of a
-    // division and a remainder -- ~50 vector instructions per ray loaded and per result stored, in the part of the persistent
-    // kernels that runs with the fewest lanes (round 4)
-    RT_DEV size_t slot(uint32_t i) const
-    {
-        const uint32_t c = n(), b = i >= c ? 1u : 0u;
-        return (size_t)b * stride + (i - b * c);
-    }
-    RT_DEV bool load(uint32_t i, RayD &r) const
-    {
-        const size_t sl = slot(i);
-        const v4f a = ldg16(O, sl * 16), b = ldg16(D, sl * 16);
-        r.o = mk3(a.x, a.y, a.z); r.tmin = a.w;
-        r.d = mk3(b.x, b.y, b.z); r.tmax = b.w;
-        return r.tmax > r.tmin;
-    }
-};
-struct SecondarySink {
-    QueueSrc q;
-    float4 *hit1;
-    uint32_t *inst1;
-    RT_DEV void store(uint32_t i, const HitD &h, bool traced) const
-    {
-        const size_t sl = q.slot(i);
-        const bool hit = h.inst != RT_NO_HIT;
-        hit1[sl] = make_float4(hit ? h.t : (traced ? HIT_MISS : HIT_UNTRACED), h.u, h.v, __uint_as_float(h.prim));
-        inst1[sl] = h.inst;
-    }
-};
-
-// The shadow rays of the frame: ONE queue for the hits of every level (PipeDev::sh_*), ONE persistent any-hit launch.  Ray number i
-// -> chunk i >> 6 -> the chunk's hits ((chunk >> log2) << 6 ...) and which of a hit's rays the chunk holds (chunk & (rays per
-// hit - 1)): shifts and masks.  Normally the queue is COMPACT ("light rays"): both shadow rays of a shaded hit start at the hit
-// point and go to the frame's two lights, so the emit pass stores one float4 per hit -- the point and, in the bits of w, which of
-// the two rays exist (bits 0-1), which need not be traversed (bits 2-3) and the hit's frame of the set (bits 8..) -- and the loader
-// rebuilds ray b of hit H with the very expressions of evaluateDirectionalLight / evaluatePointLight
-// (RaytracingCommon.hlsli:126-147; directional_light / point_light in rt_shade.h): 16 B written and read per hit instead of
-// 128 B.  The four rays of the ambient-occlusion view have random directions and keep the explicit origin / direction form.
-struct ShadowQueue {
-    const float4 *hits, *O, *D;
-    uint32_t *vis;
-    const uint32_t *nhit;               // counters + C_NHIT: the hits of every level
-    uint32_t log2, fl;
-    uint32_t lv_first, lv_count;        // the levels whose rays this launch covers (the frame's launch: all; the counting re-walks: 0 / the rest)
-    uint32_t cbase[MAXD + 1], hstride[MAXD + 1];      // storage: PipeDev::sh_cbase, LevelDev::hstride
-    LightRays lights;                   // the frame's light rays (lights.on: the compact form)
-    const LightRays *frame_lights;      // device array [n_frames] (sets of frames)
-    ShadowCacheDev cache;
-    // the launch enumerates, level after level, round64(hits) rays of kind 0, then of kind 1, ... (wave-uniform: scalar loads and adds)
-    RT_DEV uint32_t count() const
-    {
-        uint32_t b = 0;
-#pragma unroll
-        for (uint32_t k = 0; k <= (uint32_t)MAXD; k++) if (k >= lv_first && k < lv_first + lv_count) b += (nhit[k] + 63u) & ~63u;
-        return b << log2;
-    }
-    RT_DEV uint32_t flags() const { return fl; }
-};
-template <bool BATCH>
-struct ShadowSrcN : ShadowQueue {
-    // Ray i of the launch -> (level, kind of ray b, hit j of the level) by compares against wave-uniform thresholds; `ticket` =
-    // the ray's number in storage order, which is where the sink puts its result (the walk carries it in place of i).
-    // BATCH: a set of frames -- the lights of frame f (bits 8.. of the hit's word).  The single-frame kernels pass a literal nullptr:
-    // the branch folds away
-    RT_DEV bool load(uint32_t i, RayD &r, uint32_t &ticket) const
-    {
-        uint32_t n = 0, R = 0, cb = 0, hs = 0, before = 0;
-        ticket = 0;
-#pragma unroll
-        for (uint32_t k = 0; k <= (uint32_t)MAXD; k++) {
-            if (k >= lv_first && k < lv_first + lv_count) {
-                const uint32_t nk = nhit[k], Rk = (nk + 63u) & ~63u, start = before;
-                before += Rk << log2;
-                const bool here = i >= start;             // (the last level that says so wins)
-                n = here ? nk : n; R = here ? Rk : R; cb = here ? cbase[k] : cb; hs = here ? hstride[k] : hs;
-                if (here) ticket = start;                 // (queue index of the level's first ray, for now)
-            }
-        }
-        const uint32_t local = i - ticket;
-        uint32_t b = local >= R ? 1u : 0u;
-        if (log2 > 1u) { b += local >= 2u * R ? 1u : 0u; b += local >= 3u * R ? 1u : 0u; }
-        const uint32_t j = local - b * R;
-        ticket = (cb << log2) + b * hs + j;
-        r.o = mk3(0.0f, 0.0f, 0.0f);
-        r.d = mk3(0.0f, 0.0f, 0.0f);
-        r.tmin = 0.0f;
-        r.tmax = -1.0f;                                      // no such ray: never traced
-        if (j >= n) { ticket = RT_NO_HIT; return false; }   // (the entries that round a level up to 64: nothing to load, nothing to store)
-        if (lights.on) {
-            const v4f a = ldg16(hits, (size_t)(cb + j) * 16);
-            const uint32_t bits = __float_as_uint(a.w);
-            r.o = mk3(a.x, a.y, a.z);
-            if (!((bits >> b) & 1u)) return false;
-            if ((bits >> (2u + b)) & 1u) { r.tmax = RT_TMAX_SKIPPED; return false; }
-            r.tmin = RAY_EPSILON;
-            const LightRays *per_frame = BATCH ? frame_lights : nullptr;
-            if (per_frame) {                                 // (three floats by hand: a struct copy ends up in scratch memory)
-                const float *fl = b == 0u ? per_frame[(bits >> 8) & 0xffu].dir_to_light : per_frame[(bits >> 8) & 0xffu].point_pos;
-                const f3 l = mk3(fl[0], fl[1], fl[2]);
-                if (b == 0u) { r.d = l; r.tmax = RAY_MAX_T; }
-                else {
-                    const f3 path = l - r.o;
-                    const float dist = length(path);
-                    r.d = normalize(path);
-                    r.tmax = dist - fmaxf(RAY_EPSILON, fl[3]);       // (fl[3]: point_free of that frame's lights)
-                }
-                return r.tmax > r.tmin;
-            }
-            if (b == 0u) {
-                r.d = mk3(lights.dir_to_light[0], lights.dir_to_light[1], lights.dir_to_light[2]);
-                r.tmax = RAY_MAX_T;
-            } else {
-                const f3 path = mk3(lights.point_pos[0], lights.point_pos[1], lights.point_pos[2]) - r.o;
-                const float dist = length(path);
-                r.d = normalize(path);
-                r.tmax = dist - fmaxf(RAY_EPSILON, lights.point_free);
-            }
-            return r.tmax > r.tmin;
-        }
-        const v4f a = ldg16(O, (size_t)ticket * 16), d = ldg16(D, (size_t)ticket * 16);
-        r.o = mk3(a.x, a.y, a.z); r.tmin = a.w;
-        r.d = mk3(d.x, d.y, d.z); r.tmax = d.w;
-        return r.tmax > r.tmin;
-    }
-    // ---- the shadow cache (ShadowCacheDev): where this ray's entry lives, what it holds, what to put there ----
-    RT_DEV uint32_t cache_slot(const RayD &r) const
-    {
-        const uint32_t res = cache.res;
-        if (!(r.tmax < 1.0e37f)) {          // the directional light's rays run to RAY_MAX_T, the point light's to the light
-            float u = r.o.x * cache.ua[0] + r.o.y * cache.ua[1] + r.o.z * cache.ua[2] + cache.ua[3];
-            float v = r.o.x * cache.va[0] + r.o.y * cache.va[1] + r.o.z * cache.va[2] + cache.va[3];
-            u = fminf(fmaxf(u, 0.0f), cache.res_f - 1.0f);
-            v = fminf(fmaxf(v, 0.0f), cache.res_f - 1.0f);
-            return (uint32_t)u * res + (uint32_t)v;
-        }
-        const float mx = r.o.x - cache.lp[0], my = r.o.y - cache.lp[1], mz = r.o.z - cache.lp[2];      // from the light to the point
-        const float ax = fabsf(mx), ay = fabsf(my), az = fabsf(mz);
-        uint32_t face;
-        float ma, s, t;
-        if (ax >= ay && ax >= az) { face = mx < 0.0f ? 1u : 0u; ma = ax; s = my; t = mz; }
-        else if (ay >= az) { face = my < 0.0f ? 3u : 2u; ma = ay; s = mz; t = mx; }
-        else { face = mz < 0.0f ? 5u : 4u; ma = az; s = mx; t = my; }
-        const float inv = __builtin_amdgcn_rcpf(ma), half = 0.5f * cache.res_f;       // (where an entry lives need not be rounded correctly)
-        const float cs = fminf(fmaxf((s * inv * 0.5f + 0.5f) * half, 0.0f), half - 1.0f);
-        const float ct = fminf(fmaxf((t * inv * 0.5f + 0.5f) * half, 0.0f), half - 1.0f);
-        const uint32_t r2 = res >> 1;
-        return res * res + (face * r2 + (uint32_t)cs) * r2 + (uint32_t)ct;
-    }
-    // (the slot is computed once, when the ray is loaded; the walk keeps it in a spare row of the lane's LDS stack until a hit wants it)
-    static constexpr bool has_first_candidates = true;
-    template <bool TWO_LEVEL>
-    RT_DEV uint32_t cached_leaf(uint32_t ticket, const RayD &r, uint32_t &slot, uint32_t &instance) const
-    {
-        slot = RT_NO_HIT;
-        instance = 0u;
-        if (!cache.table) return RT_NO_HIT;
-        slot = RT_NO_HIT;
-        if (cache.px_base && ticket < 2u * cache.hstride0) {          // a primary hit's ray: its pixel's entry
-            const uint32_t b = ticket >= cache.hstride0 ? 1u : 0u;
-            uint32_t q = cache.jlist0[ticket - b * cache.hstride0];
-            if (cache.n_frames > 1u) q = (__umulhi(q >> 6, cache.frames_magic) << 6) | (q & 63u);      // tile-major slots of a set: chunk = tile * frames + frame
-            if (q < cache.px_slots) slot = cache.px_base + 2u * q + b;
-        }
-        if (slot == RT_NO_HIT) slot = cache_slot(r);
-        if (TWO_LEVEL) {
-            const uint2 e = ((const uint2 *)cache.table)[slot];
-            instance = e.y;
-            return e.x;                                  // (checked against its instance's triangle count by the walk)
-        }
-        const uint32_t t = cache.table[slot];
-        return t < cache.n_tris ? t : RT_NO_HIT;         // (an entry is only ever tested if it names a triangle that exists)
-    }
-    template <bool TWO_LEVEL>
-    RT_DEV void remember(uint32_t slot, uint32_t sorted_triangle, uint32_t instance) const
-    {
-        // (a slot that the stack has overwritten in the meantime is some other number: inside the table it only makes a stale entry)
-        if (!cache.table || slot >= cache.entries) return;
-        if (TWO_LEVEL) ((uint2 *)cache.table)[slot] = make_uint2(sorted_triangle, instance);
-        else cache.table[slot] = sorted_triangle;
-    }
-};
-struct ShadowSinkN {      // ShadowMiss sets visibility 1 (ProgressiveRaytracing.hlsl:178-182)
-    ShadowQueue s;
-    // Round 6: ONE BIT per shadow ray (bit ticket & 31 of word ticket >> 5, cleared before the launch), set by a no-return atomic when the ray
-    // reaches its light.  A 4-byte store per ray cost 22 B of HBM writes per ray (scattered partial lines: 4.4 GB per 20-frame launch,
-    // profiles/r05/c2s_write.md) to deliver that bit.  The 32 tickets of a word are consecutive rays of one (level, light) run and such runs
-    // start at multiples of 64, so the word belongs to ONE chunk of the queue = one wave = one XCD's L2: no two L2s ever update the same word.
-    RT_DEV void store(uint32_t ticket, const HitD &h, bool) const { if (ticket != RT_NO_HIT && h.inst == RT_NO_HIT) atomicOr(&s.vis[ticket >> 5], 1u << (ticket & 31u)); }
-};
-
-// The shadow walks are trace_wave's ANYHIT instantiation, always: only that instantiation tallies the queue slots marked "emitted but not
-// traversed" -- with ordered shadow walks rt_stats.rays_shadow would under-count when rt_pipeline_set_skip_unlit_shadow_rays is on.
-// The flags every shadow queue carries (RaytracingCommon.hlsli:94):
-constexpr uint32_t SHADOW_RAY_FLAGS = RT_RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH | RT_RAY_FLAG_SKIP_CLOSEST_HIT_SHADER;
-
 template <int STACK, bool TWO_LEVEL, bool BATCH>
 __global__ void __launch_bounds__(PBLOCK) RT_WAVES_PER_EU k_trace_shadow(SceneDev sc, ShadowQueue queues, uint32_t *pool, uint32_t *stat)
 {
-    __shared__ int smem[(RT_ROWS(STACK) + RT_TOP_ROWS(PBLOCK)) * PBLOCK];
+    __shared__ int smem[walk_lds_words(RT_ROWS(STACK))];
     ShadowSrcN<BATCH> src;
     static_cast<ShadowQueue &>(src) = queues;
     ShadowSinkN sink = {queues};
-    trace_wave<RT_ROWS(STACK), PBLOCK, TWO_LEVEL, (!TWO_LEVEL && RT_ROWS(STACK) == RT_LDS_STACK_ROWS_SETS) ? RT_POOL_CHUNK_SETS_ANYHIT : RT_POOL_CHUNK, true, false, false, RT_REFS(STACK)>(sc, src, sink, pool, smem, stat);
+    trace_wave<RT_ROWS(STACK), PBLOCK, TWO_LEVEL, pool_chunk(STACK, TWO_LEVEL, true), true, false, false, RT_REFS(STACK)>(sc, src, sink, pool, smem, stat);
 }
 
 template <int STACK, bool TWO_LEVEL>
 __global__ void __launch_bounds__(PBLOCK) RT_WAVES_PER_EU k_trace_secondary(SceneDev sc, QueueSrc src, float4 *hit1, uint32_t *inst1, uint32_t *pool, uint32_t *stat)
 {
-    __shared__ int smem[(RT_ROWS(STACK) + RT_TOP_ROWS(PBLOCK)) * PBLOCK];
+    __shared__ int smem[walk_lds_words(RT_ROWS(STACK))];
     SecondarySink sink = {src, hit1, inst1};
-    trace_wave<RT_ROWS(STACK), PBLOCK, TWO_LEVEL, (!TWO_LEVEL && RT_ROWS(STACK) == RT_LDS_STACK_ROWS_SETS) ? RT_POOL_CHUNK_SETS : RT_POOL_CHUNK, false, false, false, RT_REFS(STACK)>(sc, src, sink, pool, smem, stat);
-}
-
-// ---- walk counting (rt_pipeline_count_walk): the production walk over the last frame's queues with per-lane
-// tallies of what it fetches; results are not stored (the frame already holds them)
-struct NullSink { RT_DEV void store(uint32_t, const HitD &, bool) const {} };
-
-template <bool TWO_LEVEL>
-__global__ void __launch_bounds__(PBLOCK) k_walk_primary(PipeDev pd, unsigned long long *walk)
-{
-    __shared__ int smem[(RT_LDS_STACK_ROWS + RT_TOP_ROWS(PBLOCK)) * PBLOCK];
-    PrimarySrc src = {pd};
-    NullSink sink;
-    trace_wave<RT_LDS_STACK_ROWS, PBLOCK, TWO_LEVEL, 64u, false, true, false, true>(pd.sc, src, sink, nullptr, smem, nullptr, walk);
-}
-// (... of a primary stage that started from entry lists: the same lists, the same walk.  As k_walk_primary does for the walk from the root, it
-// keeps rows beyond LDS and walks a deep ray on from where it stands, where the timed launch hands it to k_primary_retry, which starts at the
-// root again: on a tree deeper than the LDS rows the tally leaves out the retried rays' second walk, with lists as without)
-template <bool BATCH>
-__global__ void __launch_bounds__(PBLOCK) k_walk_primary_from_entries(PipeDev pd, const uint2 *__restrict__ entries, uint32_t frames_magic, uint32_t tiles_x_magic, unsigned long long *walk)
-{
-    __shared__ int smem[(RT_LDS_STACK_ROWS + 1) * PBLOCK];
-    PrimaryEntrySrcT<BATCH> src = {{pd}, entries, frames_magic, tiles_x_magic};
-    NullSink sink;
-    trace_wave<RT_LDS_STACK_ROWS, PBLOCK, false, 64u, false, true, false, true>(pd.sc, src, sink, nullptr, smem, nullptr, walk);
-}
-template <bool TWO_LEVEL>
-__global__ void __launch_bounds__(PBLOCK) k_walk_queue(SceneDev sc, QueueSrc src, unsigned long long *walk)
-{
-    __shared__ int smem[(RT_LDS_STACK_ROWS + RT_TOP_ROWS(PBLOCK)) * PBLOCK];
-    NullSink sink;
-    trace_wave<RT_LDS_STACK_ROWS, PBLOCK, TWO_LEVEL, RT_POOL_CHUNK, false, true, false, true>(sc, src, sink, nullptr, smem, nullptr, walk);
-}
-template <bool TWO_LEVEL>
-__global__ void __launch_bounds__(PBLOCK) k_walk_shadow(SceneDev sc, ShadowQueue queue, unsigned long long *walk)
-{
-    __shared__ int smem[(RT_LDS_STACK_ROWS + RT_TOP_ROWS(PBLOCK)) * PBLOCK];
-    ShadowSrcN<true> src;
-    static_cast<ShadowQueue &>(src) = queue;
-    NullSink sink;
-    trace_wave<RT_LDS_STACK_ROWS, PBLOCK, TWO_LEVEL, RT_POOL_CHUNK, true, true, false, true>(sc, src, sink, nullptr, smem, nullptr, walk);
+    trace_wave<RT_ROWS(STACK), PBLOCK, TWO_LEVEL, pool_chunk(STACK, TWO_LEVEL, false), false, false, false, RT_REFS(STACK)>(sc, src, sink, pool, smem, stat);
 }
 
 // the frame's ray / hit counts into the running totals (one thread, once per frame)
@@ -871,73 +360,10 @@ __global__ void __launch_bounds__(PBLOCK) k_shade_level(PipeDev pd, int L)
     else shade_level_body<BATCH, MAXD>(pd, L);
 }
 
-// every lane of the wave must call this (no early exits before it)
-RT_DEV void wave_add64(unsigned long long v, unsigned long long *counter)
-{
-    for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
-    if ((threadIdx.x & 63u) == 0u && v) atomicAdd(counter, v);
-}
-
-// canonical-order re-trace of a queue: sums rays / nodes / triangles into out[0..2]
-template <class Src>
-__global__ void __launch_bounds__(PBLOCK)
-k_count_queue(SceneDev sc, Src src, unsigned long long *__restrict__ out)
-{
-    const uint32_t idx = blockIdx.x * PBLOCK + threadIdx.x;
-    unsigned long long rays = 0, nodes = 0, tris = 0;
-    if (idx < src.count()) {
-        RayD r;
-        uint32_t ticket;
-        if (load_ray_of(src, idx, r, ticket, 0)) {
-            uint32_t cn, ct;
-            (void)trace_canonical(sc, r, src.flags(), cn, ct);
-            rays = 1; nodes = cn; tris = ct;
-        }
-    }
-    wave_add64(rays, &out[0]);
-    wave_add64(nodes, &out[1]);
-    wave_add64(tris, &out[2]);
-}
-
-__global__ void k_debug_cube(PipeDev pd, const float *__restrict__ dirs, float *__restrict__ out, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const f3 c = sample_cube(pd, mk3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
-    out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
-}
-
-
-}  // namespace
-
-namespace {
-
-// The radiance rays of level l >= 1 (ProgressiveRaytracing.hlsl:53): level 1 holds the diffuse and the specular batch of the primary
-// hits, a deeper level one ray per hit of level l - 1.
-QueueSrc level_rays(const PipeDev &pd, uint32_t l)
-{
-    return {pd.lv[l].O, pd.lv[l].D, &pd.counters[C_NHIT + l - 1], pd.lv[1].rstride, l == 1 ? 2u : 1u, RT_RAY_FLAG_NONE};
-}
-
-// The shared shadow queue as a launch over the rays of levels lv_first .. lv_first + lv_count - 1 sees it; no shadow cache (the frame's
-// launch adds its own, the counting re-walks have none).
-ShadowQueue shadow_queue(const PipeDev &pd, uint32_t lv_first, uint32_t lv_count)
-{
-    ShadowQueue sq;
-    memset(&sq, 0, sizeof sq);
-    sq.hits = pd.sh_hits; sq.O = pd.sh_O; sq.D = pd.sh_D; sq.vis = pd.sh_vis;
-    sq.nhit = &pd.counters[C_NHIT];
-    sq.log2 = pd.sh_log2; sq.fl = SHADOW_RAY_FLAGS;
-    sq.lv_first = lv_first; sq.lv_count = lv_count;
-    for (int k = 0; k <= MAXD; k++) { sq.cbase[k] = pd.sh_cbase[k]; sq.hstride[k] = pd.lv[k].hstride; }
-    sq.lights = light_rays(pd);
-    sq.frame_lights = pd.n_frames > 1u ? pd.frame_lights : nullptr;
-    return sq;
-}
-
 // The launches of one frame (BATCH = false), or of one set of frames: the shading kernels then pick the constants of every hit's frame.
-// plan.counted: the levels beyond the pixel slots are sized by what the compaction before them has counted (see "queue memory"
-// above); otherwise the caller has reserved the worst case and set the strides.  pd is updated as the levels are bound and is what the counting re-walks replay (rt_pipeline::last_pd).
+// plan.counted: the levels beyond the pixel slots are sized by what the compaction before them has counted ("queue memory",
+// rt_pipeline_queues.h); otherwise the caller has reserved the worst case and set the strides.  pd is updated as the levels are bound
+// and is what the counting passes replay (rt_pipeline::last_pd, rt_pipeline_inspect.hip).
 template <int STACK, bool TWO_LEVEL, bool BATCH>
 int launch_frame(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
 {
@@ -989,10 +415,8 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
         bool from_entries = false;
         if constexpr (!TWO_LEVEL) {
             if (p->primary_entries.on) {
-                const uint32_t tiles_y = (pd.fcap >> 6) / pd.tiles_x;
-                uint2 *lists = p->primary_entries.lists.as<uint2>();
-                k_primary_entries<<<((pd.tiles_x + 7u) / 8u) * ((tiles_y + 7u) / 8u), EBLOCK, 0, st>>>(pd, lists, p->primary_entries.cut, p->primary_entries.cap);
-                k_primary_from_entries<STACK, BATCH><<<blocks(cap), PBLOCK, 0, st>>>(pd, lists, (uint32_t)(0x100000000ull / pd.n_frames) + 1u, (uint32_t)(0x100000000ull / pd.tiles_x) + 1u);
+                const uint2 *lists = rt_entries_launch(p, pd);
+                k_primary_from_entries<STACK, BATCH><<<blocks(cap), PBLOCK, 0, st>>>(pd, lists, recip32(pd.n_frames), recip32(pd.tiles_x));
                 from_entries = true;
             }
         }
@@ -1022,7 +446,7 @@ int launch_frame(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
         sq.cache.jlist0 = pd.lv[0].jlist;
         sq.cache.hstride0 = pd.lv[0].hstride;
         sq.cache.n_frames = pd.n_frames;
-        sq.cache.frames_magic = (uint32_t)(0x100000000ull / (pd.n_frames ? pd.n_frames : 1u)) + 1u;
+        sq.cache.frames_magic = recip32(pd.n_frames);
         if (sq.cache.px_slots > pd.fcap) sq.cache.px_slots = pd.fcap;
         const size_t rays_max = sh_total << pd.sh_log2;
         HIP_TRY(hipMemsetAsync(pd.sh_vis, 0, ((rays_max + 31) / 32) * 4, st));      // the visibility bits: set by the rays that reach their light
@@ -1054,34 +478,6 @@ int launch_frame_any(rt_pipeline *p, PipeDev &pd, const SetPlan &plan)
     return p->scene->two_level ? launch_frame_sized<STACK, true>(p, pd, plan) : launch_frame_sized<STACK, false>(p, pd, plan);
 }
 
-template <bool TWO_LEVEL>
-static int count_walk_launch(rt_pipeline *p, unsigned long long *w)
-{
-    hipStream_t st = p->ctx->stream;
-    const rt_context *ctx = p->ctx;
-    const PipeDev &pd = p->last_pd;
-    const uint32_t cap = pd.cap;
-    if (!TWO_LEVEL && p->primary_entries.on) {
-        const uint2 *lists = p->primary_entries.lists.as<uint2>();
-        const uint32_t fm = (uint32_t)(0x100000000ull / pd.n_frames) + 1u, tm = (uint32_t)(0x100000000ull / pd.tiles_x) + 1u;
-        unsigned long long *wp = w + RT_WALK_WORDS * RT_STAGE_PRIMARY;
-        if (pd.n_frames > 1u) k_walk_primary_from_entries<true><<<rt_persistent_grid(ctx, k_walk_primary_from_entries<true>, PBLOCK, cap), PBLOCK, 0, st>>>(pd, lists, fm, tm, wp);
-        else k_walk_primary_from_entries<false><<<rt_persistent_grid(ctx, k_walk_primary_from_entries<false>, PBLOCK, cap), PBLOCK, 0, st>>>(pd, lists, fm, tm, wp);
-    } else
-        k_walk_primary<TWO_LEVEL><<<rt_persistent_grid(ctx, k_walk_primary<TWO_LEVEL>, PBLOCK, cap), PBLOCK, 0, st>>>(pd, w + RT_WALK_WORDS * RT_STAGE_PRIMARY);
-    const unsigned gq = rt_persistent_grid(ctx, k_walk_queue<TWO_LEVEL>, PBLOCK, (size_t)cap * 2);
-    const unsigned gs = rt_persistent_grid(ctx, k_walk_shadow<TWO_LEVEL>, PBLOCK, (size_t)cap * 2);
-    // the shadow rays of the primary hits ...
-    k_walk_shadow<TWO_LEVEL><<<gs, PBLOCK, 0, st>>>(pd.sc, shadow_queue(pd, 0, 1), w + RT_WALK_WORDS * RT_STAGE_SHADOW0);
-    const uint32_t levels = pd.max_rad < (uint32_t)MAXD ? pd.max_rad : (uint32_t)MAXD;
-    for (uint32_t l = 1; l <= levels; l++)
-        k_walk_queue<TWO_LEVEL><<<gq, PBLOCK, 0, st>>>(pd.sc, level_rays(pd, l), w + RT_WALK_WORDS * RT_STAGE_SECONDARY);
-    if (pd.sh_levels > 1u)                                  // ... and of all deeper hits
-        k_walk_shadow<TWO_LEVEL><<<gs, PBLOCK, 0, st>>>(pd.sc, shadow_queue(pd, 1, pd.sh_levels - 1u), w + RT_WALK_WORDS * RT_STAGE_SHADOW1);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
 }  // namespace
 
 int rt_frame_launch(rt_pipeline *p, PipeDev &pd, const SetPlan &plan, bool set_rows)
@@ -1095,39 +491,3 @@ int rt_frame_launch(rt_pipeline *p, PipeDev &pd, const SetPlan &plan, bool set_r
     if (set_rows) return launch_frame_sized<RT_LDS_STACK_ROWS_SETS, false>(p, pd, plan);
     return launch_frame_any<RT_LDS_STACK_ROWS>(p, pd, plan);
 }
-
-int rt_frame_count_walk(rt_pipeline *p, unsigned long long *w)
-{
-    return p->scene->two_level ? count_walk_launch<true>(p, w) : count_walk_launch<false>(p, w);
-}
-
-int rt_frame_count_work(rt_pipeline *p, unsigned long long *w)
-{
-    hipStream_t st = p->ctx->stream;
-    const PipeDev &pd = p->last_pd;
-    k_count_queue<<<blocks(pd.cap), PBLOCK, 0, st>>>(pd.sc, PrimarySrcByValue{pd}, w + 3 * RT_STAGE_PRIMARY);
-    ShadowSrcN<true> sq;
-    static_cast<ShadowQueue &>(sq) = shadow_queue(pd, 0, 1);
-    k_count_queue<<<blocks((size_t)pd.lv[0].hstride << pd.sh_log2), PBLOCK, 0, st>>>(pd.sc, sq, w + 3 * RT_STAGE_SHADOW0);
-    const uint32_t levels = pd.max_rad < (uint32_t)MAXD ? pd.max_rad : (uint32_t)MAXD;
-    size_t deeper = 0;
-    for (uint32_t l = 1; l <= levels; l++) {        // every secondary level adds into the same row
-        const size_t slots = l == 1 ? 2 * (size_t)pd.lv[1].rstride : (size_t)pd.lv[l - 1].hstride;
-        k_count_queue<<<blocks(slots), PBLOCK, 0, st>>>(pd.sc, level_rays(pd, l), w + 3 * RT_STAGE_SECONDARY);
-        if (l < pd.sh_levels) deeper += pd.lv[l].hstride;
-    }
-    if (pd.sh_levels > 1u) {
-        static_cast<ShadowQueue &>(sq) = shadow_queue(pd, 1, pd.sh_levels - 1u);
-        k_count_queue<<<blocks(deeper << pd.sh_log2), PBLOCK, 0, st>>>(pd.sc, sq, w + 3 * RT_STAGE_SHADOW1);
-    }
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-int rt_frame_debug_cube(hipStream_t st, const PipeDev &pd, const float *dirs, float *out, size_t n)
-{
-    k_debug_cube<<<blocks(n), PBLOCK, 0, st>>>(pd, dirs, out, n);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-

@@ -1,7 +1,8 @@
 // rt_pipeline_dev.h -- what the translation units of the pipeline share: the stage constants, the device-visible view of a
 // frame (PipeDev: what every kernel of the wavefront DAG takes as its argument), and the host object behind rt_pipeline.
-// Kernels and launches: rt_pipeline.hip.  Device shading functions: rt_shade.h.  Outputs, checkpoints, statistics:
-// rt_pipeline_host.hip.
+// Stage kernels and launches: rt_pipeline.hip, their ray sources and sinks: rt_pipeline_rays.h.  Device shading functions: rt_shade.h.
+// Render calls: rt_pipeline_render.hip.  Entry lists: rt_pipeline_entries.hip.  Replays of the last frame: rt_pipeline_inspect.hip.
+// Outputs, checkpoints, statistics: rt_pipeline_host.hip.
 #pragma once
 
 #include "rt_trace_wave.h"
@@ -86,7 +87,7 @@ struct ShadowCacheDev {
 
 #define RT_MAX_BATCH 32u                // frames one set of launches renders (rt_pipeline_render_batch)
 
-// The primary stage's entry lists (k_primary_entries, rt_pipeline.hip): per 8x8 tile of the launch's rectangle
+// The primary stage's entry lists (k_primary_entries, rt_pipeline_entries.hip): per 8x8 tile of the launch's rectangle
 // RT_ENTRY_STRIDE entries of 8 B, (child code, bits of tnear), sorted by tnear and closed by (RT_NODE_EMPTY, +inf); at most
 // RT_ENTRY_CAP entries in front of the sentinel.  264 B per tile: 8.6 MB at 1080p, written once per set of launches.
 #define RT_ENTRY_CAP 32u
@@ -272,7 +273,7 @@ struct rt_pipeline : rt_handle {
     ~rt_pipeline();                    // (rt_pipeline_host.hip) the ring's events, the scene it retains; then the members
 };
 
-// renders the frames a deferred pipeline holds (rt_pipeline.hip); every entry point that reads or changes what they see calls it first
+// renders the frames a deferred pipeline holds (rt_pipeline_render.hip); every entry point that reads or changes what they see calls it first
 int rt_pipeline_flush_pending(rt_pipeline *p);
 
 namespace rtp {

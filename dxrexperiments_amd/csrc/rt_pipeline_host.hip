@@ -1,7 +1,7 @@
 // rt_pipeline_host.hip -- the part of the pipeline object that launches no traversal or shading kernel: creation and the
 // setters of the reference's interface (include/RaytracingPipeline.h:14-38), outputs and their read-back (RGBA32F and the
 // RGBA16F view of the reference's storage format), accumulation checkpoints, stage timing and ray statistics.
-// The frame itself (kernels, launches, render calls, work counting): rt_pipeline.hip.
+// The frame itself: rt_pipeline.hip (stage kernels, launches), rt_pipeline_render.hip (render calls), rt_pipeline_inspect.hip (work counting).
 #include <hip/hip_fp16.h>
 
 #include <new>

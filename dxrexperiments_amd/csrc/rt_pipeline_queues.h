@@ -1,5 +1,6 @@
-// rt_pipeline_queues.h -- host-side helpers the two translation units of the pipeline share (rt_pipeline.hip: the frame's kernels and
-// launches; rt_pipeline_render.hip: the render calls): the frame's light rays as the host computes them, and the queue memory -- what a
+// rt_pipeline_queues.h -- host-side helpers the translation units of the pipeline share (rt_pipeline.hip: the stage kernels and their
+// launches; rt_pipeline_render.hip: the render calls; rt_pipeline_entries.hip: the primary stage's entry lists; rt_pipeline_inspect.hip:
+// the calls that replay the last frame): the frame's light rays as the host computes them, and the queue memory -- what a
 // level's buffers hold, the worst case and the budget, reservation by count, binding a level's buffers into the kernels' argument, and
 // the plan of one set of launches (SetPlan: what sizes it, and the one reservation that follows from it).
 #pragma once
@@ -119,7 +120,8 @@ inline void bind_level(const rt_pipeline *p, PipeDev &pd, int l)
 }
 
 // radiance levels a frame traces: level l exists when hits of depth l-1 may spawn rays
-inline uint32_t frame_levels(const rt_pipeline *p) { return p->max_rad < (uint32_t)MAXD ? p->max_rad : (uint32_t)MAXD; }
+inline uint32_t frame_levels(uint32_t max_rad) { return max_rad < (uint32_t)MAXD ? max_rad : (uint32_t)MAXD; }
+inline uint32_t frame_levels(const rt_pipeline *p) { return frame_levels(p->max_rad); }
 
 // ---- one set of launches: what sizes it, decided once (render_region and rt_pipeline_reserve_batch ask the same two functions) ----
 struct SetPlan {
@@ -166,10 +168,12 @@ inline int reserve_set(rt_pipeline *p, const SetPlan &s)
 
 }  // namespace rtp
 
-// ---- what rt_pipeline.hip (kernels, launches) offers rt_pipeline_render.hip (the render calls) ----
+// ---- what rt_pipeline.hip (the stage kernels, their launches) offers rt_pipeline_render.hip (the render calls) ----
 // the launches of one frame or one set of frames (set_rows: the sets' seven-wave single-level kernels); pd is updated as levels are bound
 int rt_frame_launch(rt_pipeline *p, rtp::PipeDev &pd, const rtp::SetPlan &plan, bool set_rows);
-// the counting re-walks over the last frame's queues (p->last_pd): launches only, results in w[RT_STAGE_COUNT][RT_WALK_WORDS] / [3]
-int rt_frame_count_walk(rt_pipeline *p, unsigned long long *w);
-int rt_frame_count_work(rt_pipeline *p, unsigned long long *w);
-int rt_frame_debug_cube(hipStream_t st, const rtp::PipeDev &pd, const float *dirs, float *out, size_t n);
+
+// ---- what rt_pipeline_entries.hip (the primary stage's entry lists) offers the two ----
+// choose_primary_stage: whether the coming set has lists (p->primary_entries), with their cut, their cap and room for them
+int rt_entries_choose(rt_pipeline *p, const rtp::PipeDev &pd, const rt_per_frame_constants *frames);
+// launch_frame: the launch that makes the set's lists; returns them
+const uint2 *rt_entries_launch(rt_pipeline *p, const rtp::PipeDev &pd);

@@ -1,7 +1,8 @@
 // rt_pipeline_render.hip -- the render calls of the pipeline: one frame over a region (tile, bands), sets of frames
 // (rt_pipeline_render_batch, rt_pipeline_render_bands_batch), deferred mode behind update() + render(), queue-memory
-// reservation and reporting, the host side of the shadow cache and of the free sphere around the point light, and the exports that
-// replay the last frame's queues (work counting, primary hits).  The kernels and their launch sequence: rt_pipeline.hip.
+// reservation and reporting, and the host side of the shadow cache and of the free sphere around the point light.  The stage kernels
+// and their launch sequence: rt_pipeline.hip.  The entry lists' policy: rt_pipeline_entries.hip.  The exports that replay the last
+// frame's queues (work counting, primary hits): rt_pipeline_inspect.hip.
 #include <hip/hip_fp16.h>
 
 #include <utility>
@@ -284,27 +285,7 @@ int choose_primary_stage(rt_pipeline *p, PipeDev &pd, const rt_per_frame_constan
 {
     rt_context *ctx = p->ctx;
     pd.primary_persistent = p->primary_mode.choose(ctx, p->scene) ? 1u : 0u;
-    // entry lists (k_primary_entries): a tile's 64 directions must be the same in every frame of the set
-    rt_pipeline::PrimaryEntries &pe = p->primary_entries;
-    // (auto: sets of at least RT_ENTRY_MIN_FRAMES frames.  The list kernel takes about 0.1 ms at 1080p and a frame's walk gains 0.07 ms: a
-    // single frame with lists is 0.04 ms SLOWER than without, a set of 32 frames 2.2 ms faster: profiles/r18/primary_entries.txt)
-    pe.on = !p->scene->two_level && !pd.primary_persistent &&
-            (ctx->opt_primary_entries < 0 ? pd.sc.top_n != 0 && pd.n_frames >= RT_ENTRY_MIN_FRAMES : ctx->opt_primary_entries != 0);
-    for (uint32_t f = 1; pe.on && f < pd.n_frames; f++)
-        pe.on = memcmp(&frames[f].cameraParams.U, &frames[0].cameraParams.U, sizeof frames[0].cameraParams.U) == 0 &&
-                memcmp(&frames[f].cameraParams.V, &frames[0].cameraParams.V, sizeof frames[0].cameraParams.V) == 0 &&
-                memcmp(&frames[f].cameraParams.W, &frames[0].cameraParams.W, sizeof frames[0].cameraParams.W) == 0;
-    // (the walk's source divides chunk by frames and tile by tiles_x with 32-bit reciprocals: PrimaryEntrySrcT.  plan_set's limit of 2^30 slots
-    // bounds chunks x frames; tiles x tiles_x it bounds only for images up to 8192 tiles wide or so, hence the second test)
-    if ((uint64_t)(pd.cap >> 6) * pd.n_frames >= 0x100000000ull || (uint64_t)(pd.fcap >> 6) * pd.tiles_x >= 0x100000000ull) pe.on = false;
-    if (pe.on) {
-        const uint32_t n_nodes = p->scene->inst[0].model->blas.wide_n;
-        pe.cut = ctx->opt_primary_entries_cut ? ctx->opt_primary_entries_cut : (uint32_t)RT_TOP_NODES;
-        if (pe.cut > n_nodes) pe.cut = n_nodes;
-        if (pe.cut > RT_ENTRY_CUT_MAX) pe.cut = RT_ENTRY_CUT_MAX;
-        pe.cap = ctx->opt_primary_entries_cap ? ctx->opt_primary_entries_cap : RT_ENTRY_CAP;
-        RT_TRY(pe.lists.reserve((size_t)(pd.fcap >> 6) * RT_ENTRY_STRIDE * sizeof(uint2)));
-    }
+    RT_TRY(rt_entries_choose(p, pd, frames));      // from per-tile entry lists or from the root
     pd.retry = nullptr; pd.retry_cap = 0;
     if (pd.sc.deep_stack && !pd.primary_persistent) {      // the primary launch keeps no rows beyond LDS: the list of the rays that would need one
         const uint32_t want = ctx->opt_primary_retry_cap ? ctx->opt_primary_retry_cap : (1u << 20);
@@ -407,24 +388,6 @@ int flush_pending_now(rt_pipeline *p)
     const int rc = render_frames(p, p->width, p->height, frames.data(), (uint32_t)frames.size(), 0, 0, 1);
     p->pfc = keep;
     return rc;
-}
-
-// The head and the tail of the two counting calls (`who`): the last frame's queues must still stand; `words` counters are cleared, filled
-// by `launch` (rt_frame_count_work / rt_frame_count_walk) and brought back into h.
-int count_replay(rt_pipeline *p, const char *who, int (*launch)(rt_pipeline *, unsigned long long *), unsigned long long *h, size_t words)
-{
-    RT_TRY(rt_pipeline_flush_pending(p));
-    const char *nothing = "%s: nothing rendered since the last change of scene, materials or output";
-    if (p->rendered) RT_TRY(rt_scene_require_built(p->scene, who, nothing));       // (transforms, masks or vertices pending: the message names them)
-    if (!p->rendered || p->scene->generation != p->last_scene_gen) { rt_set_error(nothing, who); return RT_ERR_STATE; }
-    RT_TRY(rt_use_device(p->ctx));
-    hipStream_t st = p->ctx->stream;
-    RT_TRY(p->work.reserve(RT_STAGE_COUNT * RT_WALK_WORDS * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(p->work.p, 0, words * sizeof(unsigned long long), st));
-    RT_TRY(launch(p, p->work.as<unsigned long long>()));
-    HIP_TRY(hipMemcpyAsync(h, p->work.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RT_OK;
 }
 
 }  // namespace
@@ -611,111 +574,6 @@ int rt_pipeline_get_free_sphere(rt_pipeline *p, float *radius)
     free_sphere_poll(f);
     const float *lp = &p->pfc.pointLight.worldPos.x;
     if (f.known_gen == p->scene->generation && memcmp(f.known_lp, lp, sizeof f.known_lp) == 0) *radius = f.known_radius;
-    return RT_OK;
-}
-
-int rt_pipeline_count_work(rt_pipeline *p, rt_stage_work *out)
-{
-    RT_REQUIRE(p && out, "null argument");
-    unsigned long long h[RT_STAGE_COUNT * 3];
-    RT_TRY(count_replay(p, "count_work", rt_frame_count_work, h, RT_STAGE_COUNT * 3));
-    for (int k = 0; k < RT_STAGE_COUNT; k++) { out[k].rays = h[3 * k]; out[k].nodes = h[3 * k + 1]; out[k].tris = h[3 * k + 2]; }
-    return RT_OK;
-}
-
-int rt_pipeline_count_walk(rt_pipeline *p, rt_stage_walk *out)
-{
-    RT_REQUIRE(p && out, "null argument");
-    unsigned long long h[RT_STAGE_COUNT * RT_WALK_WORDS];
-    RT_TRY(count_replay(p, "count_walk", rt_frame_count_walk, h, RT_STAGE_COUNT * RT_WALK_WORDS));
-    for (int k = 0; k < RT_STAGE_COUNT; k++) {
-        const unsigned long long *hk = h + RT_WALK_WORDS * k;
-        out[k].rays = hk[0]; out[k].nodes_global = hk[1]; out[k].nodes_lds = hk[2];
-        out[k].tris = hk[3]; out[k].instance_entries = hk[4]; out[k].lines = hk[5];
-        out[k].longest_walk = hk[6] >> 32;
-        out[k].longest_walk_ray = (uint32_t)hk[6];
-        out[k].wave_node_steps = hk[7]; out[k].wave_leaf_phases = hk[8]; out[k].wave_tri_steps = hk[9]; out[k].node_lines = hk[10];
-    }
-    return RT_OK;
-}
-
-// debugging aid for rt_stage_walk.longest_walk_ray: ray `index` of the level-1 radiance queue (diffuse batch, then specular batch)
-int rt_debug_read_secondary_ray(rt_pipeline *p, uint32_t index, float origin_tmin[4], float dir_tmax[4])
-{
-    RT_REQUIRE(p && origin_tmin && dir_tmax, "null argument");
-    RT_TRY(rt_pipeline_flush_pending(p));
-    if (!p->rendered) { rt_set_error("nothing rendered yet"); return RT_ERR_STATE; }
-    RT_TRY(rt_use_device(p->ctx));
-    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    uint32_t n = 0;
-    HIP_TRY(hipMemcpy(&n, p->last_pd.counters + C_NHIT, 4, hipMemcpyDeviceToHost));
-    RT_REQUIRE(n > 0 && index < 2 * n, "ray index out of range");
-    const size_t slot = (size_t)(index / n) * p->last_pd.lv[1].rstride + index % n;
-    HIP_TRY(hipMemcpy(origin_tmin, p->last_pd.lv[1].O + slot, 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dir_tmax, p->last_pd.lv[1].D + slot, 16, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_debug_read_primary_entries(rt_pipeline *p, uint32_t first_tile, uint32_t count, uint32_t *entries, uint32_t *n_tiles, uint32_t *cut)
-{
-    RT_REQUIRE(p, "null pipeline");
-    RT_TRY(rt_pipeline_flush_pending(p));
-    if (!p->rendered) { rt_set_error("nothing rendered yet"); return RT_ERR_STATE; }
-    const uint32_t tiles = p->primary_entries.on ? p->last_pd.fcap >> 6 : 0u;
-    if (n_tiles) *n_tiles = tiles;
-    if (cut) *cut = p->primary_entries.on ? p->primary_entries.cut : 0u;
-    if (!entries || count == 0) return RT_OK;
-    RT_REQUIRE(first_tile < tiles && count <= tiles - first_tile, "tile out of range");
-    RT_TRY(rt_use_device(p->ctx));
-    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    HIP_TRY(hipMemcpy(entries, p->primary_entries.lists.as<uint2>() + (size_t)first_tile * RT_ENTRY_STRIDE, (size_t)count * RT_ENTRY_STRIDE * sizeof(uint2), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_pipeline_read_primary_hits(rt_pipeline *p, float *t, uint32_t *prim, uint32_t *inst)
-{
-    RT_REQUIRE(p, "null pipeline");
-    RT_TRY(rt_pipeline_flush_pending(p));
-    if (!p->rendered) { rt_set_error("nothing rendered yet"); return RT_ERR_STATE; }
-    RT_TRY(rt_use_device(p->ctx));
-    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    const PipeDev &pd = p->last_pd;
-    const size_t cap = pd.cap;
-    std::vector<float4> h(cap);
-    std::vector<uint32_t> hi(cap);
-    HIP_TRY(hipMemcpy(h.data(), p->lv[0].hit.p, cap * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hi.data(), p->lv[0].inst.p, cap * 4, hipMemcpyDeviceToHost));
-    for (size_t q = 0; q < cap; q++) {          // slots are 8x8-tiled: scatter back to scanline order
-        const uint32_t tl = (uint32_t)(q >> 6), w = (uint32_t)(q & 63u);
-        const uint32_t lx = (tl % pd.tiles_x) * 8u + (w & 7u), ly = (tl / pd.tiles_x) * 8u + (w >> 3);
-        if (lx >= pd.tw || ly >= pd.th) continue;
-        const size_t i = (size_t)ly * pd.tw + lx;
-        if (t) t[i] = h[q].x;
-        if (prim) memcpy(&prim[i], &h[q].w, 4);
-        if (inst) inst[i] = hi[q];
-    }
-    return RT_OK;
-}
-
-int rt_debug_sample_cube(rt_context *ctx, const float *faces, uint32_t size, uint32_t filter, const float *dirs, float *out, size_t n)
-{
-    RT_REQUIRE(ctx && faces && dirs && out && size > 0, "bad argument");
-    RT_REQUIRE(filter == RT_CUBE_SEAMLESS || filter == RT_CUBE_FACE_CLAMP, "unknown cube-map filter");
-    if (n == 0) return RT_OK;
-    RT_TRY(rt_use_device(ctx));
-    DevBuf *sb = ctx->scratch;
-    const size_t fb = (size_t)6 * size * size * 16;
-    RT_TRY(sb[0].reserve(fb)); RT_TRY(sb[1].reserve(n * 12)); RT_TRY(sb[2].reserve(n * 12));
-    HIP_TRY(hipMemcpyAsync(sb[0].p, faces, fb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(sb[1].p, dirs, n * 12, hipMemcpyHostToDevice, ctx->stream));
-    PipeDev pd;
-    memset(&pd, 0, sizeof pd);
-    pd.env = sb[0].as<float4>();
-    pd.env_size = size;
-    pd.env_filter = filter;
-    RT_TRY(rt_frame_debug_cube(ctx->stream, pd, sb[1].as<float>(), sb[2].as<float>(), n));
-    HIP_TRY(hipMemcpyAsync(out, sb[2].p, n * 12, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

@@ -136,7 +136,7 @@ template <class S, class = void> struct src_has_cache { static constexpr bool va
 template <class S> struct src_has_cache<S, decltype((void)&S::has_first_candidates)> { static constexpr bool value = true; };
 
 // A ray source may hand every 64-slot chunk of its rays a LIST OF ENTRY NODES to start from instead of the root (the primary launch's
-// per-tile lists, k_primary_entries in rt_pipeline.hip: the subtrees below a cut through the top of the tree that the tile's rays can
+// per-tile lists, k_primary_entries in rt_pipeline_entries.hip: the subtrees below a cut through the top of the tree that the tile's rays can
 // reach at all, nearest first): uint32_t first_entry(slot) -> the index of the first entry of the slot's list; uint2 entry(index) ->
 // (child code, bits of a lower bound of the distance at which any of the chunk's rays enters its box); a list ends with the code
 // RT_NODE_EMPTY.  The walk keeps the index of the lane's NEXT entry in an LDS row of its own -- the row behind the stack rows, where the
@@ -174,7 +174,7 @@ template <class S> RT_DEV bool load_ray_of(const S &src, uint32_t i, RayD &r, ui
 // The per-ray numbers depend on the ray and the tree only, not on chunking or lane assignment; the per-wave ones on both.
 // NO_DEEP (round 5): a launch without rows beyond the LDS ones -- the one-tile-per-wave primary launch, whose one thread per pixel slot made
 // those rows 224 MB per 1080p frame of a set.  A lane whose walk would need such a row gives the ray up: src.overflow(ticket) puts it on a
-// list that a small persistent launch with rows (k_primary_retry, rt_pipeline.hip) walks from the start; nothing is stored for it here.
+// list that a small persistent launch with rows (k_primary_retry, rt_pipeline.hip; the list: PrimarySrcT::overflow, rt_pipeline_rays.h) walks from the start; nothing is stored for it here.
 #define RT_WALK_WORDS 11
 // REFS (round 5): the scene holds triangles that are split into references (rt_refs.h): the leaf phase passes every record's reference mark
 // to the candidate test.  Instantiations for scenes without such triangles are the kernels of round 4, instruction for instruction.

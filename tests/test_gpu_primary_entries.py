@@ -1,4 +1,4 @@
-"""The primary stage's entry lists (csrc/rt_pipeline.hip k_primary_entries, option primary_entries).
+"""The primary stage's entry lists (csrc/rt_pipeline_entries.hip k_primary_entries, option primary_entries).
 
 Once per set of launches every 8x8 tile gets a list of the children below a cut through the top of the tree that ANY of its rays, in any
 frame of the set, can be made to enter by the walk's own culling, with a lower bound tnear of the entry distance; the tile's rays start

@@ -9,7 +9,8 @@ import sys
 def kernels(path):
     txt = open(path).read()
     out = {}
-    for m in re.finditer(r'^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:', txt, re.S | re.M):
+    # (functions only: a data symbol's label -- a constant table in front of a kernel -- would swallow the kernel behind it)
+    for m in re.finditer(r'^\s*\.type\s+(_Z\w+),@function\n(?:[^\n]*\n)*?\1:[^\n]*\n(.*?)^\.Lfunc_end\d+:', txt, re.S | re.M):
         lines = []
         for l in m.group(2).split('\n'):
             t = l.split(';')[0].rstrip()
