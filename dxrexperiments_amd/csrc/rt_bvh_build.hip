@@ -16,7 +16,6 @@
 #include "rt_lbvh.h"
 
 #include <chrono>
-
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -72,12 +71,9 @@ __global__ void k_tri_boxes(const rt_vertex *__restrict__ verts, const uint32_t 
     Box6 b;
     bool valid = i < n;
     if (valid) {
-        rt_float3 p0 = verts[idx[3 * i + 0]].position;
-        rt_float3 p1 = verts[idx[3 * i + 1]].position;
-        rt_float3 p2 = verts[idx[3 * i + 2]].position;
-        b.lo[0] = fminf(fminf(p0.x, p1.x), p2.x); b.hi[0] = fmaxf(fmaxf(p0.x, p1.x), p2.x);
-        b.lo[1] = fminf(fminf(p0.y, p1.y), p2.y); b.hi[1] = fmaxf(fmaxf(p0.y, p1.y), p2.y);
-        b.lo[2] = fminf(fminf(p0.z, p1.z), p2.z); b.hi[2] = fmaxf(fmaxf(p0.z, p1.z), p2.z);
+        float p[3][3];
+        tri_positions(verts, idx, i, p);
+        b = tri_box(p);
         boxes[i] = b;
     }
     reduce_bounds(b, valid, enc);
@@ -138,38 +134,12 @@ __global__ void __launch_bounds__(BOUNDS_BLOCK) k_instance_boxes(const InstanceR
     reduce_bounds(b, true, enc + 6u * (size_t)it.x);
 }
 
-__device__ __forceinline__ uint32_t expand10(uint32_t v)
-{
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
-__device__ __forceinline__ uint32_t quant10(float c, float lo, float ext)
-{
-    if (!(ext > 0.0f)) return 0;
-    float q = (c - lo) / ext * 1024.0f;
-    q = fminf(fmaxf(q, 0.0f), 1023.0f);
-    return (uint32_t)q;
-}
-
-__global__ void k_morton(const Box6 *__restrict__ boxes, uint32_t n, const float *__restrict__ bounds,
-                         uint64_t *__restrict__ keys)
+__global__ void k_morton(const Box6 *__restrict__ boxes, uint32_t n, const float *__restrict__ bounds, uint64_t *__restrict__ keys)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Box6 b = boxes[i];
-    uint32_t m = 0;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        float ctr = (b.lo[c] + b.hi[c]) * 0.5f;
-        float ext = bounds[3 + c] - bounds[c];
-        m |= expand10(quant10(ctr, bounds[c], ext)) << (2 - c);
-    }
-    keys[i] = ((uint64_t)m << 32) | i;
+    keys[i] = ((uint64_t)morton30(b.lo, b.hi, bounds) << 32) | i;
 }
 
 __global__ void k_leaves(const uint64_t *__restrict__ keys, const Box6 *__restrict__ boxes, uint32_t n,
@@ -228,16 +198,12 @@ __global__ void k_karras(const uint64_t *__restrict__ keys, int n, rt_bvh_node *
     ranges[i] = make_uint2((uint32_t)first, (uint32_t)last);
 }
 
-// Bottom-up union, every internal node visited ONCE (Karras 2012): a thread starts at its leaf and climbs; at a parent the
-// first arriver stops, the second unites the two child boxes and goes on.  The per-XCD L2s of this chip are not coherent
-// with each other, so everything two threads exchange is stored and loaded at AGENT scope (write-through / read-through
-// past the local L2): a thread publishes its node's box and depth with four 64-bit stores, waits until they are
-// acknowledged, only then bumps the parent's arrival counter (a device-scope atomic, executed at the memory side), and the
-// second arriver -- ordered behind the first by that counter -- reads the sibling with four agent-scope loads.  One
-// read-modify-write per node; the first round-2 version exchanged every word with one (14 per node, 0.15 ms for 262 k
-// triangles), round 1's min/max climb issued ~180 per leaf.  min / max are exact and order independent, so the boxes are
-// those of the oracle bit for bit.
-// scratch per node: 6 box words + depth + arrival counter = 8 words (four 64-bit pairs), zero-initialised.
+// Bottom-up union, every internal node visited ONCE: the climb of rt_bvh_tree.h ("the ordering of a bottom-up climb"), in the shape
+// publish, then arrive.  A thread publishes its node's box and depth, waits until the stores are acknowledged, only then bumps the parent's
+// arrival counter; the second arriver reads the sibling's words and unites.  One read-modify-write per node; the first round-2 version
+// exchanged every word with one (14 per node, 0.15 ms for 262 k triangles), round 1's min/max climb issued ~180 per leaf.  min / max are
+// exact and order independent, so the boxes are the oracle's bit for bit.  Scratch per node: 6 box words + depth + arrival counter = 8
+// words (three 64-bit pairs and two words), zero-initialised.
 __global__ void k_refit(const rt_bvh_node *__restrict__ nodes, const uint32_t *__restrict__ parents, uint32_t n,
                         uint32_t *__restrict__ scratch, uint32_t *__restrict__ max_depth)
 {
@@ -246,33 +212,23 @@ __global__ void k_refit(const rt_bvh_node *__restrict__ nodes, const uint32_t *_
     const rt_bvh_node nd = nodes[n - 1 + k];
     float lo[3] = {nd.bmin[0], nd.bmin[1], nd.bmin[2]}, hi[3] = {nd.bmax[0], nd.bmax[1], nd.bmax[2]};
     uint32_t depth = 0, cur = n - 1 + k;
-    auto pack = [](uint32_t a, uint32_t b) { return (uint64_t)a | ((uint64_t)b << 32); };
     for (;;) {
         const uint32_t parent = parents[cur];
         if (parent == 0xFFFFFFFFu) { atomicMax(max_depth, depth); return; }       // cur is the root
         // publish this node (leaves too: the sibling's climber reads them the same way), then arrive
         uint64_t *mine = reinterpret_cast<uint64_t *>(scratch + (size_t)cur * 8);
-        __hip_atomic_store(&mine[0], pack(__float_as_uint(lo[0]), __float_as_uint(lo[1])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&mine[1], pack(__float_as_uint(lo[2]), __float_as_uint(hi[0])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&mine[2], pack(__float_as_uint(hi[1]), __float_as_uint(hi[2])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        climb::publish(&mine[0], climb::pair(__float_as_uint(lo[0]), __float_as_uint(lo[1])));
+        climb::publish(&mine[1], climb::pair(__float_as_uint(lo[2]), __float_as_uint(hi[0])));
+        climb::publish(&mine[2], climb::pair(__float_as_uint(hi[1]), __float_as_uint(hi[2])));
         // (word 7 of a node is its arrival counter: the depth is published as a 32-bit store so that it is left alone)
-        __hip_atomic_store(scratch + (size_t)cur * 8 + 6, depth, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // every store must have been ACKNOWLEDGED before the arrival is counted; inline asm, because the compiler may drop a
-        // wait it believes redundant (MI355X_MICROARCH.md, "Compiler hazard")
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // (a relaxed memory-side atomic: the ordering it needs is made by hand -- stores acknowledged above, sc1 loads below --
-        // and the two signal fences keep the COMPILER from moving any of them across it: ADVICE r2)
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        const uint32_t arrived = __hip_atomic_fetch_add(&scratch[(size_t)parent * 8 + 7], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        if (arrived == 0u) return;                       // the sibling's climber will take over from here
+        climb::publish(scratch + (size_t)cur * 8 + 6, depth);
+        climb::wait_acknowledged();
+        if (climb::arrive(&scratch[(size_t)parent * 8 + 7]) == 0u) return;       // the sibling's climber will take over from here
         const rt_bvh_node pn = nodes[parent];
         const uint32_t sib = pn.left == cur ? pn.right : pn.left;
         const uint64_t *other = reinterpret_cast<const uint64_t *>(scratch + (size_t)sib * 8);
-        const uint64_t o0 = __hip_atomic_load(&other[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint64_t o1 = __hip_atomic_load(&other[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint64_t o2 = __hip_atomic_load(&other[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t od = __hip_atomic_load(scratch + (size_t)sib * 8 + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t o0 = climb::load(&other[0]), o1 = climb::load(&other[1]), o2 = climb::load(&other[2]);
+        const uint32_t od = climb::load(scratch + (size_t)sib * 8 + 6);
         lo[0] = fminf(lo[0], __uint_as_float((uint32_t)o0));
         lo[1] = fminf(lo[1], __uint_as_float((uint32_t)(o0 >> 32)));
         lo[2] = fminf(lo[2], __uint_as_float((uint32_t)o1));
@@ -307,20 +263,14 @@ __global__ void k_refit_decode(const uint32_t *__restrict__ scratch, rt_bvh_node
     }
 }
 
-__global__ void k_gather_tris(const uint64_t *__restrict__ keys, const rt_vertex *__restrict__ verts,
-                              const uint32_t *__restrict__ idx, uint32_t n, TriRec *__restrict__ tris)
+__global__ void k_gather_tris(const uint64_t *__restrict__ keys, const rt_vertex *__restrict__ verts, const uint32_t *__restrict__ idx, uint32_t n, TriRec *__restrict__ tris)
 {
     uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     uint32_t prim = (uint32_t)(keys[k] & 0xFFFFFFFFull);
-    rt_float3 p0 = verts[idx[3 * prim + 0]].position;
-    rt_float3 p1 = verts[idx[3 * prim + 1]].position;
-    rt_float3 p2 = verts[idx[3 * prim + 2]].position;
-    TriRec t;
-    t.a = make_float4(p0.x, p0.y, p0.z, p1.x);
-    t.b = make_float4(p1.y, p1.z, p2.x, p2.y);
-    t.c = make_float4(p2.z, __uint_as_float(prim), 0.0f, 0.0f);
-    tris[k] = t;
+    float p[3][3];
+    tri_positions(verts, idx, prim, p);
+    tris[k] = tri_record(p, prim, 0u);
 }
 
 // the vertex normals of every primitive, gathered once per build into one record per primitive (shading reads them per hit)
@@ -348,13 +298,6 @@ __global__ void k_sum64(const uint32_t *__restrict__ v, uint32_t n, unsigned lon
 }
 
 // ---- split references (rt_refs.h): count the pieces of every triangle, then (after a scan) write their boxes ----
-__device__ __forceinline__ void ref_load_tri(const rt_vertex *__restrict__ verts, const uint32_t *__restrict__ idx, uint32_t i, float p[3][3])
-{
-    for (int k = 0; k < 3; k++) {
-        const rt_float3 v = verts[idx[3 * i + k]].position;
-        p[k][0] = v.x; p[k][1] = v.y; p[k][2] = v.z;
-    }
-}
 __device__ __forceinline__ float ref_min_len(const float *__restrict__ bounds)
 {
     const float ex = bounds[3] - bounds[0], ey = bounds[4] - bounds[1], ez = bounds[5] - bounds[2];
@@ -367,7 +310,7 @@ __global__ void k_ref_count(const rt_vertex *__restrict__ verts, const uint32_t 
     if (i > n) return;
     if (i == n) { count[n] = 0u; return; }           // (the scan's last element: the total)
     float p[3][3];
-    ref_load_tri(verts, idx, i, p);
+    tri_positions(verts, idx, i, p);
     int axis;
     count[i] = rtd::ref_pieces(p, ref_min_len(bounds), axis);
 }
@@ -377,14 +320,12 @@ __global__ void k_ref_emit(const rt_vertex *__restrict__ verts, const uint32_t *
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float p[3][3];
-    ref_load_tri(verts, idx, i, p);
+    tri_positions(verts, idx, i, p);
     const uint32_t first = off[i], k = off[i + 1] - first;
-    if (k == 1u) {                                     // not split: its own box (what k_tri_boxes wrote: exact min / max)
+    if (k == 1u) {                                     // not split: its own box
+        const Box6 own = tri_box(p);
         float *b = ref_boxes + 6 * (size_t)first;
-        for (int q = 0; q < 3; q++) {
-            b[q] = fminf(fminf(p[0][q], p[1][q]), p[2][q]);
-            b[3 + q] = fmaxf(fmaxf(p[0][q], p[1][q]), p[2][q]);
-        }
+        for (int q = 0; q < 3; q++) { b[q] = own.lo[q]; b[3 + q] = own.hi[q]; }
         ref_prim[first] = i;
         return;
     }
@@ -403,13 +344,7 @@ __global__ void k_ref_keys(const float *__restrict__ ref_boxes, uint32_t m, cons
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const float *b = ref_boxes + 6 * (size_t)i;
-    uint32_t code = 0;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float ctr = (b[c] + b[3 + c]) * 0.5f;
-        code |= expand10(quant10(ctr, bounds[c], bounds[3 + c] - bounds[c])) << (2 - c);
-    }
-    keys[i] = ((uint64_t)code << 32) | i;
+    keys[i] = ((uint64_t)morton30(b, b + 3, bounds) << 32) | i;
 }
 __global__ void k_ref_leaves(const uint64_t *__restrict__ keys, uint32_t m, const float *__restrict__ ref_boxes, const uint32_t *__restrict__ ref_prim,
                              float *__restrict__ leaf_box, uint32_t *__restrict__ leaf_prim)
@@ -441,6 +376,21 @@ void carve_blas(Carver &c, uint32_t n, BlasTemps &t)
     t.ref_off = c.take<uint32_t>((size_t)n + 1);
     t.scan_bytes = (size_t)1 << 20;
     t.scan = c.take<char>(t.scan_bytes);
+}
+// A rocPRIM call with its temporary storage: call(storage, bytes) asks for the size when storage is null and queues the work otherwise.
+// tmp adopts the arena's slice (nullptr: none) or, if the library asks for more, becomes an allocation of its own: the caller says where it lives.
+template <class Call> int rocprim_with_temp(DevBuf &tmp, void *slice, size_t slice_bytes, Call call)
+{
+    size_t bytes = 0;
+    HIP_TRY(call(nullptr, bytes));
+    tmp.adopt(slice, slice_bytes);
+    RT_TRY(tmp.reserve(bytes));
+    HIP_TRY(call(tmp.p, bytes));
+    return RT_OK;
+}
+int sort_by_morton_code(DevBuf &tmp, void *slice, size_t slice_bytes, uint64_t *keys, uint64_t *sorted, uint32_t n, hipStream_t st)
+{
+    return rocprim_with_temp(tmp, slice, slice_bytes, [&](void *storage, size_t &bytes) { return rocprim::radix_sort_keys(storage, bytes, keys, sorted, n, 32, 62, st); });
 }
 void drop_build_arena_if_large(rt_context *ctx)
 {
@@ -481,12 +431,8 @@ int lbvh_from_boxes(rt_context *ctx, BvhDev &bv, uint32_t n, const LbvhTemps &t)
     k_morton<<<grid_for(n, B), B, 0, st>>>(t.boxes, n, t.bounds, t.keys);
     // keys are (30-bit Morton code << 32) | index with the indices ascending on input: a STABLE sort of the code bits alone
     // gives the order of the full 64-bit keys (the oracle's) with half the radix passes
-    size_t sort_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, t.keys, bv.keys.as<uint64_t>(), n, 32, 62, st));
-    DevBuf sort_tmp;             // the arena's slice, or an allocation of its own when the library asks for more
-    sort_tmp.adopt(t.sort, t.sort_bytes);
-    RT_TRY(sort_tmp.reserve(sort_bytes));
-    HIP_TRY(rocprim::radix_sort_keys(sort_tmp.p, sort_bytes, t.keys, bv.keys.as<uint64_t>(), n, 32, 62, st));
+    DevBuf sort_tmp;
+    RT_TRY(sort_by_morton_code(sort_tmp, t.sort, t.sort_bytes, t.keys, bv.keys.as<uint64_t>(), n, st));
 
     rt_bvh_node *nodes = bv.nodes.as<rt_bvh_node>();
     uint32_t *parents = bv.parents.as<uint32_t>();
@@ -579,12 +525,10 @@ int blas_split_refs(rt_context *ctx, rt_model *m, const BlasTemps &t, RefLeaves 
     m->n_recs = n;
     m->rec_boxes.release(); m->ref_off.release(); m->ref_boxes.release();      // (a rebuild starts from a model without references)
     k_ref_count<<<grid_for(n + 1, BB), BB, 0, st>>>(m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), n, t.bounds, t.ref_count);
-    size_t scan_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, t.ref_count, t.ref_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-    DevBuf scan_tmp;             // as lbvh_from_boxes' sort_tmp
-    scan_tmp.adopt(t.scan, t.scan_bytes);
-    RT_TRY(scan_tmp.reserve(scan_bytes));
-    HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, t.ref_count, t.ref_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+    DevBuf scan_tmp;
+    RT_TRY(rocprim_with_temp(scan_tmp, t.scan, t.scan_bytes, [&](void *storage, size_t &bytes) {
+        return rocprim::exclusive_scan(storage, bytes, t.ref_count, t.ref_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st);
+    }));
     r.n_refs = n;
     uint32_t *back = ctx->pinned ? ctx->pinned : &r.n_refs;
     HIP_TRY(hipMemcpyAsync(back, t.ref_off + n, 4, hipMemcpyDeviceToHost, st));
@@ -624,10 +568,7 @@ int blas_ref_leaves(rt_context *ctx, rt_model *m, const BlasTemps &t, RefLeaves 
     RT_TRY(r.leaf_box.reserve(24 * (size_t)n_refs));
     RT_TRY(r.leaf_prim.reserve(4 * (size_t)n_refs));
     k_ref_keys<<<grid_for(n_refs, BB), BB, 0, st>>>(m->ref_boxes.as<float>(), n_refs, t.bounds, r.keys.as<uint64_t>());
-    size_t sort_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, r.keys.as<uint64_t>(), r.sorted.as<uint64_t>(), n_refs, 32, 62, st));
-    RT_TRY(r.sort_tmp.reserve(sort_bytes));
-    HIP_TRY(rocprim::radix_sort_keys(r.sort_tmp.p, sort_bytes, r.keys.as<uint64_t>(), r.sorted.as<uint64_t>(), n_refs, 32, 62, st));
+    RT_TRY(sort_by_morton_code(r.sort_tmp, nullptr, 0, r.keys.as<uint64_t>(), r.sorted.as<uint64_t>(), n_refs, st));
     k_ref_leaves<<<grid_for(n_refs, BB), BB, 0, st>>>(r.sorted.as<uint64_t>(), n_refs, m->ref_boxes.as<float>(), r.prim.as<uint32_t>(),
                                                     r.leaf_box.as<float>(), r.leaf_prim.as<uint32_t>());
     return RT_OK;
@@ -641,8 +582,8 @@ int blas_layout(rt_context *ctx, rt_model *m, const RefLeaves &r, PhaseClock &cl
     const uint32_t n = m->n_tris;
     bool ploc_done = false;
     if (ctx->use_ploc) {
-        const int rc = r.split_layout ? rt_build_ploc_layout(ctx, m, &ploc_done, r.n_refs, r.leaf_box.as<float>(), r.leaf_prim.as<uint32_t>())
-                                      : rt_build_ploc_layout(ctx, m, &ploc_done);
+        const PlocLeaves leaves = r.split_layout ? PlocLeaves{r.n_refs, r.leaf_box.as<float>(), r.leaf_prim.as<uint32_t>()} : PlocLeaves{};
+        const int rc = rt_build_ploc_layout(ctx, m, &ploc_done, leaves);
         // PLOC's nearest-neighbour rounds make no progress on boxes whose surface is not finite (NaN / inf vertices,
         // extents that overflow): such a mesh keeps the LBVH as its traversal layout.  rt_build_ploc_layout may give up AFTER k_ploc_tris
         // had rewritten m->tris in PLOC order (the collapse that follows it can refuse a tree too), so the records are gathered again

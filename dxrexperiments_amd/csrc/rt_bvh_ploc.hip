@@ -15,7 +15,7 @@
 // Output: triangles re-gathered in the depth-first order of the new tree, so that every subtree is a
 // contiguous triangle range and subtrees of <= leaf_max triangles collapse to leaves, and the binary
 // tree itself, which rt_bvh_wide.hip collapses into the four-wide 64-B nodes the traversal walks.
-#include "rt_internal.h"
+#include "rt_bvh_tree.h"
 
 #include "rt_level_scan.h"
 
@@ -37,16 +37,6 @@ constexpr int PLOC_RADIUS = RT_PLOC_RADIUS;
 constexpr int PLOC_TAIL_RADIUS = RT_PLOC_TAIL_RADIUS;       // window of the single-workgroup rounds at the top of the tree
 constexpr unsigned PB = 256;
 
-struct Box6 { float lo[3]; float hi[3]; };
-
-__device__ __forceinline__ float merged_area(const Box6 &a, const Box6 &b)
-{
-    const float dx = fmaxf(a.hi[0], b.hi[0]) - fminf(a.lo[0], b.lo[0]);
-    const float dy = fmaxf(a.hi[1], b.hi[1]) - fminf(a.lo[1], b.lo[1]);
-    const float dz = fmaxf(a.hi[2], b.hi[2]) - fminf(a.lo[2], b.lo[2]);
-    return dx * dy + dy * dz + dz * dx;
-}
-
 // where the clustering stands before round r (device memory, one entry per round of a batch)
 struct PlocRound { uint32_t c, next_node, cur, error; };
 constexpr uint32_t PLOC_TAIL = 2048, TAIL_BLOCK = 1024, PLOC_MAX_BATCH = 64;   // (tail at 4096: 0.20 ms in the one workgroup; a multi-kernel round costs ~12 us)
@@ -59,9 +49,46 @@ struct PlocArrays {
     PlocRound *round;                  // PLOC_MAX_BATCH + 1 entries
     uint32_t *cl_node[2];
     Box6 *cl_box[2];
-    uint32_t *left, *right, *size, *parent;
-    Box6 *node_box;
+    BinTree tree;                      // what the rounds build (its offsets: k_ploc_offsets, once the tree stands)
 };
+
+// ---- the steps of a round, each written once: taken by the multi-kernel rounds (k_ploc_pair, k_ploc_apply) and by the tail (k_ploc_tail) ----
+// The nearest neighbour of cluster i of c inside the window of R either side: smallest merged area, ties -> lower index (itself, if it has
+// no neighbour).  box_at(j): the box of cluster j.
+template <int R, class BoxAt> __device__ __forceinline__ uint32_t ploc_nearest(int i, int c, BoxAt box_at)
+{
+    const Box6 me = box_at(i);
+    float best = __uint_as_float(0x7f800000u);
+    uint32_t arg = (uint32_t)i;
+    for (int d = -R; d <= R; d++) {
+        const int j = i + d;
+        if (d == 0 || j < 0 || j >= c) continue;
+        const float ar = merged_area(me, box_at(j));
+        if (ar < best) { best = ar; arg = (uint32_t)j; }
+    }
+    return arg;
+}
+// What becomes of cluster i whose nearest neighbour is j (nn_at(j): j's own): of a mutual pair the lower index creates the node and the
+// higher one disappears; every other cluster is kept as it is.
+template <class NnAt> __device__ __forceinline__ void ploc_flags(uint32_t i, uint32_t j, NnAt nn_at, uint32_t &kept, uint32_t &created)
+{
+    const bool mutual = j != i && nn_at(j) == i;
+    created = (mutual && i < j) ? 1u : 0u;
+    kept = (mutual && i > j) ? 0u : 1u;
+}
+// Node m from the clusters with the ids na, nb and the boxes ba, bb: its children, box and size, the three parents; returns the box.
+// size_sum(): the leaves below the two (the rounds read them from the tree, the tail keeps them in LDS), asked for where the rounds always
+// read them: behind the stores of the children and the box.
+template <class SizeSum> __device__ __forceinline__ Box6 ploc_merge(const BinTree &t, uint32_t m, uint32_t na, uint32_t nb, const Box6 &ba, const Box6 &bb,
+                                                                    SizeSum size_sum, uint32_t &size)
+{
+    const Box6 u = box_union(ba, bb);
+    t.left[m - t.n] = na; t.right[m - t.n] = nb;
+    t.box[m] = u;
+    t.size[m] = size = size_sum();
+    t.parent[na] = m; t.parent[nb] = m; t.parent[m] = 0xFFFFFFFFu;
+    return u;
+}
 
 // clusters start as the canonical leaves, in key order
 // (leaf_box6 != nullptr: the leaves are the references of a model with split triangles, rt_refs.h -- 6 floats each, in Morton order)
@@ -113,25 +140,15 @@ __global__ void __launch_bounds__(PB) k_ploc_pair(PlocArrays a, uint32_t r)
     for (int t = threadIdx.x; t < (int)PB + 2 * R; t += PB) {       // near[t] = nn of cluster base + R + t
         const int i = base + R + t;
         if (i < 0 || i >= (int)c) continue;
-        const Box6 me = tile[t + R];
-        float best = __uint_as_float(0x7f800000u);
-        uint32_t arg = (uint32_t)i;
-        for (int d = -R; d <= R; d++) {
-            const int j = i + d;
-            if (d == 0 || j < 0 || j >= (int)c) continue;
-            const float ar = merged_area(me, tile[t + R + d]);
-            if (ar < best) { best = ar; arg = (uint32_t)j; }
-        }
-        near[t] = arg;
+        near[t] = ploc_nearest<R>(i, (int)c, [&](int j) -> const Box6 & { return tile[j - base]; });
     }
     __syncthreads();
     const uint32_t i = blockIdx.x * PB + threadIdx.x;
     uint32_t packed = 0;                                // kept | created << 16
     if (i < c) {
         const uint32_t j = near[threadIdx.x + R];
-        const bool mutual = j != i && near[(int)j - base - R] == i;
-        const uint32_t mg = (mutual && i < j) ? 1u : 0u;        // the lower index of a mutual pair creates the node
-        const uint32_t kp = (mutual && i > j) ? 0u : 1u;        // the higher index disappears
+        uint32_t kp, mg;
+        ploc_flags(i, j, [&](uint32_t o) { return near[(int)o - base - R]; }, kp, mg);
         a.nn[i] = j;
         a.flags[i] = kp | (mg << 1);
         packed = kp | (mg << 16);
@@ -151,8 +168,8 @@ __global__ void __launch_bounds__(PB) k_ploc_pair(PlocArrays a, uint32_t r)
 }
 
 // Second half: every surviving cluster moves to its place in the other cluster array; the lower index of a mutual pair
-// becomes the new node (same arithmetic and numbering as the tail kernel below).
-__global__ void __launch_bounds__(PB) k_ploc_apply(PlocArrays a, uint32_t r, uint32_t n)
+// becomes the new node.
+__global__ void __launch_bounds__(PB) k_ploc_apply(PlocArrays a, uint32_t r)
 {
     __shared__ uint32_t lds[PB / 64];
     const PlocRound s = a.round[r];
@@ -174,16 +191,8 @@ __global__ void __launch_bounds__(PB) k_ploc_apply(PlocArrays a, uint32_t r, uin
         const uint32_t j = a.nn[i];
         const uint32_t m = s.next_node + (uint32_t)(off >> 32) + (before >> 16);
         const uint32_t na = cl_node[i], nb = cl_node[j];
-        const Box6 ba = cl_box[i], bb = cl_box[j];
-        Box6 u;
-        for (int k = 0; k < 3; k++) { u.lo[k] = fminf(ba.lo[k], bb.lo[k]); u.hi[k] = fmaxf(ba.hi[k], bb.hi[k]); }
-        a.left[m - n] = na;
-        a.right[m - n] = nb;
-        a.node_box[m] = u;
-        a.size[m] = a.size[na] + a.size[nb];
-        a.parent[na] = m;
-        a.parent[nb] = m;
-        a.parent[m] = 0xFFFFFFFFu;
+        uint32_t sz;
+        const Box6 u = ploc_merge(a.tree, m, na, nb, cl_box[i], cl_box[j], [&] { return a.tree.size[na] + a.tree.size[nb]; }, sz);
         out_node[pos] = m;
         out_box[pos] = u;
     } else {
@@ -193,9 +202,8 @@ __global__ void __launch_bounds__(PB) k_ploc_apply(PlocArrays a, uint32_t r, uin
 }
 
 // The tail of the clustering: once PLOC_TAIL or fewer clusters are left, ONE workgroup runs all the remaining rounds
-// (nearest neighbour, mutual-pair flags, the two prefix sums, merge) back to back with barriers in between -- the same
-// arithmetic and the same node numbering as the multi-kernel rounds, without ~40 rounds of launches and host round trips
-// for a handful of clusters each.  The cluster array (boxes, node ids, sizes) lives in LDS for the whole tail: 2048 x 34 B
+// (nearest neighbour, mutual-pair flags, the two prefix sums, merge: the steps above) back to back with barriers in between,
+// without ~40 rounds of launches and host round trips for a handful of clusters each.  The cluster array (boxes, node ids, sizes) lives in LDS for the whole tail: 2048 x 34 B
 // = 68 KiB of the CU's 160; the first version kept it in global memory and spent 0.36 ms of a 2.5 ms build on round trips.
 struct TailLds {
     Box6 box[PLOC_TAIL];
@@ -203,7 +211,7 @@ struct TailLds {
     uint16_t nn[PLOC_TAIL];
     uint32_t scan[TAIL_BLOCK / 64];
 };
-__global__ void __launch_bounds__(TAIL_BLOCK) k_ploc_tail(PlocArrays a, uint32_t r, uint32_t n, PlocRound *__restrict__ result)
+__global__ void __launch_bounds__(TAIL_BLOCK) k_ploc_tail(PlocArrays a, uint32_t r, PlocRound *__restrict__ result)
 {
     const PlocRound s = a.round[r];
     if (s.c > PLOC_TAIL || s.error) {                  // the batch of rounds fell short (or failed): the host decides
@@ -220,22 +228,12 @@ __global__ void __launch_bounds__(TAIL_BLOCK) k_ploc_tail(PlocArrays a, uint32_t
         const uint32_t id = a.cl_node[cur][i];
         L.box[i] = a.cl_box[cur][i];
         L.node[i] = id;
-        L.size[i] = a.size[id];
+        L.size[i] = a.tree.size[id];
     }
     __syncthreads();
     while (c > 1) {
-        for (uint32_t i = t; i < c; i += TAIL_BLOCK) {               // nearest neighbour (as k_ploc_pair)
-            const Box6 me = L.box[i];
-            float best = __uint_as_float(0x7f800000u);
-            uint32_t arg = i;
-            for (int d = -PLOC_TAIL_RADIUS; d <= PLOC_TAIL_RADIUS; d++) {
-                const int j = (int)i + d;
-                if (d == 0 || j < 0 || j >= (int)c) continue;
-                const float ar = merged_area(me, L.box[j]);
-                if (ar < best) { best = ar; arg = (uint32_t)j; }
-            }
-            L.nn[i] = (uint16_t)arg;
-        }
+        for (uint32_t i = t; i < c; i += TAIL_BLOCK)
+            L.nn[i] = (uint16_t)ploc_nearest<PLOC_TAIL_RADIUS>((int)i, (int)c, [&](int j) -> const Box6 & { return L.box[j]; });
         __syncthreads();
         // flags, PER consecutive clusters per thread, kept in registers; tallies packed kept | created << 16
         uint32_t mine = 0, keep_bits = 0, merge_bits = 0;
@@ -243,8 +241,8 @@ __global__ void __launch_bounds__(TAIL_BLOCK) k_ploc_tail(PlocArrays a, uint32_t
             const uint32_t i = t * PER + e;
             if (i >= c) break;
             const uint32_t j = L.nn[i];
-            const bool mutual = j != i && L.nn[j] == i;
-            const uint32_t mg = (mutual && i < j) ? 1u : 0u, kp = (mutual && i > j) ? 0u : 1u;
+            uint32_t kp, mg;
+            ploc_flags(i, j, [&](uint32_t o) -> uint32_t { return L.nn[o]; }, kp, mg);
             merge_bits |= mg << e;
             keep_bits |= kp << e;
             mine += kp | (mg << 16);
@@ -264,20 +262,8 @@ __global__ void __launch_bounds__(TAIL_BLOCK) k_ploc_tail(PlocArrays a, uint32_t
             out_pos[e] = k_run;
             if ((merge_bits >> e) & 1u) {
                 const uint32_t j = L.nn[i], m = next_node + m_run;
-                const uint32_t na = L.node[i], nb = L.node[j], sz = L.size[i] + L.size[j];
-                const Box6 ba = L.box[i], bb = L.box[j];
-                Box6 u;
-                for (int k = 0; k < 3; k++) { u.lo[k] = fminf(ba.lo[k], bb.lo[k]); u.hi[k] = fmaxf(ba.hi[k], bb.hi[k]); }
-                a.left[m - n] = na;
-                a.right[m - n] = nb;
-                a.node_box[m] = u;
-                a.size[m] = sz;
-                a.parent[na] = m;
-                a.parent[nb] = m;
-                a.parent[m] = 0xFFFFFFFFu;
+                out_box[e] = ploc_merge(a.tree, m, L.node[i], L.node[j], L.box[i], L.box[j], [&] { return L.size[i] + L.size[j]; }, out_size[e]);
                 out_node[e] = m;
-                out_box[e] = u;
-                out_size[e] = sz;
                 m_run++;
             } else {
                 out_node[e] = L.node[i];
@@ -304,17 +290,16 @@ __global__ void k_ploc_leaf_boxes(const Box6 *__restrict__ cl_box, uint32_t n, B
 }
 
 // depth-first offset of every node = number of leaves before it
-__global__ void k_ploc_offsets(const uint32_t *__restrict__ left, const uint32_t *__restrict__ right, const uint32_t *__restrict__ size,
-                               const uint32_t *__restrict__ parent, uint32_t n, uint32_t *__restrict__ offset)
+__global__ void k_ploc_offsets(BinTree t)
 {
-    const uint32_t id = blockIdx.x * PB + threadIdx.x;
+    const uint32_t id = blockIdx.x * PB + threadIdx.x, n = t.n;
     if (id >= 2 * n - 1) return;
     uint32_t off = 0, cur = id;
-    for (uint32_t p = parent[cur]; p != 0xFFFFFFFFu; p = parent[cur]) {
-        if (right[p - n] == cur) off += size[left[p - n]];
+    for (uint32_t p = t.parent[cur]; p != 0xFFFFFFFFu; p = t.parent[cur]) {
+        if (t.right[p - n] == cur) off += t.size[t.left[p - n]];
         cur = p;
     }
-    offset[id] = off;
+    t.offset[id] = off;
 }
 
 // (leaf_prim != nullptr: leaf k is a reference of primitive leaf_prim[k] with the box leaf_box6[k]; the record of a split triangle's reference
@@ -326,20 +311,13 @@ __global__ void k_ploc_tris(const uint64_t *__restrict__ keys, const uint32_t *_
     const uint32_t k = blockIdx.x * PB + threadIdx.x;
     if (k >= n) return;
     const uint32_t prim = leaf_prim ? leaf_prim[k] : (uint32_t)(keys[k] & 0xFFFFFFFFull);
-    const rt_float3 p0 = verts[idx[3 * prim + 0]].position;
-    const rt_float3 p1 = verts[idx[3 * prim + 1]].position;
-    const rt_float3 p2 = verts[idx[3 * prim + 2]].position;
-    TriRec t;
-    t.a = make_float4(p0.x, p0.y, p0.z, p1.x);
-    t.b = make_float4(p1.y, p1.z, p2.x, p2.y);
+    float p[3][3];
+    tri_positions(verts, idx, prim, p);
     const bool split = leaf_prim && ref_off[prim + 1] - ref_off[prim] > 1u;
-    t.c = make_float4(p2.z, __uint_as_float(prim), __uint_as_float(split ? 1u : 0u), 0.0f);
-    tris[offset[k]] = t;
+    tris[offset[k]] = tri_record(p, prim, split ? 1u : 0u);
     if (rec_boxes)
         for (int q = 0; q < 6; q++) rec_boxes[6 * (size_t)offset[k] + q] = leaf_box6[6 * (size_t)k + q];
 }
-
-inline unsigned gr(size_t n) { return (unsigned)((n + PB - 1) / PB); }
 
 // Every temporary of the build is carved out of ONE allocation, the context's build arena (hipMalloc / hipFree synchronise the
 // device and cost more than the kernels of a small build).  The cluster arrays of the rounds, up to `left`, are free once the tree
@@ -347,26 +325,24 @@ inline unsigned gr(size_t n) { return (unsigned)((n + PB - 1) / PB); }
 struct PlocTemps {
     PlocArrays pa;
     PlocRound *result;           // where a batch of rounds stopped: the entry behind pa.round's PLOC_MAX_BATCH + 1
-    uint32_t *offset;
     size_t scratch_bytes;        // from pa.cl_node[0]
 };
 void carve_ploc(Carver &c, uint32_t n, PlocTemps &t)
 {
     const size_t nn2 = 2 * (size_t)n - 1, scratch_from = c.offset;
     PlocArrays &pa = t.pa;
+    BinTree &tree = pa.tree;
     for (int k = 0; k < 2; k++) pa.cl_node[k] = c.take<uint32_t>(n);
     for (int k = 0; k < 2; k++) pa.cl_box[k] = c.take<Box6>(n);
     pa.nn = c.take<uint32_t>(n);
     pa.flags = c.take<uint32_t>(n);
-    pa.tally = c.take<uint64_t>(gr(n));
+    pa.tally = c.take<uint64_t>(grid_for(n, PB));
     (void)c.take<char>(64 * (size_t)n);          // (only widens what the collapse uses as its scratch: rt_wide_temp_bytes)
     t.scratch_bytes = c.offset - scratch_from;
-    pa.left = c.take<uint32_t>(n - 1);
-    pa.right = c.take<uint32_t>(n - 1);
-    pa.node_box = c.take<Box6>(nn2);
-    pa.size = c.take<uint32_t>(nn2);
-    pa.parent = c.take<uint32_t>(nn2);
-    t.offset = c.take<uint32_t>(nn2);
+    tree.left = c.take<uint32_t>(n - 1); tree.right = c.take<uint32_t>(n - 1);
+    tree.box = c.take<Box6>(nn2);
+    tree.size = c.take<uint32_t>(nn2); tree.parent = c.take<uint32_t>(nn2); tree.offset = c.take<uint32_t>(nn2);
+    tree.leaf_prim = nullptr; tree.n = n;      // (a BLAS)
     pa.round = c.take<PlocRound>(PLOC_MAX_BATCH + 2);
     t.result = pa.round ? pa.round + PLOC_MAX_BATCH + 1 : nullptr;
     pa.arrivals = c.take<uint32_t>(1);
@@ -385,13 +361,13 @@ size_t rt_ploc_temp_bytes(uint32_t n)
 
 // Rebuilds m->tris and m->blas.wide / root_code / fast_depth from a PLOC tree.  The canonical arrays
 // (nodes, keys, parents) are left untouched.  Returns RT_OK with *done = false for meshes too small to bother.
-int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, uint32_t n_leaves, const float *leaf_box6, const uint32_t *leaf_prim)
+int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, const PlocLeaves &leaves)
 {
-    const uint32_t n = leaf_box6 ? n_leaves : m->n_tris;          // leaves of the tree: triangles, or the references of a model with split ones
+    const float *leaf_box6 = leaves.box6;
+    const uint32_t n = leaf_box6 ? leaves.n : m->n_tris;          // leaves of the tree: triangles, or the references of a model with split ones
     *done = false;
     if (n < 2 * ctx->leaf_max + 2) return RT_OK;          // tiny meshes: the LBVH layout is as good as any
     hipStream_t st = ctx->stream;
-    const size_t nn2 = 2 * (size_t)n - 1;
     RT_TRY(ctx->build_arena.reserve(rt_ploc_temp_bytes(n)));      // normally already there (take_build_temps)
     Carver arena(ctx->build_arena.p);
     PlocTemps t;
@@ -404,8 +380,8 @@ int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, uint32_t n_le
         RT_TRY(m->tris.reserve(sizeof(TriRec) * (size_t)n));
         RT_TRY(m->rec_boxes.reserve(24 * (size_t)n));
     }
-    k_ploc_init<<<gr(n), PB, 0, st>>>(m->blas.nodes.as<rt_bvh_node>(), leaf_box6, n, pa.cl_node[0], pa.cl_box[0], pa.size, pa.parent, pa.round, pa.arrivals);
-    k_ploc_leaf_boxes<<<gr(n), PB, 0, st>>>(pa.cl_box[0], n, pa.node_box);
+    k_ploc_init<<<grid_for(n, PB), PB, 0, st>>>(m->blas.nodes.as<rt_bvh_node>(), leaf_box6, n, pa.cl_node[0], pa.cl_box[0], pa.tree.size, pa.tree.parent, pa.round, pa.arrivals);
+    k_ploc_leaf_boxes<<<grid_for(n, PB), PB, 0, st>>>(pa.cl_box[0], n, pa.tree.box);
     // Rounds are launched in batches without looking at the cluster count: every launch covers the count the batch
     // started with (workgroups past the live count leave at once), a round past the tail threshold costs two empty
     // launches, and the tail kernel closes the batch.  A round keeps ~0.76 of its clusters on the scenes measured;
@@ -417,10 +393,10 @@ int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, uint32_t n_le
         if (rounds > 0 && rounds < PLOC_MAX_BATCH) rounds++;
         if (ctx->build_batch && rounds > ctx->build_batch) rounds = ctx->build_batch;      // (tests: force short batches)
         for (uint32_t r = 0; r < rounds; r++) {
-            k_ploc_pair<<<gr(res.c), PB, 0, st>>>(pa, r);
-            k_ploc_apply<<<gr(res.c), PB, 0, st>>>(pa, r, n);
+            k_ploc_pair<<<grid_for(res.c, PB), PB, 0, st>>>(pa, r);
+            k_ploc_apply<<<grid_for(res.c, PB), PB, 0, st>>>(pa, r);
         }
-        k_ploc_tail<<<1, TAIL_BLOCK, sizeof(TailLds), st>>>(pa, rounds, n, t.result);
+        k_ploc_tail<<<1, TAIL_BLOCK, sizeof(TailLds), st>>>(pa, rounds, t.result);
         PlocRound *host = ctx->pinned ? (PlocRound *)ctx->pinned : &res;      // page-locked: no staging copy
         HIP_TRY(hipMemcpyAsync(host, t.result, sizeof(PlocRound), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -439,15 +415,14 @@ int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, uint32_t n_le
         rt_set_error("PLOC did not converge (%u clusters, %u nodes)", res.c, res.next_node);
         return RT_ERR_STATE;
     }
-    k_ploc_offsets<<<gr(nn2), PB, 0, st>>>(pa.left, pa.right, pa.size, pa.parent, n, t.offset);
-    k_ploc_tris<<<gr(n), PB, 0, st>>>(m->blas.keys.as<uint64_t>(), leaf_prim, leaf_box6, leaf_box6 ? m->ref_off.as<uint32_t>() : nullptr,
-                                     m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), t.offset, n, m->tris.as<TriRec>(),
+    k_ploc_offsets<<<grid_for(2 * (size_t)n - 1, PB), PB, 0, st>>>(pa.tree);
+    k_ploc_tris<<<grid_for(n, PB), PB, 0, st>>>(m->blas.keys.as<uint64_t>(), leaves.prim, leaf_box6, leaf_box6 ? m->ref_off.as<uint32_t>() : nullptr,
+                                     m->d_verts.as<rt_vertex>(), m->d_idx.as<uint32_t>(), pa.tree.offset, n, m->tris.as<TriRec>(),
                                      leaf_box6 ? m->rec_boxes.as<float>() : nullptr);
     HIP_TRY(hipGetLastError());
     // four-wide nodes from the binary tree (root = the last node created); the cluster arrays of the rounds are free now
     // and serve as its scratch
-    RT_TRY(rt_build_wide_layout(ctx, m->blas, n, 2 * n - 2, pa.left, pa.right, pa.parent, (const float *)pa.node_box, pa.size, t.offset, nullptr,
-                                ctx->leaf_max, pa.cl_node[0], t.scratch_bytes));
+    RT_TRY(rt_build_wide_layout(ctx, m->blas, pa.tree, 2 * n - 2, ctx->leaf_max, pa.cl_node[0], t.scratch_bytes));
     if (leaf_box6) m->n_recs = n;
     *done = true;
     return RT_OK;

@@ -6,8 +6,8 @@
 // 24 plane bytes and four child codes are 64 B.  (Eight children in a 128-B record of which the traversal reads 96 B --
 // the L2 line and every fabric / HBM request are 128 B, profiles/r03/slab_fetch.txt, and the tree is a third shallower --
 // was round 3's experiment: a third fewer steps, each nearly twice the arithmetic, 29 - 40 % slower;
-// profiles/r03/wide8_experiment.md, experiments/r03_wide8.patch.  The code below is written in terms of RT_WIDE, and the
-// bounds it takes for the growth of a level -- eight times the level before -- hold for either width.)
+// profiles/r03/wide8_experiment.md, experiments/r03_wide8.patch.  The code below is written in terms of RT_WIDE; three sizes are still
+// those of the eight-wide layout and conservative for four, and each says so where it stands.)
 //
 // Collapse: breadth first, two launches per level and no host round trip inside a batch of levels (rt_level_scan.h).  A
 // frontier element is a binary node that becomes a wide node: its two children are taken, and while fewer than RT_WIDE, the
@@ -26,7 +26,7 @@
 // candidate the canonical definition accepts.  An axis that cannot be quantised at all (non-finite or overflowing
 // extents: huge instance boxes, NaN / inf vertices) gets an infinite scale and q = 0 planes: the decoded planes are
 // NaN, which every slab test here ignores, i.e. that axis never culls -- slower, never wrong.
-#include "rt_internal.h"
+#include "rt_bvh_tree.h"
 
 #include "rt_level_scan.h"
 
@@ -39,14 +39,6 @@ constexpr unsigned WB = 256;
 constexpr uint32_t NO_KID = 0xFFFFFFFFu;
 constexpr uint32_t RT_WIDE_MAX_LEVELS = 254;            // of wide nodes; a collapsed level spans one to two binary levels
 
-struct Box6 { float lo[3]; float hi[3]; };
-
-__device__ __forceinline__ float box_area(const Box6 &b)
-{
-    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-    return dx * dy + dy * dz + dz * dx;
-}
-
 // The surface-area-optimal collapse (Ylitie, Karras, Laine 2017, section 3.2), one record per internal binary node:
 //   cost[i-1], i = 1 .. RT_WIDE: the cheapest way to represent the subtree as a forest of at most i roots (a root is a
 //                                leaf or a wide node), in units of (half) surface area;
@@ -54,16 +46,14 @@ __device__ __forceinline__ float box_area(const Box6 &b)
 //                                and i - k from the right;
 //   spread:     the k of the best split of ALL RT_WIDE slots among the two children (what a wide node made of this
 //                                binary node does with its slots).
+// (conservative: eight costs and picks, of which RT_WIDE = 4 are used -- the eight-wide layout's record, six published words; kept as measured)
 struct SahRecord { float cost[8]; uint8_t pick[8]; uint32_t spread; uint32_t pad; };      // 48 B
-static_assert(sizeof(SahRecord) == 48, "SahRecord layout");
+static_assert(sizeof(SahRecord) == 48 && RT_WIDE <= 8 && RT_WIDE % 2 == 0, "SahRecord layout");
 
-struct TreeView {
-    const uint32_t *left, *right;      // indexed by id - n
-    const Box6 *box;                   // indexed by id
-    const uint32_t *size, *offset;     // indexed by id
-    const uint32_t *leaf_prim;         // TLAS: instance of leaf id; nullptr for a BLAS
+// the binary tree (rt_bvh_tree.h) and what only the collapse knows of it
+struct TreeView : BinTree {
     const SahRecord *sah;              // indexed by id - n; nullptr: the area-greedy collapse
-    uint32_t n, leaf_max;
+    uint32_t leaf_max;
     __device__ bool may_be_leaf(uint32_t id) const { return id < n || (!leaf_prim && size[id] <= leaf_max); }
     __device__ bool is_leaf(uint32_t id) const
     {
@@ -151,31 +141,24 @@ __device__ __forceinline__ uint32_t expand_node(const TreeView &t, uint32_t b, u
     return cnt;
 }
 
-// The bottom-up pass of the SAH collapse: a thread starts at every leaf and climbs; at a parent the first arriver stops,
-// the second fills the parent's record from its children's (the scheme of k_refit, rt_bvh_build.hip: records are published
-// with agent-scope stores that are waited for before the arrival is counted, and read with agent-scope loads -- the per-XCD
-// L2s are not coherent).  leaf_cost = cost of testing one primitive (a TLAS: of entering one instance).
+// The bottom-up pass of the SAH collapse: the climb of rt_bvh_tree.h ("the ordering of a bottom-up climb"), in the shape arrive, then
+// publish.  At a parent the first arriver stops; the second fills the parent's record from its children's, publishes it and waits for the
+// acknowledgement before it arrives at the next parent.  c_prim = cost of testing one primitive (a TLAS: of entering one instance).
 __device__ __forceinline__ float leaf_sah(const TreeView &t, uint32_t id, float c_prim)
 {
     return box_area(t.box[id]) * c_prim * (float)(t.leaf_prim ? 1u : t.size[id]);
 }
 
-__global__ void __launch_bounds__(WB) k_wide_sah(TreeView t, const uint32_t *__restrict__ parent, SahRecord *__restrict__ rec, uint32_t *__restrict__ arrive,
-                                                 float c_node, float c_prim)
+__global__ void __launch_bounds__(WB) k_wide_sah(TreeView t, SahRecord *__restrict__ rec, uint32_t *__restrict__ arrive, float c_node, float c_prim)
 {
     const uint32_t leaf = blockIdx.x * WB + threadIdx.x;
     if (leaf >= t.n) return;
     uint32_t cur = leaf;
     const float inf = __builtin_inff();
     for (;;) {
-        const uint32_t p = parent[cur];
+        const uint32_t p = t.parent[cur];
         if (p == 0xFFFFFFFFu) return;                       // cur is the root: its record is complete
-        // (a relaxed memory-side atomic: what it orders is done by hand -- the stores above have been acknowledged (s_waitcnt), the
-        // loads below bypass the local L2 -- and the signal fences keep the compiler from moving either across it)
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        const uint32_t arrived = __hip_atomic_fetch_add(&arrive[p - t.n], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        if (arrived == 0u) return;                          // the sibling's climber takes over
+        if (climb::arrive(&arrive[p - t.n]) == 0u) return;  // the sibling's climber takes over
         // both children are complete: cost tables of the two (a single primitive costs its leaf whatever the budget)
         float cl[RT_WIDE], cr[RT_WIDE];
         const uint32_t kids[2] = {t.left[p - t.n], t.right[p - t.n]};
@@ -188,7 +171,7 @@ __global__ void __launch_bounds__(WB) k_wide_sah(TreeView t, const uint32_t *__r
             } else {
                 const uint64_t *w = reinterpret_cast<const uint64_t *>(rec[id - t.n].cost);
                 for (int i = 0; i < RT_WIDE / 2; i++) {
-                    const uint64_t v = __hip_atomic_load(&w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const uint64_t v = climb::load(&w[i]);
                     c[2 * i] = __uint_as_float((uint32_t)v); c[2 * i + 1] = __uint_as_float((uint32_t)(v >> 32));
                 }
             }
@@ -219,13 +202,12 @@ __global__ void __launch_bounds__(WB) k_wide_sah(TreeView t, const uint32_t *__r
         // publish, wait for the acknowledgement, go on to the parent
         SahRecord *mine = rec + (p - t.n);
         uint64_t *w = reinterpret_cast<uint64_t *>(mine->cost);
-        for (int i = 0; i < 4; i++)
-            __hip_atomic_store(&w[i], (uint64_t)__float_as_uint(cost[2 * i]) | ((uint64_t)__float_as_uint(cost[2 * i + 1]) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = 0; i < 4; i++) climb::publish(&w[i], climb::pair(__float_as_uint(cost[2 * i]), __float_as_uint(cost[2 * i + 1])));
         uint64_t pk = 0;
         for (int i = 0; i < 8; i++) pk |= (uint64_t)(pick[i] & 0xffu) << (8 * i);
-        __hip_atomic_store(&w[4], pk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&w[5], (uint64_t)spread_all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        climb::publish(&w[4], pk);
+        climb::publish(&w[5], (uint64_t)spread_all);
+        climb::wait_acknowledged();
         cur = p;
     }
 }
@@ -390,10 +372,11 @@ __global__ void __launch_bounds__(WB) k_wide_emit(TreeView t, const uint32_t *__
 }
 
 // The top of the tree in ONE workgroup: while a level has at most TOPW nodes, expand, number and emit it between two
-// barriers -- a level is ~6 dependent loads whatever its size, and as two launches each it cost 27 us.  Levels 0 .. 4
-// (8^2 = 64 nodes) are certain to be handled here; the per-level launches start behind them and skip whatever else this
-// kernel got to (ws->done).  (256 threads: the emit code wants 156 VGPRs, a 1024-thread workgroup would spill.)
-constexpr uint32_t TOPW = 256, TOP_SURE = 3;            // levels 0 .. TOP_SURE-1 have at most 8^l <= TOPW nodes
+// barriers -- a level is ~6 dependent loads whatever its size, and as two launches each it cost 27 us.  Level l has at most
+// RT_WIDE^l nodes, so levels 0 .. TOP_SURE-1 (at most 4^2 = 16 nodes) are certain to be handled here; the per-level launches start
+// behind them and skip whatever else this kernel got to (ws->done).  (256 threads: the emit code wants 156 VGPRs, 1024 would spill.)
+// (TOP_SURE conservative: RT_WIDE^4 = 256 = TOPW would allow 5 -- 3 is what 8^2 <= TOPW allowed the eight-wide layout; kept as measured)
+constexpr uint32_t TOPW = 256, TOP_SURE = 3;
 __global__ void __launch_bounds__(TOPW) k_wide_top(TreeView t, uint32_t *__restrict__ frontier0, uint32_t *__restrict__ frontier1,
                                                     WideState *__restrict__ ws, uint32_t root, uint32_t fcap, WNode *__restrict__ out)
 {
@@ -432,38 +415,30 @@ __global__ void __launch_bounds__(TOPW) k_wide_top(TreeView t, uint32_t *__restr
 }
 
 // canonical LBVH (rt_bvh_node[2n-1] + leaf ranges) -> cluster numbering: leaf k -> id k, internal c -> id n + c
-__global__ void __launch_bounds__(WB) k_lbvh_to_tree(const rt_bvh_node *__restrict__ nodes, const uint2 *__restrict__ ranges, uint32_t n,
-                                                     uint32_t *__restrict__ left, uint32_t *__restrict__ right, Box6 *__restrict__ box,
-                                                     uint32_t *__restrict__ size, uint32_t *__restrict__ offset, uint32_t *__restrict__ leaf_prim,
-                                                     uint32_t *__restrict__ parent)
+__global__ void __launch_bounds__(WB) k_lbvh_to_tree(const rt_bvh_node *__restrict__ nodes, const uint2 *__restrict__ ranges, BinTree t)
 {
-    const uint32_t c = blockIdx.x * WB + threadIdx.x;
+    const uint32_t c = blockIdx.x * WB + threadIdx.x, n = t.n;
     if (c >= 2 * n - 1) return;
     const rt_bvh_node nd = nodes[c];
     const bool leaf = c >= n - 1;
     const uint32_t id = leaf ? c - (n - 1) : n + c;
     Box6 b;
     for (int k = 0; k < 3; k++) { b.lo[k] = nd.bmin[k]; b.hi[k] = nd.bmax[k]; }
-    box[id] = b;
+    t.box[id] = b;
     if (leaf) {
-        size[id] = 1;
-        offset[id] = id;
-        leaf_prim[id] = nd.left;
+        t.size[id] = 1; t.offset[id] = id;
+        t.leaf_prim[id] = nd.left;
     } else {
         const uint2 r = ranges[c];
-        size[id] = r.y - r.x + 1;
-        offset[id] = r.x;
+        t.size[id] = r.y - r.x + 1; t.offset[id] = r.x;
         const uint32_t l = nd.left >= n - 1 ? nd.left - (n - 1) : n + nd.left;
         const uint32_t r2 = nd.right >= n - 1 ? nd.right - (n - 1) : n + nd.right;
-        left[c] = l;
-        right[c] = r2;
-        parent[l] = id;
-        parent[r2] = id;
-        if (c == 0) parent[id] = 0xFFFFFFFFu;
+        t.left[c] = l; t.right[c] = r2;
+        t.parent[l] = id; t.parent[r2] = id;
+        if (c == 0) t.parent[id] = 0xFFFFFFFFu;
     }
 }
 
-inline unsigned gr(size_t n) { return (unsigned)((n + WB - 1) / WB); }
 // scratch of the collapse: two frontiers, the children of a frontier, one tally per workgroup of a level, the level table, and (option
 // wide_sah) the cost records with their arrival counters
 struct WideTemps {
@@ -478,7 +453,7 @@ void carve_wide(Carver &c, uint32_t n, WideTemps &t)
     t.fcap = (size_t)n / 2 + 2;
     for (int k = 0; k < 2; k++) t.frontier[k] = c.take<uint32_t>(t.fcap);
     t.kids = c.take<uint32_t>(RT_WIDE * t.fcap);
-    t.tally = c.take<uint32_t>(gr(t.fcap));
+    t.tally = c.take<uint32_t>(grid_for(t.fcap, WB));
     t.ws = c.take<WideState>(1);
     t.sah = c.take<SahRecord>(n);
     t.arrive = c.take<uint32_t>(n);
@@ -486,23 +461,29 @@ void carve_wide(Carver &c, uint32_t n, WideTemps &t)
 
 // the canonical LBVH as a tree in cluster numbering (rt_build_wide_from_lbvh), and behind it the scratch of its collapse
 struct LbvhTreeTemps {
-    uint32_t *left, *right;
-    Box6 *box;
-    uint32_t *size, *offset, *leaf_prim, *parent;
+    BinTree tree;
     void *scratch; size_t scratch_bytes;
 };
 void carve_lbvh_tree(Carver &c, uint32_t n, LbvhTreeTemps &t)
 {
     const size_t nn2 = 2 * (size_t)n - 1;
-    t.left = c.take<uint32_t>(n - 1);
-    t.right = c.take<uint32_t>(n - 1);
-    t.box = c.take<Box6>(nn2);
-    t.size = c.take<uint32_t>(nn2);
-    t.offset = c.take<uint32_t>(nn2);
-    t.leaf_prim = c.take<uint32_t>(nn2);
-    t.parent = c.take<uint32_t>(nn2);
+    t.tree.left = c.take<uint32_t>(n - 1); t.tree.right = c.take<uint32_t>(n - 1);
+    t.tree.box = c.take<Box6>(nn2);
+    t.tree.size = c.take<uint32_t>(nn2); t.tree.offset = c.take<uint32_t>(nn2);
+    t.tree.leaf_prim = c.take<uint32_t>(nn2);
+    t.tree.parent = c.take<uint32_t>(nn2);
+    t.tree.n = n;
     t.scratch_bytes = rt_wide_temp_bytes(n);
     t.scratch = c.take<char>(t.scratch_bytes);
+}
+
+// the whole structure is one leaf of `count` primitives, the first ones: no node, and one WNode of room so that nobody holds a null array
+int wide_single_leaf(BvhDev &bv, uint32_t count)
+{
+    bv.wide_n = 0;
+    bv.root_code = ~(int)(count - 1);                  // leaf(first 0, count); a TLAS: instance 0
+    bv.fast_depth = 0;
+    return bv.wide.reserve(sizeof(WNode));
 }
 
 }  // namespace
@@ -515,23 +496,13 @@ size_t rt_wide_temp_bytes(uint32_t n)
     return sizing.offset;
 }
 
-int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, uint32_t n, uint32_t root, const uint32_t *left, const uint32_t *right, const uint32_t *parent,
-                         const float *box6, const uint32_t *size, const uint32_t *offset, const uint32_t *leaf_prim, uint32_t leaf_max,
-                         void *tmp, size_t tmp_bytes)
+int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, const BinTree &tree, uint32_t root, uint32_t leaf_max, void *tmp, size_t tmp_bytes)
 {
     hipStream_t st = ctx->stream;
-    TreeView t;
-    t.left = left; t.right = right; t.box = (const Box6 *)box6; t.size = size; t.offset = offset; t.leaf_prim = leaf_prim;
-    t.sah = nullptr;
-    t.n = n; t.leaf_max = leaf_max;
+    const uint32_t n = tree.n;
+    TreeView t{tree, nullptr, leaf_max};
     bv.wide_n = 0;
-    // the whole structure is one leaf (one primitive, or a BLAS of <= leaf_max triangles)
-    if (!leaf_prim && n <= leaf_max) {
-        bv.root_code = ~(int)(n - 1);                  // leaf(first 0, count n)
-        bv.fast_depth = 0;
-        RT_TRY(bv.wide.reserve(sizeof(WNode)));
-        return RT_OK;
-    }
+    if (!tree.leaf_prim && n <= leaf_max) return wide_single_leaf(bv, n);      // a BLAS of <= leaf_max triangles
     DevBuf own;                        // only if the caller's slice is too small
     if (rt_wide_temp_bytes(n) > tmp_bytes) { RT_TRY(own.reserve(rt_wide_temp_bytes(n))); tmp = own.p; }
     Carver scratch(tmp);
@@ -540,19 +511,21 @@ int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, uint32_t n, uint32_t root,
     const size_t fcap = w.fcap;
     uint32_t *const *frontier = w.frontier;
     RT_TRY(bv.wide.reserve(sizeof(WNode) * (size_t)(n - 1)));
-    if (ctx->wide_sah && parent) {
+    if (ctx->wide_sah) {
         // which binary nodes become wide nodes, which leaves, and how a wide node spends its slots: one bottom-up pass
         HIP_TRY(hipMemsetAsync(w.arrive, 0, 4 * (size_t)(n - 1), st));
-        k_wide_sah<<<gr(n), WB, 0, st>>>(t, parent, w.sah, w.arrive, ctx->sah_node, ctx->sah_prim);
+        k_wide_sah<<<grid_for(n, WB), WB, 0, st>>>(t, w.sah, w.arrive, ctx->sah_node, ctx->sah_prim);
         t.sah = w.sah;
     }
     k_wide_top<<<1, TOPW, 0, st>>>(t, frontier[0], frontier[1], w.ws, root, (uint32_t)fcap, bv.wide.as<WNode>());
-    // Levels are launched in batches without looking at their sizes: a level has at most eight times the nodes of the
-    // one before (and never more than fcap), a level past the end of the tree costs two empty launches.  The first
-    // batch is sized for a tree half again as deep as a balanced one; the host reads the level table after each batch.
-    // k_wide_top has certainly built levels 0 .. TOP_SURE-1 (a level has at most 8^l nodes, it takes every level of <= TOPW)
+    // Levels are launched in batches without looking at their sizes: a level has at most RT_WIDE times the nodes of the
+    // one before (and never more than fcap), a level past the end of the tree costs two empty launches.  The first batch is sized for
+    // a binary tree half again as deep as a balanced one (log8: its depth in steps of three binary levels; a collapsed level spans one
+    // to two); the host reads the level table after each batch.  k_wide_top has certainly built levels 0 .. TOP_SURE-1.
     uint32_t lvl = TOP_SURE, levels = 0, wide_n = 0;
-    uint64_t bound = 2 * TOPW;                            // upper bound of the frontier at level lvl: 8^TOP_SURE
+    // upper bound of the frontier at level lvl (conservative: RT_WIDE^TOP_SURE = 64 would do; 2 * TOPW = 8^TOP_SURE is the eight-wide
+    // layout's, and the workgroups it launches beyond a level's nodes leave at once; kept as measured)
+    uint64_t bound = 2 * TOPW;
     uint32_t log8 = 0;
     for (uint32_t m = n; m > 1; m >>= 3) log8++;
     uint32_t batch = 4 + log8 + log8 / 2;
@@ -562,7 +535,7 @@ int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, uint32_t n, uint32_t root,
     for (bool done = false; !done;) {
         const uint32_t end = lvl + batch < RT_WIDE_MAX_LEVELS + 1 ? lvl + batch : RT_WIDE_MAX_LEVELS + 1;
         for (; lvl < end; lvl++) {
-            const unsigned blocks = gr((size_t)(bound < fcap ? bound : fcap));
+            const unsigned blocks = grid_for((size_t)(bound < fcap ? bound : fcap), WB);
             k_wide_expand<<<blocks, WB, 0, st>>>(t, frontier[lvl & 1], w.ws, lvl, w.kids, w.tally, (uint32_t)fcap);
             k_wide_emit<<<blocks, WB, 0, st>>>(t, frontier[lvl & 1], w.ws, lvl, w.kids, w.tally, frontier[(lvl & 1) ^ 1], bv.wide.as<WNode>());
             bound = bound < fcap ? bound * RT_WIDE : fcap;
@@ -599,19 +572,13 @@ int rt_build_wide_from_lbvh(rt_context *ctx, BvhDev &bv, bool tlas, uint32_t lea
 {
     const uint32_t n = bv.n;
     hipStream_t st = ctx->stream;
-    if (n == 1) {                                      // one primitive: the root is its leaf (TLAS: instance 0; BLAS: triangle 0)
-        bv.wide_n = 0;
-        bv.root_code = ~(int)0;
-        bv.fast_depth = 0;
-        RT_TRY(bv.wide.reserve(sizeof(WNode)));
-        return RT_OK;
-    }
+    if (n == 1) return wide_single_leaf(bv, 1);         // one primitive has no tree to convert (TLAS: instance 0; BLAS: triangle 0)
     RT_TRY(ctx->build_arena.reserve(rt_wide_lbvh_temp_bytes(n)));
     Carver arena(ctx->build_arena.p);
     LbvhTreeTemps t;
     carve_lbvh_tree(arena, n, t);
-    k_lbvh_to_tree<<<gr(2 * (size_t)n - 1), WB, 0, st>>>(bv.nodes.as<rt_bvh_node>(), bv.ranges.as<uint2>(), n, t.left, t.right, t.box, t.size, t.offset, t.leaf_prim, t.parent);
+    k_lbvh_to_tree<<<grid_for(2 * (size_t)n - 1, WB), WB, 0, st>>>(bv.nodes.as<rt_bvh_node>(), bv.ranges.as<uint2>(), t.tree);
     HIP_TRY(hipGetLastError());
-    return rt_build_wide_layout(ctx, bv, n, n /* canonical root 0 */, t.left, t.right, t.parent, (const float *)t.box, t.size, t.offset, tlas ? t.leaf_prim : nullptr,
-                                tlas ? 1u : leaf_max, t.scratch, t.scratch_bytes);
+    if (!tlas) t.tree.leaf_prim = nullptr;             // (the leaves of a BLAS are records, not the primitives the conversion wrote there)
+    return rt_build_wide_layout(ctx, bv, t.tree, n /* canonical root 0 */, tlas ? 1u : leaf_max, t.scratch, t.scratch_bytes);
 }

@@ -496,20 +496,23 @@ void rt_scene_model_changed(rt_scene *s);
 // nothing is, `not_built`, a format that may name `who` once
 int rt_scene_require_built(const rt_scene *s, const char *who, const char *not_built);
 
-// rt_bvh_ploc.hip
-// n_leaves / leaf_box6 / leaf_prim: the leaves to cluster in Morton order -- nullptr: the canonical leaves (one per triangle); else the
-// references of a model with split triangles (rt_refs.h): 6 floats and a primitive id per leaf
-int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, uint32_t n_leaves = 0, const float *leaf_box6 = nullptr, const uint32_t *leaf_prim = nullptr);
+// rt_bvh_ploc.hip.  The leaves PLOC clusters, in Morton order.  Empty: the canonical leaves, one per triangle; otherwise the references of a
+// model with split triangles (rt_refs.h): their count, 6 floats and a primitive id per leaf
+struct PlocLeaves {
+    uint32_t n = 0;
+    const float *box6 = nullptr;
+    const uint32_t *prim = nullptr;
+};
+size_t rt_ploc_temp_bytes(uint32_t n);
+int rt_build_ploc_layout(rt_context *ctx, rt_model *m, bool *done, const PlocLeaves &leaves);
 
-// rt_bvh_wide.hip: collapses a binary tree into the four-wide traversal layout (bv.wide, wide_n, fast_depth, root_code).
-// The binary tree is given in "cluster" numbering: leaves 0..n-1 in sorted-key order, internal nodes n..2n-2;
-// left / right are indexed by id - n; parent by id (0xFFFFFFFF for the root); box6 = {lo[3], hi[3]} per id; size = leaves below; offset = leaves before (depth
-// first); leaf_prim (TLAS only) maps a leaf to its instance.  Temporaries come from the arena slice [tmp, tmp + tmp_bytes).
+// rt_bvh_wide.hip: collapses a binary tree (BinTree, rt_bvh_tree.h: the numbering is stated there) into the four-wide traversal layout
+// (bv.wide, wide_n, fast_depth, root_code); subtrees of at most leaf_max leaves become leaves (a TLAS: 1).  Temporaries come from the arena
+// slice [scratch, scratch + scratch_bytes), or from an allocation of the collapse's own if that is too small.
+struct BinTree;
 size_t rt_wide_temp_bytes(uint32_t n);
 size_t rt_wide_lbvh_temp_bytes(uint32_t n);
-int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, uint32_t n, uint32_t root, const uint32_t *left, const uint32_t *right, const uint32_t *parent,
-                         const float *box6, const uint32_t *size, const uint32_t *offset, const uint32_t *leaf_prim, uint32_t leaf_max,
-                         void *tmp, size_t tmp_bytes);
+int rt_build_wide_layout(rt_context *ctx, BvhDev &bv, const BinTree &tree, uint32_t root, uint32_t leaf_max, void *scratch, size_t scratch_bytes);
 // the same from the canonical LBVH arrays of bv (TLAS, tiny meshes, option fast_bvh=lbvh)
 int rt_build_wide_from_lbvh(rt_context *ctx, BvhDev &bv, bool tlas, uint32_t leaf_max);
 
@@ -579,9 +582,6 @@ static inline uint32_t rt_lds_stack_rows(const rt_context *ctx)
 {
     return ctx->lds_stack_rows == RT_LDS_STACK_ROWS_TEST ? RT_LDS_STACK_ROWS_TEST : RT_LDS_STACK_ROWS;
 }
-
-// rt_bvh_ploc.hip
-size_t rt_ploc_temp_bytes(uint32_t n);
 
 // rt_pipeline_render.hip: renders the frames every deferred pipeline of the context still holds (rt_pipeline_set_deferred)
 int rt_context_flush_deferred(rt_context *ctx);

@@ -1,10 +1,8 @@
 // rt_lbvh.h -- what the BLAS (rt_bvh_build.hip) and the TLAS (rt_scene.hip) share of the LBVH builder: the temporaries of a build, the
-// encoding of bounds as inline device code, and the builder's host entry points (defined in rt_bvh_build.hip).
+// encoding of bounds as inline device code, and the builder's host entry points (defined in rt_bvh_build.hip).  (Box6, grid_for: rt_bvh_tree.h)
 #pragma once
 
-#include "rt_internal.h"
-
-struct Box6 { float lo[3]; float hi[3]; };
+#include "rt_bvh_tree.h"
 
 // order-preserving float <-> uint map for atomicMin / atomicMax
 __device__ __forceinline__ uint32_t f_enc(float f)
@@ -19,8 +17,6 @@ __device__ __forceinline__ float f_dec(uint32_t k)
 }
 #define ENC_POS_INF 0xFF800000u
 #define ENC_NEG_INF 0x007FFFFFu
-
-inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 // Temporaries of an LBVH build over n primitives: slices of the context's build arena.  Every builder describes its slices once, to a
 // Carver; the arena is sized by running the same description without a base (and for the larger of the LBVH and the PLOC / collapse

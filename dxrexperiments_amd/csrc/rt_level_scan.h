@@ -7,7 +7,8 @@
 // the size of the next round to device memory, and the host launches a batch of rounds without looking.  Order is by
 // workgroup index, not by arrival, so node numbers stay run-to-run deterministic.
 //
-// gfx950 has one L2 per XCD and they are not coherent with each other: tallies are stored and loaded at agent scope and
+// The tallies cross the per-XCD L2s, which are not coherent with each other (rt_bvh_tree.h, "the ordering of a bottom-up climb", explains
+// what that asks for).  One hand-off per workgroup and launch affords the plain form of it: tallies are stored and loaded at agent scope and
 // bracketed by __threadfence() (write-back before the arrival counter is bumped, invalidate before the last workgroup reads).
 #pragma once
 #include <hip/hip_runtime.h>

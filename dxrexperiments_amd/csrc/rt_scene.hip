@@ -9,6 +9,7 @@
 
 #include "rt_attach.h"
 #include "rt_lbvh.h"
+#include "rt_level_scan.h"
 #include "rt_xform.h"
 
 namespace {
@@ -370,11 +371,7 @@ __global__ void __launch_bounds__(UPD_BLOCK) k_update_records(InstanceRec *__res
     }
     // (every lane of the block is here: the block is whole waves and nothing has returned)
     if (__ballot(chunks != 0u) == 0ull) return;        // wave-uniform
-    uint32_t incl = chunks;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t below = __shfl_up(incl, o, 64);
-        if (lane >= (unsigned)o) incl += below;
-    }
+    const uint32_t incl = rt_scan::wave_inclusive(chunks);
     const uint32_t total = __shfl(incl, 63, 64);
     uint32_t base = 0;
     if (lane == 63u) base = atomicAdd(n_items, total);

@@ -52,9 +52,10 @@ def blas_model(sc, v, i, opts):
     return M.build_blas(leaves, prims, opts.get("leaf_max", 2), canonical=cn, layout=layout, split_count=count, split_layout=split_layout, sah=sah)
 
 
-def hold_blas(capi, name, opts, doubled=0, layout=None, split=None):
+def hold_blas(capi, name, opts, doubled=0, layout=None, split=None, model_opts=None):
     """builds mesh `name` under `opts` and holds nodes, root code and records to the model; then the independent reader, with the exact number
-    of grids the quantiser had to coarsen.  Returns the model's build."""
+    of grids the quantiser had to coarsen.  model_opts: the options the model sees, where they are not the context's.  Returns the model's
+    build."""
     v, i = C.mesh(name)
     ctx = context(capi, opts)
     sc = capi.Scene(ctx)
@@ -62,7 +63,7 @@ def hold_blas(capi, name, opts, doubled=0, layout=None, split=None):
     sc.add_model(model)
     sc.build()
     what = "%s %s" % (name, opts)
-    want = blas_model(sc, v, i, opts)
+    want = blas_model(sc, v, i, opts if model_opts is None else model_opts)
     if layout is not None:
         assert want["layout"] == layout, "%s: the case is meant for the %s layout" % (what, layout)
     if split is not None:
@@ -119,6 +120,35 @@ def test_split_references(capi, name, opts):
     if opts.get("split_refs", 1):
         n_refs = want["prim"].shape[0]
         assert (n_refs < 2048) == (name == "slivers_small") and n_refs > C.mesh(name)[1].shape[0], n_refs
+
+
+def build_bytes(capi, name, opts):
+    """what the C ABI reads back of mesh `name` built under `opts`: nodes, root code, records, then the three reference arrays (or None)"""
+    v, i = C.mesh(name)
+    ctx = context(capi, opts)
+    sc = capi.Scene(ctx)
+    sc.add_model(capi.Model(ctx, v, i))
+    sc.build()
+    out = [a.tobytes() if isinstance(a, np.ndarray) else a for a in sc.wide_read(0) + sc.refs(0)]
+    sc.close()
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("name", ["fat_6", "fat_2049", "slivers_small"])
+def test_fallback_is_the_lbvh_layout(capi, name):
+    """A PLOC layout that is thrown away (fail_ploc_rounds=1: what non-finite boxes do) leaves the LBVH layout and nothing else.  PLOC had
+    rewritten the records in its own order -- for slivers_small one per REFERENCE, with their boxes -- and the fallback gathers them again,
+    one per triangle, split ones with mark 2.  Held to the model's build of the LBVH layout, and byte for byte to a build under
+    fast_bvh=lbvh.  fat_6 is the smallest mesh that runs PLOC at leaf_max 2; fat_2049 runs one multi-kernel round before the tail."""
+    split = name == "slivers_small"
+    want = hold_blas(capi, name, {"fail_ploc_rounds": 1}, layout="lbvh", split=False, model_opts={"fast_bvh": "lbvh"})
+    assert want["prim"].shape[0] == C.mesh(name)[1].shape[0] and bool((want["mark"] == 2).any()) == split, \
+        "%s: one record per triangle, the split ones (%s) marked 2" % (name, "some" if split else "none")
+    fallback, lbvh = build_bytes(capi, name, {"fail_ploc_rounds": 1}), build_bytes(capi, name, {"fast_bvh": "lbvh"})
+    assert (fallback[3] is not None) == split, "%s: the case is meant %s split triangles" % (name, "for" if split else "without")
+    for k, what in enumerate(("nodes", "root code", "records", "reference offsets", "reference boxes", "record boxes")):
+        assert fallback[k] == lbvh[k], "%s: the %s of the fallback are not those of fast_bvh=lbvh" % (name, what)
 
 
 @pytest.mark.parametrize("costs", [{}, {"sah_node": 2.5, "sah_prim": 0.25}], ids=str)

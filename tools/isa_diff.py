@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Compare two `hipcc -S --cuda-device-only` listings kernel by kernel (comments, directives and label numbers ignored).
     python tools/isa_diff.py before.s after.s
+A kernel whose parameter types were renamed or moved has another mangled name on each side: kernels left over on both sides are paired
+by their own name (`k_ploc_apply`) where that is unique, and reported as RENAMED.
 Used in round 4 to show that moving the experiments out of rt_trace_wave.h left the production kernels' ISA unchanged."""
 import re
 import sys
@@ -21,7 +23,19 @@ def kernels(path):
     return out
 
 
+def own_name(mangled):
+    """k_name of _ZN12_GLOBAL__N_16k_nameE... or _Z6k_name..."""
+    m = re.match(r'_ZN?(?:12_GLOBAL__N_1)?(\d+)', mangled)
+    return mangled[m.end():m.end() + int(m.group(1))] if m else mangled
+
+
 a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+left_a, left_b = [k for k in a if k not in b], [k for k in b if k not in a]
+for k in left_a:
+    twins = [j for j in left_b if own_name(j) == own_name(k)]
+    if len(twins) == 1 and sum(own_name(j) == own_name(k) for j in left_a) == 1:
+        print("  RENAMED %s: %s -> %s" % (own_name(k), k[:110], twins[0][:110]))
+        b[k] = b.pop(twins[0])
 same = [k for k in a if k in b and a[k] == b[k]]
 diff = [k for k in a if k in b and a[k] != b[k]]
 print("kernels: %d before, %d after; identical %d, different %d" % (len(a), len(b), len(same), len(diff)))
