@@ -104,6 +104,20 @@ SIGNATURES = {
     "rt_skeleton_get_palette_device_ptr": (_i, [_p, _pp]),
     "rt_model_set_bones_from_skeleton": (_i, [_p, _p]),
     "rt_skeleton_get_joints_device_ptr": (_i, [_p, _pp]),
+    "rt_crowd_create": (_i, [_p, _u32, _pp]),
+    "rt_crowd_destroy": (_i, [_p]),
+    "rt_crowd_get_info": (_i, [_p, _pp, _pu, _pu]),
+    "rt_crowd_set_poses": (_i, [_p, _p, _u32]),
+    "rt_crowd_set_times": (_i, [_p, _p, _p]),
+    "rt_crowd_set_blend": (_i, [_p, _u32, _p]),
+    "rt_crowd_read_pose": (_i, [_p, _u32, _u32, _p]),
+    "rt_crowd_read_joints": (_i, [_p, _u32, _u32, _p]),
+    "rt_crowd_read_palette": (_i, [_p, _u32, _u32, _p]),
+    "rt_crowd_get_joints_device_ptr": (_i, [_p, _pp]),
+    "rt_crowd_get_palette_device_ptr": (_i, [_p, _pp]),
+    "rt_model_set_bones_from_crowd": (_i, [_p, _p, _u32]),
+    "rt_scene_attach_instances_crowd": (_i, [_p, _u32, _u32, _p, _p, _p, _p]),
+    "rt_scene_get_instance_crowd_attachment": (_i, [_p, _u32, _pp, _pu, _pu]),
     "rt_model_retain": (_i, [_p]),
     "rt_model_destroy": (_i, [_p]),
     "rt_scene_create": (_i, [_p, _pp]),
@@ -528,6 +542,10 @@ class Model:
         """set_bones_device with the palette of a posed Skeleton of as many joints as the skin has bones: nothing leaves the device"""
         _check(lib().rt_model_set_bones_from_skeleton(self.h, skeleton.h))
 
+    def set_bones_from_crowd(self, crowd, actor):
+        """set_bones_device with the palette of one actor of a posed Crowd: nothing leaves the device"""
+        _check(lib().rt_model_set_bones_from_crowd(self.h, crowd.h, actor))
+
 
 class Skeleton:
     """Extension: a joint hierarchy posed on the device (include/dxr_amd.h "Posed skeletons").  parents int32[n_joints] (-1: a root, else a
@@ -673,6 +691,94 @@ class Skeleton:
         return p.value
 
 
+class Crowd:
+    """Extension: n_actors poses of one Skeleton, all made by one launch (include/dxr_amd.h "Posed skeletons", crowds).  Actor a is, bit for
+    bit, a Skeleton given the same call.  The crowd keeps its skeleton alive."""
+
+    def __init__(self, skeleton, n_actors):
+        self.ctx = skeleton.ctx
+        self.skeleton = skeleton
+        h = C.c_void_p()
+        _check(lib().rt_crowd_create(skeleton.h, n_actors, C.byref(h)))
+        self.h = h
+        self.n_actors = n_actors
+        self.n_joints = skeleton.n_joints
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().rt_crowd_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def info(self):
+        """(skeleton handle, actors, joints)"""
+        sk, a, j = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        _check(lib().rt_crowd_get_info(self.h, C.byref(sk), C.byref(a), C.byref(j)))
+        return sk.value, a.value, j.value
+
+    def set_poses(self, trs):
+        """float32[n_actors, n_joints, 10] from a host array: every actor's world matrices and palette on the device"""
+        a = _f32(trs, (-1, self.n_joints, 10))
+        if a.shape[0] != self.n_actors:
+            raise RtError(-1, "set_poses: %d actors for a crowd of %d" % (a.shape[0], self.n_actors))
+        _check(lib().rt_crowd_set_poses(self.h, _ptr(a), MEM_HOST))
+
+    def set_poses_device(self, ptr):
+        """... from n_actors x n_joints x 10 floats in device memory"""
+        _check(lib().rt_crowd_set_poses(self.h, C.c_void_p(ptr), MEM_DEVICE))
+
+    def set_times(self, clips, times):
+        """actor a samples clip clips[a] at times[a]: uint32[n_actors], float32[n_actors]; one upload, one launch"""
+        c = np.ascontiguousarray(clips, dtype=np.uint32).reshape(-1)
+        t = _f32(times, (-1,))
+        if c.shape[0] != self.n_actors or t.shape[0] != self.n_actors:
+            raise RtError(-1, "set_times: %d clips and %d times for a crowd of %d actors" % (c.shape[0], t.shape[0], self.n_actors))
+        _check(lib().rt_crowd_set_times(self.h, _ptr(c), _ptr(t)))
+
+    def set_blend(self, layers):
+        """every actor blends its own layers: a list, per actor, of equally long lists as Skeleton.set_blend takes them, or an array of
+        rtypes.SKELETON_LAYER of shape [n_actors, n_layers]"""
+        if isinstance(layers, np.ndarray) and layers.dtype == T.SKELETON_LAYER:
+            a = layers
+        else:
+            a = np.stack([Skeleton.layers(mine) for mine in layers]) if len(layers) else np.zeros((0, 0), T.SKELETON_LAYER)
+        a = np.ascontiguousarray(a)
+        if a.ndim != 2 or a.shape[0] != self.n_actors:
+            raise RtError(-1, "set_blend: layers of shape %s for a crowd of %d actors" % (a.shape, self.n_actors))
+        _check(lib().rt_crowd_set_blend(self.h, a.shape[1], _ptr(a)))
+
+    def _read(self, fn, width, first, count):
+        n = self.n_actors - first if count is None else count
+        out = np.empty((max(n, 0), self.n_joints, width), np.float32)
+        _check(fn(self.h, first, n, _ptr(out)))
+        return out
+
+    def pose(self, first=0, count=None):
+        """the local poses of actors first .. first + count - 1 (None: to the last): float32[count, n_joints, 10]"""
+        return self._read(lib().rt_crowd_read_pose, 10, first, count)
+
+    def joints(self, first=0, count=None):
+        """their world matrices W_j: float32[count, n_joints, 12]"""
+        return self._read(lib().rt_crowd_read_joints, 12, first, count)
+
+    def palette(self, first=0, count=None):
+        """their skinning matrices M_j: float32[count, n_joints, 12]"""
+        return self._read(lib().rt_crowd_read_palette, 12, first, count)
+
+    def joints_ptr(self):
+        """W in device memory, n_actors x n_joints x 12 floats, actor major"""
+        p = C.c_void_p()
+        _check(lib().rt_crowd_get_joints_device_ptr(self.h, C.byref(p)))
+        return p.value
+
+    def palette_ptr(self):
+        """the palettes in device memory, n_actors x n_joints x 12 floats, actor major"""
+        p = C.c_void_p()
+        _check(lib().rt_crowd_get_palette_device_ptr(self.h, C.byref(p)))
+        return p.value
+
+
 class Scene:
     """RtScene (libs/DXRFramework/RtScene.h:14-37)."""
 
@@ -741,6 +847,28 @@ class Scene:
         _check(lib().rt_scene_attach_instances(self.h, first, j.shape[0], skeleton.h, _ptr(j), None if x is None else _ptr(x)))
         held = self.__dict__.setdefault("_skeletons", {})
         held[skeleton.h.value] = skeleton
+
+    def attach_crowd(self, first, crowd, actors, joints, locals=None):
+        """Extension: instances first .. first + len(joints) - 1 follow joints[k] of actor actors[k] of a Crowd, as attach().  The scene keeps
+        the crowd alive."""
+        a = np.ascontiguousarray(actors, dtype=np.uint32).reshape(-1)
+        j = np.ascontiguousarray(joints, dtype=np.uint32).reshape(-1)
+        x = None if locals is None else _f32(locals, (-1, 12))
+        if a.shape[0] != j.shape[0] or (x is not None and x.shape[0] != j.shape[0]):
+            raise RtError(-1, "attach_crowd: %d actors, %d joints, %s local matrices" % (a.shape[0], j.shape[0], "no" if x is None else x.shape[0]))
+        _check(lib().rt_scene_attach_instances_crowd(self.h, first, j.shape[0], crowd.h, _ptr(a), _ptr(j), None if x is None else _ptr(x)))
+        held = self.__dict__.setdefault("_crowds", {})
+        held[crowd.h.value] = crowd
+
+    def crowd_attachment(self, i):
+        """(Crowd, actor, joint) of an instance attached to a crowd -- the Crowd object attach_crowd() was given, or its handle if this
+        wrapper never saw it -- or None"""
+        c, actor, joint = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        _check(lib().rt_scene_get_instance_crowd_attachment(self.h, i, C.byref(c), C.byref(actor), C.byref(joint)))
+        if not c.value:
+            return None
+        known = self.__dict__.get("_crowds", {}).get(c.value)
+        return (known if known is not None and known.h else c.value), actor.value, joint.value
 
     def detach(self, first, count=1):
         """Extension: the instances keep the transform their last update() or build() gave them and follow no joint any more"""

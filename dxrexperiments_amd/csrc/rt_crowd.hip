@@ -1,0 +1,364 @@
+// rt_crowd.hip -- crowds (include/dxr_amd.h "Posed skeletons", crowds): n_actors poses of ONE skeleton, all made by one launch.  A crowd
+// reads its skeleton's hierarchy, inverse binds, clips and masks where they live and owns the actors' poses, world matrices and palettes,
+// actor major; what reads a skeleton's palette or W -- the skin kernel, the scene's gather kernel -- reads an actor's slice unchanged.  The
+// arithmetic is rt_pose_device.h's, shared with rt_skeleton.hip statement for statement: actor a is, bit for bit, a skeleton given the same
+// call.  No reference counterpart, as for rt_skeleton.hip (libs/DXRFramework/RtModel.cpp:26 drops bones and node animation).
+#include <cmath>
+#include <new>
+
+#include "rt_crowd.h"
+#include "rt_internal.h"
+#include "rt_pose_device.h"
+
+namespace {
+
+using namespace rtd;
+
+// ONE block poses ONE actor, blockIdx.x: no block waits on another, and a launch of n_actors blocks fills the device where the single
+// skeleton's one block fills one CU.  Blend and pose are fused: the local pose never makes a round trip through memory between them.
+//   Phase 0, a lane per joint, strided: the actor's accumulated pose P (blend_joint; `layers` are this actor's n_layers records, read through
+//     addresses that are uniform over the block: scalar loads, and the branch on a layer's mode stays a scalar branch), written to the
+//     actor's slice of `pose`, and local_of(P) into LDS where W will stand.  n_layers == 0 (rt_crowd_set_poses): the slice holds the pose
+//     already, and L comes from it as k_skeleton_pose takes it.
+//   Phase 1: the level walk of k_skeleton_pose's LDS form, statement for statement.
+//   Phase 2: W and W o inverse_bind out to the actor's slices of `joints` and `palette`.
+// LDS is dynamic and sized by the rig (rt_crowd_lds_bytes): W component major with a row of n_joints floats per component -- the lanes of a
+// wave read consecutive words -- then the level table and the level offsets.  `pose` is read and written in place by the lane that owns the
+// joint: not __restrict__.
+template <uint32_t BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_crowd_pose(const rt_blend_layer *__restrict__ layers, uint32_t n_layers, const uint32_t *__restrict__ table,
+                                                      const uint32_t *__restrict__ level_offsets, uint32_t n_levels, uint32_t n_joints,
+                                                      const float *__restrict__ inverse_bind, float *pose, float *__restrict__ joints,
+                                                      float *__restrict__ palette)
+{
+    extern __shared__ float s_dyn[];
+    const uint32_t N = n_joints;
+    float *s_w = s_dyn;                                          // [12][N]
+    uint32_t *s_table = (uint32_t *)(s_dyn + 12u * (size_t)N);   // [N]
+    uint32_t *s_off = s_table + N;                               // [n_levels + 1] (n_levels <= N)
+    auto load = [&](uint32_t j, float M[12]) {
+#pragma unroll
+        for (int e = 0; e < 12; e++) M[e] = s_w[e * N + j];
+    };
+    auto store = [&](uint32_t j, const float M[12]) {
+#pragma unroll
+        for (int e = 0; e < 12; e++) s_w[e * N + j] = M[e];
+    };
+    const uint32_t tid = threadIdx.x, actor = blockIdx.x;
+    const rt_blend_layer *mine = layers + (size_t)actor * n_layers;
+    pose += RT_SKELETON_POSE_FLOATS * (size_t)N * actor;
+    joints += 12u * (size_t)N * actor;
+    palette += 12u * (size_t)N * actor;
+    for (uint32_t j = tid; j < n_joints; j += BLOCK) {
+        float L[12];
+        if (n_layers) {
+            float P[10];
+            blend_joint(mine, n_layers, n_joints, j, pose + RT_SKELETON_POSE_FLOATS * (size_t)j, P);
+#pragma unroll
+            for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = P[c];
+            local_of(P, L);
+        } else
+            local_of(pose + RT_SKELETON_POSE_FLOATS * (size_t)j, L);
+        store(j, L);
+        s_table[j] = table[j];
+    }
+    for (uint32_t l = tid; l <= n_levels; l += BLOCK) s_off[l] = level_offsets[l];
+    __syncthreads();
+    for (uint32_t l = 1; l < n_levels; l++) {            // (uniform: every lane passes every barrier)
+        const uint32_t begin = s_off[l], end = s_off[l + 1u];
+        for (uint32_t k = begin + tid; k < end; k += BLOCK) {
+            const uint32_t entry = s_table[k];
+            const uint32_t j = entry & 0xFFFFu, p = entry >> 16;
+            float P[12], L[12], W[12];
+            load(p, P);
+            load(j, L);
+            compose(P, L, W);
+            store(j, W);
+        }
+        __syncthreads();
+    }
+    for (uint32_t j = tid; j < n_joints; j += BLOCK) {
+        float W[12], B[12], M[12];
+        load(j, W);
+#pragma unroll
+        for (int e = 0; e < 12; e++) B[e] = inverse_bind[12u * (size_t)j + e];
+        compose(W, B, M);
+#pragma unroll
+        for (int e = 0; e < 12; e++) {
+            joints[12u * (size_t)j + e] = W[e];
+            palette[12u * (size_t)j + e] = M[e];
+        }
+    }
+}
+
+// c->pose holds every actor's held pose, and (n_layers > 0) c->layers every actor's records: ONE launch, queued on the context's stream
+int pose_crowd(rt_crowd *c, uint32_t n_layers)
+{
+    const rt_skeleton *sk = c->sk;
+    hipStream_t st = c->ctx->stream;
+    const uint32_t block = rt_crowd_block(c->n_joints);
+    const size_t lds = rt_crowd_lds_bytes(c->n_joints);
+    const rt_blend_layer *layers = c->layers.as<rt_blend_layer>();
+    const uint32_t *table = sk->table.as<uint32_t>(), *off = sk->d_level_offsets.as<uint32_t>();
+    const float *ib = sk->inverse_bind.as<float>();
+    float *pose = c->pose.as<float>(), *joints = c->joints.as<float>(), *palette = c->palette.as<float>();
+    if (block == 64u)
+        k_crowd_pose<64><<<c->n_poses, 64, lds, st>>>(layers, n_layers, table, off, sk->n_levels, c->n_joints, ib, pose, joints, palette);
+    else if (block == 128u)
+        k_crowd_pose<128><<<c->n_poses, 128, lds, st>>>(layers, n_layers, table, off, sk->n_levels, c->n_joints, ib, pose, joints, palette);
+    else
+        k_crowd_pose<256><<<c->n_poses, 256, lds, st>>>(layers, n_layers, table, off, sk->n_levels, c->n_joints, ib, pose, joints, palette);
+    HIP_TRY(hipGetLastError());
+    c->posed = true;
+    c->pose_count++;          // once for the whole crowd (scenes with instances attached to an actor's joint compare it: rt_scene_update)
+    return RT_OK;
+}
+
+// The next staging slot, the host's to write `bytes` into: the two slots are written in turn, and a slot is waited for only while the copy
+// out of it -- the one of the call before last -- has not passed on the stream.  Back-to-back calls therefore never wait for the device
+// unless they run two uploads ahead of it.
+int crowd_stage(rt_crowd *c, size_t bytes, CrowdStage **out)
+{
+    CrowdStage &s = c->stage[c->next_stage];
+    if (s.in_flight) {
+        HIP_TRY(hipEventSynchronize(s.event));
+        s.in_flight = false;
+    }
+    if (!s.event) HIP_TRY(hipEventCreateWithFlags(&s.event, hipEventDisableTiming));
+    if (s.bytes < bytes) {
+        void *b = nullptr;
+        if (hipHostMalloc(&b, bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            rt_set_error("out of page-locked host memory (%zu bytes)", bytes);
+            return RT_ERR_OOM;
+        }
+        if (s.block) (void)hipHostFree(s.block);
+        s.block = b;
+        s.bytes = bytes;
+    }
+    c->next_stage ^= 1u;
+    *out = &s;
+    return RT_OK;
+}
+
+// every actor's validated layers: packed into a staging slot, uploaded -- the one upload of the call -- and posed
+int blend_crowd(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers)
+{
+    rt_context *ctx = c->ctx;
+    const rt_skeleton *sk = c->sk;
+    std::vector<rt_crowd_clip> clips(sk->clips.size());
+    std::vector<const float *> masks(sk->masks.size());
+    for (size_t k = 0; k < clips.size(); k++) clips[k] = {(uint32_t)sk->clips[k].times.size(), sk->clips[k].times.data(), sk->clips[k].keys.as<float>()};
+    for (size_t k = 0; k < masks.size(); k++) masks[k] = sk->masks[k].as<float>();
+    const size_t bytes = sizeof(rt_blend_layer) * (size_t)c->n_poses * n_layers;
+    RT_TRY(rt_use_device(ctx));
+    // (what can refuse comes first: a table that cannot grow keeps the one it has -- nothing is queued that reads it -- and nothing has changed)
+    RT_TRY(c->layers.reserve(bytes));
+    CrowdStage *s = nullptr;
+    RT_TRY(crowd_stage(c, bytes, &s));
+    rt_crowd_pack_layers(c->n_poses, n_layers, layers, c->n_joints, clips.data(), masks.data(), (rt_blend_layer *)s->block);
+    HIP_TRY(hipMemcpyAsync(c->layers.p, s->block, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(s->event, ctx->stream));
+    s->in_flight = true;
+    return pose_crowd(c, n_layers);
+}
+
+int require_pose(const rt_crowd *c, const char *who)
+{
+    if (c->posed) return RT_OK;
+    rt_set_error("%s: the crowd has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", who);
+    return RT_ERR_STATE;
+}
+
+int read_back(rt_crowd *c, const char *who, const DevBuf &from, uint32_t first_actor, uint32_t count, float *to, size_t floats_per_joint)
+{
+    RT_TRY(require_pose(c, who));
+    if (first_actor > c->n_poses || count > c->n_poses - first_actor) {
+        rt_set_error("%s: actors %u .. %u: the crowd has %u", who, first_actor, first_actor + count - 1u, c->n_poses);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (count == 0) return RT_OK;
+    const size_t per_actor = floats_per_joint * c->n_joints;
+    RT_TRY(rt_use_device(c->ctx));
+    HIP_TRY(hipMemcpyAsync(to, from.as<float>() + per_actor * first_actor, sizeof(float) * per_actor * count, hipMemcpyDeviceToHost, c->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    return RT_OK;
+}
+
+}  // namespace
+
+rt_crowd::~rt_crowd()
+{
+    for (CrowdStage &s : stage) {
+        if (s.event) (void)hipEventDestroy(s.event);
+        if (s.block) (void)hipHostFree(s.block);
+    }
+    (void)rt_release(sk);
+}
+
+extern "C" {
+
+int rt_crowd_create(rt_skeleton *sk, uint32_t n_actors, rt_crowd **out)
+{
+    RT_REQUIRE(sk && out, "null argument");
+    RT_REQUIRE(n_actors >= 1u, "a crowd has at least one actor");
+    if (sk->n_joints > RT_SKELETON_LDS_JOINTS) {
+        rt_set_error("rt_crowd_create: a skeleton of %u joints: a crowd poses rigs of up to %u (the actor's world matrices stand in LDS; a larger rig is a skeleton of its own)",
+                     sk->n_joints, RT_SKELETON_LDS_JOINTS);
+        return RT_ERR_UNSUPPORTED;
+    }
+    rt_context *ctx = sk->ctx;
+    rt_made<rt_crowd> c;
+    RT_TRY(rt_make(ctx, c));
+    c->is_crowd = true;
+    c->sk = sk;
+    rt_retain(sk);
+    c->n_joints = sk->n_joints;
+    c->n_poses = n_actors;
+    const size_t joints = (size_t)n_actors * sk->n_joints;
+    RT_TRY(rt_use_device(ctx));
+    RT_TRY(c->pose.reserve(sizeof(float) * RT_SKELETON_POSE_FLOATS * joints));
+    RT_TRY(c->joints.reserve(48 * joints));
+    RT_TRY(c->palette.reserve(48 * joints));
+    *out = c.release();
+    return RT_OK;
+}
+
+// (a scene with instances attached to it, or a model posed from it, holds what it needs: the scene retains the crowd, and the last release
+// joins the stream)
+int rt_crowd_destroy(rt_crowd *c) { return rt_release(c); }
+
+int rt_crowd_get_info(const rt_crowd *c, rt_skeleton **sk, uint32_t *n_actors, uint32_t *n_joints)
+{
+    RT_REQUIRE(c, "null crowd");
+    if (sk) *sk = c->sk;
+    if (n_actors) *n_actors = c->n_poses;
+    if (n_joints) *n_joints = c->n_joints;
+    return RT_OK;
+}
+
+int rt_crowd_set_poses(rt_crowd *c, const float *trs, uint32_t mem)
+{
+    RT_REQUIRE(c && trs, "null argument");
+    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
+    rt_context *ctx = c->ctx;
+    RT_TRY(rt_use_device(ctx));
+    const size_t bytes = sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)c->n_joints * c->n_poses;
+    // (the crowd keeps the poses: rt_crowd_read_pose answers from them, and a device source is the caller's again once the stream has passed the copy)
+    HIP_TRY(hipMemcpyAsync(c->pose.p, trs, bytes, mem == RT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    RT_TRY(pose_crowd(c, 0u));
+    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again)
+    return RT_OK;
+}
+
+int rt_crowd_set_blend(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers)
+{
+    RT_REQUIRE(c && layers, "null argument");
+    const uint32_t n_clips = (uint32_t)c->sk->clips.size(), n_masks = (uint32_t)c->sk->masks.size();
+    uint32_t a = 0, bad = 0;
+    const int what = rt_crowd_validate_layers(c->n_poses, n_layers, layers, n_clips, n_masks, c->posed, &a, &bad);
+    const rt_skeleton_layer *l = what > 2 ? &layers[(size_t)a * n_layers + bad] : nullptr;
+    switch (what) {
+    case 0: break;
+    case 1: rt_set_error("rt_crowd_set_blend: null argument"); return RT_ERR_INVALID_ARG;
+    case 2: rt_set_error("rt_crowd_set_blend: %u layers: 1 .. %u are supported", n_layers, RT_SKELETON_MAX_LAYERS); return RT_ERR_INVALID_ARG;
+    case 3: rt_set_error("rt_crowd_set_blend: actor %u: layer %u has mode %u: RT_LAYER_BLEND (0) or RT_LAYER_ADDITIVE (1)", a, bad, l->mode); return RT_ERR_INVALID_ARG;
+    case 4: rt_set_error("rt_crowd_set_blend: actor %u: layer 0 is additive: the base layer is RT_LAYER_BLEND", a); return RT_ERR_INVALID_ARG;
+    case 5: rt_set_error("rt_crowd_set_blend: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: only layer 0 may", a, bad); return RT_ERR_INVALID_ARG;
+    case 6: rt_set_error("rt_crowd_set_blend: actor %u: the time of layer %u is NaN", a, bad); return RT_ERR_INVALID_ARG;
+    case 7:
+        rt_set_error("rt_crowd_set_blend: actor %u: layer %u names clip %u: the skeleton has %u (rt_skeleton_add_clip adds one)", a, bad, l->clip, n_clips);
+        return RT_ERR_STATE;
+    case 8:
+        rt_set_error("rt_crowd_set_blend: actor %u: layer %u names mask %u: the skeleton has %u (rt_skeleton_add_mask adds one)", a, bad, l->mask, n_masks);
+        return RT_ERR_STATE;
+    default:
+        rt_set_error("rt_crowd_set_blend: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: the crowd has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", a, bad);
+        return RT_ERR_STATE;
+    }
+    return blend_crowd(c, n_layers, layers);
+}
+
+int rt_crowd_set_times(rt_crowd *c, const uint32_t *clips, const float *times)
+{
+    RT_REQUIRE(c && clips && times, "null argument");
+    // the refusals of rt_skeleton_set_time, per actor: every actor's time before any actor's clip, the first bad actor first
+    for (uint32_t a = 0; a < c->n_poses; a++)
+        if (std::isnan(times[a])) {
+            rt_set_error("rt_crowd_set_times: actor %u: the time is NaN", a);
+            return RT_ERR_INVALID_ARG;
+        }
+    for (uint32_t a = 0; a < c->n_poses; a++)
+        if (clips[a] >= c->sk->clips.size()) {
+            rt_set_error("rt_crowd_set_times: actor %u: clip %u: the skeleton has %zu (rt_skeleton_add_clip adds one)", a, clips[a], c->sk->clips.size());
+            return RT_ERR_STATE;
+        }
+    std::vector<rt_skeleton_layer> layers;
+    try {
+        layers.resize(c->n_poses);
+    } catch (const std::bad_alloc &) {
+        rt_set_error("out of host memory");
+        return RT_ERR_OOM;
+    }
+    rt_crowd_layers_of_times(c->n_poses, clips, times, layers.data());
+    return blend_crowd(c, 1u, layers.data());
+}
+
+int rt_crowd_read_pose(rt_crowd *c, uint32_t first_actor, uint32_t count, float *trs)
+{
+    RT_REQUIRE(c && trs, "null argument");
+    return read_back(c, "rt_crowd_read_pose", c->pose, first_actor, count, trs, RT_SKELETON_POSE_FLOATS);
+}
+
+int rt_crowd_read_joints(rt_crowd *c, uint32_t first_actor, uint32_t count, float *world3x4)
+{
+    RT_REQUIRE(c && world3x4, "null argument");
+    return read_back(c, "rt_crowd_read_joints", c->joints, first_actor, count, world3x4, 12);
+}
+
+int rt_crowd_read_palette(rt_crowd *c, uint32_t first_actor, uint32_t count, float *palette3x4)
+{
+    RT_REQUIRE(c && palette3x4, "null argument");
+    return read_back(c, "rt_crowd_read_palette", c->palette, first_actor, count, palette3x4, 12);
+}
+
+int rt_crowd_get_joints_device_ptr(rt_crowd *c, void **ptr)
+{
+    RT_REQUIRE(c && ptr, "null argument");
+    RT_TRY(require_pose(c, "rt_crowd_get_joints_device_ptr"));
+    *ptr = c->joints.p;
+    return RT_OK;
+}
+
+int rt_crowd_get_palette_device_ptr(rt_crowd *c, void **ptr)
+{
+    RT_REQUIRE(c && ptr, "null argument");
+    RT_TRY(require_pose(c, "rt_crowd_get_palette_device_ptr"));
+    *ptr = c->palette.p;
+    return RT_OK;
+}
+
+int rt_model_set_bones_from_crowd(rt_model *m, rt_crowd *c, uint32_t actor)
+{
+    RT_REQUIRE(m && c, "null argument");
+    if (actor >= c->n_poses) {
+        rt_set_error("rt_model_set_bones_from_crowd: actor %u: the crowd has %u", actor, c->n_poses);
+        return RT_ERR_INVALID_ARG;
+    }
+    RT_TRY(require_pose(c, "rt_model_set_bones_from_crowd"));
+    if (m->skin.k == 0) {
+        rt_set_error("rt_model_set_bones_from_crowd: the model has no skin (rt_model_set_skin gives it one)");
+        return RT_ERR_STATE;
+    }
+    if (m->skin.bones != c->n_joints) {
+        rt_set_error("rt_model_set_bones_from_crowd: a skin of %u bones and a crowd of %u joints", m->skin.bones, c->n_joints);
+        return RT_ERR_STATE;
+    }
+    if (m->ctx != c->ctx) {
+        rt_set_error("rt_model_set_bones_from_crowd: the model and the crowd belong to different contexts");
+        return RT_ERR_STATE;
+    }
+    return rt_model_set_bones(m, c->palette.as<float>() + 12u * (size_t)c->n_joints * actor, RT_MEM_DEVICE);
+}
+
+}  // extern "C"

@@ -397,22 +397,53 @@ struct SkeletonClip {
     DevBuf keys;                 // float[n_keys][10][n_joints]: component major within a key, so that the lanes of a wave read 64 consecutive floats
 };
 
-struct rt_skeleton : rt_handle {
-    using rt_handle::rt_handle;  // refs: handle + every scene that has instances attached to it (once per scene)
+// What an attached instance follows, and what a skeleton and a crowd both are: n_poses poses of n_joints joints whose world matrices W stand
+// in `joints`, pose after pose.  A scene holds, retains and releases its pose sources through this type alone (rt_scene::sources), so the
+// pending rule, the refusals and the lifetime of attachments are written once for both; the destructor is virtual for that release.
+struct rt_pose_source : rt_handle {
+    using rt_handle::rt_handle;  // refs: handle + every scene that has instances attached to it (once per scene) (+ a skeleton: every crowd made of it)
     static constexpr bool joins_stream = true;       // a skin kernel that reads the palette, or a pose kernel, may still be queued
-    uint64_t pose_count = 0;     // bumped by every pose set or sampled: a scene records it per attached instance at build / update (SceneInstance::seen_pose)
-    uint32_t n_joints = 0, n_levels = 0;
+    uint64_t pose_count = 0;     // bumped by every posing call: a scene records it per attached instance at build / update (SceneInstance::seen_pose)
+    uint32_t n_joints = 0;
+    uint32_t n_poses = 1;        // a skeleton: 1; a crowd: its actors
+    DevBuf joints;               // float[n_poses][n_joints][12]: W_j
+    bool posed = false;          // a pose has been set or sampled: joints (and the palette) hold something
+    bool is_crowd = false;       // the object is an rt_crowd, else an rt_skeleton
+    const float *w_of(uint32_t pose) const { return joints.as<float>() + 12u * (size_t)n_joints * pose; }
+    virtual ~rt_pose_source() = default;
+};
+
+struct rt_skeleton : rt_pose_source {
+    using rt_pose_source::rt_pose_source;
+    uint32_t n_levels = 0;
     std::vector<uint32_t> level_offsets;     // n_levels + 1 (rt_skeleton.h)
     std::vector<int32_t> parents;            // n_joints, as rt_skeleton_create took them: rt_skeleton_solve_ik finds a constraint's chain and checks independence with them
     DevBuf table;                // uint32[n_joints]: joint | parent << 16 in level order (rt_skeleton_pack_table)
     DevBuf d_level_offsets;      // uint32[n_levels + 1]
     DevBuf inverse_bind;         // float[n_joints][12]
     DevBuf pose;                 // float[n_joints][10]: the local pose last set or sampled
-    DevBuf joints;               // float[n_joints][12]: W_j
     DevBuf palette;              // float[n_joints][12]: M_j = W_j o inverse_bind_j, what rt_model_set_bones_from_skeleton hands to the skin kernel
-    bool posed = false;          // a pose has been set or sampled: joints and palette hold something
     std::vector<SkeletonClip> clips;
     std::vector<DevBuf> masks;   // rt_skeleton_add_mask: float[n_joints] each, one weight per joint of a blend layer (rt_skeleton_set_blend)
+};
+
+// rt_crowd_create (rt_crowd.hip): n_poses = n_actors poses of one skeleton, which it retains and whose hierarchy, inverse binds, clips and
+// masks it reads where they live.  Every posing call is one upload of the actors' layer records and one launch of k_crowd_pose.
+struct CrowdStage {              // one slot of page-locked staging for that upload, and the event behind the copy out of it
+    void *block = nullptr;
+    size_t bytes = 0;
+    hipEvent_t event = nullptr;
+    bool in_flight = false;
+};
+struct rt_crowd : rt_pose_source {
+    using rt_pose_source::rt_pose_source;
+    rt_skeleton *sk = nullptr;   // retained
+    DevBuf pose;                 // float[n_actors][n_joints][10]
+    DevBuf palette;              // float[n_actors][n_joints][12]
+    DevBuf layers;               // rt_blend_layer[n_actors][n_layers] of the call last queued (rt_skeleton.h)
+    CrowdStage stage[2];         // written in turn: a slot is the host's again once its own event has passed (rt_crowd.hip: crowd_stage)
+    uint32_t next_stage = 0;
+    ~rt_crowd() override;        // (rt_crowd.hip) the staging, then the skeleton; the caller has selected the device and joined the stream
 };
 
 // Where an instance's transform comes from.  Host: SceneInstance::xform is the truth.  Device: set from device memory, rt_scene::d_xf holds it and
@@ -428,8 +459,9 @@ struct SceneInstance {
     XfSource source = XfSource::Host;
     uint64_t seen_geom = 0;      // its model's geom_gen when its record was last written (build / update); another value now: the model's
                                  //   vertices changed since, the scene is STALE as with a pending transform
-    rt_skeleton *sk = nullptr;   // source == Joint: the skeleton, retained by the scene once (rt_scene::skeletons); else nullptr
-    uint64_t seen_pose = 0;      // sk->pose_count when the scene last applied a pose to this instance (0: never)
+    rt_pose_source *src = nullptr;       // source == Joint: the skeleton or crowd, retained by the scene once (rt_scene::sources); else nullptr
+    uint32_t actor = 0;          // ... and which of its poses: a crowd's actor, 0 for a skeleton
+    uint64_t seen_pose = 0;      // src->pose_count when the scene last applied a pose to this instance (0: never)
 };
 
 // The records and the binding mirrors (inst, att_words, att_local) have exactly inst.size() entries at every entry point: rt_scene_add_model
@@ -467,8 +499,8 @@ struct rt_scene : rt_handle {
     DevBuf xf_back;                      // the device-sourced transforms an update listed, slot by slot, on their way to SceneInstance::xform
     std::vector<uint32_t> att_words;     // per instance: the binding as the device reads it (rt_attach.h), 0: not attached ...
     std::vector<float> att_local;        // ... its local matrix, float[12] per instance ...
-    DevBuf d_att_words, d_att_local, d_att_w;    // ... and both on the device, with the skeleton's W array (const float *) of every attached instance
-    std::vector<rt_skeleton *> skeletons;        // the skeletons the scene retains: every one some instance is or was attached to, each once
+    DevBuf d_att_words, d_att_local, d_att_w;    // ... and both on the device, with the W array (const float *: its skeleton's, or its actor's slice of its crowd's) of every attached instance
+    std::vector<rt_pose_source *> sources;       // the skeletons and crowds the scene retains: every one some instance is or was attached to, each once
     SceneDev dev() const
     {
         SceneDev s;
@@ -481,7 +513,7 @@ struct rt_scene : rt_handle {
         s.top_n = 0;
         return s;
     }
-    ~rt_scene();                 // (rt_scene.hip) lets go of the models and skeletons it retains; then the buffers
+    ~rt_scene();                 // (rt_scene.hip) lets go of the models and pose sources it retains; then the buffers
 };
 
 // ---- internal entry points shared between translation units ---------------------

@@ -51,7 +51,7 @@ void scene_build_begins(rt_scene *s) { s->updatable = false; }
 void scene_applied(rt_scene *s, const std::vector<uint32_t> *changed)
 {
     // the attached instances it listed now stand where their skeleton's current pose puts them
-    const auto listed = [](SceneInstance &in) { if (in.source == XfSource::Joint) in.seen_pose = in.sk->pose_count; in.pending = false; };
+    const auto listed = [](SceneInstance &in) { if (in.source == XfSource::Joint) in.seen_pose = in.src->pose_count; in.pending = false; };
     if (changed) {
         for (uint32_t i : s->pending) listed(s->inst[i]);
         for (uint32_t i : *changed) s->inst[i].seen_geom = s->inst[i].model->geom_gen;
@@ -86,31 +86,35 @@ void scene_add_instance(rt_scene *s, rt_model *m, const float xform[12])
     s->att_local.resize(12 * s->inst.size(), 0.0f);
 }
 
-// instance i follows a joint of sk (which the scene retains: rt_scene::skeletons); `word`: the binding as the device reads it (rt_attach.h)
-void scene_bind(rt_scene *s, uint32_t i, rt_skeleton *sk, uint32_t word)
+// instance i follows a joint of pose `actor` of src, a skeleton or a crowd (which the scene retains: rt_scene::sources); `word`: the binding
+// as the device reads it (rt_attach.h) -- the actor is not in it: it is in the W pointer the device holds for the instance
+void scene_bind(rt_scene *s, uint32_t i, rt_pose_source *src, uint32_t actor, uint32_t word)
 {
     SceneInstance &in = s->inst[i];
-    in.source = sk ? XfSource::Joint : XfSource::Host; in.sk = sk; in.seen_pose = 0; s->att_words[i] = word;
+    in.source = src ? XfSource::Joint : XfSource::Host; in.src = src; in.actor = actor; in.seen_pose = 0; s->att_words[i] = word;
 }
 
 // ... and no longer: it keeps the floats its last update or build gave it, which the host copy holds
-void scene_unbind(rt_scene *s, uint32_t i) { scene_bind(s, i, nullptr, 0u); }
+void scene_unbind(rt_scene *s, uint32_t i) { scene_bind(s, i, nullptr, 0u, 0u); }
 
 // attached instances of an updatable scene whose skeleton has been posed since the scene last applied it, and that are not pending already
 void scene_posed_instances(const rt_scene *s, std::vector<uint32_t> &which)
 {
-    for (size_t i = 0; s->updatable && !s->skeletons.empty() && i < s->inst.size(); i++) {      // (no skeleton: nobody has ever been attached)
+    for (size_t i = 0; s->updatable && !s->sources.empty() && i < s->inst.size(); i++) {      // (no skeleton: nobody has ever been attached)
         const SceneInstance &in = s->inst[i];
-        if (in.source == XfSource::Joint && !in.pending && in.sk->posed && in.sk->pose_count != in.seen_pose) which.push_back((uint32_t)i);
+        if (in.source == XfSource::Joint && !in.pending && in.src->posed && in.src->pose_count != in.seen_pose) which.push_back((uint32_t)i);
     }
 }
 
 // an update or a build composes every attached instance it lists from W: refused, with nothing changed, while some skeleton has no pose
 int scene_require_poses(const rt_scene *s, const char *who)
 {
-    for (size_t i = 0; !s->skeletons.empty() && i < s->inst.size(); i++)
-        if (s->inst[i].source == XfSource::Joint && !s->inst[i].sk->posed) {
-            rt_set_error("%s: instance %zu is attached to a skeleton that has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", who, i);
+    for (size_t i = 0; !s->sources.empty() && i < s->inst.size(); i++)
+        if (s->inst[i].source == XfSource::Joint && !s->inst[i].src->posed) {
+            if (s->inst[i].src->is_crowd)
+                rt_set_error("%s: instance %zu is attached to a crowd that has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", who, i);
+            else
+                rt_set_error("%s: instance %zu is attached to a skeleton that has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", who, i);
             return RT_ERR_STATE;
         }
     return RT_OK;
@@ -121,8 +125,12 @@ int scene_refuse_attached(const rt_scene *s, const char *who, uint32_t first, ui
 {
     uint32_t i = 0;
     if (!rt_attach_range_holds(s->att_words.data(), s->att_words.size(), first, count, &i)) return RT_OK;
-    rt_set_error("%s: instance %u is attached to joint %u of a skeleton, which gives it its transform (rt_scene_detach_instances lets it go)", who, i,
-                 s->att_words[i] & RT_ATTACH_JOINT_MASK);
+    if (s->inst[i].src && s->inst[i].src->is_crowd)
+        rt_set_error("%s: instance %u is attached to joint %u of actor %u of a crowd, which gives it its transform (rt_scene_detach_instances lets it go)", who, i,
+                     s->att_words[i] & RT_ATTACH_JOINT_MASK, s->inst[i].actor);
+    else
+        rt_set_error("%s: instance %u is attached to joint %u of a skeleton, which gives it its transform (rt_scene_detach_instances lets it go)", who, i,
+                     s->att_words[i] & RT_ATTACH_JOINT_MASK);
     return RT_ERR_STATE;
 }
 
@@ -152,7 +160,7 @@ int scene_reserve_device(rt_context *ctx, rt_scene *s)
     if (held) HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::vector<const float *> w_of(n, nullptr);
     for (size_t i = 0; i < n; i++)
-        if (s->inst[i].source == XfSource::Joint) { w_of[i] = s->inst[i].sk->joints.as<float>(); bound = true; }
+        if (s->inst[i].source == XfSource::Joint) { w_of[i] = s->inst[i].src->w_of(s->inst[i].actor); bound = true; }
     RT_TRY(s->d_att_words.reserve(4 * n));
     RT_TRY(s->d_att_local.reserve(48 * n));
     RT_TRY(s->d_att_w.reserve(sizeof(const float *) * n));
@@ -669,7 +677,7 @@ rt_scene::~rt_scene()
             if (held[k] == this) { held.erase(held.begin() + k); break; }
         rt_model_destroy(in.model);
     }
-    for (rt_skeleton *sk : skeletons) rt_skeleton_destroy(sk);     // (joins the stream when the scene held the last reference)
+    for (rt_pose_source *src : sources) (void)rt_release(src);     // (joins the stream when the scene held the last reference)
 }
 
 void rt_scene_model_changed(rt_scene *s) { scene_vertices_changed(s); }
@@ -773,19 +781,26 @@ int rt_scene_get_instance_transforms(const rt_scene *s, uint32_t first, uint32_t
     return RT_OK;
 }
 
-int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_skeleton *sk, const uint32_t *joints, const float *local3x4)
+// Attaches instances first .. first + count - 1 to joints[k] of pose actors[k] (nullptr: pose 0, a skeleton's only one) of `src`; `what`
+// names the kind of source in the messages.  Both entry points below are this.
+static int scene_attach(rt_scene *s, const char *who, const char *what, uint32_t first, uint32_t count, rt_pose_source *src, const uint32_t *actors,
+                        const uint32_t *joints, const float *local3x4)
 {
-    RT_REQUIRE(s && sk && (joints || count == 0), "null argument");
     uint32_t bad = 0;
-    switch (rt_attach_validate((uint32_t)s->inst.size(), first, count, sk->n_joints, joints, &bad)) {
+    switch (rt_attach_validate((uint32_t)s->inst.size(), first, count, src->n_joints, joints, &bad)) {
     case 0: break;
-    case 1: rt_set_error("rt_scene_attach_instances: null argument"); return RT_ERR_INVALID_ARG;
-    case 2: return scene_range_check(s, __func__, first, count);
+    case 1: rt_set_error("%s: null argument", who); return RT_ERR_INVALID_ARG;
+    case 2: return scene_range_check(s, who, first, count);
     default:
-        rt_set_error("rt_scene_attach_instances: entry %u names joint %u: the skeleton has %u", bad, joints[bad], sk->n_joints);
+        rt_set_error("%s: entry %u names joint %u: the %s has %u", who, bad, joints[bad], what, src->n_joints);
         return RT_ERR_INVALID_ARG;
     }
-    if (sk->ctx != s->ctx) { rt_set_error("rt_scene_attach_instances: the scene and the skeleton belong to different contexts"); return RT_ERR_STATE; }
+    for (uint32_t k = 0; actors && k < count; k++)
+        if (actors[k] >= src->n_poses) {
+            rt_set_error("%s: entry %u names actor %u: the %s has %u", who, k, actors[k], what, src->n_poses);
+            return RT_ERR_INVALID_ARG;
+        }
+    if (src->ctx != s->ctx) { rt_set_error("%s: the scene and the %s belong to different contexts", who, what); return RT_ERR_STATE; }
     if (count == 0) return RT_OK;
     rt_context *ctx = s->ctx;
     RT_TRY(rt_use_device(ctx));
@@ -793,7 +808,8 @@ int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_sk
     // the device first -- the only steps that can refuse -- then, behind the wait, the host: nothing changes if the device refuses
     RT_TRY(scene_reserve_device(ctx, s));              // (where the composed transforms will stand, and the bindings of every instance)
     std::vector<uint32_t> words(count);
-    std::vector<const float *> w_of(count, sk->joints.as<float>());
+    std::vector<const float *> w_of(count, src->w_of(0));
+    for (uint32_t k = 0; actors && k < count; k++) w_of[k] = src->w_of(actors[k]);
     rt_attach_pack(count, joints, local3x4 != nullptr, words.data());
     HIP_TRY(hipMemcpyAsync(s->d_att_words.as<uint32_t>() + first, words.data(), 4 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
     if (local3x4)                                      // (without one the rows stay: nobody reads them)
@@ -803,12 +819,26 @@ int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_sk
     RT_TRY(scene_bring_down(ctx, s, first, count, &held));
     HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vectors go out of scope, the caller's arrays are its own again)
     held = false;
-    for (rt_skeleton *o : s->skeletons) held = held || o == sk;
-    if (!held) { s->skeletons.push_back(sk); rt_retain(sk); }      // (as the scene retains its models; let go of when the scene goes)
+    for (rt_pose_source *o : s->sources) held = held || o == src;
+    if (!held) { s->sources.push_back(src); rt_retain(src); }      // (as the scene retains its models; let go of when the scene goes)
     if (local3x4) memcpy(&s->att_local[12 * (size_t)first], local3x4, 48 * (size_t)count);
-    for (uint32_t k = 0; k < count; k++) scene_bind(s, first + k, sk, words[k]);
+    for (uint32_t k = 0; k < count; k++) scene_bind(s, first + k, src, actors ? actors[k] : 0u, words[k]);
     if (s->updatable) scene_transforms_changed(s, first, count);      // (never built, or instances added since: the next build reads the binding)
     return RT_OK;
+}
+
+int rt_scene_attach_instances(rt_scene *s, uint32_t first, uint32_t count, rt_skeleton *sk, const uint32_t *joints, const float *local3x4)
+{
+    RT_REQUIRE(s && sk && (joints || count == 0), "null argument");
+    return scene_attach(s, "rt_scene_attach_instances", "skeleton", first, count, sk, nullptr, joints, local3x4);
+}
+
+int rt_scene_attach_instances_crowd(rt_scene *s, uint32_t first, uint32_t count, rt_crowd *c, const uint32_t *actors, const uint32_t *joints,
+                                    const float *local3x4)
+{
+    RT_REQUIRE(s && c && ((actors && joints) || count == 0), "null argument");
+    static const uint32_t none = 0;                     // (count == 0 with a null `actors`: nothing is read)
+    return scene_attach(s, "rt_scene_attach_instances_crowd", "crowd", first, count, c, actors ? actors : &none, joints, local3x4);
 }
 
 int rt_scene_detach_instances(rt_scene *s, uint32_t first, uint32_t count)
@@ -829,8 +859,19 @@ int rt_scene_get_instance_attachment(const rt_scene *s, uint32_t instance, rt_sk
 {
     RT_REQUIRE(s, "null scene");
     RT_TRY(scene_range_check(s, __func__, instance, 1, true));
-    const bool bound = s->inst[instance].source == XfSource::Joint;
-    if (sk) *sk = bound ? s->inst[instance].sk : nullptr;
+    const bool bound = s->inst[instance].source == XfSource::Joint && !s->inst[instance].src->is_crowd;      // (a crowd's: rt_scene_get_instance_crowd_attachment)
+    if (sk) *sk = bound ? static_cast<rt_skeleton *>(s->inst[instance].src) : nullptr;
+    if (joint) *joint = bound ? s->att_words[instance] & RT_ATTACH_JOINT_MASK : 0u;
+    return RT_OK;
+}
+
+int rt_scene_get_instance_crowd_attachment(const rt_scene *s, uint32_t instance, rt_crowd **c, uint32_t *actor, uint32_t *joint)
+{
+    RT_REQUIRE(s, "null scene");
+    RT_TRY(scene_range_check(s, __func__, instance, 1, true));
+    const bool bound = s->inst[instance].source == XfSource::Joint && s->inst[instance].src->is_crowd;
+    if (c) *c = bound ? static_cast<rt_crowd *>(s->inst[instance].src) : nullptr;
+    if (actor) *actor = bound ? s->inst[instance].actor : 0u;
     if (joint) *joint = bound ? s->att_words[instance] & RT_ATTACH_JOINT_MASK : 0u;
     return RT_OK;
 }

@@ -1,6 +1,6 @@
 // rt_skeleton.h -- the host side of a skeleton (rt_skeleton_create, rt_skeleton_add_clip, rt_skeleton_set_time, rt_skeleton_set_blend):
-// validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip, the check of a layer list and the
-// check of a list of IK constraints (rt_skeleton_solve_ik).  Host code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp,
+// validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip, the check of a layer list, the
+// record a validated layer is packed into (shared with rt_crowd.h) and the check of a list of IK constraints (rt_skeleton_solve_ik).  Host code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp,
 // tests/cpp/skeleton_blend_sanitized.cpp and tests/cpp/ik_sanitized.cpp compile it alone.
 #pragma once
 
@@ -141,6 +141,37 @@ static inline int rt_skeleton_validate_layers(uint32_t n_layers, const rt_skelet
         }
     }
     return 0;
+}
+
+// A validated layer as the kernels read it (rt_pose_device.h: blend_joint, blend_layer).  k_skeleton_blend takes up to
+// RT_SKELETON_MAX_LAYERS of them by value, as its argument; k_crowd_pose reads n_layers of them per actor from a table in device memory,
+// through addresses that are uniform over the block.  Either way they come by scalar loads.
+struct rt_blend_layer {
+    const float *key_a, *key_b;          // the two keys about the layer's time (layer 0: nullptr = the pose that is held) ...
+    const float *ref_a, *ref_b;          // ... and the clip's first two keys: the reference pose of an additive layer is sampled from them at a = 0
+    const float *mask;                   // float[n_joints], or nullptr: none
+    float a, weight;
+    uint32_t mode, pad;
+};
+
+// Layer k of a validated list, packed.  `times` (n_keys of them) and `keys` (device memory, float[n_keys][10][n_joints]) are the layer's
+// clip -- not read for RT_SKELETON_CURRENT_POSE, where key_a stays null -- and `mask` the layer's mask in device memory or nullptr; the base
+// layer's mask is dropped.  The segment (i, a) is found here, on the host, by rt_skeleton_segment; no pointer is dereferenced but `times`.
+static inline void rt_skeleton_pack_layer(const rt_skeleton_layer &l, uint32_t k, uint32_t n_joints, uint32_t n_keys, const float *times, const float *keys,
+                                          const float *mask, rt_blend_layer &b)
+{
+    const size_t per_key = RT_SKELETON_POSE_FLOATS * (size_t)n_joints;
+    b = rt_blend_layer();
+    b.weight = l.weight;
+    b.mode = l.mode;
+    if (l.clip == RT_SKELETON_CURRENT_POSE) return;      // (layer 0 only: key_a stays null, the kernel starts from the pose that is held)
+    uint32_t i = 0;
+    rt_skeleton_segment(n_keys, times, l.time, &i, &b.a);
+    b.ref_a = keys;
+    b.ref_b = n_keys == 1u ? b.ref_a : b.ref_a + per_key;
+    b.key_a = b.ref_a + per_key * i;
+    b.key_b = n_keys == 1u ? b.key_a : b.key_a + per_key;
+    if (k > 0u && l.mask != RT_SKELETON_NO_MASK) b.mask = mask;
 }
 
 // 0: the constraints describe one solve of a skeleton of n_joints joints with these parents, posed or not.  Else what is wrong, and bad[0]

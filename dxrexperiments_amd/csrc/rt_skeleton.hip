@@ -8,34 +8,12 @@
 #include "rt_device_math.h"
 #include "rt_ik.h"
 #include "rt_internal.h"
+#include "rt_pose_device.h"
 #include "rt_skeleton.h"
 
 namespace {
 
 using namespace rtd;
-
-// The local matrix of a joint, T.R.S, from its ten floats tx ty tz  qx qy qz qw  sx sy sz: the quaternion as given, never normalised.
-RT_DEV void local_of(const float *__restrict__ trs, float L[12])
-{
-    const float x = trs[3], y = trs[4], z = trs[5], w = trs[6];
-    const float sx = trs[7], sy = trs[8], sz = trs[9];
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-    L[0] = (1.0f - 2.0f * (yy + zz)) * sx; L[1] = (2.0f * (xy - wz)) * sy;        L[2] = (2.0f * (xz + wy)) * sz;         L[3] = trs[0];
-    L[4] = (2.0f * (xy + wz)) * sx;        L[5] = (1.0f - 2.0f * (xx + zz)) * sy; L[6] = (2.0f * (yz - wx)) * sz;         L[7] = trs[1];
-    L[8] = (2.0f * (xz - wy)) * sx;        L[9] = (2.0f * (yz + wx)) * sy;        L[10] = (1.0f - 2.0f * (xx + yy)) * sz; L[11] = trs[2];
-}
-
-// C = A o B of two 3x4 affine matrices, grouped as the header groups it
-RT_DEV void compose(const float A[12], const float B[12], float C[12])
-{
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const float a0 = A[4 * r], a1 = A[4 * r + 1], a2 = A[4 * r + 2], a3 = A[4 * r + 3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) C[4 * r + c] = (a0 * B[c] + a1 * B[4 + c]) + a2 * B[8 + c];
-        C[4 * r + 3] = ((a0 * B[3] + a1 * B[7]) + a2 * B[11]) + a3;
-    }
-}
 
 // ONE block poses a skeleton: no block ever waits on another.  Step 1, every joint at once: L from the pose, stored where W will stand (a
 // root's W is its L bit for bit).  Step 2, level by level from level 1, the lanes striding a level's joints and meeting at __syncthreads():
@@ -100,40 +78,6 @@ __global__ void __launch_bounds__(RT_SKELETON_BLOCK) k_skeleton_pose(const float
     }
 }
 
-// The quaternion q[0 .. 3] = (x, y, z, w) normalised by the rule of rt_model_recompute_normals, with (0, 0, 0, 1) where that has no answer
-RT_DEV void unit_or_identity(float q[4])
-{
-    const float n = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
-    if (n > 0.0f && n < __uint_as_float(0x7f800000u)) {
-        const float inv = rsqrt_ieee(n);
-#pragma unroll
-        for (int c = 0; c < 4; c++) q[c] = q[c] * inv;
-    } else {
-        q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f; q[3] = 1.0f;
-    }
-}
-
-// The local pose of joint j between two keys of a clip.  A key is component major (float[10][n_joints]): at every one of the twenty loads the
-// lanes of a wave read 64 consecutive floats.  Translation and scale A + (a * (B - A)); the quaternion the same after B has been turned onto
-// A's side (d < 0; a NaN d turns nothing), then normalised.
-RT_DEV void sample_joint(const float *__restrict__ key_a, const float *__restrict__ key_b, uint32_t n_joints, uint32_t j, float a, float o[10])
-{
-    float A[10], B[10];
-#pragma unroll
-    for (int c = 0; c < 10; c++) {
-        A[c] = key_a[(size_t)c * n_joints + j];
-        B[c] = key_b[(size_t)c * n_joints + j];
-    }
-    const float d = ((A[3] * B[3] + A[4] * B[4]) + A[5] * B[5]) + A[6] * B[6];
-    if (d < 0.0f) {
-#pragma unroll
-        for (int c = 3; c < 7; c++) B[c] = -B[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 10; c++) o[c] = A[c] + a * (B[c] - A[c]);
-    unit_or_identity(o + 3);
-}
-
 // One lane per joint: the local pose between two keys of a clip, written as rt_skeleton_set_pose takes it, ten floats per joint.
 __global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict__ key_a, const float *__restrict__ key_b, uint32_t n_joints, float a,
                                                          float *__restrict__ pose)
@@ -146,79 +90,21 @@ __global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict
     for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = o[c];
 }
 
-// A layer of a blend as the kernel reads it, and the table of them that travels by value as the kernel's argument: wave uniform, so it comes
+// The table of a blend's layers (rt_blend_layer, rt_skeleton.h) that travels by value as the kernel's argument: wave uniform, so it comes
 // through scalar loads and the branch on the mode is a scalar branch.
-struct BlendLayer {
-    const float *key_a, *key_b;          // the two keys about the layer's time (layer 0: nullptr = the pose the skeleton holds) ...
-    const float *ref_a, *ref_b;          // ... and the clip's first two keys: the reference pose of an additive layer is sampled from them at a = 0
-    const float *mask;                   // float[n_joints], or nullptr: none
-    float a, weight;
-    uint32_t mode, pad;
-};
 struct BlendTable {
-    BlendLayer layer[RT_SKELETON_MAX_LAYERS];
+    rt_blend_layer layer[RT_SKELETON_MAX_LAYERS];
 };
 
-// the Hamilton product r = p (x) q of quaternions (x, y, z, w), grouped as the header groups it
-RT_DEV void hamilton(const float p[4], const float q[4], float r[4])
-{
-    r[0] = ((p[3] * q[0] + p[0] * q[3]) + p[1] * q[2]) - p[2] * q[1];
-    r[1] = ((p[3] * q[1] - p[0] * q[2]) + p[1] * q[3]) + p[2] * q[0];
-    r[2] = ((p[3] * q[2] + p[0] * q[1]) - p[1] * q[0]) + p[2] * q[3];
-    r[3] = ((p[3] * q[3] - p[0] * q[0]) - p[1] * q[1]) - p[2] * q[2];
-}
-
-// One lane per joint: the layers of a blend accumulated into the local pose (include/dxr_amd.h "Posed skeletons", blending).  P starts as
-// layer 0's sample, or as the stored pose, which this lane alone reads and overwrites; every later layer is sampled as k_skeleton_sample
-// samples and blended or added with w = weight (* mask[j]).  The loop over the layers and the branch on a layer's mode are uniform; P, S and
-// R live in registers, and there is no LDS.  `pose` is read and written in place: not __restrict__.
+// One lane per joint: the layers of a blend accumulated into the local pose (include/dxr_amd.h "Posed skeletons", blending; the arithmetic
+// is blend_joint, rt_pose_device.h).  P starts as layer 0's sample, or as the stored pose, which this lane alone reads and overwrites;
+// there is no LDS.  `pose` is read and written in place: not __restrict__.
 __global__ void __launch_bounds__(256) k_skeleton_blend(const BlendTable table, uint32_t n_layers, uint32_t n_joints, float *pose)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= n_joints) return;
     float P[10];
-    if (table.layer[0].key_a) sample_joint(table.layer[0].key_a, table.layer[0].key_b, n_joints, j, table.layer[0].a, P);
-    else {
-#pragma unroll
-        for (int c = 0; c < 10; c++) P[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c];
-    }
-    for (uint32_t k = 1; k < n_layers; k++) {
-        const BlendLayer &l = table.layer[k];
-        float S[10];
-        sample_joint(l.key_a, l.key_b, n_joints, j, l.a, S);
-        const float w = l.mask ? l.weight * l.mask[j] : l.weight;
-        if (l.mode == RT_LAYER_ADDITIVE) {
-            float R[10], cr[4], D[4], E[4], q[4];
-            sample_joint(l.ref_a, l.ref_b, n_joints, j, 0.0f, R);
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                P[c] = P[c] + w * (S[c] - R[c]);
-                P[7 + c] = P[7 + c] + w * (S[7 + c] - R[7 + c]);
-            }
-            cr[0] = -R[3]; cr[1] = -R[4]; cr[2] = -R[5]; cr[3] = R[6];
-            hamilton(cr, S + 3, D);
-            if (D[3] < 0.0f) {
-#pragma unroll
-                for (int c = 0; c < 4; c++) D[c] = -D[c];
-            }
-            E[0] = w * D[0]; E[1] = w * D[1]; E[2] = w * D[2];
-            E[3] = 1.0f + w * (D[3] - 1.0f);
-            unit_or_identity(E);
-            hamilton(P + 3, E, q);
-            unit_or_identity(q);
-#pragma unroll
-            for (int c = 0; c < 4; c++) P[3 + c] = q[c];
-        } else {
-            const float d = ((P[3] * S[3] + P[4] * S[4]) + P[5] * S[5]) + P[6] * S[6];
-            if (d < 0.0f) {
-#pragma unroll
-                for (int c = 3; c < 7; c++) S[c] = -S[c];
-            }
-#pragma unroll
-            for (int c = 0; c < 10; c++) P[c] = P[c] + w * (S[c] - P[c]);
-            unit_or_identity(P + 3);
-        }
-    }
+    blend_joint(table.layer, n_layers, n_joints, j, pose + RT_SKELETON_POSE_FLOATS * (size_t)j, P);
 #pragma unroll
     for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = P[c];
 }
@@ -491,23 +377,13 @@ int rt_skeleton_set_blend(rt_skeleton *sk, uint32_t n_layers, const rt_skeleton_
         return RT_ERR_STATE;
     }
     rt_context *ctx = sk->ctx;
-    const size_t per_key = RT_SKELETON_POSE_FLOATS * (size_t)sk->n_joints;
     BlendTable table = {};
     for (uint32_t k = 0; k < n_layers; k++) {
         const rt_skeleton_layer &l = layers[k];
-        BlendLayer &b = table.layer[k];
-        b.weight = l.weight;
-        b.mode = l.mode;
-        if (l.clip == RT_SKELETON_CURRENT_POSE) continue;            // (layer 0 only: key_a stays null, the kernel starts from sk->pose)
-        const SkeletonClip &c = sk->clips[l.clip];
-        const uint32_t n_keys = (uint32_t)c.times.size();
-        uint32_t i = 0;
-        rt_skeleton_segment(n_keys, c.times.data(), l.time, &i, &b.a);
-        b.ref_a = c.keys.as<float>();
-        b.ref_b = n_keys == 1u ? b.ref_a : b.ref_a + per_key;
-        b.key_a = b.ref_a + per_key * i;
-        b.key_b = n_keys == 1u ? b.key_a : b.key_a + per_key;
-        if (k > 0u && l.mask != RT_SKELETON_NO_MASK) b.mask = sk->masks[l.mask].as<float>();
+        const SkeletonClip *c = l.clip == RT_SKELETON_CURRENT_POSE ? nullptr : &sk->clips[l.clip];
+        const float *mask = k > 0u && l.mask != RT_SKELETON_NO_MASK ? sk->masks[l.mask].as<float>() : nullptr;
+        rt_skeleton_pack_layer(l, k, sk->n_joints, c ? (uint32_t)c->times.size() : 0u, c ? c->times.data() : nullptr, c ? c->keys.as<float>() : nullptr, mask,
+                               table.layer[k]);
     }
     RT_TRY(rt_use_device(ctx));
     k_skeleton_blend<<<(sk->n_joints + 255u) / 256u, 256, 0, ctx->stream>>>(table, n_layers, sk->n_joints, sk->pose.as<float>());

@@ -164,6 +164,40 @@ namespace DXRFramework
         rt_skeleton *mHandle;
     };
 
+    // ---- RtCrowd -- EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): numActors poses of ONE RtSkeleton, all
+    // made by one launch (include/dxr_amd.h "Posed skeletons", crowds): actor a is, bit for bit, a skeleton given the same call.  The crowd
+    // reads the skeleton's clips and masks where they live and keeps it alive.  setPoses: numActors x numJoints x 10 floats; setTimes: a
+    // clip and a time per actor; setBlend: numLayers layers per actor, actor major.  A skinned model takes one actor's palette with
+    // setBones(crowd, actor); instances follow actors' joints with RtScene::attach(..., crowd, actors, joints): a frame is one setTimes and
+    // one RtScene::update, whatever the number of actors.
+    class RtCrowd
+    {
+    public:
+        using SharedPtr = std::shared_ptr<RtCrowd>;
+
+        static SharedPtr create(RtSkeleton::SharedPtr skeleton, uint32_t numActors)
+        {
+            rt_crowd *h = nullptr;
+            ThrowIfFailed(rt_crowd_create(skeleton->getHandle(), numActors, &h));
+            return SharedPtr(new RtCrowd(skeleton, h));
+        }
+        ~RtCrowd() { rt_crowd_destroy(mHandle); }
+
+        rt_crowd *getHandle() const { return mHandle; }
+        RtSkeleton::SharedPtr getSkeleton() const { return mSkeleton; }
+        RtContext::SharedPtr getContext() const { return mSkeleton->getContext(); }
+        uint32_t getNumActors() const { uint32_t n = 0; ThrowIfFailed(rt_crowd_get_info(mHandle, nullptr, &n, nullptr)); return n; }
+        void setPoses(const float *trs) { ThrowIfFailed(rt_crowd_set_poses(mHandle, trs, RT_MEM_HOST)); }
+        void setPosesDevice(const float *trs) { ThrowIfFailed(rt_crowd_set_poses(mHandle, trs, RT_MEM_DEVICE)); }
+        void setTimes(const uint32_t *clips, const float *times) { ThrowIfFailed(rt_crowd_set_times(mHandle, clips, times)); }
+        void setBlend(const rt_skeleton_layer *layers, uint32_t numLayers) { ThrowIfFailed(rt_crowd_set_blend(mHandle, numLayers, layers)); }
+
+    private:
+        RtCrowd(RtSkeleton::SharedPtr sk, rt_crowd *h) : mSkeleton(sk), mHandle(h) {}
+        RtSkeleton::SharedPtr mSkeleton;
+        rt_crowd *mHandle;
+    };
+
     // ---- RtModel (RtModel.h:9-40) ------------------------------------------------------
     class RtModel
     {
@@ -227,6 +261,8 @@ namespace DXRFramework
         // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): the palette of a posed RtSkeleton of as many joints
         // as the skin has bones, in place on the device
         void setBones(const RtSkeleton::SharedPtr &skeleton) { ThrowIfFailed(rt_model_set_bones_from_skeleton(mHandle, skeleton->getHandle())); }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): ... of one actor of a posed RtCrowd
+        void setBones(const std::shared_ptr<RtCrowd> &crowd, uint32_t actor) { ThrowIfFailed(rt_model_set_bones_from_crowd(mHandle, crowd->getHandle(), actor)); }
 
         // EXTENSIONS (the reference reads only mVertices / mNormals of an imported mesh, RtModel.cpp:26, :38-45, never its blend shapes; the
         // update path is the never-taken one, Helpers/BottomLevelASGenerator.h:136-176): morph targets.  setMorphTargets: numTargets sparse
@@ -330,6 +366,12 @@ namespace DXRFramework
         {
             realize(skeleton->getContext());
             ThrowIfFailed(rt_scene_attach_instances(mHandle, first, count, skeleton->getHandle(), joints, locals));
+        }
+        // ... of actor actors[k] of a crowd (rt_scene_attach_instances_crowd); the scene keeps the crowd alive
+        void attach(uint32_t first, uint32_t count, const std::shared_ptr<RtCrowd> &crowd, const uint32_t *actors, const uint32_t *joints, const float *locals = nullptr)
+        {
+            realize(crowd->getContext());
+            ThrowIfFailed(rt_scene_attach_instances_crowd(mHandle, first, count, crowd->getHandle(), actors, joints, locals));
         }
         void detach(uint32_t first, uint32_t count)
         {

@@ -37,6 +37,7 @@ typedef struct rt_model    rt_model;
 typedef struct rt_scene    rt_scene;
 typedef struct rt_pipeline rt_pipeline;
 typedef struct rt_skeleton rt_skeleton;
+typedef struct rt_crowd rt_crowd;
 typedef struct rt_progressive_host rt_progressive_host;
 
 /* ---- library ------------------------------------------------------------- */
@@ -403,6 +404,15 @@ int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */
  *           invertible affine matrices.  Under non-uniform scale on a or b the answer is still this definition, but the tip's position is
  *           approximate.  Twist about the bones is whatever the input pose had.  No joint limits, no chains longer than two bones, no CCD
  *           or FABRIK.
+ *   crowds  (rt_crowd_*): a CROWD is n_actors poses of ONE skeleton.  It retains the skeleton and reads its hierarchy, inverse binds, clips
+ *           and masks where they live -- a clip or mask added after the crowd was made is there for the next call -- and owns three device
+ *           arrays, actor major: pose[n_actors][n_joints][10], joints[n_actors][n_joints][12], palette[n_actors][n_joints][12].  Actor a of
+ *           a crowd is, bit for bit, a skeleton given the same call: rt_crowd_set_poses is rt_skeleton_set_pose with actor a's n_joints x 10
+ *           floats, rt_crowd_set_times rt_skeleton_set_time(clips[a], times[a]), rt_crowd_set_blend rt_skeleton_set_blend with actor a's
+ *           n_layers layers, by the definitions above and by the same statements (the segment (i, a) of every sampled layer found on the
+ *           host); RT_SKELETON_CURRENT_POSE on layer 0 is that actor's own held pose.  Every posing call poses ALL actors with one kernel
+ *           launch and counts one pose for the whole crowd.  No per-actor IK, no times or layers read from device memory, no posing of a
+ *           sub-range of actors, no rigs above 1024 joints.
  * Validation is done on the host, and nothing changes when a call refuses.  Setting a pose touches no model and no scene.
  * rt_skeleton_create: a null argument is RT_ERR_INVALID_ARG; so is n_joints outside 1 .. 65536 (the skin's bone limit), and a parent that is
  * neither -1 nor < j -- parents come before children -- (the message names the joint).  inverse_bind: n_joints x 12, 3x4 row-major, as
@@ -480,6 +490,55 @@ int rt_skeleton_get_palette_device_ptr(rt_skeleton *sk, void **ptr);
  * of different contexts.  Otherwise it is exactly rt_model_set_bones(m, palette, RT_MEM_DEVICE): frames a deferred pipeline still holds are
  * rendered first, the model is left CHANGED and every built scene that holds it STALE until rt_scene_update or rt_scene_build. */
 int rt_model_set_bones_from_skeleton(rt_model *m, rt_skeleton *sk);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): a crowd of n_actors poses of `sk` ("crowds" above), which it
+ * retains: destroying the skeleton while the crowd lives is legal.  A null argument or n_actors == 0 is RT_ERR_INVALID_ARG; a skeleton of
+ * more than 1024 joints is RT_ERR_UNSUPPORTED (the message gives both numbers: an actor's world matrices stand in LDS, and the path through
+ * global memory stays the single skeleton's); a device allocation that fails is RT_ERR_OOM.  The crowd has no pose yet. */
+int rt_crowd_create(rt_skeleton *sk, uint32_t n_actors, rt_crowd **out);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): joins the context's stream first, as rt_skeleton_destroy does, so
+ * destroying a crowd right after rt_model_set_bones_from_crowd is legal; a scene with instances attached to it retains it. */
+int rt_crowd_destroy(rt_crowd *c);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the crowd's skeleton, its actors and the joints of each; each
+ * may be NULL */
+int rt_crowd_get_info(const rt_crowd *c, rt_skeleton **sk, uint32_t *n_actors, uint32_t *n_joints);   /* each may be NULL */
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local pose of every actor, and from it every actor's W and
+ * palette: one copy and one kernel on the context's stream.  `mem` as for rt_skeleton_set_pose: RT_MEM_HOST synchronises the stream before
+ * the call returns, RT_MEM_DEVICE copies device to device, ordered on the stream; a null argument or an unknown `mem` is RT_ERR_INVALID_ARG. */
+int rt_crowd_set_poses(rt_crowd *c, const float *trs /* n_actors x n_joints x 10 */, uint32_t mem);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): actor a samples clip clips[a] at times[a] and is posed with the
+ * result: rt_crowd_set_blend with one layer per actor, without a mask (one layer without a mask is rt_skeleton_set_time, bit for bit).  One
+ * upload and one kernel, as for rt_crowd_set_blend.  The refusals are rt_skeleton_set_time's, and the message names the actor: a null
+ * argument or a NaN time is RT_ERR_INVALID_ARG, an unknown clip RT_ERR_STATE (after rt_skeleton_clear_clips: every clip); every actor's time
+ * is looked at before any actor's clip, and the first bad actor wins. */
+int rt_crowd_set_times(rt_crowd *c, const uint32_t *clips /* n_actors */, const float *times /* n_actors */);   /* host arrays */
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): every actor blends and layers clips as rt_skeleton_set_blend
+ * does, all actors with n_layers layers, actor a's at layers[a * n_layers].  The per-actor records -- where the two keys and the reference
+ * keys of a layer's clip stand, `a`, weight, mask, mode -- cross to the device in ONE upload ordered on the context's stream, and ONE kernel
+ * blends and poses every actor.  The call does not wait for the device: the records are staged in two page-locked slots written in turn,
+ * each with an event recorded behind the copy out of it, and a slot is waited for only while the copy of the call before last has not
+ * passed -- back-to-back calls are safe and wait only when they run two uploads ahead of the device.  Each actor's list is held to the
+ * rules of rt_skeleton_set_blend unchanged, and the message names the actor and the layer; the first bad actor wins, and every actor is
+ * held to the first group (RT_ERR_INVALID_ARG: mode, additive base, RT_SKELETON_CURRENT_POSE above layer 0, NaN time) before any actor is
+ * held to the second (RT_ERR_STATE: unknown clip, unknown mask, RT_SKELETON_CURRENT_POSE before the crowd's first pose -- the message names
+ * rt_crowd_set_poses).  A device table that cannot grow is RT_ERR_OOM.  Nothing changes when the call refuses. */
+int rt_crowd_set_blend(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers /* n_actors x n_layers, actor major, host */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local poses of actors first_actor .. first_actor + count - 1.
+ * This and the calls below that return what a pose made are RT_ERR_STATE before the first pose (the message names rt_crowd_set_poses); a
+ * range beyond the actors is RT_ERR_INVALID_ARG (the message gives both numbers); the reads synchronise. */
+int rt_crowd_read_pose(rt_crowd *c, uint32_t first_actor, uint32_t count, float *trs /* count x n_joints x 10 */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): W_j of those actors, count x n_joints x 12 */
+int rt_crowd_read_joints(rt_crowd *c, uint32_t first_actor, uint32_t count, float *world3x4 /* count x n_joints x 12 */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): M_j of those actors, count x n_joints x 12 */
+int rt_crowd_read_palette(rt_crowd *c, uint32_t first_actor, uint32_t count, float *palette3x4 /* count x n_joints x 12 */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): W where it lives, n_actors x n_joints x 12 floats of device
+ * memory, actor major, that every later posing call overwrites on the context's stream and rt_crowd_destroy frees */
+int rt_crowd_get_joints_device_ptr(rt_crowd *c, void **ptr);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the palettes where they live, likewise */
+int rt_crowd_get_palette_device_ptr(rt_crowd *c, void **ptr);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): poses a skinned model from actor `actor`'s palette: exactly
+ * rt_model_set_bones(m, palette + actor * n_joints * 12, RT_MEM_DEVICE).  The refusals are those of rt_model_set_bones_from_skeleton, with
+ * the crowd in the skeleton's place; an actor >= n_actors is RT_ERR_INVALID_ARG (the message gives both numbers). */
+int rt_model_set_bones_from_crowd(rt_model *m, rt_crowd *c, uint32_t actor);
 
 /* Attached instances -- EXTENSIONS: instance transforms that come from the device.  The reference's only statement of a transform is addModel
  * (RtScene.h:30); what these calls write is the Transform member of the instance descriptor
@@ -539,6 +598,20 @@ int rt_scene_detach_instances(rt_scene *s, uint32_t first, uint32_t count);
 /* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): *sk = the skeleton instance `instance`
  * is attached to (NULL: none) and *joint its joint; either pointer may be NULL; an instance out of range is RT_ERR_STATE */
 int rt_scene_get_instance_attachment(const rt_scene *s, uint32_t instance, rt_skeleton **sk /* NULL: none */, uint32_t *joint);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): ATTACHMENTS TO A CROWD are
+ * attachments as above with W taken from the actor's slice: instance first + k follows joints[k] of actor actors[k] of `c`, T_i = W_j of
+ * that actor o local_i.  The pending rule (the crowd counts one pose per posing call), the refusal of an update or build before the crowd's
+ * first pose (the message names rt_crowd_set_poses), the refusal of transform setters, detaching, retention until the scene goes and
+ * "update == build, with attachments" are those of a skeleton's attachments, by the same code.  A null argument (s, c, actors, joints) is
+ * RT_ERR_INVALID_ARG; so is a joint >= n_joints or an actor >= n_actors (the message names the entry and both numbers); a range beyond the
+ * instances and a crowd of another context are RT_ERR_STATE.  rt_scene_get_instance_attachment reports skeleton attachments only: none for
+ * an instance attached to a crowd.  rt_scene_detach_instances lets go of either kind. */
+int rt_scene_attach_instances_crowd(rt_scene *s, uint32_t first, uint32_t count, rt_crowd *c,
+                                    const uint32_t *actors /* count */, const uint32_t *joints /* count */, const float *local3x4 /* count x 12, or NULL */);
+/* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above): *c = the crowd instance `instance`
+ * is attached to (NULL: none, also for one attached to a skeleton), *actor and *joint where; each pointer may be NULL; an instance out of
+ * range is RT_ERR_STATE */
+int rt_scene_get_instance_crowd_attachment(const rt_scene *s, uint32_t instance, rt_crowd **c /* NULL: none */, uint32_t *actor, uint32_t *joint);
 /* EXTENSION (TopLevelASGenerator.cpp:344-362, RtScene.h:30 and TopLevelASGenerator.h:144-163 as above; RtModel.cpp:26 and
  * BottomLevelASGenerator.h:136-176 as for the skeleton's other calls): W_j where it lives, n_joints x 12 floats of device memory that every
  * later pose overwrites on the context's stream, as rt_skeleton_get_palette_device_ptr; RT_ERR_STATE before the first pose */
