@@ -17,7 +17,7 @@ SRCS = $(CSRC)/rt_api.hip $(CSRC)/rt_scene.hip $(CSRC)/rt_model.hip $(CSRC)/rt_s
 HDRS = $(wildcard $(CSRC)/*.h) include/dxr_amd.h include/dxr_amd_types.h
 OBJS = $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 
-BIN = $(LIBDIR)/progressive $(LIBDIR)/realtime_denoise $(LIBDIR)/realtime_animated $(LIBDIR)/realtime_deform $(LIBDIR)/realtime_skinned $(LIBDIR)/realtime_morph $(LIBDIR)/realtime_character $(LIBDIR)/realtime_blend $(LIBDIR)/realtime_reach $(LIBDIR)/realtime_machines $(LIBDIR)/realtime_crowd $(LIBDIR)/realtime_visibility $(LIBDIR)/test_wrapper $(LIBDIR)/progressive_multi
+BIN = $(LIBDIR)/progressive $(LIBDIR)/realtime_denoise $(LIBDIR)/realtime_animated $(LIBDIR)/realtime_deform $(LIBDIR)/realtime_skinned $(LIBDIR)/realtime_morph $(LIBDIR)/realtime_character $(LIBDIR)/realtime_blend $(LIBDIR)/realtime_reach $(LIBDIR)/realtime_machines $(LIBDIR)/realtime_crowd $(LIBDIR)/realtime_crowd_device $(LIBDIR)/realtime_visibility $(LIBDIR)/test_wrapper $(LIBDIR)/progressive_multi
 CXX ?= g++
 HOSTFLAGS = -O2 -std=c++17 -Wall -Iinclude -Idxrexperiments_amd/include
 HOSTLINK = -L$(LIBDIR) -ldxrexperiments_amd -L/opt/rocm/lib -Wl,-rpath,'$$ORIGIN' -Wl,-rpath-link,/opt/rocm/lib
@@ -61,6 +61,9 @@ $(LIBDIR)/realtime_machines: examples/realtime_machines.cpp $(LIB) $(wildcard dx
 	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
 
 $(LIBDIR)/realtime_crowd: examples/realtime_crowd.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)
+	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
+
+$(LIBDIR)/realtime_crowd_device: examples/realtime_crowd_device.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)
 	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
 
 $(LIBDIR)/realtime_visibility: examples/realtime_visibility.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)

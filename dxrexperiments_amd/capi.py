@@ -110,6 +110,9 @@ SIGNATURES = {
     "rt_crowd_set_poses": (_i, [_p, _p, _u32]),
     "rt_crowd_set_times": (_i, [_p, _p, _p]),
     "rt_crowd_set_blend": (_i, [_p, _u32, _p]),
+    "rt_crowd_set_layout": (_i, [_p, _u32, _p]),
+    "rt_crowd_get_layout": (_i, [_p, _pu]),
+    "rt_crowd_set_blend_device": (_i, [_p, _p, _p]),
     "rt_crowd_read_pose": (_i, [_p, _u32, _u32, _p]),
     "rt_crowd_read_joints": (_i, [_p, _u32, _u32, _p]),
     "rt_crowd_read_palette": (_i, [_p, _u32, _u32, _p]),
@@ -747,6 +750,29 @@ class Crowd:
         if a.ndim != 2 or a.shape[0] != self.n_actors:
             raise RtError(-1, "set_blend: layers of shape %s for a crowd of %d actors" % (a.shape, self.n_actors))
         _check(lib().rt_crowd_set_blend(self.h, a.shape[1], _ptr(a)))
+
+    def set_layout(self, layers):
+        """the crowd's layout -- clip, mask, mode and a default weight per actor and layer, checked and uploaded once; the times are not
+        read: what set_blend takes.  set_blend_device then poses from times and weights in device memory"""
+        if isinstance(layers, np.ndarray) and layers.dtype == T.SKELETON_LAYER:
+            a = layers
+        else:
+            a = np.stack([Skeleton.layers(mine) for mine in layers]) if len(layers) else np.zeros((0, 0), T.SKELETON_LAYER)
+        a = np.ascontiguousarray(a)
+        if a.ndim != 2 or a.shape[0] != self.n_actors:
+            raise RtError(-1, "set_layout: layers of shape %s for a crowd of %d actors" % (a.shape, self.n_actors))
+        _check(lib().rt_crowd_set_layout(self.h, a.shape[1], _ptr(a)))
+
+    def layout(self):
+        """the layers of the layout; 0: none"""
+        n = C.c_uint32()
+        _check(lib().rt_crowd_get_layout(self.h, C.byref(n)))
+        return n.value
+
+    def set_blend_device(self, times_ptr, weights_ptr=None):
+        """every actor posed from the layout and n_actors x n_layers float32 times -- and weights, or None: the layout's -- in device memory
+        (addresses, e.g. DeviceBuffer.ptr or a tensor's data_ptr(), written on the context's stream): one launch, nothing uploaded"""
+        _check(lib().rt_crowd_set_blend_device(self.h, C.c_void_p(times_ptr), None if weights_ptr is None else C.c_void_p(weights_ptr)))
 
     def _read(self, fn, width, first, count):
         n = self.n_actors - first if count is None else count

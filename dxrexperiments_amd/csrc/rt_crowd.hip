@@ -2,7 +2,9 @@
 // reads its skeleton's hierarchy, inverse binds, clips and masks where they live and owns the actors' poses, world matrices and palettes,
 // actor major; what reads a skeleton's palette or W -- the skin kernel, the scene's gather kernel -- reads an actor's slice unchanged.  The
 // arithmetic is rt_pose_device.h's, shared with rt_skeleton.hip statement for statement: actor a is, bit for bit, a skeleton given the same
-// call.  No reference counterpart, as for rt_skeleton.hip (libs/DXRFramework/RtModel.cpp:26 drops bones and node animation).
+// call.  rt_crowd_set_layout + rt_crowd_set_blend_device drive a crowd from device memory: the host checks and uploads, once, which clip, mask
+// and mode every layer of every actor has, and a posing call is then the launch alone, its times and weights read where the caller keeps them.
+// No reference counterpart, as for rt_skeleton.hip (libs/DXRFramework/RtModel.cpp:26 drops bones and node animation).
 #include <cmath>
 #include <new>
 
@@ -25,16 +27,33 @@ using namespace rtd;
 // LDS is dynamic and sized by the rig (rt_crowd_lds_bytes): W component major with a row of n_joints floats per component -- the lanes of a
 // wave read consecutive words -- then the level table and the level offsets.  `pose` is read and written in place by the lane that owns the
 // joint: not __restrict__.
-template <uint32_t BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_crowd_pose(const rt_blend_layer *__restrict__ layers, uint32_t n_layers, const uint32_t *__restrict__ table,
+// The kernel has TWO FORMS.  DEVICE == false: `src` is the table of records the host packed and uploaded (rt_crowd_set_times, _set_blend),
+// or nothing it reads (rt_crowd_set_poses).  DEVICE == true (rt_crowd_set_blend_device): `src` names the slots of the crowd's layout and the
+// caller's times and weights, all n_actors x n_layers in device memory.  Lane k < n_layers of the block's first wave loads slot (actor, k), its
+// time and its weight, finds the segment in the clip's device copy of its key times and writes record k -- rt_crowd_layer_of_slot, the text
+// the host packs with -- into a table at the BASE of the block's LDS (rt_crowd_lds_bytes_device), so that the records never touch global
+// memory; one barrier; then the phases above run as they are, with blend_joint reading that table (the same word for every lane: a
+// broadcast).  Nothing of a time or a weight becomes an address except the segment index, which rt_skeleton_segment keeps inside the clip
+// for any 32 bits: no validation on the device, and none needed.
+template <bool DEVICE> struct CrowdSource;
+template <> struct CrowdSource<false> { using type = const rt_blend_layer *__restrict__; };
+struct CrowdDeviceSource {
+    const rt_crowd_slot *slots;          // [n_actors][n_layers]
+    const float *times, *weights;        // [n_actors][n_layers] each; weights == nullptr: the slots' own
+};
+template <> struct CrowdSource<true> { using type = CrowdDeviceSource; };
+
+template <uint32_t BLOCK, bool DEVICE>
+__global__ void __launch_bounds__(BLOCK) k_crowd_pose(typename CrowdSource<DEVICE>::type src, uint32_t n_layers, const uint32_t *__restrict__ table,
                                                       const uint32_t *__restrict__ level_offsets, uint32_t n_levels, uint32_t n_joints,
                                                       const float *__restrict__ inverse_bind, float *pose, float *__restrict__ joints,
                                                       float *__restrict__ palette)
 {
-    extern __shared__ float s_dyn[];
+    extern __shared__ __align__(8) float s_dyn[];
     const uint32_t N = n_joints;
     float *s_w = s_dyn;                                          // [12][N]
-    uint32_t *s_table = (uint32_t *)(s_dyn + 12u * (size_t)N);   // [N]
+    if constexpr (DEVICE) s_w += (sizeof(rt_blend_layer) / sizeof(float)) * (size_t)n_layers;      // (behind the records)
+    uint32_t *s_table = (uint32_t *)(s_w + 12u * (size_t)N);     // [N]
     uint32_t *s_off = s_table + N;                               // [n_levels + 1] (n_levels <= N)
     auto load = [&](uint32_t j, float M[12]) {
 #pragma unroll
@@ -45,7 +64,20 @@ __global__ void __launch_bounds__(BLOCK) k_crowd_pose(const rt_blend_layer *__re
         for (int e = 0; e < 12; e++) s_w[e * N + j] = M[e];
     };
     const uint32_t tid = threadIdx.x, actor = blockIdx.x;
-    const rt_blend_layer *mine = layers + (size_t)actor * n_layers;
+    const rt_blend_layer *mine;
+    if constexpr (DEVICE) {
+        rt_blend_layer *s_layers = (rt_blend_layer *)s_dyn;      // [n_layers] (n_layers <= RT_SKELETON_MAX_LAYERS < a wave)
+        if (tid < n_layers) {
+            const size_t e = (size_t)actor * n_layers + tid;
+            const rt_crowd_slot slot = src.slots[e];
+            rt_blend_layer b;
+            rt_crowd_layer_of_slot(slot, n_joints, src.times[e], src.weights ? src.weights[e] : slot.weight, b);
+            s_layers[tid] = b;
+        }
+        __syncthreads();
+        mine = s_layers;
+    } else
+        mine = src + (size_t)actor * n_layers;
     pose += RT_SKELETON_POSE_FLOATS * (size_t)N * actor;
     joints += 12u * (size_t)N * actor;
     palette += 12u * (size_t)N * actor;
@@ -91,23 +123,30 @@ __global__ void __launch_bounds__(BLOCK) k_crowd_pose(const rt_blend_layer *__re
     }
 }
 
-// c->pose holds every actor's held pose, and (n_layers > 0) c->layers every actor's records: ONE launch, queued on the context's stream
-int pose_crowd(rt_crowd *c, uint32_t n_layers)
+// c->pose holds every actor's held pose, and (n_layers > 0) c->layers every actor's records -- or (`device`) c->slots every actor's slots,
+// and `device` names the caller's times and weights: ONE launch, queued on the context's stream
+template <uint32_t BLOCK>
+void launch_pose(rt_crowd *c, uint32_t n_layers, const CrowdDeviceSource *device)
 {
     const rt_skeleton *sk = c->sk;
     hipStream_t st = c->ctx->stream;
-    const uint32_t block = rt_crowd_block(c->n_joints);
-    const size_t lds = rt_crowd_lds_bytes(c->n_joints);
-    const rt_blend_layer *layers = c->layers.as<rt_blend_layer>();
     const uint32_t *table = sk->table.as<uint32_t>(), *off = sk->d_level_offsets.as<uint32_t>();
     const float *ib = sk->inverse_bind.as<float>();
     float *pose = c->pose.as<float>(), *joints = c->joints.as<float>(), *palette = c->palette.as<float>();
-    if (block == 64u)
-        k_crowd_pose<64><<<c->n_poses, 64, lds, st>>>(layers, n_layers, table, off, sk->n_levels, c->n_joints, ib, pose, joints, palette);
-    else if (block == 128u)
-        k_crowd_pose<128><<<c->n_poses, 128, lds, st>>>(layers, n_layers, table, off, sk->n_levels, c->n_joints, ib, pose, joints, palette);
+    if (device)
+        k_crowd_pose<BLOCK, true><<<c->n_poses, BLOCK, rt_crowd_lds_bytes_device(c->n_joints, n_layers), st>>>(*device, n_layers, table, off, sk->n_levels, c->n_joints, ib,
+                                                                                                            pose, joints, palette);
     else
-        k_crowd_pose<256><<<c->n_poses, 256, lds, st>>>(layers, n_layers, table, off, sk->n_levels, c->n_joints, ib, pose, joints, palette);
+        k_crowd_pose<BLOCK, false><<<c->n_poses, BLOCK, rt_crowd_lds_bytes(c->n_joints), st>>>(c->layers.as<rt_blend_layer>(), n_layers, table, off, sk->n_levels,
+                                                                                             c->n_joints, ib, pose, joints, palette);
+}
+
+int pose_crowd(rt_crowd *c, uint32_t n_layers, const CrowdDeviceSource *device = nullptr)
+{
+    const uint32_t block = rt_crowd_block(c->n_joints);
+    if (block == 64u) launch_pose<64>(c, n_layers, device);
+    else if (block == 128u) launch_pose<128>(c, n_layers, device);
+    else launch_pose<256>(c, n_layers, device);
     HIP_TRY(hipGetLastError());
     c->posed = true;
     c->pose_count++;          // once for the whole crowd (scenes with instances attached to an actor's joint compare it: rt_scene_update)
@@ -141,15 +180,24 @@ int crowd_stage(rt_crowd *c, size_t bytes, CrowdStage **out)
     return RT_OK;
 }
 
+// the skeleton's clips and masks as the packing reads them
+void clips_and_masks(const rt_skeleton *sk, std::vector<rt_crowd_clip> &clips, std::vector<const float *> &masks)
+{
+    clips.resize(sk->clips.size());
+    masks.resize(sk->masks.size());
+    for (size_t k = 0; k < clips.size(); k++)
+        clips[k] = {(uint32_t)sk->clips[k].times.size(), sk->clips[k].times.data(), sk->clips[k].keys.as<float>(), sk->clips[k].d_times.as<float>()};
+    for (size_t k = 0; k < masks.size(); k++) masks[k] = sk->masks[k].as<float>();
+}
+
 // every actor's validated layers: packed into a staging slot, uploaded -- the one upload of the call -- and posed
 int blend_crowd(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers)
 {
     rt_context *ctx = c->ctx;
     const rt_skeleton *sk = c->sk;
-    std::vector<rt_crowd_clip> clips(sk->clips.size());
-    std::vector<const float *> masks(sk->masks.size());
-    for (size_t k = 0; k < clips.size(); k++) clips[k] = {(uint32_t)sk->clips[k].times.size(), sk->clips[k].times.data(), sk->clips[k].keys.as<float>()};
-    for (size_t k = 0; k < masks.size(); k++) masks[k] = sk->masks[k].as<float>();
+    std::vector<rt_crowd_clip> clips;
+    std::vector<const float *> masks;
+    clips_and_masks(sk, clips, masks);
     const size_t bytes = sizeof(rt_blend_layer) * (size_t)c->n_poses * n_layers;
     RT_TRY(rt_use_device(ctx));
     // (what can refuse comes first: a table that cannot grow keeps the one it has -- nothing is queued that reads it -- and nothing has changed)
@@ -161,6 +209,33 @@ int blend_crowd(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers)
     HIP_TRY(hipEventRecord(s->event, ctx->stream));
     s->in_flight = true;
     return pose_crowd(c, n_layers);
+}
+
+// every actor's list held to rt_crowd_validate_layers; RT_OK, or the refusal under the name of the call that asked
+int check_layers(const rt_crowd *c, const char *who, uint32_t n_layers, const rt_skeleton_layer *layers)
+{
+    const uint32_t n_clips = (uint32_t)c->sk->clips.size(), n_masks = (uint32_t)c->sk->masks.size();
+    uint32_t a = 0, bad = 0;
+    const int what = rt_crowd_validate_layers(c->n_poses, n_layers, layers, n_clips, n_masks, c->posed, &a, &bad);
+    const rt_skeleton_layer *l = what > 2 ? &layers[(size_t)a * n_layers + bad] : nullptr;
+    switch (what) {
+    case 0: return RT_OK;
+    case 1: rt_set_error("%s: null argument", who); return RT_ERR_INVALID_ARG;
+    case 2: rt_set_error("%s: %u layers: 1 .. %u are supported", who, n_layers, RT_SKELETON_MAX_LAYERS); return RT_ERR_INVALID_ARG;
+    case 3: rt_set_error("%s: actor %u: layer %u has mode %u: RT_LAYER_BLEND (0) or RT_LAYER_ADDITIVE (1)", who, a, bad, l->mode); return RT_ERR_INVALID_ARG;
+    case 4: rt_set_error("%s: actor %u: layer 0 is additive: the base layer is RT_LAYER_BLEND", who, a); return RT_ERR_INVALID_ARG;
+    case 5: rt_set_error("%s: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: only layer 0 may", who, a, bad); return RT_ERR_INVALID_ARG;
+    case 6: rt_set_error("%s: actor %u: the time of layer %u is NaN", who, a, bad); return RT_ERR_INVALID_ARG;
+    case 7:
+        rt_set_error("%s: actor %u: layer %u names clip %u: the skeleton has %u (rt_skeleton_add_clip adds one)", who, a, bad, l->clip, n_clips);
+        return RT_ERR_STATE;
+    case 8:
+        rt_set_error("%s: actor %u: layer %u names mask %u: the skeleton has %u (rt_skeleton_add_mask adds one)", who, a, bad, l->mask, n_masks);
+        return RT_ERR_STATE;
+    default:
+        rt_set_error("%s: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: the crowd has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", who, a, bad);
+        return RT_ERR_STATE;
+    }
 }
 
 int require_pose(const rt_crowd *c, const char *who)
@@ -254,29 +329,66 @@ int rt_crowd_set_poses(rt_crowd *c, const float *trs, uint32_t mem)
 int rt_crowd_set_blend(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers)
 {
     RT_REQUIRE(c && layers, "null argument");
-    const uint32_t n_clips = (uint32_t)c->sk->clips.size(), n_masks = (uint32_t)c->sk->masks.size();
-    uint32_t a = 0, bad = 0;
-    const int what = rt_crowd_validate_layers(c->n_poses, n_layers, layers, n_clips, n_masks, c->posed, &a, &bad);
-    const rt_skeleton_layer *l = what > 2 ? &layers[(size_t)a * n_layers + bad] : nullptr;
-    switch (what) {
-    case 0: break;
-    case 1: rt_set_error("rt_crowd_set_blend: null argument"); return RT_ERR_INVALID_ARG;
-    case 2: rt_set_error("rt_crowd_set_blend: %u layers: 1 .. %u are supported", n_layers, RT_SKELETON_MAX_LAYERS); return RT_ERR_INVALID_ARG;
-    case 3: rt_set_error("rt_crowd_set_blend: actor %u: layer %u has mode %u: RT_LAYER_BLEND (0) or RT_LAYER_ADDITIVE (1)", a, bad, l->mode); return RT_ERR_INVALID_ARG;
-    case 4: rt_set_error("rt_crowd_set_blend: actor %u: layer 0 is additive: the base layer is RT_LAYER_BLEND", a); return RT_ERR_INVALID_ARG;
-    case 5: rt_set_error("rt_crowd_set_blend: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: only layer 0 may", a, bad); return RT_ERR_INVALID_ARG;
-    case 6: rt_set_error("rt_crowd_set_blend: actor %u: the time of layer %u is NaN", a, bad); return RT_ERR_INVALID_ARG;
-    case 7:
-        rt_set_error("rt_crowd_set_blend: actor %u: layer %u names clip %u: the skeleton has %u (rt_skeleton_add_clip adds one)", a, bad, l->clip, n_clips);
-        return RT_ERR_STATE;
-    case 8:
-        rt_set_error("rt_crowd_set_blend: actor %u: layer %u names mask %u: the skeleton has %u (rt_skeleton_add_mask adds one)", a, bad, l->mask, n_masks);
-        return RT_ERR_STATE;
-    default:
-        rt_set_error("rt_crowd_set_blend: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: the crowd has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", a, bad);
+    RT_TRY(check_layers(c, "rt_crowd_set_blend", n_layers, layers));
+    return blend_crowd(c, n_layers, layers);
+}
+
+int rt_crowd_set_layout(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers)
+{
+    RT_REQUIRE(c && layers, "null argument");
+    if (n_layers < 1u || n_layers > RT_SKELETON_MAX_LAYERS) return check_layers(c, "rt_crowd_set_layout", n_layers, layers);     // (refuses, and reads no entry)
+    rt_context *ctx = c->ctx;
+    const rt_skeleton *sk = c->sk;
+    const size_t n = (size_t)c->n_poses * n_layers;
+    std::vector<rt_skeleton_layer> mine;                 // the caller's list without its times
+    std::vector<rt_crowd_slot> slots;
+    std::vector<rt_crowd_clip> clips;
+    std::vector<const float *> masks;
+    try {
+        mine.resize(n);
+        slots.resize(n);
+        clips_and_masks(sk, clips, masks);
+    } catch (const std::bad_alloc &) {
+        rt_set_error("out of host memory");
+        return RT_ERR_OOM;
+    }
+    rt_crowd_layout_layers(n, layers, mine.data());
+    RT_TRY(check_layers(c, "rt_crowd_set_layout", n_layers, mine.data()));
+    rt_crowd_pack_slots(c->n_poses, n_layers, mine.data(), clips.data(), masks.data(), slots.data());
+    RT_TRY(rt_use_device(ctx));
+    // a buffer of its own: a launch already queued reads the slots the crowd has, and a refusal here leaves them, and the layout, as they were
+    DevBuf fresh;
+    RT_TRY(rt_upload(ctx, fresh, slots.data(), sizeof(rt_crowd_slot) * n));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vector goes out of scope, and nothing queued reads the old slots any more)
+    c->slots = std::move(fresh);
+    c->layout_layers = n_layers;
+    c->layout_clip_gen = sk->clip_gen;
+    c->layout_mask_gen = sk->mask_gen;
+    return RT_OK;
+}
+
+int rt_crowd_get_layout(const rt_crowd *c, uint32_t *n_layers)
+{
+    RT_REQUIRE(c && n_layers, "null argument");
+    *n_layers = c->layout_layers;
+    return RT_OK;
+}
+
+int rt_crowd_set_blend_device(rt_crowd *c, const float *times, const float *weights)
+{
+    RT_REQUIRE(c && times, "null argument");
+    if (c->layout_layers == 0u) {
+        rt_set_error("rt_crowd_set_blend_device: the crowd has no layout (rt_crowd_set_layout gives it one)");
         return RT_ERR_STATE;
     }
-    return blend_crowd(c, n_layers, layers);
+    if (c->layout_clip_gen != c->sk->clip_gen || c->layout_mask_gen != c->sk->mask_gen) {
+        rt_set_error("rt_crowd_set_blend_device: the layout is stale: the skeleton's %s were cleared after it was set (rt_crowd_set_layout sets a new one)",
+                     c->layout_clip_gen != c->sk->clip_gen ? "clips" : "masks");
+        return RT_ERR_STATE;
+    }
+    RT_TRY(rt_use_device(c->ctx));
+    const CrowdDeviceSource src = {c->slots.as<rt_crowd_slot>(), times, weights};
+    return pose_crowd(c, c->layout_layers, &src);
 }
 
 int rt_crowd_set_times(rt_crowd *c, const uint32_t *clips, const float *times)

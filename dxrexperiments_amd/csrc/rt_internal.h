@@ -394,6 +394,7 @@ struct rt_model : rt_handle {
 // rt_skeleton_create (rt_skeleton.hip): a joint hierarchy, its current pose and the palette a skin reads
 struct SkeletonClip {
     std::vector<float> times;    // n_keys, ascending strictly
+    DevBuf d_times;              // ... and their copy on the device, which the slots of a crowd's layout name (k_crowd_pose searches it)
     DevBuf keys;                 // float[n_keys][10][n_joints]: component major within a key, so that the lanes of a wave read 64 consecutive floats
 };
 
@@ -425,10 +426,12 @@ struct rt_skeleton : rt_pose_source {
     DevBuf palette;              // float[n_joints][12]: M_j = W_j o inverse_bind_j, what rt_model_set_bones_from_skeleton hands to the skin kernel
     std::vector<SkeletonClip> clips;
     std::vector<DevBuf> masks;   // rt_skeleton_add_mask: float[n_joints] each, one weight per joint of a blend layer (rt_skeleton_set_blend)
+    uint64_t clip_gen = 0, mask_gen = 0;     // bumped by rt_skeleton_clear_clips / _clear_masks when they free something: a crowd's layout holds device addresses of clips and masks and records both (adding keeps every address, and bumps nothing)
 };
 
 // rt_crowd_create (rt_crowd.hip): n_poses = n_actors poses of one skeleton, which it retains and whose hierarchy, inverse binds, clips and
-// masks it reads where they live.  Every posing call is one upload of the actors' layer records and one launch of k_crowd_pose.
+// masks it reads where they live.  Every posing call is one upload of the actors' layer records and one launch of k_crowd_pose, or
+// (rt_crowd_set_blend_device) the launch alone, over the slots of a layout uploaded once.
 struct CrowdStage {              // one slot of page-locked staging for that upload, and the event behind the copy out of it
     void *block = nullptr;
     size_t bytes = 0;
@@ -443,6 +446,9 @@ struct rt_crowd : rt_pose_source {
     DevBuf layers;               // rt_blend_layer[n_actors][n_layers] of the call last queued (rt_skeleton.h)
     CrowdStage stage[2];         // written in turn: a slot is the host's again once its own event has passed (rt_crowd.hip: crowd_stage)
     uint32_t next_stage = 0;
+    DevBuf slots;                // rt_crowd_slot[n_actors][layout_layers] of rt_crowd_set_layout (rt_crowd.h)
+    uint32_t layout_layers = 0;  // 0: no layout
+    uint64_t layout_clip_gen = 0, layout_mask_gen = 0;   // the skeleton's generations when the layout was packed: it is stale once either has moved
     ~rt_crowd() override;        // (rt_crowd.hip) the staging, then the skeleton; the caller has selected the device and joined the stream
 };
 

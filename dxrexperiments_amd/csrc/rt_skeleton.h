@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/dxr_amd_types.h"     // rt_skeleton_layer, rt_skeleton_ik and their constants
+#include "rt_xform.h"                        // RT_HOST_DEVICE: the segment and the layer record are found by ONE text, on the host and in k_crowd_pose
 
 #define RT_SKELETON_MAX_JOINTS 65536u    // the skin's bone limit (RT_SKIN_MAX_BONES): a joint is a bone, and fits 16 bits
 #define RT_SKELETON_POSE_FLOATS 10u      // a joint of a pose: tx ty tz  qx qy qz qw  sx sy sz
@@ -91,7 +92,11 @@ static inline int rt_skeleton_validate_times(uint32_t n_keys, const float *times
 // The segment of validated key times that holds t (not NaN), and where t stands in it: one key, or t at or before the first, gives (0, 0);
 // t at or beyond the last (n_keys - 2, 1); otherwise i is the largest key with times[i] <= t and a = (t - times[i]) / (times[i + 1] -
 // times[i]), two fp32 differences and one fp32 quotient.
-static inline void rt_skeleton_segment(uint32_t n_keys, const float *times, float t, uint32_t *i_out, float *a_out)
+// The host never hands it a NaN (every host call refuses one), but rt_crowd_set_blend_device reads its times from device memory unseen, so
+// what a NaN does is part of the statement: with one key, (0, 0); otherwise both range tests are false, every comparison of the search is
+// false, so hi comes down to 1 and lo stays 0: (0, NaN).  Whatever the 32 bits of t, every read is times[0 .. n_keys - 1] and i <= n_keys - 2
+// (0 with one key): the two keys a record names exist.
+RT_HOST_DEVICE static inline void rt_skeleton_segment(uint32_t n_keys, const float *times, float t, uint32_t *i_out, float *a_out)
 {
     if (n_keys == 1u || t <= times[0]) { *i_out = 0u; *a_out = 0.0f; return; }
     if (t >= times[n_keys - 1u]) { *i_out = n_keys - 2u; *a_out = 1.0f; return; }
@@ -154,24 +159,36 @@ struct rt_blend_layer {
     uint32_t mode, pad;
 };
 
-// Layer k of a validated list, packed.  `times` (n_keys of them) and `keys` (device memory, float[n_keys][10][n_joints]) are the layer's
-// clip -- not read for RT_SKELETON_CURRENT_POSE, where key_a stays null -- and `mask` the layer's mask in device memory or nullptr; the base
-// layer's mask is dropped.  The segment (i, a) is found here, on the host, by rt_skeleton_segment; no pointer is dereferenced but `times`.
-static inline void rt_skeleton_pack_layer(const rt_skeleton_layer &l, uint32_t k, uint32_t n_joints, uint32_t n_keys, const float *times, const float *keys,
-                                          const float *mask, rt_blend_layer &b)
+// The sampling half of a layer record: the segment of `t` in the clip's `times` (n_keys of them; read HERE, so host memory for a host
+// caller and the clip's device copy inside k_crowd_pose), the two keys about it and the clip's first two in `keys` (device memory,
+// float[n_keys][10][n_joints], never dereferenced), weight, mode and mask.  keys == nullptr is RT_SKELETON_CURRENT_POSE: key_a stays null and
+// nothing is read.  ONE text for rt_skeleton_pack_layer, whose times the host validated, and for the kernel, whose times and weights are
+// any 32 bits (rt_skeleton_segment says what a NaN does).
+RT_HOST_DEVICE static inline void rt_skeleton_sample_layer(uint32_t n_joints, uint32_t n_keys, const float *times, const float *keys, float t, float weight,
+                                                           uint32_t mode, const float *mask, rt_blend_layer &b)
 {
     const size_t per_key = RT_SKELETON_POSE_FLOATS * (size_t)n_joints;
     b = rt_blend_layer();
-    b.weight = l.weight;
-    b.mode = l.mode;
-    if (l.clip == RT_SKELETON_CURRENT_POSE) return;      // (layer 0 only: key_a stays null, the kernel starts from the pose that is held)
+    b.weight = weight;
+    b.mode = mode;
+    if (!keys) return;                                   // (layer 0 only: the kernel starts from the pose that is held)
     uint32_t i = 0;
-    rt_skeleton_segment(n_keys, times, l.time, &i, &b.a);
+    rt_skeleton_segment(n_keys, times, t, &i, &b.a);
     b.ref_a = keys;
     b.ref_b = n_keys == 1u ? b.ref_a : b.ref_a + per_key;
     b.key_a = b.ref_a + per_key * i;
     b.key_b = n_keys == 1u ? b.key_a : b.key_a + per_key;
-    if (k > 0u && l.mask != RT_SKELETON_NO_MASK) b.mask = mask;
+    b.mask = mask;
+}
+
+// Layer k of a validated list, packed.  `times` (n_keys of them) and `keys` (device memory, float[n_keys][10][n_joints]) are the layer's
+// clip -- not read for RT_SKELETON_CURRENT_POSE, where key_a stays null -- and `mask` the layer's mask in device memory or nullptr; the base
+// layer's mask is dropped.  The segment (i, a) is found here, on the host, by rt_skeleton_sample_layer; no pointer is dereferenced but `times`.
+static inline void rt_skeleton_pack_layer(const rt_skeleton_layer &l, uint32_t k, uint32_t n_joints, uint32_t n_keys, const float *times, const float *keys,
+                                          const float *mask, rt_blend_layer &b)
+{
+    const bool held = l.clip == RT_SKELETON_CURRENT_POSE;
+    rt_skeleton_sample_layer(n_joints, n_keys, times, held ? nullptr : keys, l.time, l.weight, l.mode, k > 0u && l.mask != RT_SKELETON_NO_MASK ? mask : nullptr, b);
 }
 
 // 0: the constraints describe one solve of a skeleton of n_joints joints with these parents, posed or not.  Else what is wrong, and bad[0]

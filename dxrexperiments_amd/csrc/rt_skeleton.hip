@@ -283,7 +283,8 @@ int rt_skeleton_add_clip(rt_skeleton *sk, uint32_t n_keys, const float *times, c
     clip.times.assign(times, times + n_keys);
     RT_TRY(rt_use_device(ctx));
     RT_TRY(rt_upload(ctx, clip.keys, keys.data(), sizeof(float) * keys.size()));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vector goes out of scope)
+    RT_TRY(rt_upload(ctx, clip.d_times, times, sizeof(float) * (size_t)n_keys));      // (the copy a crowd's layout names: rt_crowd_set_blend_device searches it on the device)
+    HIP_TRY(hipStreamSynchronize(ctx->stream));         // (the vector goes out of scope, and the caller's times are its own again)
     sk->clips.push_back(std::move(clip));               // (earlier clips keep their ids and their buffers)
     if (clip_out) *clip_out = (uint32_t)sk->clips.size() - 1u;
     return RT_OK;
@@ -296,6 +297,7 @@ int rt_skeleton_clear_clips(rt_skeleton *sk)
     RT_TRY(rt_use_device(sk->ctx));
     HIP_TRY(hipStreamSynchronize(sk->ctx->stream));     // (a sampling kernel that reads a clip may still be queued)
     sk->clips.clear();
+    sk->clip_gen++;                                     // (a crowd's layout that names a clip is stale: rt_crowd_set_blend_device refuses it)
     return RT_OK;
 }
 
@@ -342,6 +344,7 @@ int rt_skeleton_clear_masks(rt_skeleton *sk)
     RT_TRY(rt_use_device(sk->ctx));
     HIP_TRY(hipStreamSynchronize(sk->ctx->stream));     // (a blend kernel that reads a mask may still be queued)
     sk->masks.clear();
+    sk->mask_gen++;                                     // (likewise)
     return RT_OK;
 }
 

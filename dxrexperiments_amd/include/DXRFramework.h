@@ -169,7 +169,8 @@ namespace DXRFramework
     // reads the skeleton's clips and masks where they live and keeps it alive.  setPoses: numActors x numJoints x 10 floats; setTimes: a
     // clip and a time per actor; setBlend: numLayers layers per actor, actor major.  A skinned model takes one actor's palette with
     // setBones(crowd, actor); instances follow actors' joints with RtScene::attach(..., crowd, actors, joints): a frame is one setTimes and
-    // one RtScene::update, whatever the number of actors.
+    // one RtScene::update, whatever the number of actors.  setLayout + setBlendDevice: the clips, masks and modes of every actor's layers are
+    // checked and uploaded once, and a frame's times and weights are read from DEVICE memory -- one launch, nothing uploaded.
     class RtCrowd
     {
     public:
@@ -191,6 +192,13 @@ namespace DXRFramework
         void setPosesDevice(const float *trs) { ThrowIfFailed(rt_crowd_set_poses(mHandle, trs, RT_MEM_DEVICE)); }
         void setTimes(const uint32_t *clips, const float *times) { ThrowIfFailed(rt_crowd_set_times(mHandle, clips, times)); }
         void setBlend(const rt_skeleton_layer *layers, uint32_t numLayers) { ThrowIfFailed(rt_crowd_set_blend(mHandle, numLayers, layers)); }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): the layout -- clip, mask, mode and a default weight of
+        // numLayers layers per actor, actor major; the times are not read -- checked and uploaded once (rt_crowd_set_layout)
+        void setLayout(const rt_skeleton_layer *layers, uint32_t numLayers) { ThrowIfFailed(rt_crowd_set_layout(mHandle, numLayers, layers)); }
+        uint32_t getLayoutLayers() const { uint32_t n = 0; ThrowIfFailed(rt_crowd_get_layout(mHandle, &n)); return n; }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): every actor posed from the layout and numActors x
+        // numLayers times (and weights; nullptr: the layout's) in DEVICE memory, written on the context's stream: one launch (rt_crowd_set_blend_device)
+        void setBlendDevice(const float *times, const float *weights = nullptr) { ThrowIfFailed(rt_crowd_set_blend_device(mHandle, times, weights)); }
 
     private:
         RtCrowd(RtSkeleton::SharedPtr sk, rt_crowd *h) : mSkeleton(sk), mHandle(h) {}

@@ -411,8 +411,18 @@ int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */
  *           floats, rt_crowd_set_times rt_skeleton_set_time(clips[a], times[a]), rt_crowd_set_blend rt_skeleton_set_blend with actor a's
  *           n_layers layers, by the definitions above and by the same statements (the segment (i, a) of every sampled layer found on the
  *           host); RT_SKELETON_CURRENT_POSE on layer 0 is that actor's own held pose.  Every posing call poses ALL actors with one kernel
- *           launch and counts one pose for the whole crowd.  No per-actor IK, no times or layers read from device memory, no posing of a
- *           sub-range of actors, no rigs above 1024 joints.
+ *           launch and counts one pose for the whole crowd.  No per-actor IK, no posing of a sub-range of actors, no rigs above 1024
+ *           joints.  Times and weights may be read from device memory (rt_crowd_set_blend_device); the LAYOUT -- which clip, which mask
+ *           and which mode every layer of every actor has -- is the host's (rt_crowd_set_layout): those three are indices that become
+ *           addresses, so the host checks them once, while a time and a weight are plain floats that are taken as given.  Actor a of
+ *           rt_crowd_set_blend_device is, bit for bit, rt_crowd_set_blend with the layout's layers and time = times[a * n_layers + k],
+ *           weight = weights[a * n_layers + k] wherever no time is NaN: the segment (i, a) is then found on the device, by the statements
+ *           the host finds it with.  The host never sees those times, so a NaN is no error there.  It follows the segment's statements
+ *           literally: on a clip of one key it gives (0, 0), the key itself; on any other clip both range tests fail, every comparison of
+ *           the search fails and the search ends at i = 0, so it gives (0, NaN) and that layer's sample is NaN.  -inf samples the first
+ *           key and +inf the last, as everywhere.  For any 32 bits in `times` the two keys a layer reads are keys of its clip, and the
+ *           search reads key times inside [0, n_keys); a weight is never an address.  The call is therefore memory-safe whatever the
+ *           arrays hold, and nothing on the device validates, flags or asserts.
  * Validation is done on the host, and nothing changes when a call refuses.  Setting a pose touches no model and no scene.
  * rt_skeleton_create: a null argument is RT_ERR_INVALID_ARG; so is n_joints outside 1 .. 65536 (the skin's bone limit), and a parent that is
  * neither -1 nor < j -- parents come before children -- (the message names the joint).  inverse_bind: n_joints x 12, 3x4 row-major, as
@@ -522,6 +532,32 @@ int rt_crowd_set_times(rt_crowd *c, const uint32_t *clips /* n_actors */, const 
  * held to the second (RT_ERR_STATE: unknown clip, unknown mask, RT_SKELETON_CURRENT_POSE before the crowd's first pose -- the message names
  * rt_crowd_set_poses).  A device table that cannot grow is RT_ERR_OOM.  Nothing changes when the call refuses. */
 int rt_crowd_set_blend(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers /* n_actors x n_layers, actor major, host */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the LAYOUT of the crowd ("crowds" above): clip, mask, mode and a
+ * default weight of every layer of every actor, all actors with n_layers layers, actor a's at layers[a * n_layers].  The `time` of an entry is
+ * not read (a NaN there is fine).  Every actor's list is held to the rules of rt_crowd_set_blend with every time taken as 0 -- the same
+ * codes in the same order, every actor to the first group before any to the second, the first bad actor wins, the messages those of
+ * rt_crowd_set_blend under this call's name; RT_SKELETON_CURRENT_POSE on layer 0 needs a crowd that has a pose.  One slot per actor and
+ * layer -- where the clip's keys and its key times stand on the device, how many keys, the mask or none (the base layer's is dropped), the
+ * mode, the weight -- is uploaded ONCE; the call synchronises the stream, as rt_skeleton_add_clip does.  It poses nothing and counts no
+ * pose.  The layout stays until the next rt_crowd_set_layout; rt_crowd_set_poses, rt_crowd_set_times and rt_crowd_set_blend neither use it
+ * nor disturb it.  A null argument is RT_ERR_INVALID_ARG, a device allocation that fails RT_ERR_OOM.  Nothing changes when the call
+ * refuses: the crowd keeps the layout it had. */
+int rt_crowd_set_layout(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers /* n_actors x n_layers, actor major, host */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the layers of the crowd's layout, stale or not; 0: it has none.
+ * A null argument is RT_ERR_INVALID_ARG. */
+int rt_crowd_get_layout(const rt_crowd *c, uint32_t *n_layers /* 0: none */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): poses every actor from the crowd's layout and times and weights in
+ * DEVICE memory: layer k of actor a is the layout's layer with time = times[a * n_layers + k] and weight = weights[a * n_layers + k], or the
+ * layout's own weight when `weights` is NULL.  Exactly ONE kernel launch on the context's stream: no upload, no host loop over the actors,
+ * no wait -- the host's cost does not grow with actors or layers.  By the definition above ("crowds") actor a is, bit for bit,
+ * rt_crowd_set_blend with those layers for times that are not NaN -- pose, joints and palette -- and with a layout of one layer the call is
+ * rt_crowd_set_times with the times on the device.  It counts one pose for the whole crowd.  The values are taken as given: NaN, -inf, +inf
+ * and any weight are no error, as in rt_skeleton_solve_ik, and the call is memory-safe for any 32 bits in either array ("crowds" above says
+ * why).  The caller orders its writes of `times` and `weights` before the call on the context's stream; the arrays are the caller's again once
+ * the stream has passed the launch.  A null c or times is RT_ERR_INVALID_ARG.  RT_ERR_STATE: a crowd without a layout, and a STALE layout --
+ * rt_skeleton_clear_clips or rt_skeleton_clear_masks has freed what its slots point to since it was set (adding clips or masks keeps ids
+ * and addresses, and stales nothing); both messages name rt_crowd_set_layout.  Nothing changes when the call refuses. */
+int rt_crowd_set_blend_device(rt_crowd *c, const float *times /* n_actors x n_layers, device */, const float *weights /* n_actors x n_layers, device, or NULL */);
 /* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local poses of actors first_actor .. first_actor + count - 1.
  * This and the calls below that return what a pose made are RT_ERR_STATE before the first pose (the message names rt_crowd_set_poses); a
  * range beyond the actors is RT_ERR_INVALID_ARG (the message gives both numbers); the reads synchronise. */

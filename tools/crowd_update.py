@@ -2,7 +2,7 @@
 """What posing a crowd costs (rt_crowd_set_times = one upload + one k_crowd_pose) beside the loop it replaces: one rt_skeleton_set_time
 (k_skeleton_sample + k_skeleton_pose) per actor on separate skeletons, the code as it was before crowds.
 
-  python3 tools/crowd_update.py [--actors N ...] [--joints J] [--boxes B] [--steps S] [--warmup W] [--repeats R]
+  python3 tools/crowd_update.py [--actors N ...] [--joints J] [--boxes B] [--steps S] [--warmup W] [--repeats R] [--layers L ...] [--no-loop]
 
 A rig of J joints (default 64: the random tree of tools/skeleton_timing.py, about six levels) with a three-key clip; per actor count
 (default 16, 256 and 1000), every actor at its own time:
@@ -14,7 +14,13 @@ for the crowd with the block width the rig gives (64 lanes up to 64 joints, 128 
 for the three side by side); and for B boxes attached per actor (default 6), the device time of the rt_scene_update behind the pose (rt_scene_update_ms) under both.  Medians and interquartile
 ranges over S >= 20 samples after W warm-up samples.  For the kernels alone, run ONE actor count under
 `rocprofv3 --kernel-trace --stats -- python3 tools/crowd_update.py --actors N`: the trace names k_crowd_pose, k_skeleton_sample and
-k_skeleton_pose.  Nothing here gates: the figures are recorded."""
+k_skeleton_pose.
+With --layers L ... the crowd is also posed with L layers per actor (layer 0 the clip at the actor's time, every later layer the same clip at
+another time with weight 0.25, replacing and additive in turn), both ways: rt_crowd_set_blend (rt_crowd_set_times for L = 1) with the layers
+packed on the host and uploaded every frame, and rt_crowd_set_blend_device over a layout set once, its times read from a table of 64 frames
+that was uploaded once -- one launch, and nothing crosses.  --no-loop leaves out the loop of skeletons and the scene (10,000 skeletons are
+not what is being measured).  With DXR_AMD_LIB naming a library from before rt_crowd_set_blend_device, the host rows alone are taken.
+Nothing here gates: the figures are recorded."""
 import argparse
 import os
 import sys
@@ -53,8 +59,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--layers", type=int, nargs="*", default=[])
+    ap.add_argument("--no-loop", action="store_true")
     args = ap.parse_args()
     assert args.steps >= 20, "at least 20 timed samples"
+    if os.environ.get("DXR_AMD_LIB"):                    # an older build of the library: what it lacks is not bound, and not measured
+        import ctypes
+        older = ctypes.CDLL(capi.LIB_PATH)
+        for name in [name for name in capi.SIGNATURES if not hasattr(older, name)]:
+            del capi.SIGNATURES[name]
+    has_device = "rt_crowd_set_blend_device" in capi.SIGNATURES
     ctx = capi.Context(0)
     ev = Events(ctx)
     lib = capi.lib()
@@ -86,7 +100,7 @@ def main():
         shared = capi.Skeleton(ctx, parents, ib)
         clip = shared.add_clip(times, keys)
         crowd = capi.Crowd(shared, n_actors)
-        singles = [capi.Skeleton(ctx, parents, ib) for _ in range(n_actors)]
+        singles = [capi.Skeleton(ctx, parents, ib) for _ in range(0 if args.no_loop else n_actors)]
         for sk in singles:
             sk.add_clip(times, keys)
         handles = [sk.h for sk in singles]
@@ -107,12 +121,46 @@ def main():
                 set_time(h, clip, x)
 
         head = "%4d actors x %d joints (%d levels): " % (n_actors, n, shared.info()[1])
-        report(head + "loop of rt_skeleton_set_time (2 launches an actor)", timed(loop_frame))
+        if not args.no_loop:
+            report(head + "loop of rt_skeleton_set_time (2 launches an actor)", timed(loop_frame))
         report(head + "rt_crowd_set_times (%d-lane blocks)" % (64 if n <= 64 else 128 if n <= 128 else 256), timed(crowd_frame))
-        report(head + "loop of rt_skeleton_set_time, again (spread)", timed(loop_frame))
+        if not args.no_loop:
+            report(head + "loop of rt_skeleton_set_time, again (spread)", timed(loop_frame))
+
+        # L layers an actor: packed on the host and uploaded every frame, or a layout set once and times read from device memory
+        for n_layers in args.layers:
+            layers = np.zeros((n_actors, n_layers), T.SKELETON_LAYER)
+            layers["clip"], layers["weight"], layers["mask"] = clip, 0.25, T.SKELETON_NO_MASK
+            layers["mode"] = np.where(np.arange(n_layers) % 2 == 0, T.LAYER_BLEND, T.LAYER_ADDITIVE)[None, :]
+            layers["mode"][:, :2] = T.LAYER_BLEND
+            offsets = (np.arange(n_layers) * 0.21).astype(np.float32)
+
+            def layer_times(f):
+                return np.mod(now(f)[:, None] + offsets[None, :], np.float32(span)).astype(np.float32)
+
+            def blend_frame(f):
+                layers["time"] = layer_times(f)
+                crowd.set_blend(layers)
+
+            if n_layers > 1:
+                report(head + "rt_crowd_set_blend, %d layers (packed on the host, one upload)" % n_layers, timed(blend_frame))
+            if has_device:
+                frames = 64
+                table = ctx.upload(np.stack([layer_times(f) for f in range(frames)]))
+                stride = 4 * n_actors * n_layers
+                crowd.set_layout(layers)
+                set_device = lib.rt_crowd_set_blend_device
+                handle, base = crowd.h, table.ptr
+
+                def device_frame(f):
+                    set_device(handle, base + (f % frames) * stride, None)
+
+                report(head + "rt_crowd_set_blend_device, %d layer%s (layout set once, times on the device)" % (n_layers, "s" if n_layers > 1 else ""), timed(device_frame))
+                ctx.synchronize()
+                table.close()
 
         # the scene behind the pose: B boxes an actor, attached to its joints
-        if args.boxes:
+        if args.boxes and not args.no_loop:
             model = capi.Model(ctx, *cube())
             n_inst = n_actors * args.boxes
             joints = (np.arange(n_inst) * 7 % n).astype(np.uint32)
