@@ -1,8 +1,10 @@
 // rt_crowd.hip -- crowds (include/dxr_amd.h "Posed skeletons", crowds): n_actors poses of ONE skeleton, all made by one launch.  A crowd
 // reads its skeleton's hierarchy, inverse binds, clips and masks where they live and owns the actors' poses, world matrices and palettes,
 // actor major; what reads a skeleton's palette or W -- the skin kernel, the scene's gather kernel -- reads an actor's slice unchanged.  The
-// arithmetic is rt_pose_device.h's, shared with rt_skeleton.hip statement for statement: actor a is, bit for bit, a skeleton given the same
-// call.  rt_crowd_set_layout + rt_crowd_set_blend_device drive a crowd from device memory: the host checks and uploads, once, which clip, mask
+// arithmetic and the walk over the levels are rt_pose_device.h's, the very functions rt_skeleton.hip calls: actor a is, bit for bit, a skeleton
+// given the same call.  What the host does alike for both -- the pose check, read-backs, the copy of the caller's poses, handing a palette to
+// a skin, the text of a layer refusal -- is rt_skeleton.hip's (rt_internal.h).
+// rt_crowd_set_layout + rt_crowd_set_blend_device drive a crowd from device memory: the host checks and uploads, once, which clip, mask
 // and mode every layer of every actor has, and a posing call is then the launch alone, its times and weights read where the caller keeps them.
 // No reference counterpart, as for rt_skeleton.hip (libs/DXRFramework/RtModel.cpp:26 drops bones and node animation).
 #include <cmath>
@@ -22,8 +24,8 @@ using namespace rtd;
 //     addresses that are uniform over the block: scalar loads, and the branch on a layer's mode stays a scalar branch), written to the
 //     actor's slice of `pose`, and local_of(P) into LDS where W will stand.  n_layers == 0 (rt_crowd_set_poses): the slice holds the pose
 //     already, and L comes from it as k_skeleton_pose takes it.
-//   Phase 1: the level walk of k_skeleton_pose's LDS form, statement for statement.
-//   Phase 2: W and W o inverse_bind out to the actor's slices of `joints` and `palette`.
+//   Phases 1 and 2: walk_levels (rt_pose_device.h), the text k_skeleton_pose ends in: the level walk, then W and W o inverse_bind out to the
+//     actor's slices of `joints` and `palette`.
 // LDS is dynamic and sized by the rig (rt_crowd_lds_bytes): W component major with a row of n_joints floats per component -- the lanes of a
 // wave read consecutive words -- then the level table and the level offsets.  `pose` is read and written in place by the lane that owns the
 // joint: not __restrict__.
@@ -55,14 +57,7 @@ __global__ void __launch_bounds__(BLOCK) k_crowd_pose(typename CrowdSource<DEVIC
     if constexpr (DEVICE) s_w += (sizeof(rt_blend_layer) / sizeof(float)) * (size_t)n_layers;      // (behind the records)
     uint32_t *s_table = (uint32_t *)(s_w + 12u * (size_t)N);     // [N]
     uint32_t *s_off = s_table + N;                               // [n_levels + 1] (n_levels <= N)
-    auto load = [&](uint32_t j, float M[12]) {
-#pragma unroll
-        for (int e = 0; e < 12; e++) M[e] = s_w[e * N + j];
-    };
-    auto store = [&](uint32_t j, const float M[12]) {
-#pragma unroll
-        for (int e = 0; e < 12; e++) s_w[e * N + j] = M[e];
-    };
+    const PoseStorage<0> at = {s_w, s_table, s_off, N};
     const uint32_t tid = threadIdx.x, actor = blockIdx.x;
     const rt_blend_layer *mine;
     if constexpr (DEVICE) {
@@ -86,41 +81,16 @@ __global__ void __launch_bounds__(BLOCK) k_crowd_pose(typename CrowdSource<DEVIC
         if (n_layers) {
             float P[10];
             blend_joint(mine, n_layers, n_joints, j, pose + RT_SKELETON_POSE_FLOATS * (size_t)j, P);
-#pragma unroll
-            for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = P[c];
+            store_pose(pose, j, P);
             local_of(P, L);
         } else
             local_of(pose + RT_SKELETON_POSE_FLOATS * (size_t)j, L);
-        store(j, L);
+        at.store(j, L);
         s_table[j] = table[j];
     }
     for (uint32_t l = tid; l <= n_levels; l += BLOCK) s_off[l] = level_offsets[l];
     __syncthreads();
-    for (uint32_t l = 1; l < n_levels; l++) {            // (uniform: every lane passes every barrier)
-        const uint32_t begin = s_off[l], end = s_off[l + 1u];
-        for (uint32_t k = begin + tid; k < end; k += BLOCK) {
-            const uint32_t entry = s_table[k];
-            const uint32_t j = entry & 0xFFFFu, p = entry >> 16;
-            float P[12], L[12], W[12];
-            load(p, P);
-            load(j, L);
-            compose(P, L, W);
-            store(j, W);
-        }
-        __syncthreads();
-    }
-    for (uint32_t j = tid; j < n_joints; j += BLOCK) {
-        float W[12], B[12], M[12];
-        load(j, W);
-#pragma unroll
-        for (int e = 0; e < 12; e++) B[e] = inverse_bind[12u * (size_t)j + e];
-        compose(W, B, M);
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            joints[12u * (size_t)j + e] = W[e];
-            palette[12u * (size_t)j + e] = M[e];
-        }
-    }
+    walk_levels<BLOCK, true>(at, n_levels, n_joints, inverse_bind, joints, palette);
 }
 
 // c->pose holds every actor's held pose, and (n_layers > 0) c->layers every actor's records -- or (`device`) c->slots every actor's slots,
@@ -148,8 +118,7 @@ int pose_crowd(rt_crowd *c, uint32_t n_layers, const CrowdDeviceSource *device =
     else if (block == 128u) launch_pose<128>(c, n_layers, device);
     else launch_pose<256>(c, n_layers, device);
     HIP_TRY(hipGetLastError());
-    c->posed = true;
-    c->pose_count++;          // once for the whole crowd (scenes with instances attached to an actor's joint compare it: rt_scene_update)
+    c->queued();              // (once for the whole crowd)
     return RT_OK;
 }
 
@@ -217,47 +186,7 @@ int check_layers(const rt_crowd *c, const char *who, uint32_t n_layers, const rt
     const uint32_t n_clips = (uint32_t)c->sk->clips.size(), n_masks = (uint32_t)c->sk->masks.size();
     uint32_t a = 0, bad = 0;
     const int what = rt_crowd_validate_layers(c->n_poses, n_layers, layers, n_clips, n_masks, c->posed, &a, &bad);
-    const rt_skeleton_layer *l = what > 2 ? &layers[(size_t)a * n_layers + bad] : nullptr;
-    switch (what) {
-    case 0: return RT_OK;
-    case 1: rt_set_error("%s: null argument", who); return RT_ERR_INVALID_ARG;
-    case 2: rt_set_error("%s: %u layers: 1 .. %u are supported", who, n_layers, RT_SKELETON_MAX_LAYERS); return RT_ERR_INVALID_ARG;
-    case 3: rt_set_error("%s: actor %u: layer %u has mode %u: RT_LAYER_BLEND (0) or RT_LAYER_ADDITIVE (1)", who, a, bad, l->mode); return RT_ERR_INVALID_ARG;
-    case 4: rt_set_error("%s: actor %u: layer 0 is additive: the base layer is RT_LAYER_BLEND", who, a); return RT_ERR_INVALID_ARG;
-    case 5: rt_set_error("%s: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: only layer 0 may", who, a, bad); return RT_ERR_INVALID_ARG;
-    case 6: rt_set_error("%s: actor %u: the time of layer %u is NaN", who, a, bad); return RT_ERR_INVALID_ARG;
-    case 7:
-        rt_set_error("%s: actor %u: layer %u names clip %u: the skeleton has %u (rt_skeleton_add_clip adds one)", who, a, bad, l->clip, n_clips);
-        return RT_ERR_STATE;
-    case 8:
-        rt_set_error("%s: actor %u: layer %u names mask %u: the skeleton has %u (rt_skeleton_add_mask adds one)", who, a, bad, l->mask, n_masks);
-        return RT_ERR_STATE;
-    default:
-        rt_set_error("%s: actor %u: layer %u names RT_SKELETON_CURRENT_POSE: the crowd has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", who, a, bad);
-        return RT_ERR_STATE;
-    }
-}
-
-int require_pose(const rt_crowd *c, const char *who)
-{
-    if (c->posed) return RT_OK;
-    rt_set_error("%s: the crowd has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", who);
-    return RT_ERR_STATE;
-}
-
-int read_back(rt_crowd *c, const char *who, const DevBuf &from, uint32_t first_actor, uint32_t count, float *to, size_t floats_per_joint)
-{
-    RT_TRY(require_pose(c, who));
-    if (first_actor > c->n_poses || count > c->n_poses - first_actor) {
-        rt_set_error("%s: actors %u .. %u: the crowd has %u", who, first_actor, first_actor + count - 1u, c->n_poses);
-        return RT_ERR_INVALID_ARG;
-    }
-    if (count == 0) return RT_OK;
-    const size_t per_actor = floats_per_joint * c->n_joints;
-    RT_TRY(rt_use_device(c->ctx));
-    HIP_TRY(hipMemcpyAsync(to, from.as<float>() + per_actor * first_actor, sizeof(float) * per_actor * count, hipMemcpyDeviceToHost, c->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-    return RT_OK;
+    return what ? rt_pose_refuse_layers(c, who, what, &a, bad, what > 2 ? &layers[(size_t)a * n_layers + bad] : nullptr, n_layers, n_clips, n_masks) : RT_OK;
 }
 
 }  // namespace
@@ -315,15 +244,9 @@ int rt_crowd_get_info(const rt_crowd *c, rt_skeleton **sk, uint32_t *n_actors, u
 int rt_crowd_set_poses(rt_crowd *c, const float *trs, uint32_t mem)
 {
     RT_REQUIRE(c && trs, "null argument");
-    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
-    rt_context *ctx = c->ctx;
-    RT_TRY(rt_use_device(ctx));
-    const size_t bytes = sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)c->n_joints * c->n_poses;
-    // (the crowd keeps the poses: rt_crowd_read_pose answers from them, and a device source is the caller's again once the stream has passed the copy)
-    HIP_TRY(hipMemcpyAsync(c->pose.p, trs, bytes, mem == RT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    RT_TRY(rt_pose_copy_in(c, "rt_crowd_set_poses", trs, mem));
     RT_TRY(pose_crowd(c, 0u));
-    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again)
-    return RT_OK;
+    return rt_pose_join_host(c, mem);
 }
 
 int rt_crowd_set_blend(rt_crowd *c, uint32_t n_layers, const rt_skeleton_layer *layers)
@@ -419,35 +342,31 @@ int rt_crowd_set_times(rt_crowd *c, const uint32_t *clips, const float *times)
 int rt_crowd_read_pose(rt_crowd *c, uint32_t first_actor, uint32_t count, float *trs)
 {
     RT_REQUIRE(c && trs, "null argument");
-    return read_back(c, "rt_crowd_read_pose", c->pose, first_actor, count, trs, RT_SKELETON_POSE_FLOATS);
+    return rt_pose_read_back(c, "rt_crowd_read_pose", c->pose, RT_SKELETON_POSE_FLOATS, first_actor, count, trs);
 }
 
 int rt_crowd_read_joints(rt_crowd *c, uint32_t first_actor, uint32_t count, float *world3x4)
 {
     RT_REQUIRE(c && world3x4, "null argument");
-    return read_back(c, "rt_crowd_read_joints", c->joints, first_actor, count, world3x4, 12);
+    return rt_pose_read_back(c, "rt_crowd_read_joints", c->joints, 12, first_actor, count, world3x4);
 }
 
 int rt_crowd_read_palette(rt_crowd *c, uint32_t first_actor, uint32_t count, float *palette3x4)
 {
     RT_REQUIRE(c && palette3x4, "null argument");
-    return read_back(c, "rt_crowd_read_palette", c->palette, first_actor, count, palette3x4, 12);
+    return rt_pose_read_back(c, "rt_crowd_read_palette", c->palette, 12, first_actor, count, palette3x4);
 }
 
 int rt_crowd_get_joints_device_ptr(rt_crowd *c, void **ptr)
 {
     RT_REQUIRE(c && ptr, "null argument");
-    RT_TRY(require_pose(c, "rt_crowd_get_joints_device_ptr"));
-    *ptr = c->joints.p;
-    return RT_OK;
+    return rt_pose_device_ptr(c, "rt_crowd_get_joints_device_ptr", c->joints, ptr);
 }
 
 int rt_crowd_get_palette_device_ptr(rt_crowd *c, void **ptr)
 {
     RT_REQUIRE(c && ptr, "null argument");
-    RT_TRY(require_pose(c, "rt_crowd_get_palette_device_ptr"));
-    *ptr = c->palette.p;
-    return RT_OK;
+    return rt_pose_device_ptr(c, "rt_crowd_get_palette_device_ptr", c->palette, ptr);
 }
 
 int rt_model_set_bones_from_crowd(rt_model *m, rt_crowd *c, uint32_t actor)
@@ -457,20 +376,7 @@ int rt_model_set_bones_from_crowd(rt_model *m, rt_crowd *c, uint32_t actor)
         rt_set_error("rt_model_set_bones_from_crowd: actor %u: the crowd has %u", actor, c->n_poses);
         return RT_ERR_INVALID_ARG;
     }
-    RT_TRY(require_pose(c, "rt_model_set_bones_from_crowd"));
-    if (m->skin.k == 0) {
-        rt_set_error("rt_model_set_bones_from_crowd: the model has no skin (rt_model_set_skin gives it one)");
-        return RT_ERR_STATE;
-    }
-    if (m->skin.bones != c->n_joints) {
-        rt_set_error("rt_model_set_bones_from_crowd: a skin of %u bones and a crowd of %u joints", m->skin.bones, c->n_joints);
-        return RT_ERR_STATE;
-    }
-    if (m->ctx != c->ctx) {
-        rt_set_error("rt_model_set_bones_from_crowd: the model and the crowd belong to different contexts");
-        return RT_ERR_STATE;
-    }
-    return rt_model_set_bones(m, c->palette.as<float>() + 12u * (size_t)c->n_joints * actor, RT_MEM_DEVICE);
+    return rt_pose_set_bones(m, c, actor, "rt_model_set_bones_from_crowd");
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/dxr_amd.h"
+#include "rt_skeleton.h"                     // RT_SKELETON_POSE_FLOATS: what rt_pose_source holds per joint
 
 void rt_set_error(const char *fmt, ...);
 
@@ -399,18 +400,28 @@ struct SkeletonClip {
 };
 
 // What an attached instance follows, and what a skeleton and a crowd both are: n_poses poses of n_joints joints whose world matrices W stand
-// in `joints`, pose after pose.  A scene holds, retains and releases its pose sources through this type alone (rt_scene::sources), so the
-// pending rule, the refusals and the lifetime of attachments are written once for both; the destructor is virtual for that release.
+// in `joints`, pose after pose, beside the local poses they came from and the palettes made of them.  A scene holds, retains and releases
+// its pose sources through this type alone (rt_scene::sources), so the pending rule, the refusals and the lifetime of attachments are
+// written once for both; the destructor is virtual for that release.  What a skeleton and a crowd do alike with these members is written
+// once too (below: rt_skeleton.hip), and this is the one place that knows what either is called and how it comes by a pose.
 struct rt_pose_source : rt_handle {
     using rt_handle::rt_handle;  // refs: handle + every scene that has instances attached to it (once per scene) (+ a skeleton: every crowd made of it)
     static constexpr bool joins_stream = true;       // a skin kernel that reads the palette, or a pose kernel, may still be queued
     uint64_t pose_count = 0;     // bumped by every posing call: a scene records it per attached instance at build / update (SceneInstance::seen_pose)
     uint32_t n_joints = 0;
     uint32_t n_poses = 1;        // a skeleton: 1; a crowd: its actors
+    DevBuf pose;                 // float[n_poses][n_joints][10]: the local pose last set, sampled or blended
     DevBuf joints;               // float[n_poses][n_joints][12]: W_j
+    DevBuf palette;              // float[n_poses][n_joints][12]: M_j = W_j o inverse_bind_j, what rt_model_set_bones_from_skeleton / _from_crowd hand to the skin kernel
     bool posed = false;          // a pose has been set or sampled: joints (and the palette) hold something
     bool is_crowd = false;       // the object is an rt_crowd, else an rt_skeleton
-    const float *w_of(uint32_t pose) const { return joints.as<float>() + 12u * (size_t)n_joints * pose; }
+    float *pose_of(uint32_t i) const { return pose.as<float>() + RT_SKELETON_POSE_FLOATS * (size_t)n_joints * i; }
+    const float *w_of(uint32_t i) const { return joints.as<float>() + 12u * (size_t)n_joints * i; }
+    const float *palette_of(uint32_t i) const { return palette.as<float>() + 12u * (size_t)n_joints * i; }
+    void queued() { posed = true; pose_count++; }     // a posing launch has been queued: one count per call, whatever n_poses
+    const char *noun() const { return is_crowd ? "crowd" : "skeleton"; }
+    // ... and how "the <noun> has no pose yet (<hint>)" ends
+    const char *pose_hint() const { return is_crowd ? "rt_crowd_set_poses or rt_crowd_set_times gives it one" : "rt_skeleton_set_pose or rt_skeleton_set_time gives it one"; }
     virtual ~rt_pose_source() = default;
 };
 
@@ -422,8 +433,6 @@ struct rt_skeleton : rt_pose_source {
     DevBuf table;                // uint32[n_joints]: joint | parent << 16 in level order (rt_skeleton_pack_table)
     DevBuf d_level_offsets;      // uint32[n_levels + 1]
     DevBuf inverse_bind;         // float[n_joints][12]
-    DevBuf pose;                 // float[n_joints][10]: the local pose last set or sampled
-    DevBuf palette;              // float[n_joints][12]: M_j = W_j o inverse_bind_j, what rt_model_set_bones_from_skeleton hands to the skin kernel
     std::vector<SkeletonClip> clips;
     std::vector<DevBuf> masks;   // rt_skeleton_add_mask: float[n_joints] each, one weight per joint of a blend layer (rt_skeleton_set_blend)
     uint64_t clip_gen = 0, mask_gen = 0;     // bumped by rt_skeleton_clear_clips / _clear_masks when they free something: a crowd's layout holds device addresses of clips and masks and records both (adding keeps every address, and bumps nothing)
@@ -441,8 +450,6 @@ struct CrowdStage {              // one slot of page-locked staging for that upl
 struct rt_crowd : rt_pose_source {
     using rt_pose_source::rt_pose_source;
     rt_skeleton *sk = nullptr;   // retained
-    DevBuf pose;                 // float[n_actors][n_joints][10]
-    DevBuf palette;              // float[n_actors][n_joints][12]
     DevBuf layers;               // rt_blend_layer[n_actors][n_layers] of the call last queued (rt_skeleton.h)
     CrowdStage stage[2];         // written in turn: a slot is the host's again once its own event has passed (rt_crowd.hip: crowd_stage)
     uint32_t next_stage = 0;
@@ -533,6 +540,23 @@ void rt_scene_model_changed(rt_scene *s);
 // RT_OK for a built scene.  Otherwise RT_ERR_STATE and its message: what is pending -- transforms, instance masks, models' vertices -- or, if
 // nothing is, `not_built`, a format that may name `who` once
 int rt_scene_require_built(const rt_scene *s, const char *who, const char *not_built);
+
+// rt_skeleton.hip: what a skeleton and a crowd do alike with the record they share
+// RT_OK for a source that has a pose; else RT_ERR_STATE and "<who>: the <noun> has no pose yet (<hint>)"
+int rt_pose_require(const rt_pose_source *src, const char *who);
+// the refusal behind code `what` of rt_skeleton_validate_layers (rt_skeleton_layers_refusal, rt_skeleton.h, with the source's noun and hint) as the last error; its class
+int rt_pose_refuse_layers(const rt_pose_source *src, const char *who, int what, const uint32_t *actor, uint32_t bad, const rt_skeleton_layer *l, uint32_t n_layers,
+                          uint32_t n_clips, uint32_t n_masks);
+// `count` poses from `first` on out of `from` (pose, joints or palette: floats_per_joint 10 or 12), joined.  A skeleton asks for (0, 1)
+int rt_pose_read_back(rt_pose_source *src, const char *who, const DevBuf &from, size_t floats_per_joint, uint32_t first, uint32_t count, float *to);
+// the caller's n_poses local poses (`mem`: RT_MEM_HOST or RT_MEM_DEVICE, else the refusal under `who`) queued into src->pose; the type's own
+// launch follows, and then the join that makes a host array the caller's own again
+int rt_pose_copy_in(rt_pose_source *src, const char *who, const float *trs, uint32_t mem);
+static inline int rt_pose_join_host(rt_pose_source *src, uint32_t mem) { if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(src->ctx->stream)); return RT_OK; }
+// pose `actor`'s palette handed to the model's skin (rt_model_set_bones, RT_MEM_DEVICE), or the refusal under `who`
+int rt_pose_set_bones(rt_model *m, rt_pose_source *src, uint32_t actor, const char *who);
+// the device address of `which` (joints or palette) of a source that has a pose
+int rt_pose_device_ptr(const rt_pose_source *src, const char *who, const DevBuf &which, void **ptr);
 
 // rt_bvh_ploc.hip.  The leaves PLOC clusters, in Morton order.  Empty: the canonical leaves, one per triangle; otherwise the references of a
 // model with split triangles (rt_refs.h): their count, 6 floats and a primitive id per leaf

@@ -1,6 +1,7 @@
-// rt_pose_device.h -- the device arithmetic of a pose (include/dxr_amd.h "Posed skeletons": local, product, sampling, blending), each function
-// written ONCE for the two translation units that pose: rt_skeleton.hip (one skeleton, one pose) and rt_crowd.hip (n_actors poses of one
-// skeleton).  Actor a of a crowd is, bit for bit, a skeleton given the same call because both run these statements and no others.
+// rt_pose_device.h -- the device side of a pose (include/dxr_amd.h "Posed skeletons": local, product, sampling, blending; the walk over the
+// levels and the palette step, over whichever storage holds W), each function written ONCE for the two translation units that pose:
+// rt_skeleton.hip (one skeleton, one pose) and rt_crowd.hip (n_actors poses of one skeleton).  Actor a of a crowd is, bit for bit, a
+// skeleton given the same call because both run these statements and no others; a kernel of either keeps only its own phase 0.
 #pragma once
 
 #include "rt_device_math.h"
@@ -126,6 +127,72 @@ RT_DEV void blend_joint(const rt_blend_layer *layers, uint32_t n_layers, uint32_
         for (int c = 0; c < 10; c++) P[c] = held[c];
     }
     for (uint32_t k = 1; k < n_layers; k++) blend_layer(layers[k], n_joints, j, P);
+}
+
+// the ten floats of joint j's local pose, out to `pose` as rt_skeleton_set_pose takes them
+RT_DEV void store_pose(float *pose, uint32_t j, const float P[10])
+{
+#pragma unroll
+    for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = P[c];
+}
+
+// Where W and the level tables stand while a pose is walked: load and store move the twelve floats of a joint's W, entry(k) is entry k of
+// the level table (joint | parent << 16, rt_skeleton_pack_table) and offset(l) where level l begins.  ROW > 0: LDS, W component major in twelve
+// rows of ROW floats beside copies of both tables.  ROW == 0: the same with rows of `n` floats, a row only the launch knows.  ROW < 0: W
+// where it ends up, joint major in `joints`, and the tables where the skeleton keeps them, in global memory.
+template <int ROW>
+struct PoseStorage {
+    float *w;
+    const uint32_t *table, *off;
+    uint32_t n;
+    RT_DEV size_t at(uint32_t j, int e) const { return ROW < 0 ? 12u * (size_t)j + e : (size_t)(e * (ROW ? (uint32_t)ROW : n) + j); }
+    RT_DEV void load(uint32_t j, float M[12]) const
+    {
+#pragma unroll
+        for (int e = 0; e < 12; e++) M[e] = w[at(j, e)];
+    }
+    RT_DEV void store(uint32_t j, const float M[12]) const
+    {
+#pragma unroll
+        for (int e = 0; e < 12; e++) w[at(j, e)] = M[e];
+    }
+    RT_DEV uint32_t entry(uint32_t k) const { return table[k]; }
+    RT_DEV uint32_t offset(uint32_t l) const { return off[l]; }
+};
+
+// Steps 2 and 3 of a pose by one block of BLOCK lanes, once every joint's L stands in `at` where its W will (a root's W is its L bit for
+// bit) and the block has met.  Level by level from level 1, the lanes striding a level's joints and meeting at __syncthreads():
+// W_j = W_parent o L_j, in place -- a joint's parent stands in an earlier level, so nothing read in a level is written in it.  Then every
+// joint at once: M_j = W_j o inverse_bind_j out to `palette`, and (WRITE_W: the storage is not `joints` itself) W_j out to `joints`.
+template <uint32_t BLOCK, bool WRITE_W, class Storage>
+RT_DEV void walk_levels(const Storage &at, uint32_t n_levels, uint32_t n_joints, const float *__restrict__ inverse_bind, float *joints, float *__restrict__ palette)
+{
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t l = 1; l < n_levels; l++) {            // (uniform: every lane passes every barrier)
+        const uint32_t begin = at.offset(l), end = at.offset(l + 1u);
+        for (uint32_t k = begin + tid; k < end; k += BLOCK) {
+            const uint32_t entry = at.entry(k);
+            const uint32_t j = entry & 0xFFFFu, p = entry >> 16;
+            float P[12], L[12], W[12];
+            at.load(p, P);
+            at.load(j, L);
+            compose(P, L, W);
+            at.store(j, W);
+        }
+        __syncthreads();
+    }
+    for (uint32_t j = tid; j < n_joints; j += BLOCK) {
+        float W[12], B[12], M[12];
+        at.load(j, W);
+#pragma unroll
+        for (int e = 0; e < 12; e++) B[e] = inverse_bind[12u * (size_t)j + e];
+        compose(W, B, M);
+#pragma unroll
+        for (int e = 0; e < 12; e++) {
+            if (WRITE_W) joints[12u * (size_t)j + e] = W[e];
+            palette[12u * (size_t)j + e] = M[e];
+        }
+    }
 }
 
 }  // namespace rtd

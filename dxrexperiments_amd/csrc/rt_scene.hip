@@ -111,10 +111,7 @@ int scene_require_poses(const rt_scene *s, const char *who)
 {
     for (size_t i = 0; !s->sources.empty() && i < s->inst.size(); i++)
         if (s->inst[i].source == XfSource::Joint && !s->inst[i].src->posed) {
-            if (s->inst[i].src->is_crowd)
-                rt_set_error("%s: instance %zu is attached to a crowd that has no pose yet (rt_crowd_set_poses or rt_crowd_set_times gives it one)", who, i);
-            else
-                rt_set_error("%s: instance %zu is attached to a skeleton that has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", who, i);
+            rt_set_error("%s: instance %zu is attached to a %s that has no pose yet (%s)", who, i, s->inst[i].src->noun(), s->inst[i].src->pose_hint());
             return RT_ERR_STATE;
         }
     return RT_OK;

@@ -1,5 +1,6 @@
 // rt_skeleton.h -- the host side of a skeleton (rt_skeleton_create, rt_skeleton_add_clip, rt_skeleton_set_time, rt_skeleton_set_blend):
-// validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip, the check of a layer list, the
+// validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip, the check of a layer list and the
+// text of its refusals (a skeleton's and a crowd's alike: tests/cpp/layer_refusals_sanitized.cpp holds it to what both used to say), the
 // record a validated layer is packed into (shared with rt_crowd.h) and the check of a list of IK constraints (rt_skeleton_solve_ik).  Host code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp,
 // tests/cpp/skeleton_blend_sanitized.cpp and tests/cpp/ik_sanitized.cpp compile it alone.
 #pragma once
@@ -7,6 +8,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <vector>
 
 #include "../../include/dxr_amd_types.h"     // rt_skeleton_layer, rt_skeleton_ik and their constants
@@ -146,6 +148,30 @@ static inline int rt_skeleton_validate_layers(uint32_t n_layers, const rt_skelet
         }
     }
     return 0;
+}
+
+// The refusal behind a code 1 .. 9 of rt_skeleton_validate_layers, in the ONE text that rt_skeleton_set_blend, rt_crowd_set_blend and
+// rt_crowd_set_layout answer with: written into out[size] under the name `who` of the call that asked.  `actor`: null for a skeleton, else the
+// bad actor of a crowd, named in front of what is wrong with a layer (3 .. 9; 1 and 2 name none).  `bad` is the bad layer and `l` its record (read for 3, 7 and
+// 8 only).  `noun` and `hint` are the pose source's own (rt_pose_source, rt_internal.h).  Returns the error class: RT_ERR_INVALID_ARG for
+// 1 .. 6, RT_ERR_STATE for 7 .. 9.
+static inline int rt_skeleton_layers_refusal(int what, const char *who, const uint32_t *actor, uint32_t bad, const rt_skeleton_layer *l, uint32_t n_layers,
+                                             uint32_t n_clips, uint32_t n_masks, const char *noun, const char *hint, char *out, size_t size)
+{
+    char at[24] = "";                                    // "actor 4294967295: " is 18
+    if (actor) snprintf(at, sizeof at, "actor %u: ", *actor);
+    switch (what) {
+    case 1: snprintf(out, size, "%s: null argument", who); break;
+    case 2: snprintf(out, size, "%s: %u layers: 1 .. %u are supported", who, n_layers, RT_SKELETON_MAX_LAYERS); break;
+    case 3: snprintf(out, size, "%s: %slayer %u has mode %u: RT_LAYER_BLEND (0) or RT_LAYER_ADDITIVE (1)", who, at, bad, l->mode); break;
+    case 4: snprintf(out, size, "%s: %slayer 0 is additive: the base layer is RT_LAYER_BLEND", who, at); break;
+    case 5: snprintf(out, size, "%s: %slayer %u names RT_SKELETON_CURRENT_POSE: only layer 0 may", who, at, bad); break;
+    case 6: snprintf(out, size, "%s: %sthe time of layer %u is NaN", who, at, bad); break;
+    case 7: snprintf(out, size, "%s: %slayer %u names clip %u: the skeleton has %u (rt_skeleton_add_clip adds one)", who, at, bad, l->clip, n_clips); break;
+    case 8: snprintf(out, size, "%s: %slayer %u names mask %u: the skeleton has %u (rt_skeleton_add_mask adds one)", who, at, bad, l->mask, n_masks); break;
+    default: snprintf(out, size, "%s: %slayer %u names RT_SKELETON_CURRENT_POSE: the %s has no pose yet (%s)", who, at, bad, noun, hint); break;
+    }
+    return what <= 6 ? RT_ERR_INVALID_ARG : RT_ERR_STATE;
 }
 
 // A validated layer as the kernels read it (rt_pose_device.h: blend_joint, blend_layer).  k_skeleton_blend takes up to

@@ -2,6 +2,8 @@
 // from a baked clip -- becomes world matrices and a skinning palette on the device.  The palette is what rt_model_set_bones(RT_MEM_DEVICE)
 // takes: rt_model_set_bones_from_skeleton hands it over and k_skin_vertices (rt_model.hip) runs unchanged.  No reference counterpart: the
 // reference imports with aiProcess_PreTransformVertices (libs/DXRFramework/RtModel.cpp:26), which drops bones and node animation.
+// Also here, after the kernels: the host steps a skeleton and a crowd do alike over the record they share (rt_pose_source; declared in
+// rt_internal.h, called from here, rt_crowd.hip and rt_scene.hip).  The walk over the levels is rt_pose_device.h's, as the arithmetic is.
 #include <cmath>
 #include <new>
 
@@ -15,12 +17,11 @@ namespace {
 
 using namespace rtd;
 
-// ONE block poses a skeleton: no block ever waits on another.  Step 1, every joint at once: L from the pose, stored where W will stand (a
-// root's W is its L bit for bit).  Step 2, level by level from level 1, the lanes striding a level's joints and meeting at __syncthreads():
-// W_j = W_parent o L_j, in place -- a joint's parent stands in an earlier level, so nothing read in a level is written in it.  Step 3, every
-// joint at once: M_j = W_j o inverse_bind_j.  LDS (n_joints <= RT_SKELETON_LDS_JOINTS): W component major in LDS, and with it the level table
-// and the level offsets, so that a level costs LDS round trips only; else W in `joints` and the tables in global memory, a global round trip per
-// level.  The same statements either way: the same bytes.  `joints` is read back by other lanes than wrote it: not __restrict__.
+// ONE block poses a skeleton: no block ever waits on another.  Step 1, every joint at once: L from the pose, stored where W will stand.
+// Steps 2 and 3 -- the walk over the levels, then M_j = W_j o inverse_bind_j -- are walk_levels (rt_pose_device.h), which k_crowd_pose ends
+// in too.  LDS (n_joints <= RT_SKELETON_LDS_JOINTS): W component major in LDS, and with it the level table and the level offsets, so that a
+// level costs LDS round trips only; else W in `joints` and the tables in global memory, a global round trip per level.  The same statements
+// either way: the same bytes.  `joints` is read back by other lanes than wrote it: not __restrict__.
 template <bool LDS>
 __global__ void __launch_bounds__(RT_SKELETON_BLOCK) k_skeleton_pose(const float *__restrict__ pose, const uint32_t *__restrict__ table,
                                                                      const uint32_t *__restrict__ level_offsets, uint32_t n_levels, uint32_t n_joints,
@@ -30,52 +31,18 @@ __global__ void __launch_bounds__(RT_SKELETON_BLOCK) k_skeleton_pose(const float
     __shared__ float s_w[LDS ? 12u * N : 1u];
     __shared__ uint32_t s_table[LDS ? N : 1u];
     __shared__ uint32_t s_off[LDS ? N + 1u : 1u];
-    auto load = [&](uint32_t j, float M[12]) {
-#pragma unroll
-        for (int e = 0; e < 12; e++) M[e] = LDS ? s_w[e * N + j] : joints[12u * (size_t)j + e];
-    };
-    auto store = [&](uint32_t j, const float M[12]) {
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            if (LDS) s_w[e * N + j] = M[e];
-            else joints[12u * (size_t)j + e] = M[e];
-        }
-    };
+    const PoseStorage<LDS ? (int)N : -1> at = {LDS ? s_w : joints, LDS ? s_table : table, LDS ? s_off : level_offsets, N};
     const uint32_t tid = threadIdx.x;
     for (uint32_t j = tid; j < n_joints; j += RT_SKELETON_BLOCK) {
         float L[12];
         local_of(pose + RT_SKELETON_POSE_FLOATS * (size_t)j, L);
-        store(j, L);
+        at.store(j, L);
         if (LDS) s_table[j] = table[j];
     }
     if (LDS)
         for (uint32_t l = tid; l <= n_levels; l += RT_SKELETON_BLOCK) s_off[l] = level_offsets[l];
     __syncthreads();
-    for (uint32_t l = 1; l < n_levels; l++) {            // (uniform: every lane passes every barrier)
-        const uint32_t begin = LDS ? s_off[l] : level_offsets[l], end = LDS ? s_off[l + 1u] : level_offsets[l + 1u];
-        for (uint32_t k = begin + tid; k < end; k += RT_SKELETON_BLOCK) {
-            const uint32_t entry = LDS ? s_table[k] : table[k];
-            const uint32_t j = entry & 0xFFFFu, p = entry >> 16;
-            float P[12], L[12], W[12];
-            load(p, P);
-            load(j, L);
-            compose(P, L, W);
-            store(j, W);
-        }
-        __syncthreads();
-    }
-    for (uint32_t j = tid; j < n_joints; j += RT_SKELETON_BLOCK) {
-        float W[12], B[12], M[12];
-        load(j, W);
-#pragma unroll
-        for (int e = 0; e < 12; e++) B[e] = inverse_bind[12u * (size_t)j + e];
-        compose(W, B, M);
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            if (LDS) joints[12u * (size_t)j + e] = W[e];
-            palette[12u * (size_t)j + e] = M[e];
-        }
-    }
+    walk_levels<RT_SKELETON_BLOCK, LDS>(at, n_levels, n_joints, inverse_bind, joints, palette);
 }
 
 // One lane per joint: the local pose between two keys of a clip, written as rt_skeleton_set_pose takes it, ten floats per joint.
@@ -86,8 +53,7 @@ __global__ void __launch_bounds__(256) k_skeleton_sample(const float *__restrict
     if (j >= n_joints) return;
     float o[10];
     sample_joint(key_a, key_b, n_joints, j, a, o);
-#pragma unroll
-    for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = o[c];
+    store_pose(pose, j, o);
 }
 
 // The table of a blend's layers (rt_blend_layer, rt_skeleton.h) that travels by value as the kernel's argument: wave uniform, so it comes
@@ -105,8 +71,7 @@ __global__ void __launch_bounds__(256) k_skeleton_blend(const BlendTable table, 
     if (j >= n_joints) return;
     float P[10];
     blend_joint(table.layer, n_layers, n_joints, j, pose + RT_SKELETON_POSE_FLOATS * (size_t)j, P);
-#pragma unroll
-    for (int c = 0; c < 10; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)j + c] = P[c];
+    store_pose(pose, j, P);
 }
 
 // A constraint of a solve as the kernel reads it -- the host has found the chain: tip c, middle b, root a of a two-bone reach (an aim: c is
@@ -172,28 +137,81 @@ int pose_skeleton(rt_skeleton *sk)
     else
         k_skeleton_pose<false><<<1, RT_SKELETON_BLOCK, 0, st>>>(pose, table, off, sk->n_levels, sk->n_joints, ib, sk->joints.as<float>(), sk->palette.as<float>());
     HIP_TRY(hipGetLastError());
-    sk->posed = true;
-    sk->pose_count++;         // (scenes with instances attached to a joint compare it with the count they last applied: rt_scene_update)
-    return RT_OK;
-}
-
-int require_pose(const rt_skeleton *sk, const char *who)
-{
-    if (sk->posed) return RT_OK;
-    rt_set_error("%s: the skeleton has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", who);
-    return RT_ERR_STATE;
-}
-
-int read_back(rt_skeleton *sk, const char *who, const DevBuf &from, float *to, size_t floats_per_joint)
-{
-    RT_TRY(require_pose(sk, who));
-    RT_TRY(rt_use_device(sk->ctx));
-    HIP_TRY(hipMemcpyAsync(to, from.p, sizeof(float) * floats_per_joint * sk->n_joints, hipMemcpyDeviceToHost, sk->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(sk->ctx->stream));
+    sk->queued();
     return RT_OK;
 }
 
 }  // namespace
+
+// ---- what a skeleton and a crowd do alike (rt_internal.h) ---------------------------------------------------------------------------------
+int rt_pose_require(const rt_pose_source *src, const char *who)
+{
+    if (src->posed) return RT_OK;
+    rt_set_error("%s: the %s has no pose yet (%s)", who, src->noun(), src->pose_hint());
+    return RT_ERR_STATE;
+}
+
+int rt_pose_refuse_layers(const rt_pose_source *src, const char *who, int what, const uint32_t *actor, uint32_t bad, const rt_skeleton_layer *l, uint32_t n_layers,
+                          uint32_t n_clips, uint32_t n_masks)
+{
+    char msg[512];
+    const int rc = rt_skeleton_layers_refusal(what, who, actor, bad, l, n_layers, n_clips, n_masks, src->noun(), src->pose_hint(), msg, sizeof msg);
+    rt_set_error("%s", msg);
+    return rc;
+}
+
+int rt_pose_read_back(rt_pose_source *src, const char *who, const DevBuf &from, size_t floats_per_joint, uint32_t first, uint32_t count, float *to)
+{
+    RT_TRY(rt_pose_require(src, who));
+    if (first > src->n_poses || count > src->n_poses - first) {
+        rt_set_error("%s: actors %u .. %u: the crowd has %u", who, first, first + count - 1u, src->n_poses);
+        return RT_ERR_INVALID_ARG;
+    }
+    if (count == 0) return RT_OK;
+    const size_t per_pose = floats_per_joint * src->n_joints;
+    RT_TRY(rt_use_device(src->ctx));
+    HIP_TRY(hipMemcpyAsync(to, from.as<float>() + per_pose * first, sizeof(float) * per_pose * count, hipMemcpyDeviceToHost, src->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(src->ctx->stream));
+    return RT_OK;
+}
+
+int rt_pose_copy_in(rt_pose_source *src, const char *who, const float *trs, uint32_t mem)
+{
+    if (mem != RT_MEM_HOST && mem != RT_MEM_DEVICE) {
+        rt_set_error("%s: unknown memory selector", who);
+        return RT_ERR_INVALID_ARG;
+    }
+    RT_TRY(rt_use_device(src->ctx));
+    const size_t bytes = sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)src->n_joints * src->n_poses;
+    // (the source keeps the poses: its read_pose answers from them, and a device source is the caller's again once the stream has passed the copy)
+    HIP_TRY(hipMemcpyAsync(src->pose_of(0), trs, bytes, mem == RT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, src->ctx->stream));
+    return RT_OK;
+}
+
+int rt_pose_set_bones(rt_model *m, rt_pose_source *src, uint32_t actor, const char *who)
+{
+    RT_TRY(rt_pose_require(src, who));
+    if (m->skin.k == 0) {
+        rt_set_error("%s: the model has no skin (rt_model_set_skin gives it one)", who);
+        return RT_ERR_STATE;
+    }
+    if (m->skin.bones != src->n_joints) {
+        rt_set_error("%s: a skin of %u bones and a %s of %u joints", who, m->skin.bones, src->noun(), src->n_joints);
+        return RT_ERR_STATE;
+    }
+    if (m->ctx != src->ctx) {
+        rt_set_error("%s: the model and the %s belong to different contexts", who, src->noun());
+        return RT_ERR_STATE;
+    }
+    return rt_model_set_bones(m, src->palette_of(actor), RT_MEM_DEVICE);
+}
+
+int rt_pose_device_ptr(const rt_pose_source *src, const char *who, const DevBuf &which, void **ptr)
+{
+    RT_TRY(rt_pose_require(src, who));
+    *ptr = which.p;
+    return RT_OK;
+}
 
 extern "C" {
 
@@ -243,15 +261,9 @@ int rt_skeleton_get_info(const rt_skeleton *sk, uint32_t *n_joints, uint32_t *n_
 int rt_skeleton_set_pose(rt_skeleton *sk, const float *trs, uint32_t mem)
 {
     RT_REQUIRE(sk && trs, "null argument");
-    RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, "unknown memory selector");
-    rt_context *ctx = sk->ctx;
-    RT_TRY(rt_use_device(ctx));
-    const size_t bytes = sizeof(float) * RT_SKELETON_POSE_FLOATS * (size_t)sk->n_joints;
-    // (the skeleton keeps the pose: rt_skeleton_read_pose answers from it, and a device source is the caller's again once the stream has passed the copy)
-    HIP_TRY(hipMemcpyAsync(sk->pose.p, trs, bytes, mem == RT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    RT_TRY(rt_pose_copy_in(sk, "rt_skeleton_set_pose", trs, mem));
     RT_TRY(pose_skeleton(sk));
-    if (mem == RT_MEM_HOST) HIP_TRY(hipStreamSynchronize(ctx->stream));      // (the caller's array is its own again)
-    return RT_OK;
+    return rt_pose_join_host(sk, mem);
 }
 
 int rt_skeleton_add_clip(rt_skeleton *sk, uint32_t n_keys, const float *times, const float *trs, uint32_t *clip_out)
@@ -361,24 +373,7 @@ int rt_skeleton_set_blend(rt_skeleton *sk, uint32_t n_layers, const rt_skeleton_
     const uint32_t n_clips = (uint32_t)sk->clips.size(), n_masks = (uint32_t)sk->masks.size();
     uint32_t bad = 0;
     const int what = rt_skeleton_validate_layers(n_layers, layers, n_clips, n_masks, sk->posed, &bad);
-    switch (what) {
-    case 0: break;
-    case 1: rt_set_error("rt_skeleton_set_blend: null argument"); return RT_ERR_INVALID_ARG;
-    case 2: rt_set_error("rt_skeleton_set_blend: %u layers: 1 .. %u are supported", n_layers, RT_SKELETON_MAX_LAYERS); return RT_ERR_INVALID_ARG;
-    case 3: rt_set_error("rt_skeleton_set_blend: layer %u has mode %u: RT_LAYER_BLEND (0) or RT_LAYER_ADDITIVE (1)", bad, layers[bad].mode); return RT_ERR_INVALID_ARG;
-    case 4: rt_set_error("rt_skeleton_set_blend: layer 0 is additive: the base layer is RT_LAYER_BLEND"); return RT_ERR_INVALID_ARG;
-    case 5: rt_set_error("rt_skeleton_set_blend: layer %u names RT_SKELETON_CURRENT_POSE: only layer 0 may", bad); return RT_ERR_INVALID_ARG;
-    case 6: rt_set_error("rt_skeleton_set_blend: the time of layer %u is NaN", bad); return RT_ERR_INVALID_ARG;
-    case 7:
-        rt_set_error("rt_skeleton_set_blend: layer %u names clip %u: the skeleton has %u (rt_skeleton_add_clip adds one)", bad, layers[bad].clip, n_clips);
-        return RT_ERR_STATE;
-    case 8:
-        rt_set_error("rt_skeleton_set_blend: layer %u names mask %u: the skeleton has %u (rt_skeleton_add_mask adds one)", bad, layers[bad].mask, n_masks);
-        return RT_ERR_STATE;
-    default:
-        rt_set_error("rt_skeleton_set_blend: layer %u names RT_SKELETON_CURRENT_POSE: the skeleton has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)", bad);
-        return RT_ERR_STATE;
-    }
+    if (what) return rt_pose_refuse_layers(sk, "rt_skeleton_set_blend", what, nullptr, bad, what > 2 ? &layers[bad] : nullptr, n_layers, n_clips, n_masks);
     rt_context *ctx = sk->ctx;
     BlendTable table = {};
     for (uint32_t k = 0; k < n_layers; k++) {
@@ -417,7 +412,7 @@ int rt_skeleton_solve_ik(rt_skeleton *sk, uint32_t n, const rt_skeleton_ik *cons
                      bad[0], bad[1], bad[0], bad[2], bad[1]);
         return RT_ERR_INVALID_ARG;
     default:
-        rt_set_error("rt_skeleton_solve_ik: the skeleton has no pose yet (rt_skeleton_set_pose or rt_skeleton_set_time gives it one)");
+        rt_set_error("rt_skeleton_solve_ik: the %s has no pose yet (%s)", sk->noun(), sk->pose_hint());
         return RT_ERR_STATE;
     }
     IkTable table = {};
@@ -446,54 +441,37 @@ int rt_skeleton_solve_ik(rt_skeleton *sk, uint32_t n, const rt_skeleton_ik *cons
 int rt_skeleton_read_pose(rt_skeleton *sk, float *trs)
 {
     RT_REQUIRE(sk && trs, "null argument");
-    return read_back(sk, "rt_skeleton_read_pose", sk->pose, trs, RT_SKELETON_POSE_FLOATS);
+    return rt_pose_read_back(sk, "rt_skeleton_read_pose", sk->pose, RT_SKELETON_POSE_FLOATS, 0u, 1u, trs);
 }
 
 int rt_skeleton_read_joints(rt_skeleton *sk, float *world3x4)
 {
     RT_REQUIRE(sk && world3x4, "null argument");
-    return read_back(sk, "rt_skeleton_read_joints", sk->joints, world3x4, 12);
+    return rt_pose_read_back(sk, "rt_skeleton_read_joints", sk->joints, 12, 0u, 1u, world3x4);
 }
 
 int rt_skeleton_read_palette(rt_skeleton *sk, float *palette3x4)
 {
     RT_REQUIRE(sk && palette3x4, "null argument");
-    return read_back(sk, "rt_skeleton_read_palette", sk->palette, palette3x4, 12);
+    return rt_pose_read_back(sk, "rt_skeleton_read_palette", sk->palette, 12, 0u, 1u, palette3x4);
 }
 
 int rt_skeleton_get_palette_device_ptr(rt_skeleton *sk, void **ptr)
 {
     RT_REQUIRE(sk && ptr, "null argument");
-    RT_TRY(require_pose(sk, "rt_skeleton_get_palette_device_ptr"));
-    *ptr = sk->palette.p;
-    return RT_OK;
+    return rt_pose_device_ptr(sk, "rt_skeleton_get_palette_device_ptr", sk->palette, ptr);
 }
 
 int rt_skeleton_get_joints_device_ptr(rt_skeleton *sk, void **ptr)
 {
     RT_REQUIRE(sk && ptr, "null argument");
-    RT_TRY(require_pose(sk, "rt_skeleton_get_joints_device_ptr"));
-    *ptr = sk->joints.p;
-    return RT_OK;
+    return rt_pose_device_ptr(sk, "rt_skeleton_get_joints_device_ptr", sk->joints, ptr);
 }
 
 int rt_model_set_bones_from_skeleton(rt_model *m, rt_skeleton *sk)
 {
     RT_REQUIRE(m && sk, "null argument");
-    RT_TRY(require_pose(sk, "rt_model_set_bones_from_skeleton"));
-    if (m->skin.k == 0) {
-        rt_set_error("rt_model_set_bones_from_skeleton: the model has no skin (rt_model_set_skin gives it one)");
-        return RT_ERR_STATE;
-    }
-    if (m->skin.bones != sk->n_joints) {
-        rt_set_error("rt_model_set_bones_from_skeleton: a skin of %u bones and a skeleton of %u joints", m->skin.bones, sk->n_joints);
-        return RT_ERR_STATE;
-    }
-    if (m->ctx != sk->ctx) {
-        rt_set_error("rt_model_set_bones_from_skeleton: the model and the skeleton belong to different contexts");
-        return RT_ERR_STATE;
-    }
-    return rt_model_set_bones(m, sk->palette.as<float>(), RT_MEM_DEVICE);
+    return rt_pose_set_bones(m, sk, 0u, "rt_model_set_bones_from_skeleton");
 }
 
 }  // extern "C"

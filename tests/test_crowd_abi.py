@@ -117,11 +117,12 @@ def test_the_mirror_the_example_and_the_documents():
 
 
 def test_the_pose_arithmetic_is_written_once():
-    """local_of, compose, unit_or_identity, sample_joint, hamilton and the body of one blend layer are defined in rt_pose_device.h and
-    nowhere else; both translation units include it; rt_crowd.h is host code without HIP"""
+    """local_of, compose, unit_or_identity, sample_joint, hamilton, the body of one blend layer, the store of a local pose and the walk over
+    the levels with its palette step are defined in rt_pose_device.h and nowhere else; both translation units include it and neither takes a
+    level table's entry apart itself; rt_crowd.h is host code without HIP"""
     csrc = os.path.join(ROOT, "dxrexperiments_amd", "csrc")
     shared = open(os.path.join(csrc, "rt_pose_device.h")).read()
-    for name in ("local_of", "compose", "unit_or_identity", "sample_joint", "hamilton", "blend_layer", "blend_joint"):
+    for name in ("local_of", "compose", "unit_or_identity", "sample_joint", "hamilton", "blend_layer", "blend_joint", "store_pose", "walk_levels"):
         define = r"^RT_DEV void %s\(" % name
         assert len(re.findall(define, shared, flags=re.M)) == 1, name
         for unit in ("rt_skeleton.hip", "rt_crowd.hip"):
@@ -130,6 +131,7 @@ def test_the_pose_arithmetic_is_written_once():
     for unit in ("rt_skeleton.hip", "rt_crowd.hip"):
         body = re.sub(r"//.*", "", open(os.path.join(csrc, unit)).read())
         assert "P[c] + w *" not in body and "rsqrt_ieee" not in body, unit
+        assert "entry >> 16" not in body and "walk_levels<" in body and "store_pose(" in body, unit
     header = open(os.path.join(csrc, "rt_crowd.h")).read()
     assert "static inline int rt_crowd_validate_layers(" in header and "static inline void rt_crowd_pack_layers(" in header
     assert "hip" not in re.sub(r"//.*", "", header).lower(), "rt_crowd.h is host code without HIP"

@@ -192,6 +192,33 @@ def test_layer_lists_under_asan_ubsan(tmp_path):
     assert seen == set(range(10)), "a refusal no case reaches"
 
 
+def test_layer_refusals_under_asan_ubsan():
+    """rt_skeleton_layers_refusal, the one text behind rt_skeleton_set_blend, rt_crowd_set_blend and rt_crowd_set_layout, says for every code
+    1 .. 9, in the skeleton's form and in the crowd's, what the two switches it replaced said, byte for byte, with their error class (the
+    program holds the literals and says where they came from); no report.  The noun and the hint it is given there are the ones
+    rt_pose_source hands it in the library, and neither .hip keeps a switch of its own"""
+    out_dir = os.path.join(ROOT, "build_san")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "layer_refusals_sanitized")
+    src = os.path.join(ROOT, "tests", "cpp", "layer_refusals_sanitized.cpp")
+    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", src, "-o", exe],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and "18 refusals, 0 sanitizer reports" in r.stdout and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    csrc = os.path.join(ROOT, "dxrexperiments_amd", "csrc")
+    program, record = open(src).read(), open(os.path.join(csrc, "rt_internal.h")).read()
+    said = ('"skeleton"', '"crowd"', '"rt_skeleton_set_pose or rt_skeleton_set_time gives it one"', '"rt_crowd_set_poses or rt_crowd_set_times gives it one"')
+    for words in said:
+        assert words in program and words in record, words
+    assert "is_crowd ? %s : %s" % (said[1], said[0]) in record and "is_crowd ? %s : %s" % (said[3], said[2]) in record, "which is the crowd's"
+    for unit in ("rt_skeleton.hip", "rt_crowd.hip", "rt_scene.hip"):
+        body = re.sub(r"//.*", "", open(os.path.join(csrc, unit)).read())
+        assert "only layer 0 may" not in body and not any(words[1:-1] in body for words in said[2:]), unit
+        assert len(re.findall(r"rt_skeleton_layers_refusal\(", body)) == (1 if unit == "rt_skeleton.hip" else 0), unit
+
+
 # ---- the restatement is what it states -----------------------------------------------------------------------------------------------------
 def unit_clip(n, seed, n_keys=2):
     parents = S.hierarchy("random", n, seed)
