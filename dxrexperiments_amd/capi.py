@@ -119,6 +119,9 @@ SIGNATURES = {
     "rt_crowd_get_joints_device_ptr": (_i, [_p, _pp]),
     "rt_crowd_get_palette_device_ptr": (_i, [_p, _pp]),
     "rt_model_set_bones_from_crowd": (_i, [_p, _p, _u32]),
+    "rt_crowd_set_ik_chains": (_i, [_p, _u32, _p]),
+    "rt_crowd_get_ik_chains": (_i, [_p, _pu]),
+    "rt_crowd_solve_ik": (_i, [_p, _p, _p, _p, _u32]),
     "rt_scene_attach_instances_crowd": (_i, [_p, _u32, _u32, _p, _p, _p, _p]),
     "rt_scene_get_instance_crowd_attachment": (_i, [_p, _u32, _pp, _pu, _pu]),
     "rt_model_retain": (_i, [_p]),
@@ -773,6 +776,40 @@ class Crowd:
         """every actor posed from the layout and n_actors x n_layers float32 times -- and weights, or None: the layout's -- in device memory
         (addresses, e.g. DeviceBuffer.ptr or a tensor's data_ptr(), written on the context's stream): one launch, nothing uploaded"""
         _check(lib().rt_crowd_set_blend_device(self.h, C.c_void_p(times_ptr), None if weights_ptr is None else C.c_void_p(weights_ptr)))
+
+    def set_ik_chains(self, constraints):
+        """the crowd's chains -- the one list of constraints every actor solves, checked once: what Skeleton.solve_ik takes.  kind and joint
+        are read, pole and weight kept as the defaults of solve_ik calls that bring none; the targets are not read"""
+        a = constraints if isinstance(constraints, np.ndarray) and constraints.dtype == T.SKELETON_IK else Skeleton.constraints(constraints)
+        a = np.ascontiguousarray(a)
+        _check(lib().rt_crowd_set_ik_chains(self.h, a.shape[0], _ptr(a)))
+
+    def ik_chains(self):
+        """the chains the crowd holds; 0: none"""
+        n = C.c_uint32()
+        _check(lib().rt_crowd_get_ik_chains(self.h, C.byref(n)))
+        return n.value
+
+    def solve_ik(self, targets, poles=None, weights=None):
+        """every actor solves the crowd's chains with its own values, from host arrays, and is posed with the result: targets
+        float32[n_actors, n, 3], poles the same or None (the chains' own), weights float32[n_actors, n] or None (likewise); one upload, one
+        launch"""
+        n = self.ik_chains()
+        arrays = []
+        for name, a, tail in (("targets", targets, (3,)), ("poles", poles, (3,)), ("weights", weights, ())):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != (self.n_actors, n) + tail:
+                    raise RtError(-1, "solve_ik: %s of shape %s for a crowd of %d actors and %d chains" % (name, a.shape, self.n_actors, n))
+            arrays.append(a)
+        t, p, w = arrays
+        _check(lib().rt_crowd_solve_ik(self.h, None if t is None else _ptr(t), None if p is None else _ptr(p), None if w is None else _ptr(w), MEM_HOST))
+
+    def solve_ik_device(self, targets_ptr, poles_ptr=None, weights_ptr=None):
+        """... from n_actors x n x 3 float32 targets -- and poles, and n_actors x n weights, or None: the chains' own -- in device memory
+        (addresses, written on the context's stream): one launch, nothing uploaded"""
+        _check(lib().rt_crowd_solve_ik(self.h, C.c_void_p(targets_ptr), None if poles_ptr is None else C.c_void_p(poles_ptr),
+                                       None if weights_ptr is None else C.c_void_p(weights_ptr), MEM_DEVICE))
 
     def _read(self, fn, width, first, count):
         n = self.n_actors - first if count is None else count

@@ -122,33 +122,6 @@ int pose_crowd(rt_crowd *c, uint32_t n_layers, const CrowdDeviceSource *device =
     return RT_OK;
 }
 
-// The next staging slot, the host's to write `bytes` into: the two slots are written in turn, and a slot is waited for only while the copy
-// out of it -- the one of the call before last -- has not passed on the stream.  Back-to-back calls therefore never wait for the device
-// unless they run two uploads ahead of it.
-int crowd_stage(rt_crowd *c, size_t bytes, CrowdStage **out)
-{
-    CrowdStage &s = c->stage[c->next_stage];
-    if (s.in_flight) {
-        HIP_TRY(hipEventSynchronize(s.event));
-        s.in_flight = false;
-    }
-    if (!s.event) HIP_TRY(hipEventCreateWithFlags(&s.event, hipEventDisableTiming));
-    if (s.bytes < bytes) {
-        void *b = nullptr;
-        if (hipHostMalloc(&b, bytes, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            rt_set_error("out of page-locked host memory (%zu bytes)", bytes);
-            return RT_ERR_OOM;
-        }
-        if (s.block) (void)hipHostFree(s.block);
-        s.block = b;
-        s.bytes = bytes;
-    }
-    c->next_stage ^= 1u;
-    *out = &s;
-    return RT_OK;
-}
-
 // the skeleton's clips and masks as the packing reads them
 void clips_and_masks(const rt_skeleton *sk, std::vector<rt_crowd_clip> &clips, std::vector<const float *> &masks)
 {
@@ -190,6 +163,33 @@ int check_layers(const rt_crowd *c, const char *who, uint32_t n_layers, const rt
 }
 
 }  // namespace
+
+// The next staging slot, the host's to write `bytes` into: the two slots are written in turn, and a slot is waited for only while the copy
+// out of it -- the one of the call before last -- has not passed on the stream.  Back-to-back calls therefore never wait for the device
+// unless they run two uploads ahead of it.  Declared in rt_internal.h: rt_crowd_ik.hip stages its one upload through it too.
+int crowd_stage(rt_crowd *c, size_t bytes, CrowdStage **out)
+{
+    CrowdStage &s = c->stage[c->next_stage];
+    if (s.in_flight) {
+        HIP_TRY(hipEventSynchronize(s.event));
+        s.in_flight = false;
+    }
+    if (!s.event) HIP_TRY(hipEventCreateWithFlags(&s.event, hipEventDisableTiming));
+    if (s.bytes < bytes) {
+        void *b = nullptr;
+        if (hipHostMalloc(&b, bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            rt_set_error("out of page-locked host memory (%zu bytes)", bytes);
+            return RT_ERR_OOM;
+        }
+        if (s.block) (void)hipHostFree(s.block);
+        s.block = b;
+        s.bytes = bytes;
+    }
+    c->next_stage ^= 1u;
+    *out = &s;
+    return RT_OK;
+}
 
 rt_crowd::~rt_crowd()
 {

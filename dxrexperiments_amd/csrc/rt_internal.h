@@ -440,7 +440,8 @@ struct rt_skeleton : rt_pose_source {
 
 // rt_crowd_create (rt_crowd.hip): n_poses = n_actors poses of one skeleton, which it retains and whose hierarchy, inverse binds, clips and
 // masks it reads where they live.  Every posing call is one upload of the actors' layer records and one launch of k_crowd_pose, or
-// (rt_crowd_set_blend_device) the launch alone, over the slots of a layout uploaded once.
+// (rt_crowd_set_blend_device) the launch alone, over the slots of a layout uploaded once.  rt_crowd_solve_ik (rt_crowd_ik.hip) is one
+// launch of k_crowd_ik over the chains the crowd holds, after one upload of the actors' values where they are the host's.
 struct CrowdStage {              // one slot of page-locked staging for that upload, and the event behind the copy out of it
     void *block = nullptr;
     size_t bytes = 0;
@@ -456,6 +457,9 @@ struct rt_crowd : rt_pose_source {
     DevBuf slots;                // rt_crowd_slot[n_actors][layout_layers] of rt_crowd_set_layout (rt_crowd.h)
     uint32_t layout_layers = 0;  // 0: no layout
     uint64_t layout_clip_gen = 0, layout_mask_gen = 0;   // the skeleton's generations when the layout was packed: it is stale once either has moved
+    IkTable ik_chains = {};      // rt_crowd_set_ik_chains: the one list every actor solves, packed (rt_skeleton_pack_ik); it travels by value to k_crowd_ik
+    uint32_t n_ik_chains = 0;    // 0: no chains
+    DevBuf ik_values;            // rt_crowd_solve_ik(RT_MEM_HOST): the targets, poles and weights of the call last queued, one behind another (rt_crowd_ik.h)
     ~rt_crowd() override;        // (rt_crowd.hip) the staging, then the skeleton; the caller has selected the device and joined the stream
 };
 
@@ -549,6 +553,8 @@ int rt_pose_refuse_layers(const rt_pose_source *src, const char *who, int what, 
                           uint32_t n_clips, uint32_t n_masks);
 // `count` poses from `first` on out of `from` (pose, joints or palette: floats_per_joint 10 or 12), joined.  A skeleton asks for (0, 1)
 int rt_pose_read_back(rt_pose_source *src, const char *who, const DevBuf &from, size_t floats_per_joint, uint32_t first, uint32_t count, float *to);
+// the refusal behind code `what` of rt_skeleton_validate_ik (rt_skeleton_ik_refusal, rt_skeleton.h, with the source's joints, noun and hint) as the last error; its class
+int rt_pose_refuse_ik(const rt_pose_source *src, const char *who, int what, uint32_t n, const rt_skeleton_ik *constraints, const uint32_t bad[3]);
 // the caller's n_poses local poses (`mem`: RT_MEM_HOST or RT_MEM_DEVICE, else the refusal under `who`) queued into src->pose; the type's own
 // launch follows, and then the join that makes a host array the caller's own again
 int rt_pose_copy_in(rt_pose_source *src, const char *who, const float *trs, uint32_t mem);
@@ -557,6 +563,8 @@ static inline int rt_pose_join_host(rt_pose_source *src, uint32_t mem) { if (mem
 int rt_pose_set_bones(rt_model *m, rt_pose_source *src, uint32_t actor, const char *who);
 // the device address of `which` (joints or palette) of a source that has a pose
 int rt_pose_device_ptr(const rt_pose_source *src, const char *who, const DevBuf &which, void **ptr);
+// rt_crowd.hip: the crowd's next staging slot, the host's to write `bytes` into (what every upload of a crowd call goes through: rt_crowd.hip, rt_crowd_ik.hip)
+int crowd_stage(rt_crowd *c, size_t bytes, CrowdStage **out);
 
 // rt_bvh_ploc.hip.  The leaves PLOC clusters, in Morton order.  Empty: the canonical leaves, one per triangle; otherwise the references of a
 // model with split triangles (rt_refs.h): their count, 6 floats and a primitive id per leaf

@@ -1,10 +1,11 @@
 // rt_pose_device.h -- the device side of a pose (include/dxr_amd.h "Posed skeletons": local, product, sampling, blending; the walk over the
-// levels and the palette step, over whichever storage holds W), each function written ONCE for the two translation units that pose:
-// rt_skeleton.hip (one skeleton, one pose) and rt_crowd.hip (n_actors poses of one skeleton).  Actor a of a crowd is, bit for bit, a
+// levels and the palette step, over whichever storage holds W; the lane of an IK constraint), each function written ONCE for the translation
+// units that pose: rt_skeleton.hip (one skeleton, one pose), rt_crowd.hip and rt_crowd_ik.hip (n_actors poses of one skeleton).  Actor a of a crowd is, bit for bit, a
 // skeleton given the same call because both run these statements and no others; a kernel of either keeps only its own phase 0.
 #pragma once
 
 #include "rt_device_math.h"
+#include "rt_ik.h"
 #include "rt_skeleton.h"
 
 namespace rtd {
@@ -192,6 +193,33 @@ RT_DEV void walk_levels(const Storage &at, uint32_t n_levels, uint32_t n_joints,
             if (WRITE_W) joints[12u * (size_t)j + e] = W[e];
             palette[12u * (size_t)j + e] = M[e];
         }
+    }
+}
+
+// What the lane of one IK constraint does once it holds its entry (IkEntry, rt_skeleton.h: the chain c, b, a and a's parent p, -1 for a
+// root of the skeleton) and its values, written ONCE for k_skeleton_ik (rt_skeleton.hip) and k_crowd_ik (rt_crowd_ik.hip): the thirty floats
+// of its three joints from `pose`, the twelve of W_p from `joints` -- the pose before this call: what the last posing launch left --,
+// rt_ik_solve (rt_ik.h), and four floats, or eight, back into `pose`.  Nothing of the values becomes an address.  `pose` is read and
+// written in place: not __restrict__.
+RT_DEV void ik_solve_lane(uint32_t kind, uint32_t jc, uint32_t jb, uint32_t ja, int32_t jp, const float target[3], const float pole[3], float weight,
+                          const float *joints, float *pose)
+{
+    float tip[10], mid[10], root[10], W[12], qa[4], qb[4];
+#pragma unroll
+    for (int c = 0; c < 10; c++) {
+        tip[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)jc + c];
+        mid[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)jb + c];
+        root[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)ja + c];
+    }
+    const bool has_parent = jp >= 0;
+#pragma unroll
+    for (int c = 0; c < 12; c++) W[c] = has_parent ? joints[12u * (size_t)(has_parent ? jp : 0) + c] : 0.0f;
+    rt_ik_solve(kind, tip, mid, root, has_parent ? W : nullptr, target, pole, weight, qa, qb);
+#pragma unroll
+    for (int c = 0; c < 4; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)ja + 3 + c] = qa[c];
+    if (kind == RT_IK_TWO_BONE) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)jb + 3 + c] = qb[c];
     }
 }
 

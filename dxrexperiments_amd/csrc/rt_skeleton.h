@@ -1,8 +1,10 @@
 // rt_skeleton.h -- the host side of a skeleton (rt_skeleton_create, rt_skeleton_add_clip, rt_skeleton_set_time, rt_skeleton_set_blend):
 // validation of the caller's arrays, the level table k_skeleton_pose walks, the segment search of a clip, the check of a layer list and the
 // text of its refusals (a skeleton's and a crowd's alike: tests/cpp/layer_refusals_sanitized.cpp holds it to what both used to say), the
-// record a validated layer is packed into (shared with rt_crowd.h) and the check of a list of IK constraints (rt_skeleton_solve_ik).  Host code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp,
-// tests/cpp/skeleton_blend_sanitized.cpp and tests/cpp/ik_sanitized.cpp compile it alone.
+// record a validated layer is packed into (shared with rt_crowd.h), the check of a list of IK constraints (rt_skeleton_solve_ik,
+// rt_crowd_set_ik_chains), the text of its refusals and the table a checked list is packed into, which both IK kernels take by value.  Host
+// code without HIP, as rt_skin.h is: tests/cpp/skeleton_sanitized.cpp, tests/cpp/skeleton_blend_sanitized.cpp, tests/cpp/ik_sanitized.cpp
+// and tests/cpp/crowd_ik_sanitized.cpp compile it alone.
 #pragma once
 
 #include <math.h>
@@ -265,4 +267,66 @@ static inline int rt_skeleton_validate_ik(uint32_t n, const rt_skeleton_ik *cons
                     return 7;
                 }
     return posed ? 0 : 8;
+}
+
+// The refusal behind a code 1 .. 8 of rt_skeleton_validate_ik, in the ONE text that rt_skeleton_solve_ik and rt_crowd_set_ik_chains answer
+// with: written into out[size] under the name `who` of the call that asked.  `bad` is what the check filled in, `constraints` the list it
+// read (entry bad[0] is read for 3 only).  `noun` and `hint` are the pose source's own (rt_pose_source, rt_internal.h; 8 only).  Returns the
+// error class: RT_ERR_INVALID_ARG for 1 .. 7, RT_ERR_STATE for 8.
+static inline int rt_skeleton_ik_refusal(int what, const char *who, uint32_t n, const rt_skeleton_ik *constraints, const uint32_t bad[3], uint32_t n_joints,
+                                         const char *noun, const char *hint, char *out, size_t size)
+{
+    switch (what) {
+    case 1: snprintf(out, size, "%s: null argument", who); break;
+    case 2: snprintf(out, size, "%s: %u constraints: 1 .. %u are supported", who, n, RT_SKELETON_MAX_IK); break;
+    case 3: snprintf(out, size, "%s: constraint %u has kind %u: RT_IK_TWO_BONE (0) or RT_IK_AIM (1)", who, bad[0], constraints[bad[0]].kind); break;
+    case 4: snprintf(out, size, "%s: constraint %u names joint %u: the skeleton has %u", who, bad[0], bad[2], n_joints); break;
+    case 5:
+        snprintf(out, size, "%s: constraint %u names joint %u for the tip of a two-bone chain: it has fewer than two ancestors (the tip's parent is the middle joint, that joint's parent the chain's root)",
+                 who, bad[0], bad[2]);
+        break;
+    case 6: snprintf(out, size, "%s: the weight of constraint %u is NaN", who, bad[0]); break;
+    case 7:
+        snprintf(out, size, "%s: constraints %u and %u are not independent: constraint %u writes joint %u, which constraint %u reads (its joint or an ancestor of it); solve them in two calls",
+                 who, bad[0], bad[1], bad[0], bad[2], bad[1]);
+        break;
+    default: snprintf(out, size, "%s: the %s has no pose yet (%s)", who, noun, hint); break;
+    }
+    return what <= 7 ? RT_ERR_INVALID_ARG : RT_ERR_STATE;
+}
+
+// A constraint of a solve as the kernels read it -- the host has found the chain: tip c, middle b, root a of a two-bone reach (an aim: c is
+// its joint; b and a repeat it) and the parent p of the joint whose space the target is carried into, -1 for a root of the skeleton -- and
+// the table of them that travels by value as the kernel's argument, as k_skeleton_blend's table of layers does.  k_skeleton_ik reads all of
+// an entry; k_crowd_ik reads the chain, and target, pole and weight from the actor's own values (pole and weight here are the defaults of
+// rt_crowd_set_ik_chains, for a call that brings none).
+struct IkEntry {
+    uint32_t kind, c, b, a;
+    int32_t p;
+    float target[3], pole[3], weight;
+};
+struct IkTable {
+    IkEntry e[RT_SKELETON_MAX_IK];
+};
+
+// The table of a list that rt_skeleton_validate_ik passed (codes 0 and 8: the pose is not its business), over the parents the check read:
+// entries 0 .. n - 1; the rest of `table` is left as it is.
+static inline void rt_skeleton_pack_ik(uint32_t n, const rt_skeleton_ik *constraints, const int32_t *parents, IkTable &table)
+{
+    for (uint32_t k = 0; k < n; k++) {
+        const rt_skeleton_ik &c = constraints[k];
+        IkEntry &e = table.e[k];
+        e.kind = c.kind;
+        e.c = e.b = e.a = c.joint;
+        if (c.kind == RT_IK_TWO_BONE) {
+            e.b = (uint32_t)parents[c.joint];
+            e.a = (uint32_t)parents[e.b];
+        }
+        e.p = parents[e.a];
+        for (int i = 0; i < 3; i++) {
+            e.target[i] = c.target[i];
+            e.pole[i] = c.pole[i];
+        }
+        e.weight = c.weight;
+    }
 }

@@ -74,18 +74,6 @@ __global__ void __launch_bounds__(256) k_skeleton_blend(const BlendTable table, 
     store_pose(pose, j, P);
 }
 
-// A constraint of a solve as the kernel reads it -- the host has found the chain: tip c, middle b, root a of a two-bone reach (an aim: c is
-// its joint; b and a repeat it) and the parent p of the joint whose space the target is carried into, -1 for a root of the skeleton -- and
-// the table of them that travels by value as the kernel's argument, as BlendTable does.
-struct IkEntry {
-    uint32_t kind, c, b, a;
-    int32_t p;
-    float target[3], pole[3], weight;
-};
-struct IkTable {
-    IkEntry e[RT_SKELETON_MAX_IK];
-};
-
 // One block of one wave: lane k < n solves constraint k (include/dxr_amd.h "Posed skeletons", inverse kinematics; the arithmetic is
 // rt_ik_solve, rt_ik.h).  The lane reads its own entry where the table lies, in the kernel-argument segment: three 16-byte vector loads at
 // 48 * lane, one latency for the wave -- the by-value argument is never copied to scratch (tools/kernel_resources.py: 0 B; a uniform loop
@@ -107,23 +95,7 @@ __global__ void __launch_bounds__(64) k_skeleton_ik(const IkTable table, uint32_
         pole[c] = e.pole[c];
     }
     const float weight = e.weight;
-    float tip[10], mid[10], root[10], W[12], qa[4], qb[4];
-#pragma unroll
-    for (int c = 0; c < 10; c++) {
-        tip[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)jc + c];
-        mid[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)jb + c];
-        root[c] = pose[RT_SKELETON_POSE_FLOATS * (size_t)ja + c];
-    }
-    const bool has_parent = jp >= 0;
-#pragma unroll
-    for (int c = 0; c < 12; c++) W[c] = has_parent ? joints[12u * (size_t)(has_parent ? jp : 0) + c] : 0.0f;
-    rt_ik_solve(kind, tip, mid, root, has_parent ? W : nullptr, target, pole, weight, qa, qb);
-#pragma unroll
-    for (int c = 0; c < 4; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)ja + 3 + c] = qa[c];
-    if (kind == RT_IK_TWO_BONE) {
-#pragma unroll
-        for (int c = 0; c < 4; c++) pose[RT_SKELETON_POSE_FLOATS * (size_t)jb + 3 + c] = qb[c];
-    }
+    ik_solve_lane(kind, jc, jb, ja, jp, target, pole, weight, joints, pose);
 }
 
 // sk->pose holds a local pose: W and the palette from it, queued on the context's stream
@@ -156,6 +128,14 @@ int rt_pose_refuse_layers(const rt_pose_source *src, const char *who, int what, 
 {
     char msg[512];
     const int rc = rt_skeleton_layers_refusal(what, who, actor, bad, l, n_layers, n_clips, n_masks, src->noun(), src->pose_hint(), msg, sizeof msg);
+    rt_set_error("%s", msg);
+    return rc;
+}
+
+int rt_pose_refuse_ik(const rt_pose_source *src, const char *who, int what, uint32_t n, const rt_skeleton_ik *constraints, const uint32_t bad[3])
+{
+    char msg[512];
+    const int rc = rt_skeleton_ik_refusal(what, who, n, constraints, bad, src->n_joints, src->noun(), src->pose_hint(), msg, sizeof msg);
     rt_set_error("%s", msg);
     return rc;
 }
@@ -394,44 +374,10 @@ int rt_skeleton_solve_ik(rt_skeleton *sk, uint32_t n, const rt_skeleton_ik *cons
     RT_REQUIRE(sk && constraints, "null argument");
     const int32_t *parents = sk->parents.data();
     uint32_t bad[3] = {0, 0, 0};
-    switch (rt_skeleton_validate_ik(n, constraints, sk->n_joints, parents, sk->posed, bad)) {
-    case 0: break;
-    case 1: rt_set_error("rt_skeleton_solve_ik: null argument"); return RT_ERR_INVALID_ARG;
-    case 2: rt_set_error("rt_skeleton_solve_ik: %u constraints: 1 .. %u are supported", n, RT_SKELETON_MAX_IK); return RT_ERR_INVALID_ARG;
-    case 3:
-        rt_set_error("rt_skeleton_solve_ik: constraint %u has kind %u: RT_IK_TWO_BONE (0) or RT_IK_AIM (1)", bad[0], constraints[bad[0]].kind);
-        return RT_ERR_INVALID_ARG;
-    case 4: rt_set_error("rt_skeleton_solve_ik: constraint %u names joint %u: the skeleton has %u", bad[0], bad[2], sk->n_joints); return RT_ERR_INVALID_ARG;
-    case 5:
-        rt_set_error("rt_skeleton_solve_ik: constraint %u names joint %u for the tip of a two-bone chain: it has fewer than two ancestors (the tip's parent is the middle joint, that joint's parent the chain's root)",
-                     bad[0], bad[2]);
-        return RT_ERR_INVALID_ARG;
-    case 6: rt_set_error("rt_skeleton_solve_ik: the weight of constraint %u is NaN", bad[0]); return RT_ERR_INVALID_ARG;
-    case 7:
-        rt_set_error("rt_skeleton_solve_ik: constraints %u and %u are not independent: constraint %u writes joint %u, which constraint %u reads (its joint or an ancestor of it); solve them in two calls",
-                     bad[0], bad[1], bad[0], bad[2], bad[1]);
-        return RT_ERR_INVALID_ARG;
-    default:
-        rt_set_error("rt_skeleton_solve_ik: the %s has no pose yet (%s)", sk->noun(), sk->pose_hint());
-        return RT_ERR_STATE;
-    }
+    const int what = rt_skeleton_validate_ik(n, constraints, sk->n_joints, parents, sk->posed, bad);
+    if (what) return rt_pose_refuse_ik(sk, "rt_skeleton_solve_ik", what, n, constraints, bad);
     IkTable table = {};
-    for (uint32_t k = 0; k < n; k++) {
-        const rt_skeleton_ik &c = constraints[k];
-        IkEntry &e = table.e[k];
-        e.kind = c.kind;
-        e.c = e.b = e.a = c.joint;
-        if (c.kind == RT_IK_TWO_BONE) {
-            e.b = (uint32_t)parents[c.joint];
-            e.a = (uint32_t)parents[e.b];
-        }
-        e.p = parents[e.a];
-        for (int i = 0; i < 3; i++) {
-            e.target[i] = c.target[i];
-            e.pole[i] = c.pole[i];
-        }
-        e.weight = c.weight;
-    }
+    rt_skeleton_pack_ik(n, constraints, parents, table);
     RT_TRY(rt_use_device(sk->ctx));
     k_skeleton_ik<<<1, 64, 0, sk->ctx->stream>>>(table, n, sk->joints.as<float>(), sk->pose.as<float>());
     HIP_TRY(hipGetLastError());

@@ -170,7 +170,9 @@ namespace DXRFramework
     // clip and a time per actor; setBlend: numLayers layers per actor, actor major.  A skinned model takes one actor's palette with
     // setBones(crowd, actor); instances follow actors' joints with RtScene::attach(..., crowd, actors, joints): a frame is one setTimes and
     // one RtScene::update, whatever the number of actors.  setLayout + setBlendDevice: the clips, masks and modes of every actor's layers are
-    // checked and uploaded once, and a frame's times and weights are read from DEVICE memory -- one launch, nothing uploaded.
+    // checked and uploaded once, and a frame's times and weights are read from DEVICE memory -- one launch, nothing uploaded.  setIKChains +
+    // solveIK / solveIKDevice: one list of reach and aim chains for every actor, checked once, and every actor's own targets, poles and
+    // weights per frame -- one launch that solves and poses all actors.
     class RtCrowd
     {
     public:
@@ -199,6 +201,23 @@ namespace DXRFramework
         // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): every actor posed from the layout and numActors x
         // numLayers times (and weights; nullptr: the layout's) in DEVICE memory, written on the context's stream: one launch (rt_crowd_set_blend_device)
         void setBlendDevice(const float *times, const float *weights = nullptr) { ThrowIfFailed(rt_crowd_set_blend_device(mHandle, times, weights)); }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): the chains -- kind and joint of 1 .. RT_SKELETON_MAX_IK
+        // constraints, the one list every actor solves, with a default pole and weight each; the targets are not read -- checked once (rt_crowd_set_ik_chains)
+        void setIKChains(const rt_skeleton_ik *chains, uint32_t count) { ThrowIfFailed(rt_crowd_set_ik_chains(mHandle, count, chains)); }
+        uint32_t getIKChains() const { uint32_t n = 0; ThrowIfFailed(rt_crowd_get_ik_chains(mHandle, &n)); return n; }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): every actor solves the chains against the pose it holds,
+        // with numActors x count x 3 targets (and poles, and numActors x count weights; nullptr: the chains' own) from host arrays, and is posed
+        // with the result: one upload, one launch (rt_crowd_solve_ik, RT_MEM_HOST)
+        void solveIK(const float *targets, const float *poles = nullptr, const float *weights = nullptr)
+        {
+            ThrowIfFailed(rt_crowd_solve_ik(mHandle, targets, poles, weights, RT_MEM_HOST));
+        }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): ... with the values in DEVICE memory, written on the
+        // context's stream: one launch, nothing uploaded (rt_crowd_solve_ik, RT_MEM_DEVICE)
+        void solveIKDevice(const float *targets, const float *poles = nullptr, const float *weights = nullptr)
+        {
+            ThrowIfFailed(rt_crowd_solve_ik(mHandle, targets, poles, weights, RT_MEM_DEVICE));
+        }
 
     private:
         RtCrowd(RtSkeleton::SharedPtr sk, rt_crowd *h) : mSkeleton(sk), mHandle(h) {}

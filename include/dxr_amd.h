@@ -411,8 +411,19 @@ int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */
  *           floats, rt_crowd_set_times rt_skeleton_set_time(clips[a], times[a]), rt_crowd_set_blend rt_skeleton_set_blend with actor a's
  *           n_layers layers, by the definitions above and by the same statements (the segment (i, a) of every sampled layer found on the
  *           host); RT_SKELETON_CURRENT_POSE on layer 0 is that actor's own held pose.  Every posing call poses ALL actors with one kernel
- *           launch and counts one pose for the whole crowd.  No per-actor IK, no posing of a sub-range of actors, no rigs above 1024
- *           joints.  Times and weights may be read from device memory (rt_crowd_set_blend_device); the LAYOUT -- which clip, which mask
+ *           launch and counts one pose for the whole crowd.  No per-actor IK chains: every actor solves the crowd's one list
+ *           (rt_crowd_set_ik_chains) with its own targets, poles and weights (rt_crowd_solve_ik); no posing of a sub-range of actors, no
+ *           rigs above 1024 joints.  A CHAIN is the kind and the joint of an rt_skeleton_ik: those become addresses, so the host checks
+ *           the list once, against the hierarchy that never changes; an actor's VALUES -- a target, a pole and a weight per chain -- are
+ *           plain floats that are taken as given, from host or device memory.  Actor a after rt_crowd_solve_ik is, bit for bit, a
+ *           skeleton that holds actor a's pose and is given rt_skeleton_solve_ik with the constraints (kind_k, joint_k,
+ *           target[a * n + k], pole[a * n + k], weight[a * n + k]): pose, joints and palette, by the definition above ("inverse
+ *           kinematics") and by the same statements, for every weight that is not NaN.  A constraint reads W of its chain root's parent
+ *           from the pose the actor holds when the call is made -- the actor's joints as the last posing call left them --, as
+ *           rt_skeleton_solve_ik does.  The host refuses a NaN weight it sees; a NaN weight in DEVICE memory is no error, and follows
+ *           WEIGHT above literally: q_c = A_c + (NaN * (A'_c - A_c)) is NaN in all four components, so the sum of squares is NaN, the
+ *           normalisation rule has no answer and every quaternion that constraint writes is (0, 0, 0, 1) -- both joints of a two-bone
+ *           chain, the joint of an aim.  Times and weights may be read from device memory (rt_crowd_set_blend_device); the LAYOUT -- which clip, which mask
  *           and which mode every layer of every actor has -- is the host's (rt_crowd_set_layout): those three are indices that become
  *           addresses, so the host checks them once, while a time and a weight are plain floats that are taken as given.  Actor a of
  *           rt_crowd_set_blend_device is, bit for bit, rt_crowd_set_blend with the layout's layers and time = times[a * n_layers + k],
@@ -575,6 +586,37 @@ int rt_crowd_get_palette_device_ptr(rt_crowd *c, void **ptr);
  * rt_model_set_bones(m, palette + actor * n_joints * 12, RT_MEM_DEVICE).  The refusals are those of rt_model_set_bones_from_skeleton, with
  * the crowd in the skeleton's place; an actor >= n_actors is RT_ERR_INVALID_ARG (the message gives both numbers). */
 int rt_model_set_bones_from_crowd(rt_model *m, rt_crowd *c, uint32_t actor);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the CHAINS of the crowd ("crowds" above): the one list of
+ * 1 .. RT_SKELETON_MAX_IK (32) constraints that every actor solves.  Reads `kind` and `joint` of every entry and keeps its `pole` and
+ * `weight` as the defaults of rt_crowd_solve_ik calls that bring no poles or no weights; the `target` of an entry is not read.  The list is
+ * held to the rules of rt_skeleton_solve_ik unchanged -- the same codes in the same order, the messages those of rt_skeleton_solve_ik under
+ * this call's name, the NaN weight being an entry's default weight -- except that it needs no pose: kind, joint, two ancestors under a
+ * two-bone tip and independence are matters of the hierarchy, which never changes.  The checked list travels to every solve by value, as a
+ * kernel argument: the call poses nothing, counts no pose, touches no device memory and does not wait.  The list stays until the next
+ * rt_crowd_set_ik_chains; no other crowd call uses it or disturbs it.  A null argument is RT_ERR_INVALID_ARG.  Nothing changes when the
+ * call refuses: the crowd keeps the list it had. */
+int rt_crowd_set_ik_chains(rt_crowd *c, uint32_t n, const rt_skeleton_ik *chains /* n, host */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the chains the crowd holds; 0: it has none.  A null argument is
+ * RT_ERR_INVALID_ARG. */
+int rt_crowd_get_ik_chains(const rt_crowd *c, uint32_t *n /* 0: none */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): every actor solves the crowd's chains against the pose it holds
+ * and is posed with the result ("crowds" above): constraint k of actor a has target targets[(a * n + k) * 3 ..], pole poles[(a * n + k) * 3 ..]
+ * and weight weights[a * n + k]; a NULL `poles` or `weights` takes every chain's default.  A frame of a reaching crowd is
+ * rt_crowd_set_blend_device, rt_crowd_solve_ik, rt_scene_update.  It counts one pose for the whole crowd.  Refused, in this order: a null c
+ * or targets and an unknown `mem` (RT_ERR_INVALID_ARG), a crowd without chains (RT_ERR_STATE; the message names rt_crowd_set_ik_chains), a
+ * crowd without a pose (RT_ERR_STATE; the message names rt_crowd_set_poses).
+ * RT_MEM_DEVICE: exactly ONE kernel launch on the context's stream: no upload, no host loop over the actors, no wait.  The values are taken
+ * as given, as rt_crowd_set_blend_device takes its times: NaN, -inf, +inf and any weight are no error ("crowds" above says what a NaN weight
+ * does).  A value never becomes an address -- the joints are those of the host-checked chains -- so the call is memory-safe for any 32 bits
+ * in the three arrays.  The caller orders its writes of the arrays before the call on the context's stream; they are the caller's again once
+ * the stream has passed the launch.
+ * RT_MEM_HOST: the host sees the weights, and a NaN weight is RT_ERR_INVALID_ARG (the message names the actor and the constraint; the first
+ * bad actor wins); targets and poles are taken as given, as on a skeleton.  The arrays the call brings cross to the device in ONE upload, one
+ * behind another, through the two page-locked staging slots of rt_crowd_set_blend and under their event rule, into a buffer the crowd owns;
+ * the same launch follows, and the call does not wait: back-to-back calls are safe.  A device buffer that cannot grow is RT_ERR_OOM.
+ * Nothing changes when the call refuses. */
+int rt_crowd_solve_ik(rt_crowd *c, const float *targets /* n_actors x n x 3 */, const float *poles /* n_actors x n x 3, or NULL */,
+                      const float *weights /* n_actors x n, or NULL */, uint32_t mem /* RT_MEM_HOST | RT_MEM_DEVICE */);
 
 /* Attached instances -- EXTENSIONS: instance transforms that come from the device.  The reference's only statement of a transform is addModel
  * (RtScene.h:30); what these calls write is the Transform member of the instance descriptor
