@@ -12,12 +12,12 @@ LIB = $(LIBDIR)/$(LIBNAME)
 HIPFLAGS = -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-math \
            -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -fno-slp-vectorize \
            -Wall -Wno-unused-function -Iinclude $(EXTRA)
-SRCS = $(CSRC)/rt_api.hip $(CSRC)/rt_scene.hip $(CSRC)/rt_model.hip $(CSRC)/rt_skeleton.hip $(CSRC)/rt_crowd.hip $(CSRC)/rt_crowd_ik.hip $(CSRC)/rt_bvh_build.hip $(CSRC)/rt_bvh_ploc.hip $(CSRC)/rt_bvh_wide.hip $(CSRC)/rt_trace.hip $(CSRC)/rt_pipeline.hip $(CSRC)/rt_pipeline_entries.hip $(CSRC)/rt_pipeline_render.hip $(CSRC)/rt_pipeline_inspect.hip $(CSRC)/rt_pipeline_host.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_dist.hip \
+SRCS = $(CSRC)/rt_api.hip $(CSRC)/rt_scene.hip $(CSRC)/rt_model.hip $(CSRC)/rt_skeleton.hip $(CSRC)/rt_crowd.hip $(CSRC)/rt_crowd_ik.hip $(CSRC)/rt_ik_groups.hip $(CSRC)/rt_bvh_build.hip $(CSRC)/rt_bvh_ploc.hip $(CSRC)/rt_bvh_wide.hip $(CSRC)/rt_trace.hip $(CSRC)/rt_pipeline.hip $(CSRC)/rt_pipeline_entries.hip $(CSRC)/rt_pipeline_render.hip $(CSRC)/rt_pipeline_inspect.hip $(CSRC)/rt_pipeline_host.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_dist.hip \
        $(CSRC)/rt_obj.cpp $(CSRC)/rt_fbx.cpp $(CSRC)/rt_host.cpp $(CSRC)/rt_dds.cpp $(CSRC)/rt_image.cpp
 HDRS = $(wildcard $(CSRC)/*.h) include/dxr_amd.h include/dxr_amd_types.h
 OBJS = $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 
-BIN = $(LIBDIR)/progressive $(LIBDIR)/realtime_denoise $(LIBDIR)/realtime_animated $(LIBDIR)/realtime_deform $(LIBDIR)/realtime_skinned $(LIBDIR)/realtime_morph $(LIBDIR)/realtime_character $(LIBDIR)/realtime_blend $(LIBDIR)/realtime_reach $(LIBDIR)/realtime_machines $(LIBDIR)/realtime_crowd $(LIBDIR)/realtime_crowd_device $(LIBDIR)/realtime_crowd_reach $(LIBDIR)/realtime_visibility $(LIBDIR)/test_wrapper $(LIBDIR)/progressive_multi
+BIN = $(LIBDIR)/progressive $(LIBDIR)/realtime_denoise $(LIBDIR)/realtime_animated $(LIBDIR)/realtime_deform $(LIBDIR)/realtime_skinned $(LIBDIR)/realtime_morph $(LIBDIR)/realtime_character $(LIBDIR)/realtime_blend $(LIBDIR)/realtime_reach $(LIBDIR)/realtime_machines $(LIBDIR)/realtime_crowd $(LIBDIR)/realtime_crowd_device $(LIBDIR)/realtime_crowd_reach $(LIBDIR)/realtime_crowd_grasp $(LIBDIR)/realtime_visibility $(LIBDIR)/test_wrapper $(LIBDIR)/progressive_multi
 CXX ?= g++
 HOSTFLAGS = -O2 -std=c++17 -Wall -Iinclude -Idxrexperiments_amd/include
 HOSTLINK = -L$(LIBDIR) -ldxrexperiments_amd -L/opt/rocm/lib -Wl,-rpath,'$$ORIGIN' -Wl,-rpath-link,/opt/rocm/lib
@@ -67,6 +67,9 @@ $(LIBDIR)/realtime_crowd_device: examples/realtime_crowd_device.cpp $(LIB) $(wil
 	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
 
 $(LIBDIR)/realtime_crowd_reach: examples/realtime_crowd_reach.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)
+	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
+
+$(LIBDIR)/realtime_crowd_grasp: examples/realtime_crowd_grasp.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)
 	$(CXX) $(HOSTFLAGS) $< -o $@ $(HOSTLINK)
 
 $(LIBDIR)/realtime_visibility: examples/realtime_visibility.cpp $(LIB) $(wildcard dxrexperiments_amd/include/*.h)

@@ -98,6 +98,7 @@ SIGNATURES = {
     "rt_skeleton_get_num_masks": (_i, [_p, _pu]),
     "rt_skeleton_set_blend": (_i, [_p, _u32, _p]),
     "rt_skeleton_solve_ik": (_i, [_p, _u32, _p]),
+    "rt_skeleton_solve_ik_groups": (_i, [_p, _u32, _p, _p]),
     "rt_skeleton_read_pose": (_i, [_p, _p]),
     "rt_skeleton_read_joints": (_i, [_p, _p]),
     "rt_skeleton_read_palette": (_i, [_p, _p]),
@@ -121,6 +122,8 @@ SIGNATURES = {
     "rt_model_set_bones_from_crowd": (_i, [_p, _p, _u32]),
     "rt_crowd_set_ik_chains": (_i, [_p, _u32, _p]),
     "rt_crowd_get_ik_chains": (_i, [_p, _pu]),
+    "rt_crowd_set_ik_chain_groups": (_i, [_p, _u32, _p, _p]),
+    "rt_crowd_get_ik_chain_groups": (_i, [_p, _pu, _pu]),
     "rt_crowd_solve_ik": (_i, [_p, _p, _p, _p, _u32]),
     "rt_scene_attach_instances_crowd": (_i, [_p, _u32, _u32, _p, _p, _p, _p]),
     "rt_scene_get_instance_crowd_attachment": (_i, [_p, _u32, _pp, _pu, _pu]),
@@ -667,6 +670,21 @@ class Skeleton:
         a = np.ascontiguousarray(a)
         _check(lib().rt_skeleton_solve_ik(self.h, a.shape[0], _ptr(a)))
 
+    @staticmethod
+    def constraint_groups(groups):
+        """(uint32[n_groups] sizes, rtypes.SKELETON_IK[sum of the sizes]) from an ordered list of groups, each a list as Skeleton.constraints
+        takes it or an array of rtypes.SKELETON_IK"""
+        parts = [np.ascontiguousarray(g) if isinstance(g, np.ndarray) and g.dtype == T.SKELETON_IK else Skeleton.constraints(g) for g in groups]
+        sizes = np.array([len(a) for a in parts], np.uint32)
+        flat = np.concatenate(parts) if parts else np.zeros(0, T.SKELETON_IK)
+        return sizes, np.ascontiguousarray(flat)
+
+    def solve_ik_groups(self, groups):
+        """solves an ordered list of groups of constraints in one call: the constraints of a group are independent, a later group sees the
+        pose the earlier ones left; bit for bit one solve_ik per group, in order (rt_skeleton_solve_ik_groups)"""
+        sizes, a = self.constraint_groups(groups)
+        _check(lib().rt_skeleton_solve_ik_groups(self.h, sizes.shape[0], _ptr(sizes), _ptr(a)))
+
     def _read(self, fn, width):
         out = np.empty((self.n_joints, width), np.float32)
         _check(fn(self.h, _ptr(out)))
@@ -783,6 +801,18 @@ class Crowd:
         a = constraints if isinstance(constraints, np.ndarray) and constraints.dtype == T.SKELETON_IK else Skeleton.constraints(constraints)
         a = np.ascontiguousarray(a)
         _check(lib().rt_crowd_set_ik_chains(self.h, a.shape[0], _ptr(a)))
+
+    def set_ik_chain_groups(self, groups):
+        """the crowd's chains as an ordered list of groups, checked once: what Skeleton.solve_ik_groups takes.  solve_ik and
+        solve_ik_device then solve all groups of all actors in one launch, their arrays running over the whole list"""
+        sizes, a = Skeleton.constraint_groups(groups)
+        _check(lib().rt_crowd_set_ik_chain_groups(self.h, sizes.shape[0], _ptr(sizes), _ptr(a)))
+
+    def ik_chain_groups(self):
+        """the sizes of the groups of the list the crowd holds; []: none"""
+        n, sizes = C.c_uint32(), np.zeros(8, np.uint32)
+        _check(lib().rt_crowd_get_ik_chain_groups(self.h, C.byref(n), sizes.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return [int(x) for x in sizes[:n.value]]
 
     def ik_chains(self):
         """the chains the crowd holds; 0: none"""

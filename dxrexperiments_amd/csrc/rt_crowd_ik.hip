@@ -84,9 +84,11 @@ void launch_ik(rt_crowd *c, const CrowdIkValues &values)
         c->pose.as<float>(), c->joints.as<float>(), c->palette.as<float>());
 }
 
-// the values stand in device memory: ONE launch, queued on the context's stream
+// the values stand in device memory: ONE launch, queued on the context's stream -- of k_crowd_ik for a list of one group, of k_ik_groups
+// (rt_ik_groups.hip) for an ordered list of several
 int solve_crowd(rt_crowd *c, const CrowdIkValues &values)
 {
+    if (c->n_ik_groups > 1u) return rt_ik_groups_solve_crowd(c, values.targets, values.poles, values.weights);
     const uint32_t block = rt_crowd_block(c->n_joints);
     if (block == 64u) launch_ik<64>(c, values);
     else if (block == 128u) launch_ik<128>(c, values);
@@ -114,6 +116,8 @@ int rt_crowd_set_ik_chains(rt_crowd *c, uint32_t n, const rt_skeleton_ik *chains
     // by value into the crowd: a launch already queued holds its own copy of the table it was given, in its kernel arguments
     rt_skeleton_pack_ik(n, mine, parents, c->ik_chains);
     c->n_ik_chains = n;
+    c->ik_group_ends = rt_ik_group_ends(1u, &n);          // (a list of one group)
+    c->n_ik_groups = 1u;
     return RT_OK;
 }
 

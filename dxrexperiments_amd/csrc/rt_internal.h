@@ -15,6 +15,7 @@
 
 #include "../../include/dxr_amd.h"
 #include "rt_skeleton.h"                     // RT_SKELETON_POSE_FLOATS: what rt_pose_source holds per joint
+#include "rt_ik_groups.h"                    // the group ends of a crowd's chain list
 
 void rt_set_error(const char *fmt, ...);
 
@@ -459,6 +460,8 @@ struct rt_crowd : rt_pose_source {
     uint64_t layout_clip_gen = 0, layout_mask_gen = 0;   // the skeleton's generations when the layout was packed: it is stale once either has moved
     IkTable ik_chains = {};      // rt_crowd_set_ik_chains: the one list every actor solves, packed (rt_skeleton_pack_ik); it travels by value to k_crowd_ik
     uint32_t n_ik_chains = 0;    // 0: no chains
+    uint64_t ik_group_ends = 0;  // rt_crowd_set_ik_chain_groups: where the ordered groups of that list end (rt_ik_group_ends, rt_ik_groups.h); rt_crowd_set_ik_chains: one group
+    uint32_t n_ik_groups = 0;    // 0: no chains; 1: rt_crowd_solve_ik launches k_crowd_ik; more: k_ik_groups (rt_ik_groups.hip)
     DevBuf ik_values;            // rt_crowd_solve_ik(RT_MEM_HOST): the targets, poles and weights of the call last queued, one behind another (rt_crowd_ik.h)
     ~rt_crowd() override;        // (rt_crowd.hip) the staging, then the skeleton; the caller has selected the device and joined the stream
 };
@@ -565,6 +568,8 @@ int rt_pose_set_bones(rt_model *m, rt_pose_source *src, uint32_t actor, const ch
 int rt_pose_device_ptr(const rt_pose_source *src, const char *who, const DevBuf &which, void **ptr);
 // rt_crowd.hip: the crowd's next staging slot, the host's to write `bytes` into (what every upload of a crowd call goes through: rt_crowd.hip, rt_crowd_ik.hip)
 int crowd_stage(rt_crowd *c, size_t bytes, CrowdStage **out);
+// rt_ik_groups.hip: the ONE launch of k_ik_groups over the grouped list a crowd holds, every actor's values in device memory (what rt_crowd_solve_ik ends in when the list has more than one group)
+int rt_ik_groups_solve_crowd(rt_crowd *c, const float *targets, const float *poles, const float *weights);
 
 // rt_bvh_ploc.hip.  The leaves PLOC clusters, in Morton order.  Empty: the canonical leaves, one per triangle; otherwise the references of a
 // model with split triangles (rt_refs.h): their count, 6 floats and a primitive id per leaf

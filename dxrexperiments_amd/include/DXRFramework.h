@@ -155,8 +155,15 @@ namespace DXRFramework
         void setBlend(const rt_skeleton_layer *layers, uint32_t numLayers) { ThrowIfFailed(rt_skeleton_set_blend(mHandle, numLayers, layers)); }
         // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): 1 .. RT_SKELETON_MAX_IK two-bone reach and aim
         // constraints (rt_skeleton_ik: kind, joint, target, pole, weight) solved on the device against the pose the skeleton holds, and the
-        // skeleton posed with the result; nothing is uploaded.  The constraints of one call are independent; dependent ones take two calls
+        // skeleton posed with the result; nothing is uploaded.  The constraints of one call are independent; dependent ones go into the ordered groups of solveIKGroups
         void solveIK(const rt_skeleton_ik *constraints, uint32_t count) { ThrowIfFailed(rt_skeleton_solve_ik(mHandle, count, constraints)); }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): numGroups (1 .. RT_SKELETON_MAX_IK_GROUPS) ordered
+        // groups of groupSizes[g] constraints over one array: the constraints of a group are independent, a later group sees the pose the
+        // earlier ones left -- reach, then aim the hand -- bit for bit one solveIK per group, in one launch (rt_skeleton_solve_ik_groups)
+        void solveIKGroups(const rt_skeleton_ik *constraints, const uint32_t *groupSizes, uint32_t numGroups)
+        {
+            ThrowIfFailed(rt_skeleton_solve_ik_groups(mHandle, numGroups, groupSizes, constraints));
+        }
 
     private:
         RtSkeleton(RtContext::SharedPtr ctx, rt_skeleton *h) : mContext(ctx), mHandle(h) {}
@@ -205,6 +212,14 @@ namespace DXRFramework
         // constraints, the one list every actor solves, with a default pole and weight each; the targets are not read -- checked once (rt_crowd_set_ik_chains)
         void setIKChains(const rt_skeleton_ik *chains, uint32_t count) { ThrowIfFailed(rt_crowd_set_ik_chains(mHandle, count, chains)); }
         uint32_t getIKChains() const { uint32_t n = 0; ThrowIfFailed(rt_crowd_get_ik_chains(mHandle, &n)); return n; }
+        // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): the chains as numGroups (1 .. RT_SKELETON_MAX_IK_GROUPS)
+        // ordered groups of groupSizes[g] entries: what RtSkeleton::solveIKGroups takes, checked once; solveIK / solveIKDevice then solve all
+        // groups of all actors in one launch, their value arrays running over the whole list (rt_crowd_set_ik_chain_groups)
+        void setIKChainGroups(const rt_skeleton_ik *chains, const uint32_t *groupSizes, uint32_t numGroups)
+        {
+            ThrowIfFailed(rt_crowd_set_ik_chain_groups(mHandle, numGroups, groupSizes, chains));
+        }
+        uint32_t getIKChainGroups(uint32_t *groupSizes = nullptr) const { uint32_t n = 0; ThrowIfFailed(rt_crowd_get_ik_chain_groups(mHandle, &n, groupSizes)); return n; }
         // EXTENSION (RtModel.cpp:26 and Helpers/BottomLevelASGenerator.h:136-176 as above): every actor solves the chains against the pose it holds,
         // with numActors x count x 3 targets (and poles, and numActors x count weights; nullptr: the chains' own) from host arrays, and is posed
         // with the result: one upload, one launch (rt_crowd_solve_ik, RT_MEM_HOST)

@@ -400,6 +400,15 @@ int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */
  *           and no joint written by one constraint may be read by another.  Four limbs of one body pass; an aim on a hand whose arm is
  *           solved in the same call does not: that is two calls, the second seeing the first's pose.  The result is posed exactly as
  *           rt_skeleton_set_pose poses, and the pose is counted once.
+ *           GROUPS (rt_skeleton_solve_ik_groups, rt_crowd_set_ik_chain_groups).  Constraints that depend on one another -- the hand aimed
+ *           at what its arm has just reached for, a foot aimed after its leg is planted -- go into ONE call as an ordered list of
+ *           1 .. RT_SKELETON_MAX_IK_GROUPS (8) groups, given as group_sizes[n_groups] over one array of n = the sum of the sizes
+ *           constraints, n at most RT_SKELETON_MAX_IK (32).  The constraints WITHIN a group are independent by the rule above; ACROSS
+ *           groups anything goes: a later group may read or write what an earlier group wrote.  The call leaves pose, joints and palette
+ *           exactly as n_groups successive rt_skeleton_solve_ik calls would, one per group in order, bit for bit: group g reads the W of
+ *           the pose that group g - 1 left, the whole list is checked before anything is solved, and a list of one group is
+ *           rt_skeleton_solve_ik itself.  Eight groups is a choice: the ends of the groups travel to the kernel by value as eight bytes
+ *           beside the table of constraints.  The pose is counted once.
  *           Geometry: the tip reaches the clamped target exactly, up to rounding, when a and b carry uniform scale; ancestors may be any
  *           invertible affine matrices.  Under non-uniform scale on a or b the answer is still this definition, but the tip's position is
  *           approximate.  Twist about the bones is whatever the input pose had.  No joint limits, no chains longer than two bones, no CCD
@@ -423,7 +432,10 @@ int rt_model_set_morph_weights(rt_model *m, const float *weights /* n_targets */
  *           rt_skeleton_solve_ik does.  The host refuses a NaN weight it sees; a NaN weight in DEVICE memory is no error, and follows
  *           WEIGHT above literally: q_c = A_c + (NaN * (A'_c - A_c)) is NaN in all four components, so the sum of squares is NaN, the
  *           normalisation rule has no answer and every quaternion that constraint writes is (0, 0, 0, 1) -- both joints of a two-bone
- *           chain, the joint of an aim.  Times and weights may be read from device memory (rt_crowd_set_blend_device); the LAYOUT -- which clip, which mask
+ *           chain, the joint of an aim.  The crowd's list may be an ordered list of groups (rt_crowd_set_ik_chain_groups; GROUPS above):
+ *           actor a is then a skeleton that holds the actor's pose and is given rt_skeleton_solve_ik_groups with the same constraints,
+ *           the value arrays running over the whole list, and all groups of all actors are solved in one launch.  A NaN weight in device
+ *           memory does what it does today, and later groups solve against the pose that gives.  Times and weights may be read from device memory (rt_crowd_set_blend_device); the LAYOUT -- which clip, which mask
  *           and which mode every layer of every actor has -- is the host's (rt_crowd_set_layout): those three are indices that become
  *           addresses, so the host checks them once, while a time and a weight are plain floats that are taken as given.  Actor a of
  *           rt_crowd_set_blend_device is, bit for bit, rt_crowd_set_blend with the layout's layers and time = times[a * n_layers + k],
@@ -494,6 +506,20 @@ int rt_skeleton_set_blend(rt_skeleton *sk, uint32_t n_layers, const rt_skeleton_
  * shared joint).  RT_ERR_STATE: the skeleton has no pose yet (the message names rt_skeleton_set_pose).  Every constraint is held to the first
  * group before the state is looked at. */
 int rt_skeleton_solve_ik(rt_skeleton *sk, uint32_t n, const rt_skeleton_ik *constraints /* n, host */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): solves an ordered list of n_groups (1 .. 8) groups of
+ * constraints, group g being constraints[offset_g .. offset_g + group_sizes[g]), by the definition above ("inverse kinematics", GROUPS): the
+ * result is, bit for bit, that of rt_skeleton_solve_ik(sk, group_sizes[g], constraints + offset_g) for g = 0, 1, ... in order.  On a
+ * skeleton of at most 1024 joints it is exactly ONE kernel launch on the context's stream, one block that solves a group, walks the pose and
+ * meets at a barrier before the next group; nothing is uploaded and nothing waits -- the constraints and the ends of the groups travel as
+ * kernel arguments.  A larger skeleton is checked as a whole and then takes the loop of rt_skeleton_solve_ik, two launches per group.
+ * Validation runs on the host before anything is queued, and nothing changes when the call refuses.  Refused, in this order: a null argument;
+ * n_groups outside 1 .. RT_SKELETON_MAX_IK_GROUPS (group_sizes is not read); a group of size 0 (the message names the group); a total
+ * outside 1 .. 32 (no constraint is read); then every constraint of the list held to the rules of rt_skeleton_solve_ik -- kind, joint, two
+ * ancestors under a two-bone tip, NaN weight, the messages those of rt_skeleton_solve_ik under this call's name with list indices --; then,
+ * group by group, two constraints of one group of which one writes a joint the other reads (the message names both list indices, the joint
+ * and the group, and says to put the reader in a later group): all RT_ERR_INVALID_ARG.  RT_ERR_STATE: the skeleton has no pose yet. */
+int rt_skeleton_solve_ik_groups(rt_skeleton *sk, uint32_t n_groups, const uint32_t *group_sizes /* n_groups, host */,
+                                const rt_skeleton_ik *constraints /* sum of the sizes, host */);
 /* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the local pose last set or sampled.  This and the calls below
  * that return what a pose made are RT_ERR_STATE before the first pose (the message names rt_skeleton_set_pose); the reads synchronise. */
 int rt_skeleton_read_pose(rt_skeleton *sk, float *trs /* n_joints x 10 */);
@@ -599,6 +625,21 @@ int rt_crowd_set_ik_chains(rt_crowd *c, uint32_t n, const rt_skeleton_ik *chains
 /* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the chains the crowd holds; 0: it has none.  A null argument is
  * RT_ERR_INVALID_ARG. */
 int rt_crowd_get_ik_chains(const rt_crowd *c, uint32_t *n /* 0: none */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the chains of the crowd as an ordered list of groups ("inverse
+ * kinematics" above, GROUPS): what rt_crowd_set_ik_chains takes, with the list cut into n_groups (1 .. 8) groups of group_sizes[g]
+ * entries.  The refusals are those of rt_skeleton_solve_ik_groups in the same order under this call's name, except that a list needs no
+ * pose.  rt_crowd_solve_ik keeps its signature and solves whatever list the crowd holds: its value arrays run over the whole list,
+ * n_actors x n with n the sum of the sizes, and rt_crowd_get_ik_chains answers that n.  A list of more than one group is exactly ONE launch
+ * per rt_crowd_solve_ik, after the one upload where the values are the host's; a list of one group is rt_crowd_set_ik_chains with the same
+ * list, bit for bit and launch for launch.  rt_crowd_set_ik_chains sets a list of one group.  Nothing changes when the call refuses: the
+ * crowd keeps the list it had. */
+int rt_crowd_set_ik_chain_groups(rt_crowd *c, uint32_t n_groups, const uint32_t *group_sizes /* n_groups, host */,
+                                 const rt_skeleton_ik *chains /* sum of the sizes, host */);
+/* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): the groups of the list the crowd holds; 0: it has none.
+ * `group_sizes` takes the sizes of the *n_groups groups (room for RT_SKELETON_MAX_IK_GROUPS) and may be NULL.  After rt_crowd_set_ik_chains
+ * it says 1 and {n}.  A null c or n_groups is RT_ERR_INVALID_ARG. */
+int rt_crowd_get_ik_chain_groups(const rt_crowd *c, uint32_t *n_groups /* 0: none */,
+                                 uint32_t *group_sizes /* RT_SKELETON_MAX_IK_GROUPS, or NULL */);
 /* EXTENSION (RtModel.cpp:26 and BottomLevelASGenerator.h:136-176 as above): every actor solves the crowd's chains against the pose it holds
  * and is posed with the result ("crowds" above): constraint k of actor a has target targets[(a * n + k) * 3 ..], pole poles[(a * n + k) * 3 ..]
  * and weight weights[a * n + k]; a NULL `poles` or `weights` takes every chain's default.  A frame of a reaching crowd is

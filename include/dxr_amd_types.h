@@ -196,6 +196,10 @@ typedef struct rt_skeleton_layer {
 
 /* One constraint of an inverse-kinematics solve (rt_skeleton_solve_ik; include/dxr_amd.h "Posed skeletons", "inverse kinematics"). */
 #define RT_SKELETON_MAX_IK 32u
+/* ... and the ordered GROUPS such a list may be given in (rt_skeleton_solve_ik_groups, rt_crowd_set_ik_chain_groups): the constraints of a
+ * group are independent, a later group sees what the earlier ones wrote.  Eight is a choice: the ends of the groups travel to the kernel by
+ * value as eight bytes, one 64-bit argument beside the table of constraints. */
+#define RT_SKELETON_MAX_IK_GROUPS 8u
 #define RT_IK_TWO_BONE 0u
 #define RT_IK_AIM      1u
 typedef struct rt_skeleton_ik {
